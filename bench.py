@@ -14,14 +14,16 @@ every step streams its 92 N algorithmic bytes from HBM, as it would inside a rea
 have flushed the caches.  (The cache-hot figure, same frame every step, is reported under "extras".)
 
 All inputs are resident in HBM before the timed region.  Timing: W warm-up steps, barrier + synchronize,
-K steps, synchronize + barrier; the slowest rank's time is used; value = N_gpus * K / t.
+K steps, synchronize + barrier; the slowest rank's time is used; value = N_gpus * K / t, ms_per_step = 1e3 * t / K.
 
-One JSON line on rank 0, with
+A plain run does only that and prints one JSON line on rank 0.  --dump-outputs DIR then also writes, on rank 0, what
+the last timed step computed (write_outputs).  --full adds, as before it became optional:
   roofline      dominant kernel's algorithmic bytes per launch / its mean launch duration (HIP events on the
                 launch stream, taken in a second pass of K steps so the events do not perturb `value`),
                 against the 8 TB/s HBM peak
   cpu_baseline  the CPU oracle (a port of the reference's CavityForceCompute::computeForces, one thread) timed
-                on this box's host cores on the same workload for a bounded number of evaluations
+                on this box's host cores on the same workload for a bounded number of evaluations (one-GPU jobs only)
+  extras        the side measurements (cache-hot, 1e5, 1e7, N = 501, observables, thermostat, ...; one-GPU jobs only)
 """
 import argparse
 import json
@@ -118,9 +120,16 @@ def parse_args():
     ap.add_argument("--n-molecular", type=int, default=1_000_000)
     ap.add_argument("--frames", type=int, default=0, help="trajectory frames in the ring (0 = enough to exceed 2x the Infinity Cache)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="budget for the cpu_baseline leg (split over the -O2 and -O3 builds)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the 1e5 / 1e7 / cache-hot side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the 1e5 / 1e7 / cache-hot side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (a second, event-timed pass), the cpu_baseline and the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Frame:
@@ -171,6 +180,33 @@ def timed(ring, steps, warmup, ctx=None):
     if ctx is not None:
         replicas.barrier(ctx)
     return time.perf_counter() - t0, own    # (the contract's bracket: barrier + synchronize on both sides, this rank's own)
+
+
+DUMP_BYTES_MAX = 64 * 2**20
+
+
+def write_outputs(out_dir, frame):
+    """What a caller of the timed path receives after the last timed step, as float64 .npy files: the (N,4) force array
+    (x, y, z, per-particle energy), the three energies and the result block's dipole, total dipole and photon force.  A
+    force array larger than the budget is written as a fixed, seeded sample of its rows (force_rows.npy: their indices)."""
+    torch.cuda.synchronize()
+    c = frame.compute
+    res = c.getResult()
+    out = {"energies": np.array(c.getEnergies(), dtype=np.float64), "dipole": np.array(res.dipole[:], dtype=np.float64),
+           "total_dipole": np.array(res.total_dipole[:], dtype=np.float64),
+           "photon_force": np.array(res.photon_force[:], dtype=np.float64)}
+    force = c.getForceArray()
+    n = force.shape[0]
+    max_rows = (DUMP_BYTES_MAX - (1 << 20)) // (force.shape[1] * 8 + 8)
+    if n > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max_rows, replace=False))
+        out["force"] = force[torch.from_numpy(rows).to(force.device)].cpu().numpy()
+        out["force_rows"] = rows.astype(np.float64)
+    else:
+        out["force"] = force.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def kernel_times(ring, steps, warmup):
@@ -451,16 +487,9 @@ def main():
     value = ctx.world_size * spec["steps"] / elapsed
     # every rank's own rate (its K steps over its own clock between the two barriers): an imbalanced node shows here
     per_rank = {"min": replicas.min_over_ranks(ctx, spec["steps"] / own), "max": replicas.max_over_ranks(ctx, spec["steps"] / own)}
-
-    kt, launches, samples = kernel_times(ring, spec["steps"], spec["warmup"])
-    roof = roofline_block(n, kt)
-    roof["kernel_time_us_percentiles"] = percentiles(samples)
-    pmc = load_pmc_traffic(n)
-    if pmc is not None:
-        roof["traffic"] = pmc.get(roof["kernel"], {}).get("hbm_bytes_per_launch")
-        roof["traffic_source"] = ("profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                  "workload taken by the builder and committed; NOT measured in this run")
-        roof["traffic_detail"] = pmc
+    if args.dump_outputs and ctx.rank == 0:
+        # the last timed step is step warmup + steps - 1 (timed() runs steps warmup ... warmup + steps - 1)
+        write_outputs(args.dump_outputs, ring[(spec["warmup"] + spec["steps"] - 1) % len(ring)])
 
     line = {
         "metric": "cavity_force_evals_per_sec", "value": value, "unit": "evals/s", "n_gpus": ctx.world_size,
@@ -477,10 +506,21 @@ def main():
                    "dist_backend": ctx.backend, "dist_collective_device": str(ctx.coll_device) if ctx.backend else None},
         "per_rank_evals_per_s": per_rank,
         "achieved_GBps_wall": BYTES_EVAL * n * value / 1e9,
-        "roofline": roof,
     }
 
-    if ctx.rank == 0 and ctx.world_size == 1:
+    if args.full:
+        kt, launches, samples = kernel_times(ring, spec["steps"], spec["warmup"])
+        roof = roofline_block(n, kt)
+        roof["kernel_time_us_percentiles"] = percentiles(samples)
+        pmc = load_pmc_traffic(n)
+        if pmc is not None:
+            roof["traffic"] = pmc.get(roof["kernel"], {}).get("hbm_bytes_per_launch")
+            roof["traffic_source"] = ("profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                      "workload taken by the builder and committed; NOT measured in this run")
+            roof["traffic_detail"] = pmc
+        line["roofline"] = roof
+
+    if args.full and ctx.rank == 0 and ctx.world_size == 1:
         if not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
+import sys
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -219,10 +220,33 @@ def make_params(omegac: float, couplstr: float, phmass: float = 1.0) -> Params:
     return load().cavmd_make_params(float(omegac), float(couplstr), float(phmass))
 
 
+# Workspaces released while a stream capture was under way, destroyed at the next release or creation outside one.  Python
+# may collect a dropped workspace at any allocation, inside a capture too (torch.cuda.graph does not collect before it
+# captures); the frees of cavmd_destroy would invalidate that capture.
+_deferred = []
+
+
+def _capturing() -> bool:
+    """True while the current stream of this thread is being captured into a graph."""
+    torch = sys.modules.get("torch")
+    try:
+        return torch is not None and torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+    except Exception:
+        return False
+
+
+def _destroy_deferred() -> None:
+    while _deferred:
+        lib, h = _deferred.pop()
+        lib.cavmd_destroy(h)
+
+
 class Workspace:
     """Owns one cavmd_workspace (scratch for partial sums + the 192-byte result block)."""
 
     def __init__(self, max_N: int, device: int = -1, hooks: bool = False):
+        if not _capturing():
+            _destroy_deferred()
         self._lib = load_hooks_build() if hooks else load()
         self._h = ctypes.c_void_p()
         check(self._lib.cavmd_create(int(device), int(max_N), ctypes.byref(self._h)), "cavmd_create")
@@ -234,8 +258,13 @@ class Workspace:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cavmd_destroy(self._h)
+            if _capturing():
+                _deferred.append((self._lib, self._h))
+            else:
+                self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
+        if _deferred and not _capturing():
+            _destroy_deferred()
 
     def __del__(self):
         try:

@@ -1060,3 +1060,39 @@ def test_replays_of_a_captured_graph_behind_an_uncompleted_evaluation_fail_as_a_
     with pytest.raises(_capi.CavmdError) as e:
         ws.result()
     assert e.value.status == _capi.CAVMD_ERR_SYNC_TIMEOUT
+
+
+def test_a_workspace_collected_during_a_capture_leaves_the_capture_intact():
+    """Python may collect a dropped workspace at any allocation, inside torch.cuda.graph's capture too (it does not collect
+    before capturing).  Destroying it there would free device memory in the middle of the caller's capture and invalidate
+    it; the binding destroys such a workspace at the next release or creation outside a capture instead."""
+    import gc
+    n = 3_001
+    cfg, pos, chg, img = _device_inputs(n, seed=93, photon_at=5)
+    prm = _capi.make_params(0.0091, 1e-3, 1.0)
+    want = torch.full((n, 4), 7.0, dtype=torch.float64, device="cuda")
+    got = torch.full((n, 4), 7.0, dtype=torch.float64, device="cuda")
+    ws, ws_graph = _capi.Workspace(n), _capi.Workspace(n)
+    ws.compute_hoomd(torch.cuda.current_stream().cuda_stream, n, pos.data_ptr(), chg.data_ptr(), img.data_ptr(), cfg["box"],
+                     2, prm, want.data_ptr())
+    torch.cuda.synchronize()
+    gc.collect()
+    gc.disable()                                                    # the cycle below is collected inside the capture, not before
+    try:
+        cycle = [_capi.Workspace(n)]
+        cycle.append(cycle)
+        del cycle
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            gc.collect()
+            assert len(_capi._deferred) == 1
+            ws_graph.compute_hoomd(torch.cuda.current_stream().cuda_stream, n, pos.data_ptr(), chg.data_ptr(), img.data_ptr(),
+                                   cfg["box"], 2, prm, got.data_ptr())
+    finally:
+        gc.enable()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(got.view(torch.int64), want.view(torch.int64))
+    ws.close()                                                      # outside a capture: the deferred workspace goes too
+    assert not _capi._deferred
+    ws_graph.close()

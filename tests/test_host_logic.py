@@ -141,6 +141,24 @@ def test_bench_self_launch_plumbing_without_a_gpu():
         assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_options_plain_by_default(monkeypatch):
+    """A plain `bench.py --steps K --warmup W` is lean: --full (roofline pass, cpu_baseline, extras) and --dump-outputs
+    are off unless asked for, and --steps must ask for at least one timed step."""
+    import sys
+    root = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "9", "--warmup", "4"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (9, 4, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
 def test_launch_ranks_hands_out_eight_ranks_and_relays_rank0_json_last(tmp_path, capfd):
     """The driver's N = 8 form, `python bench.py --gpus 8`, without a GPU: the parent starts eight processes with
     RANK = LOCAL_RANK = 0..7, WORLD_SIZE = LOCAL_WORLD_SIZE = 8, ONE rendezvous address 127.0.0.1:<port> for all, the dmabuf
@@ -205,3 +223,30 @@ def test_a_launched_job_of_one_rank_joins_a_process_group(tmp_path):
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "JOINED True gloo True" in out.stdout and "VALUES 12 1.5 2.5 3.5" in out.stdout
+
+
+def test_workspace_released_during_a_capture_is_destroyed_after_it(monkeypatch):
+    """Workspace.close() inside a stream capture must not free device memory (that would invalidate the capture): the
+    destruction waits for the next release or creation outside a capture.  A stand-in library records the calls."""
+    import ctypes
+
+    from cavitymd import _capi
+    destroyed = []
+
+    class Lib:
+        def cavmd_destroy(self, h):
+            destroyed.append(h.value)
+
+    def fake(h):
+        ws = object.__new__(_capi.Workspace)
+        ws._lib, ws._h = Lib(), ctypes.c_void_p(h)
+        return ws
+    a, b = fake(0x10), fake(0x20)
+    monkeypatch.setattr(_capi, "_capturing", lambda: True)
+    a.close()
+    assert destroyed == [] and [h.value for _, h in _capi._deferred] == [0x10] and not a._h.value
+    monkeypatch.setattr(_capi, "_capturing", lambda: False)
+    b.close()
+    assert sorted(destroyed) == [0x10, 0x20] and not _capi._deferred
+    b.close()                                                       # idempotent
+    assert len(destroyed) == 2
