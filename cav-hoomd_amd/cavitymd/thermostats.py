@@ -97,7 +97,8 @@ class BussiReservoir:
                    rng=None, stream=None) -> None:
         """The translational step without a host round trip: the kernel that folds the kinetic energy evaluates the rule on
         the device and leaves alpha for the rescale kernel enqueued right behind it; nothing is waited for.  The counters are
-        fetched when a property is read.  (Rotational degrees of freedom are not handled on this path: use ``step``.)"""
+        fetched when a property is read.  (Rotational degrees of freedom are not handled on this path: use ``step``.)
+        Not capturable into a CUDA/HIP graph: raises ``CavmdError`` while the stream is being captured, enqueueing nothing."""
         if not self._attached:
             raise RuntimeError("BussiReservoir.step_async before attach()")
         if velocity.dtype != torch.float64 or velocity.dim() != 2 or velocity.shape[1] != 4 or not velocity.is_contiguous():
@@ -106,9 +107,12 @@ class BussiReservoir:
             rng = rng if rng is not None else np.random.default_rng()
             variates = draw_variates(rng, translational_dof, 0.0)
         mp = self._members.data_ptr() if self._members is not None else None
-        self._dev_stream = self._stream(velocity, stream)
-        self._ws.bussi_step_device(self._dev_stream, velocity.data_ptr(), mp, self._n_members, translational_dof, deltaT,
+        handle = self._stream(velocity, stream)
+        # raises CavmdError(CAVMD_ERR_INVALID_VALUE) while the stream is being captured: the variates are kernel arguments, a
+        # graph replay would apply the same ones again (include/cavmd.h, cavmd_bussi_step_device)
+        self._ws.bussi_step_device(handle, velocity.data_ptr(), mp, self._n_members, translational_dof, deltaT,
                                    self._set_T(timestep), self.tau, variates[0], variates[1])
+        self._dev_stream = handle
         if deltaT != 0.0 and self._n_members:
             self._dev_used = True
             self._last_on_device = True

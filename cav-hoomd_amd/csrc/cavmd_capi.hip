@@ -1263,9 +1263,18 @@ int cavmd_bussi_step_device(cavmd_workspace* ws, void* stream_, cavmd_double4* d
         return CAVMD_ERR_INVALID_VALUE;
     if (n_members > (size_t)INT_MAX)
         return CAVMD_ERR_CAPACITY;
+    hipStream_t stream = (hipStream_t)stream_;
+    // The variates, c, set_T and dof travel by value in BussiStepArgs: a captured step would apply the same R and gamma on
+    // every replay (a thermostat that is no longer stochastic).  Refused before anything is allocated, enqueued or counted.
+    // (The null stream cannot be captured, as in note_capture.)
+    if (stream != nullptr)
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+            return CAVMD_ERR_INVALID_VALUE;
+    }
     if (deltaT == 0.0 || n_members == 0) // src/BussiReservoirThermostat.h:45-48: factors {1, 1}, counters untouched
         return CAVMD_OK;
-    hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(ws->device);
     {
         int st0 = ensure_scalar_scratch(ws);

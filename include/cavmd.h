@@ -273,7 +273,10 @@ CAVMD_API int cavmd_bussi_step(cavmd_bussi_reservoir* state, double K_translatio
  * translational degrees of freedom; rotational ones stay on the host path above (cavmd_bussi_step).  The rule runs the same
  * source function as cavmd_bussi_rescale_factor (c = exp(-dt / tau) is taken on the host): same bits for the same kinetic energy.
  * deltaT == 0 enqueues nothing (factors 1, counters untouched, :45-48).  Degrees of freedom with zero kinetic energy: the step
- * is refused on the device (alpha = 1, nothing rescaled) and the NEXT cavmd_bussi_device_read returns CAVMD_ERR_BAD_PARAMS once. */
+ * is refused on the device (alpha = 1, nothing rescaled) and the NEXT cavmd_bussi_device_read returns CAVMD_ERR_BAD_PARAMS once.
+ * Not capturable: the variates, c, set_T and dof are kernel arguments, so a step captured into a hipGraph would apply the same
+ * random variates on every replay.  While `stream` is being captured the call returns CAVMD_ERR_INVALID_VALUE and enqueues
+ * nothing (the step is not counted; the state stays that of the last uncaptured step). */
 CAVMD_API int cavmd_bussi_step_device(cavmd_workspace* ws, void* stream, cavmd_double4* d_vel, const uint32_t* d_members,
                                       size_t n_members, double dof_translational, double deltaT, double set_T, double tau,
                                       double normal_variate, double gamma_variate);
@@ -288,9 +291,8 @@ typedef struct cavmd_bussi_device_state
 } cavmd_bussi_device_state;
 /* State after the last enqueued cavmd_bussi_step_device: spins on the flag that step publishes into mapped host memory (no
  * copy, no stream synchronisation; it watches the stream that step was enqueued on); before any step: zeros.
- * CAVMD_ERR_BAD_PARAMS (once) if a step was refused since the last call.  Steps captured into a hipGraph replay correctly on
- * the device (alpha and the counters live there); the flag, however, carries the sequence number frozen at capture, so after
- * replays synchronise the stream (or device) before reading. */
+ * CAVMD_ERR_BAD_PARAMS (once) if a step was refused since the last call.  (Steps cannot be captured into a hipGraph: see
+ * cavmd_bussi_step_device.) */
 CAVMD_API int cavmd_bussi_device_read(cavmd_workspace* ws, cavmd_bussi_device_state* out);
 /* reset_reservoir_energy() of the reference's Python class: zero the counters (ordered on `stream`). */
 CAVMD_API int cavmd_bussi_device_reset(cavmd_workspace* ws, void* stream);

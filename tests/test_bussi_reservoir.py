@@ -2,11 +2,15 @@
 
 CPU part (no GPU): the product's scalar rule (host arithmetic inside libcavmd) against the oracle restatement bit for bit,
 closed-form known answers, both branches of the sign rule, the edge cases of the reference (Nf = 0, Nf = 1, tau = 0,
-deltaT = 0, zero momenta) and the reservoir bookkeeping.  GPU part (-m gpu): the group kinetic energy and a 1000-step run.
+deltaT = 0, zero momenta) and the reservoir bookkeeping.  GPU part (-m gpu): the group kinetic energy, a 1000-step run, the
+on-device step against the host step, over launch shapes and member layouts (grid changes of either launch, the tile tail,
+unsorted and sparse member lists, byte offsets above 2^31, one workspace cycled large -> small -> large), and its refusal
+to be captured into a graph.
 
-PARITY UNPINNED by the reference (its own test, src/pytest/test_bussi_reservoir.py, asserts only that the counters start at
-zero, move and reset -- mirrored in test_counters_start_at_zero_move_and_reset).  Variate GENERATION (HOOMD's RandomGenerator)
-is outside this comparison: the variates are inputs here.
+The reference's own test (src/pytest/test_bussi_reservoir.py) asserts only that the counters start at zero, move and reset --
+mirrored in test_counters_start_at_zero_move_and_reset.  The alpha rule, the counters and the variate slot order are pinned
+by EXECUTING the reference's C++ (tests/test_bussi_reference_golden.py).  Variate GENERATION (HOOMD's RandomGenerator) is
+outside this comparison: the variates are inputs here.
 """
 import math
 
@@ -255,3 +259,177 @@ def test_on_device_step_refuses_zero_momenta_and_keeps_the_array():
     # argument validation, as the other entry points
     with pytest.raises(_capi.CavmdError):
         ws.bussi_step_device(0, dvel.data_ptr() + 8, None, n, 3.0, 0.02, 3e-4, 0.5, 0.3, 0.0)
+
+
+# ---- GPU: launch-shape sweep of the on-device step and of the host-path kernels -------------------------------------------
+# The first launch of the on-device step uses one block per CU, the second kScaleBlocksPerCu = 4 per CU, and both sweep tiles
+# of 1024 members: the sizes where those grids change (262 144 and 1 048 576 members on 256 CUs) and the tile tail are where
+# one block could apply a different alpha or skip a tail.  Sizes are visited large -> small -> large on ONE workspace, so
+# that stale partials of a larger grid would show.
+SWEEP_N = [10_000_019, 1, 262_145, 2, 1_048_577, 255, 1_048_576, 1_023, 262_144, 1_024, 1_048_575, 1_025, 262_143]
+GUARD = 1024   # NaN-filled rows past N that nothing may touch
+
+
+def _layouts(n, rng):
+    yield "all", None
+    yield "every_third_reversed", np.arange(0, n, 3, dtype=np.uint32)[::-1].copy()
+    yield "random_subset_permuted", rng.permutation(n)[:max(1, (n * 3) // 5)].astype(np.uint32)
+    yield "last_only", np.array([n - 1], dtype=np.uint32)
+    if n > 1:
+        yield "all_but_last", np.arange(n - 1, dtype=np.uint32)
+
+
+def _gpu_velocities(n, seed):
+    """(n + GUARD, 4) on the device: normal velocities, positive masses, a NaN guard tail."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    v = torch.empty((n + GUARD, 4), dtype=torch.float64, device="cuda")
+    v[:n, :3] = torch.randn((n, 3), generator=g, dtype=torch.float64, device="cuda") * 1e-3
+    v[:n, 3] = torch.rand((n,), generator=g, dtype=torch.float64, device="cuda") * 3e4 + 1.0
+    v[n:] = float("nan")
+    return v
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.view(torch.int64), b.view(torch.int64))
+
+
+def _scaled(old, idx, n, alpha):
+    """old with the xyz of the members (idx: long tensor, or None = the first n rows) multiplied by alpha: IEEE products."""
+    want = old.clone()
+    if idx is None:
+        want[:n, :3] = old[:n, :3] * alpha
+    else:
+        want[idx, :3] = old[idx, :3] * alpha
+    return want
+
+
+def _check_steps(bussi, ws, stream, vel, members, n, steps, seed):
+    """Enqueue the on-device steps back to back (a device-side snapshot after each, no host wait in between), then check
+    every step: K as the host-path kernel computes it on the step's input, within 2 ulp of the exactly rounded sum; alpha by
+    the scalar rule on that K; every member's xyz == old * alpha bit for bit, .w, non-members and the guard untouched; the
+    device's counters == the host-side fold of the same K and alpha, bit for bit."""
+    nm = n if members is None else len(members)
+    dm = None if members is None else torch.from_numpy(members.view(np.int32).copy()).cuda()
+    mp = None if dm is None else dm.data_ptr()
+    idx = None if dm is None else dm.long()
+    dof = 3.0 * nm
+    rng = np.random.default_rng(seed)
+    ws.bussi_device_reset(stream)
+    snaps = [vel.clone()]
+    args = []
+    for k, (dt, tau) in enumerate(steps):
+        r, g = float(rng.standard_normal()), float(rng.gamma((dof - 1) / 2, 1.0)) if dof > 1 else 0.0
+        if tau == 0.0:
+            r = -abs(r) - 0.1                      # instantaneous thermalisation with R < 0: the negative branch
+        ws.bussi_step_device(stream, vel.data_ptr(), mp, nm, dof, dt, 3e-4, tau, r, g)
+        snaps.append(vel.clone())
+        args.append((dof, dt, 3e-4, tau, r, g))
+    torch.cuda.synchronize()
+    st = ws.bussi_device_read()
+    reservoir, K, alpha, neg = 0.0, None, None, 0
+    for k, a in enumerate(args):
+        K = ws.kinetic_energy(stream, snaps[k].data_ptr(), mp, nm)
+        alpha = _capi.bussi_rescale_factor(K, *a)
+        neg += alpha < 0
+        assert _bits_equal(snaps[k + 1], _scaled(snaps[k], idx, n, alpha)), (n, nm, k, alpha)
+        hi, lo = bussi.kinetic_energy(snaps[k][:n].cpu().numpy(), members, exact=True)
+        assert abs(K - hi) <= 2 * np.spacing(abs(hi)), (n, nm, k, K, hi)
+        reservoir += K * (1.0 - alpha * alpha)
+    assert st.last_kinetic_energy == K and st.last_alpha == alpha and st.steps == len(steps) and st.refused == 0
+    assert st.reservoir_translational == reservoir
+    assert neg >= 1
+    # the host path on the same shape: cavmd_kinetic_energy + cavmd_scale_velocities
+    old = vel.clone()
+    ws.scale_velocities(stream, vel.data_ptr(), mp, nm, -0.8125)
+    torch.cuda.synchronize()
+    assert _bits_equal(vel, _scaled(old, idx, n, -0.8125))
+
+
+@pytest.mark.gpu
+def test_on_device_step_over_launch_shapes_and_member_layouts(bussi):
+    ws = _capi.Workspace(max(SWEEP_N))
+    stream = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(2026)
+    steps = [(0.02, 0.5), (0.02, 0.0), (0.01, 2.0)]
+    for n in SWEEP_N:
+        for name, members in _layouts(n, rng):
+            vel = _gpu_velocities(n, seed=n % 100_003 + len(name))
+            _check_steps(bussi, ws, stream, vel, members, n, steps, seed=n)
+            del vel
+    ws.close()
+
+
+@pytest.mark.gpu
+def test_on_device_step_with_byte_offsets_above_2_to_the_31(bussi):
+    """N = 70 000 001: 2.24 GB of velocities, so that the last members sit past 2^31 bytes; all members and a sparse list
+    with N - 1 and indices above 2^26 (byte offsets above 2^31)."""
+    n = 70_000_001
+    ws = _capi.Workspace(n)
+    stream = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(70)
+    sparse = np.concatenate([rng.choice(np.arange(2 ** 26, n - 1), 20_000, replace=False), [n - 1],
+                             rng.choice(2 ** 26, 5_000, replace=False)]).astype(np.uint32)
+    rng.shuffle(sparse)
+    for members in (None, sparse):
+        vel = _gpu_velocities(n, seed=7)
+        _check_steps(bussi, ws, stream, vel, members, n, [(0.02, 0.5), (0.02, 0.0)], seed=11)
+        del vel
+        torch.cuda.empty_cache()
+    ws.close()
+
+
+# ---- GPU: graph capture is refused --------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_on_device_step_refuses_graph_capture():
+    """The variates travel as kernel arguments, so a captured step would apply the same R and gamma on every replay.  Under
+    capture step_async raises CavmdError(CAVMD_ERR_INVALID_VALUE) and enqueues nothing: the capture (with a cheap torch op in
+    it) ends cleanly, replays leave the velocities and the device state as they were, and the next uncaptured step is the host
+    step bit for bit."""
+    n = 50_001
+    vel = _velocities(n, seed=3)
+    a_vel, b_vel = torch.from_numpy(vel.copy()).cuda(), torch.from_numpy(vel.copy()).cuda()
+    host = thermostats.BussiReservoir(kT=3.167e-4, tau=0.5)
+    dev = thermostats.BussiReservoir(kT=3.167e-4, tau=0.5)
+    fresh = thermostats.BussiReservoir(kT=3.167e-4, tau=0.5)    # never stepped: nothing may be allocated under capture
+    for th in (host, dev, fresh):
+        th.attach(n)
+    dof = 3.0 * n - 3.0
+    rng = np.random.default_rng(5)
+    var = thermostats.draw_variates(rng, dof)
+    host.step(0, 0.02, a_vel, dof, variates=var)
+    dev.step_async(0, 0.02, b_vel, dof, variates=var)
+    torch.cuda.synchronize()
+    st0 = dev.device_state()
+    before = (st0.reservoir_translational, st0.instantaneous_translational, st0.last_alpha, st0.last_kinetic_energy, st0.steps)
+    snap = b_vel.clone()
+    y = torch.zeros(4, dtype=torch.float64, device="cuda")
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        y.add_(1.0)
+        with pytest.raises(_capi.CavmdError) as e:
+            dev.step_async(1, 0.02, b_vel, dof, variates=thermostats.draw_variates(rng, dof))
+        assert e.value.status == _capi.CAVMD_ERR_INVALID_VALUE
+        with pytest.raises(_capi.CavmdError) as e2:
+            fresh.step_async(1, 0.02, b_vel, dof, variates=[0.5, 1e5, 0.0, 0.0])
+        assert e2.value.status == _capi.CAVMD_ERR_INVALID_VALUE
+        y.add_(1.0)
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.full_like(y, 6.0))
+    assert _bits_equal(b_vel, snap)
+    st1 = dev.device_state()
+    assert (st1.reservoir_translational, st1.instantaneous_translational, st1.last_alpha, st1.last_kinetic_energy,
+            st1.steps) == before
+    assert fresh.device_state().steps == 0
+    var = thermostats.draw_variates(rng, dof)
+    ke = host.kinetic_energy(a_vel)
+    at, _ = host.step(2, 0.02, a_vel, dof, variates=var)
+    dev.step_async(2, 0.02, b_vel, dof, variates=var)
+    st = dev.device_state()
+    assert st.last_kinetic_energy == ke and st.last_alpha == at and st.steps == 2
+    torch.cuda.synchronize()
+    assert _bits_equal(a_vel, b_vel)
+    assert dev.reservoir_energy_translational == host.reservoir_energy_translational
+    assert dev.instantaneous_reservoir_translational == host.instantaneous_reservoir_translational
+    del g
