@@ -10,11 +10,12 @@ force; standalone (no HOOMD, as in the build/test image) it is imported as ``cav
 from .utils import PhysicalConstants, unwrap_positions
 from .forces import CavityForce
 from .compute import CavityForceComputeHIP
+from .history import EnergyHistory
 from .state import BoxDim, ParticleData, SystemDefinition
 from . import _capi, observables, replicas, synthetic, thermostats
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "CavityForce", "CavityForceComputeHIP", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
     "SystemDefinition", "observables", "replicas", "synthetic", "thermostats",
 ]
 __version__ = "0.1.0"

@@ -26,6 +26,7 @@ CAVMD_ERR_CAPACITY = -3
 CAVMD_ERR_BAD_PARAMS = -4
 CAVMD_ERR_NOT_COMPUTED = -5
 CAVMD_ERR_SYNC_TIMEOUT = -6
+CAVMD_ERR_EXPIRED = -7
 
 
 class CavmdError(RuntimeError):
@@ -72,7 +73,8 @@ class BussiDeviceState(ctypes.Structure):
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
     "cavmd_make_params", "cavmd_create", "cavmd_destroy", "cavmd_compute_hoomd", "cavmd_compute_soa",
-    "cavmd_energies", "cavmd_result_read", "cavmd_result_device_ptr", "cavmd_set_wavevectors", "cavmd_density_field",
+    "cavmd_energies", "cavmd_result_read", "cavmd_result_device_ptr", "cavmd_last_sequence", "cavmd_result_at",
+    "cavmd_energies_at", "cavmd_set_wavevectors", "cavmd_density_field",
     "cavmd_density_field_read", "cavmd_cavity_mode", "cavmd_force_mass_sum", "cavmd_kinetic_energy", "cavmd_scale_velocities",
     "cavmd_bussi_step_device", "cavmd_bussi_device_read", "cavmd_bussi_device_reset",
     "cavmd_bussi_rescale_factor", "cavmd_bussi_step", "cavmd_profile_enable", "cavmd_profile_read", "cavmd_profile_samples",
@@ -148,6 +150,12 @@ def _declare(lib):
         lib.cavmd_result_read.restype = ci
         lib.cavmd_result_device_ptr.argtypes = [vp, P(vp)]
         lib.cavmd_result_device_ptr.restype = ci
+        lib.cavmd_last_sequence.argtypes = [vp, P(ctypes.c_uint64)]
+        lib.cavmd_last_sequence.restype = ci
+        lib.cavmd_result_at.argtypes = [vp, ctypes.c_uint64, P(Result)]
+        lib.cavmd_result_at.restype = ci
+        lib.cavmd_energies_at.argtypes = [vp, ctypes.c_uint64, P(dbl * 3)]
+        lib.cavmd_energies_at.restype = ci
         lib.cavmd_set_wavevectors.argtypes = [vp, sz, vp]
         lib.cavmd_set_wavevectors.restype = ci
         lib.cavmd_density_field.argtypes = [vp, vp, sz, vp, sz]
@@ -303,6 +311,23 @@ class Workspace:
         r = Result()
         check(self._lib.cavmd_result_read(self._h, ctypes.byref(r)), "cavmd_result_read")
         return r
+
+    def last_sequence(self) -> int:
+        """Sequence number of the last evaluation enqueued (0 before any); no wait."""
+        out = ctypes.c_uint64()
+        check(self._lib.cavmd_last_sequence(self._h, ctypes.byref(out)), "cavmd_last_sequence")
+        return int(out.value)
+
+    def result_at(self, sequence: int) -> Result:
+        """Result block of evaluation `sequence`, from its slot of the result ring: waits for that evaluation only."""
+        r = Result()
+        check(self._lib.cavmd_result_at(self._h, int(sequence), ctypes.byref(r)), "cavmd_result_at")
+        return r
+
+    def energies_at(self, sequence: int):
+        out = (ctypes.c_double * 3)()
+        check(self._lib.cavmd_energies_at(self._h, int(sequence), ctypes.byref(out)), "cavmd_energies_at")
+        return float(out[0]), float(out[1]), float(out[2])
 
     def result_device_ptr(self) -> int:
         p = ctypes.c_void_p()

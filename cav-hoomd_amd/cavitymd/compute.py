@@ -6,6 +6,7 @@ Same constructor and method names as ``_cavitymd.CavityForceCompute[GPU]``
     CavityForceComputeHIP(sysdef, omegac, couplstr, phmass=1.0)
     .setParams(omegac, couplstr, phmass) / .getParams() -> {omegac, couplstr, K, phmass}
     .getHarmonicEnergy() / .getCouplingEnergy() / .getDipoleSelfEnergy()
+    .lastSequence() / .getEnergiesAt(seq) / .getResultAt(seq)   # an earlier evaluation, no wait for the newest
     .compute(timestep)            # HOOMD: ForceCompute::compute -> computeForces(timestep)
 
 The work itself is one HIP kernel launch (two above ~2.4e6 particles) behind the C ABI
@@ -116,6 +117,18 @@ class CavityForceComputeHIP:
 
     def getResult(self) -> _capi.Result:
         return self._ws.result()
+
+    # -- result history (cavmd_result_at): read an earlier evaluation without waiting for the newest one --------------
+    def lastSequence(self) -> int:
+        """Sequence number of the last evaluation enqueued (0 before any); no wait."""
+        return self._ws.last_sequence()
+
+    def getResultAt(self, sequence: int) -> _capi.Result:
+        return self._ws.result_at(sequence)
+
+    def getEnergiesAt(self, sequence: int):
+        """(harmonic, coupling, dipole_self) of evaluation ``sequence``; waits for that evaluation only."""
+        return self._ws.energies_at(sequence)
 
     def getForceArray(self) -> torch.Tensor:
         """(N,4) float64 device tensor laid out like HOOMD's ``m_force`` (x, y, z, per-particle energy)."""

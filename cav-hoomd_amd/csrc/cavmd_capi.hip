@@ -47,11 +47,22 @@ constexpr int kPersistBlock = 256;
 constexpr size_t kPersistMaxLds = 156 * 1024; // dynamic LDS of the single-launch kernel (charges of a block's tiles); 160 KiB per CU
 constexpr uint64_t kSuspendFirst = 1ull << 16, kSuspendMax = 1ull << 31, kSuspendForever = ~0ull;
 constexpr size_t kPersistSharedLds = 76 * 1024; // default ceiling: two such blocks (+ 1.7 KiB static each) fit on one CU, so two concurrent grids stay resident
+constexpr unsigned kResultHistory = 64;          // default depth of the result ring ("result_history"): 16 KiB pinned
+constexpr unsigned kResultHistoryMax = 16384;
 
 static_assert(sizeof(cavmd_double4) == 32, "Scalar4 layout");
 static_assert(sizeof(cavmd_int3) == 12, "int3 layout");
 static_assert(sizeof(cavmd_params) == 32, "params layout");
 static_assert(sizeof(cavmd_result) == 192, "result layout");
+
+// The fixed part of the workspace's mapped host memory (never reallocated): the starvation flag of the single-launch kernel,
+// and the one block every evaluation publishes into once the workspace has been captured (a replay cannot pick a ring slot).
+struct HostControl
+{
+    HostResult fixed;
+    unsigned sync_error; // kSyncFailed / kSyncRepaired, raised by a starved single-launch evaluation (consume_sync_timeout)
+    unsigned pad[63];
+};
 } // namespace
 
 struct cavmd_workspace
@@ -64,8 +75,12 @@ struct cavmd_workspace
     double* d_part = nullptr;
     int* d_ipart = nullptr;
     cavmd_result* d_result = nullptr;
-    HostResult* h_result = nullptr;     // pinned + mapped: the publishing block writes the result + ready flag here
-    HostResult* h_result_dev = nullptr; // device-side address of h_result
+    HostResult* h_ring = nullptr;       // pinned + mapped: ring_depth result slots; evaluation s publishes into slot s % ring_depth
+    HostResult* h_ring_dev = nullptr;   // device-side address of h_ring
+    unsigned ring_depth = kResultHistory;
+    uint64_t history_first = 1;         // oldest sequence the ring can hold (raised when "result_history" reallocates it)
+    HostControl* h_ctl = nullptr;       // pinned + mapped, fixed: starvation flag + the block of a captured workspace
+    HostControl* h_ctl_dev = nullptr;
     hipStream_t last_stream = nullptr;
     bool computed = false;
     uint64_t sequence = 0;
@@ -105,6 +120,7 @@ struct cavmd_workspace
     bool sync_state_dirty = false;  // a starved evaluation may have left records or counts behind: wipe before the next single launch
     bool sync_timeout_seen = false; // an inter-workgroup wait of the single-launch kernel gave up once: two launches from then on
     bool captured = false; // some evaluation was enqueued into a stream capture: the host-side flag protocol is off
+    uint64_t captured_from = 0; // sequence of the last evaluation before the first captured one (its block stays in the ring)
     // profiling
     bool profiling = false;
     std::vector<hipEvent_t> events; // kEventsPerSlot per slot: start/stop of each of the three kernels
@@ -225,7 +241,10 @@ void note_capture(cavmd_workspace* ws, hipStream_t stream)
         return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    {
         ws->captured = true;
+        ws->captured_from = ws->sequence;
+    }
 }
 
 // Where the single-launch evaluation is the default (measured on MI355X, profiles/r02/microbench_persistent_*.txt).
@@ -453,16 +472,21 @@ int cavmd_create(int device, size_t max_N, cavmd_workspace** out_ws)
     }
     if (e == hipSuccess)
         e = allow_large_lds();
-    if (e == hipSuccess) // coherent: the polled flag must not depend on HIP_HOST_COHERENT
-        e = hipHostMalloc((void**)&ws->h_result, sizeof(HostResult), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) // coherent: the polled flags must not depend on HIP_HOST_COHERENT
+        e = hipHostMalloc((void**)&ws->h_ring, sizeof(HostResult) * ws->ring_depth, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&ws->h_result_dev, ws->h_result, 0);
+        e = hipHostGetDevicePointer((void**)&ws->h_ring_dev, ws->h_ring, 0);
+    if (e == hipSuccess)
+        e = hipHostMalloc((void**)&ws->h_ctl, sizeof(HostControl), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess)
+        e = hipHostGetDevicePointer((void**)&ws->h_ctl_dev, ws->h_ctl, 0);
     if (e != hipSuccess)
     {
         cavmd_destroy(ws);
         return (int)e;
     }
-    memset(ws->h_result, 0, sizeof(HostResult));
+    memset(ws->h_ring, 0, sizeof(HostResult) * ws->ring_depth);
+    memset(ws->h_ctl, 0, sizeof(HostControl));
     *out_ws = ws;
     return CAVMD_OK;
 }
@@ -484,8 +508,10 @@ int cavmd_destroy(cavmd_workspace* ws)
         (void)hipFree(ws->d_granules);
     if (ws->d_epoch)
         (void)hipFree(ws->d_epoch);
-    if (ws->h_result)
-        (void)hipHostFree(ws->h_result);
+    if (ws->h_ring)
+        (void)hipHostFree(ws->h_ring);
+    if (ws->h_ctl)
+        (void)hipHostFree(ws->h_ctl);
     if (ws->d_kvec)
         (void)hipFree(ws->d_kvec);
     if (ws->d_rho_part)
@@ -516,15 +542,34 @@ int cavmd_destroy(cavmd_workspace* ws)
 
 namespace
 {
-// Where the kernels publish the result block for the host: the workspace's mapped block -- or, in the test-hooks build with
-// "debug_skip_publish" set, a scratch block the host never looks at (what a launch that died on the device looks like).
+// Where the kernels of evaluation ws->sequence publish the result block for the host: its slot of the ring in mapped host
+// memory; once the workspace has been captured, the one fixed block (a replayed kernel keeps the address it was captured
+// with, so the ring could not tell replays apart) -- or, in the test-hooks build with "debug_skip_publish" set, a scratch
+// block the host never looks at (what a launch that died on the device looks like).
 inline HostResult* host_block(cavmd_workspace* ws)
 {
 #ifdef CAVMD_TEST_HOOKS
     if (ws->debug_skip_publish && ws->h_scratch_dev)
         return ws->h_scratch_dev;
 #endif
-    return ws->h_result_dev;
+    if (ws->captured)
+        return &ws->h_ctl_dev->fixed;
+    return ws->h_ring_dev + ws->sequence % ws->ring_depth;
+}
+
+// Host address of evaluation s's slot.
+inline HostResult* ring_slot(cavmd_workspace* ws, uint64_t s)
+{
+    return ws->h_ring + s % ws->ring_depth;
+}
+
+// The block the synchronous getters read: the last evaluation's slot; on a captured workspace the fixed block, until the
+// first evaluation after the capture has published there the slot of the last one before it.
+inline HostResult* last_block(cavmd_workspace* ws)
+{
+    if (ws->captured)
+        return __atomic_load_n(&ws->h_ctl->fixed.ready, __ATOMIC_ACQUIRE) ? &ws->h_ctl->fixed : ring_slot(ws, ws->captured_from);
+    return ring_slot(ws, ws->sequence);
 }
 
 // A single-launch evaluation whose blocks were not resident together (other grids held the CUs) either got completed by its
@@ -534,7 +579,7 @@ inline HostResult* host_block(cavmd_workspace* ws)
 // one step, and the two-launch path does not depend on residency.  Returns 0 (nothing happened), kSyncRepaired or kSyncFailed.
 unsigned consume_sync_timeout(cavmd_workspace* ws)
 {
-    if (!ws->h_result || !__atomic_load_n(&ws->h_result->sync_error, __ATOMIC_ACQUIRE))
+    if (!ws->h_ctl || !__atomic_load_n(&ws->h_ctl->sync_error, __ATOMIC_ACQUIRE))
         return 0;
     // kSyncFailed is provisional while the kernel runs (the first block that gives up raises it, the last one may still
     // complete the evaluation): the verdict is the flag once the stream has drained.  A stream that is being captured cannot
@@ -543,8 +588,8 @@ unsigned consume_sync_timeout(cavmd_workspace* ws)
     if (ws->last_stream == nullptr || hipStreamIsCapturing(ws->last_stream, &cap) != hipSuccess
         || cap == hipStreamCaptureStatusNone)
         (void)hipStreamSynchronize(ws->last_stream);
-    const unsigned verdict = __atomic_load_n(&ws->h_result->sync_error, __ATOMIC_ACQUIRE);
-    __atomic_store_n(&ws->h_result->sync_error, 0u, __ATOMIC_RELEASE);
+    const unsigned verdict = __atomic_load_n(&ws->h_ctl->sync_error, __ATOMIC_ACQUIRE);
+    __atomic_store_n(&ws->h_ctl->sync_error, 0u, __ATOMIC_RELEASE);
     ws->sync_timeout_seen = true;
     ws->sync_state_dirty = true;
     if (verdict == kSyncRepaired)
@@ -671,7 +716,8 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
             ws->sequence += 1;
             const AosInputT<2> inx {in.pos2, in.charge, in.image};
             const SyncState sync {ws->d_granules, ws->d_epoch, ws->debug_spin_limit > 0 ? (unsigned)ws->debug_spin_limit : kSpinLimit,
-                                  ws->debug_late_block, (unsigned)ws->debug_late_ticks, ws->debug_silent_block};
+                                  ws->debug_late_block, (unsigned)ws->debug_late_ticks, ws->debug_silent_block,
+                                  &ws->h_ctl_dev->sync_error};
 #define CAVMD_LAUNCH_PERSIST(UNR, NTS)                                                                               \
     st = ls.launch_lds(0, lds, cavity_persistent_kernel<kPersistBlock, UNR, NTS>, g1, kPersistBlock, inx, n, Lx, Ly, Lz, \
                        dp, L_typeid, sync, ws->sequence, ws->d_result, host_block(ws), force2, (unsigned)lds_slots, balanced);
@@ -917,14 +963,15 @@ int cavmd_result_read(cavmd_workspace* ws, cavmd_result* out)
         // about a PCIe write after, instead of a stream synchronisation (~15 us).  The stream going idle ends the wait as
         // well (a failed launch, or a timed-out single-launch kernel, never sets the flag).
         const uint64_t want = ws->sequence;
+        const HostResult* h = ring_slot(ws, want);
         for (;;)
         {
-            if (__atomic_load_n(&ws->h_result->ready, __ATOMIC_ACQUIRE) == want)
+            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want)
                 break;
             const hipError_t q = hipStreamQuery(ws->last_stream);
             if (q == hipSuccess)
             {
-                published = __atomic_load_n(&ws->h_result->ready, __ATOMIC_ACQUIRE) == want;
+                published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want;
                 break;
             }
             if (q != hipErrorNotReady)
@@ -944,7 +991,7 @@ int cavmd_result_read(cavmd_workspace* ws, cavmd_result* out)
         ws->computed = false;
         return (int)hipErrorLaunchFailure;
     }
-    memcpy(out, &ws->h_result->result, sizeof(cavmd_result));
+    memcpy(out, &last_block(ws)->result, sizeof(cavmd_result));
     return CAVMD_OK;
 }
 
@@ -960,6 +1007,86 @@ int cavmd_energies(cavmd_workspace* ws, double out[3])
     }
     cavmd_result r;
     int st = cavmd_result_read(ws, &r);
+    if (st != CAVMD_OK)
+        return st;
+    out[0] = r.energy[0];
+    out[1] = r.energy[1];
+    out[2] = r.energy[2];
+    return CAVMD_OK;
+}
+
+int cavmd_last_sequence(cavmd_workspace* ws, uint64_t* out)
+{
+    if (!ws || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = ws->sequence;
+    return CAVMD_OK;
+}
+
+// Result of evaluation `sequence`, read from its own slot of the ring: waits for THAT evaluation only, so a tracker can
+// enqueue step k and read step k - 1 while step k keeps the GPU busy.  No seqlock: slot s % depth is reused only by the
+// enqueue of evaluation s + depth, which this (one) host thread would have to make itself, and the range check below
+// refuses every s whose slot that enqueue has already handed out.
+int cavmd_result_at(cavmd_workspace* ws, uint64_t sequence, cavmd_result* out)
+{
+    if (!ws || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->sequence == 0)
+        return CAVMD_ERR_NOT_COMPUTED;
+    if (ws->captured) // replays publish into one fixed block under their frozen sequence: no history to read
+        return CAVMD_ERR_INVALID_VALUE;
+    const uint64_t last = ws->sequence;
+    if (sequence == 0 || sequence > last)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (sequence < ws->history_first || last - sequence >= ws->ring_depth)
+        return CAVMD_ERR_EXPIRED;
+    DeviceGuard guard(ws->device);
+    const HostResult* h = ring_slot(ws, sequence);
+    bool published = false;
+    for (;;)
+    {
+        if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence)
+        {
+            published = true;
+            break;
+        }
+        // The evaluation is over once a LATER one has published (the stream runs them in order) or the stream is idle.
+        // Never a stream synchronisation, and never the workspace-wide starvation flag: either would wait behind newer
+        // evaluations (a starved one among them can take a third of a second).
+        bool later = false;
+        for (uint64_t j = sequence + 1; j <= last && !later; ++j)
+            later = __atomic_load_n(&ring_slot(ws, j)->ready, __ATOMIC_ACQUIRE) == j;
+        if (later)
+        {
+            published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence;
+            break;
+        }
+        const hipError_t q = hipStreamQuery(ws->last_stream);
+        if (q == hipSuccess)
+        {
+            published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence;
+            break;
+        }
+        if (q != hipErrorNotReady)
+            return (int)q;
+    }
+    if (!published)
+    {
+        // over, and its slot does not carry it: a starved single-launch evaluation that could not be completed tagged its
+        // slot with its own sequence; anything else is a launch that died on the device.  Never an earlier occupant's block.
+        const uint64_t failed = __atomic_load_n(&h->failed, __ATOMIC_ACQUIRE);
+        return failed == ((sequence << 2) | kSyncFailed) ? CAVMD_ERR_SYNC_TIMEOUT : (int)hipErrorLaunchFailure;
+    }
+    memcpy(out, &h->result, sizeof(cavmd_result));
+    return CAVMD_OK;
+}
+
+int cavmd_energies_at(cavmd_workspace* ws, uint64_t sequence, double out[3])
+{
+    if (!ws || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    cavmd_result r;
+    const int st = cavmd_result_at(ws, sequence, &r);
     if (st != CAVMD_OK)
         return st;
     out[0] = r.energy[0];
@@ -1428,10 +1555,52 @@ int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap, size_t* 
     return CAVMD_OK;
 }
 
+namespace
+{
+// "result_history": a new ring of `depth` slots.  The stream is drained first (no kernel may still publish into the old
+// ring); the last evaluation's block moves to its slot of the new ring, so the synchronous getters keep returning it, and
+// every earlier sequence expires.
+int resize_history(cavmd_workspace* ws, unsigned depth)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (ws->last_stream != nullptr && hipStreamIsCapturing(ws->last_stream, &cap) == hipSuccess
+        && cap != hipStreamCaptureStatusNone)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(ws->device);
+    if (ws->sequence)
+        CAVMD_HIP_TRY(hipStreamSynchronize(ws->last_stream));
+    HostResult* ring = nullptr;
+    HostResult* ring_dev = nullptr;
+    CAVMD_HIP_TRY(hipHostMalloc((void**)&ring, sizeof(HostResult) * depth, hipHostMallocMapped | hipHostMallocCoherent));
+    const hipError_t e = hipHostGetDevicePointer((void**)&ring_dev, ring, 0);
+    if (e != hipSuccess)
+    {
+        (void)hipHostFree(ring);
+        return (int)e;
+    }
+    memset(ring, 0, sizeof(HostResult) * depth);
+    const uint64_t keep = ws->captured ? ws->captured_from : ws->sequence;
+    if (keep)
+        memcpy(ring + keep % depth, ring_slot(ws, keep), sizeof(HostResult));
+    (void)hipHostFree(ws->h_ring);
+    ws->h_ring = ring;
+    ws->h_ring_dev = ring_dev;
+    ws->ring_depth = depth;
+    ws->history_first = ws->sequence ? ws->sequence : 1;
+    return CAVMD_OK;
+}
+} // namespace
+
 int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
 {
     if (!ws || !name)
         return CAVMD_ERR_INVALID_VALUE;
+    if (!strcmp(name, "result_history"))
+    {
+        if (value < 2 || value > (int)kResultHistoryMax)
+            return CAVMD_ERR_INVALID_VALUE;
+        return resize_history(ws, (unsigned)value);
+    }
     if (!strcmp(name, "reduce_blocks_per_cu"))
     {
         if (value < 1 || value > kMaxBlocksPerCU)
@@ -1549,7 +1718,7 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
         if (value < 0 || value > 2)
             return CAVMD_ERR_INVALID_VALUE;
         if (value)
-            __atomic_store_n(&ws->h_result->sync_error, value == 2 ? kSyncRepaired : kSyncFailed, __ATOMIC_RELEASE);
+            __atomic_store_n(&ws->h_ctl->sync_error, value == 2 ? kSyncRepaired : kSyncFailed, __ATOMIC_RELEASE);
         else
             ws->sync_timeout_seen = false;
 #else
@@ -1596,6 +1765,8 @@ int cavmd_get_tunable(cavmd_workspace* ws, const char* name, int* value)
         return CAVMD_ERR_INVALID_VALUE;
     if (!strcmp(name, "reduce_blocks_per_cu"))
         *value = ws->reduce_blocks_per_cu;
+    else if (!strcmp(name, "result_history"))
+        *value = (int)ws->ring_depth;
     else if (!strcmp(name, "map_blocks_per_cu"))
         *value = ws->map_blocks_per_cu;
     else if (!strcmp(name, "map_nt_store"))
@@ -1676,6 +1847,8 @@ const char* cavmd_error_string(int status)
         return "bad cavity parameters (K == 0 or non-finite)";
     case CAVMD_ERR_NOT_COMPUTED:
         return "no evaluation has been enqueued on this workspace yet";
+    case CAVMD_ERR_EXPIRED:
+        return "that evaluation's result slot has been reused: read it sooner or raise the \"result_history\" tunable";
     case CAVMD_ERR_SYNC_TIMEOUT:
         return "a single-launch evaluation was starved (its workgroups were not resident together) and could not be completed; "
                "forces of that evaluation are NaN";

@@ -468,13 +468,17 @@ __device__ __forceinline__ void write_result(cavmd_result* __restrict__ res, con
 // Host hand-off of the result block: `host` points at mapped pinned host memory.  The block is written first, then the
 // evaluation's sequence number is release-stored at SYSTEM scope into host->ready, so a host thread that acquires
 // ready == sequence sees the whole block (cavmd_result_read spins on it instead of paying a stream synchronisation).
+// The workspace keeps a ring of these (one slot per evaluation, sequence % depth: cavmd_result_at), padded to 256 bytes so
+// that two slots never share a line.
 struct HostResult
 {
     cavmd_result result;
     uint64_t ready;
-    unsigned sync_error; // single-launch kernel, starved evaluation: kSyncFailed / kSyncRepaired (cavmd_persistent_kernel.hpp)
-    unsigned pad;
+    uint64_t failed; // single-launch kernel, starved evaluation that could not be completed: (sequence << 2) | kSyncFailed,
+                     // tagged so that a stale word of an earlier occupant of the slot never names a later evaluation
+    unsigned char pad[48];
 };
+static_assert(sizeof(HostResult) == 256, "one result slot = 256 bytes");
 __device__ __forceinline__ void publish_to_host(HostResult* __restrict__ host, const Scalars& sc, unsigned N,
                                                 unsigned nparts, uint64_t sequence)
 {

@@ -78,8 +78,10 @@ struct SyncState
     unsigned late_ticks;          // wall clock late, as if its CU had been held by another grid; -1: none
     int silent_block;             // fault injection (FAULT instantiation only): this block never publishes its record, as if
                                   // it were not resident -> the evaluation cannot be completed; -1: none
+    unsigned* sync_error;         // the workspace's starvation flag, a fixed word in mapped host memory (kSyncFailed /
+                                  // kSyncRepaired; the host consumes it): outside the per-evaluation result slots
 };
-// HostResult::sync_error
+// *SyncState::sync_error, and the low bits of HostResult::failed
 constexpr unsigned kSyncFailed = 1u;   // some block gave up and nobody could complete the evaluation: its forces hold NaN
 constexpr unsigned kSyncRepaired = 2u; // every block gave up; the last one completed the whole evaluation alone: results valid
 
@@ -499,7 +501,9 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
         __syncthreads();
         if (tid == 0)
         {
-            __hip_atomic_store(&res_host->sync_error, kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(st.sync_error, kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            // this evaluation's own slot says so too, tagged with its sequence (a repair below publishes the result over it)
+            __hip_atomic_store(&res_host->failed, (sequence << 2) | kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (poisoned)
                 s_last = 0u; // a launch behind an evaluation nobody could complete: fail as a whole, touch nothing
             else
@@ -550,7 +554,7 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
                 if (ok)
                 {
                     // the verdict first, the result's ready flag (a release) after it: a host that sees the result sees "repaired"
-                    __hip_atomic_store(&res_host->sync_error, kSyncRepaired, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(st.sync_error, kSyncRepaired, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     write_result(res, sc, N, G, sequence);
                     publish_to_host(res_host, sc, N, G, sequence);
                 }
@@ -566,7 +570,7 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
         if (tid == 0)
         {
             // every block has read the epoch and been counted, none is left in the hand-off: count, epoch and poison are put
-            // back in order for the next evaluation (whether or not THIS one could be completed: that is sync_error's to say)
+            // back in order for the next evaluation (whether or not THIS one could be completed: that is the starvation flag's to say)
             __hip_atomic_store(st.epoch + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(st.epoch, tag + 1u ? tag + 1u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(st.epoch + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

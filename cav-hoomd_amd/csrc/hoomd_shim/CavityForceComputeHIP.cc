@@ -158,6 +158,38 @@ Scalar CavityForceComputeHIP::getDipoleSelfEnergy()
     return m_energy[2];
     }
 
+uint64_t CavityForceComputeHIP::lastSequence()
+    {
+    uint64_t s = 0;
+    check(cavmd_last_sequence(m_ws, &s), "cavmd_last_sequence");
+    return s;
+    }
+
+pybind11::tuple CavityForceComputeHIP::getEnergiesAt(uint64_t sequence)
+    {
+    double e[3];
+    check(cavmd_energies_at(m_ws, sequence, e), "cavmd_energies_at");
+    return pybind11::make_tuple(e[0], e[1], e[2]);
+    }
+
+pybind11::dict CavityForceComputeHIP::getResultAt(uint64_t sequence)
+    {
+    cavmd_result r;
+    check(cavmd_result_at(m_ws, sequence, &r), "cavmd_result_at");
+    pybind11::dict v;
+    v["dipole"] = pybind11::make_tuple(r.dipole[0], r.dipole[1], r.dipole[2]);
+    v["total_dipole"] = pybind11::make_tuple(r.total_dipole[0], r.total_dipole[1], r.total_dipole[2]);
+    v["q"] = pybind11::make_tuple(r.q[0], r.q[1], r.q[2]);
+    v["Dq"] = pybind11::make_tuple(r.Dq[0], r.Dq[1]);
+    v["energy"] = pybind11::make_tuple(r.energy[0], r.energy[1], r.energy[2]);
+    v["photon_force"] = pybind11::make_tuple(r.photon_force[0], r.photon_force[1], r.photon_force[2]);
+    v["photon_idx"] = r.photon_idx;
+    v["n_photon_typed"] = r.n_photon_typed;
+    v["n_particles"] = r.n_particles;
+    v["sequence"] = r.sequence;
+    return v;
+    }
+
 namespace detail
     {
 void export_CavityForceComputeHIP(pybind11::module& m)
@@ -174,7 +206,10 @@ void export_CavityForceComputeHIP(pybind11::module& m)
         .def("getParams", &CavityForceComputeHIP::getParams)
         .def("getHarmonicEnergy", &CavityForceComputeHIP::getHarmonicEnergy)
         .def("getCouplingEnergy", &CavityForceComputeHIP::getCouplingEnergy)
-        .def("getDipoleSelfEnergy", &CavityForceComputeHIP::getDipoleSelfEnergy);
+        .def("getDipoleSelfEnergy", &CavityForceComputeHIP::getDipoleSelfEnergy)
+        .def("lastSequence", &CavityForceComputeHIP::lastSequence)
+        .def("getEnergiesAt", &CavityForceComputeHIP::getEnergiesAt, pybind11::arg("sequence"))
+        .def("getResultAt", &CavityForceComputeHIP::getResultAt, pybind11::arg("sequence"));
     }
     } // namespace detail
     } // namespace cavitymd

@@ -37,6 +37,12 @@ class PYBIND11_EXPORT CavityForceComputeHIP : public ForceCompute
     Scalar getCouplingEnergy();
     Scalar getDipoleSelfEnergy();
 
+    //! Result history: the sequence of the last evaluation enqueued, and the energies / result block of an earlier one,
+    //! read from its own slot without waiting for the newest evaluation (cavmd_result_at in include/cavmd.h)
+    uint64_t lastSequence();
+    pybind11::tuple getEnergiesAt(uint64_t sequence);
+    pybind11::dict getResultAt(uint64_t sequence);
+
     protected:
     void computeForces(uint64_t timestep) override;
 

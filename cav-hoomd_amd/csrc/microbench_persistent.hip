@@ -106,7 +106,7 @@ int main(int argc, char** argv)
         printf("frame %d: pos %p  force %p  charge %p  image %p\n", f, (void*)d_pos[f], (void*)d_frc[f], (void*)d_chg[f], (void*)d_img[f]);
     const unsigned max_parts = CU * 16;
     double* d_part; int* d_ipart; cavmd_result* d_res; HostResult* d_hres;
-    unsigned long long* d_gran; unsigned* d_epoch;
+    unsigned long long* d_gran; unsigned* d_epoch; unsigned* d_syncerr;
     CHECK(hipMalloc((void**)&d_part, sizeof(double) * kNumPartDoubles * max_parts));
     CHECK(hipMalloc((void**)&d_ipart, sizeof(int) * kNumPartInts * max_parts));
     CHECK(hipMalloc((void**)&d_res, sizeof(cavmd_result)));
@@ -116,8 +116,10 @@ int main(int argc, char** argv)
     CHECK(hipMalloc((void**)&d_epoch, 16));
     const unsigned epoch_init[4] = {1u, 0u, 0u, 0u};
     CHECK(hipMemcpy(d_epoch, epoch_init, 16, hipMemcpyHostToDevice));
+    CHECK(hipMalloc((void**)&d_syncerr, sizeof(unsigned)));
+    CHECK(hipMemset(d_syncerr, 0, sizeof(unsigned)));
     Partials part {d_part, d_ipart, max_parts};
-    SyncState sync {d_gran, d_epoch, kSpinLimit, -1, 0u, -1};
+    SyncState sync {d_gran, d_epoch, kSpinLimit, -1, 0u, -1, d_syncerr};
     const double L = 215.4;
     const unsigned n = (unsigned)N;
     hipStream_t st = 0;
@@ -188,6 +190,7 @@ int main(int argc, char** argv)
         CHECK(hipEventSynchronize(b2));
         float ms; CHECK(hipEventElapsedTime(&ms, a, b2));
         HostResult hr; CHECK(hipMemcpy(&hr, d_hres, sizeof(hr), hipMemcpyDeviceToHost));
+        unsigned sync_error; CHECK(hipMemcpy(&sync_error, d_syncerr, sizeof(sync_error), hipMemcpyDeviceToHost));
         cavmd_result got_res; CHECK(hipMemcpy(&got_res, d_res, sizeof(got_res), hipMemcpyDeviceToHost));
         unsigned after[3]; CHECK(hipMemcpy(after, d_epoch, 12, hipMemcpyDeviceToHost));
         CHECK(hipMemcpy(h_f.data(), d_frc[0], 32 * N, hipMemcpyDeviceToHost));
@@ -197,16 +200,17 @@ int main(int argc, char** argv)
                                  && memcmp(hr.result.dipole, want_res.dipole, sizeof(got_res.dipole)) == 0;
 #ifdef CAVMD_FAULT_SILENT_BLOCK
         (void)differ; (void)same_dipole;
-        printf("fault injection (block %d silent, grid %u): kernel returned after %.1f ms, sync_error=%u, ready=%llu, NaN force entries %zu of %zu, epoch %u, give-up count left %u, poison word %s\n",
-               CAVMD_FAULT_SILENT_BLOCK, g1, ms, hr.sync_error, (unsigned long long)hr.ready, nan, h_f.size(), after[0], after[1], after[2] ? "set" : "clear");
+        printf("fault injection (block %d silent, grid %u): kernel returned after %.1f ms, sync_error=%u, ready=%llu, slot failure word %llu, NaN force entries %zu of %zu, epoch %u, give-up count left %u, poison word %s\n",
+               CAVMD_FAULT_SILENT_BLOCK, g1, ms, sync_error, (unsigned long long)hr.ready, (unsigned long long)hr.failed, nan, h_f.size(), after[0], after[1], after[2] ? "set" : "clear");
         // (with at most 16 blocks every block gathers the block records itself: the silent block, which has its own record in
         // registers, completes its own tile and leaves; the others can never be complete -- a stuck give-up count and an epoch
         // that was not advanced are what the host wipes before it would use the single launch again)
-        return (hr.sync_error == 1 && nan >= h_f.size() - 4 * (size_t)tile && hr.ready == 0) ? 0 : 1;
+        // (the result slot names the failed evaluation: sequence 7, tagged kSyncFailed)
+        return (sync_error == 1 && hr.failed == ((7ull << 2) | kSyncFailed) && nan >= h_f.size() - 4 * (size_t)tile && hr.ready == 0) ? 0 : 1;
 #else
         printf("fault injection (block %d late, grid %u): kernel returned after %.1f ms, sync_error=%u, ready=%llu, NaN force entries %zu, force entries differing from the two-launch path %zu of %zu, dipole identical %d, epoch %u, give-up count left %u, poison word %s\n",
-               CAVMD_FAULT_LATE_BLOCK, g1, ms, hr.sync_error, (unsigned long long)hr.ready, nan, differ, h_f.size(), (int)same_dipole, after[0], after[1], after[2] ? "set" : "clear");
-        return (hr.sync_error == 2 && nan == 0 && differ == 0 && hr.ready == 7 && same_dipole && after[0] == 2 && after[1] == 0 && after[2] == 0) ? 0 : 1;
+               CAVMD_FAULT_LATE_BLOCK, g1, ms, sync_error, (unsigned long long)hr.ready, nan, differ, h_f.size(), (int)same_dipole, after[0], after[1], after[2] ? "set" : "clear");
+        return (sync_error == 2 && nan == 0 && differ == 0 && hr.ready == 7 && same_dipole && after[0] == 2 && after[1] == 0 && after[2] == 0) ? 0 : 1;
 #endif
     }
 #endif

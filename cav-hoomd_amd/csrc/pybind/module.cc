@@ -26,6 +26,22 @@ void check(int status, const char* where)
                                  + cavmd_error_string(status));
 }
 
+py::dict result_dict(const cavmd_result& r)
+{
+    py::dict v;
+    v["dipole"] = py::make_tuple(r.dipole[0], r.dipole[1], r.dipole[2]);
+    v["total_dipole"] = py::make_tuple(r.total_dipole[0], r.total_dipole[1], r.total_dipole[2]);
+    v["q"] = py::make_tuple(r.q[0], r.q[1], r.q[2]);
+    v["Dq"] = py::make_tuple(r.Dq[0], r.Dq[1]);
+    v["energy"] = py::make_tuple(r.energy[0], r.energy[1], r.energy[2]);
+    v["photon_force"] = py::make_tuple(r.photon_force[0], r.photon_force[1], r.photon_force[2]);
+    v["photon_idx"] = r.photon_idx;
+    v["n_photon_typed"] = r.n_photon_typed;
+    v["n_particles"] = r.n_particles;
+    v["sequence"] = r.sequence;
+    return v;
+}
+
 class CavityForceComputeHIP
 {
 public:
@@ -81,18 +97,29 @@ public:
     {
         cavmd_result r;
         check(cavmd_result_read(m_ws, &r), "cavmd_result_read");
-        py::dict v;
-        v["dipole"] = py::make_tuple(r.dipole[0], r.dipole[1], r.dipole[2]);
-        v["total_dipole"] = py::make_tuple(r.total_dipole[0], r.total_dipole[1], r.total_dipole[2]);
-        v["q"] = py::make_tuple(r.q[0], r.q[1], r.q[2]);
-        v["Dq"] = py::make_tuple(r.Dq[0], r.Dq[1]);
-        v["energy"] = py::make_tuple(r.energy[0], r.energy[1], r.energy[2]);
-        v["photon_force"] = py::make_tuple(r.photon_force[0], r.photon_force[1], r.photon_force[2]);
-        v["photon_idx"] = r.photon_idx;
-        v["n_photon_typed"] = r.n_photon_typed;
-        v["n_particles"] = r.n_particles;
-        v["sequence"] = r.sequence;
-        return v;
+        return result_dict(r);
+    }
+
+    // result history (cavmd_result_at): an earlier evaluation, read without waiting for the newest one
+    std::uint64_t lastSequence()
+    {
+        std::uint64_t s = 0;
+        check(cavmd_last_sequence(m_ws, &s), "cavmd_last_sequence");
+        return s;
+    }
+
+    py::dict getResultAt(std::uint64_t sequence)
+    {
+        cavmd_result r;
+        check(cavmd_result_at(m_ws, sequence, &r), "cavmd_result_at");
+        return result_dict(r);
+    }
+
+    py::tuple getEnergiesAt(std::uint64_t sequence)
+    {
+        double e[3];
+        check(cavmd_energies_at(m_ws, sequence, e), "cavmd_energies_at");
+        return py::make_tuple(e[0], e[1], e[2]);
     }
 
 private:
@@ -139,5 +166,8 @@ PYBIND11_MODULE(_cavitymd, m)
         .def("getCouplingEnergy", &CavityForceComputeHIP::getCouplingEnergy)
         .def("getDipoleSelfEnergy", &CavityForceComputeHIP::getDipoleSelfEnergy)
         .def("getEnergies", &CavityForceComputeHIP::getEnergies)
-        .def("getResult", &CavityForceComputeHIP::getResult);
+        .def("getResult", &CavityForceComputeHIP::getResult)
+        .def("lastSequence", &CavityForceComputeHIP::lastSequence)
+        .def("getResultAt", &CavityForceComputeHIP::getResultAt, py::arg("sequence"))
+        .def("getEnergiesAt", &CavityForceComputeHIP::getEnergiesAt, py::arg("sequence"));
 }

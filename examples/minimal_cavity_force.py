@@ -42,6 +42,15 @@ def main():
               f"E_dipole_self={force.dipole_self_energy:.6e} total={force.energy:.6e}")
         pdata.getPositions()[:, :3] += 1e-3 * torch.randn((n, 3), dtype=torch.float64, device="cuda")
 
+    # the same energies without waiting for the step just enqueued: read one step late from the result history
+    history = cavitymd.EnergyHistory(force._force_impl)
+    for step in range(5, 10):
+        force.compute(step)
+        history.record(step)
+        for timestep, e_h, e_c, e_d in history.drain() + (history.flush() if step == 9 else []):
+            print(f"step {timestep} (read one step late): E_harmonic={e_h:.6e} E_coupling={e_c:.6e} E_dipole_self={e_d:.6e}")
+        pdata.getPositions()[:, :3] += 1e-3 * torch.randn((n, 3), dtype=torch.float64, device="cuda")
+
     impl = force._force_impl
     print("total dipole:", observables.compute_total_dipole_moment(impl))
     print("cavity mode (KE, PE, total, T):", observables.cavity_mode(impl, vel4))

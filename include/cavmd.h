@@ -36,6 +36,8 @@
  *     the reference).  A workspace that has been captured reads its results (cavmd_result_read,
  *     cavmd_energies) behind a hipDeviceSynchronize instead of the host-visible flag: a replayed kernel
  *     carries the sequence number of its capture, so the flag cannot tell replays apart.
+ *     Nor can it keep a history of results (cavmd_result_at answers CAVMD_ERR_INVALID_VALUE from the first captured
+ *     evaluation on; see "result history" below).
  *     A graph whose replay ended in CAVMD_ERR_SYNC_TIMEOUT must be captured again before it is replayed (the
  *     library's own recovery -- two launches, wiped hand-off slabs -- does not reach into a captured graph): until then
  *     every replay of it fails at once and as a whole (NaN forces, nothing published; the poison word of
@@ -88,7 +90,9 @@ extern "C" {
 #define CAVMD_ERR_NOT_COMPUTED (-5)  /* results requested before any cavmd_compute_* call */
 #define CAVMD_ERR_SYNC_TIMEOUT (-6)  /* a starved single-launch evaluation that could not be completed (see the "persistent"
                                         tunable): that evaluation's forces are NaN.  Returned by cavmd_result_read /
-                                        cavmd_energies or by the next cavmd_compute_* call, whichever comes first. */
+                                        cavmd_energies or by the next cavmd_compute_* call, whichever comes first
+                                        (cavmd_result_at returns it for that evaluation without consuming it). */
+#define CAVMD_ERR_EXPIRED (-7)       /* the evaluation's slot has been reused: read it sooner or raise "result_history" */
 
 /* ---- layouts (bit-compatible with HOOMD-blue's Scalar4 / int3 in a double-precision build) -- */
 typedef struct cavmd_double4
@@ -202,6 +206,36 @@ CAVMD_API int cavmd_energies(cavmd_workspace* ws, double out[3]);
 CAVMD_API int cavmd_result_read(cavmd_workspace* ws, cavmd_result* out);
 /* Device address of the result block, for consumers that stay on the GPU (trackers, graphs). */
 CAVMD_API int cavmd_result_device_ptr(cavmd_workspace* ws, const cavmd_result** out);
+
+/* ---- result history: read an earlier evaluation without waiting for the newest one -------------------------------- */
+/* Every evaluation publishes its result block into its own slot of a ring in mapped pinned host memory (slot
+ * sequence % depth, depth = the tunable "result_history", default 64).  A tracker that reads the energies after every step
+ * (the reference's EnergyTracker / CavityModeTracker) can then enqueue step k and read step k - 1: the GPU always has the
+ * next evaluation queued, and the read costs no wait once that evaluation has published.
+ *
+ * cavmd_last_sequence: sequence number of the last evaluation enqueued on ws (0 before any; a call with N == 0 consumes
+ * none).  No wait.  The n-th evaluation of a workspace has sequence n (cavmd_result.sequence).
+ * cavmd_result_at: the result block of evaluation `sequence`, byte for byte what cavmd_result_read returned right after it.
+ *   - CAVMD_ERR_NOT_COMPUTED on a workspace that has never evaluated;
+ *   - CAVMD_ERR_INVALID_VALUE for sequence 0 or beyond cavmd_last_sequence, and for EVERY sequence once the workspace has
+ *     been captured (see below);
+ *   - CAVMD_ERR_EXPIRED once depth or more evaluations followed it, or if "result_history" was set after it;
+ *   - waits for THAT evaluation only (its slot's flag; the wait also ends once a later evaluation has published or the
+ *     stream is idle): never a stream synchronisation, never behind newer evaluations;
+ *   - an evaluation that ended without publishing returns an error, never another evaluation's block:
+ *     CAVMD_ERR_SYNC_TIMEOUT for a starved single-launch evaluation that could not be completed (the starvation flag is
+ *     left for cavmd_result_read / the next cavmd_compute_*, which report it once, as before), a HIP launch failure
+ *     otherwise.  Other sequences stay readable.  A starved evaluation that was completed by its last workgroup is valid.
+ * cavmd_energies_at: out = its energy[0..2], as cavmd_energies.
+ * The synchronous getters above (cavmd_energies, cavmd_result_read, cavmd_result_device_ptr) keep reading the LAST
+ * evaluation.  One workspace serves one host thread and one stream: a slot is reused only by an enqueue the caller makes.
+ * Graph capture: a captured kernel keeps the sequence and slot it was captured with, so the ring cannot tell its replays
+ * apart.  From the first evaluation enqueued into a capture on, the workspace publishes every evaluation (replays and
+ * eager ones alike) into one fixed block, read by the synchronous getters behind a device synchronisation as before, and
+ * cavmd_result_at / cavmd_energies_at answer CAVMD_ERR_INVALID_VALUE. */
+CAVMD_API int cavmd_last_sequence(cavmd_workspace* ws, uint64_t* out);
+CAVMD_API int cavmd_result_at(cavmd_workspace* ws, uint64_t sequence, cavmd_result* out);
+CAVMD_API int cavmd_energies_at(cavmd_workspace* ws, uint64_t sequence, double out[3]);
 
 /* ---- observables next to the force path ------------------------------------------- */
 /* Wavevectors for the density field: n_k rows of (kx, ky, kz) in HOST memory; copied into the workspace once.
@@ -358,6 +392,10 @@ CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap
  *                                  wavevectors per chunk, -1 auto by n_k
  *   "persistent_lds_kb"    0..156  LDS budget per block of the single-launch kernel in KiB (0 = default); the charges of tiles
  *                                  beyond it are read a second time
+ *   "result_history"       2..16384 slots of the result ring read by cavmd_result_at (default 64, 256 B each).  Setting it
+ *                                  synchronises the workspace's last stream and reallocates the ring: the last evaluation's
+ *                                  block is carried over (the synchronous getters still return it), every earlier sequence
+ *                                  expires.  CAVMD_ERR_INVALID_VALUE while that stream is being captured.
  *   "persistent_balanced"  -1..1   partition of the particles over the blocks of the single-launch kernel: 0 tiles dealt
  *                                  round-robin (the two-launch path's partition: then also its bits), 1 contiguous equal
  *                                  shares, -1 auto
