@@ -11,11 +11,12 @@ from .utils import PhysicalConstants, unwrap_positions
 from .forces import CavityForce
 from .compute import CavityForceComputeHIP
 from .history import EnergyHistory
+from .batch import BatchEnergyHistory, CavityForceBatch
 from .state import BoxDim, ParticleData, SystemDefinition
 from . import _capi, observables, replicas, synthetic, thermostats
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
     "SystemDefinition", "observables", "replicas", "synthetic", "thermostats",
 ]
 __version__ = "0.1.0"

@@ -70,8 +70,40 @@ class BussiDeviceState(ctypes.Structure):
                 ("refused", ctypes.c_uint64)]
 
 
+class BatchItem(ctypes.Structure):
+    """cavmd_batch_item (128 bytes): one system of a batch; the four arrays are DEVICE pointers."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_charge", ctypes.c_void_p), ("d_image", ctypes.c_void_p),
+                ("d_force", ctypes.c_void_p), ("Lx", ctypes.c_double), ("Ly", ctypes.c_double), ("Lz", ctypes.c_double),
+                ("params", Params), ("N", ctypes.c_uint32), ("L_typeid", ctypes.c_int32), ("reserved", ctypes.c_uint64 * 4)]
+
+
+BATCH_MAX_ITEMS = 65536
+BATCH_MAX_ITEM_N = 65536
+
+
+def batch_launch_order(sizes):
+    """The order in which cavmd_batch_compute starts the systems of a batch: by N descending, ties in item order (the hardware
+    hands out workgroups in launch order, so the long systems of a ragged batch go first).  Results stay indexed by item.
+    This restates the library's rule (std::stable_sort in cavmd_capi.hip); it does not read the library's table."""
+    import numpy as np
+    n = np.asarray(list(sizes), dtype=np.int64)
+    return [int(i) for i in np.argsort(-n, kind="stable")]
+
+
+def batch_item(N, pos_ptr, charge_ptr, image_ptr, force_ptr, box_L, L_typeid, params) -> "BatchItem":
+    it = BatchItem()
+    it.d_pos, it.d_charge, it.d_image, it.d_force = pos_ptr or None, charge_ptr or None, image_ptr or None, force_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.params = params
+    it.N, it.L_typeid = int(N), int(L_typeid)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_batch_item_check", "cavmd_batch_create", "cavmd_batch_destroy", "cavmd_batch_set_items", "cavmd_batch_compute",
+    "cavmd_batch_last_sequence", "cavmd_batch_results_read", "cavmd_batch_results_at", "cavmd_batch_energies_at",
+    "cavmd_batch_results_device_ptr",
     "cavmd_make_params", "cavmd_create", "cavmd_destroy", "cavmd_compute_hoomd", "cavmd_compute_soa",
     "cavmd_energies", "cavmd_result_read", "cavmd_result_device_ptr", "cavmd_last_sequence", "cavmd_result_at",
     "cavmd_energies_at", "cavmd_set_wavevectors", "cavmd_density_field",
@@ -156,6 +188,27 @@ def _declare(lib):
         lib.cavmd_result_at.restype = ci
         lib.cavmd_energies_at.argtypes = [vp, ctypes.c_uint64, P(dbl * 3)]
         lib.cavmd_energies_at.restype = ci
+        u64 = ctypes.c_uint64
+        lib.cavmd_batch_item_check.argtypes = [P(BatchItem)]
+        lib.cavmd_batch_item_check.restype = ci
+        lib.cavmd_batch_create.argtypes = [vp, sz, P(BatchItem), ci, P(vp)]
+        lib.cavmd_batch_create.restype = ci
+        lib.cavmd_batch_destroy.argtypes = [vp]
+        lib.cavmd_batch_destroy.restype = ci
+        lib.cavmd_batch_set_items.argtypes = [vp, sz, sz, P(BatchItem)]
+        lib.cavmd_batch_set_items.restype = ci
+        lib.cavmd_batch_compute.argtypes = [vp, vp]
+        lib.cavmd_batch_compute.restype = ci
+        lib.cavmd_batch_last_sequence.argtypes = [vp, P(u64)]
+        lib.cavmd_batch_last_sequence.restype = ci
+        lib.cavmd_batch_results_read.argtypes = [vp, P(Result)]
+        lib.cavmd_batch_results_read.restype = ci
+        lib.cavmd_batch_results_at.argtypes = [vp, u64, P(Result)]
+        lib.cavmd_batch_results_at.restype = ci
+        lib.cavmd_batch_energies_at.argtypes = [vp, u64, vp]
+        lib.cavmd_batch_energies_at.restype = ci
+        lib.cavmd_batch_results_device_ptr.argtypes = [vp, P(vp)]
+        lib.cavmd_batch_results_device_ptr.restype = ci
         lib.cavmd_set_wavevectors.argtypes = [vp, sz, vp]
         lib.cavmd_set_wavevectors.restype = ci
         lib.cavmd_density_field.argtypes = [vp, vp, sz, vp, sz]
@@ -232,6 +285,7 @@ def make_params(omegac: float, couplstr: float, phmass: float = 1.0) -> Params:
 # may collect a dropped workspace at any allocation, inside a capture too (torch.cuda.graph does not collect before it
 # captures); the frees of cavmd_destroy would invalidate that capture.
 _deferred = []
+_deferred_batches = []  # the same for batches (cavmd_batch_destroy)
 
 
 def _capturing() -> bool:
@@ -244,6 +298,9 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
+    while _deferred_batches:  # batches before the workspaces they were created from
+        lib, h = _deferred_batches.pop()
+        lib.cavmd_batch_destroy(h)
     while _deferred:
         lib, h = _deferred.pop()
         lib.cavmd_destroy(h)
@@ -269,9 +326,11 @@ class Workspace:
             if _capturing():
                 _deferred.append((self._lib, self._h))
             else:
+                if _deferred_batches:  # batches deferred during a capture go before any workspace (include/cavmd.h)
+                    _destroy_deferred()
                 self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if _deferred and not _capturing():
+        if (_deferred or _deferred_batches) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -425,3 +484,91 @@ class Workspace:
         buf = ctypes.create_string_buffer(64)
         check(self._lib.cavmd_device_info(self._h, ctypes.byref(dev), ctypes.byref(cu), buf, 64), "cavmd_device_info")
         return {"device": dev.value, "compute_units": cu.value, "arch": buf.value.decode()}
+
+
+def batch_item_check(item: BatchItem) -> int:
+    """Status cavmd_batch_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_batch_item_check(ctypes.byref(item)))
+
+
+class Batch:
+    """Owns one cavmd_batch: B independent small systems evaluated by ONE kernel launch, one workgroup per system
+    (the reference's replica loop, examples/05_advanced_run.py:1570-1612, on one GPU).  Keeps its workspace alive."""
+
+    def __init__(self, workspace: Workspace, items, history_depth: int = 64):
+        self._ws = workspace
+        self._lib = workspace._lib
+        items = list(items)
+        self.n_items = len(items)
+        self.history_depth = int(history_depth)
+        self.sizes = [int(it.N) for it in items]
+        arr = (BatchItem * max(self.n_items, 1))(*items)
+        self._h = ctypes.c_void_p()
+        check(self._lib.cavmd_batch_create(workspace.handle, self.n_items, arr, self.history_depth, ctypes.byref(self._h)),
+              "cavmd_batch_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def launch_order(self):
+        """Item indices in the order their workgroups start (N descending, stable), as PREDICTED from the sizes by
+        ``batch_launch_order``: the rule the library sorts by, restated in Python, not a read-back of the table the library
+        uploaded (results do not depend on the order; it matters for load balance only)."""
+        return batch_launch_order(self.sizes)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if _capturing():
+                _deferred_batches.append((self._lib, self._h))
+            else:
+                self._lib.cavmd_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        if (_deferred or _deferred_batches) and not _capturing():
+            _destroy_deferred()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_items(self, first: int, items) -> None:
+        items = list(items)
+        arr = (BatchItem * max(len(items), 1))(*items)
+        check(self._lib.cavmd_batch_set_items(self._h, int(first), len(items), arr), "cavmd_batch_set_items")
+        for k, it in enumerate(items):
+            self.sizes[first + k] = int(it.N)
+
+    def compute(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_batch_compute(self._h, ctypes.c_void_p(stream)), "cavmd_batch_compute")
+
+    def last_sequence(self) -> int:
+        out = ctypes.c_uint64()
+        check(self._lib.cavmd_batch_last_sequence(self._h, ctypes.byref(out)), "cavmd_batch_last_sequence")
+        return int(out.value)
+
+    def results(self):
+        """The n_items result blocks of the last evaluation (a ctypes array of Result)."""
+        out = (Result * self.n_items)()
+        check(self._lib.cavmd_batch_results_read(self._h, out), "cavmd_batch_results_read")
+        return out
+
+    def results_at(self, sequence: int):
+        out = (Result * self.n_items)()
+        check(self._lib.cavmd_batch_results_at(self._h, int(sequence), out), "cavmd_batch_results_at")
+        return out
+
+    def energies_at(self, sequence: int):
+        """(n_items, 3) array: harmonic, coupling, dipole-self energy of every system at evaluation `sequence`."""
+        import numpy as np
+        out = np.empty((self.n_items, 3), dtype=np.float64)
+        check(self._lib.cavmd_batch_energies_at(self._h, int(sequence), ctypes.c_void_p(out.ctypes.data)),
+              "cavmd_batch_energies_at")
+        return out
+
+    def results_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        check(self._lib.cavmd_batch_results_device_ptr(self._h, ctypes.byref(p)), "cavmd_batch_results_device_ptr")
+        return int(p.value)

@@ -48,6 +48,27 @@ def assign_replicas(replica_ids, world_size: int):
     return plan
 
 
+def local_batch(ctx: "ReplicaContext", replica_ids, make_cfg, history_depth: int = 64):
+    """The replicas ``assign_replicas`` gave this rank, as ONE ``CavityForceBatch`` on ``ctx.device``: one kernel launch
+    per step evaluates all of them, instead of the reference's loop over replicas (examples/05_advanced_run.py:1570-1612).
+    ``make_cfg(replica_id)`` returns a config dict in snapshot form (``synthetic``'s schema, ``params`` included).  No
+    collective is involved: replicas never exchange data.  Returns ``(batch, ids)`` with ``ids`` this rank's replica ids
+    in batch order."""
+    from .batch import CavityForceBatch
+    from .state import ParticleData, SystemDefinition
+    ids = assign_replicas(replica_ids, ctx.world_size)[ctx.rank]
+    if not ids:
+        return None, []
+    sysdefs, params = [], []
+    for rid in ids:
+        cfg = make_cfg(rid)
+        pd = ParticleData.from_arrays(cfg["position"], cfg["typeid"], cfg["charge"], cfg["image"], cfg["types"], cfg["box"],
+                                      device=ctx.device)
+        sysdefs.append(SystemDefinition(pd))
+        params.append(cfg["params"])
+    return CavityForceBatch(sysdefs, params, history_depth=history_depth), ids
+
+
 def replica_seed(replica_id: int, base_seed: int = 0) -> int:
     """Seed of a replica.  BASELINE config 5 uses seeds 1-8 for replicas 1-8 (base_seed 0).  (The reference
     draws its HOOMD seed from np.random.randint and is not reproducible, examples/05_advanced_run.py:401.)"""

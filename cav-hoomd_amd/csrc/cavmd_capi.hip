@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -1863,6 +1864,358 @@ const char* cavmd_error_string(int status)
 int cavmd_version(void)
 {
     return CAVMD_VERSION_MAJOR * 1000 + CAVMD_VERSION_MINOR;
+}
+
+// ---- a batch of independent small systems in one launch (cavmd_batch_kernel.hpp) ------------------------------------------
+// The replica loop of the reference (examples/05_advanced_run.py:1570-1612) on one GPU: B systems, one kernel, one
+// workgroup per system.  The table of rows lives on the device from create / set_items on; compute enqueues the kernel and
+// nothing else.
+} // extern "C"
+
+namespace
+{
+constexpr int kBatchBlock = kSmallBlock; // the block size of cavity_small_system_kernel: the two paths share bits
+constexpr size_t kBatchRingMaxBytes = (size_t)64 << 20;
+static_assert(sizeof(cavmd_batch_item) == 128, "batch item layout");
+} // namespace
+
+struct cavmd_batch
+{
+    int device = -1;
+    size_t n = 0;
+    unsigned depth = 0;
+    std::vector<cavmd_batch_item> items; // host copy of the table, as the caller gave it
+    std::vector<unsigned> order;         // items by N descending, stable
+    BatchRow* d_rows = nullptr;
+    unsigned* d_order = nullptr;
+    cavmd_result* d_result = nullptr;    // n blocks, indexed by item
+    HostResult* h_ring = nullptr;        // pinned + mapped: depth x n blocks; evaluation s, item i -> (s % depth) * n + i
+    HostResult* h_ring_dev = nullptr;
+    hipStream_t last_stream = nullptr;
+    uint64_t sequence = 0;
+    bool captured = false; // some evaluation was enqueued into a stream capture: the stamps cannot tell replays apart
+};
+
+namespace
+{
+BatchRow batch_row(const cavmd_batch_item& it)
+{
+    BatchRow r;
+    memset(&r, 0, sizeof(r));
+    r.pos2 = reinterpret_cast<const v2d*>(it.d_pos);
+    r.charge = it.d_charge;
+    r.image = reinterpret_cast<const int*>(it.d_image);
+    r.force2 = reinterpret_cast<v2d*>(it.d_force);
+    r.Lx = it.Lx; r.Ly = it.Ly; r.Lz = it.Lz;
+    if (it.N)
+        r.prm = derive(&it.params);
+    r.N = it.N;
+    r.L_typeid = it.L_typeid;
+    return r;
+}
+
+// Launch order: items by N descending, ties in item order (the hardware starts workgroups in blockIdx order, so the long
+// systems of a ragged batch go first and the short ones fill in behind them).
+std::vector<unsigned> batch_order(const std::vector<cavmd_batch_item>& items)
+{
+    // counting would do; B <= 65536 and this is set-up time
+    std::vector<unsigned> order(items.size());
+    for (size_t i = 0; i < items.size(); ++i)
+        order[i] = (unsigned)i;
+    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) { return items[x].N > items[y].N; });
+    return order;
+}
+
+bool stream_capturing(hipStream_t stream)
+{
+    if (stream == nullptr) // the null stream cannot be captured
+        return false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+inline const HostResult* batch_slot(const cavmd_batch* b, uint64_t s)
+{
+    return b->h_ring + (s % b->depth) * b->n;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_batch_item_check(const cavmd_batch_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 4; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    // the checks of cavmd_compute_hoomd, in its order; an empty system may leave its arrays out
+    if (it->N != 0 && (!it->d_pos || !it->d_charge || !it->d_image || !it->d_force))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_force & 15) || ((uintptr_t)it->d_charge & 7)
+        || ((uintptr_t)it->d_image & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N == 0)
+        return CAVMD_OK;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    if (!params_ok(&it->params))
+        return CAVMD_ERR_BAD_PARAMS;
+    return CAVMD_OK;
+}
+
+int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_item* h_items, int history_depth,
+                       cavmd_batch** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || history_depth < 2
+        || history_depth > (int)kResultHistoryMax)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const int st = cavmd_batch_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    const size_t ring_blocks = (size_t)history_depth * n_items;
+    if (ring_blocks * sizeof(HostResult) > kBatchRingMaxBytes)
+        return CAVMD_ERR_CAPACITY;
+
+    cavmd_batch* b = new (std::nothrow) cavmd_batch();
+    if (!b)
+        return (int)hipErrorOutOfMemory;
+    b->device = ws->device;
+    b->n = n_items;
+    b->depth = (unsigned)history_depth;
+    b->items.assign(h_items, h_items + n_items);
+    b->order = batch_order(b->items);
+    std::vector<BatchRow> rows(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+        rows[i] = batch_row(b->items[i]);
+
+    DeviceGuard guard(b->device);
+    hipError_t e = hipMalloc((void**)&b->d_rows, sizeof(BatchRow) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->d_rows, rows.data(), sizeof(BatchRow) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&b->d_order, sizeof(unsigned) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&b->d_result, sizeof(cavmd_result) * n_items);
+    if (e == hipSuccess)
+        e = hipMemset(b->d_result, 0, sizeof(cavmd_result) * n_items);
+    if (e == hipSuccess) // coherent: the polled stamps must not depend on HIP_HOST_COHERENT
+        e = hipHostMalloc((void**)&b->h_ring, sizeof(HostResult) * ring_blocks, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess)
+        e = hipHostGetDevicePointer((void**)&b->h_ring_dev, b->h_ring, 0);
+    if (e != hipSuccess)
+    {
+        cavmd_batch_destroy(b);
+        return (int)e;
+    }
+    memset(b->h_ring, 0, sizeof(HostResult) * ring_blocks);
+    *out = b;
+    return CAVMD_OK;
+}
+
+int cavmd_batch_destroy(cavmd_batch* b)
+{
+    if (!b)
+        return CAVMD_OK;
+    DeviceGuard guard(b->device);
+    // the kernels in flight read the table and write the ring: let them finish (a capturing stream cannot be waited for)
+    if (b->sequence && !stream_capturing(b->last_stream))
+        (void)hipStreamSynchronize(b->last_stream);
+    if (b->d_rows)
+        (void)hipFree(b->d_rows);
+    if (b->d_order)
+        (void)hipFree(b->d_order);
+    if (b->d_result)
+        (void)hipFree(b->d_result);
+    if (b->h_ring)
+        (void)hipHostFree(b->h_ring);
+    delete b;
+    return CAVMD_OK;
+}
+
+int cavmd_batch_set_items(cavmd_batch* b, size_t first, size_t count, const cavmd_batch_item* h_items)
+{
+    if (!b || !h_items || count == 0 || first >= b->n || count > b->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = cavmd_batch_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    DeviceGuard guard(b->device);
+    if (b->sequence)
+    {
+        if (stream_capturing(b->last_stream))
+            return CAVMD_ERR_INVALID_VALUE;
+        CAVMD_HIP_TRY(hipStreamSynchronize(b->last_stream)); // evaluations in flight read the rows this call rewrites
+    }
+    // the new table and order are built aside and committed only after both copies went through: a failed copy leaves the
+    // host's view and (up to the rows already overwritten by a copy that died half-way) the device's as they were
+    std::vector<cavmd_batch_item> items(b->items);
+    std::vector<BatchRow> rows(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        items[first + i] = h_items[i];
+        rows[i] = batch_row(h_items[i]);
+    }
+    const std::vector<unsigned> order = batch_order(items);
+    CAVMD_HIP_TRY(hipMemcpy(b->d_order, order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice));
+    const hipError_t e = hipMemcpy(b->d_rows + first, rows.data(), sizeof(BatchRow) * count, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice); // the old order back
+        return (int)e;
+    }
+    b->items.swap(items);
+    b->order = order;
+    return CAVMD_OK;
+}
+
+int cavmd_batch_compute(cavmd_batch* b, void* stream_)
+{
+    if (!b)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(b->device);
+    if (!b->captured && stream_capturing(stream))
+        b->captured = true;
+    b->sequence += 1;
+    HostResult* host = b->h_ring_dev + (b->sequence % b->depth) * b->n;
+    hipLaunchKernelGGL(cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, stream, b->d_rows,
+                       b->d_order, b->sequence, b->d_result, host);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+    {
+        b->sequence -= 1;
+        return st;
+    }
+    b->last_stream = stream;
+    return CAVMD_OK;
+}
+
+int cavmd_batch_last_sequence(cavmd_batch* b, uint64_t* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = b->sequence;
+    return CAVMD_OK;
+}
+
+namespace
+{
+// Waits for the n stamps of evaluation `sequence` (never for the stream) and leaves b's blocks of it readable.  Each wait ends
+// with the stamp, or once the same item's block of a LATER evaluation carries its stamp (the stream runs them in order), or
+// with the stream idle; an evaluation that is over without its stamp died on the device.
+int batch_wait(cavmd_batch* b, uint64_t sequence)
+{
+    const HostResult* slot = batch_slot(b, sequence);
+    const uint64_t last = b->sequence;
+    for (size_t i = 0; i < b->n; ++i)
+    {
+        const HostResult* h = slot + i;
+        for (;;)
+        {
+            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence)
+                break;
+            bool over = false;
+            for (uint64_t j = sequence + 1; j <= last && !over; ++j)
+                over = __atomic_load_n(&(batch_slot(b, j) + i)->ready, __ATOMIC_ACQUIRE) == j;
+            if (!over)
+            {
+                const hipError_t q = hipStreamQuery(b->last_stream);
+                if (q == hipErrorNotReady)
+                    continue;
+                if (q != hipSuccess)
+                    return (int)q;
+            }
+            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) != sequence)
+                return (int)hipErrorLaunchFailure;
+            break;
+        }
+    }
+    return CAVMD_OK;
+}
+
+int batch_range_check(cavmd_batch* b, uint64_t sequence)
+{
+    if (b->sequence == 0)
+        return CAVMD_ERR_NOT_COMPUTED;
+    if (b->captured) // replays publish under their frozen sequence: no history to read
+        return CAVMD_ERR_INVALID_VALUE;
+    if (sequence == 0 || sequence > b->sequence)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (b->sequence - sequence >= b->depth)
+        return CAVMD_ERR_EXPIRED;
+    return CAVMD_OK;
+}
+} // namespace
+
+int cavmd_batch_results_at(cavmd_batch* b, uint64_t sequence, cavmd_result* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    int st = batch_range_check(b, sequence);
+    if (st != CAVMD_OK)
+        return st;
+    DeviceGuard guard(b->device);
+    st = batch_wait(b, sequence);
+    if (st != CAVMD_OK)
+        return st;
+    const HostResult* slot = batch_slot(b, sequence);
+    for (size_t i = 0; i < b->n; ++i)
+        memcpy(out + i, &slot[i].result, sizeof(cavmd_result));
+    return CAVMD_OK;
+}
+
+int cavmd_batch_energies_at(cavmd_batch* b, uint64_t sequence, double* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    int st = batch_range_check(b, sequence);
+    if (st != CAVMD_OK)
+        return st;
+    DeviceGuard guard(b->device);
+    st = batch_wait(b, sequence);
+    if (st != CAVMD_OK)
+        return st;
+    const HostResult* slot = batch_slot(b, sequence);
+    for (size_t i = 0; i < b->n; ++i)
+        memcpy(out + 3 * i, slot[i].result.energy, 3 * sizeof(double));
+    return CAVMD_OK;
+}
+
+int cavmd_batch_results_read(cavmd_batch* b, cavmd_result* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (b->sequence == 0)
+        return CAVMD_ERR_NOT_COMPUTED;
+    if (!b->captured)
+        return cavmd_batch_results_at(b, b->sequence, out);
+    // graph replays: the stamps cannot be trusted (frozen sequence) and the replay stream is unknown -> wait for the device
+    // and copy the device blocks, which every replay rewrites
+    DeviceGuard guard(b->device);
+    CAVMD_HIP_TRY(hipDeviceSynchronize());
+    CAVMD_HIP_TRY(hipMemcpy(out, b->d_result, sizeof(cavmd_result) * b->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = b->d_result;
+    return CAVMD_OK;
 }
 
 } // extern "C"

@@ -23,10 +23,12 @@
 // a given (N, launch geometry).  The kernel boundary is the only inter-workgroup hand-off.
 //
 // Files: cavmd_reduce.hpp (double-double arithmetic, DPP, block trees), cavmd_force_kernels.hpp (the force path),
+//        cavmd_batch_kernel.hpp (many small systems in one launch, one workgroup each),
 //        cavmd_persistent_kernel.hpp (the single-launch evaluation), cavmd_observable_kernels.hpp (rows f2-f4).
 #pragma once
 
 #include "cavmd_reduce.hpp"
 #include "cavmd_force_kernels.hpp"
+#include "cavmd_batch_kernel.hpp"
 #include "cavmd_persistent_kernel.hpp"
 #include "cavmd_observable_kernels.hpp"

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "cavmd.h"
 
@@ -145,6 +146,121 @@ void compute_hoomd(std::uintptr_t ws, std::uintptr_t stream, size_t N, std::uint
                               reinterpret_cast<cavmd_double4*>(force)),
           "cavmd_compute_hoomd");
 }
+
+// A batch of independent small systems evaluated by one launch (cavmd_batch_*; the reference's replica loop,
+// examples/05_advanced_run.py:1570-1612, on one GPU).  Items are tuples
+// (pos, charge, image, force, Lx, Ly, Lz, omegac, couplstr, phmass, N, L_typeid) with the four arrays as device pointers.
+cavmd_batch_item item_from_tuple(const py::tuple& t)
+{
+    if (t.size() != 12)
+        throw std::invalid_argument("batch item: (pos, charge, image, force, Lx, Ly, Lz, omegac, couplstr, phmass, N, L_typeid)");
+    cavmd_batch_item it = {};
+    it.d_pos = reinterpret_cast<const cavmd_double4*>(t[0].cast<std::uintptr_t>());
+    it.d_charge = reinterpret_cast<const double*>(t[1].cast<std::uintptr_t>());
+    it.d_image = reinterpret_cast<const cavmd_int3*>(t[2].cast<std::uintptr_t>());
+    it.d_force = reinterpret_cast<cavmd_double4*>(t[3].cast<std::uintptr_t>());
+    it.Lx = t[4].cast<double>();
+    it.Ly = t[5].cast<double>();
+    it.Lz = t[6].cast<double>();
+    it.params = cavmd_make_params(t[7].cast<double>(), t[8].cast<double>(), t[9].cast<double>());
+    it.N = t[10].cast<std::uint32_t>();
+    it.L_typeid = t[11].cast<std::int32_t>();
+    return it;
+}
+
+std::vector<cavmd_batch_item> items_from_list(const py::list& items)
+{
+    std::vector<cavmd_batch_item> v;
+    v.reserve(items.size());
+    for (const py::handle& h : items)
+        v.push_back(item_from_tuple(h.cast<py::tuple>()));
+    return v;
+}
+
+// (Unlike cavitymd._capi.Batch this class frees in its destructor unconditionally: an owner that may be collected while a
+// stream capture is under way keeps it alive until the capture has ended.)
+class Batch
+{
+public:
+    Batch(const py::list& items, int history_depth, int device)
+    {
+        const std::vector<cavmd_batch_item> v = items_from_list(items);
+        check(cavmd_create(device, 1, &m_ws), "cavmd_create");
+        const int st = cavmd_batch_create(m_ws, v.size(), v.data(), history_depth, &m_batch);
+        if (st != CAVMD_OK)
+        {
+            cavmd_destroy(m_ws);
+            check(st, "cavmd_batch_create");
+        }
+        m_n = v.size();
+    }
+    ~Batch()
+    {
+        cavmd_batch_destroy(m_batch);
+        cavmd_destroy(m_ws);
+    }
+    Batch(const Batch&) = delete;
+    Batch& operator=(const Batch&) = delete;
+
+    void setItems(size_t first, const py::list& items)
+    {
+        const std::vector<cavmd_batch_item> v = items_from_list(items);
+        check(cavmd_batch_set_items(m_batch, first, v.size(), v.data()), "cavmd_batch_set_items");
+    }
+    void compute(std::uintptr_t stream) { check(cavmd_batch_compute(m_batch, reinterpret_cast<void*>(stream)), "cavmd_batch_compute"); }
+    std::uint64_t lastSequence()
+    {
+        std::uint64_t s = 0;
+        check(cavmd_batch_last_sequence(m_batch, &s), "cavmd_batch_last_sequence");
+        return s;
+    }
+    py::list results()
+    {
+        std::vector<cavmd_result> r(m_n);
+        check(cavmd_batch_results_read(m_batch, r.data()), "cavmd_batch_results_read");
+        return result_list(r);
+    }
+    py::list resultsAt(std::uint64_t sequence)
+    {
+        std::vector<cavmd_result> r(m_n);
+        check(cavmd_batch_results_at(m_batch, sequence, r.data()), "cavmd_batch_results_at");
+        return result_list(r);
+    }
+    py::list energiesAt(std::uint64_t sequence)
+    {
+        std::vector<double> e(3 * m_n);
+        check(cavmd_batch_energies_at(m_batch, sequence, e.data()), "cavmd_batch_energies_at");
+        py::list out;
+        for (size_t i = 0; i < m_n; ++i)
+            out.append(py::make_tuple(e[3 * i], e[3 * i + 1], e[3 * i + 2]));
+        return out;
+    }
+    std::uintptr_t resultsDevicePtr()
+    {
+        const cavmd_result* p = nullptr;
+        check(cavmd_batch_results_device_ptr(m_batch, &p), "cavmd_batch_results_device_ptr");
+        return reinterpret_cast<std::uintptr_t>(p);
+    }
+    size_t size() const { return m_n; }
+
+private:
+    static py::list result_list(const std::vector<cavmd_result>& r)
+    {
+        py::list out;
+        for (const cavmd_result& x : r)
+            out.append(result_dict(x));
+        return out;
+    }
+    cavmd_workspace* m_ws = nullptr;
+    cavmd_batch* m_batch = nullptr;
+    size_t m_n = 0;
+};
+
+int batch_item_check(const py::tuple& item)
+{
+    const cavmd_batch_item it = item_from_tuple(item);
+    return cavmd_batch_item_check(&it);
+}
 } // namespace
 
 PYBIND11_MODULE(_cavitymd, m)
@@ -154,6 +270,17 @@ PYBIND11_MODULE(_cavitymd, m)
     m.def("compute_hoomd", &compute_hoomd, py::arg("ws"), py::arg("stream"), py::arg("N"), py::arg("pos"), py::arg("charge"),
           py::arg("image"), py::arg("Lx"), py::arg("Ly"), py::arg("Lz"), py::arg("L_typeid"), py::arg("omegac"),
           py::arg("couplstr"), py::arg("K"), py::arg("phmass"), py::arg("force"));
+    m.def("batch_item_check", &batch_item_check, py::arg("item"));
+    py::class_<Batch>(m, "Batch")
+        .def(py::init<const py::list&, int, int>(), py::arg("items"), py::arg("history_depth") = 64, py::arg("device") = -1)
+        .def("setItems", &Batch::setItems, py::arg("first"), py::arg("items"))
+        .def("compute", &Batch::compute, py::arg("stream") = 0)
+        .def("lastSequence", &Batch::lastSequence)
+        .def("results", &Batch::results)
+        .def("resultsAt", &Batch::resultsAt, py::arg("sequence"))
+        .def("energiesAt", &Batch::energiesAt, py::arg("sequence"))
+        .def("resultsDevicePtr", &Batch::resultsDevicePtr)
+        .def("__len__", &Batch::size);
     py::class_<CavityForceComputeHIP>(m, "CavityForceComputeHIP")
         .def(py::init<size_t, double, double, double, int>(), py::arg("max_N"), py::arg("omegac"), py::arg("couplstr"),
              py::arg("phmass") = 1.0, py::arg("device") = -1)

@@ -51,6 +51,22 @@ def main():
             print(f"step {timestep} (read one step late): E_harmonic={e_h:.6e} E_coupling={e_c:.6e} E_dipole_self={e_d:.6e}")
         pdata.getPositions()[:, :3] += 1e-3 * torch.randn((n, 3), dtype=torch.float64, device="cuda")
 
+    # several independent systems (the reference's replicas, examples/05_advanced_run.py:1570-1612) in ONE launch per step:
+    # one workgroup per system, each system's forces and energies bit for bit those of a CavityForce of its own
+    replicas = []
+    for seed in range(1, 9):
+        c = synthetic.config1(seed=seed)
+        replicas.append(cavitymd.SystemDefinition(cavitymd.ParticleData.from_arrays(
+            c["position"], c["typeid"], c["charge"], c["image"], c["types"], c["box"], device="cuda")))
+    batch = cavitymd.CavityForceBatch(replicas, {"omegac": omegac, "couplstr": 1e-3, "phmass": 1.0})
+    batch_history = batch.history()
+    for step in range(3):
+        batch.compute(step)                                   # one kernel launch for all eight, asynchronous
+        batch_history.record(step)
+        for timestep, energies in batch_history.drain() + (batch_history.flush() if step == 2 else []):
+            print(f"batch step {timestep}: total energy per replica = {energies.sum(axis=1)}")
+    print("forces on the first particle of replica 3:", batch.forces[3][0])
+
     impl = force._force_impl
     print("total dipole:", observables.compute_total_dipole_moment(impl))
     print("cavity mode (KE, PE, total, T):", observables.cavity_mode(impl, vel4))

@@ -21,6 +21,8 @@
  *                                                                   cavmd_bussi_step / cavmd_bussi_rescale_factor,
  *                                                                   cavmd_kinetic_energy, cavmd_scale_velocities,
  *                                                                   cavmd_bussi_step_device (the step without a host round trip)
+ *   the replica loop (one process, replicas one after the other)
+ *                               examples/05_advanced_run.py:1570-1612    cavmd_batch_create / cavmd_batch_compute (all in one launch)
  *   CavityForceCompute::computeForces (the CPU semantics both follow)
  *                               src/CavityForceCompute.cc:134-208   (semantic contract, see below)
  *
@@ -236,6 +238,76 @@ CAVMD_API int cavmd_result_device_ptr(cavmd_workspace* ws, const cavmd_result** 
 CAVMD_API int cavmd_last_sequence(cavmd_workspace* ws, uint64_t* out);
 CAVMD_API int cavmd_result_at(cavmd_workspace* ws, uint64_t sequence, cavmd_result* out);
 CAVMD_API int cavmd_energies_at(cavmd_workspace* ws, uint64_t sequence, double out[3]);
+
+/* ---- a batch of independent small systems in ONE launch --------------------------------------------------------------- */
+/* The reference's production workload is N = 501 particles run as 500 independent replicas: a sequential loop over replica
+ * ids in one process, or one SLURM array task each (examples/05_advanced_run.py:1336-1351, 1570-1612; submit.sh:3).  A caller
+ * that holds several of them on one GPU registers their arrays ONCE as a batch and evaluates all of them with one kernel, one
+ * 256-thread workgroup per system, instead of one cavmd_compute_hoomd call (one launch, one CU of 256) per replica.
+ * Each system's forces and result block are, bit for bit, what cavmd_compute_hoomd gives for that system alone through its
+ * single-block kernel (the "small_system_max_n" path): both kernels run the same function.  Systems are independent: no
+ * workgroup ever waits for another one inside the launch, hence no starvation and no CAVMD_ERR_SYNC_TIMEOUT on this path. */
+typedef struct cavmd_batch_item
+{
+    const cavmd_double4* d_pos; /* the four arrays of cavmd_compute_hoomd; all DEVICE pointers, same alignments (16/8/4/16) */
+    const double* d_charge;
+    const cavmd_int3* d_image;
+    cavmd_double4* d_force;     /* all N entries are written by every evaluation */
+    double Lx, Ly, Lz;
+    cavmd_params params;        /* 32 B */
+    uint32_t N;                 /* 0 is legal: see below */
+    int32_t L_typeid;
+    uint64_t reserved[4];       /* must be 0 */
+} cavmd_batch_item;             /* 128 B = 32 + 24 + 32 + 8 + 32 */
+typedef struct cavmd_batch cavmd_batch; /* opaque; belongs to the workspace it was created from */
+
+#define CAVMD_BATCH_MAX_ITEMS 65536
+#define CAVMD_BATCH_MAX_ITEM_N 65536 /* larger systems belong to cavmd_compute_hoomd (crossover measured at 1024) */
+
+/* The per-item validation of cavmd_batch_create / cavmd_batch_set_items, as cavmd_compute_hoomd validates its arguments: host
+ * arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item, reserved != 0, a null array (with N > 0) or a
+ * misaligned one; CAVMD_ERR_CAPACITY for N > CAVMD_BATCH_MAX_ITEM_N; CAVMD_ERR_BAD_PARAMS for K == 0 or non-finite parameters
+ * (with N > 0).  An item with N == 0 is legal and may leave its four arrays NULL: nothing of it is read or written except its
+ * result block (all zero, photon_idx = -1, n_particles = 0), so a ragged batch needs no special casing.  What cannot be
+ * checked is not: force arrays of two items that overlap, or arrays shorter than N, are the caller's problem. */
+CAVMD_API int cavmd_batch_item_check(const cavmd_batch_item* item);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS; 0 is CAVMD_ERR_INVALID_VALUE), copies the table to
+ * the device of `ws` (set-up time, like cavmd_set_wavevectors: the only copy this path ever makes) and allocates one
+ * cavmd_result per item on the device plus a ring of history_depth x n_items 256-byte blocks in mapped pinned host memory.
+ * history_depth 2 .. 16384 (else CAVMD_ERR_INVALID_VALUE); CAVMD_ERR_CAPACITY if the ring would exceed 64 MiB.  The batch
+ * uses the workspace's device and nothing else of it; destroying the workspace before its batches is an error.  Without a
+ * device there is no workspace (cavmd_create: CAVMD_ERR_NO_DEVICE), hence no batch and no CPU fallback. */
+CAVMD_API int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_item* h_items, int history_depth,
+                                 cavmd_batch** out);
+/* Synchronises the stream of the batch's last evaluation (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_batch_destroy(cavmd_batch* b);
+/* Rewrites rows first .. first + count - 1 from HOST memory -- how a caller follows a box change or a reallocated array --
+ * after synchronising the stream of the last evaluation; validated as in create, nothing is changed if a row is refused.
+ * CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the batch. */
+CAVMD_API int cavmd_batch_set_items(cavmd_batch* b, size_t first, size_t count, const cavmd_batch_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait; may be captured into
+ * a hipGraph.  Workgroups start in order of N descending (ties in item order), so the long systems of a ragged batch go
+ * first; results stay indexed by item.  The batch counts its own evaluations (the first one is 1): every item's
+ * cavmd_result.sequence carries that number.  One batch serves one host thread and one stream at a time. */
+CAVMD_API int cavmd_batch_compute(cavmd_batch* b, void* stream);
+/* Sequence number of the last evaluation enqueued on b (0 before any).  No wait. */
+CAVMD_API int cavmd_batch_last_sequence(cavmd_batch* b, uint64_t* out);
+/* Reading follows "result history" above, per item: every workgroup publishes its own block into slot
+ * (sequence % history_depth) * n_items + item, after its force stores have been issued.
+ * cavmd_batch_results_at / cavmd_batch_energies_at wait for the n_items stamps of THAT evaluation only, never for the stream:
+ * out = n_items blocks / 3 * n_items doubles (harmonic, coupling, dipole-self per item).  CAVMD_ERR_NOT_COMPUTED before any
+ * evaluation, CAVMD_ERR_INVALID_VALUE for sequence 0 or beyond the last, CAVMD_ERR_EXPIRED once history_depth or more
+ * evaluations followed it.  cavmd_batch_results_read = the last evaluation.
+ * Graph capture: a replay carries the sequence of its capture, so from the first evaluation enqueued into a capture on the
+ * two _at calls answer CAVMD_ERR_INVALID_VALUE, and cavmd_batch_results_read copies the device blocks behind a
+ * hipDeviceSynchronize instead of trusting the stamps: the stream a graph is replayed on is not known to the library, so
+ * that read waits for EVERY stream of the process on this device, other batches' included (as cavmd_result_read does on a
+ * captured workspace).  Forces and the device blocks are right on every replay. */
+CAVMD_API int cavmd_batch_results_read(cavmd_batch* b, cavmd_result* out);
+CAVMD_API int cavmd_batch_results_at(cavmd_batch* b, uint64_t sequence, cavmd_result* out);
+CAVMD_API int cavmd_batch_energies_at(cavmd_batch* b, uint64_t sequence, double* out);
+/* Device address of the n_items result blocks (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out);
 
 /* ---- observables next to the force path ------------------------------------------- */
 /* Wavevectors for the density field: n_k rows of (kx, ky, kz) in HOST memory; copied into the workspace once.
