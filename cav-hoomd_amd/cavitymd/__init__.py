@@ -12,11 +12,12 @@ from .forces import CavityForce
 from .compute import CavityForceComputeHIP
 from .history import EnergyHistory
 from .batch import BatchEnergyHistory, CavityForceBatch
+from .thermostat_batch import BussiReservoirBatch
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, observables, replicas, synthetic, thermostats
+from . import _capi, observables, replicas, synthetic, thermostat_batch, thermostats
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "observables", "replicas", "synthetic", "thermostats",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "observables", "replicas", "synthetic", "thermostat_batch", "thermostats",
 ]
 __version__ = "0.1.0"

@@ -77,6 +77,18 @@ class BatchItem(ctypes.Structure):
                 ("params", Params), ("N", ctypes.c_uint32), ("L_typeid", ctypes.c_int32), ("reserved", ctypes.c_uint64 * 4)]
 
 
+class BussiBatchItem(ctypes.Structure):
+    """cavmd_bussi_batch_item (64 bytes): one system of a thermostat batch; d_vel / d_members are DEVICE pointers."""
+    _fields_ = [("d_vel", ctypes.c_void_p), ("d_members", ctypes.c_void_p), ("n_members", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("dof_translational", ctypes.c_double), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class BussiBatchInput(ctypes.Structure):
+    """cavmd_bussi_batch_input (64 bytes): one step's inputs of one item; the rows live in DEVICE memory."""
+    _fields_ = [("normal_variate", ctypes.c_double), ("gamma_variate", ctypes.c_double), ("c", ctypes.c_double),
+                ("set_T", ctypes.c_double), ("skip", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3)]
+
+
 BATCH_MAX_ITEMS = 65536
 BATCH_MAX_ITEM_N = 65536
 
@@ -99,8 +111,18 @@ def batch_item(N, pos_ptr, charge_ptr, image_ptr, force_ptr, box_L, L_typeid, pa
     return it
 
 
+def bussi_batch_item(vel_ptr, members_ptr, n_members, dof_translational) -> "BussiBatchItem":
+    it = BussiBatchItem()
+    it.d_vel, it.d_members = vel_ptr or None, members_ptr or None
+    it.n_members, it.dof_translational = int(n_members), float(dof_translational)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_bussi_batch_item_check", "cavmd_bussi_batch_input_make", "cavmd_bussi_batch_create", "cavmd_bussi_batch_destroy",
+    "cavmd_bussi_batch_set_items", "cavmd_bussi_batch_step", "cavmd_bussi_batch_last_sequence", "cavmd_bussi_batch_read",
+    "cavmd_bussi_batch_reset", "cavmd_bussi_batch_state_device_ptr",
     "cavmd_batch_item_check", "cavmd_batch_create", "cavmd_batch_destroy", "cavmd_batch_set_items", "cavmd_batch_compute",
     "cavmd_batch_last_sequence", "cavmd_batch_results_read", "cavmd_batch_results_at", "cavmd_batch_energies_at",
     "cavmd_batch_results_device_ptr",
@@ -233,6 +255,26 @@ def _declare(lib):
         lib.cavmd_bussi_device_read.restype = ci
         lib.cavmd_bussi_device_reset.argtypes = [vp, vp]
         lib.cavmd_bussi_device_reset.restype = ci
+        lib.cavmd_bussi_batch_item_check.argtypes = [P(BussiBatchItem)]
+        lib.cavmd_bussi_batch_item_check.restype = ci
+        lib.cavmd_bussi_batch_input_make.argtypes = [dbl] * 5 + [P(BussiBatchInput)]
+        lib.cavmd_bussi_batch_input_make.restype = ci
+        lib.cavmd_bussi_batch_create.argtypes = [vp, sz, P(BussiBatchItem), P(vp)]
+        lib.cavmd_bussi_batch_create.restype = ci
+        lib.cavmd_bussi_batch_destroy.argtypes = [vp]
+        lib.cavmd_bussi_batch_destroy.restype = ci
+        lib.cavmd_bussi_batch_set_items.argtypes = [vp, sz, sz, P(BussiBatchItem)]
+        lib.cavmd_bussi_batch_set_items.restype = ci
+        lib.cavmd_bussi_batch_step.argtypes = [vp, vp, vp]
+        lib.cavmd_bussi_batch_step.restype = ci
+        lib.cavmd_bussi_batch_last_sequence.argtypes = [vp, P(u64)]
+        lib.cavmd_bussi_batch_last_sequence.restype = ci
+        lib.cavmd_bussi_batch_read.argtypes = [vp, P(BussiDeviceState)]
+        lib.cavmd_bussi_batch_read.restype = ci
+        lib.cavmd_bussi_batch_reset.argtypes = [vp, vp]
+        lib.cavmd_bussi_batch_reset.restype = ci
+        lib.cavmd_bussi_batch_state_device_ptr.argtypes = [vp, P(vp)]
+        lib.cavmd_bussi_batch_state_device_ptr.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -286,6 +328,7 @@ def make_params(omegac: float, couplstr: float, phmass: float = 1.0) -> Params:
 # captures); the frees of cavmd_destroy would invalidate that capture.
 _deferred = []
 _deferred_batches = []  # the same for batches (cavmd_batch_destroy)
+_deferred_bussi_batches = []  # and for thermostat batches (cavmd_bussi_batch_destroy)
 
 
 def _capturing() -> bool:
@@ -298,7 +341,10 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
-    while _deferred_batches:  # batches before the workspaces they were created from
+    while _deferred_bussi_batches:  # batches before the workspaces they were created from
+        lib, h = _deferred_bussi_batches.pop()
+        lib.cavmd_bussi_batch_destroy(h)
+    while _deferred_batches:
         lib, h = _deferred_batches.pop()
         lib.cavmd_batch_destroy(h)
     while _deferred:
@@ -326,11 +372,11 @@ class Workspace:
             if _capturing():
                 _deferred.append((self._lib, self._h))
             else:
-                if _deferred_batches:  # batches deferred during a capture go before any workspace (include/cavmd.h)
+                if _deferred_batches or _deferred_bussi_batches:  # batches deferred during a capture go before any workspace
                     _destroy_deferred()
                 self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -525,7 +571,7 @@ class Batch:
             else:
                 self._lib.cavmd_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -571,4 +617,93 @@ class Batch:
     def results_device_ptr(self) -> int:
         p = ctypes.c_void_p()
         check(self._lib.cavmd_batch_results_device_ptr(self._h, ctypes.byref(p)), "cavmd_batch_results_device_ptr")
+        return int(p.value)
+
+
+def bussi_batch_item_check(item: BussiBatchItem) -> int:
+    """Status cavmd_bussi_batch_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_bussi_batch_item_check(ctypes.byref(item)))
+
+
+def bussi_batch_input_make(deltaT, set_T, tau, normal_variate, gamma_variate) -> BussiBatchInput:
+    """One input row with the c = exp(-dt / tau) and the skip flag cavmd_bussi_step_device would use (host arithmetic)."""
+    row = BussiBatchInput()
+    check(load().cavmd_bussi_batch_input_make(float(deltaT), float(set_T), float(tau), float(normal_variate),
+                                              float(gamma_variate), ctypes.byref(row)), "cavmd_bussi_batch_input_make")
+    return row
+
+
+class BussiBatch:
+    """Owns one cavmd_bussi_batch: the translational Bussi thermostat step of B independent small systems as ONE kernel
+    launch, one workgroup per system, its per-step inputs read from device memory.  Keeps its workspace alive."""
+
+    def __init__(self, workspace: Workspace, items):
+        self._ws = workspace
+        self._lib = workspace._lib
+        items = list(items)
+        self.n_items = len(items)
+        self.sizes = [int(it.n_members) for it in items]
+        arr = (BussiBatchItem * max(self.n_items, 1))(*items)
+        self._h = ctypes.c_void_p()
+        check(self._lib.cavmd_bussi_batch_create(workspace.handle, self.n_items, arr, ctypes.byref(self._h)),
+              "cavmd_bussi_batch_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def launch_order(self):
+        """Item indices in the order their workgroups start (n_members descending, stable), predicted by ``batch_launch_order``."""
+        return batch_launch_order(self.sizes)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if _capturing():
+                _deferred_bussi_batches.append((self._lib, self._h))
+            else:
+                self._lib.cavmd_bussi_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
+            _destroy_deferred()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_items(self, first: int, items) -> None:
+        items = list(items)
+        arr = (BussiBatchItem * max(len(items), 1))(*items)
+        check(self._lib.cavmd_bussi_batch_set_items(self._h, int(first), len(items), arr), "cavmd_bussi_batch_set_items")
+        for k, it in enumerate(items):
+            self.sizes[first + k] = int(it.n_members)
+
+    def step(self, stream: int, inputs_ptr: int) -> None:
+        """One kernel: the step of every item, inputs read from the n_items device rows at `inputs_ptr` when the kernel runs."""
+        check(self._lib.cavmd_bussi_batch_step(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)),
+              "cavmd_bussi_batch_step")
+
+    def last_sequence(self) -> int:
+        out = ctypes.c_uint64()
+        check(self._lib.cavmd_bussi_batch_last_sequence(self._h, ctypes.byref(out)), "cavmd_bussi_batch_last_sequence")
+        return int(out.value)
+
+    def read(self, raise_refused: bool = True):
+        """The n_items states after the last step (a ctypes array of BussiDeviceState).  A refusal since the last read raises
+        CavmdError(CAVMD_ERR_BAD_PARAMS) once; with raise_refused=False it returns (states, refused_flag) instead."""
+        out = (BussiDeviceState * self.n_items)()
+        st = self._lib.cavmd_bussi_batch_read(self._h, out)
+        if not raise_refused and st in (CAVMD_OK, CAVMD_ERR_BAD_PARAMS):
+            return out, st == CAVMD_ERR_BAD_PARAMS
+        check(st, "cavmd_bussi_batch_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_bussi_batch_reset(self._h, ctypes.c_void_p(stream)), "cavmd_bussi_batch_reset")
+
+    def state_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        check(self._lib.cavmd_bussi_batch_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_bussi_batch_state_device_ptr")
         return int(p.value)

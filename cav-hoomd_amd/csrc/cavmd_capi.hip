@@ -156,6 +156,7 @@ struct cavmd_workspace
     uint64_t bussi_sequence = 0;
     uint64_t bussi_refused_seen = 0;  // refusals already reported to the caller
     hipStream_t bussi_stream = nullptr; // stream of the last enqueued step: the one whose idleness ends a wait for its flag
+    unsigned bussi_batches = 0;         // live cavmd_bussi_batch objects created from this workspace (cavmd_destroy refuses)
 };
 
 namespace
@@ -496,6 +497,8 @@ int cavmd_destroy(cavmd_workspace* ws)
 {
     if (!ws)
         return CAVMD_OK;
+    if (ws->bussi_batches != 0) // a thermostat batch outlives nothing of its workspace: destroy the batches first
+        return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
         (void)hipEventDestroy(ev);
@@ -2215,6 +2218,307 @@ int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out)
     if (!b || !out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = b->d_result;
+    return CAVMD_OK;
+}
+
+} // extern "C"
+
+// ---- the Bussi thermostat step of a batch of independent small systems in one launch (cavmd_bussi_batch_kernel.hpp) ---------
+struct cavmd_bussi_batch
+{
+    cavmd_workspace* ws = nullptr;
+    int device = -1;
+    size_t n = 0;
+    std::vector<cavmd_bussi_batch_item> items; // host copy of the table, as the caller gave it
+    std::vector<unsigned> order;               // items by n_members descending, stable
+    std::vector<uint64_t> refused_seen;        // per item: refusals already reported to the caller
+    BussiBatchRow* d_rows = nullptr;
+    unsigned* d_order = nullptr;
+    BussiDevice* d_state = nullptr;            // n states, indexed by item
+    HostBussiBatch* h_blocks = nullptr;        // pinned + mapped + coherent: n blocks, indexed by item
+    HostBussiBatch* h_blocks_dev = nullptr;
+    hipStream_t last_stream = nullptr;
+    uint64_t sequence = 0;
+    bool captured = false; // some step was enqueued into a stream capture: the stamps cannot tell replays apart
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_bussi_batch_item) == sizeof(BussiBatchRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_bussi_batch_item, n_members) == offsetof(BussiBatchRow, n)
+                  && offsetof(cavmd_bussi_batch_item, dof_translational) == offsetof(BussiBatchRow, dof),
+              "thermostat batch item layout");
+static_assert(sizeof(cavmd_bussi_batch_input) == sizeof(BussiBatchInput) && offsetof(cavmd_bussi_batch_input, skip) == 32,
+              "thermostat batch input layout");
+static_assert(sizeof(cavmd_bussi_device_state) == sizeof(BussiDevice), "the device states are read out as they are");
+static_assert(CAVMD_BATCH_MAX_ITEM_N <= kBussiBatchMaxTiles * 256 * kBussiBatchUnroll, "one LDS partial per tile");
+
+std::vector<unsigned> bussi_batch_order(const std::vector<cavmd_bussi_batch_item>& items)
+{
+    std::vector<unsigned> order(items.size());
+    for (size_t i = 0; i < items.size(); ++i)
+        order[i] = (unsigned)i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&items](unsigned x, unsigned y) { return items[x].n_members > items[y].n_members; });
+    return order;
+}
+
+void bussi_state_out(cavmd_bussi_device_state* out, const BussiDevice& s)
+{
+    out->reservoir_translational = s.reservoir;
+    out->instantaneous_translational = s.instantaneous;
+    out->last_alpha = s.alpha;
+    out->last_kinetic_energy = s.kinetic;
+    out->steps = s.steps;
+    out->refused = s.errors;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_bussi_batch_item_check(const cavmd_bussi_batch_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved0 != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 4; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if (it->n_members != 0 && !it->d_vel)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_members & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (!std::isfinite(it->dof_translational) || it->dof_translational < 0.0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->n_members > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_input_make(double deltaT, double set_T, double tau, double normal_variate, double gamma_variate,
+                                 cavmd_bussi_batch_input* row)
+{
+    if (!row)
+        return CAVMD_ERR_INVALID_VALUE;
+    memset(row, 0, sizeof(*row));
+    row->normal_variate = normal_variate;
+    row->gamma_variate = gamma_variate;
+    row->c = (tau != 0.0) ? exp(-deltaT / tau) : 0.0; // the expression of cavmd_bussi_step_device (:186-190)
+    row->set_T = set_T;
+    row->skip = (deltaT == 0.0) ? 1u : 0u;             // src/BussiReservoirThermostat.h:45-48
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bussi_batch_item* h_items,
+                             cavmd_bussi_batch** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const int st = cavmd_bussi_batch_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    cavmd_bussi_batch* b = new (std::nothrow) cavmd_bussi_batch();
+    if (!b)
+        return (int)hipErrorOutOfMemory;
+    b->device = ws->device;
+    b->n = n_items;
+    b->items.assign(h_items, h_items + n_items);
+    b->order = bussi_batch_order(b->items);
+    b->refused_seen.assign(n_items, 0);
+
+    DeviceGuard guard(b->device);
+    hipError_t e = hipMalloc((void**)&b->d_rows, sizeof(BussiBatchRow) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->d_rows, b->items.data(), sizeof(BussiBatchRow) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&b->d_order, sizeof(unsigned) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&b->d_state, sizeof(BussiDevice) * n_items);
+    if (e == hipSuccess)
+        e = hipMemset(b->d_state, 0, sizeof(BussiDevice) * n_items);
+    if (e == hipSuccess) // coherent: the polled stamps must not depend on HIP_HOST_COHERENT
+        e = hipHostMalloc((void**)&b->h_blocks, sizeof(HostBussiBatch) * n_items, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess)
+        e = hipHostGetDevicePointer((void**)&b->h_blocks_dev, b->h_blocks, 0);
+    if (e != hipSuccess)
+    {
+        cavmd_bussi_batch_destroy(b);
+        return (int)e;
+    }
+    memset(b->h_blocks, 0, sizeof(HostBussiBatch) * n_items);
+    b->ws = ws;
+    ws->bussi_batches += 1;
+    *out = b;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
+{
+    if (!b)
+        return CAVMD_OK;
+    DeviceGuard guard(b->device);
+    // the kernels in flight read the table and write the blocks: let them finish (a capturing stream cannot be waited for)
+    if (b->sequence && !stream_capturing(b->last_stream))
+        (void)hipStreamSynchronize(b->last_stream);
+    if (b->d_rows)
+        (void)hipFree(b->d_rows);
+    if (b->d_order)
+        (void)hipFree(b->d_order);
+    if (b->d_state)
+        (void)hipFree(b->d_state);
+    if (b->h_blocks)
+        (void)hipHostFree(b->h_blocks);
+    if (b->ws)
+        b->ws->bussi_batches -= 1;
+    delete b;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_set_items(cavmd_bussi_batch* b, size_t first, size_t count, const cavmd_bussi_batch_item* h_items)
+{
+    if (!b || !h_items || count == 0 || first >= b->n || count > b->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = cavmd_bussi_batch_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    DeviceGuard guard(b->device);
+    if (b->sequence)
+    {
+        if (stream_capturing(b->last_stream))
+            return CAVMD_ERR_INVALID_VALUE;
+        CAVMD_HIP_TRY(hipStreamSynchronize(b->last_stream)); // steps in flight read the rows this call rewrites
+    }
+    // built aside and committed only after both copies went through (as cavmd_batch_set_items)
+    std::vector<cavmd_bussi_batch_item> items(b->items);
+    for (size_t i = 0; i < count; ++i)
+        items[first + i] = h_items[i];
+    const std::vector<unsigned> order = bussi_batch_order(items);
+    CAVMD_HIP_TRY(hipMemcpy(b->d_order, order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice));
+    const hipError_t e = hipMemcpy(b->d_rows + first, h_items, sizeof(BussiBatchRow) * count, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice); // the old order back
+        return (int)e;
+    }
+    b->items.swap(items);
+    b->order = order;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_bussi_batch_input* d_inputs)
+{
+    if (!b || !d_inputs || ((uintptr_t)d_inputs & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(b->device);
+    if (!b->captured && stream_capturing(stream))
+        b->captured = true;
+    b->sequence += 1;
+    hipLaunchKernelGGL(bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, stream, b->d_rows, b->d_order,
+                       reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state, b->h_blocks_dev);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+    {
+        b->sequence -= 1;
+        return st;
+    }
+    b->last_stream = stream;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_last_sequence(cavmd_bussi_batch* b, uint64_t* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = b->sequence;
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_read(cavmd_bussi_batch* b, cavmd_bussi_device_state* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    memset(out, 0, sizeof(*out) * b->n);
+    if (b->sequence == 0)
+        return CAVMD_OK;
+    DeviceGuard guard(b->device);
+    if (b->captured)
+    {
+        // graph replays: frozen sequence, unknown replay stream -> wait for the device and copy the device states
+        CAVMD_HIP_TRY(hipDeviceSynchronize());
+        CAVMD_HIP_TRY(hipMemcpy(out, b->d_state, sizeof(BussiDevice) * b->n, hipMemcpyDeviceToHost));
+    }
+    else
+    {
+        const uint64_t want = b->sequence;
+        for (size_t i = 0; i < b->n; ++i)
+        {
+            const HostBussiBatch* h = b->h_blocks + i;
+            for (;;)
+            {
+                if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want)
+                    break;
+                const hipError_t q = hipStreamQuery(b->last_stream);
+                if (q == hipErrorNotReady)
+                    continue;
+                if (q != hipSuccess)
+                    return (int)q;
+                if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) != want)
+                    return (int)hipErrorLaunchFailure; // a launch that never published
+                break;
+            }
+            bussi_state_out(out + i, h->state);
+        }
+    }
+    bool refused = false;
+    for (size_t i = 0; i < b->n; ++i)
+        if (out[i].refused != b->refused_seen[i])
+        {
+            b->refused_seen[i] = out[i].refused;
+            refused = true;
+        }
+    return refused ? CAVMD_ERR_BAD_PARAMS : CAVMD_OK; // "Bussi thermostat requires non-zero initial momenta."
+}
+
+int cavmd_bussi_batch_reset(cavmd_bussi_batch* b, void* stream_)
+{
+    if (!b)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(b->device);
+    // wait for the last step's stamps first so that the host copies can be reset consistently (not while it is being captured)
+    if (b->sequence && !b->captured)
+    {
+        std::vector<cavmd_bussi_device_state> unused(b->n);
+        const int st = cavmd_bussi_batch_read(b, unused.data());
+        if (st != CAVMD_OK && st != CAVMD_ERR_BAD_PARAMS)
+            return st;
+    }
+    CAVMD_HIP_TRY(hipMemsetAsync(b->d_state, 0, sizeof(BussiDevice) * b->n, stream));
+    for (size_t i = 0; i < b->n; ++i)
+        memset(&b->h_blocks[i].state, 0, sizeof(BussiDevice));
+    std::fill(b->refused_seen.begin(), b->refused_seen.end(), (uint64_t)0);
+    return CAVMD_OK;
+}
+
+int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_device_state** out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = reinterpret_cast<const cavmd_bussi_device_state*>(b->d_state);
     return CAVMD_OK;
 }
 

@@ -403,6 +403,83 @@ CAVMD_API int cavmd_bussi_device_read(cavmd_workspace* ws, cavmd_bussi_device_st
 /* reset_reservoir_energy() of the reference's Python class: zero the counters (ordered on `stream`). */
 CAVMD_API int cavmd_bussi_device_reset(cavmd_workspace* ws, void* stream);
 
+/* ---- the same translational step for a batch of independent small systems in ONE launch ------------------------------- */
+/* The thermostat half of "a batch of independent small systems" above: every replica of the production workload is
+ * thermostatted each step (src/BussiReservoirThermostat.h:43-98, 177-225), and cavmd_bussi_step_device costs two launches per
+ * system and cannot be captured.  A caller registers the velocity arrays of its B systems ONCE; cavmd_bussi_batch_step then
+ * performs the step of all of them with one kernel, one 256-thread workgroup per system (kinetic energy -> alpha -> counters
+ * -> velocities *= alpha), and takes the per-step random inputs from a row per item in DEVICE memory, so the launch may be
+ * captured into a hipGraph and still applies fresh variates on every replay.
+ * Equivalence: per item, velocities and state are bit for bit what cavmd_bussi_step_device gives that item alone with the same
+ * inputs, on a device with at least 64 compute units (there the single path sums one tile of 1024 members per workgroup, the
+ * order this kernel reproduces).  On a smaller device the batch is still a fixed-order compensated sum (within 2 ulp of the
+ * exact kinetic energy), with a tree different from the single path's.  Systems are independent: no workgroup waits for
+ * another one, hence no CAVMD_ERR_SYNC_TIMEOUT on this path.  Rotational degrees of freedom stay on the host path
+ * (cavmd_bussi_step). */
+typedef struct cavmd_bussi_batch_item
+{
+    cavmd_double4* d_vel;       /* HOOMD Scalar4 velocities, mass in .w; DEVICE pointer, 16-byte aligned */
+    const uint32_t* d_members;  /* device index list of the thermostatted group, or NULL = 0 .. n_members-1 */
+    uint32_t n_members;         /* 0 is legal: the item is never touched or counted; <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t reserved0;         /* must be 0 */
+    double dof_translational;
+    uint64_t reserved[4];       /* must be 0 */
+} cavmd_bussi_batch_item;       /* 64 B */
+typedef struct cavmd_bussi_batch_input /* one row per item, in DEVICE memory, owned by the caller */
+{
+    double normal_variate;      /* as cavmd_bussi_step_device */
+    double gamma_variate;
+    double c;                   /* exp(-deltaT / tau), 0 for tau == 0 */
+    double set_T;
+    uint64_t skip;              /* != 0: deltaT == 0, velocities and counters of this item untouched */
+    uint64_t reserved[3];
+} cavmd_bussi_batch_input;      /* 64 B */
+typedef struct cavmd_bussi_batch cavmd_bussi_batch; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * a null d_vel (with n_members > 0), a d_vel not 16-byte or a d_members not 4-byte aligned, reserved != 0, a negative or
+ * non-finite dof_translational; CAVMD_ERR_CAPACITY for n_members > CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_bussi_batch_item_check(const cavmd_bussi_batch_item* item);
+/* Fills one input row on the HOST from the arguments of cavmd_bussi_step_device, with the expression that call uses:
+ * c = tau != 0 ? exp(-deltaT / tau) : 0, skip = (deltaT == 0).  Needs no device.  The caller copies rows to its device array. */
+CAVMD_API int cavmd_bussi_batch_input_make(double deltaT, double set_T, double tau, double normal_variate,
+                                           double gamma_variate, cavmd_bussi_batch_input* row);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), copies the table to the device of `ws` (set-up
+ * time) and allocates one state per item on the device plus one 64-byte block per item in mapped pinned host memory.  All
+ * counters start at zero.  Destroying the workspace before its thermostat batches is an error: cavmd_destroy answers
+ * CAVMD_ERR_INVALID_VALUE and frees nothing while one is alive.  Without a device there is no workspace, hence no batch. */
+CAVMD_API int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bussi_batch_item* h_items,
+                                       cavmd_bussi_batch** out);
+/* Synchronises the stream of the batch's last step (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b);
+/* Rewrites rows first .. first + count - 1 from HOST memory (a reallocated velocity array, another group) after synchronising
+ * the stream of the last step; nothing is changed if a row is refused; the items' counters are kept.
+ * CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the batch. */
+CAVMD_API int cavmd_bussi_batch_set_items(cavmd_bussi_batch* b, size_t first, size_t count,
+                                          const cavmd_bussi_batch_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait.  d_inputs: n_items rows
+ * in DEVICE memory (CAVMD_ERR_INVALID_VALUE if null or not 8-byte aligned), read by the kernel when it RUNS.  May be captured
+ * into a hipGraph: a replay reads whatever d_inputs holds at that moment, so the caller refreshes that buffer, in stream
+ * order, between replays; the pointer itself is frozen at capture.  An item whose row has skip != 0, and an item with
+ * n_members == 0, is left alone: velocities and counters untouched, nothing counted.  Workgroups start in order of n_members
+ * descending (ties in item order); states stay indexed by item.  One batch serves one host thread and one stream at a time. */
+CAVMD_API int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream, const cavmd_bussi_batch_input* d_inputs);
+/* Number of steps enqueued on b (0 before any).  No wait. */
+CAVMD_API int cavmd_bussi_batch_last_sequence(cavmd_bussi_batch* b, uint64_t* out);
+/* out = n_items states after the last enqueued step: waits for the n_items stamps of THAT step only (every workgroup stamps
+ * its item's host block after its velocity stores have been issued; a skipped item is stamped too and keeps its earlier
+ * state), or for that step's stream to be idle; never a stream synchronisation.  Before any step: zeros.
+ * CAVMD_ERR_BAD_PARAMS, ONCE, if a step of any item was refused for zero kinetic energy since the last read; `out` is filled
+ * all the same (per item: `refused`).  Once the batch has seen a capturing stream the stamps cannot be trusted (a replay
+ * carries the sequence of its capture): the read then copies the device states behind a hipDeviceSynchronize, as
+ * cavmd_batch_results_read does. */
+CAVMD_API int cavmd_bussi_batch_read(cavmd_bussi_batch* b, cavmd_bussi_device_state* out);
+/* Zero all counters of all items (ordered on `stream`). */
+CAVMD_API int cavmd_bussi_batch_reset(cavmd_bussi_batch* b, void* stream);
+/* Device address of the n_items states (indexed by item; six 8-byte words each: reservoir, instantaneous, alpha, kinetic
+ * energy, steps, refused -- the layout of cavmd_bussi_device_state), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_device_state** out);
+
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
 CAVMD_API int cavmd_profile_enable(cavmd_workspace* ws, int on);
