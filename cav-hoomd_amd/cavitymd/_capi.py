@@ -89,6 +89,21 @@ class BussiBatchInput(ctypes.Structure):
                 ("set_T", ctypes.c_double), ("skip", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3)]
 
 
+class Record(ctypes.Structure):
+    """cavmd_record (128 bytes): one row of a recorder's time series."""
+    _fields_ = [("call", ctypes.c_uint64), ("eval_sequence", ctypes.c_uint64), ("energy", ctypes.c_double * 3),
+                ("total_dipole", ctypes.c_double * 3), ("q", ctypes.c_double * 3), ("cavity_kinetic", ctypes.c_double),
+                ("cavity_temperature", ctypes.c_double), ("kinetic_energy", ctypes.c_double),
+                ("force_mass_sum", ctypes.c_double), ("reserved", ctypes.c_double)]
+
+
+class RecorderItem(ctypes.Structure):
+    """cavmd_recorder_item (64 bytes): one system of a recorder; all four pointers are DEVICE pointers."""
+    _fields_ = [("d_result", ctypes.c_void_p), ("d_vel", ctypes.c_void_p), ("d_net_force", ctypes.c_void_p),
+                ("d_members", ctypes.c_void_p), ("N", ctypes.c_uint32), ("n_members", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64 * 3)]
+
+
 BATCH_MAX_ITEMS = 65536
 BATCH_MAX_ITEM_N = 65536
 
@@ -118,8 +133,18 @@ def bussi_batch_item(vel_ptr, members_ptr, n_members, dof_translational) -> "Bus
     return it
 
 
+def recorder_item(result_ptr, vel_ptr, net_force_ptr, members_ptr, N, n_members) -> "RecorderItem":
+    it = RecorderItem()
+    it.d_result, it.d_vel, it.d_net_force, it.d_members = result_ptr or None, vel_ptr or None, net_force_ptr or None, \
+        members_ptr or None
+    it.N, it.n_members = int(N), int(n_members)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_recorder_item_check", "cavmd_recorder_create", "cavmd_recorder_destroy", "cavmd_recorder_set_items",
+    "cavmd_recorder_record", "cavmd_recorder_rows", "cavmd_recorder_read", "cavmd_recorder_reset", "cavmd_recorder_device_ptr",
     "cavmd_bussi_batch_item_check", "cavmd_bussi_batch_input_make", "cavmd_bussi_batch_create", "cavmd_bussi_batch_destroy",
     "cavmd_bussi_batch_set_items", "cavmd_bussi_batch_step", "cavmd_bussi_batch_last_sequence", "cavmd_bussi_batch_read",
     "cavmd_bussi_batch_reset", "cavmd_bussi_batch_state_device_ptr",
@@ -275,6 +300,24 @@ def _declare(lib):
         lib.cavmd_bussi_batch_reset.restype = ci
         lib.cavmd_bussi_batch_state_device_ptr.argtypes = [vp, P(vp)]
         lib.cavmd_bussi_batch_state_device_ptr.restype = ci
+        lib.cavmd_recorder_item_check.argtypes = [P(RecorderItem)]
+        lib.cavmd_recorder_item_check.restype = ci
+        lib.cavmd_recorder_create.argtypes = [vp, sz, P(RecorderItem), sz, u64, dbl, P(vp)]
+        lib.cavmd_recorder_create.restype = ci
+        lib.cavmd_recorder_destroy.argtypes = [vp]
+        lib.cavmd_recorder_destroy.restype = ci
+        lib.cavmd_recorder_set_items.argtypes = [vp, sz, sz, P(RecorderItem)]
+        lib.cavmd_recorder_set_items.restype = ci
+        lib.cavmd_recorder_record.argtypes = [vp, vp]
+        lib.cavmd_recorder_record.restype = ci
+        lib.cavmd_recorder_rows.argtypes = [vp, vp, vp]
+        lib.cavmd_recorder_rows.restype = ci
+        lib.cavmd_recorder_read.argtypes = [vp, vp, sz, sz, u64, sz, vp]
+        lib.cavmd_recorder_read.restype = ci
+        lib.cavmd_recorder_reset.argtypes = [vp, vp]
+        lib.cavmd_recorder_reset.restype = ci
+        lib.cavmd_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
+        lib.cavmd_recorder_device_ptr.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -329,6 +372,7 @@ def make_params(omegac: float, couplstr: float, phmass: float = 1.0) -> Params:
 _deferred = []
 _deferred_batches = []  # the same for batches (cavmd_batch_destroy)
 _deferred_bussi_batches = []  # and for thermostat batches (cavmd_bussi_batch_destroy)
+_deferred_recorders = []  # and for recorders (cavmd_recorder_destroy)
 
 
 def _capturing() -> bool:
@@ -341,7 +385,10 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
-    while _deferred_bussi_batches:  # batches before the workspaces they were created from
+    while _deferred_recorders:  # recorders and batches before the workspaces they were created from
+        lib, h = _deferred_recorders.pop()
+        lib.cavmd_recorder_destroy(h)
+    while _deferred_bussi_batches:
         lib, h = _deferred_bussi_batches.pop()
         lib.cavmd_bussi_batch_destroy(h)
     while _deferred_batches:
@@ -372,11 +419,11 @@ class Workspace:
             if _capturing():
                 _deferred.append((self._lib, self._h))
             else:
-                if _deferred_batches or _deferred_bussi_batches:  # batches deferred during a capture go before any workspace
+                if _deferred_batches or _deferred_bussi_batches or _deferred_recorders:  # batches deferred during a capture go before any workspace
                     _destroy_deferred()
                 self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -571,7 +618,7 @@ class Batch:
             else:
                 self._lib.cavmd_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -664,7 +711,7 @@ class BussiBatch:
             else:
                 self._lib.cavmd_bussi_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -707,3 +754,102 @@ class BussiBatch:
         p = ctypes.c_void_p()
         check(self._lib.cavmd_bussi_batch_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_bussi_batch_state_device_ptr")
         return int(p.value)
+
+
+RECORD_DTYPE_FIELDS = [("call", "<u8"), ("eval_sequence", "<u8"), ("energy", "<f8", (3,)), ("total_dipole", "<f8", (3,)),
+                       ("q", "<f8", (3,)), ("cavity_kinetic", "<f8"), ("cavity_temperature", "<f8"), ("kinetic_energy", "<f8"),
+                       ("force_mass_sum", "<f8"), ("reserved", "<f8")]
+
+
+def record_dtype():
+    """numpy structured dtype with the layout of cavmd_record (128 bytes)."""
+    import numpy as np
+    return np.dtype(RECORD_DTYPE_FIELDS)
+
+
+def recorder_item_check(item: RecorderItem) -> int:
+    """Status cavmd_recorder_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_recorder_item_check(ctypes.byref(item)))
+
+
+class Recorder:
+    """Owns one cavmd_recorder: the per-step observables of B independent small systems appended, by ONE kernel launch per
+    call, to a time series in device memory whose write position lives on the device (a graph replay appends a new row).
+    Keeps its workspace alive."""
+
+    def __init__(self, workspace: Workspace, items, capacity: int, period: int, kB: float):
+        self._ws = workspace
+        self._lib = workspace._lib
+        items = list(items)
+        self.n_items = len(items)
+        self.capacity, self.period, self.kB = int(capacity), int(period), float(kB)
+        self.sizes = [max(int(it.N), int(it.n_members)) for it in items]
+        arr = (RecorderItem * max(self.n_items, 1))(*items)
+        self._h = ctypes.c_void_p()
+        if self.capacity < 0 or self.period < 0:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_recorder_create")
+        check(self._lib.cavmd_recorder_create(workspace.handle, self.n_items, arr, self.capacity, self.period, self.kB,
+                                              ctypes.byref(self._h)), "cavmd_recorder_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def launch_order(self):
+        """Item indices in the order their workgroups start (max(N, n_members) descending, stable), predicted by
+        ``batch_launch_order``."""
+        return batch_launch_order(self.sizes)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if _capturing():
+                _deferred_recorders.append((self._lib, self._h))
+            else:
+                self._lib.cavmd_recorder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
+            _destroy_deferred()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_items(self, first: int, items) -> None:
+        items = list(items)
+        arr = (RecorderItem * max(len(items), 1))(*items)
+        check(self._lib.cavmd_recorder_set_items(self._h, int(first), len(items), arr), "cavmd_recorder_set_items")
+        for k, it in enumerate(items):
+            self.sizes[first + k] = max(int(it.N), int(it.n_members))
+
+    def record(self, stream: int = 0) -> None:
+        """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
+        check(self._lib.cavmd_recorder_record(self._h, ctypes.c_void_p(stream)), "cavmd_recorder_record")
+
+    def rows(self, stream: int = 0):
+        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=np.uint64)
+        check(self._lib.cavmd_recorder_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
+              "cavmd_recorder_rows")
+        return out
+
+    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
+        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
+        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_record."""
+        import numpy as np
+        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=record_dtype())
+        check(self._lib.cavmd_recorder_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items), int(first_row),
+                                            int(n_rows), ctypes.c_void_p(out.ctypes.data)), "cavmd_recorder_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_recorder_reset(self._h, ctypes.c_void_p(stream)), "cavmd_recorder_reset")
+
+    def device_ptr(self):
+        """(records, rows): device addresses of the series (item-major, `capacity` records each) and of the row counters."""
+        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.cavmd_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)), "cavmd_recorder_device_ptr")
+        return int(rec.value), int(rows.value)

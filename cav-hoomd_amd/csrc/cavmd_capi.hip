@@ -157,6 +157,7 @@ struct cavmd_workspace
     uint64_t bussi_refused_seen = 0;  // refusals already reported to the caller
     hipStream_t bussi_stream = nullptr; // stream of the last enqueued step: the one whose idleness ends a wait for its flag
     unsigned bussi_batches = 0;         // live cavmd_bussi_batch objects created from this workspace (cavmd_destroy refuses)
+    unsigned recorders = 0;             // live cavmd_recorder objects created from this workspace (the same)
 };
 
 namespace
@@ -498,6 +499,8 @@ int cavmd_destroy(cavmd_workspace* ws)
     if (!ws)
         return CAVMD_OK;
     if (ws->bussi_batches != 0) // a thermostat batch outlives nothing of its workspace: destroy the batches first
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->recorders != 0)     // nor does a recorder
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -2519,6 +2522,278 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
     if (!b || !out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = reinterpret_cast<const cavmd_bussi_device_state*>(b->d_state);
+    return CAVMD_OK;
+}
+
+} // extern "C"
+
+// ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
+struct cavmd_recorder
+{
+    cavmd_workspace* ws = nullptr;
+    int device = -1;
+    size_t n = 0;
+    size_t capacity = 0;
+    uint64_t period = 1;
+    double kB = 0.0;
+    std::vector<cavmd_recorder_item> items; // host copy of the table, as the caller gave it
+    std::vector<unsigned> order;            // items by max(N, n_members) descending, stable
+    RecorderRow* d_rows = nullptr;
+    unsigned* d_order = nullptr;
+    cavmd_record* d_series = nullptr;       // n x capacity records, item-major
+    uint64_t* d_counters = nullptr;         // kRecCounters arrays of n words: rows, calls, phase, slot
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;                  // some record call was enqueued: last_stream means something
+};
+
+namespace
+{
+constexpr size_t kRecorderMaxBytes = (size_t)1 << 30;
+static_assert(sizeof(cavmd_record) == 128 && offsetof(cavmd_record, energy) == 16 && offsetof(cavmd_record, cavity_kinetic) == 88,
+              "record layout");
+static_assert(sizeof(cavmd_recorder_item) == sizeof(RecorderRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_recorder_item, d_result) == offsetof(RecorderRow, res)
+                  && offsetof(cavmd_recorder_item, d_vel) == offsetof(RecorderRow, vel2)
+                  && offsetof(cavmd_recorder_item, d_net_force) == offsetof(RecorderRow, force2)
+                  && offsetof(cavmd_recorder_item, d_members) == offsetof(RecorderRow, members)
+                  && offsetof(cavmd_recorder_item, N) == offsetof(RecorderRow, N)
+                  && offsetof(cavmd_recorder_item, n_members) == offsetof(RecorderRow, n_members),
+              "recorder item layout");
+static_assert(CAVMD_BATCH_MAX_ITEM_N <= kRecorderMaxTiles * 256 * kRecorderUnroll, "one LDS partial per tile");
+
+std::vector<unsigned> recorder_order(const std::vector<cavmd_recorder_item>& items)
+{
+    std::vector<unsigned> order(items.size());
+    for (size_t i = 0; i < items.size(); ++i)
+        order[i] = (unsigned)i;
+    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) {
+        return std::max(items[x].N, items[x].n_members) > std::max(items[y].N, items[y].n_members);
+    });
+    return order;
+}
+
+// waits for what was recorded on `stream`; a capturing stream cannot be waited for
+int recorder_sync(cavmd_recorder* r, hipStream_t stream)
+{
+    if (stream_capturing(stream))
+        return CAVMD_ERR_INVALID_VALUE;
+    CAVMD_HIP_TRY(hipStreamSynchronize(stream));
+    return CAVMD_OK;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_recorder_item_check(const cavmd_recorder_item* it)
+{
+    if (!it || !it->d_result)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 3; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_result & 15) || ((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_net_force & 15)
+        || ((uintptr_t)it->d_members & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N || it->n_members > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recorder_item* h_items, size_t capacity,
+                          uint64_t period, double kB, cavmd_recorder** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || capacity == 0 || period == 0 || !(kB > 0.0)
+        || !std::isfinite(kB))
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const int st = cavmd_recorder_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    if (capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items)
+        return CAVMD_ERR_CAPACITY;
+    cavmd_recorder* r = new (std::nothrow) cavmd_recorder();
+    if (!r)
+        return (int)hipErrorOutOfMemory;
+    r->device = ws->device;
+    r->n = n_items;
+    r->capacity = capacity;
+    r->period = period;
+    r->kB = kB;
+    r->items.assign(h_items, h_items + n_items);
+    r->order = recorder_order(r->items);
+
+    DeviceGuard guard(r->device);
+    const size_t series_bytes = sizeof(cavmd_record) * n_items * capacity;
+    const size_t counter_bytes = sizeof(uint64_t) * kRecCounters * n_items;
+    hipError_t e = hipMalloc((void**)&r->d_rows, sizeof(RecorderRow) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_rows, r->items.data(), sizeof(RecorderRow) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_order, sizeof(unsigned) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_series, series_bytes);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_series, 0, series_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_counters, counter_bytes);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_counters, 0, counter_bytes);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
+    if (e != hipSuccess)
+    {
+        cavmd_recorder_destroy(r);
+        return (int)e;
+    }
+    r->ws = ws;
+    ws->recorders += 1;
+    *out = r;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_destroy(cavmd_recorder* r)
+{
+    if (!r)
+        return CAVMD_OK;
+    DeviceGuard guard(r->device);
+    // the kernels in flight read the table and write the series: let them finish (a capturing stream cannot be waited for)
+    if (r->recorded && !stream_capturing(r->last_stream))
+        (void)hipStreamSynchronize(r->last_stream);
+    if (r->d_rows)
+        (void)hipFree(r->d_rows);
+    if (r->d_order)
+        (void)hipFree(r->d_order);
+    if (r->d_series)
+        (void)hipFree(r->d_series);
+    if (r->d_counters)
+        (void)hipFree(r->d_counters);
+    if (r->ws)
+        r->ws->recorders -= 1;
+    delete r;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, const cavmd_recorder_item* h_items)
+{
+    if (!r || !h_items || count == 0 || first >= r->n || count > r->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = cavmd_recorder_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    DeviceGuard guard(r->device);
+    if (r->recorded)
+    {
+        if (stream_capturing(r->last_stream))
+            return CAVMD_ERR_INVALID_VALUE;
+        CAVMD_HIP_TRY(hipStreamSynchronize(r->last_stream)); // record calls in flight read the rows this call rewrites
+    }
+    // built aside and committed only after both copies went through (as cavmd_bussi_batch_set_items)
+    std::vector<cavmd_recorder_item> items(r->items);
+    for (size_t i = 0; i < count; ++i)
+        items[first + i] = h_items[i];
+    const std::vector<unsigned> order = recorder_order(items);
+    CAVMD_HIP_TRY(hipMemcpy(r->d_order, order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice));
+    const hipError_t e = hipMemcpy(r->d_rows + first, h_items, sizeof(RecorderRow) * count, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice); // the old order back
+        return (int)e;
+    }
+    r->items.swap(items);
+    r->order = order;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
+{
+    if (!r)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(r->device);
+    hipLaunchKernelGGL(recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows, r->d_order,
+                       (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series, r->d_counters);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    r->last_stream = stream;
+    r->recorded = true;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
+{
+    if (!r || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = recorder_sync(r, (hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(hipMemcpy(out, r->d_counters + (size_t)kRecRows * r->n, sizeof(uint64_t) * r->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_read(cavmd_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
+                        cavmd_record* out)
+{
+    if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = recorder_sync(r, (hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<uint64_t> rows(n_items);
+    CAVMD_HIP_TRY(hipMemcpy(rows.data(), r->d_counters + (size_t)kRecRows * r->n + first_item, sizeof(uint64_t) * n_items,
+                            hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_items; ++k)
+    {
+        if (rows[k] == 0)
+            return CAVMD_ERR_NOT_COMPUTED;
+        if (first_row >= rows[k] || n_rows > rows[k] - first_row)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (rows[k] > r->capacity && first_row < rows[k] - r->capacity)
+            return CAVMD_ERR_EXPIRED;
+    }
+    // row j of an item sits in slot j % capacity of that item's stretch: at most two runs of slots, each fetched for all the
+    // items with one strided copy
+    const size_t rec = sizeof(cavmd_record);
+    const size_t slot0 = (size_t)(first_row % r->capacity);
+    const size_t run0 = std::min(n_rows, r->capacity - slot0);
+    const cavmd_record* src = r->d_series + first_item * r->capacity;
+    CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, r->capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
+    if (run0 < n_rows)
+        CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, r->capacity * rec, (n_rows - run0) * rec, n_items,
+                                  hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_reset(cavmd_recorder* r, void* stream_)
+{
+    if (!r)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    CAVMD_HIP_TRY(hipMemsetAsync(r->d_counters, 0, sizeof(uint64_t) * kRecCounters * r->n, (hipStream_t)stream_));
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows)
+{
+    if (!r || (!records && !rows))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (records)
+        *records = r->d_series;
+    if (rows)
+        *rows = r->d_counters + (size_t)kRecRows * r->n;
     return CAVMD_OK;
 }
 

@@ -25,7 +25,8 @@
 // Files: cavmd_reduce.hpp (double-double arithmetic, DPP, block trees), cavmd_force_kernels.hpp (the force path),
 //        cavmd_batch_kernel.hpp (many small systems in one launch, one workgroup each),
 //        cavmd_persistent_kernel.hpp (the single-launch evaluation), cavmd_observable_kernels.hpp (rows f2-f4),
-//        cavmd_bussi_batch_kernel.hpp (the thermostat step of many small systems in one launch, one workgroup each).
+//        cavmd_bussi_batch_kernel.hpp (the thermostat step of many small systems in one launch, one workgroup each),
+//        cavmd_recorder_kernel.hpp (their per-step observables appended to a time series in device memory, one launch).
 #pragma once
 
 #include "cavmd_reduce.hpp"
@@ -34,3 +35,4 @@
 #include "cavmd_persistent_kernel.hpp"
 #include "cavmd_observable_kernels.hpp"
 #include "cavmd_bussi_batch_kernel.hpp"
+#include "cavmd_recorder_kernel.hpp"

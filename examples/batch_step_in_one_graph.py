@@ -1,5 +1,6 @@
-"""Force batch + thermostat batch of B replicas captured into ONE graph: two kernels per step for all replicas, and the
-thermostat stays stochastic on replay because its variates are read from device memory.
+"""Force batch + recorder + thermostat batch of B replicas captured into ONE graph: three kernels per step for all replicas.
+The thermostat stays stochastic on replay because its variates are read from device memory, and the recorder appends one row
+per replica and replay to a time series in device memory, read once after the replays.
 
     python examples/batch_step_in_one_graph.py [B] [steps]
 
@@ -32,6 +33,7 @@ def main():
         v[:, :3] = rng.normal(0.0, 1e-3, (pd.getN(), 3))
         velocities.append(torch.from_numpy(v).cuda())
     forces = cavitymd.CavityForceBatch(sysdefs, cfg["params"])
+    recorder = cavitymd.BatchRecorder(forces, velocities, net_forces=forces.forces, capacity=max(steps, 1))
     thermostat = cavitymd.BussiReservoirBatch(kT=1e-6, tau=0.5)
     thermostat.attach(velocities, translational_dof=3.0 * 501 - 3.0)
 
@@ -42,6 +44,7 @@ def main():
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         forces.compute(0)                                                  # one kernel: the cavity force of all B systems
+        recorder.record()                                                  # one kernel: one row per system into the series
         thermostat.draw_inputs(0, dt)                                      # fresh variates, drawn on the device
         thermostat.step_async()                                            # one kernel: the thermostat step of all B systems
     for _ in range(steps):
@@ -49,6 +52,11 @@ def main():
     state = thermostat.device_state()                                      # after a capture: behind a device synchronisation
     print(f"B={B}: {state[0].steps} thermostat steps per system from one captured graph; "
           f"last alpha of system 0 = {state[0].last_alpha:.6f}, reservoir = {thermostat.total_reservoir_energy[0]:.3e}")
+    series = recorder.read()                                               # (B, steps) rows, one copy after all the replays
+    print(f"recorded rows per system: {recorder.rows().tolist()}")
+    for label, row in (("first", series[0, 0]), ("last", series[0, -1])):
+        print(f"system 0, {label} row (call {row['call']}): energies {row['energy'].tolist()}, "
+              f"cavity T = {row['cavity_temperature']:.6e} K, kinetic energy = {row['kinetic_energy']:.6e}")
 
 
 if __name__ == "__main__":

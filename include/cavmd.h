@@ -23,6 +23,10 @@
  *                                                                   cavmd_bussi_step_device (the step without a host round trip)
  *   the replica loop (one process, replicas one after the other)
  *                               examples/05_advanced_run.py:1570-1612    cavmd_batch_create / cavmd_batch_compute (all in one launch)
+ *   EnergyTracker / CavityModeTracker / DipoleAutocorrelation / AdaptiveTimestepUpdater, per step and replica
+ *                               src/cavitymd/analysis.py:425-, 1285-1417, 1424-; src/cavitymd/simulation.py:66-92
+ *                                                                   cavmd_recorder_create / cavmd_recorder_record /
+ *                                                                   cavmd_recorder_read (a time series in device memory)
  *   CavityForceCompute::computeForces (the CPU semantics both follow)
  *                               src/CavityForceCompute.cc:134-208   (semantic contract, see below)
  *
@@ -479,6 +483,90 @@ CAVMD_API int cavmd_bussi_batch_reset(cavmd_bussi_batch* b, void* stream);
 /* Device address of the n_items states (indexed by item; six 8-byte words each: reservoir, instantaneous, alpha, kinetic
  * energy, steps, refused -- the layout of cavmd_bussi_device_state), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_device_state** out);
+
+/* ---- per-step observables of a batch, recorded on the device: the third kernel of the batched step -------------------- */
+/* What the reference's trackers write every step for every replica -- EnergyTracker (src/cavitymd/analysis.py:425-),
+ * CavityModeTracker (:1285-1417), DipoleAutocorrelation (:1424-) and the reduction of AdaptiveTimestepUpdater
+ * (src/cavitymd/simulation.py:66-92) -- as ONE launch for all systems that appends one 128-byte record per system to a time
+ * series kept in DEVICE memory.  The write position is kept on the device too, so a hipGraph replay appends a NEW row each
+ * time: the series is how a captured {cavmd_batch_compute, cavmd_recorder_record, cavmd_bussi_batch_step} loop is observed
+ * (cavmd_batch_results_at / cavmd_batch_energies_at cannot tell replays apart, see above).  The host reads the series when it
+ * likes -- every few thousand steps, or once at the end -- behind a synchronisation of the stream it names; nothing is mapped,
+ * nothing is polled.  Systems are independent: no workgroup waits for another one, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ * Equivalences, per item and recorded row, bit for bit:
+ *   - energy, total_dipole, q, eval_sequence: the bytes of the cavmd_result block d_result points at when the kernel runs;
+ *   - cavity_kinetic, cavity_temperature: cavmd_cavity_mode's out[0], out[3] for that system alone, and
+ *     cavity_kinetic + energy[0] is its out[2] (one IEEE addition on either side);
+ *   - kinetic_energy = cavmd_kinetic_energy, force_mass_sum = cavmd_force_mass_sum for that item alone, on a device with at
+ *     least 64 compute units (there the single paths sum one tile of 1024 entries per workgroup, the order this kernel
+ *     reproduces; same condition and reason as for cavmd_bussi_batch_step).  On a smaller device they are still fixed-order
+ *     compensated sums within 2 ulp of the exact value, with a tree different from the single paths'. */
+typedef struct cavmd_record              /* 128 B, one per item and recorded call */
+{
+    uint64_t call;            /* 1-based index of the cavmd_recorder_record call (of this item) that wrote the row */
+    uint64_t eval_sequence;   /* cavmd_result.sequence of the block it read (frozen under replay: diagnostic only) */
+    double energy[3];         /* harmonic, coupling, dipole-self: bytes of cavmd_result.energy */
+    double total_dipole[3];   /* bytes of cavmd_result.total_dipole (DipoleAutocorrelation's observable) */
+    double q[3];              /* bytes of cavmd_result.q */
+    double cavity_kinetic;    /* CavityModeTracker: KE; its PE is energy[0], its total is cavity_kinetic + energy[0] */
+    double cavity_temperature;
+    double kinetic_energy;    /* of the item's group, as cavmd_kinetic_energy */
+    double force_mass_sum;    /* as cavmd_force_mass_sum; dt = sqrt(tol / S) stays the caller's */
+    double reserved;          /* 0 */
+} cavmd_record;
+
+typedef struct cavmd_recorder_item       /* 64 B; all pointers DEVICE pointers */
+{
+    const cavmd_result* d_result;        /* required: e.g. cavmd_batch_results_device_ptr + item */
+    const cavmd_double4* d_vel;          /* Scalar4 velocities, mass in .w, of the system d_result belongs to (the photon's
+                                            entry is read at its photon_idx); NULL: the three velocity columns are 0 */
+    const cavmd_double4* d_net_force;    /* Scalar4 net force; NULL (or d_vel NULL): force_mass_sum is 0 */
+    const uint32_t* d_members;           /* group of kinetic_energy, or NULL = 0 .. n_members-1 */
+    uint32_t N;                          /* particles covered by force_mass_sum; <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t n_members;                  /* <= CAVMD_BATCH_MAX_ITEM_N; 0 is legal (kinetic_energy 0) */
+    uint64_t reserved[3];                /* must be 0 */
+} cavmd_recorder_item;
+typedef struct cavmd_recorder cavmd_recorder; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * a null d_result, a d_result / d_vel / d_net_force not 16-byte or a d_members not 4-byte aligned, reserved != 0;
+ * CAVMD_ERR_CAPACITY for N or n_members above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_recorder_item_check(const cavmd_recorder_item* item);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), copies the table to the device of `ws` (set-up time)
+ * and allocates n_items x capacity records plus the per-item counters in device memory, all zero.  Every `period`-th call of
+ * cavmd_recorder_record writes a row (period 1: every call); an item keeps its last `capacity` rows.  capacity >= 1,
+ * period >= 1, kB > 0 and finite (Hartree/K, as cavmd_cavity_mode), else CAVMD_ERR_INVALID_VALUE; CAVMD_ERR_CAPACITY if the
+ * series would exceed 1 GiB.  cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while a recorder of the
+ * workspace is alive.  Without a device there is no workspace, hence no recorder. */
+CAVMD_API int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recorder_item* h_items, size_t capacity,
+                                    uint64_t period, double kB, cavmd_recorder** out);
+/* Synchronises the stream of the last cavmd_recorder_record call (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_recorder_destroy(cavmd_recorder* r);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last record call; nothing is
+ * changed if a row is refused; counters and series are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured,
+ * and for a range outside the batch. */
+CAVMD_API int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, const cavmd_recorder_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait.  May be captured into a
+ * hipGraph, and a replay appends like an eager call: every item's call counter moves, and on every period-th call the item
+ * writes row number `rows` into slot rows % capacity of its series and moves `rows`.  The kernel reads the result blocks, the
+ * velocities and the net forces as they are when it RUNS and writes nothing but the series and the counters.  Workgroups
+ * start in order of max(N, n_members) descending (ties in item order).  One recorder serves one stream at a time. */
+CAVMD_API int cavmd_recorder_record(cavmd_recorder* r, void* stream);
+/* Synchronises `stream` (the stream the record calls, or the graph that holds them, ran on), then out[i] = rows written by
+ * item i since creation / the last reset.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
+CAVMD_API int cavmd_recorder_rows(cavmd_recorder* r, void* stream, uint64_t* out);
+/* Synchronises `stream`, then out[k * n_rows + j] = row first_row + j (0-based count of RECORDED rows) of item first_item + k.
+ * CAVMD_ERR_NOT_COMPUTED if an item asked for has never recorded, CAVMD_ERR_INVALID_VALUE for rows at or beyond the item's
+ * `rows`, n_rows or n_items 0, items outside the batch and while `stream` is being captured, CAVMD_ERR_EXPIRED if a
+ * requested row has been overwritten (row < rows - capacity).  It never looks at a sequence stamp, so it works the same
+ * before, between and after the replays of a graph. */
+CAVMD_API int cavmd_recorder_read(cavmd_recorder* r, void* stream, size_t first_item, size_t n_items, uint64_t first_row,
+                                  size_t n_rows, cavmd_record* out);
+/* Zero all counters of all items (ordered on `stream`): the next recorded row is row 0, written by call 1. */
+CAVMD_API int cavmd_recorder_reset(cavmd_recorder* r, void* stream);
+/* Device addresses of the series (item-major: record j of item i at records[i * capacity + j % capacity]) and of the n_items
+ * row counters, for consumers that stay on the GPU.  Either out pointer may be NULL. */
+CAVMD_API int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows);
 
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
