@@ -508,7 +508,12 @@ template <int NT>
 __device__ __forceinline__ void store_chunk(v2d* p, v2d v)
 {
     if (NT == 2)
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+    {
+        // The hardware reads the data registers of a store wider than 64 bits up to two wait states after issue.  hipcc pads
+        // its own stores but does not look into an asm statement, and may write v's registers in the very next
+        // instruction: the pad (s_nop 1 = two wait states) ends the string.
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+    }
     else if (NT == 1)
         __builtin_nontemporal_store(v, p);
     else
