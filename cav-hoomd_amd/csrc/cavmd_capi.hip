@@ -140,6 +140,8 @@ struct cavmd_workspace
     double* h_rho = nullptr; // pinned
     hipStream_t rho_stream = nullptr;
     bool rho_computed = false;
+    int rho_last_mapping = -1; // what the last cavmd_density_field call launched: mapping 0..3 after the automatic rule,
+    int rho_last_blocks = -1;  // and the grid's x extent, which is also the fold's nblocks (-1: no call yet); read-only tunables
     double* d_mode = nullptr;
     HostMode* h_mode = nullptr;     // pinned, mapped, coherent: cavity_mode_kernel publishes here
     HostMode* h_mode_dev = nullptr;
@@ -1191,6 +1193,8 @@ int cavmd_density_field(cavmd_workspace* ws, void* stream_, size_t N, const doub
     CAVMD_HIP_TRY(hipGetLastError());
     ws->rho_stream = stream;
     ws->rho_computed = true;
+    ws->rho_last_mapping = lp;
+    ws->rho_last_blocks = (int)gb;
     return CAVMD_OK;
 }
 
@@ -1813,6 +1817,10 @@ int cavmd_get_tunable(cavmd_workspace* ws, const char* name, int* value)
         *value = ws->reduce_unroll;
     else if (!strcmp(name, "rho_lane_particle"))
         *value = ws->rho_lane_particle;
+    else if (!strcmp(name, "rho_last_mapping"))
+        *value = ws->rho_last_mapping;
+    else if (!strcmp(name, "rho_last_blocks"))
+        *value = ws->rho_last_blocks;
     else if (!strcmp(name, "persistent_lds_kb"))
         *value = ws->persistent_lds_kb;
     else if (!strcmp(name, "persistent_balanced"))

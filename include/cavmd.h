@@ -627,6 +627,10 @@ CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap
  *                                  demand -- and the length of the next pause in evaluations
  *   "rho_lane_particle"    -1..3   density-field mapping: 0 lane = wavevector, 1 / 2 / 3 lane = particle with 25 / 10 / 5
  *                                  wavevectors per chunk, -1 auto by n_k
+ *   "rho_last_mapping"     (read only)  the mapping the last cavmd_density_field call used, 0..3, after the automatic rule;
+ *                                  -1 before the first call
+ *   "rho_last_blocks"      (read only)  the x extent of the grid that call launched, which is also the number of partial
+ *                                  blocks its fold summed; -1 before the first call
  *   "persistent_lds_kb"    0..156  LDS budget per block of the single-launch kernel in KiB (0 = default); the charges of tiles
  *                                  beyond it are read a second time
  *   "result_history"       2..16384 slots of the result ring read by cavmd_result_at (default 64, 256 B each).  Setting it

@@ -63,6 +63,19 @@ def test_version_and_error_strings(capi):
     assert capi.error_string(-99) == "unknown cavmd status"
 
 
+def test_read_only_tunables_are_documented_and_not_settable(capi):
+    """The names cavmd_get_tunable serves but cavmd_set_tunable refuses: documented as read only in the header, present in
+    the library, and absent from the setter's chain of names in the source."""
+    text = open(HEADER).read()
+    src = open(os.path.join(os.path.dirname(capi.LIB_PATH), "cavmd_capi.hip")).read()
+    setter = src[src.index("int cavmd_set_tunable("):src.index("int cavmd_get_tunable(")]
+    getter = src[src.index("int cavmd_get_tunable("):src.index("int cavmd_device_info(")]
+    blob = open(capi.LIB_PATH, "rb").read()
+    for name in ("persistent_suspended", "rho_last_mapping", "rho_last_blocks"):
+        assert re.search(r'"%s"\s+\(read only\)' % name, text), name
+        assert name.encode() in blob and '"%s"' % name in getter and '"%s"' % name not in setter, name
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_device_is_a_loud_error_not_a_fallback(capi):
     with pytest.raises(capi.CavmdError) as e:
