@@ -14,11 +14,12 @@ from .history import EnergyHistory
 from .batch import BatchEnergyHistory, CavityForceBatch
 from .thermostat_batch import BussiReservoirBatch
 from .recorder import BatchRecorder
+from .field_recorder import BatchFieldRecorder
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, observables, recorder, replicas, synthetic, thermostat_batch, thermostats
+from . import _capi, field_recorder, observables, recorder, replicas, synthetic, thermostat_batch, thermostats
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "observables", "recorder", "replicas", "synthetic", "thermostat_batch", "thermostats",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "field_recorder", "observables", "recorder", "replicas", "synthetic", "thermostat_batch", "thermostats",
 ]
 __version__ = "0.1.0"

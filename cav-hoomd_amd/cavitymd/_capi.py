@@ -104,6 +104,20 @@ class RecorderItem(ctypes.Structure):
                 ("reserved", ctypes.c_uint64 * 3)]
 
 
+class FieldRecord(ctypes.Structure):
+    """cavmd_field_record (160 bytes): one row of a field recorder's time series."""
+    _fields_ = [("call", ctypes.c_uint64), ("n_references", ctypes.c_uint32), ("took_reference", ctypes.c_uint32),
+                ("rho2", ctypes.c_double), ("reserved", ctypes.c_double), ("F", ctypes.c_double * 16)]
+
+
+class FieldItem(ctypes.Structure):
+    """cavmd_field_item (64 bytes): one system of a field recorder; d_position is a DEVICE pointer."""
+    _fields_ = [("d_position", ctypes.c_void_p), ("position_stride", ctypes.c_uint64), ("N", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 5)]
+
+
+FIELD_MAX_WAVEVECTORS = 256
+FIELD_MAX_REFERENCES = 16
 BATCH_MAX_ITEMS = 65536
 BATCH_MAX_ITEM_N = 65536
 
@@ -141,8 +155,18 @@ def recorder_item(result_ptr, vel_ptr, net_force_ptr, members_ptr, N, n_members)
     return it
 
 
+def field_item(position_ptr, position_stride, N) -> "FieldItem":
+    it = FieldItem()
+    it.d_position = position_ptr or None
+    it.position_stride, it.N = int(position_stride), int(N)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_field_recorder_item_check", "cavmd_field_recorder_create", "cavmd_field_recorder_destroy",
+    "cavmd_field_recorder_set_items", "cavmd_field_recorder_record", "cavmd_field_recorder_rows", "cavmd_field_recorder_read",
+    "cavmd_field_recorder_read_fields", "cavmd_field_recorder_reset", "cavmd_field_recorder_device_ptr",
     "cavmd_recorder_item_check", "cavmd_recorder_create", "cavmd_recorder_destroy", "cavmd_recorder_set_items",
     "cavmd_recorder_record", "cavmd_recorder_rows", "cavmd_recorder_read", "cavmd_recorder_reset", "cavmd_recorder_device_ptr",
     "cavmd_bussi_batch_item_check", "cavmd_bussi_batch_input_make", "cavmd_bussi_batch_create", "cavmd_bussi_batch_destroy",
@@ -318,6 +342,28 @@ def _declare(lib):
         lib.cavmd_recorder_reset.restype = ci
         lib.cavmd_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
         lib.cavmd_recorder_device_ptr.restype = ci
+    if hasattr(lib, "cavmd_field_recorder_create"):
+        u32 = ctypes.c_uint32
+        lib.cavmd_field_recorder_item_check.argtypes = [P(FieldItem)]
+        lib.cavmd_field_recorder_item_check.restype = ci
+        lib.cavmd_field_recorder_create.argtypes = [vp, sz, P(FieldItem), sz, vp, sz, u64, u32, u64, P(vp)]
+        lib.cavmd_field_recorder_create.restype = ci
+        lib.cavmd_field_recorder_destroy.argtypes = [vp]
+        lib.cavmd_field_recorder_destroy.restype = ci
+        lib.cavmd_field_recorder_set_items.argtypes = [vp, sz, sz, P(FieldItem)]
+        lib.cavmd_field_recorder_set_items.restype = ci
+        lib.cavmd_field_recorder_record.argtypes = [vp, vp, vp]
+        lib.cavmd_field_recorder_record.restype = ci
+        lib.cavmd_field_recorder_rows.argtypes = [vp, vp, vp]
+        lib.cavmd_field_recorder_rows.restype = ci
+        lib.cavmd_field_recorder_read.argtypes = [vp, vp, sz, sz, u64, sz, vp]
+        lib.cavmd_field_recorder_read.restype = ci
+        lib.cavmd_field_recorder_read_fields.argtypes = [vp, vp, sz, vp, vp, vp, P(u32)]
+        lib.cavmd_field_recorder_read_fields.restype = ci
+        lib.cavmd_field_recorder_reset.argtypes = [vp, vp]
+        lib.cavmd_field_recorder_reset.restype = ci
+        lib.cavmd_field_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
+        lib.cavmd_field_recorder_device_ptr.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -373,6 +419,7 @@ _deferred = []
 _deferred_batches = []  # the same for batches (cavmd_batch_destroy)
 _deferred_bussi_batches = []  # and for thermostat batches (cavmd_bussi_batch_destroy)
 _deferred_recorders = []  # and for recorders (cavmd_recorder_destroy)
+_deferred_field_recorders = []  # and for field recorders (cavmd_field_recorder_destroy)
 
 
 def _capturing() -> bool:
@@ -385,6 +432,9 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
+    while _deferred_field_recorders:  # like the recorders: before the workspaces they were created from
+        lib, h = _deferred_field_recorders.pop()
+        lib.cavmd_field_recorder_destroy(h)
     while _deferred_recorders:  # recorders and batches before the workspaces they were created from
         lib, h = _deferred_recorders.pop()
         lib.cavmd_recorder_destroy(h)
@@ -419,11 +469,12 @@ class Workspace:
             if _capturing():
                 _deferred.append((self._lib, self._h))
             else:
-                if _deferred_batches or _deferred_bussi_batches or _deferred_recorders:  # batches deferred during a capture go before any workspace
+                if _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders:  # batches deferred during a capture go before any workspace
                     _destroy_deferred()
                 self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
+                and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -618,7 +669,8 @@ class Batch:
             else:
                 self._lib.cavmd_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
+                and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -711,7 +763,8 @@ class BussiBatch:
             else:
                 self._lib.cavmd_bussi_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
+                and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -808,7 +861,8 @@ class Recorder:
             else:
                 self._lib.cavmd_recorder_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders) and not _capturing():
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
+                and not _capturing():
             _destroy_deferred()
 
     def __del__(self):
@@ -852,4 +906,128 @@ class Recorder:
         """(records, rows): device addresses of the series (item-major, `capacity` records each) and of the row counters."""
         rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
         check(self._lib.cavmd_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)), "cavmd_recorder_device_ptr")
+        return int(rec.value), int(rows.value)
+
+
+FIELD_RECORD_DTYPE_FIELDS = [("call", "<u8"), ("n_references", "<u4"), ("took_reference", "<u4"), ("rho2", "<f8"),
+                             ("reserved", "<f8"), ("F", "<f8", (16,))]
+
+
+def field_record_dtype():
+    """numpy structured dtype with the layout of cavmd_field_record (160 bytes)."""
+    import numpy as np
+    return np.dtype(FIELD_RECORD_DTYPE_FIELDS)
+
+
+def field_item_check(item: FieldItem) -> int:
+    """Status cavmd_field_recorder_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_field_recorder_item_check(ctypes.byref(item)))
+
+
+class FieldRecorder:
+    """Owns one cavmd_field_recorder: rho(k) of B independent small systems, its correlation with each system's stored
+    reference fields and the reference bookkeeping, appended by ONE kernel launch per call to a time series in device memory
+    (a graph replay appends a new row and takes references when they are due).  Keeps its workspace alive."""
+
+    def __init__(self, workspace: Workspace, items, wavevectors, capacity: int, period: int, max_references: int,
+                 reference_interval: int):
+        import numpy as np
+        self._ws = workspace
+        self._lib = workspace._lib
+        items = list(items)
+        self.n_items = len(items)
+        kv = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)
+        self.n_k = int(kv.shape[0])
+        self.capacity, self.period = int(capacity), int(period)
+        self.max_references, self.reference_interval = int(max_references), int(reference_interval)
+        self.sizes = [int(it.N) for it in items]
+        arr = (FieldItem * max(self.n_items, 1))(*items)
+        self._h = ctypes.c_void_p()
+        if self.capacity < 0 or self.period < 0 or self.max_references < 0 or self.reference_interval < 0 \
+                or self.max_references >= 2**32:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_field_recorder_create")
+        check(self._lib.cavmd_field_recorder_create(workspace.handle, self.n_items, arr, self.n_k,
+                                                    ctypes.c_void_p(kv.ctypes.data), self.capacity, self.period,
+                                                    self.max_references, self.reference_interval, ctypes.byref(self._h)),
+              "cavmd_field_recorder_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def launch_order(self):
+        """Item indices in the order their workgroups start (N descending, stable), predicted by ``batch_launch_order``."""
+        return batch_launch_order(self.sizes)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if _capturing():
+                _deferred_field_recorders.append((self._lib, self._h))
+            else:
+                self._lib.cavmd_field_recorder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
+                and not _capturing():
+            _destroy_deferred()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_items(self, first: int, items) -> None:
+        items = list(items)
+        arr = (FieldItem * max(len(items), 1))(*items)
+        check(self._lib.cavmd_field_recorder_set_items(self._h, int(first), len(items), arr), "cavmd_field_recorder_set_items")
+        for k, it in enumerate(items):
+            self.sizes[first + k] = int(it.N)
+
+    def record(self, stream: int = 0, take_reference_ptr: int = 0) -> None:
+        """One kernel: every item's call counter moves; on every period-th call the item appends one row.
+        take_reference_ptr: 0 or the device address of n_items uint32 words read when the kernel runs."""
+        check(self._lib.cavmd_field_recorder_record(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(take_reference_ptr)),
+              "cavmd_field_recorder_record")
+
+    def rows(self, stream: int = 0):
+        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=np.uint64)
+        check(self._lib.cavmd_field_recorder_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
+              "cavmd_field_recorder_rows")
+        return out
+
+    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
+        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
+        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_field_record."""
+        import numpy as np
+        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=field_record_dtype())
+        check(self._lib.cavmd_field_recorder_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items),
+                                                  int(first_row), int(n_rows), ctypes.c_void_p(out.ctypes.data)),
+              "cavmd_field_recorder_read")
+        return out
+
+    def read_fields(self, stream: int, item: int):
+        """(rho_now, rho_refs, ref_rows) of one item after synchronising `stream`: complex arrays of shape (n_k,) and
+        (n_refs, n_k), and the row each reference was taken at."""
+        import numpy as np
+        now = np.zeros(2 * self.n_k)
+        refs = np.zeros((self.max_references, 2 * self.n_k))
+        ref_rows = np.zeros(self.max_references, dtype=np.uint64)
+        n = ctypes.c_uint32()
+        check(self._lib.cavmd_field_recorder_read_fields(self._h, ctypes.c_void_p(stream), int(item),
+                                                         ctypes.c_void_p(now.ctypes.data), ctypes.c_void_p(refs.ctypes.data),
+                                                         ctypes.c_void_p(ref_rows.ctypes.data), ctypes.byref(n)),
+              "cavmd_field_recorder_read_fields")
+        return now.view(np.complex128), refs[:n.value].copy().view(np.complex128), ref_rows[:n.value].copy()
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_field_recorder_reset(self._h, ctypes.c_void_p(stream)), "cavmd_field_recorder_reset")
+
+    def device_ptr(self):
+        """(records, rows): device addresses of the series (item-major, `capacity` records each) and of the row counters."""
+        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.cavmd_field_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)),
+              "cavmd_field_recorder_device_ptr")
         return int(rec.value), int(rows.value)

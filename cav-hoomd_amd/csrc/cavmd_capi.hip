@@ -160,6 +160,7 @@ struct cavmd_workspace
     hipStream_t bussi_stream = nullptr; // stream of the last enqueued step: the one whose idleness ends a wait for its flag
     unsigned bussi_batches = 0;         // live cavmd_bussi_batch objects created from this workspace (cavmd_destroy refuses)
     unsigned recorders = 0;             // live cavmd_recorder objects created from this workspace (the same)
+    unsigned field_recorders = 0;       // live cavmd_field_recorder objects created from this workspace (the same)
 };
 
 namespace
@@ -503,6 +504,8 @@ int cavmd_destroy(cavmd_workspace* ws)
     if (ws->bussi_batches != 0) // a thermostat batch outlives nothing of its workspace: destroy the batches first
         return CAVMD_ERR_INVALID_VALUE;
     if (ws->recorders != 0)     // nor does a recorder
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->field_recorders != 0) // nor a field recorder
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -2802,6 +2805,332 @@ int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, c
         *records = r->d_series;
     if (rows)
         *rows = r->d_counters + (size_t)kRecRows * r->n;
+    return CAVMD_OK;
+}
+
+} // extern "C"
+
+// ---- density field and F(k,t) of a batch recorded into a time series in device memory (cavmd_field_recorder_kernel.hpp) -------
+struct cavmd_field_recorder
+{
+    cavmd_workspace* ws = nullptr;
+    int device = -1;
+    size_t n = 0;
+    size_t n_k = 0;
+    size_t capacity = 0;
+    uint64_t period = 1;
+    unsigned max_refs = 1;
+    uint64_t interval = 0;
+    std::vector<cavmd_field_item> items; // host copy of the table, as the caller gave it
+    std::vector<unsigned> order;         // items by N descending, stable
+    FieldRow* d_rows = nullptr;
+    unsigned* d_order = nullptr;
+    double* d_kvec = nullptr;               // n_k x 3
+    cavmd_field_record* d_series = nullptr; // n x capacity records, item-major
+    uint64_t* d_counters = nullptr;         // kFldCounters arrays of n words
+    uint64_t* d_ref_rows = nullptr;         // n x max_refs: the row each reference was taken at
+    double* d_now = nullptr;                // n x n_k x 2: the field of the last recorded call
+    double* d_refs = nullptr;               // n x max_refs x n_k x 2
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_field_record) == 160 && offsetof(cavmd_field_record, n_references) == 8
+                  && offsetof(cavmd_field_record, took_reference) == 12 && offsetof(cavmd_field_record, rho2) == 16
+                  && offsetof(cavmd_field_record, F) == 32,
+              "field record layout");
+static_assert(sizeof(cavmd_field_item) == sizeof(FieldRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_field_item, d_position) == offsetof(FieldRow, pos)
+                  && offsetof(cavmd_field_item, position_stride) == offsetof(FieldRow, stride)
+                  && offsetof(cavmd_field_item, N) == offsetof(FieldRow, N),
+              "field item layout");
+
+std::vector<unsigned> field_recorder_order(const std::vector<cavmd_field_item>& items)
+{
+    std::vector<unsigned> order(items.size());
+    for (size_t i = 0; i < items.size(); ++i)
+        order[i] = (unsigned)i;
+    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) { return items[x].N > items[y].N; });
+    return order;
+}
+
+int field_recorder_sync(hipStream_t stream)
+{
+    if (stream_capturing(stream))
+        return CAVMD_ERR_INVALID_VALUE;
+    CAVMD_HIP_TRY(hipStreamSynchronize(stream));
+    return CAVMD_OK;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_field_recorder_item_check(const cavmd_field_item* it)
+{
+    if (!it || it->reserved0 != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 5; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if ((!it->d_position && it->N > 0) || ((uintptr_t)it->d_position & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->position_stride < 24 || (it->position_stride & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_field_item* h_items, size_t n_k,
+                                const double* h_wavevectors, size_t capacity, uint64_t period, uint32_t max_references,
+                                uint64_t reference_interval, cavmd_field_recorder** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || !h_wavevectors || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || n_k == 0
+        || n_k > CAVMD_FIELD_MAX_WAVEVECTORS || capacity == 0 || period == 0 || max_references == 0
+        || max_references > CAVMD_FIELD_MAX_REFERENCES)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < 3 * n_k; ++i)
+        if (!std::isfinite(h_wavevectors[i]))
+            return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const int st = cavmd_field_recorder_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    // series + fields (the current one and the references) within the recorder's cap
+    const size_t field_bytes = sizeof(double) * 2 * n_k;
+    const size_t fields_per_item = field_bytes * ((size_t)max_references + 1);
+    if (fields_per_item * n_items > kRecorderMaxBytes
+        || capacity > (kRecorderMaxBytes - fields_per_item * n_items) / sizeof(cavmd_field_record) / n_items)
+        return CAVMD_ERR_CAPACITY;
+    cavmd_field_recorder* r = new (std::nothrow) cavmd_field_recorder();
+    if (!r)
+        return (int)hipErrorOutOfMemory;
+    r->device = ws->device;
+    r->n = n_items;
+    r->n_k = n_k;
+    r->capacity = capacity;
+    r->period = period;
+    r->max_refs = max_references;
+    r->interval = reference_interval;
+    r->items.assign(h_items, h_items + n_items);
+    r->order = field_recorder_order(r->items);
+
+    DeviceGuard guard(r->device);
+    const size_t series_bytes = sizeof(cavmd_field_record) * n_items * capacity;
+    const size_t counter_bytes = sizeof(uint64_t) * kFldCounters * n_items;
+    const size_t ref_row_bytes = sizeof(uint64_t) * n_items * max_references;
+    hipError_t e = hipMalloc((void**)&r->d_rows, sizeof(FieldRow) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_rows, r->items.data(), sizeof(FieldRow) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_order, sizeof(unsigned) * n_items);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_kvec, sizeof(double) * 3 * n_k);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_kvec, h_wavevectors, sizeof(double) * 3 * n_k, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_series, series_bytes);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_series, 0, series_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_counters, counter_bytes);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_counters, 0, counter_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_ref_rows, ref_row_bytes);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_ref_rows, 0, ref_row_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_now, field_bytes * n_items);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_now, 0, field_bytes * n_items);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&r->d_refs, field_bytes * n_items * max_references);
+    if (e == hipSuccess)
+        e = hipMemset(r->d_refs, 0, field_bytes * n_items * max_references);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
+    if (e != hipSuccess)
+    {
+        cavmd_field_recorder_destroy(r);
+        return (int)e;
+    }
+    r->ws = ws;
+    ws->field_recorders += 1;
+    *out = r;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
+{
+    if (!r)
+        return CAVMD_OK;
+    DeviceGuard guard(r->device);
+    // the kernels in flight read the table and write the series: let them finish (a capturing stream cannot be waited for)
+    if (r->recorded && !stream_capturing(r->last_stream))
+        (void)hipStreamSynchronize(r->last_stream);
+    for (void* p : {(void*)r->d_rows, (void*)r->d_order, (void*)r->d_kvec, (void*)r->d_series, (void*)r->d_counters,
+                    (void*)r->d_ref_rows, (void*)r->d_now, (void*)r->d_refs})
+        if (p)
+            (void)hipFree(p);
+    if (r->ws)
+        r->ws->field_recorders -= 1;
+    delete r;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_set_items(cavmd_field_recorder* r, size_t first, size_t count, const cavmd_field_item* h_items)
+{
+    if (!r || !h_items || count == 0 || first >= r->n || count > r->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = cavmd_field_recorder_item_check(h_items + i);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    DeviceGuard guard(r->device);
+    if (r->recorded)
+    {
+        if (stream_capturing(r->last_stream))
+            return CAVMD_ERR_INVALID_VALUE;
+        CAVMD_HIP_TRY(hipStreamSynchronize(r->last_stream)); // record calls in flight read the rows this call rewrites
+    }
+    // built aside and committed only after both copies went through (as cavmd_recorder_set_items)
+    std::vector<cavmd_field_item> items(r->items);
+    for (size_t i = 0; i < count; ++i)
+        items[first + i] = h_items[i];
+    const std::vector<unsigned> order = field_recorder_order(items);
+    CAVMD_HIP_TRY(hipMemcpy(r->d_order, order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice));
+    const hipError_t e = hipMemcpy(r->d_rows + first, h_items, sizeof(FieldRow) * count, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice); // the old order back
+        return (int)e;
+    }
+    r->items.swap(items);
+    r->order = order;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const uint32_t* d_take_reference)
+{
+    if (!r || ((uintptr_t)d_take_reference & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(r->device);
+    hipLaunchKernelGGL(field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows, r->d_order,
+                       (unsigned)r->n, r->d_kvec, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity, r->period,
+                       r->max_refs, r->interval, d_take_reference, r->d_series, r->d_counters, r->d_ref_rows, r->d_now,
+                       r->d_refs);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    r->last_stream = stream;
+    r->recorded = true;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream_, uint64_t* out)
+{
+    if (!r || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = field_recorder_sync((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(hipMemcpy(out, r->d_counters + (size_t)kFldRows * r->n, sizeof(uint64_t) * r->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_read(cavmd_field_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row,
+                              size_t n_rows, cavmd_field_record* out)
+{
+    if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = field_recorder_sync((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<uint64_t> rows(n_items);
+    CAVMD_HIP_TRY(hipMemcpy(rows.data(), r->d_counters + (size_t)kFldRows * r->n + first_item, sizeof(uint64_t) * n_items,
+                            hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_items; ++k)
+    {
+        if (rows[k] == 0)
+            return CAVMD_ERR_NOT_COMPUTED;
+        if (first_row >= rows[k] || n_rows > rows[k] - first_row)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (rows[k] > r->capacity && first_row < rows[k] - r->capacity)
+            return CAVMD_ERR_EXPIRED;
+    }
+    // row j of an item sits in slot j % capacity of that item's stretch: at most two runs of slots (cavmd_recorder_read's)
+    const size_t rec = sizeof(cavmd_field_record);
+    const size_t slot0 = (size_t)(first_row % r->capacity);
+    const size_t run0 = std::min(n_rows, r->capacity - slot0);
+    const cavmd_field_record* src = r->d_series + first_item * r->capacity;
+    CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, r->capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
+    if (run0 < n_rows)
+        CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, r->capacity * rec, (n_rows - run0) * rec, n_items,
+                                  hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, size_t item, double* rho_now, double* rho_refs,
+                                     uint64_t* ref_rows, uint32_t* n_refs)
+{
+    if (!r || !n_refs || item >= r->n)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = field_recorder_sync((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    uint64_t rows = 0, refs = 0;
+    CAVMD_HIP_TRY(hipMemcpy(&rows, r->d_counters + (size_t)kFldRows * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rows == 0)
+        return CAVMD_ERR_NOT_COMPUTED;
+    CAVMD_HIP_TRY(hipMemcpy(&refs, r->d_counters + (size_t)kFldRefs * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (refs > r->max_refs)
+        return CAVMD_ERR_INVALID_VALUE;
+    const size_t field_len = 2 * r->n_k;
+    if (rho_now)
+        CAVMD_HIP_TRY(hipMemcpy(rho_now, r->d_now + item * field_len, sizeof(double) * field_len, hipMemcpyDeviceToHost));
+    if (rho_refs && refs)
+        CAVMD_HIP_TRY(hipMemcpy(rho_refs, r->d_refs + item * r->max_refs * field_len, sizeof(double) * field_len * refs,
+                                hipMemcpyDeviceToHost));
+    if (ref_rows && refs)
+        CAVMD_HIP_TRY(hipMemcpy(ref_rows, r->d_ref_rows + item * r->max_refs, sizeof(uint64_t) * refs, hipMemcpyDeviceToHost));
+    *n_refs = (uint32_t)refs;
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream_)
+{
+    if (!r)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    CAVMD_HIP_TRY(hipMemsetAsync(r->d_counters, 0, sizeof(uint64_t) * kFldCounters * r->n, (hipStream_t)stream_));
+    return CAVMD_OK;
+}
+
+int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records, const uint64_t** rows)
+{
+    if (!r || (!records && !rows))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (records)
+        *records = r->d_series;
+    if (rows)
+        *rows = r->d_counters + (size_t)kFldRows * r->n;
     return CAVMD_OK;
 }
 

@@ -1,0 +1,289 @@
+// cavmd_field_recorder_kernel.hpp -- the density field rho(k) of a batch of independent small systems and its correlation with
+// each system's stored reference fields, F_r(t) = mean_k Re(rho_r(k) conj rho(k, t)), in ONE launch, one workgroup per system,
+// appended to a time series in DEVICE memory: the fourth kernel of the batched step next to cavmd_batch_kernel.hpp (forces),
+// cavmd_recorder_kernel.hpp (per-step observables) and cavmd_bussi_batch_kernel.hpp (thermostat).
+//
+// What the reference's FieldAutocorrelationTracker (src/cavitymd/analysis.py:260-418) does every step for every replica --
+// compute_density_field for 50 wavevectors, compute_field_autocorr against up to 10 stored references, and now and then a new
+// reference (act, :380-414: correlate with all active references FIRST, then maybe add one) -- is one 160-byte row here.  Write
+// position, reference count and the row of the last reference live in device memory, so a graph replay appends a NEW row and
+// takes references when they are due exactly like an eager call.  Workgroups never wait for each other; the item's workgroup
+// is the only writer of its counters, its series and its reference fields (no atomics).
+//
+// Mapping: LANE = WAVEVECTOR, density_partials_kernel's, folded into one workgroup: wavevectors in chunks of 64 looped inside
+// the workgroup, wave w walks the 64-particle tiles w, w + 4, ... in ascending order and inside a tile the particles in
+// ascending order (coordinates through scalar loads from the uniform tile address on the fast path), two plain fp64
+// accumulators per lane, and the four waves meet in LDS where wave 0 adds them in WAVE order.  The sum order is therefore a
+// function of (N, n_k) alone.  Term arithmetic, sincos_reduced and the per-tile choice between the fast path and the device
+// library's sincos are density_partials_kernel's own (the device functions are used by inclusion).
+#pragma once
+
+#include "cavmd_observable_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace cavmd
+{
+constexpr unsigned kFieldMaxK = CAVMD_FIELD_MAX_WAVEVECTORS;
+constexpr unsigned kFieldMaxRefs = CAVMD_FIELD_MAX_REFERENCES;
+
+typedef const __attribute__((address_space(4))) double* FieldConstPtr; // read-only for the kernel's duration: scalar loads
+
+// One system as the kernel reads it: the layout of cavmd_field_item (the table is uploaded as it is).
+struct FieldRow
+{
+    const char* pos;
+    uint64_t stride;
+    unsigned N;
+    unsigned pad0;
+    uint64_t pad[5];
+};
+static_assert(sizeof(FieldRow) == 64, "one field-recorder row = 64 bytes");
+
+// Six words per item, kept as six arrays of n_items (rows first: that array is what cavmd_field_recorder_device_ptr hands
+// out).  phase and slot are calls % period and rows % capacity, carried along so that the kernel never divides.
+enum FieldCounter
+{
+    kFldRows = 0,
+    kFldCalls = 1,
+    kFldPhase = 2,
+    kFldSlot = 3,
+    kFldRefs = 4,    // references stored
+    kFldLastRef = 5, // row at which the last one was taken
+    kFldCounters = 6
+};
+
+// blockIdx.x -> order[blockIdx.x] (items by N descending, sorted on the host) -> the row, fetched once per workgroup.
+// Counters, series and fields are indexed by ITEM, never by block.
+// field_now: [item][n_k][2], refs: [item][max_refs][n_k][2], ref_rows: [item][max_refs].
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void field_recorder_batch_kernel(
+    const FieldRow* __restrict__ rows, const unsigned* __restrict__ order, unsigned n_items, const double* __restrict__ kvec,
+    unsigned n_k, SinCosCoef coef, uint64_t capacity, uint64_t period, unsigned max_refs, uint64_t interval,
+    const unsigned* __restrict__ take, cavmd_field_record* __restrict__ series, uint64_t* __restrict__ counters,
+    uint64_t* __restrict__ ref_rows, double* __restrict__ field_now, double* __restrict__ refs)
+{
+    constexpr int NW = BLOCK / kWave;
+    __shared__ double s_acc[NW][2][kWave];
+    __shared__ double s_rho[2 * kFieldMaxK];
+    __shared__ double s_F[kFieldMaxRefs + 1]; // [n_refs] holds rho2
+    __shared__ uint64_t s_ctl[4];             // rows, slot, references, row of the last reference
+    __shared__ int s_record;
+
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const unsigned item = __builtin_amdgcn_readfirstlane(order[blockIdx.x]);
+    const FieldRow* __restrict__ row = rows + item;
+    uint64_t* __restrict__ c_rows = counters + (size_t)kFldRows * n_items + item;
+    uint64_t* __restrict__ c_calls = counters + (size_t)kFldCalls * n_items + item;
+    uint64_t* __restrict__ c_phase = counters + (size_t)kFldPhase * n_items + item;
+    uint64_t* __restrict__ c_slot = counters + (size_t)kFldSlot * n_items + item;
+    uint64_t* __restrict__ c_refs = counters + (size_t)kFldRefs * n_items + item;
+    uint64_t* __restrict__ c_last = counters + (size_t)kFldLastRef * n_items + item;
+
+    // 1. does this call record?  Thread 0 alone reads the counters (it is also their only writer) and tells the others.
+    uint64_t calls = 0, phase = 0;
+    if (threadIdx.x == 0)
+    {
+        calls = *c_calls + 1;
+        phase = *c_phase + 1;
+        s_record = (phase >= period);
+        s_ctl[0] = *c_rows;
+        s_ctl[1] = *c_slot;
+        s_ctl[2] = *c_refs;
+        s_ctl[3] = *c_last;
+    }
+    __syncthreads();
+    if (!s_record)
+    {
+        if (threadIdx.x == 0)
+        {
+            *c_calls = calls;
+            *c_phase = phase;
+        }
+        return;
+    }
+    const uint64_t t = s_ctl[0];
+    const uint64_t slot = s_ctl[1];
+    const unsigned n_refs = (unsigned)s_ctl[2];
+    const uint64_t last_ref = s_ctl[3];
+
+    // 2. rho(k): density_partials_kernel's tile loop with "grid" = the four waves of this workgroup
+    const char* __restrict__ pos = row->pos;
+    const size_t pos_stride = row->stride;
+    const unsigned N = row->N;
+    const unsigned ntiles = (N + kWave - 1) / kWave;
+    const unsigned wave_u = (unsigned)__builtin_amdgcn_readfirstlane(wave);
+    const unsigned nchunks = (n_k + kWave - 1) / kWave;
+    for (unsigned chunk = 0; chunk < nchunks; ++chunk)
+    {
+        const unsigned k = chunk * kWave + lane;
+        const bool active = k < n_k;
+        const double kx = active ? kvec[3 * k + 0] : 0.0;
+        const double ky = active ? kvec[3 * k + 1] : 0.0;
+        const double kz = active ? kvec[3 * k + 2] : 0.0;
+        const double ksum = (fabs(kx) + fabs(ky)) + fabs(kz);
+        double re = 0.0, im = 0.0;
+        for (unsigned tile = wave_u; tile < ntiles; tile += NW)
+        {
+            // lane = particle: one coalesced round, used for the tile's coordinate bound and for the rare slow path
+            const size_t i = (size_t)tile * kWave + lane;
+            double px = 0.0, py = 0.0, pz = 0.0;
+            if (i < N)
+            {
+                const double* p = reinterpret_cast<const double*>(pos + i * pos_stride);
+                px = p[0];
+                py = p[1];
+                pz = p[2];
+            }
+            const unsigned left = N - tile * kWave;
+            const int cnt = left < (unsigned)kWave ? (int)left : kWave; // wave-uniform
+            double m = fmax(fmax(fabs(px), fabs(py)), fabs(pz));
+            m = fmax(m, dpp_f64<0xB1, 0xF>(m, 0.0));
+            m = fmax(m, dpp_f64<0x4E, 0xF>(m, 0.0));
+            m = fmax(m, dpp_f64<0x124, 0xF>(m, 0.0));
+            m = fmax(m, dpp_f64<0x128, 0xF>(m, 0.0));
+            m = fmax(m, __shfl_xor(m, 16, kWave));
+            m = fmax(m, __shfl_xor(m, 32, kWave));
+            const bool all_finite = !__any(!(fabs(px) < 1.0e300) || !(fabs(py) < 1.0e300) || !(fabs(pz) < 1.0e300));
+            if (all_finite && !__any(!(ksum * m < 1.0e8)))
+            {
+                // fast path: every |k . r| of this tile is below 1e8.  The coordinates come through the scalar cache: the tile
+                // address is uniform, and the constant address space tells the compiler what it cannot see through a pointer
+                // that was itself loaded from the item table -- this kernel never writes a position.
+                const uintptr_t base = (uintptr_t)(pos + (size_t)tile * kWave * pos_stride);
+                constexpr int PU = 4;
+                int j = 0;
+                for (; j + PU <= cnt; j += PU)
+                {
+                    double x[PU], y[PU], z[PU];
+#pragma unroll
+                    for (int u = 0; u < PU; ++u)
+                    {
+                        const FieldConstPtr p = (FieldConstPtr)(base + (size_t)(j + u) * pos_stride);
+                        x[u] = p[0];
+                        y[u] = p[1];
+                        z[u] = p[2];
+                    }
+#pragma unroll
+                    for (int u = 0; u < PU; ++u)
+                    {
+                        double sn, cs;
+                        sincos_reduced(coef, (x[u] * kx + y[u] * ky) + z[u] * kz, sn, cs);
+                        re += cs;
+                        im += sn;
+                    }
+                }
+                for (; j < cnt; ++j)
+                {
+                    const FieldConstPtr p0 = (FieldConstPtr)(base + (size_t)j * pos_stride);
+                    double s0, c0;
+                    sincos_reduced(coef, (p0[0] * kx + p0[1] * ky) + p0[2] * kz, s0, c0);
+                    re += c0;
+                    im += s0;
+                }
+            }
+            else
+            {
+                for (int j = 0; j < cnt; ++j)
+                {
+                    const double x = readlane_f64(px, j), y = readlane_f64(py, j), z = readlane_f64(pz, j);
+                    const double kr = (x * kx + y * ky) + z * kz;
+                    double sn, cs;
+                    if (__any(!(fabs(kr) < 1.0e8))) // wave-uniform; also catches NaN/Inf
+                        sincos(kr, &sn, &cs);
+                    else
+                        sincos_reduced(coef, kr, sn, cs);
+                    re += cs;
+                    im += sn;
+                }
+            }
+        }
+        s_acc[wave][0][lane] = re;
+        s_acc[wave][1][lane] = im;
+        __syncthreads();
+        if (wave == 0)
+        {
+#pragma unroll
+            for (int w = 1; w < NW; ++w) // in wave order, whichever wave arrived first
+            {
+                re += s_acc[w][0][lane];
+                im += s_acc[w][1][lane];
+            }
+            if (active)
+            {
+                s_rho[2 * k] = re;
+                s_rho[2 * k + 1] = im;
+            }
+        }
+        __syncthreads(); // s_acc is free for the next chunk; after the last one the field is complete in LDS
+    }
+
+    // 3. F[r] = (sum over k ascending of (a_r a + b_r b)) / n_k: lane r of wave 0 walks k for reference r, the first lane
+    //    of wave 1 does the same with the field itself (rho2).  One rounding per operation, no FMA, the sum starts at +0.
+    const size_t field_len = 2 * (size_t)n_k;
+    const double inv_count = (double)n_k;
+    if (threadIdx.x < n_refs)
+    {
+        const v2d* __restrict__ ref = reinterpret_cast<const v2d*>(refs + ((size_t)item * max_refs + threadIdx.x) * field_len);
+        double acc = 0.0;
+#pragma unroll 4
+        for (unsigned k = 0; k < n_k; ++k)
+        {
+            const v2d ab = ref[k];
+            acc = acc + (ab.x * s_rho[2 * k] + ab.y * s_rho[2 * k + 1]);
+        }
+        s_F[threadIdx.x] = acc / inv_count;
+    }
+    else if (threadIdx.x == (unsigned)kWave)
+    {
+        double acc = 0.0;
+        for (unsigned k = 0; k < n_k; ++k)
+            acc = acc + (s_rho[2 * k] * s_rho[2 * k] + s_rho[2 * k + 1] * s_rho[2 * k + 1]);
+        s_F[kFieldMaxRefs] = acc / inv_count;
+    }
+    else if (threadIdx.x < kFieldMaxRefs)
+        s_F[threadIdx.x] = 0.0;
+
+    // 4. the field of this call (cavmd_field_recorder_read_fields), and a new reference AFTER the correlation if one is due
+    const bool asked = take != nullptr && take[item] != 0;
+    const bool due = n_refs < max_refs && (n_refs == 0 || (interval > 0 && t - last_ref >= interval) || asked);
+    double* __restrict__ now = field_now + (size_t)item * field_len;
+    for (unsigned i = threadIdx.x; i < field_len; i += BLOCK)
+        now[i] = s_rho[i];
+    if (due)
+    {
+        double* __restrict__ dst = refs + ((size_t)item * max_refs + n_refs) * field_len;
+        for (unsigned i = threadIdx.x; i < field_len; i += BLOCK)
+            dst[i] = s_rho[i];
+    }
+    __syncthreads();
+
+    // 5. the row with 16-byte stores, then the counters
+    if (threadIdx.x == 0)
+    {
+        v2d* __restrict__ out = reinterpret_cast<v2d*>(series + (size_t)item * capacity + slot);
+        const uint64_t word1 = (uint64_t)n_refs | ((uint64_t)(due ? 1u : 0u) << 32);
+        const v2d head = {__longlong_as_double((long long)calls), __longlong_as_double((long long)word1)};
+        const v2d sums = {s_F[kFieldMaxRefs], 0.0};
+        out[0] = head;
+        out[1] = sums;
+#pragma unroll
+        for (unsigned r = 0; r < kFieldMaxRefs; r += 2)
+        {
+            const v2d f = {s_F[r], s_F[r + 1]};
+            out[2 + r / 2] = f;
+        }
+        if (due)
+        {
+            ref_rows[(size_t)item * max_refs + n_refs] = t;
+            *c_refs = (uint64_t)n_refs + 1;
+            *c_last = t;
+        }
+        *c_rows = t + 1;
+        *c_slot = (slot + 1 >= capacity) ? 0 : slot + 1;
+        *c_calls = calls;
+        *c_phase = 0;
+    }
+}
+} // namespace cavmd

@@ -36,3 +36,4 @@
 #include "cavmd_observable_kernels.hpp"
 #include "cavmd_bussi_batch_kernel.hpp"
 #include "cavmd_recorder_kernel.hpp"
+#include "cavmd_field_recorder_kernel.hpp"

@@ -27,6 +27,9 @@
  *                               src/cavitymd/analysis.py:425-, 1285-1417, 1424-; src/cavitymd/simulation.py:66-92
  *                                                                   cavmd_recorder_create / cavmd_recorder_record /
  *                                                                   cavmd_recorder_read (a time series in device memory)
+ *   FieldAutocorrelationTracker, per step and replica
+ *                               src/cavitymd/analysis.py:260-418    cavmd_field_recorder_create / cavmd_field_recorder_record /
+ *                                                                   cavmd_field_recorder_read (rho(k), F(k,t), references)
  *   CavityForceCompute::computeForces (the CPU semantics both follow)
  *                               src/CavityForceCompute.cc:134-208   (semantic contract, see below)
  *
@@ -567,6 +570,112 @@ CAVMD_API int cavmd_recorder_reset(cavmd_recorder* r, void* stream);
 /* Device addresses of the series (item-major: record j of item i at records[i * capacity + j % capacity]) and of the n_items
  * row counters, for consumers that stay on the GPU.  Either out pointer may be NULL. */
 CAVMD_API int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows);
+
+/* ---- density field and F(k,t) of a batch, recorded on the device: the fourth kernel of the batched step ------------------ */
+/* What the reference's FieldAutocorrelationTracker (src/cavitymd/analysis.py:260-418) does every step for every replica --
+ * rho(k) = sum_j exp(i k . r_j) for a set of wavevectors (compute_density_field, :34-47), F_r(t) = mean_k Re(rho_r(k)
+ * conj rho(k, t)) against every stored reference field (compute_field_autocorr), and now and then a new reference (act,
+ * :380-414: correlate with all active references FIRST, then maybe add one) -- as ONE launch for all systems that appends one
+ * 160-byte record per system to a time series kept in DEVICE memory.  Write position, reference count and the row of the last
+ * reference are kept on the device too, so a hipGraph replay appends a NEW row, and takes a reference when one is due, exactly
+ * like an eager call: with this a captured step is {cavmd_batch_compute, cavmd_recorder_record, cavmd_field_recorder_record,
+ * cavmd_bussi_batch_step}.  The host reads when it likes, behind a synchronisation of the stream it names; nothing is mapped,
+ * nothing is polled.  Systems are independent: no workgroup waits for another one, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ *
+ * One recording call for one item (t = rows the item has recorded so far, 0-based):
+ *   1. rho(k) of the positions as they are when the kernel RUNS: the term arithmetic of cavmd_density_field
+ *      (k . r = (x kx + y ky) + z kz, the same sincos and the same choice, per 64-particle tile, between the fast path and the
+ *      device library's for |k . r| >= 1e8 or non-finite coordinates), plain sums in an order that depends on (N, n_k) ONLY --
+ *      not on the batch, the item's place in it, the compute unit, eager or replay.  Within 1e-13 * N of the exact sum per
+ *      component, within 2e-13 * N of cavmd_density_field (whose sum order differs).
+ *   2. F[r] = (sum over k ascending of (a_r[k] * a[k] + b_r[k] * b[k])) / n_k for every stored reference r (a, b = Re, Im;
+ *      one IEEE rounding per operation, no FMA, left to right in k from +0): bit for bit that expression on the fields
+ *      cavmd_field_recorder_read_fields returns.  rho2 is the same expression with the field itself.
+ *   3. The row goes to slot t % capacity.
+ *   4. AFTER step 2 the field is stored as reference number n_references if fewer than max_references are stored and (none is
+ *      stored yet, or reference_interval > 0 and t - (row of the last reference) >= reference_interval, or the item's word of
+ *      d_take_reference is non-zero).  Row 0 therefore has n_references = 0, took_reference = 1, and the row that takes
+ *      reference r does not yet contain F[r], as in the reference.
+ *   5. cavmd_field_recorder_reset forgets rows, counters and references.
+ * An item with N = 0 records rows of zeros and takes zero fields as references; it touches no particle array.  A call that
+ * records no row (period > 1) computes nothing and ignores d_take_reference. */
+#define CAVMD_FIELD_MAX_WAVEVECTORS 256
+#define CAVMD_FIELD_MAX_REFERENCES 16
+
+typedef struct cavmd_field_item          /* 64 B; DEVICE pointer */
+{
+    const double* d_position;            /* particle i's x, y, z at d_position + i * position_stride bytes (WRAPPED) */
+    uint64_t position_stride;            /* 24 or any multiple of 8 >= 24 (32 = HOOMD's Scalar4 pos) */
+    uint32_t N;                          /* 0 legal; <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t reserved0;
+    uint64_t reserved[5];                /* must be 0 */
+} cavmd_field_item;
+
+typedef struct cavmd_field_record        /* 160 B, one per item and recorded call */
+{
+    uint64_t call;                       /* 1-based index of the record call that wrote the row */
+    uint32_t n_references;               /* references the row was correlated with (F[n_references..] are 0) */
+    uint32_t took_reference;             /* 1 if this call stored its field as reference number n_references */
+    double rho2;                         /* mean_k |rho(k)|^2 of this call: the lag-0 value of a reference taken now */
+    double reserved;                     /* 0 */
+    double F[CAVMD_FIELD_MAX_REFERENCES];
+} cavmd_field_record;
+typedef struct cavmd_field_recorder cavmd_field_recorder; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * a null d_position with N > 0, a d_position not 8-byte aligned, a position_stride below 24 or not a multiple of 8,
+ * reserved0 or reserved != 0; CAVMD_ERR_CAPACITY for N above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_field_recorder_item_check(const cavmd_field_item* item);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS) and copies the table and the n_k wavevectors (rows of
+ * (kx, ky, kz) in HOST memory, ONE set for the whole batch: the reference builds kmag * generate_fibonacci_sphere(50) for
+ * every replica, src/cavitymd/analysis.py:296-306) to the device of `ws`, once.  Allocates n_items x capacity records, n_items x
+ * (max_references + 1) fields and the per-item counters in device memory, all zero.  Every `period`-th record call writes a
+ * row.  reference_interval counts RECORDED ROWS; 0 = no automatic reference after the first.  CAVMD_ERR_INVALID_VALUE unless
+ * 1 <= n_k <= CAVMD_FIELD_MAX_WAVEVECTORS with finite components, capacity >= 1, period >= 1 and
+ * 1 <= max_references <= CAVMD_FIELD_MAX_REFERENCES; CAVMD_ERR_CAPACITY if series plus fields would exceed 1 GiB.
+ * cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while a field recorder of the workspace is alive.  Without a
+ * device there is no workspace, hence no field recorder. */
+CAVMD_API int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_field_item* h_items, size_t n_k,
+                                          const double* h_wavevectors, size_t capacity, uint64_t period,
+                                          uint32_t max_references, uint64_t reference_interval, cavmd_field_recorder** out);
+/* Synchronises the stream of the last record call (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_field_recorder_destroy(cavmd_field_recorder* r);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last record call; nothing is
+ * changed if a row is refused; counters, series and references are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being
+ * captured, and for a range outside the batch. */
+CAVMD_API int cavmd_field_recorder_set_items(cavmd_field_recorder* r, size_t first, size_t count,
+                                             const cavmd_field_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait.  May be captured into a
+ * hipGraph; a replay appends like an eager call.  d_take_reference is NULL or a DEVICE array of n_items uint32_t read when the
+ * kernel RUNS (like cavmd_bussi_batch_step's inputs; CAVMD_ERR_INVALID_VALUE if not 4-byte aligned): a non-zero word asks
+ * that item to take a reference at this call (step 4).  That is how a caller implements the reference's time-based
+ * reference_interval_ps under an adaptive timestep; the policy stays the caller's.  Workgroups start in order of N
+ * descending (ties in item order).  One field recorder serves one stream at a time. */
+CAVMD_API int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream, const uint32_t* d_take_reference);
+/* Synchronises `stream`, then out[i] = rows written by item i since creation / the last reset.  CAVMD_ERR_INVALID_VALUE while
+ * `stream` is being captured. */
+CAVMD_API int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream, uint64_t* out);
+/* Synchronises `stream`, then out[k * n_rows + j] = row first_row + j (0-based count of RECORDED rows) of item first_item + k.
+ * CAVMD_ERR_NOT_COMPUTED if an item asked for has never recorded, CAVMD_ERR_INVALID_VALUE for rows at or beyond the item's
+ * `rows`, n_rows or n_items 0, items outside the batch and while `stream` is being captured, CAVMD_ERR_EXPIRED if a
+ * requested row has been overwritten (row < rows - capacity). */
+CAVMD_API int cavmd_field_recorder_read(cavmd_field_recorder* r, void* stream, size_t first_item, size_t n_items,
+                                        uint64_t first_row, size_t n_rows, cavmd_field_record* out);
+/* Synchronises `stream`, then for one item: rho_now = the field of its last recorded call (2 n_k doubles, h_out[2k] = Re,
+ * h_out[2k+1] = Im, as cavmd_density_field_read), rho_refs = its stored reference fields one after the other (room for
+ * max_references x 2 n_k doubles; *n_refs of them are written), ref_rows = the row each was taken at (room for max_references),
+ * *n_refs = how many are stored.  rho_now, rho_refs and ref_rows may each be NULL.  CAVMD_ERR_NOT_COMPUTED if the item has
+ * never recorded (also after a reset), CAVMD_ERR_INVALID_VALUE for an item outside the batch, a null n_refs and while `stream`
+ * is being captured. */
+CAVMD_API int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream, size_t item, double* rho_now,
+                                               double* rho_refs, uint64_t* ref_rows, uint32_t* n_refs);
+/* Zero all counters of all items (ordered on `stream`): rows, calls and references are forgotten; the next recorded row is
+ * row 0, written by call 1, and takes reference 0. */
+CAVMD_API int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream);
+/* Device addresses of the series (item-major: record j of item i at records[i * capacity + j % capacity]) and of the n_items
+ * row counters, for consumers that stay on the GPU.  Either out pointer may be NULL. */
+CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records,
+                                              const uint64_t** rows);
 
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
