@@ -125,7 +125,7 @@ BATCH_MAX_ITEM_N = 65536
 def batch_launch_order(sizes):
     """The order in which cavmd_batch_compute starts the systems of a batch: by N descending, ties in item order (the hardware
     hands out workgroups in launch order, so the long systems of a ragged batch go first).  Results stay indexed by item.
-    This restates the library's rule (std::stable_sort in cavmd_capi.hip); it does not read the library's table."""
+    This restates the library's rule (launch_order in csrc/cavmd_item_table.hpp); it does not read the library's table."""
     import numpy as np
     n = np.asarray(list(sizes), dtype=np.int64)
     return [int(i) for i in np.argsort(-n, kind="stable")]
@@ -416,10 +416,9 @@ def make_params(omegac: float, couplstr: float, phmass: float = 1.0) -> Params:
 # may collect a dropped workspace at any allocation, inside a capture too (torch.cuda.graph does not collect before it
 # captures); the frees of cavmd_destroy would invalidate that capture.
 _deferred = []
-_deferred_batches = []  # the same for batches (cavmd_batch_destroy)
-_deferred_bussi_batches = []  # and for thermostat batches (cavmd_bussi_batch_destroy)
-_deferred_recorders = []  # and for recorders (cavmd_recorder_destroy)
-_deferred_field_recorders = []  # and for field recorders (cavmd_field_recorder_destroy)
+# The same for the objects created from a workspace (batches, thermostat batches, recorders, field recorders), as
+# (destroy entry point, handle): always emptied before _deferred, the workspaces they were created from.
+_deferred_children = []
 
 
 def _capturing() -> bool:
@@ -432,21 +431,17 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
-    while _deferred_field_recorders:  # like the recorders: before the workspaces they were created from
-        lib, h = _deferred_field_recorders.pop()
-        lib.cavmd_field_recorder_destroy(h)
-    while _deferred_recorders:  # recorders and batches before the workspaces they were created from
-        lib, h = _deferred_recorders.pop()
-        lib.cavmd_recorder_destroy(h)
-    while _deferred_bussi_batches:
-        lib, h = _deferred_bussi_batches.pop()
-        lib.cavmd_bussi_batch_destroy(h)
-    while _deferred_batches:
-        lib, h = _deferred_batches.pop()
-        lib.cavmd_batch_destroy(h)
+    while _deferred_children:
+        destroy, h = _deferred_children.pop()
+        destroy(h)
     while _deferred:
         lib, h = _deferred.pop()
         lib.cavmd_destroy(h)
+
+
+def _destroy_deferred_outside_capture() -> None:
+    if (_deferred_children or _deferred) and not _capturing():
+        _destroy_deferred()
 
 
 class Workspace:
@@ -469,13 +464,11 @@ class Workspace:
             if _capturing():
                 _deferred.append((self._lib, self._h))
             else:
-                if _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders:  # batches deferred during a capture go before any workspace
+                if _deferred_children:  # children deferred during a capture go before any workspace
                     _destroy_deferred()
                 self._lib.cavmd_destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
-                and not _capturing():
-            _destroy_deferred()
+        _destroy_deferred_outside_capture()
 
     def __del__(self):
         try:
@@ -630,26 +623,27 @@ class Workspace:
         return {"device": dev.value, "compute_units": cu.value, "arch": buf.value.decode()}
 
 
-def batch_item_check(item: BatchItem) -> int:
-    """Status cavmd_batch_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_batch_item_check(ctypes.byref(item)))
+class _ItemTableHandle:
+    """What Batch, BussiBatch, Recorder and FieldRecorder share: a handle created from a workspace (kept alive here) over a
+    table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
+    the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
+    _ITEM = None    # the ctypes structure of one item
+    _PREFIX = None  # entry points <prefix>_create, <prefix>_destroy, <prefix>_set_items
+    _size = None    # item -> the size key of the launch order
 
-
-class Batch:
-    """Owns one cavmd_batch: B independent small systems evaluated by ONE kernel launch, one workgroup per system
-    (the reference's replica loop, examples/05_advanced_run.py:1570-1612, on one GPU).  Keeps its workspace alive."""
-
-    def __init__(self, workspace: Workspace, items, history_depth: int = 64):
+    def _create(self, workspace: Workspace, items, *args) -> None:
+        """<prefix>_create(workspace, n_items, items, *args, &handle)"""
         self._ws = workspace
         self._lib = workspace._lib
         items = list(items)
         self.n_items = len(items)
-        self.history_depth = int(history_depth)
-        self.sizes = [int(it.N) for it in items]
-        arr = (BatchItem * max(self.n_items, 1))(*items)
+        self.sizes = [self._size(it) for it in items]
         self._h = ctypes.c_void_p()
-        check(self._lib.cavmd_batch_create(workspace.handle, self.n_items, arr, self.history_depth, ctypes.byref(self._h)),
-              "cavmd_batch_create")
+        check(getattr(self._lib, self._PREFIX + "_create")(workspace.handle, self.n_items, self._array(items), *args,
+                                                            ctypes.byref(self._h)), self._PREFIX + "_create")
+
+    def _array(self, items):
+        return (self._ITEM * max(len(items), 1))(*items)   # at least one element: a ctypes array cannot be empty
 
     @property
     def handle(self):
@@ -657,21 +651,20 @@ class Batch:
 
     @property
     def launch_order(self):
-        """Item indices in the order their workgroups start (N descending, stable), as PREDICTED from the sizes by
+        """Item indices in the order their workgroups start (size key descending, stable), as PREDICTED from the sizes by
         ``batch_launch_order``: the rule the library sorts by, restated in Python, not a read-back of the table the library
         uploaded (results do not depend on the order; it matters for load balance only)."""
         return batch_launch_order(self.sizes)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            destroy = getattr(self._lib, self._PREFIX + "_destroy")
             if _capturing():
-                _deferred_batches.append((self._lib, self._h))
+                _deferred_children.append((destroy, self._h))
             else:
-                self._lib.cavmd_batch_destroy(self._h)
+                destroy(self._h)
             self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
-                and not _capturing():
-            _destroy_deferred()
+        _destroy_deferred_outside_capture()
 
     def __del__(self):
         try:
@@ -681,10 +674,26 @@ class Batch:
 
     def set_items(self, first: int, items) -> None:
         items = list(items)
-        arr = (BatchItem * max(len(items), 1))(*items)
-        check(self._lib.cavmd_batch_set_items(self._h, int(first), len(items), arr), "cavmd_batch_set_items")
+        check(getattr(self._lib, self._PREFIX + "_set_items")(self._h, int(first), len(items), self._array(items)),
+              self._PREFIX + "_set_items")
         for k, it in enumerate(items):
-            self.sizes[first + k] = int(it.N)
+            self.sizes[first + k] = self._size(it)
+
+
+def batch_item_check(item: BatchItem) -> int:
+    """Status cavmd_batch_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_batch_item_check(ctypes.byref(item)))
+
+
+class Batch(_ItemTableHandle):
+    """Owns one cavmd_batch: B independent small systems evaluated by ONE kernel launch, one workgroup per system
+    (the reference's replica loop, examples/05_advanced_run.py:1570-1612, on one GPU).  Launched by N descending."""
+    _ITEM, _PREFIX = BatchItem, "cavmd_batch"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items, history_depth: int = 64):
+        self.history_depth = int(history_depth)
+        self._create(workspace, items, self.history_depth)
 
     def compute(self, stream: int = 0) -> None:
         check(self._lib.cavmd_batch_compute(self._h, ctypes.c_void_p(stream)), "cavmd_batch_compute")
@@ -732,53 +741,14 @@ def bussi_batch_input_make(deltaT, set_T, tau, normal_variate, gamma_variate) ->
     return row
 
 
-class BussiBatch:
+class BussiBatch(_ItemTableHandle):
     """Owns one cavmd_bussi_batch: the translational Bussi thermostat step of B independent small systems as ONE kernel
-    launch, one workgroup per system, its per-step inputs read from device memory.  Keeps its workspace alive."""
+    launch, one workgroup per system, its per-step inputs read from device memory.  Launched by n_members descending."""
+    _ITEM, _PREFIX = BussiBatchItem, "cavmd_bussi_batch"
+    _size = staticmethod(lambda it: int(it.n_members))
 
     def __init__(self, workspace: Workspace, items):
-        self._ws = workspace
-        self._lib = workspace._lib
-        items = list(items)
-        self.n_items = len(items)
-        self.sizes = [int(it.n_members) for it in items]
-        arr = (BussiBatchItem * max(self.n_items, 1))(*items)
-        self._h = ctypes.c_void_p()
-        check(self._lib.cavmd_bussi_batch_create(workspace.handle, self.n_items, arr, ctypes.byref(self._h)),
-              "cavmd_bussi_batch_create")
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def launch_order(self):
-        """Item indices in the order their workgroups start (n_members descending, stable), predicted by ``batch_launch_order``."""
-        return batch_launch_order(self.sizes)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if _capturing():
-                _deferred_bussi_batches.append((self._lib, self._h))
-            else:
-                self._lib.cavmd_bussi_batch_destroy(self._h)
-            self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
-                and not _capturing():
-            _destroy_deferred()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_items(self, first: int, items) -> None:
-        items = list(items)
-        arr = (BussiBatchItem * max(len(items), 1))(*items)
-        check(self._lib.cavmd_bussi_batch_set_items(self._h, int(first), len(items), arr), "cavmd_bussi_batch_set_items")
-        for k, it in enumerate(items):
-            self.sizes[first + k] = int(it.n_members)
+        self._create(workspace, items)
 
     def step(self, stream: int, inputs_ptr: int) -> None:
         """One kernel: the step of every item, inputs read from the n_items device rows at `inputs_ptr` when the kernel runs."""
@@ -825,58 +795,18 @@ def recorder_item_check(item: RecorderItem) -> int:
     return int(load().cavmd_recorder_item_check(ctypes.byref(item)))
 
 
-class Recorder:
+class Recorder(_ItemTableHandle):
     """Owns one cavmd_recorder: the per-step observables of B independent small systems appended, by ONE kernel launch per
     call, to a time series in device memory whose write position lives on the device (a graph replay appends a new row).
-    Keeps its workspace alive."""
+    Launched by max(N, n_members) descending."""
+    _ITEM, _PREFIX = RecorderItem, "cavmd_recorder"
+    _size = staticmethod(lambda it: max(int(it.N), int(it.n_members)))
 
     def __init__(self, workspace: Workspace, items, capacity: int, period: int, kB: float):
-        self._ws = workspace
-        self._lib = workspace._lib
-        items = list(items)
-        self.n_items = len(items)
         self.capacity, self.period, self.kB = int(capacity), int(period), float(kB)
-        self.sizes = [max(int(it.N), int(it.n_members)) for it in items]
-        arr = (RecorderItem * max(self.n_items, 1))(*items)
-        self._h = ctypes.c_void_p()
         if self.capacity < 0 or self.period < 0:
             raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_recorder_create")
-        check(self._lib.cavmd_recorder_create(workspace.handle, self.n_items, arr, self.capacity, self.period, self.kB,
-                                              ctypes.byref(self._h)), "cavmd_recorder_create")
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def launch_order(self):
-        """Item indices in the order their workgroups start (max(N, n_members) descending, stable), predicted by
-        ``batch_launch_order``."""
-        return batch_launch_order(self.sizes)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if _capturing():
-                _deferred_recorders.append((self._lib, self._h))
-            else:
-                self._lib.cavmd_recorder_destroy(self._h)
-            self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
-                and not _capturing():
-            _destroy_deferred()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_items(self, first: int, items) -> None:
-        items = list(items)
-        arr = (RecorderItem * max(len(items), 1))(*items)
-        check(self._lib.cavmd_recorder_set_items(self._h, int(first), len(items), arr), "cavmd_recorder_set_items")
-        for k, it in enumerate(items):
-            self.sizes[first + k] = max(int(it.N), int(it.n_members))
+        self._create(workspace, items, self.capacity, self.period, self.kB)
 
     def record(self, stream: int = 0) -> None:
         """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
@@ -924,65 +854,25 @@ def field_item_check(item: FieldItem) -> int:
     return int(load().cavmd_field_recorder_item_check(ctypes.byref(item)))
 
 
-class FieldRecorder:
+class FieldRecorder(_ItemTableHandle):
     """Owns one cavmd_field_recorder: rho(k) of B independent small systems, its correlation with each system's stored
     reference fields and the reference bookkeeping, appended by ONE kernel launch per call to a time series in device memory
-    (a graph replay appends a new row and takes references when they are due).  Keeps its workspace alive."""
+    (a graph replay appends a new row and takes references when they are due).  Launched by N descending."""
+    _ITEM, _PREFIX = FieldItem, "cavmd_field_recorder"
+    _size = staticmethod(lambda it: int(it.N))
 
     def __init__(self, workspace: Workspace, items, wavevectors, capacity: int, period: int, max_references: int,
                  reference_interval: int):
         import numpy as np
-        self._ws = workspace
-        self._lib = workspace._lib
-        items = list(items)
-        self.n_items = len(items)
         kv = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)
         self.n_k = int(kv.shape[0])
         self.capacity, self.period = int(capacity), int(period)
         self.max_references, self.reference_interval = int(max_references), int(reference_interval)
-        self.sizes = [int(it.N) for it in items]
-        arr = (FieldItem * max(self.n_items, 1))(*items)
-        self._h = ctypes.c_void_p()
         if self.capacity < 0 or self.period < 0 or self.max_references < 0 or self.reference_interval < 0 \
                 or self.max_references >= 2**32:
             raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_field_recorder_create")
-        check(self._lib.cavmd_field_recorder_create(workspace.handle, self.n_items, arr, self.n_k,
-                                                    ctypes.c_void_p(kv.ctypes.data), self.capacity, self.period,
-                                                    self.max_references, self.reference_interval, ctypes.byref(self._h)),
-              "cavmd_field_recorder_create")
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def launch_order(self):
-        """Item indices in the order their workgroups start (N descending, stable), predicted by ``batch_launch_order``."""
-        return batch_launch_order(self.sizes)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if _capturing():
-                _deferred_field_recorders.append((self._lib, self._h))
-            else:
-                self._lib.cavmd_field_recorder_destroy(self._h)
-            self._h = ctypes.c_void_p()
-        if (_deferred or _deferred_batches or _deferred_bussi_batches or _deferred_recorders or _deferred_field_recorders) \
-                and not _capturing():
-            _destroy_deferred()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_items(self, first: int, items) -> None:
-        items = list(items)
-        arr = (FieldItem * max(len(items), 1))(*items)
-        check(self._lib.cavmd_field_recorder_set_items(self._h, int(first), len(items), arr), "cavmd_field_recorder_set_items")
-        for k, it in enumerate(items):
-            self.sizes[first + k] = int(it.N)
+        self._create(workspace, items, self.n_k, ctypes.c_void_p(kv.ctypes.data), self.capacity, self.period,
+                     self.max_references, self.reference_interval)
 
     def record(self, stream: int = 0, take_reference_ptr: int = 0) -> None:
         """One kernel: every item's call counter moves; on every period-th call the item appends one row.

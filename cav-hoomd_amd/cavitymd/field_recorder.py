@@ -31,6 +31,8 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import stream_handle
+from .recorder import _SeriesRecorder
 from .observables import generate_fibonacci_sphere
 
 
@@ -42,16 +44,16 @@ def _position_tensor(t):
     return t
 
 
-class BatchFieldRecorder:
+class BatchFieldRecorder(_SeriesRecorder):
     """positions: one (N_k, 3) or (N_k, 4) device tensor of WRAPPED positions per system (HOOMD's Scalar4 pos is (N, 4)).
     wavevectors: (n_k, 3), ONE set for all systems; default ``kmag * generate_fibonacci_sphere(num_wavevectors)``, the
     reference tracker's.  An item keeps its last ``capacity`` rows; every ``period``-th ``record()`` writes one; at most
     ``max_references`` reference fields per system, a new one every ``reference_interval`` recorded rows (0: only the first)
     or when asked through ``take_reference``.  The defaults are the reference tracker's."""
+    _record_dtype = staticmethod(_capi.field_record_dtype)
 
     def __init__(self, positions, wavevectors=None, kmag: float = 1.0, num_wavevectors: int = 50, capacity: int = 4096,
                  period: int = 1, max_references: int = 10, reference_interval: int = 10000):
-        self._recorder = self._ws = None
         positions = list(positions)
         for t in positions:
             _position_tensor(t)   # CPU tensors are refused before anything else is looked at
@@ -81,15 +83,6 @@ class BatchFieldRecorder:
         self.max_references, self.reference_interval = int(max_references), int(reference_interval)
         self._take = None
 
-    def _need(self):
-        if self._recorder is None:
-            raise RuntimeError("BatchFieldRecorder used after close()")
-
-    def _enqueue_stream(self, stream) -> int:
-        if stream is None:
-            return torch.cuda.current_stream(self._device).cuda_stream
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-
     def record(self, stream=None, take_reference=None) -> None:
         """ONE kernel launch on ``stream`` (default: torch's current stream): nothing is waited for; may be captured.
         take_reference: None, or a uint32 / int32 device tensor of B words read when the kernel RUNS (so a captured call
@@ -105,36 +98,13 @@ class BatchFieldRecorder:
                 raise ValueError("take_reference: a contiguous int32 / uint32 tensor with one word per system")
             self._take = t   # kept alive for the kernel (and for the graph that captured it)
             ptr = t.data_ptr()
-        self._recorder.record(self._enqueue_stream(stream), ptr)
-
-    def _read_stream(self, stream) -> int:
-        """The stream a read synchronises.  Default: the whole device first (a graph replays on the stream it is launched
-        on, which need not be the one ``record`` was captured on), then torch's current stream."""
-        if stream is None:
-            torch.cuda.synchronize(self._device)
-            return torch.cuda.current_stream(self._device).cuda_stream
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-
-    def rows(self, stream=None) -> np.ndarray:
-        """Rows written per system since creation / reset, behind a synchronisation (see ``read``)."""
-        self._need()
-        return self._recorder.rows(self._read_stream(stream))
+        self._recorder.record(stream_handle(stream, self._device), ptr)
 
     def read(self, first=0, count=None, stream=None) -> np.ndarray:
         """Structured array of shape (B, n), dtype mirroring ``cavmd_field_record``: rows first .. first + count - 1 (0-based
         count of recorded rows) of every system; ``first=None`` starts at the oldest row still held.  Waits for the device
         (or, if given, for ``stream`` only); works the same before, between and after the replays of a graph."""
-        self._need()
-        handle = self._read_stream(stream)
-        if first is None or count is None:
-            rows = self._recorder.rows(handle)
-            if first is None:
-                first = max(int(rows.max()) - self.capacity, 0)
-            if count is None:
-                count = int(rows.min()) - int(first)
-            if count <= 0:
-                return np.zeros((self.n_systems, 0), dtype=_capi.field_record_dtype())
-        return self._recorder.read(handle, 0, self.n_systems, int(first), int(count))
+        return self._read(first, count, stream)
 
     def fields(self, item: int, stream=None):
         """(rho_now, rho_refs, ref_rows) of one system: the field of its last recorded call (complex, (n_k,)), its stored
@@ -145,21 +115,8 @@ class BatchFieldRecorder:
     def reset(self, stream=None) -> None:
         """Forget rows, counters and references of every system, ordered on ``stream`` (default: torch's current stream)."""
         self._need()
-        self._recorder.reset(self._enqueue_stream(stream))
+        self._recorder.reset(stream_handle(stream, self._device))
 
     @property
     def recorder(self) -> _capi.FieldRecorder:
         return self._recorder
-
-    def close(self) -> None:
-        if self._recorder is not None:
-            self._recorder.close()
-        if self._ws is not None:
-            self._ws.close()
-        self._recorder = self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

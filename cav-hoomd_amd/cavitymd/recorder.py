@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import member_indices, stream_handle
 from .utils import PhysicalConstants
 
 
@@ -37,11 +38,62 @@ def _device_tensor(t, what: str):
     return t
 
 
-class BatchRecorder:
+class _SeriesRecorder:
+    """What ``BatchRecorder`` and ``BatchFieldRecorder`` share: the stream a read waits for, the default window of
+    ``read()`` and the release.  A subclass sets ``_device``, ``_ws``, ``_recorder``, ``n_systems``, ``capacity`` and
+    ``_record_dtype`` (a function that gives the numpy dtype of one row)."""
+    _recorder = _ws = None
+
+    def _need(self):
+        if self._recorder is None:
+            raise RuntimeError(f"{type(self).__name__} used after close()")
+
+    def _read_stream(self, stream) -> int:
+        """The stream a read synchronises.  Default: the whole device first (a graph replays on the stream it is launched
+        on, which need not be the one ``record`` was captured on), then torch's current stream."""
+        if stream is None:
+            torch.cuda.synchronize(self._device)
+        return stream_handle(stream, self._device)
+
+    def rows(self, stream=None) -> np.ndarray:
+        """Rows written per system since creation / reset, behind a synchronisation (see ``read``)."""
+        self._need()
+        return self._recorder.rows(self._read_stream(stream))
+
+    def _read(self, first, count, stream) -> np.ndarray:
+        """first=None: the oldest row still held; count=None: up to the last row every system has."""
+        self._need()
+        handle = self._read_stream(stream)
+        if first is None or count is None:
+            rows = self._recorder.rows(handle)
+            if first is None:
+                first = max(int(rows.max()) - self.capacity, 0)
+            if count is None:
+                count = int(rows.min()) - int(first)
+            if count <= 0:
+                return np.zeros((self.n_systems, 0), dtype=self._record_dtype())
+        return self._recorder.read(handle, 0, self.n_systems, int(first), int(count))
+
+    def close(self) -> None:
+        if self._recorder is not None:
+            self._recorder.close()
+        if self._ws is not None:
+            self._ws.close()
+        self._recorder = self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchRecorder(_SeriesRecorder):
     """force_batch: the ``CavityForceBatch`` whose result blocks are recorded; velocities: one (N_k, 4) device tensor per
     system (mass in column 3), or None per system; net_forces: the same for the net force (None: ``force_mass_sum`` is 0);
     members: None, or per system None / an index array of the group ``kinetic_energy`` covers.  An item keeps its last
     ``capacity`` rows; every ``period``-th ``record()`` writes one."""
+    _record_dtype = staticmethod(_capi.record_dtype)
 
     def __init__(self, force_batch, velocities, net_forces=None, members=None, capacity: int = 4096, period: int = 1,
                  kB: float = PhysicalConstants.KB_HARTREE_PER_K):
@@ -84,10 +136,7 @@ class BatchRecorder:
             if m is None:
                 mt, n_members = None, (n if v is not None else 0)
             else:
-                idx = np.ascontiguousarray(m, dtype=np.uint32)
-                if idx.size and int(idx.max()) >= n:
-                    raise ValueError("a member index lies outside its velocity array")
-                mt, n_members = torch.from_numpy(idx.view(np.int32).copy()).to(dev), int(idx.shape[0])
+                mt, n_members = member_indices(m, n, dev)
             self._members.append(mt)
             items.append(_capi.recorder_item(results + result_bytes * k,
                                              v.data_ptr() if (v is not None and n) else 0,
@@ -101,70 +150,24 @@ class BatchRecorder:
         self._stream = 0
         torch.cuda.current_stream(dev).synchronize()   # the member lists are on the device before any stream records
 
-    def _need(self):
-        if self._recorder is None:
-            raise RuntimeError("BatchRecorder used after close()")
-
     def record(self, stream=None) -> None:
         """ONE kernel launch on ``stream`` (default: torch's current stream): nothing is waited for; may be captured."""
         self._need()
-        if stream is None:
-            handle = torch.cuda.current_stream(self._device).cuda_stream
-        else:
-            handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        handle = stream_handle(stream, self._device)
         self._recorder.record(handle)
         self._stream = handle
-
-    def _read_stream(self, stream) -> int:
-        """The stream a read synchronises.  Default: the whole device first (a graph replays on the stream it is launched
-        on, which need not be the one ``record`` was captured on), then torch's current stream."""
-        if stream is None:
-            torch.cuda.synchronize(self._device)
-            return torch.cuda.current_stream(self._device).cuda_stream
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-
-    def rows(self, stream=None) -> np.ndarray:
-        """Rows written per system since creation / reset, behind a synchronisation (see ``read``)."""
-        self._need()
-        return self._recorder.rows(self._read_stream(stream))
 
     def read(self, first=None, count=None, stream=None) -> np.ndarray:
         """Structured array of shape (B, n), dtype mirroring ``cavmd_record``: rows first .. first + count - 1 (0-based count
         of recorded rows) of every system.  Default: everything still held.  Waits for the device (or, if given, for
         ``stream`` only); works the same before, between and after the replays of a graph, never inside a capture."""
-        self._need()
-        handle = self._read_stream(stream)
-        if first is None or count is None:
-            rows = self._recorder.rows(handle)
-            if first is None:
-                first = max(int(rows.max()) - self.capacity, 0)
-            if count is None:
-                count = int(rows.min()) - int(first)
-            if count <= 0:
-                return np.zeros((self.n_systems, 0), dtype=_capi.record_dtype())
-        return self._recorder.read(handle, 0, self.n_systems, int(first), int(count))
+        return self._read(first, count, stream)
 
     def reset(self, stream=None) -> None:
         """Zero every system's counters, ordered on ``stream`` (default: torch's current stream)."""
         self._need()
-        if stream is None:
-            handle = torch.cuda.current_stream(self._device).cuda_stream
-        else:
-            handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._recorder.reset(handle)
+        self._recorder.reset(stream_handle(stream, self._device))
 
     @property
     def recorder(self) -> _capi.Recorder:
         return self._recorder
-
-    def close(self) -> None:
-        if self._recorder is not None:
-            self._recorder.close()
-            self._ws.close()
-        self._recorder = self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

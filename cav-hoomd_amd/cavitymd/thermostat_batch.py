@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import member_indices, stream_handle
 
 
 def _per_system(value, n: int, name: str):
@@ -72,10 +73,7 @@ class BussiReservoirBatch:
             if m is None:
                 mt, n = None, int(v.shape[0])
             else:
-                idx = np.ascontiguousarray(m, dtype=np.uint32)
-                if idx.size and int(idx.max()) >= v.shape[0]:
-                    raise ValueError("a member index lies outside its velocity array")
-                mt, n = torch.from_numpy(idx.view(np.int32).copy()).to(dev), int(idx.shape[0])
+                mt, n = member_indices(m, v.shape[0], dev)
             self._members.append(mt)
             items.append(_capi.bussi_batch_item(v.data_ptr() if v.shape[0] else 0,
                                                 mt.data_ptr() if (mt is not None and n) else 0, n, dof))
@@ -156,10 +154,7 @@ class BussiReservoirBatch:
         """ONE kernel launch: kinetic energy -> alpha -> counters -> velocities *= alpha for every system, from ``inputs`` as
         it is when the kernel runs.  Nothing is waited for; may be captured into a graph."""
         self._need()
-        if stream is None:
-            handle = torch.cuda.current_stream(self.inputs.device).cuda_stream
-        else:
-            handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        handle = stream_handle(stream, self.inputs.device)
         self._batch.step(handle, self.inputs.data_ptr())
         self._stream = handle
 

@@ -1889,32 +1889,14 @@ int cavmd_version(void)
 // nothing else.
 } // extern "C"
 
+#include "cavmd_item_table.hpp" // how the table of the four batch objects below lives on the host and on the device
+
 namespace
 {
 constexpr int kBatchBlock = kSmallBlock; // the block size of cavity_small_system_kernel: the two paths share bits
 constexpr size_t kBatchRingMaxBytes = (size_t)64 << 20;
 static_assert(sizeof(cavmd_batch_item) == 128, "batch item layout");
-} // namespace
 
-struct cavmd_batch
-{
-    int device = -1;
-    size_t n = 0;
-    unsigned depth = 0;
-    std::vector<cavmd_batch_item> items; // host copy of the table, as the caller gave it
-    std::vector<unsigned> order;         // items by N descending, stable
-    BatchRow* d_rows = nullptr;
-    unsigned* d_order = nullptr;
-    cavmd_result* d_result = nullptr;    // n blocks, indexed by item
-    HostResult* h_ring = nullptr;        // pinned + mapped: depth x n blocks; evaluation s, item i -> (s % depth) * n + i
-    HostResult* h_ring_dev = nullptr;
-    hipStream_t last_stream = nullptr;
-    uint64_t sequence = 0;
-    bool captured = false; // some evaluation was enqueued into a stream capture: the stamps cannot tell replays apart
-};
-
-namespace
-{
 BatchRow batch_row(const cavmd_batch_item& it)
 {
     BatchRow r;
@@ -1930,27 +1912,22 @@ BatchRow batch_row(const cavmd_batch_item& it)
     r.L_typeid = it.L_typeid;
     return r;
 }
+} // namespace
 
-// Launch order: items by N descending, ties in item order (the hardware starts workgroups in blockIdx order, so the long
-// systems of a ragged batch go first and the short ones fill in behind them).
-std::vector<unsigned> batch_order(const std::vector<cavmd_batch_item>& items)
+struct cavmd_batch : ItemTable<cavmd_batch_item, BatchRow> // launched by N descending
 {
-    // counting would do; B <= 65536 and this is set-up time
-    std::vector<unsigned> order(items.size());
-    for (size_t i = 0; i < items.size(); ++i)
-        order[i] = (unsigned)i;
-    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) { return items[x].N > items[y].N; });
-    return order;
-}
+    unsigned depth = 0;
+    cavmd_result* d_result = nullptr;    // n blocks, indexed by item
+    HostResult* h_ring = nullptr;        // pinned + mapped: depth x n blocks; evaluation s, item i -> (s % depth) * n + i
+    HostResult* h_ring_dev = nullptr;
+    uint64_t sequence = 0;
+    bool captured = false; // some evaluation was enqueued into a stream capture: the stamps cannot tell replays apart
 
-bool stream_capturing(hipStream_t stream)
+    cavmd_batch() : ItemTable(cavmd_batch_item_check, [](const cavmd_batch_item& it) { return it.N; }, batch_row) {}
+};
+
+namespace
 {
-    if (stream == nullptr) // the null stream cannot be captured
-        return false;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
 inline const HostResult* batch_slot(const cavmd_batch* b, uint64_t s)
 {
     return b->h_ring + (s % b->depth) * b->n;
@@ -1991,12 +1968,9 @@ int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_it
     if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || history_depth < 2
         || history_depth > (int)kResultHistoryMax)
         return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        const int st = cavmd_batch_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
+    const int st = check_items(h_items, n_items, cavmd_batch_item_check);
+    if (st != CAVMD_OK)
+        return st;
     const size_t ring_blocks = (size_t)history_depth * n_items;
     if (ring_blocks * sizeof(HostResult) > kBatchRingMaxBytes)
         return CAVMD_ERR_CAPACITY;
@@ -2004,23 +1978,11 @@ int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_it
     cavmd_batch* b = new (std::nothrow) cavmd_batch();
     if (!b)
         return (int)hipErrorOutOfMemory;
-    b->device = ws->device;
-    b->n = n_items;
+    b->adopt(ws->device, h_items, n_items);
     b->depth = (unsigned)history_depth;
-    b->items.assign(h_items, h_items + n_items);
-    b->order = batch_order(b->items);
-    std::vector<BatchRow> rows(n_items);
-    for (size_t i = 0; i < n_items; ++i)
-        rows[i] = batch_row(b->items[i]);
 
     DeviceGuard guard(b->device);
-    hipError_t e = hipMalloc((void**)&b->d_rows, sizeof(BatchRow) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->d_rows, rows.data(), sizeof(BatchRow) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&b->d_order, sizeof(unsigned) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    hipError_t e = b->upload();
     if (e == hipSuccess)
         e = hipMalloc((void**)&b->d_result, sizeof(cavmd_result) * n_items);
     if (e == hipSuccess)
@@ -2044,13 +2006,7 @@ int cavmd_batch_destroy(cavmd_batch* b)
     if (!b)
         return CAVMD_OK;
     DeviceGuard guard(b->device);
-    // the kernels in flight read the table and write the ring: let them finish (a capturing stream cannot be waited for)
-    if (b->sequence && !stream_capturing(b->last_stream))
-        (void)hipStreamSynchronize(b->last_stream);
-    if (b->d_rows)
-        (void)hipFree(b->d_rows);
-    if (b->d_order)
-        (void)hipFree(b->d_order);
+    b->quiesce_and_free();
     if (b->d_result)
         (void)hipFree(b->d_result);
     if (b->h_ring)
@@ -2061,41 +2017,7 @@ int cavmd_batch_destroy(cavmd_batch* b)
 
 int cavmd_batch_set_items(cavmd_batch* b, size_t first, size_t count, const cavmd_batch_item* h_items)
 {
-    if (!b || !h_items || count == 0 || first >= b->n || count > b->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = cavmd_batch_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
-    DeviceGuard guard(b->device);
-    if (b->sequence)
-    {
-        if (stream_capturing(b->last_stream))
-            return CAVMD_ERR_INVALID_VALUE;
-        CAVMD_HIP_TRY(hipStreamSynchronize(b->last_stream)); // evaluations in flight read the rows this call rewrites
-    }
-    // the new table and order are built aside and committed only after both copies went through: a failed copy leaves the
-    // host's view and (up to the rows already overwritten by a copy that died half-way) the device's as they were
-    std::vector<cavmd_batch_item> items(b->items);
-    std::vector<BatchRow> rows(count);
-    for (size_t i = 0; i < count; ++i)
-    {
-        items[first + i] = h_items[i];
-        rows[i] = batch_row(h_items[i]);
-    }
-    const std::vector<unsigned> order = batch_order(items);
-    CAVMD_HIP_TRY(hipMemcpy(b->d_order, order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice));
-    const hipError_t e = hipMemcpy(b->d_rows + first, rows.data(), sizeof(BatchRow) * count, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice); // the old order back
-        return (int)e;
-    }
-    b->items.swap(items);
-    b->order = order;
-    return CAVMD_OK;
+    return b ? b->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_batch_compute(cavmd_batch* b, void* stream_)
@@ -2116,7 +2038,7 @@ int cavmd_batch_compute(cavmd_batch* b, void* stream_)
         b->sequence -= 1;
         return st;
     }
-    b->last_stream = stream;
+    b->enqueued_on(stream);
     return CAVMD_OK;
 }
 
@@ -2238,22 +2160,21 @@ int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out)
 } // extern "C"
 
 // ---- the Bussi thermostat step of a batch of independent small systems in one launch (cavmd_bussi_batch_kernel.hpp) ---------
-struct cavmd_bussi_batch
+struct cavmd_bussi_batch : ItemTable<cavmd_bussi_batch_item, BussiBatchRow> // launched by n_members descending
 {
     cavmd_workspace* ws = nullptr;
-    int device = -1;
-    size_t n = 0;
-    std::vector<cavmd_bussi_batch_item> items; // host copy of the table, as the caller gave it
-    std::vector<unsigned> order;               // items by n_members descending, stable
     std::vector<uint64_t> refused_seen;        // per item: refusals already reported to the caller
-    BussiBatchRow* d_rows = nullptr;
-    unsigned* d_order = nullptr;
     BussiDevice* d_state = nullptr;            // n states, indexed by item
     HostBussiBatch* h_blocks = nullptr;        // pinned + mapped + coherent: n blocks, indexed by item
     HostBussiBatch* h_blocks_dev = nullptr;
-    hipStream_t last_stream = nullptr;
     uint64_t sequence = 0;
     bool captured = false; // some step was enqueued into a stream capture: the stamps cannot tell replays apart
+
+    cavmd_bussi_batch()
+        : ItemTable(cavmd_bussi_batch_item_check, [](const cavmd_bussi_batch_item& it) { return it.n_members; },
+                    uploaded_as_it_is<cavmd_bussi_batch_item, BussiBatchRow>)
+    {
+    }
 };
 
 namespace
@@ -2266,16 +2187,6 @@ static_assert(sizeof(cavmd_bussi_batch_input) == sizeof(BussiBatchInput) && offs
               "thermostat batch input layout");
 static_assert(sizeof(cavmd_bussi_device_state) == sizeof(BussiDevice), "the device states are read out as they are");
 static_assert(CAVMD_BATCH_MAX_ITEM_N <= kBussiBatchMaxTiles * 256 * kBussiBatchUnroll, "one LDS partial per tile");
-
-std::vector<unsigned> bussi_batch_order(const std::vector<cavmd_bussi_batch_item>& items)
-{
-    std::vector<unsigned> order(items.size());
-    for (size_t i = 0; i < items.size(); ++i)
-        order[i] = (unsigned)i;
-    std::stable_sort(order.begin(), order.end(),
-                     [&items](unsigned x, unsigned y) { return items[x].n_members > items[y].n_members; });
-    return order;
-}
 
 void bussi_state_out(cavmd_bussi_device_state* out, const BussiDevice& s)
 {
@@ -2333,29 +2244,17 @@ int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bu
     *out = nullptr;
     if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
         return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        const int st = cavmd_bussi_batch_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
+    const int st = check_items(h_items, n_items, cavmd_bussi_batch_item_check);
+    if (st != CAVMD_OK)
+        return st;
     cavmd_bussi_batch* b = new (std::nothrow) cavmd_bussi_batch();
     if (!b)
         return (int)hipErrorOutOfMemory;
-    b->device = ws->device;
-    b->n = n_items;
-    b->items.assign(h_items, h_items + n_items);
-    b->order = bussi_batch_order(b->items);
+    b->adopt(ws->device, h_items, n_items);
     b->refused_seen.assign(n_items, 0);
 
     DeviceGuard guard(b->device);
-    hipError_t e = hipMalloc((void**)&b->d_rows, sizeof(BussiBatchRow) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->d_rows, b->items.data(), sizeof(BussiBatchRow) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&b->d_order, sizeof(unsigned) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    hipError_t e = b->upload();
     if (e == hipSuccess)
         e = hipMalloc((void**)&b->d_state, sizeof(BussiDevice) * n_items);
     if (e == hipSuccess)
@@ -2381,13 +2280,7 @@ int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
     if (!b)
         return CAVMD_OK;
     DeviceGuard guard(b->device);
-    // the kernels in flight read the table and write the blocks: let them finish (a capturing stream cannot be waited for)
-    if (b->sequence && !stream_capturing(b->last_stream))
-        (void)hipStreamSynchronize(b->last_stream);
-    if (b->d_rows)
-        (void)hipFree(b->d_rows);
-    if (b->d_order)
-        (void)hipFree(b->d_order);
+    b->quiesce_and_free();
     if (b->d_state)
         (void)hipFree(b->d_state);
     if (b->h_blocks)
@@ -2400,36 +2293,7 @@ int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
 
 int cavmd_bussi_batch_set_items(cavmd_bussi_batch* b, size_t first, size_t count, const cavmd_bussi_batch_item* h_items)
 {
-    if (!b || !h_items || count == 0 || first >= b->n || count > b->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = cavmd_bussi_batch_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
-    DeviceGuard guard(b->device);
-    if (b->sequence)
-    {
-        if (stream_capturing(b->last_stream))
-            return CAVMD_ERR_INVALID_VALUE;
-        CAVMD_HIP_TRY(hipStreamSynchronize(b->last_stream)); // steps in flight read the rows this call rewrites
-    }
-    // built aside and committed only after both copies went through (as cavmd_batch_set_items)
-    std::vector<cavmd_bussi_batch_item> items(b->items);
-    for (size_t i = 0; i < count; ++i)
-        items[first + i] = h_items[i];
-    const std::vector<unsigned> order = bussi_batch_order(items);
-    CAVMD_HIP_TRY(hipMemcpy(b->d_order, order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice));
-    const hipError_t e = hipMemcpy(b->d_rows + first, h_items, sizeof(BussiBatchRow) * count, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipMemcpy(b->d_order, b->order.data(), sizeof(unsigned) * b->n, hipMemcpyHostToDevice); // the old order back
-        return (int)e;
-    }
-    b->items.swap(items);
-    b->order = order;
-    return CAVMD_OK;
+    return b ? b->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_bussi_batch_input* d_inputs)
@@ -2449,7 +2313,7 @@ int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_buss
         b->sequence -= 1;
         return st;
     }
-    b->last_stream = stream;
+    b->enqueued_on(stream);
     return CAVMD_OK;
 }
 
@@ -2539,22 +2403,19 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
 } // extern "C"
 
 // ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
-struct cavmd_recorder
+// launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
+struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_record>
 {
     cavmd_workspace* ws = nullptr;
-    int device = -1;
-    size_t n = 0;
-    size_t capacity = 0;
     uint64_t period = 1;
     double kB = 0.0;
-    std::vector<cavmd_recorder_item> items; // host copy of the table, as the caller gave it
-    std::vector<unsigned> order;            // items by max(N, n_members) descending, stable
-    RecorderRow* d_rows = nullptr;
-    unsigned* d_order = nullptr;
-    cavmd_record* d_series = nullptr;       // n x capacity records, item-major
-    uint64_t* d_counters = nullptr;         // kRecCounters arrays of n words: rows, calls, phase, slot
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;                  // some record call was enqueued: last_stream means something
+
+    cavmd_recorder()
+        : SeriesTable(kRecCounters, cavmd_recorder_item_check,
+                      [](const cavmd_recorder_item& it) { return std::max(it.N, it.n_members); },
+                      uploaded_as_it_is<cavmd_recorder_item, RecorderRow>)
+    {
+    }
 };
 
 namespace
@@ -2571,26 +2432,7 @@ static_assert(offsetof(cavmd_recorder_item, d_result) == offsetof(RecorderRow, r
                   && offsetof(cavmd_recorder_item, n_members) == offsetof(RecorderRow, n_members),
               "recorder item layout");
 static_assert(CAVMD_BATCH_MAX_ITEM_N <= kRecorderMaxTiles * 256 * kRecorderUnroll, "one LDS partial per tile");
-
-std::vector<unsigned> recorder_order(const std::vector<cavmd_recorder_item>& items)
-{
-    std::vector<unsigned> order(items.size());
-    for (size_t i = 0; i < items.size(); ++i)
-        order[i] = (unsigned)i;
-    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) {
-        return std::max(items[x].N, items[x].n_members) > std::max(items[y].N, items[y].n_members);
-    });
-    return order;
-}
-
-// waits for what was recorded on `stream`; a capturing stream cannot be waited for
-int recorder_sync(cavmd_recorder* r, hipStream_t stream)
-{
-    if (stream_capturing(stream))
-        return CAVMD_ERR_INVALID_VALUE;
-    CAVMD_HIP_TRY(hipStreamSynchronize(stream));
-    return CAVMD_OK;
-}
+static_assert(kRecRows == 0 && kFldRows == 0, "SeriesTable: the rows-written array is the first of the counters");
 } // namespace
 
 extern "C"
@@ -2620,43 +2462,23 @@ int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recor
     if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || capacity == 0 || period == 0 || !(kB > 0.0)
         || !std::isfinite(kB))
         return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        const int st = cavmd_recorder_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
+    const int st = check_items(h_items, n_items, cavmd_recorder_item_check);
+    if (st != CAVMD_OK)
+        return st;
     if (capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items)
         return CAVMD_ERR_CAPACITY;
     cavmd_recorder* r = new (std::nothrow) cavmd_recorder();
     if (!r)
         return (int)hipErrorOutOfMemory;
-    r->device = ws->device;
-    r->n = n_items;
+    r->adopt(ws->device, h_items, n_items);
     r->capacity = capacity;
     r->period = period;
     r->kB = kB;
-    r->items.assign(h_items, h_items + n_items);
-    r->order = recorder_order(r->items);
 
     DeviceGuard guard(r->device);
-    const size_t series_bytes = sizeof(cavmd_record) * n_items * capacity;
-    const size_t counter_bytes = sizeof(uint64_t) * kRecCounters * n_items;
-    hipError_t e = hipMalloc((void**)&r->d_rows, sizeof(RecorderRow) * n_items);
+    hipError_t e = r->upload();
     if (e == hipSuccess)
-        e = hipMemcpy(r->d_rows, r->items.data(), sizeof(RecorderRow) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_order, sizeof(unsigned) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_series, series_bytes);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_series, 0, series_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_counters, counter_bytes);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_counters, 0, counter_bytes);
+        e = r->alloc_series();
     if (e == hipSuccess)
         e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
     if (e != hipSuccess)
@@ -2675,17 +2497,8 @@ int cavmd_recorder_destroy(cavmd_recorder* r)
     if (!r)
         return CAVMD_OK;
     DeviceGuard guard(r->device);
-    // the kernels in flight read the table and write the series: let them finish (a capturing stream cannot be waited for)
-    if (r->recorded && !stream_capturing(r->last_stream))
-        (void)hipStreamSynchronize(r->last_stream);
-    if (r->d_rows)
-        (void)hipFree(r->d_rows);
-    if (r->d_order)
-        (void)hipFree(r->d_order);
-    if (r->d_series)
-        (void)hipFree(r->d_series);
-    if (r->d_counters)
-        (void)hipFree(r->d_counters);
+    r->quiesce_and_free();
+    r->free_series();
     if (r->ws)
         r->ws->recorders -= 1;
     delete r;
@@ -2694,36 +2507,7 @@ int cavmd_recorder_destroy(cavmd_recorder* r)
 
 int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, const cavmd_recorder_item* h_items)
 {
-    if (!r || !h_items || count == 0 || first >= r->n || count > r->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = cavmd_recorder_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
-    DeviceGuard guard(r->device);
-    if (r->recorded)
-    {
-        if (stream_capturing(r->last_stream))
-            return CAVMD_ERR_INVALID_VALUE;
-        CAVMD_HIP_TRY(hipStreamSynchronize(r->last_stream)); // record calls in flight read the rows this call rewrites
-    }
-    // built aside and committed only after both copies went through (as cavmd_bussi_batch_set_items)
-    std::vector<cavmd_recorder_item> items(r->items);
-    for (size_t i = 0; i < count; ++i)
-        items[first + i] = h_items[i];
-    const std::vector<unsigned> order = recorder_order(items);
-    CAVMD_HIP_TRY(hipMemcpy(r->d_order, order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice));
-    const hipError_t e = hipMemcpy(r->d_rows + first, h_items, sizeof(RecorderRow) * count, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice); // the old order back
-        return (int)e;
-    }
-    r->items.swap(items);
-    r->order = order;
-    return CAVMD_OK;
+    return r ? r->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
@@ -2737,21 +2521,13 @@ int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
-    r->last_stream = stream;
-    r->recorded = true;
+    r->enqueued_on(stream);
     return CAVMD_OK;
 }
 
 int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
 {
-    if (!r || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    const int st = recorder_sync(r, (hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(hipMemcpy(out, r->d_counters + (size_t)kRecRows * r->n, sizeof(uint64_t) * r->n, hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return (r && out) ? r->rows((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_recorder_read(cavmd_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
@@ -2759,80 +2535,40 @@ int cavmd_recorder_read(cavmd_recorder* r, void* stream_, size_t first_item, siz
 {
     if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
         return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    const int st = recorder_sync(r, (hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    std::vector<uint64_t> rows(n_items);
-    CAVMD_HIP_TRY(hipMemcpy(rows.data(), r->d_counters + (size_t)kRecRows * r->n + first_item, sizeof(uint64_t) * n_items,
-                            hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_items; ++k)
-    {
-        if (rows[k] == 0)
-            return CAVMD_ERR_NOT_COMPUTED;
-        if (first_row >= rows[k] || n_rows > rows[k] - first_row)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (rows[k] > r->capacity && first_row < rows[k] - r->capacity)
-            return CAVMD_ERR_EXPIRED;
-    }
-    // row j of an item sits in slot j % capacity of that item's stretch: at most two runs of slots, each fetched for all the
-    // items with one strided copy
-    const size_t rec = sizeof(cavmd_record);
-    const size_t slot0 = (size_t)(first_row % r->capacity);
-    const size_t run0 = std::min(n_rows, r->capacity - slot0);
-    const cavmd_record* src = r->d_series + first_item * r->capacity;
-    CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, r->capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
-    if (run0 < n_rows)
-        CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, r->capacity * rec, (n_rows - run0) * rec, n_items,
-                                  hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
 }
 
 int cavmd_recorder_reset(cavmd_recorder* r, void* stream_)
 {
-    if (!r)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    CAVMD_HIP_TRY(hipMemsetAsync(r->d_counters, 0, sizeof(uint64_t) * kRecCounters * r->n, (hipStream_t)stream_));
-    return CAVMD_OK;
+    return r ? r->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows)
 {
-    if (!r || (!records && !rows))
-        return CAVMD_ERR_INVALID_VALUE;
-    if (records)
-        *records = r->d_series;
-    if (rows)
-        *rows = r->d_counters + (size_t)kRecRows * r->n;
-    return CAVMD_OK;
+    return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
 }
 
 } // extern "C"
 
 // ---- density field and F(k,t) of a batch recorded into a time series in device memory (cavmd_field_recorder_kernel.hpp) -------
-struct cavmd_field_recorder
+// launched by N descending; kFldCounters words per item
+struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_field_record>
 {
     cavmd_workspace* ws = nullptr;
-    int device = -1;
-    size_t n = 0;
     size_t n_k = 0;
-    size_t capacity = 0;
     uint64_t period = 1;
     unsigned max_refs = 1;
     uint64_t interval = 0;
-    std::vector<cavmd_field_item> items; // host copy of the table, as the caller gave it
-    std::vector<unsigned> order;         // items by N descending, stable
-    FieldRow* d_rows = nullptr;
-    unsigned* d_order = nullptr;
-    double* d_kvec = nullptr;               // n_k x 3
-    cavmd_field_record* d_series = nullptr; // n x capacity records, item-major
-    uint64_t* d_counters = nullptr;         // kFldCounters arrays of n words
-    uint64_t* d_ref_rows = nullptr;         // n x max_refs: the row each reference was taken at
-    double* d_now = nullptr;                // n x n_k x 2: the field of the last recorded call
-    double* d_refs = nullptr;               // n x max_refs x n_k x 2
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
+    double* d_kvec = nullptr;       // n_k x 3
+    uint64_t* d_ref_rows = nullptr; // n x max_refs: the row each reference was taken at
+    double* d_now = nullptr;        // n x n_k x 2: the field of the last recorded call
+    double* d_refs = nullptr;       // n x max_refs x n_k x 2
+
+    cavmd_field_recorder()
+        : SeriesTable(kFldCounters, cavmd_field_recorder_item_check, [](const cavmd_field_item& it) { return it.N; },
+                      uploaded_as_it_is<cavmd_field_item, FieldRow>)
+    {
+    }
 };
 
 namespace
@@ -2846,23 +2582,6 @@ static_assert(offsetof(cavmd_field_item, d_position) == offsetof(FieldRow, pos)
                   && offsetof(cavmd_field_item, position_stride) == offsetof(FieldRow, stride)
                   && offsetof(cavmd_field_item, N) == offsetof(FieldRow, N),
               "field item layout");
-
-std::vector<unsigned> field_recorder_order(const std::vector<cavmd_field_item>& items)
-{
-    std::vector<unsigned> order(items.size());
-    for (size_t i = 0; i < items.size(); ++i)
-        order[i] = (unsigned)i;
-    std::stable_sort(order.begin(), order.end(), [&items](unsigned x, unsigned y) { return items[x].N > items[y].N; });
-    return order;
-}
-
-int field_recorder_sync(hipStream_t stream)
-{
-    if (stream_capturing(stream))
-        return CAVMD_ERR_INVALID_VALUE;
-    CAVMD_HIP_TRY(hipStreamSynchronize(stream));
-    return CAVMD_OK;
-}
 } // namespace
 
 extern "C"
@@ -2898,12 +2617,9 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
     for (size_t i = 0; i < 3 * n_k; ++i)
         if (!std::isfinite(h_wavevectors[i]))
             return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        const int st = cavmd_field_recorder_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
+    const int st = check_items(h_items, n_items, cavmd_field_recorder_item_check);
+    if (st != CAVMD_OK)
+        return st;
     // series + fields (the current one and the references) within the recorder's cap
     const size_t field_bytes = sizeof(double) * 2 * n_k;
     const size_t fields_per_item = field_bytes * ((size_t)max_references + 1);
@@ -2913,39 +2629,22 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
     cavmd_field_recorder* r = new (std::nothrow) cavmd_field_recorder();
     if (!r)
         return (int)hipErrorOutOfMemory;
-    r->device = ws->device;
-    r->n = n_items;
+    r->adopt(ws->device, h_items, n_items);
     r->n_k = n_k;
     r->capacity = capacity;
     r->period = period;
     r->max_refs = max_references;
     r->interval = reference_interval;
-    r->items.assign(h_items, h_items + n_items);
-    r->order = field_recorder_order(r->items);
 
     DeviceGuard guard(r->device);
-    const size_t series_bytes = sizeof(cavmd_field_record) * n_items * capacity;
-    const size_t counter_bytes = sizeof(uint64_t) * kFldCounters * n_items;
     const size_t ref_row_bytes = sizeof(uint64_t) * n_items * max_references;
-    hipError_t e = hipMalloc((void**)&r->d_rows, sizeof(FieldRow) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(r->d_rows, r->items.data(), sizeof(FieldRow) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_order, sizeof(unsigned) * n_items);
-    if (e == hipSuccess)
-        e = hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * n_items, hipMemcpyHostToDevice);
+    hipError_t e = r->upload();
     if (e == hipSuccess)
         e = hipMalloc((void**)&r->d_kvec, sizeof(double) * 3 * n_k);
     if (e == hipSuccess)
         e = hipMemcpy(r->d_kvec, h_wavevectors, sizeof(double) * 3 * n_k, hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_series, series_bytes);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_series, 0, series_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_counters, counter_bytes);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_counters, 0, counter_bytes);
+        e = r->alloc_series();
     if (e == hipSuccess)
         e = hipMalloc((void**)&r->d_ref_rows, ref_row_bytes);
     if (e == hipSuccess)
@@ -2976,11 +2675,9 @@ int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
     if (!r)
         return CAVMD_OK;
     DeviceGuard guard(r->device);
-    // the kernels in flight read the table and write the series: let them finish (a capturing stream cannot be waited for)
-    if (r->recorded && !stream_capturing(r->last_stream))
-        (void)hipStreamSynchronize(r->last_stream);
-    for (void* p : {(void*)r->d_rows, (void*)r->d_order, (void*)r->d_kvec, (void*)r->d_series, (void*)r->d_counters,
-                    (void*)r->d_ref_rows, (void*)r->d_now, (void*)r->d_refs})
+    r->quiesce_and_free();
+    r->free_series();
+    for (void* p : {(void*)r->d_kvec, (void*)r->d_ref_rows, (void*)r->d_now, (void*)r->d_refs})
         if (p)
             (void)hipFree(p);
     if (r->ws)
@@ -2991,36 +2688,7 @@ int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
 
 int cavmd_field_recorder_set_items(cavmd_field_recorder* r, size_t first, size_t count, const cavmd_field_item* h_items)
 {
-    if (!r || !h_items || count == 0 || first >= r->n || count > r->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = cavmd_field_recorder_item_check(h_items + i);
-        if (st != CAVMD_OK)
-            return st;
-    }
-    DeviceGuard guard(r->device);
-    if (r->recorded)
-    {
-        if (stream_capturing(r->last_stream))
-            return CAVMD_ERR_INVALID_VALUE;
-        CAVMD_HIP_TRY(hipStreamSynchronize(r->last_stream)); // record calls in flight read the rows this call rewrites
-    }
-    // built aside and committed only after both copies went through (as cavmd_recorder_set_items)
-    std::vector<cavmd_field_item> items(r->items);
-    for (size_t i = 0; i < count; ++i)
-        items[first + i] = h_items[i];
-    const std::vector<unsigned> order = field_recorder_order(items);
-    CAVMD_HIP_TRY(hipMemcpy(r->d_order, order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice));
-    const hipError_t e = hipMemcpy(r->d_rows + first, h_items, sizeof(FieldRow) * count, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipMemcpy(r->d_order, r->order.data(), sizeof(unsigned) * r->n, hipMemcpyHostToDevice); // the old order back
-        return (int)e;
-    }
-    r->items.swap(items);
-    r->order = order;
-    return CAVMD_OK;
+    return r ? r->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const uint32_t* d_take_reference)
@@ -3036,21 +2704,13 @@ int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const ui
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
-    r->last_stream = stream;
-    r->recorded = true;
+    r->enqueued_on(stream);
     return CAVMD_OK;
 }
 
 int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream_, uint64_t* out)
 {
-    if (!r || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    const int st = field_recorder_sync((hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(hipMemcpy(out, r->d_counters + (size_t)kFldRows * r->n, sizeof(uint64_t) * r->n, hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return (r && out) ? r->rows((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_field_recorder_read(cavmd_field_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row,
@@ -3058,32 +2718,7 @@ int cavmd_field_recorder_read(cavmd_field_recorder* r, void* stream_, size_t fir
 {
     if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
         return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    const int st = field_recorder_sync((hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    std::vector<uint64_t> rows(n_items);
-    CAVMD_HIP_TRY(hipMemcpy(rows.data(), r->d_counters + (size_t)kFldRows * r->n + first_item, sizeof(uint64_t) * n_items,
-                            hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_items; ++k)
-    {
-        if (rows[k] == 0)
-            return CAVMD_ERR_NOT_COMPUTED;
-        if (first_row >= rows[k] || n_rows > rows[k] - first_row)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (rows[k] > r->capacity && first_row < rows[k] - r->capacity)
-            return CAVMD_ERR_EXPIRED;
-    }
-    // row j of an item sits in slot j % capacity of that item's stretch: at most two runs of slots (cavmd_recorder_read's)
-    const size_t rec = sizeof(cavmd_field_record);
-    const size_t slot0 = (size_t)(first_row % r->capacity);
-    const size_t run0 = std::min(n_rows, r->capacity - slot0);
-    const cavmd_field_record* src = r->d_series + first_item * r->capacity;
-    CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, r->capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
-    if (run0 < n_rows)
-        CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, r->capacity * rec, (n_rows - run0) * rec, n_items,
-                                  hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
 }
 
 int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, size_t item, double* rho_now, double* rho_refs,
@@ -3092,7 +2727,7 @@ int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, siz
     if (!r || !n_refs || item >= r->n)
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(r->device);
-    const int st = field_recorder_sync((hipStream_t)stream_);
+    const int st = sync_uncaptured((hipStream_t)stream_);
     if (st != CAVMD_OK)
         return st;
     uint64_t rows = 0, refs = 0;
@@ -3116,22 +2751,12 @@ int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, siz
 
 int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream_)
 {
-    if (!r)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(r->device);
-    CAVMD_HIP_TRY(hipMemsetAsync(r->d_counters, 0, sizeof(uint64_t) * kFldCounters * r->n, (hipStream_t)stream_));
-    return CAVMD_OK;
+    return r ? r->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records, const uint64_t** rows)
 {
-    if (!r || (!records && !rows))
-        return CAVMD_ERR_INVALID_VALUE;
-    if (records)
-        *records = r->d_series;
-    if (rows)
-        *rows = r->d_counters + (size_t)kFldRows * r->n;
-    return CAVMD_OK;
+    return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
 }
 
 } // extern "C"

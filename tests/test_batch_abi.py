@@ -209,7 +209,7 @@ def test_deferred_destroy_takes_batches_before_workspaces(capi, monkeypatch):
     monkeypatch.setattr(capi, "_capturing", lambda: False)
     capi._destroy_deferred()
     assert order == [("batch", 0x20), ("ws", 0x10)]
-    assert not capi._deferred and not capi._deferred_batches
+    assert not capi._deferred and not capi._deferred_children
 
 
 # ---- BatchEnergyHistory against a fake batch object ---------------------------------------------------------------------

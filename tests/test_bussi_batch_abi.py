@@ -244,4 +244,4 @@ def test_deferred_destroy_takes_thermostat_batches_before_workspaces(capi, monke
     monkeypatch.setattr(capi, "_capturing", lambda: False)
     capi._destroy_deferred()
     assert order == [("bussi_batch", 0x20), ("ws", 0x10)]
-    assert not capi._deferred and not capi._deferred_bussi_batches
+    assert not capi._deferred and not capi._deferred_children

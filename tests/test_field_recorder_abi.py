@@ -206,4 +206,4 @@ def test_deferred_destroy_takes_field_recorders_before_workspaces(capi, monkeypa
     monkeypatch.setattr(capi, "_capturing", lambda: False)
     capi._destroy_deferred()
     assert order == [("field_recorder", 0x20), ("ws", 0x10)]
-    assert not capi._deferred and not capi._deferred_field_recorders
+    assert not capi._deferred and not capi._deferred_children

@@ -232,4 +232,4 @@ def test_deferred_destroy_takes_recorders_before_workspaces(capi, monkeypatch):
     monkeypatch.setattr(capi, "_capturing", lambda: False)
     capi._destroy_deferred()
     assert order == [("recorder", 0x20), ("ws", 0x10)]
-    assert not capi._deferred and not capi._deferred_recorders
+    assert not capi._deferred and not capi._deferred_children
