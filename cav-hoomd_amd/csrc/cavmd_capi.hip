@@ -20,6 +20,7 @@
 
 #include "cavmd.h"
 #include "cavmd_kernels.hpp"
+#include "cavmd_host_support.hpp" // the capture query, the wait for a stamp, the buffer owners, runtime value -> template argument
 
 using namespace cavmd;
 
@@ -73,15 +74,13 @@ struct cavmd_workspace
     char arch[64] = {0};
     size_t max_N = 0;
     unsigned max_parts = 0;
-    double* d_part = nullptr;
-    int* d_ipart = nullptr;
-    cavmd_result* d_result = nullptr;
-    HostResult* h_ring = nullptr;       // pinned + mapped: ring_depth result slots; evaluation s publishes into slot s % ring_depth
-    HostResult* h_ring_dev = nullptr;   // device-side address of h_ring
+    DeviceArray<double> d_part;
+    DeviceArray<int> d_ipart;
+    DeviceArray<cavmd_result> d_result;
+    MappedBlock<HostResult> h_ring;     // ring_depth result slots; evaluation s publishes into slot s % ring_depth
     unsigned ring_depth = kResultHistory;
     uint64_t history_first = 1;         // oldest sequence the ring can hold (raised when "result_history" reallocates it)
-    HostControl* h_ctl = nullptr;       // pinned + mapped, fixed: starvation flag + the block of a captured workspace
-    HostControl* h_ctl_dev = nullptr;
+    MappedBlock<HostControl> h_ctl;     // fixed: starvation flag + the block of a captured workspace
     hipStream_t last_stream = nullptr;
     bool computed = false;
     uint64_t sequence = 0;
@@ -104,16 +103,15 @@ struct cavmd_workspace
     int persistent_balanced = -1; // partition of the particles over the blocks of the single-launch kernel: -1 auto, 0 tiles
                                   // dealt round-robin (the two-launch path's partition), 1 contiguous, equal shares
     // single-launch evaluation: granule slab + epoch word (device), see cavmd_persistent_kernel.hpp
-    unsigned long long* d_granules = nullptr;
-    unsigned* d_epoch = nullptr;
+    DeviceArray<unsigned long long> d_granules;
+    DeviceArray<unsigned> d_epoch;
     int debug_spin_limit = 0;     // tests: poll rounds of the single-launch kernel's bounded waits (0 = kSpinLimit)
     int debug_late_block = -1;    // tests: this block of the single-launch grid starts debug_late_ticks late (-1 = none)
     int debug_late_ticks = 0;     //        (100 MHz wall clock)
     int debug_silent_block = -1;  // tests: this block never publishes its record: the evaluation cannot be completed (-1 = none)
     int debug_skip_publish = 0;   // tests: the kernels publish into a scratch block instead of the one the host reads -- what a
                                   //        launch that failed on the device looks like from the host
-    HostResult* h_scratch = nullptr; // (hooks build only) that scratch block, pinned + mapped
-    HostResult* h_scratch_dev = nullptr;
+    MappedBlock<HostResult> h_scratch; // (hooks build only) that scratch block
     // after a starved evaluation the single launch is suspended: until sequence reaches suspend_until, then one probe; every
     // further starvation multiplies the pause by 8 (2^16 evaluations at first, 2^31 at most); a FAILED one suspends for good
     uint64_t suspend_until = 0;
@@ -134,27 +132,22 @@ struct cavmd_workspace
     size_t n_k = 0;
     unsigned n_chunks = 0;
     unsigned rho_blocks = 0;
-    double* d_kvec = nullptr;
-    double* d_rho_part = nullptr;
-    double* d_rho = nullptr;
-    double* h_rho = nullptr; // pinned
+    DeviceArray<double> d_kvec, d_rho_part, d_rho; // set together with n_k, n_chunks and rho_blocks (cavmd_set_wavevectors)
+    PinnedBlock<double> h_rho;
     hipStream_t rho_stream = nullptr;
     bool rho_computed = false;
     int rho_last_mapping = -1; // what the last cavmd_density_field call launched: mapping 0..3 after the automatic rule,
     int rho_last_blocks = -1;  // and the grid's x extent, which is also the fold's nblocks (-1: no call yet); read-only tunables
-    double* d_mode = nullptr;
-    HostMode* h_mode = nullptr;     // pinned, mapped, coherent: cavity_mode_kernel publishes here
-    HostMode* h_mode_dev = nullptr;
+    DeviceArray<double> d_mode;
+    MappedBlock<HostMode> h_mode;   // cavity_mode_kernel publishes here
     uint64_t mode_sequence = 0;
-    double* d_fm_part = nullptr; // [2][max_parts] + 1 result
-    HostScalar* h_fm = nullptr;     // pinned, mapped, coherent: the scalar reductions publish here, the host spins on `ready`
-    HostScalar* h_fm_dev = nullptr; // device-side address of h_fm
+    DeviceArray<double> d_fm_part; // [2][max_parts] + 1 result
+    MappedBlock<HostScalar> h_fm;  // the scalar reductions publish here, the host spins on `ready`
     uint64_t fm_sequence = 0;
-    unsigned* d_fm_ticket = nullptr; // ticket counter of the one-launch scalar reductions (reset by the folding block)
+    DeviceArray<unsigned> d_fm_ticket; // ticket counter of the one-launch scalar reductions (reset by the folding block)
     // on-device Bussi thermostat (cavmd_bussi_step_device)
-    BussiDevice* d_bussi = nullptr;
-    HostBussi* h_bussi = nullptr;     // pinned, mapped, coherent
-    HostBussi* h_bussi_dev = nullptr;
+    DeviceArray<BussiDevice> d_bussi;
+    MappedBlock<HostBussi> h_bussi;
     uint64_t bussi_sequence = 0;
     uint64_t bussi_refused_seen = 0;  // refusals already reported to the caller
     hipStream_t bussi_stream = nullptr; // stream of the last enqueued step: the one whose idleness ends a wait for its flag
@@ -242,31 +235,20 @@ int drain_profile(cavmd_workspace* ws)
 // Once a workspace has been captured its results are read behind a device synchronisation instead (include/cavmd.h).
 void note_capture(cavmd_workspace* ws, hipStream_t stream)
 {
-    // (the null stream cannot be captured: HOOMD-blue's and torch's default path pays nothing for the query)
-    if (ws->captured || stream == nullptr)
-        return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (!ws->captured && stream_capturing(stream))
     {
         ws->captured = true;
         ws->captured_from = ws->sequence;
     }
 }
 
-// Where the single-launch evaluation is the default (measured on MI355X, profiles/r02/microbench_persistent_*.txt).
-bool persistent_auto(size_t N)
-{
-    (void)N;
-    return true;
-}
+// Where the single-launch evaluation is the default (measured on MI355X, profiles/r02/microbench_persistent_*.txt): at
+// every N that passes the residency and LDS conditions of plan_evaluation.
+constexpr bool kPersistentAuto = true;
 // Contiguous equal shares measured SLOWER than tiles dealt round-robin wherever the streaming matters (21.5 vs 20.3 us at
 // N = 1e6, 63.8 vs 57.8 at 4e6: 256 sequential streams a fixed distance apart load the HBM channels less evenly than one
 // 4 MB window that all blocks sweep together); only 3e5 gained (12.0 vs 12.2).  Kept as a tunable, off.
-bool persistent_balanced_auto(size_t N)
-{
-    (void)N;
-    return false;
-}
+constexpr bool kPersistentBalancedAuto = false;
 
 unsigned grid_for(size_t work_items, unsigned tile, int num_cu, int blocks_per_cu)
 {
@@ -277,48 +259,48 @@ unsigned grid_for(size_t work_items, unsigned tile, int num_cu, int blocks_per_c
 }
 
 constexpr int kScaleBlocksPerCu = 4; // velocity rescale: 256-thread blocks per CU (4 particles per lane and tile)
+constexpr size_t kTicketBytes = 128;
 
-// Scratch of the scalar reductions (sum |F| / m, kinetic energy): partials + the host-visible scalar.
+// Scratch of the scalar reductions (sum |F| / m, kinetic energy): partials + the host-visible scalar + the ticket counter.
 int ensure_scalar_scratch(cavmd_workspace* ws)
 {
-    if (ws->d_fm_part)
+    if (ws->d_fm_part.ptr)
         return CAVMD_OK;
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_fm_part, sizeof(double) * (2 * (size_t)ws->max_parts + 1)));
-    CAVMD_HIP_TRY(hipHostMalloc((void**)&ws->h_fm, sizeof(HostScalar), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(ws->h_fm, 0, sizeof(HostScalar));
-    CAVMD_HIP_TRY(hipHostGetDevicePointer((void**)&ws->h_fm_dev, ws->h_fm, 0));
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_fm_ticket, 128));
-    CAVMD_HIP_TRY(hipMemset(ws->d_fm_ticket, 0, 128));
+    DeviceArray<double> part;
+    MappedBlock<HostScalar> host;
+    DeviceArray<unsigned> ticket;
+    CAVMD_HIP_TRY(part.alloc(2 * (size_t)ws->max_parts + 1));
+    CAVMD_HIP_TRY(host.alloc());
+    CAVMD_HIP_TRY(ticket.alloc_zeroed(kTicketBytes / sizeof(unsigned)));
+    ws->d_fm_part = std::move(part);
+    ws->h_fm = std::move(host);
+    ws->d_fm_ticket = std::move(ticket);
     return CAVMD_OK;
 }
 
-// Wait for the scalar the fold kernel publishes (flag in mapped host memory; the stream going idle ends the wait too, e.g.
-// after a failed launch) -- about a PCIe write after the kernel has it, instead of a copy plus a stream synchronisation.
+// Wait for the scalar the fold kernel publishes: about a PCIe write after the kernel has it, instead of a copy plus a stream
+// synchronisation.
 int wait_scalar(cavmd_workspace* ws, hipStream_t stream, double* out)
 {
-    const uint64_t want = ws->fm_sequence;
-    for (;;)
+    const StampWait w = wait_for_stamp(&ws->h_fm.host->ready, ws->fm_sequence, stream);
+    if (w.error != hipSuccess)
+        return (int)w.error;
+    if (!w.arrived)
     {
-        if (__atomic_load_n(&ws->h_fm->ready, __ATOMIC_ACQUIRE) == want)
-            break;
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipSuccess)
-        {
-            if (__atomic_load_n(&ws->h_fm->ready, __ATOMIC_ACQUIRE) != want)
-            {
-                // the kernel never published (failed or aborted launch): its blocks may have left the ticket counter
-                // part-way, after which no block would ever be "last" again -- put it back before reporting
-                (void)hipMemsetAsync(ws->d_fm_ticket, 0, 128, stream);
-                return (int)hipErrorLaunchFailure;
-            }
-            break;
-        }
-        if (q != hipErrorNotReady)
-            return (int)q;
+        // the kernel never published (failed or aborted launch): its blocks may have left the ticket counter
+        // part-way, after which no block would ever be "last" again -- put it back before reporting
+        (void)hipMemsetAsync(ws->d_fm_ticket.ptr, 0, kTicketBytes, stream);
+        return (int)hipErrorLaunchFailure;
     }
-    *out = ws->h_fm->value;
+    *out = ws->h_fm.host->value;
     return CAVMD_OK;
 }
+
+// The variants of the kernels the two entry points choose among, by the values their template parameters take.  The launches
+// (with_constant) and allow_large_lds (with_each_constant) walk the same lists, so what is launched is what is instantiated.
+constexpr IntList<2, 1> kUnrolls;          // particles per lane and tile of the reduction
+constexpr IntList<0, 1, 2> kLoadPolicies;  // reduction loads: plain, pos+image non-temporal, all non-temporal
+constexpr IntList<2, 1, 0> kStorePolicies; // force stores: write-through, non-temporal, plain
 
 // The single-launch kernel keeps the charges of a block's tiles in dynamic LDS (up to kPersistMaxLds); HIP wants the
 // ceiling raised per kernel before a launch may ask for more than 64 KiB.
@@ -327,25 +309,19 @@ hipError_t allow_large_lds()
     // (per device: called from cavmd_create under its device guard)
     hipError_t once = [] {
         hipError_t e = hipSuccess;
-#define CAVMD_ALLOW(UNR, NTS)                                                                                    \
-    if (e == hipSuccess)                                                                                        \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<kPersistBlock, UNR, NTS>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistMaxLds);
-        CAVMD_ALLOW(1, 0)
-        CAVMD_ALLOW(1, 1)
-        CAVMD_ALLOW(1, 2)
-        CAVMD_ALLOW(2, 0)
-        CAVMD_ALLOW(2, 1)
-        CAVMD_ALLOW(2, 2)
-#undef CAVMD_ALLOW
+        const auto allow = [&e](auto kernel) {
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)kPersistMaxLds);
+        };
+        with_each_constant(kUnrolls, [&](auto u) {
+            with_each_constant(kStorePolicies, [&](auto s) {
+                allow(&cavity_persistent_kernel<kPersistBlock, decltype(u)::value, decltype(s)::value>);
+            });
+        });
 #ifdef CAVMD_TEST_HOOKS
         // the fault-injection instantiations (tests: "debug_late_block", "debug_silent_block"; libcavmd_hooks.so only)
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<kPersistBlock, 1, 0, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistMaxLds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<kPersistBlock, 2, 0, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPersistMaxLds);
+        with_each_constant(kUnrolls, [&](auto u) { allow(&cavity_persistent_kernel<kPersistBlock, decltype(u)::value, 0, true>); });
 #endif
         return e;
     }();
@@ -398,6 +374,121 @@ struct LaunchScope
         }
     }
 };
+
+// ---- the plan of one evaluation: which kernels, which variants, which grids -------------------------------------------------
+// Pure host arithmetic on (N, CU count, tunables); tests/test_gpu_dispatch_matrix.py::dispatch_mirror restates it line for
+// line and is checked against what the launches leave behind.  What depends on the workspace's history (a suspended single
+// launch, the dirty hand-off slabs, a starved evaluation not yet reported) is the entry point's business, not the plan's.
+enum class Layout
+{
+    aos,    // Scalar4 arrays (cavmd_compute_hoomd)
+    strided // per-field strided views (cavmd_compute_soa)
+};
+
+enum class Path
+{
+    single_block,  // cavity_small_system_kernel: one block reduces, finalises and maps
+    single_launch, // cavity_persistent_kernel
+    two_launches,  // reduction, then a force map that folds the partials itself
+    three_launches // reduction, finalize, force map (kept for A/B)
+};
+
+struct EvalPlan
+{
+    Path path = Path::two_launches;
+    Path multi_launch = Path::two_launches; // what a suspended single launch falls back to ("fused_finalize")
+    int unroll = kReduceUnroll;             // particles per lane and tile of the reduction
+    unsigned g1 = 1, g2 = 1;                // grids of the reduction (= number of partials) and of the force map
+    int nt_load = 0;                        // load policy of the two-launch reduction (kLoadPolicies)
+    int nt_store = 0;                       // store policy of the force map (kStorePolicies)
+    unsigned lds_slots = 0;                 // single launch: tiles of a block whose charges stay in LDS,
+    size_t lds_bytes = 0;                   //                and the dynamic LDS that takes
+    bool balanced = false;                  // single launch: contiguous equal shares instead of tiles dealt round-robin
+    bool map_reverse = false;               // the force map walks its tiles last-to-first
+};
+
+EvalPlan plan_evaluation(const cavmd_workspace& ws, size_t N, Layout layout)
+{
+    EvalPlan p;
+    p.multi_launch = ws.fused_finalize ? Path::two_launches : Path::three_launches;
+    p.path = p.multi_launch;
+    // ---- small systems (the reference's own N = 501): one block reduces, finalises and maps in ONE launch
+    if (layout == Layout::aos && ws.small_system_max_n > 0 && N <= (size_t)ws.small_system_max_n)
+    {
+        p.path = Path::single_block;
+        return p;
+    }
+    // Tile depth: 2 particles per lane (512 per block; 8 loads in flight per lane); 1 while that leaves at most about one
+    // tile per CU (re-measured with the single-launch kernel: 1 wins by 9 % at N = 5e4 and 4 % at 1.3e5, ties at 1e5,
+    // loses by 6 % from 2e5 up: profiles/r02/ab_reduce_unroll.txt).  One rule for both layouts, so that they share one
+    // summation tree (and give equal bits).
+    p.unroll = kReduceUnroll;
+    while (p.unroll > 1 && N / ((size_t)kReduceBlock * p.unroll) < (size_t)ws.num_cu * 5 / 4)
+        p.unroll >>= 1;
+    if (ws.reduce_unroll == 1 || ws.reduce_unroll == 2)
+        p.unroll = ws.reduce_unroll;
+    p.g1 = grid_for(N, kReduceBlock * p.unroll, ws.num_cu, ws.reduce_blocks_per_cu);
+    if (layout == Layout::strided)
+    {
+        p.g2 = grid_for(N, kMapBlock * 4, ws.num_cu, ws.map_blocks_per_cu); // the strided map's tile: 4 particles per lane
+        return p;
+    }
+    p.g2 = grid_for(2 * N, kMapBlock * kMapUnroll, ws.num_cu, ws.map_blocks_per_cu);
+    // Force stores bypass the caches for all but small N: the array is consumed much later (by the integrator, after
+    // every other force of the step), and not leaving 32 N dirty bytes behind shortens this kernel's drain and spares
+    // the next reduction the evictions (measured on whole evaluations, profiles/r01/microbench_*.txt).
+    p.nt_store = ws.map_nt_store < 0 ? (N >= kNtStoreMinN ? 1 : 0) : ws.map_nt_store;
+    // Load policy of the reduction.  pos and image are read once per evaluation: non-temporal.  charge is read again
+    // by the force map: keeping it temporal lets the map find it in the Infinity Cache while 8 N bytes fit there
+    // (measured per evaluation: -8 % at N = 6e6 and 1e7, -5 % at 2e7, tie at 5e7); non-temporal above.
+    p.nt_load = ws.reduce_nt_load < 0 ? (N <= kChargeTemporalMaxN ? 1 : 2) : ws.reduce_nt_load;
+    // Reverse tile order in the force map: the charge lines the reduction touched last are then asked for first.  It only
+    // matters where the per-XCD share of the charges (N bytes) is about the size of an XCD's 4 MiB L2: -3.3 % per
+    // evaluation at N = 4e6, neutral at 3e5 / 1e6 / 2e6 / 1e7 (scripts/ab_tunable.py map_reverse 0 1 ...).
+    p.map_reverse = ws.map_reverse < 0 ? (N > 2500000 && N <= 5000000) : (ws.map_reverse != 0);
+
+    // ---- ONE launch (cavmd_persistent_kernel.hpp): the same grid as the reduction; with the strided partition also the
+    // same tiles, hence the same partials and (same fold) the same bits as two launches.  Needs the whole grid resident at
+    // once: g1 <= CUs x blocks per CU by construction, <= 256 blocks (the two-level all-reduce), LDS and registers admit
+    // that many blocks per CU.  The charges of a block's first lds_slots tiles stay in LDS; tiles beyond (N >~ 5e6) are
+    // read a second time.
+    const size_t tile = (size_t)kReduceBlock * p.unroll;
+    p.balanced = ws.persistent_balanced < 0 ? kPersistentBalancedAuto : (ws.persistent_balanced != 0);
+    size_t slots;
+    if (p.balanced)
+    {
+        const size_t units = (N + kWave - 1) / kWave;
+        slots = (((units + p.g1 - 1) / p.g1) * kWave + tile - 1) / tile; // the largest share, in tiles (ragged one included)
+    }
+    else
+        slots = ((N + tile - 1) / tile + p.g1 - 1) / p.g1;
+    size_t budget = kPersistMaxLds / (size_t)ws.reduce_blocks_per_cu - 1024;
+    if (ws.persistent_lds_kb > 0 && (size_t)ws.persistent_lds_kb * 1024 < budget)
+        budget = (size_t)ws.persistent_lds_kb * 1024;
+    const size_t cap_slots = budget / (tile * sizeof(double));
+    p.lds_slots = (unsigned)(slots < cap_slots ? slots : cap_slots);
+    p.lds_bytes = p.lds_slots * tile * sizeof(double);
+    const bool resident = p.g1 <= kMaxPersistGrid && ws.reduce_blocks_per_cu <= 4;
+    // auto: only while every tile of a block fits in LDS.  With overflow tiles re-read in the second phase (one block per
+    // CU) the kernel loses to two launches: 142 against 137 us at N = 1e7 (profiles/r02/ab_overflow.txt).
+    // Nor by default beyond half a CU's LDS per block (N >~ 2.4e6): two such grids from different streams or processes
+    // could then not be resident side by side, and two half-resident grids would wait for each other until their
+    // bounded spins give up (a loud CAVMD_ERR_SYNC_TIMEOUT, but a failure).  persistent = 1 lifts both limits.
+    if (resident
+        && (ws.persistent > 0
+            || (ws.persistent < 0 && slots <= cap_slots && p.lds_bytes <= kPersistSharedLds && kPersistentAuto)))
+        p.path = Path::single_launch;
+    return p;
+}
+
+// what both entry points do once every launch of an evaluation went through
+int evaluation_enqueued(cavmd_workspace* ws, LaunchScope& ls, hipStream_t stream)
+{
+    ls.commit();
+    ws->last_stream = stream;
+    ws->computed = true;
+    return CAVMD_OK;
+}
 } // namespace
 
 extern "C"
@@ -458,41 +549,31 @@ int cavmd_create(int device, size_t max_N, cavmd_workspace** out_ws)
     strncpy(ws->arch, prop.gcnArchName, sizeof(ws->arch) - 1);
     ws->max_parts = (unsigned)(ws->num_cu * kMaxBlocksPerCU);
 
-    e = hipMalloc((void**)&ws->d_part, sizeof(double) * kNumPartDoubles * ws->max_parts);
+    e = ws->d_part.alloc((size_t)kNumPartDoubles * ws->max_parts);
     if (e == hipSuccess)
-        e = hipMalloc((void**)&ws->d_ipart, sizeof(int) * kNumPartInts * ws->max_parts);
+        e = ws->d_ipart.alloc((size_t)kNumPartInts * ws->max_parts);
     if (e == hipSuccess)
-        e = hipMalloc((void**)&ws->d_result, sizeof(cavmd_result));
-    if (e == hipSuccess)
-        e = hipMemset(ws->d_result, 0, sizeof(cavmd_result));
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&ws->d_granules, sizeof(unsigned long long) * 2 * kGranulesPerRecord * kMaxPersistGrid);
+        e = ws->d_result.alloc_zeroed(1);
     if (e == hipSuccess) // tag 0 = never valid
-        e = hipMemset(ws->d_granules, 0, sizeof(unsigned long long) * 2 * kGranulesPerRecord * kMaxPersistGrid);
+        e = ws->d_granules.alloc_zeroed((size_t)2 * kGranulesPerRecord * kMaxPersistGrid);
     if (e == hipSuccess)
-        e = hipMalloc((void**)&ws->d_epoch, 4 * sizeof(unsigned));
+        e = ws->d_epoch.alloc(4);
     if (e == hipSuccess)
     {
         const unsigned init[4] = {1u, 0u, 0u, 0u}; // first tag; no block has given up; not poisoned
-        e = hipMemcpy(ws->d_epoch, init, sizeof(init), hipMemcpyHostToDevice);
+        e = hipMemcpy(ws->d_epoch.ptr, init, sizeof(init), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess)
         e = allow_large_lds();
-    if (e == hipSuccess) // coherent: the polled flags must not depend on HIP_HOST_COHERENT
-        e = hipHostMalloc((void**)&ws->h_ring, sizeof(HostResult) * ws->ring_depth, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&ws->h_ring_dev, ws->h_ring, 0);
+        e = ws->h_ring.alloc(ws->ring_depth);
     if (e == hipSuccess)
-        e = hipHostMalloc((void**)&ws->h_ctl, sizeof(HostControl), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&ws->h_ctl_dev, ws->h_ctl, 0);
+        e = ws->h_ctl.alloc();
     if (e != hipSuccess)
     {
-        cavmd_destroy(ws);
+        delete ws; // nobody has seen it: the owners free what was allocated (the guard above is still in place)
         return (int)e;
     }
-    memset(ws->h_ring, 0, sizeof(HostResult) * ws->ring_depth);
-    memset(ws->h_ctl, 0, sizeof(HostControl));
     *out_ws = ws;
     return CAVMD_OK;
 }
@@ -510,45 +591,7 @@ int cavmd_destroy(cavmd_workspace* ws)
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
         (void)hipEventDestroy(ev);
-    if (ws->d_part)
-        (void)hipFree(ws->d_part);
-    if (ws->d_ipart)
-        (void)hipFree(ws->d_ipart);
-    if (ws->d_result)
-        (void)hipFree(ws->d_result);
-    if (ws->d_granules)
-        (void)hipFree(ws->d_granules);
-    if (ws->d_epoch)
-        (void)hipFree(ws->d_epoch);
-    if (ws->h_ring)
-        (void)hipHostFree(ws->h_ring);
-    if (ws->h_ctl)
-        (void)hipHostFree(ws->h_ctl);
-    if (ws->d_kvec)
-        (void)hipFree(ws->d_kvec);
-    if (ws->d_rho_part)
-        (void)hipFree(ws->d_rho_part);
-    if (ws->d_rho)
-        (void)hipFree(ws->d_rho);
-    if (ws->h_rho)
-        (void)hipHostFree(ws->h_rho);
-    if (ws->d_mode)
-        (void)hipFree(ws->d_mode);
-    if (ws->h_mode)
-        (void)hipHostFree(ws->h_mode);
-    if (ws->d_fm_part)
-        (void)hipFree(ws->d_fm_part);
-    if (ws->h_fm)
-        (void)hipHostFree(ws->h_fm);
-    if (ws->d_fm_ticket)
-        (void)hipFree(ws->d_fm_ticket);
-    if (ws->h_scratch)
-        (void)hipHostFree(ws->h_scratch);
-    if (ws->d_bussi)
-        (void)hipFree(ws->d_bussi);
-    if (ws->h_bussi)
-        (void)hipHostFree(ws->h_bussi);
-    delete ws;
+    delete ws; // every buffer is freed by its owner
     return CAVMD_OK;
 }
 
@@ -561,18 +604,18 @@ namespace
 inline HostResult* host_block(cavmd_workspace* ws)
 {
 #ifdef CAVMD_TEST_HOOKS
-    if (ws->debug_skip_publish && ws->h_scratch_dev)
-        return ws->h_scratch_dev;
+    if (ws->debug_skip_publish && ws->h_scratch.dev)
+        return ws->h_scratch.dev;
 #endif
     if (ws->captured)
-        return &ws->h_ctl_dev->fixed;
-    return ws->h_ring_dev + ws->sequence % ws->ring_depth;
+        return &ws->h_ctl.dev->fixed;
+    return ws->h_ring.dev + ws->sequence % ws->ring_depth;
 }
 
 // Host address of evaluation s's slot.
 inline HostResult* ring_slot(cavmd_workspace* ws, uint64_t s)
 {
-    return ws->h_ring + s % ws->ring_depth;
+    return ws->h_ring.host + s % ws->ring_depth;
 }
 
 // The block the synchronous getters read: the last evaluation's slot; on a captured workspace the fixed block, until the
@@ -580,7 +623,8 @@ inline HostResult* ring_slot(cavmd_workspace* ws, uint64_t s)
 inline HostResult* last_block(cavmd_workspace* ws)
 {
     if (ws->captured)
-        return __atomic_load_n(&ws->h_ctl->fixed.ready, __ATOMIC_ACQUIRE) ? &ws->h_ctl->fixed : ring_slot(ws, ws->captured_from);
+        return __atomic_load_n(&ws->h_ctl.host->fixed.ready, __ATOMIC_ACQUIRE) ? &ws->h_ctl.host->fixed
+                                                                               : ring_slot(ws, ws->captured_from);
     return ring_slot(ws, ws->sequence);
 }
 
@@ -591,17 +635,15 @@ inline HostResult* last_block(cavmd_workspace* ws)
 // one step, and the two-launch path does not depend on residency.  Returns 0 (nothing happened), kSyncRepaired or kSyncFailed.
 unsigned consume_sync_timeout(cavmd_workspace* ws)
 {
-    if (!ws->h_ctl || !__atomic_load_n(&ws->h_ctl->sync_error, __ATOMIC_ACQUIRE))
+    if (!ws->h_ctl.host || !__atomic_load_n(&ws->h_ctl.host->sync_error, __ATOMIC_ACQUIRE))
         return 0;
     // kSyncFailed is provisional while the kernel runs (the first block that gives up raises it, the last one may still
     // complete the evaluation): the verdict is the flag once the stream has drained.  A stream that is being captured cannot
     // be waited for; the provisional value then counts.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (ws->last_stream == nullptr || hipStreamIsCapturing(ws->last_stream, &cap) != hipSuccess
-        || cap == hipStreamCaptureStatusNone)
+    if (!stream_capturing(ws->last_stream))
         (void)hipStreamSynchronize(ws->last_stream);
-    const unsigned verdict = __atomic_load_n(&ws->h_ctl->sync_error, __ATOMIC_ACQUIRE);
-    __atomic_store_n(&ws->h_ctl->sync_error, 0u, __ATOMIC_RELEASE);
+    const unsigned verdict = __atomic_load_n(&ws->h_ctl.host->sync_error, __ATOMIC_ACQUIRE);
+    __atomic_store_n(&ws->h_ctl.host->sync_error, 0u, __ATOMIC_RELEASE);
     ws->sync_timeout_seen = true;
     ws->sync_state_dirty = true;
     if (verdict == kSyncRepaired)
@@ -651,204 +693,95 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
     in.pos2 = reinterpret_cast<const v2d*>(d_pos);
     in.charge = d_charge;
     in.image = reinterpret_cast<const int*>(d_image);
-    Partials part {ws->d_part, ws->d_ipart, ws->max_parts};
+    Partials part {ws->d_part.ptr, ws->d_ipart.ptr, ws->max_parts};
     const unsigned n = (unsigned)N;
     const DeviceParams dp = derive(params);
+    v2d* force2 = reinterpret_cast<v2d*>(d_force);
+    cavmd_result* const d_result = ws->d_result.ptr;
     int st;
 
-    // ---- small systems (the reference's own N = 501): one block reduces, finalises and maps in ONE launch
-    if (ws->small_system_max_n > 0 && N <= (size_t)ws->small_system_max_n)
+    EvalPlan plan = plan_evaluation(*ws, N, Layout::aos);
+    if (plan.path == Path::single_launch && ws->sequence < ws->suspend_until)
+        plan.path = plan.multi_launch; // suspended after a starved evaluation (consume_sync_timeout)
+
+    if (plan.path == Path::single_block)
     {
         ws->sequence += 1;
         st = ls.launch(0, cavity_small_system_kernel<kSmallBlock>, 1u, kSmallBlock, in, n, Lx, Ly, Lz, dp, L_typeid,
-                       ws->sequence, ws->d_result, host_block(ws), reinterpret_cast<v2d*>(d_force));
-        if (st != CAVMD_OK)
-            return st;
-        ls.commit();
-        ws->last_stream = stream;
-        ws->computed = true;
-        return CAVMD_OK;
+                       ws->sequence, d_result, host_block(ws), force2);
+        return st != CAVMD_OK ? st : evaluation_enqueued(ws, ls, stream);
+    }
+
+    if (plan.path == Path::single_launch)
+    {
+        if (ws->sync_state_dirty)
+        {
+            // re-enabled after a starved evaluation: records or give-up counts of that launch must not meet this one
+            CAVMD_HIP_TRY(hipMemsetAsync(ws->d_granules.ptr, 0, sizeof(unsigned long long) * 2 * kGranulesPerRecord * kMaxPersistGrid, stream));
+            CAVMD_HIP_TRY(hipMemsetAsync(ws->d_epoch.ptr + 1, 0, 2 * sizeof(unsigned), stream)); // give-up count and poison
+            ws->sync_state_dirty = false;
+        }
+        ws->sequence += 1;
+        const AosInputT<2> inx {in.pos2, in.charge, in.image};
+        const SyncState sync {ws->d_granules.ptr, ws->d_epoch.ptr,
+                              ws->debug_spin_limit > 0 ? (unsigned)ws->debug_spin_limit : kSpinLimit, ws->debug_late_block,
+                              (unsigned)ws->debug_late_ticks, ws->debug_silent_block, &ws->h_ctl.dev->sync_error};
+        const auto launch = [&](auto kernel) {
+            return ls.launch_lds(0, plan.lds_bytes, kernel, plan.g1, kPersistBlock, inx, n, Lx, Ly, Lz, dp, L_typeid, sync,
+                                 ws->sequence, d_result, host_block(ws), force2, plan.lds_slots, plan.balanced);
+        };
+#ifdef CAVMD_TEST_HOOKS
+        // fault injection (tests): one block starts late -> the grid starves itself and has to be repaired; or one block
+        // never publishes -> the evaluation cannot be completed
+        if (ws->debug_late_block >= 0 || ws->debug_silent_block >= 0)
+            st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
+                return launch(&cavity_persistent_kernel<kPersistBlock, decltype(u)::value, 0, true>);
+            });
+        else
+#endif
+            st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
+                return with_constant(kStorePolicies, plan.nt_store, [&](auto s) {
+                    return launch(&cavity_persistent_kernel<kPersistBlock, decltype(u)::value, decltype(s)::value>);
+                });
+            });
+        return st != CAVMD_OK ? st : evaluation_enqueued(ws, ls, stream);
     }
 
     // ---- launch 1: per-block partial sums + photon search
-    // Tile depth: 2 particles per lane (512 per block; 8 loads in flight per lane); 1 while that leaves at most about one
-    // tile per CU (re-measured with the single-launch kernel: 1 wins by 9 % at N = 5e4 and 4 % at 1.3e5, ties at 1e5,
-    // loses by 6 % from 2e5 up: profiles/r02/ab_reduce_unroll.txt).
-    int unroll = kReduceUnroll;
-    while (unroll > 1 && N / ((size_t)kReduceBlock * unroll) < (size_t)ws->num_cu * 5 / 4)
-        unroll >>= 1;
-    if (ws->reduce_unroll == 1 || ws->reduce_unroll == 2)
-        unroll = ws->reduce_unroll;
-    const unsigned g1 = grid_for(N, kReduceBlock * unroll, ws->num_cu, ws->reduce_blocks_per_cu);
-    v2d* force2 = reinterpret_cast<v2d*>(d_force);
-    // Force stores bypass the caches for all but small N: the array is consumed much later (by the integrator, after
-    // every other force of the step), and not leaving 32 N dirty bytes behind shortens this kernel's drain and spares
-    // the next reduction the evictions (measured on whole evaluations, profiles/r01/microbench_*.txt).
-    const int nt_store = ws->map_nt_store < 0 ? (N >= kNtStoreMinN ? 1 : 0) : ws->map_nt_store;
-
-    // ---- ONE launch (cavmd_persistent_kernel.hpp): the same grid as launch 1 below; with the strided partition also the
-    // same tiles, hence the same partials and (same fold) the same bits as two launches.  Needs the whole grid resident at
-    // once: g1 <= CUs x blocks per CU by construction, <= 256 blocks (the two-level all-reduce), LDS and registers admit
-    // that many blocks per CU.  The charges of a block's first lds_slots tiles stay in LDS; tiles beyond (N >~ 5e6) are
-    // read a second time.
-    {
-        const size_t tile = (size_t)kReduceBlock * unroll;
-        const bool balanced = ws->persistent_balanced < 0 ? persistent_balanced_auto(N) : (ws->persistent_balanced != 0);
-        size_t slots;
-        if (balanced)
-        {
-            const size_t units = (N + kWave - 1) / kWave;
-            slots = (((units + g1 - 1) / g1) * kWave + tile - 1) / tile; // the largest share, in tiles (ragged one included)
-        }
-        else
-            slots = ((N + tile - 1) / tile + g1 - 1) / g1;
-        size_t budget = kPersistMaxLds / (size_t)ws->reduce_blocks_per_cu - 1024;
-        if (ws->persistent_lds_kb > 0 && (size_t)ws->persistent_lds_kb * 1024 < budget)
-            budget = (size_t)ws->persistent_lds_kb * 1024;
-        const size_t cap_slots = budget / (tile * sizeof(double));
-        const size_t lds_slots = slots < cap_slots ? slots : cap_slots;
-        const size_t lds = lds_slots * tile * sizeof(double);
-        const bool resident = g1 <= kMaxPersistGrid && ws->reduce_blocks_per_cu <= 4;
-        // auto: only while every tile of a block fits in LDS.  With overflow tiles re-read in the second phase (one block per
-        // CU) the kernel loses to two launches: 142 against 137 us at N = 1e7 (profiles/r02/ab_overflow.txt).
-        // Nor by default beyond half a CU's LDS per block (N >~ 2.4e6): two such grids from different streams or processes
-        // could then not be resident side by side, and two half-resident grids would wait for each other until their
-        // bounded spins give up (a loud CAVMD_ERR_SYNC_TIMEOUT, but a failure).  persistent = 1 lifts both limits.
-        if (resident && ws->sequence >= ws->suspend_until
-            && (ws->persistent > 0
-                || (ws->persistent < 0 && slots <= cap_slots && lds <= kPersistSharedLds && persistent_auto(N))))
-        {
-            if (ws->sync_state_dirty)
-            {
-                // re-enabled after a starved evaluation: records or give-up counts of that launch must not meet this one
-                CAVMD_HIP_TRY(hipMemsetAsync(ws->d_granules, 0, sizeof(unsigned long long) * 2 * kGranulesPerRecord * kMaxPersistGrid, stream));
-                CAVMD_HIP_TRY(hipMemsetAsync(ws->d_epoch + 1, 0, 2 * sizeof(unsigned), stream)); // give-up count and poison
-                ws->sync_state_dirty = false;
-            }
-            ws->sequence += 1;
-            const AosInputT<2> inx {in.pos2, in.charge, in.image};
-            const SyncState sync {ws->d_granules, ws->d_epoch, ws->debug_spin_limit > 0 ? (unsigned)ws->debug_spin_limit : kSpinLimit,
-                                  ws->debug_late_block, (unsigned)ws->debug_late_ticks, ws->debug_silent_block,
-                                  &ws->h_ctl_dev->sync_error};
-#define CAVMD_LAUNCH_PERSIST(UNR, NTS)                                                                               \
-    st = ls.launch_lds(0, lds, cavity_persistent_kernel<kPersistBlock, UNR, NTS>, g1, kPersistBlock, inx, n, Lx, Ly, Lz, \
-                       dp, L_typeid, sync, ws->sequence, ws->d_result, host_block(ws), force2, (unsigned)lds_slots, balanced);
-#ifdef CAVMD_TEST_HOOKS
-            if (ws->debug_late_block >= 0 || ws->debug_silent_block >= 0)
-            {
-                // fault injection (tests): one block starts late -> the grid starves itself and has to be repaired; or one block
-                // never publishes -> the evaluation cannot be completed
-                if (unroll == 2)
-                    st = ls.launch_lds(0, lds, cavity_persistent_kernel<kPersistBlock, 2, 0, true>, g1, kPersistBlock, inx, n, Lx, Ly,
-                                       Lz, dp, L_typeid, sync, ws->sequence, ws->d_result, host_block(ws), force2,
-                                       (unsigned)lds_slots, balanced);
-                else
-                    st = ls.launch_lds(0, lds, cavity_persistent_kernel<kPersistBlock, 1, 0, true>, g1, kPersistBlock, inx, n, Lx, Ly,
-                                       Lz, dp, L_typeid, sync, ws->sequence, ws->d_result, host_block(ws), force2,
-                                       (unsigned)lds_slots, balanced);
-            }
-            else
-#endif
-            if (unroll == 2)
-            {
-                if (nt_store == 2)
-                    CAVMD_LAUNCH_PERSIST(2, 2)
-                else if (nt_store == 1)
-                    CAVMD_LAUNCH_PERSIST(2, 1)
-                else
-                    CAVMD_LAUNCH_PERSIST(2, 0)
-            }
-            else
-            {
-                if (nt_store == 2)
-                    CAVMD_LAUNCH_PERSIST(1, 2)
-                else if (nt_store == 1)
-                    CAVMD_LAUNCH_PERSIST(1, 1)
-                else
-                    CAVMD_LAUNCH_PERSIST(1, 0)
-            }
-#undef CAVMD_LAUNCH_PERSIST
-            if (st != CAVMD_OK)
-                return st;
-            ls.commit();
-            ws->last_stream = stream;
-            ws->computed = true;
-            return CAVMD_OK;
-        }
-    }
-
-    // Load policy of the reduction.  pos and image are read once per evaluation: non-temporal.  charge is read again
-    // by the force map: keeping it temporal lets the map find it in the Infinity Cache while 8 N bytes fit there
-    // (measured per evaluation: -8 % at N = 6e6 and 1e7, -5 % at 2e7, tie at 5e7); non-temporal above.
-    int nt = ws->reduce_nt_load;
-    if (nt < 0)
-        nt = (N <= kChargeTemporalMaxN) ? 1 : 2;
-#define CAVMD_LAUNCH_REDUCE(NTMODE, UNR)                                                                              \
-    {                                                                                                                 \
-        AosInputT<NTMODE> inx {in.pos2, in.charge, in.image};                                                         \
-        st = ls.launch(0, dipole_partials_kernel<AosInputT<NTMODE>, kReduceBlock, UNR, false>, g1, kReduceBlock, inx, \
-                       n, Lx, Ly, Lz, L_typeid, part);                                                                \
-    }
-#define CAVMD_LAUNCH_REDUCE_NT(UNR)                                                                                   \
-    {                                                                                                                 \
-        if (nt == 0)                                                                                                  \
-            CAVMD_LAUNCH_REDUCE(0, UNR)                                                                               \
-        else if (nt == 1)                                                                                             \
-            CAVMD_LAUNCH_REDUCE(1, UNR)                                                                               \
-        else                                                                                                          \
-            CAVMD_LAUNCH_REDUCE(2, UNR)                                                                               \
-    }
-    if (unroll == 2)
-        CAVMD_LAUNCH_REDUCE_NT(2)
-    else
-        CAVMD_LAUNCH_REDUCE_NT(1)
-#undef CAVMD_LAUNCH_REDUCE_NT
-#undef CAVMD_LAUNCH_REDUCE
+    st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
+        return with_constant(kLoadPolicies, plan.nt_load, [&](auto nt) {
+            using Input = AosInputT<decltype(nt)::value>;
+            return ls.launch(0, &dipole_partials_kernel<Input, kReduceBlock, decltype(u)::value, false>, plan.g1, kReduceBlock,
+                             Input {in.pos2, in.charge, in.image}, n, Lx, Ly, Lz, L_typeid, part);
+        });
+    });
     if (st != CAVMD_OK)
         return st;
 
     ws->sequence += 1;
-    const unsigned g2 = grid_for(2 * N, kMapBlock * kMapUnroll, ws->num_cu, ws->map_blocks_per_cu);
-    // Reverse tile order in the force map: the charge lines the reduction touched last are then asked for first.  It only
-    // matters where the per-XCD share of the charges (N bytes) is about the size of an XCD's 4 MiB L2: -3.3 % per
-    // evaluation at N = 4e6, neutral at 3e5 / 1e6 / 2e6 / 1e7 (scripts/ab_tunable.py map_reverse 0 1 ...).
-    const bool map_reverse = ws->map_reverse < 0 ? (N > 2500000 && N <= 5000000) : (ws->map_reverse != 0);
-    if (ws->fused_finalize)
+    if (plan.path == Path::two_launches)
     {
         // ---- launch 2 of 2: every force-map block folds the partials itself, block 0 publishes the result block
-        if (nt_store == 2)
-            st = ls.launch(2, force_map_aos_fused_kernel<kMapBlock, kMapUnroll, 2>, g2, kMapBlock, in, n, g1, Lx, Ly,
-                           Lz, dp, L_typeid, part, ws->sequence, ws->d_result, host_block(ws), force2, map_reverse);
-        else if (nt_store == 1)
-            st = ls.launch(2, force_map_aos_fused_kernel<kMapBlock, kMapUnroll, 1>, g2, kMapBlock, in, n, g1, Lx, Ly,
-                           Lz, dp, L_typeid, part, ws->sequence, ws->d_result, host_block(ws), force2, map_reverse);
-        else
-            st = ls.launch(2, force_map_aos_fused_kernel<kMapBlock, kMapUnroll, 0>, g2, kMapBlock, in, n, g1, Lx, Ly,
-                           Lz, dp, L_typeid, part, ws->sequence, ws->d_result, host_block(ws), force2, map_reverse);
+        st = with_constant(kStorePolicies, plan.nt_store, [&](auto s) {
+            return ls.launch(2, &force_map_aos_fused_kernel<kMapBlock, kMapUnroll, decltype(s)::value>, plan.g2, kMapBlock, in, n,
+                             plan.g1, Lx, Ly, Lz, dp, L_typeid, part, ws->sequence, d_result, host_block(ws), force2,
+                             plan.map_reverse);
+        });
     }
     else
     {
         // ---- three-launch variant (kept for A/B): finalize, then a force map that reads the result block
-        st = ls.launch(1, finalize_kernel<AosInput, kFinalizeBlock>, 1u, kFinalizeBlock, in, n, g1, Lx, Ly, Lz, dp,
-                       part, ws->sequence, ws->d_result, host_block(ws));
+        st = ls.launch(1, finalize_kernel<AosInput, kFinalizeBlock>, 1u, kFinalizeBlock, in, n, plan.g1, Lx, Ly, Lz, dp, part,
+                       ws->sequence, d_result, host_block(ws));
         if (st != CAVMD_OK)
             return st;
-        const cavmd_result* res = ws->d_result;
-        const double g = params->couplstr;
-        if (nt_store)
-            st = ls.launch(2, force_map_aos_kernel<kMapBlock, kMapUnroll, true>, g2, kMapBlock, d_charge, in.pos2, n, g,
-                           L_typeid, res, force2);
-        else
-            st = ls.launch(2, force_map_aos_kernel<kMapBlock, kMapUnroll, false>, g2, kMapBlock, d_charge, in.pos2, n, g,
-                           L_typeid, res, force2);
+        const cavmd_result* res = d_result;
+        st = with_constant(IntList<1, 0> {}, plan.nt_store != 0, [&](auto nts) {
+            return ls.launch(2, &force_map_aos_kernel<kMapBlock, kMapUnroll, decltype(nts)::value != 0>, plan.g2, kMapBlock,
+                             d_charge, in.pos2, n, params->couplstr, L_typeid, res, force2);
+        });
     }
-    if (st != CAVMD_OK)
-        return st;
-    ls.commit();
-
-    ws->last_stream = stream;
-    ws->computed = true;
-    return CAVMD_OK;
+    return st != CAVMD_OK ? st : evaluation_enqueued(ws, ls, stream);
 }
 
 int cavmd_compute_soa(cavmd_workspace* ws, void* stream_, size_t N, const double* d_position, size_t position_stride,
@@ -907,52 +840,37 @@ int cavmd_compute_soa(cavmd_workspace* ws, void* stream_, size_t N, const double
     in.tid_stride = typeid_stride;
     in.img_stride = image_stride;
     in.chg_stride = charge_stride;
-    Partials part {ws->d_part, ws->d_ipart, ws->max_parts};
+    Partials part {ws->d_part.ptr, ws->d_ipart.ptr, ws->max_parts};
     const unsigned n = (unsigned)N;
     const DeviceParams dp = derive(params);
+    cavmd_result* const d_result = ws->d_result.ptr;
 
-    // same tile-depth rule as cavmd_compute_hoomd, so that both layouts share one summation tree (and give equal bits)
-    int unroll = kReduceUnroll;
-    while (unroll > 1 && N / ((size_t)kReduceBlock * unroll) < (size_t)ws->num_cu * 5 / 4)
-        unroll >>= 1;
-    if (ws->reduce_unroll == 1 || ws->reduce_unroll == 2)
-        unroll = ws->reduce_unroll;
-    const unsigned g1 = grid_for(N, kReduceBlock * unroll, ws->num_cu, ws->reduce_blocks_per_cu);
-    int st;
-    if (unroll == 2)
-        st = ls.launch(0, dipole_partials_kernel<StridedInput, kReduceBlock, 2, false>, g1, kReduceBlock, in, n, Lx, Ly, Lz,
-                       L_typeid, part);
-    else
-        st = ls.launch(0, dipole_partials_kernel<StridedInput, kReduceBlock, 1, false>, g1, kReduceBlock, in, n, Lx, Ly, Lz,
-                       L_typeid, part);
+    const EvalPlan plan = plan_evaluation(*ws, N, Layout::strided);
+    int st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
+        return ls.launch(0, &dipole_partials_kernel<StridedInput, kReduceBlock, decltype(u)::value, false>, plan.g1, kReduceBlock,
+                         in, n, Lx, Ly, Lz, L_typeid, part);
+    });
     if (st != CAVMD_OK)
         return st;
     ws->sequence += 1;
     char* f_out = reinterpret_cast<char*>(d_force);
     char* pe_out = reinterpret_cast<char*>(d_potential_energy);
-    const unsigned g2 = grid_for(N, kMapBlock * 4, ws->num_cu, ws->map_blocks_per_cu);
-    if (ws->fused_finalize)
+    if (plan.path == Path::two_launches)
     {
-        st = ls.launch(2, force_map_strided_fused_kernel<kMapBlock>, g2, kMapBlock, in, n, g1, Lx, Ly, Lz, dp, L_typeid, part,
-                       ws->sequence, ws->d_result, host_block(ws), f_out, force_stride, pe_out, potential_energy_stride);
+        st = ls.launch(2, force_map_strided_fused_kernel<kMapBlock>, plan.g2, kMapBlock, in, n, plan.g1, Lx, Ly, Lz, dp, L_typeid,
+                       part, ws->sequence, d_result, host_block(ws), f_out, force_stride, pe_out, potential_energy_stride);
     }
     else
     {
-        st = ls.launch(1, finalize_kernel<StridedInput, kFinalizeBlock>, 1u, kFinalizeBlock, in, n, g1, Lx, Ly, Lz, dp,
-                       part, ws->sequence, ws->d_result, host_block(ws));
+        st = ls.launch(1, finalize_kernel<StridedInput, kFinalizeBlock>, 1u, kFinalizeBlock, in, n, plan.g1, Lx, Ly, Lz, dp, part,
+                       ws->sequence, d_result, host_block(ws));
         if (st != CAVMD_OK)
             return st;
-        const cavmd_result* res = ws->d_result;
-        st = ls.launch(2, force_map_strided_kernel<kMapBlock>, g2, kMapBlock, in, n, params->couplstr, L_typeid, res,
-                       f_out, force_stride, pe_out, potential_energy_stride);
+        const cavmd_result* res = d_result;
+        st = ls.launch(2, force_map_strided_kernel<kMapBlock>, plan.g2, kMapBlock, in, n, params->couplstr, L_typeid, res, f_out,
+                       force_stride, pe_out, potential_energy_stride);
     }
-    if (st != CAVMD_OK)
-        return st;
-    ls.commit();
-
-    ws->last_stream = stream;
-    ws->computed = true;
-    return CAVMD_OK;
+    return st != CAVMD_OK ? st : evaluation_enqueued(ws, ls, stream);
 }
 
 int cavmd_result_read(cavmd_workspace* ws, cavmd_result* out)
@@ -974,21 +892,10 @@ int cavmd_result_read(cavmd_workspace* ws, cavmd_result* out)
         // host memory.  Spin on that flag: the energies arrive as soon as the block that computes the scalars has them,
         // about a PCIe write after, instead of a stream synchronisation (~15 us).  The stream going idle ends the wait as
         // well (a failed launch, or a timed-out single-launch kernel, never sets the flag).
-        const uint64_t want = ws->sequence;
-        const HostResult* h = ring_slot(ws, want);
-        for (;;)
-        {
-            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want)
-                break;
-            const hipError_t q = hipStreamQuery(ws->last_stream);
-            if (q == hipSuccess)
-            {
-                published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want;
-                break;
-            }
-            if (q != hipErrorNotReady)
-                return (int)q;
-        }
+        const StampWait w = wait_for_stamp(&ring_slot(ws, ws->sequence)->ready, ws->sequence, ws->last_stream);
+        if (w.error != hipSuccess)
+            return (int)w.error;
+        published = w.arrived;
     }
     // A starved evaluation that failed (NaN forces): the result block still holds the PREVIOUS evaluation, which is
     // invalidated so that a second read reports "nothing computed" instead of handing that out as if it were current.
@@ -1054,35 +961,18 @@ int cavmd_result_at(cavmd_workspace* ws, uint64_t sequence, cavmd_result* out)
         return CAVMD_ERR_EXPIRED;
     DeviceGuard guard(ws->device);
     const HostResult* h = ring_slot(ws, sequence);
-    bool published = false;
-    for (;;)
-    {
-        if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence)
-        {
-            published = true;
-            break;
-        }
-        // The evaluation is over once a LATER one has published (the stream runs them in order) or the stream is idle.
-        // Never a stream synchronisation, and never the workspace-wide starvation flag: either would wait behind newer
-        // evaluations (a starved one among them can take a third of a second).
-        bool later = false;
-        for (uint64_t j = sequence + 1; j <= last && !later; ++j)
-            later = __atomic_load_n(&ring_slot(ws, j)->ready, __ATOMIC_ACQUIRE) == j;
-        if (later)
-        {
-            published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence;
-            break;
-        }
-        const hipError_t q = hipStreamQuery(ws->last_stream);
-        if (q == hipSuccess)
-        {
-            published = __atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence;
-            break;
-        }
-        if (q != hipErrorNotReady)
-            return (int)q;
-    }
-    if (!published)
+    // The evaluation is over once a LATER one has published (the stream runs them in order) or the stream is idle.
+    // Never a stream synchronisation, and never the workspace-wide starvation flag: either would wait behind newer
+    // evaluations (a starved one among them can take a third of a second).
+    const StampWait w = wait_for_stamp(&h->ready, sequence, ws->last_stream, [&] {
+        for (uint64_t j = sequence + 1; j <= last; ++j)
+            if (__atomic_load_n(&ring_slot(ws, j)->ready, __ATOMIC_ACQUIRE) == j)
+                return true;
+        return false;
+    });
+    if (w.error != hipSuccess)
+        return (int)w.error;
+    if (!w.arrived)
     {
         // over, and its slot does not carry it: a starved single-launch evaluation that could not be completed tagged its
         // slot with its own sequence; anything else is a launch that died on the device.  Never an earlier occupant's block.
@@ -1111,7 +1001,7 @@ int cavmd_result_device_ptr(cavmd_workspace* ws, const cavmd_result** out)
 {
     if (!ws || !out)
         return CAVMD_ERR_INVALID_VALUE;
-    *out = ws->d_result;
+    *out = ws->d_result.ptr;
     return CAVMD_OK;
 }
 
@@ -1120,25 +1010,30 @@ int cavmd_set_wavevectors(cavmd_workspace* ws, size_t n_k, const double* h_wavev
     if (!ws || !h_wavevectors || n_k == 0 || n_k > (size_t)1 << 20)
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
-    if (ws->d_kvec)
-        (void)hipFree(ws->d_kvec);
-    if (ws->d_rho_part)
-        (void)hipFree(ws->d_rho_part);
-    if (ws->d_rho)
-        (void)hipFree(ws->d_rho);
-    if (ws->h_rho)
-        (void)hipHostFree(ws->h_rho);
-    ws->d_kvec = ws->d_rho_part = ws->d_rho = ws->h_rho = nullptr;
+    // the old set goes first (its memory may be what the new one needs); from here to the commit the workspace has none
+    ws->d_kvec.free();
+    ws->d_rho_part.free();
+    ws->d_rho.free();
+    ws->h_rho.free();
     ws->rho_computed = false;
+    ws->n_k = 0;
+    const unsigned n_chunks = (unsigned)((n_k + kWave - 1) / kWave);
+    const unsigned rho_blocks = (unsigned)ws->num_cu * 4; // capacity of the partial buffer: three 256-thread blocks per CU (lane =
+                                                          // particle mapping) or one 1024-thread block per CU (lane = wavevector)
+    DeviceArray<double> kvec, rho_part, rho;
+    PinnedBlock<double> h_rho;
+    CAVMD_HIP_TRY(kvec.alloc(3 * n_k));
+    CAVMD_HIP_TRY(rho_part.alloc(2 * kWave * (size_t)n_chunks * rho_blocks));
+    CAVMD_HIP_TRY(rho.alloc(2 * n_k));
+    CAVMD_HIP_TRY(h_rho.alloc(2 * n_k));
+    CAVMD_HIP_TRY(hipMemcpy(kvec.ptr, h_wavevectors, sizeof(double) * 3 * n_k, hipMemcpyHostToDevice));
+    ws->d_kvec = std::move(kvec);
+    ws->d_rho_part = std::move(rho_part);
+    ws->d_rho = std::move(rho);
+    ws->h_rho = std::move(h_rho);
     ws->n_k = n_k;
-    ws->n_chunks = (unsigned)((n_k + kWave - 1) / kWave);
-    ws->rho_blocks = (unsigned)ws->num_cu * 4; // capacity of the partial buffer: three 256-thread blocks per CU (lane = particle
-                                               // mapping) or one 1024-thread block per CU (lane = wavevector)
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_kvec, sizeof(double) * 3 * n_k));
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_rho_part, sizeof(double) * 2 * kWave * (size_t)ws->n_chunks * ws->rho_blocks));
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_rho, sizeof(double) * 2 * n_k));
-    CAVMD_HIP_TRY(hipHostMalloc((void**)&ws->h_rho, sizeof(double) * 2 * n_k, hipHostMallocDefault));
-    CAVMD_HIP_TRY(hipMemcpy(ws->d_kvec, h_wavevectors, sizeof(double) * 3 * n_k, hipMemcpyHostToDevice));
+    ws->n_chunks = n_chunks;
+    ws->rho_blocks = rho_blocks;
     return CAVMD_OK;
 }
 
@@ -1168,17 +1063,12 @@ int cavmd_density_field(cavmd_workspace* ws, void* stream_, size_t N, const doub
         if (g > ws->rho_blocks)
             g = ws->rho_blocks;
         gb = (unsigned)(g ? g : 1);
-#define CAVMD_LAUNCH_LP(KCV)                                                                                              \
-    hipLaunchKernelGGL((density_partials_lp_kernel<kLpBlock, KCV>), dim3(gb, (unsigned)((ws->n_k + KCV - 1) / KCV)),        \
-                       dim3(kLpBlock), 0, stream, reinterpret_cast<const char*>(d_position), position_stride, (unsigned)N, \
-                       ws->d_kvec, (unsigned)ws->n_k, make_sincos_coef(), ws->d_rho_part);
-        if (lp == 1)
-            CAVMD_LAUNCH_LP(25)
-        else if (lp == 2)
-            CAVMD_LAUNCH_LP(10)
-        else
-            CAVMD_LAUNCH_LP(5)
-#undef CAVMD_LAUNCH_LP
+        with_constant(IntList<25, 10, 5> {}, lp == 1 ? 25 : lp == 2 ? 10 : 5, [&](auto kc) {
+            constexpr int KC = decltype(kc)::value; // wavevectors per chunk
+            hipLaunchKernelGGL((density_partials_lp_kernel<kLpBlock, KC>), dim3(gb, (unsigned)((ws->n_k + KC - 1) / KC)),
+                               dim3(kLpBlock), 0, stream, reinterpret_cast<const char*>(d_position), position_stride, (unsigned)N,
+                               ws->d_kvec.ptr, (unsigned)ws->n_k, make_sincos_coef(), ws->d_rho_part.ptr);
+        });
     }
     else
     {
@@ -1187,12 +1077,12 @@ int cavmd_density_field(cavmd_workspace* ws, void* stream_, size_t N, const doub
             g = (size_t)ws->num_cu;
         gb = (unsigned)(g ? g : 1);
         hipLaunchKernelGGL((density_partials_kernel<kBlock>), dim3(gb, ws->n_chunks), dim3(kBlock), 0, stream,
-                           reinterpret_cast<const char*>(d_position), position_stride, (unsigned)N, ws->d_kvec,
-                           (unsigned)ws->n_k, make_sincos_coef(), ws->d_rho_part);
+                           reinterpret_cast<const char*>(d_position), position_stride, (unsigned)N, ws->d_kvec.ptr,
+                           (unsigned)ws->n_k, make_sincos_coef(), ws->d_rho_part.ptr);
     }
     CAVMD_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((density_fold_kernel<kBlock>), dim3(ws->n_chunks), dim3(kBlock), 0, stream, ws->d_rho_part,
-                       gb, (unsigned)ws->n_k, ws->d_rho);
+    hipLaunchKernelGGL((density_fold_kernel<kBlock>), dim3(ws->n_chunks), dim3(kBlock), 0, stream, ws->d_rho_part.ptr,
+                       gb, (unsigned)ws->n_k, ws->d_rho.ptr);
     CAVMD_HIP_TRY(hipGetLastError());
     ws->rho_stream = stream;
     ws->rho_computed = true;
@@ -1208,9 +1098,9 @@ int cavmd_density_field_read(cavmd_workspace* ws, double* h_out)
     if (!ws->rho_computed)
         return CAVMD_ERR_NOT_COMPUTED;
     DeviceGuard guard(ws->device);
-    CAVMD_HIP_TRY(hipMemcpyAsync(ws->h_rho, ws->d_rho, sizeof(double) * 2 * ws->n_k, hipMemcpyDeviceToHost, ws->rho_stream));
+    CAVMD_HIP_TRY(hipMemcpyAsync(ws->h_rho.host, ws->d_rho.ptr, sizeof(double) * 2 * ws->n_k, hipMemcpyDeviceToHost, ws->rho_stream));
     CAVMD_HIP_TRY(hipStreamSynchronize(ws->rho_stream));
-    memcpy(h_out, ws->h_rho, sizeof(double) * 2 * ws->n_k);
+    memcpy(h_out, ws->h_rho.host, sizeof(double) * 2 * ws->n_k);
     return CAVMD_OK;
 }
 
@@ -1226,35 +1116,27 @@ int cavmd_cavity_mode(cavmd_workspace* ws, void* stream_, const cavmd_double4* d
         return CAVMD_ERR_SYNC_TIMEOUT;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(ws->device);
-    if (!ws->d_mode)
+    if (!ws->d_mode.ptr)
     {
-        CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_mode, sizeof(double) * 4));
-        CAVMD_HIP_TRY(hipHostMalloc((void**)&ws->h_mode, sizeof(HostMode), hipHostMallocMapped | hipHostMallocCoherent));
-        memset(ws->h_mode, 0, sizeof(HostMode));
-        CAVMD_HIP_TRY(hipHostGetDevicePointer((void**)&ws->h_mode_dev, ws->h_mode, 0));
+        DeviceArray<double> mode;
+        MappedBlock<HostMode> host;
+        CAVMD_HIP_TRY(mode.alloc(4));
+        CAVMD_HIP_TRY(host.alloc());
+        ws->d_mode = std::move(mode);
+        ws->h_mode = std::move(host);
     }
-    const cavmd_result* res = ws->d_result;
+    const cavmd_result* res = ws->d_result.ptr;
     ws->mode_sequence += 1;
-    hipLaunchKernelGGL(cavity_mode_kernel, dim3(1), dim3(1), 0, stream, res, d_vel, kB, ws->d_mode, ws->h_mode_dev,
+    hipLaunchKernelGGL(cavity_mode_kernel, dim3(1), dim3(1), 0, stream, res, d_vel, kB, ws->d_mode.ptr, ws->h_mode.dev,
                        ws->mode_sequence);
     CAVMD_HIP_TRY(hipGetLastError());
-    // spin on the flag (the stream going idle ends the wait too, e.g. after a failed launch)
-    for (;;)
-    {
-        if (__atomic_load_n(&ws->h_mode->ready, __ATOMIC_ACQUIRE) == ws->mode_sequence)
-            break;
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipSuccess)
-        {
-            if (__atomic_load_n(&ws->h_mode->ready, __ATOMIC_ACQUIRE) != ws->mode_sequence)
-                return (int)hipErrorLaunchFailure;
-            break;
-        }
-        if (q != hipErrorNotReady)
-            return (int)q;
-    }
+    const StampWait w = wait_for_stamp(&ws->h_mode.host->ready, ws->mode_sequence, stream);
+    if (w.error != hipSuccess)
+        return (int)w.error;
+    if (!w.arrived)
+        return (int)hipErrorLaunchFailure;
     for (int k = 0; k < 4; ++k)
-        out[k] = ws->h_mode->v[k];
+        out[k] = ws->h_mode.host->v[k];
     return CAVMD_OK;
 }
 
@@ -1281,11 +1163,11 @@ int cavmd_force_mass_sum(cavmd_workspace* ws, void* stream_, size_t N, const cav
     // one block per CU: every block draws a ticket from ONE counter (~12 ns each, serialised at the memory side); with four
     // blocks per CU the 1024 tickets alone took 12 us
     const unsigned g = grid_for(N, kBlock * kUnroll, ws->num_cu, 1);
-    double* d_out = ws->d_fm_part + 2 * (size_t)ws->max_parts;
+    double* d_out = ws->d_fm_part.ptr + 2 * (size_t)ws->max_parts;
     ws->fm_sequence += 1;
     hipLaunchKernelGGL((force_mass_fused_kernel<kBlock, kUnroll>), dim3(g), dim3(kBlock), 0, stream,
                        reinterpret_cast<const v2d*>(d_net_force), reinterpret_cast<const v2d*>(d_vel), (unsigned)N,
-                       ws->d_fm_part, ws->d_fm_ticket, d_out, ws->h_fm_dev, ws->fm_sequence);
+                       ws->d_fm_part.ptr, ws->d_fm_ticket.ptr, d_out, ws->h_fm.dev, ws->fm_sequence);
     CAVMD_HIP_TRY(hipGetLastError());
     return wait_scalar(ws, stream, out);
 }
@@ -1311,11 +1193,11 @@ int cavmd_kinetic_energy(cavmd_workspace* ws, void* stream_, const cavmd_double4
     }
     constexpr int kBlock = 256, kUnroll = 4;
     const unsigned g = grid_for(n_members, kBlock * kUnroll, ws->num_cu, 1); // one ticket per CU, see cavmd_force_mass_sum
-    double* d_out = ws->d_fm_part + 2 * (size_t)ws->max_parts;
+    double* d_out = ws->d_fm_part.ptr + 2 * (size_t)ws->max_parts;
     ws->fm_sequence += 1;
     hipLaunchKernelGGL((kinetic_fused_kernel<kBlock, kUnroll>), dim3(g), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part, ws->d_fm_ticket,
-                       d_out, ws->h_fm_dev, ws->fm_sequence);
+                       reinterpret_cast<const v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part.ptr,
+                       ws->d_fm_ticket.ptr, d_out, ws->h_fm.dev, ws->fm_sequence);
     CAVMD_HIP_TRY(hipGetLastError());
     return wait_scalar(ws, stream, out);
 }
@@ -1385,13 +1267,14 @@ namespace
 {
 int ensure_bussi_state(cavmd_workspace* ws)
 {
-    if (ws->d_bussi)
+    if (ws->d_bussi.ptr)
         return CAVMD_OK;
-    CAVMD_HIP_TRY(hipMalloc((void**)&ws->d_bussi, sizeof(BussiDevice)));
-    CAVMD_HIP_TRY(hipMemset(ws->d_bussi, 0, sizeof(BussiDevice)));
-    CAVMD_HIP_TRY(hipHostMalloc((void**)&ws->h_bussi, sizeof(HostBussi), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(ws->h_bussi, 0, sizeof(HostBussi));
-    CAVMD_HIP_TRY(hipHostGetDevicePointer((void**)&ws->h_bussi_dev, ws->h_bussi, 0));
+    DeviceArray<BussiDevice> state;
+    MappedBlock<HostBussi> host;
+    CAVMD_HIP_TRY(state.alloc_zeroed(1));
+    CAVMD_HIP_TRY(host.alloc());
+    ws->d_bussi = std::move(state);
+    ws->h_bussi = std::move(host);
     return CAVMD_OK;
 }
 } // namespace
@@ -1407,13 +1290,9 @@ int cavmd_bussi_step_device(cavmd_workspace* ws, void* stream_, cavmd_double4* d
     hipStream_t stream = (hipStream_t)stream_;
     // The variates, c, set_T and dof travel by value in BussiStepArgs: a captured step would apply the same R and gamma on
     // every replay (a thermostat that is no longer stochastic).  Refused before anything is allocated, enqueued or counted.
-    // (The null stream cannot be captured, as in note_capture.)
-    if (stream != nullptr)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-            return CAVMD_ERR_INVALID_VALUE;
-    }
+    // A capture query that fails refuses too.
+    if (capture_state(stream) != Capture::none)
+        return CAVMD_ERR_INVALID_VALUE;
     if (deltaT == 0.0 || n_members == 0) // src/BussiReservoirThermostat.h:45-48: factors {1, 1}, counters untouched
         return CAVMD_OK;
     DeviceGuard guard(ws->device);
@@ -1435,12 +1314,12 @@ int cavmd_bussi_step_device(cavmd_workspace* ws, void* stream_, cavmd_double4* d
     ws->bussi_sequence += 1;
     ws->bussi_stream = stream;
     hipLaunchKernelGGL((kinetic_partials_kernel<kBlock, kUnroll>), dim3(g), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part);
+                       reinterpret_cast<const v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part.ptr);
     CAVMD_HIP_TRY(hipGetLastError());
     const unsigned g2 = grid_for(n_members, kBlock * kUnroll, ws->num_cu, kScaleBlocksPerCu);
     hipLaunchKernelGGL((bussi_rescale_fused_kernel<kBlock, kUnroll>), dim3(g2), dim3(kBlock), 0, stream,
-                       reinterpret_cast<v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part, g, a, ws->d_bussi,
-                       ws->h_bussi_dev, ws->bussi_sequence);
+                       reinterpret_cast<v2d*>(d_vel), d_members, (unsigned)n_members, ws->d_fm_part.ptr, g, a, ws->d_bussi.ptr,
+                       ws->h_bussi.dev, ws->bussi_sequence);
     return hip_status(hipGetLastError());
 }
 
@@ -1449,26 +1328,16 @@ int cavmd_bussi_device_read(cavmd_workspace* ws, cavmd_bussi_device_state* out)
     if (!ws || !out)
         return CAVMD_ERR_INVALID_VALUE;
     memset(out, 0, sizeof(*out));
-    if (!ws->d_bussi || ws->bussi_sequence == 0)
+    if (!ws->d_bussi.ptr || ws->bussi_sequence == 0)
         return CAVMD_OK;
-    hipStream_t stream = ws->bussi_stream; // the stream the last step went to, whatever stream the caller is on now
     DeviceGuard guard(ws->device);
-    const uint64_t want = ws->bussi_sequence;
-    for (;;)
-    {
-        if (__atomic_load_n(&ws->h_bussi->ready, __ATOMIC_ACQUIRE) == want)
-            break;
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipSuccess)
-        {
-            if (__atomic_load_n(&ws->h_bussi->ready, __ATOMIC_ACQUIRE) != want)
-                return (int)hipErrorLaunchFailure; // a launch that never published
-            break;
-        }
-        if (q != hipErrorNotReady)
-            return (int)q;
-    }
-    const BussiDevice s = ws->h_bussi->state;
+    // (on the stream the last step went to, whatever stream the caller is on now)
+    const StampWait w = wait_for_stamp(&ws->h_bussi.host->ready, ws->bussi_sequence, ws->bussi_stream);
+    if (w.error != hipSuccess)
+        return (int)w.error;
+    if (!w.arrived)
+        return (int)hipErrorLaunchFailure; // a launch that never published
+    const BussiDevice s = ws->h_bussi.host->state;
     out->reservoir_translational = s.reservoir;
     out->instantaneous_translational = s.instantaneous;
     out->last_alpha = s.alpha;
@@ -1487,7 +1356,7 @@ int cavmd_bussi_device_reset(cavmd_workspace* ws, void* stream_)
 {
     if (!ws)
         return CAVMD_ERR_INVALID_VALUE;
-    if (!ws->d_bussi)
+    if (!ws->d_bussi.ptr)
         return CAVMD_OK;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(ws->device);
@@ -1496,8 +1365,8 @@ int cavmd_bussi_device_reset(cavmd_workspace* ws, void* stream_)
     const int st = cavmd_bussi_device_read(ws, &unused);
     if (st != CAVMD_OK && st != CAVMD_ERR_BAD_PARAMS)
         return st;
-    CAVMD_HIP_TRY(hipMemsetAsync(ws->d_bussi, 0, sizeof(BussiDevice), stream));
-    memset(&ws->h_bussi->state, 0, sizeof(BussiDevice));
+    CAVMD_HIP_TRY(hipMemsetAsync(ws->d_bussi.ptr, 0, sizeof(BussiDevice), stream));
+    memset(&ws->h_bussi.host->state, 0, sizeof(BussiDevice));
     ws->bussi_refused_seen = 0;
     return CAVMD_OK;
 }
@@ -1576,32 +1445,55 @@ namespace
 // every earlier sequence expires.
 int resize_history(cavmd_workspace* ws, unsigned depth)
 {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (ws->last_stream != nullptr && hipStreamIsCapturing(ws->last_stream, &cap) == hipSuccess
-        && cap != hipStreamCaptureStatusNone)
+    if (stream_capturing(ws->last_stream))
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     if (ws->sequence)
         CAVMD_HIP_TRY(hipStreamSynchronize(ws->last_stream));
-    HostResult* ring = nullptr;
-    HostResult* ring_dev = nullptr;
-    CAVMD_HIP_TRY(hipHostMalloc((void**)&ring, sizeof(HostResult) * depth, hipHostMallocMapped | hipHostMallocCoherent));
-    const hipError_t e = hipHostGetDevicePointer((void**)&ring_dev, ring, 0);
-    if (e != hipSuccess)
-    {
-        (void)hipHostFree(ring);
-        return (int)e;
-    }
-    memset(ring, 0, sizeof(HostResult) * depth);
+    MappedBlock<HostResult> ring;
+    CAVMD_HIP_TRY(ring.alloc(depth));
     const uint64_t keep = ws->captured ? ws->captured_from : ws->sequence;
     if (keep)
-        memcpy(ring + keep % depth, ring_slot(ws, keep), sizeof(HostResult));
-    (void)hipHostFree(ws->h_ring);
-    ws->h_ring = ring;
-    ws->h_ring_dev = ring_dev;
+        memcpy(ring.host + keep % depth, ring_slot(ws, keep), sizeof(HostResult));
+    ws->h_ring = std::move(ring); // frees the old ring
     ws->ring_depth = depth;
     ws->history_first = ws->sequence ? ws->sequence : 1;
     return CAVMD_OK;
+}
+
+// The plain integer tunables: a name, the member it sets and the values it accepts (lo..hi); cavmd_set_tunable and
+// cavmd_get_tunable both walk this table.  Whatever does more than store a checked int is spelled out in the two functions.
+struct TunableRow
+{
+    const char* name;
+    int cavmd_workspace::*member;
+    int lo, hi;
+};
+const TunableRow kTunables[] = {
+    {"reduce_blocks_per_cu", &cavmd_workspace::reduce_blocks_per_cu, 1, kMaxBlocksPerCU},
+    {"map_blocks_per_cu", &cavmd_workspace::map_blocks_per_cu, 1, kMaxBlocksPerCU},
+    {"map_nt_store", &cavmd_workspace::map_nt_store, -1, 2},
+    {"reduce_nt_load", &cavmd_workspace::reduce_nt_load, -1, 2},
+    {"fused_finalize", &cavmd_workspace::fused_finalize, 0, 1},
+    {"map_reverse", &cavmd_workspace::map_reverse, -1, 1},
+    {"small_system_max_n", &cavmd_workspace::small_system_max_n, 0, 1 << 20},
+    {"rho_lane_particle", &cavmd_workspace::rho_lane_particle, -1, 3},
+    {"persistent_lds_kb", &cavmd_workspace::persistent_lds_kb, 0, 156},
+    {"persistent_balanced", &cavmd_workspace::persistent_balanced, -1, 1},
+#ifdef CAVMD_TEST_HOOKS
+    {"debug_spin_limit", &cavmd_workspace::debug_spin_limit, 0, INT_MAX},
+    {"debug_late_block", &cavmd_workspace::debug_late_block, -1, (int)kMaxPersistGrid - 1},
+    {"debug_late_ticks", &cavmd_workspace::debug_late_ticks, 0, 100000000}, // at most one second
+    {"debug_silent_block", &cavmd_workspace::debug_silent_block, -1, (int)kMaxPersistGrid - 1},
+#endif
+};
+
+const TunableRow* find_tunable(const char* name)
+{
+    for (const TunableRow& row : kTunables)
+        if (!strcmp(name, row.name))
+            return &row;
+    return nullptr;
 }
 } // namespace
 
@@ -1609,60 +1501,18 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
 {
     if (!ws || !name)
         return CAVMD_ERR_INVALID_VALUE;
+    if (const TunableRow* row = find_tunable(name))
+    {
+        if (value < row->lo || value > row->hi)
+            return CAVMD_ERR_INVALID_VALUE;
+        ws->*(row->member) = value;
+        return CAVMD_OK;
+    }
     if (!strcmp(name, "result_history"))
     {
         if (value < 2 || value > (int)kResultHistoryMax)
             return CAVMD_ERR_INVALID_VALUE;
         return resize_history(ws, (unsigned)value);
-    }
-    if (!strcmp(name, "reduce_blocks_per_cu"))
-    {
-        if (value < 1 || value > kMaxBlocksPerCU)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->reduce_blocks_per_cu = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "map_blocks_per_cu"))
-    {
-        if (value < 1 || value > kMaxBlocksPerCU)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->map_blocks_per_cu = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "map_nt_store"))
-    {
-        if (value < -1 || value > 2)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->map_nt_store = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "reduce_nt_load"))
-    {
-        if (value < -1 || value > 2)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->reduce_nt_load = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "fused_finalize"))
-    {
-        if (value != 0 && value != 1)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->fused_finalize = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "map_reverse"))
-    {
-        if (value < -1 || value > 1)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->map_reverse = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "small_system_max_n"))
-    {
-        if (value < 0 || value > (1 << 20))
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->small_system_max_n = value;
-        return CAVMD_OK;
     }
     if (!strcmp(name, "persistent"))
     {
@@ -1673,6 +1523,13 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
         ws->suspend_backoff = kSuspendFirst;
         return CAVMD_OK;
     }
+    if (!strcmp(name, "reduce_unroll"))
+    {
+        if (value != -1 && value != 1 && value != 2)
+            return CAVMD_ERR_INVALID_VALUE;
+        ws->reduce_unroll = value;
+        return CAVMD_OK;
+    }
 #ifdef CAVMD_TEST_HOOKS
     if (!strcmp(name, "debug_suspend_first"))
     {
@@ -1681,44 +1538,14 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
         ws->suspend_backoff = (uint64_t)value;
         return CAVMD_OK;
     }
-    if (!strcmp(name, "debug_spin_limit"))
-    {
-        if (value < 0)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->debug_spin_limit = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "debug_late_block"))
-    {
-        if (value < -1 || value >= (int)kMaxPersistGrid)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->debug_late_block = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "debug_late_ticks"))
-    {
-        if (value < 0 || value > 100000000) // at most one second
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->debug_late_ticks = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "debug_silent_block"))
-    {
-        if (value < -1 || value >= (int)kMaxPersistGrid)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->debug_silent_block = value;
-        return CAVMD_OK;
-    }
     if (!strcmp(name, "debug_skip_publish"))
     {
         if (value < 0 || value > 1)
             return CAVMD_ERR_INVALID_VALUE;
-        if (value && !ws->h_scratch)
+        if (value && !ws->h_scratch.host)
         {
             DeviceGuard guard(ws->device);
-            CAVMD_HIP_TRY(hipHostMalloc((void**)&ws->h_scratch, sizeof(HostResult), hipHostMallocMapped | hipHostMallocCoherent));
-            memset(ws->h_scratch, 0, sizeof(HostResult));
-            CAVMD_HIP_TRY(hipHostGetDevicePointer((void**)&ws->h_scratch_dev, ws->h_scratch, 0));
+            CAVMD_HIP_TRY(ws->h_scratch.alloc()); // one owner: there, or empty
         }
         ws->debug_skip_publish = value;
         return CAVMD_OK;
@@ -1732,7 +1559,7 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
         if (value < 0 || value > 2)
             return CAVMD_ERR_INVALID_VALUE;
         if (value)
-            __atomic_store_n(&ws->h_ctl->sync_error, value == 2 ? kSyncRepaired : kSyncFailed, __ATOMIC_RELEASE);
+            __atomic_store_n(&ws->h_ctl.host->sync_error, value == 2 ? kSyncRepaired : kSyncFailed, __ATOMIC_RELEASE);
         else
             ws->sync_timeout_seen = false;
 #else
@@ -1742,34 +1569,6 @@ int cavmd_set_tunable(cavmd_workspace* ws, const char* name, int value)
 #endif
         return CAVMD_OK;
     }
-    if (!strcmp(name, "reduce_unroll"))
-    {
-        if (value != -1 && value != 1 && value != 2)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->reduce_unroll = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "rho_lane_particle"))
-    {
-        if (value < -1 || value > 3)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->rho_lane_particle = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "persistent_lds_kb"))
-    {
-        if (value < 0 || value > 156)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->persistent_lds_kb = value;
-        return CAVMD_OK;
-    }
-    if (!strcmp(name, "persistent_balanced"))
-    {
-        if (value < -1 || value > 1)
-            return CAVMD_ERR_INVALID_VALUE;
-        ws->persistent_balanced = value;
-        return CAVMD_OK;
-    }
     return CAVMD_ERR_INVALID_VALUE;
 }
 
@@ -1777,37 +1576,23 @@ int cavmd_get_tunable(cavmd_workspace* ws, const char* name, int* value)
 {
     if (!ws || !name || !value)
         return CAVMD_ERR_INVALID_VALUE;
-    if (!strcmp(name, "reduce_blocks_per_cu"))
-        *value = ws->reduce_blocks_per_cu;
+    if (const TunableRow* row = find_tunable(name))
+        *value = ws->*(row->member);
     else if (!strcmp(name, "result_history"))
         *value = (int)ws->ring_depth;
-    else if (!strcmp(name, "map_blocks_per_cu"))
-        *value = ws->map_blocks_per_cu;
-    else if (!strcmp(name, "map_nt_store"))
-        *value = ws->map_nt_store;
-    else if (!strcmp(name, "reduce_nt_load"))
-        *value = ws->reduce_nt_load;
-    else if (!strcmp(name, "fused_finalize"))
-        *value = ws->fused_finalize;
-    else if (!strcmp(name, "map_reverse"))
-        *value = ws->map_reverse;
-    else if (!strcmp(name, "small_system_max_n"))
-        *value = ws->small_system_max_n;
     else if (!strcmp(name, "persistent"))
         *value = ws->persistent;
+    else if (!strcmp(name, "reduce_unroll"))
+        *value = ws->reduce_unroll;
     else if (!strcmp(name, "sync_timeout_seen"))
         *value = ws->sync_timeout_seen ? 1 : 0;
     else if (!strcmp(name, "persistent_suspended"))
         *value = ws->suspend_until == kSuspendForever ? 2 : (ws->sequence < ws->suspend_until ? 1 : 0);
+    else if (!strcmp(name, "rho_last_mapping"))
+        *value = ws->rho_last_mapping;
+    else if (!strcmp(name, "rho_last_blocks"))
+        *value = ws->rho_last_blocks;
 #ifdef CAVMD_TEST_HOOKS
-    else if (!strcmp(name, "debug_spin_limit"))
-        *value = ws->debug_spin_limit;
-    else if (!strcmp(name, "debug_late_block"))
-        *value = ws->debug_late_block;
-    else if (!strcmp(name, "debug_late_ticks"))
-        *value = ws->debug_late_ticks;
-    else if (!strcmp(name, "debug_silent_block"))
-        *value = ws->debug_silent_block;
     else if (!strcmp(name, "debug_skip_publish"))
         *value = ws->debug_skip_publish;
     else if (!strcmp(name, "test_hooks"))
@@ -1816,18 +1601,6 @@ int cavmd_get_tunable(cavmd_workspace* ws, const char* name, int* value)
     else if (!strcmp(name, "test_hooks"))
         *value = 0;
 #endif
-    else if (!strcmp(name, "reduce_unroll"))
-        *value = ws->reduce_unroll;
-    else if (!strcmp(name, "rho_lane_particle"))
-        *value = ws->rho_lane_particle;
-    else if (!strcmp(name, "rho_last_mapping"))
-        *value = ws->rho_last_mapping;
-    else if (!strcmp(name, "rho_last_blocks"))
-        *value = ws->rho_last_blocks;
-    else if (!strcmp(name, "persistent_lds_kb"))
-        *value = ws->persistent_lds_kb;
-    else if (!strcmp(name, "persistent_balanced"))
-        *value = ws->persistent_balanced;
     else
         return CAVMD_ERR_INVALID_VALUE;
     return CAVMD_OK;
@@ -1917,9 +1690,8 @@ BatchRow batch_row(const cavmd_batch_item& it)
 struct cavmd_batch : ItemTable<cavmd_batch_item, BatchRow> // launched by N descending
 {
     unsigned depth = 0;
-    cavmd_result* d_result = nullptr;    // n blocks, indexed by item
-    HostResult* h_ring = nullptr;        // pinned + mapped: depth x n blocks; evaluation s, item i -> (s % depth) * n + i
-    HostResult* h_ring_dev = nullptr;
+    DeviceArray<cavmd_result> d_result;  // n blocks, indexed by item
+    MappedBlock<HostResult> h_ring;      // depth x n blocks; evaluation s, item i -> (s % depth) * n + i
     uint64_t sequence = 0;
     bool captured = false; // some evaluation was enqueued into a stream capture: the stamps cannot tell replays apart
 
@@ -1930,7 +1702,7 @@ namespace
 {
 inline const HostResult* batch_slot(const cavmd_batch* b, uint64_t s)
 {
-    return b->h_ring + (s % b->depth) * b->n;
+    return b->h_ring.host + (s % b->depth) * b->n;
 }
 } // namespace
 
@@ -1984,19 +1756,14 @@ int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_it
     DeviceGuard guard(b->device);
     hipError_t e = b->upload();
     if (e == hipSuccess)
-        e = hipMalloc((void**)&b->d_result, sizeof(cavmd_result) * n_items);
+        e = b->d_result.alloc_zeroed(n_items);
     if (e == hipSuccess)
-        e = hipMemset(b->d_result, 0, sizeof(cavmd_result) * n_items);
-    if (e == hipSuccess) // coherent: the polled stamps must not depend on HIP_HOST_COHERENT
-        e = hipHostMalloc((void**)&b->h_ring, sizeof(HostResult) * ring_blocks, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&b->h_ring_dev, b->h_ring, 0);
+        e = b->h_ring.alloc(ring_blocks);
     if (e != hipSuccess)
     {
         cavmd_batch_destroy(b);
         return (int)e;
     }
-    memset(b->h_ring, 0, sizeof(HostResult) * ring_blocks);
     *out = b;
     return CAVMD_OK;
 }
@@ -2007,11 +1774,7 @@ int cavmd_batch_destroy(cavmd_batch* b)
         return CAVMD_OK;
     DeviceGuard guard(b->device);
     b->quiesce_and_free();
-    if (b->d_result)
-        (void)hipFree(b->d_result);
-    if (b->h_ring)
-        (void)hipHostFree(b->h_ring);
-    delete b;
+    delete b; // the results and the ring go with their owners
     return CAVMD_OK;
 }
 
@@ -2029,9 +1792,9 @@ int cavmd_batch_compute(cavmd_batch* b, void* stream_)
     if (!b->captured && stream_capturing(stream))
         b->captured = true;
     b->sequence += 1;
-    HostResult* host = b->h_ring_dev + (b->sequence % b->depth) * b->n;
+    HostResult* host = b->h_ring.dev + (b->sequence % b->depth) * b->n;
     hipLaunchKernelGGL(cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, stream, b->d_rows,
-                       b->d_order, b->sequence, b->d_result, host);
+                       b->d_order, b->sequence, b->d_result.ptr, host);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
     {
@@ -2061,26 +1824,16 @@ int batch_wait(cavmd_batch* b, uint64_t sequence)
     const uint64_t last = b->sequence;
     for (size_t i = 0; i < b->n; ++i)
     {
-        const HostResult* h = slot + i;
-        for (;;)
-        {
-            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == sequence)
-                break;
-            bool over = false;
-            for (uint64_t j = sequence + 1; j <= last && !over; ++j)
-                over = __atomic_load_n(&(batch_slot(b, j) + i)->ready, __ATOMIC_ACQUIRE) == j;
-            if (!over)
-            {
-                const hipError_t q = hipStreamQuery(b->last_stream);
-                if (q == hipErrorNotReady)
-                    continue;
-                if (q != hipSuccess)
-                    return (int)q;
-            }
-            if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) != sequence)
-                return (int)hipErrorLaunchFailure;
-            break;
-        }
+        const StampWait w = wait_for_stamp(&slot[i].ready, sequence, b->last_stream, [&] {
+            for (uint64_t j = sequence + 1; j <= last; ++j)
+                if (__atomic_load_n(&batch_slot(b, j)[i].ready, __ATOMIC_ACQUIRE) == j)
+                    return true;
+            return false;
+        });
+        if (w.error != hipSuccess)
+            return (int)w.error;
+        if (!w.arrived)
+            return (int)hipErrorLaunchFailure;
     }
     return CAVMD_OK;
 }
@@ -2145,7 +1898,7 @@ int cavmd_batch_results_read(cavmd_batch* b, cavmd_result* out)
     // and copy the device blocks, which every replay rewrites
     DeviceGuard guard(b->device);
     CAVMD_HIP_TRY(hipDeviceSynchronize());
-    CAVMD_HIP_TRY(hipMemcpy(out, b->d_result, sizeof(cavmd_result) * b->n, hipMemcpyDeviceToHost));
+    CAVMD_HIP_TRY(hipMemcpy(out, b->d_result.ptr, sizeof(cavmd_result) * b->n, hipMemcpyDeviceToHost));
     return CAVMD_OK;
 }
 
@@ -2153,7 +1906,7 @@ int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out)
 {
     if (!b || !out)
         return CAVMD_ERR_INVALID_VALUE;
-    *out = b->d_result;
+    *out = b->d_result.ptr;
     return CAVMD_OK;
 }
 
@@ -2164,9 +1917,8 @@ struct cavmd_bussi_batch : ItemTable<cavmd_bussi_batch_item, BussiBatchRow> // l
 {
     cavmd_workspace* ws = nullptr;
     std::vector<uint64_t> refused_seen;        // per item: refusals already reported to the caller
-    BussiDevice* d_state = nullptr;            // n states, indexed by item
-    HostBussiBatch* h_blocks = nullptr;        // pinned + mapped + coherent: n blocks, indexed by item
-    HostBussiBatch* h_blocks_dev = nullptr;
+    DeviceArray<BussiDevice> d_state;          // n states, indexed by item
+    MappedBlock<HostBussiBatch> h_blocks;      // n blocks, indexed by item
     uint64_t sequence = 0;
     bool captured = false; // some step was enqueued into a stream capture: the stamps cannot tell replays apart
 
@@ -2256,19 +2008,14 @@ int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bu
     DeviceGuard guard(b->device);
     hipError_t e = b->upload();
     if (e == hipSuccess)
-        e = hipMalloc((void**)&b->d_state, sizeof(BussiDevice) * n_items);
+        e = b->d_state.alloc_zeroed(n_items);
     if (e == hipSuccess)
-        e = hipMemset(b->d_state, 0, sizeof(BussiDevice) * n_items);
-    if (e == hipSuccess) // coherent: the polled stamps must not depend on HIP_HOST_COHERENT
-        e = hipHostMalloc((void**)&b->h_blocks, sizeof(HostBussiBatch) * n_items, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess)
-        e = hipHostGetDevicePointer((void**)&b->h_blocks_dev, b->h_blocks, 0);
+        e = b->h_blocks.alloc(n_items);
     if (e != hipSuccess)
     {
         cavmd_bussi_batch_destroy(b);
         return (int)e;
     }
-    memset(b->h_blocks, 0, sizeof(HostBussiBatch) * n_items);
     b->ws = ws;
     ws->bussi_batches += 1;
     *out = b;
@@ -2281,10 +2028,6 @@ int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
         return CAVMD_OK;
     DeviceGuard guard(b->device);
     b->quiesce_and_free();
-    if (b->d_state)
-        (void)hipFree(b->d_state);
-    if (b->h_blocks)
-        (void)hipHostFree(b->h_blocks);
     if (b->ws)
         b->ws->bussi_batches -= 1;
     delete b;
@@ -2306,7 +2049,7 @@ int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_buss
         b->captured = true;
     b->sequence += 1;
     hipLaunchKernelGGL(bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, stream, b->d_rows, b->d_order,
-                       reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state, b->h_blocks_dev);
+                       reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state.ptr, b->h_blocks.dev);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
     {
@@ -2337,27 +2080,19 @@ int cavmd_bussi_batch_read(cavmd_bussi_batch* b, cavmd_bussi_device_state* out)
     {
         // graph replays: frozen sequence, unknown replay stream -> wait for the device and copy the device states
         CAVMD_HIP_TRY(hipDeviceSynchronize());
-        CAVMD_HIP_TRY(hipMemcpy(out, b->d_state, sizeof(BussiDevice) * b->n, hipMemcpyDeviceToHost));
+        CAVMD_HIP_TRY(hipMemcpy(out, b->d_state.ptr, sizeof(BussiDevice) * b->n, hipMemcpyDeviceToHost));
     }
     else
     {
         const uint64_t want = b->sequence;
         for (size_t i = 0; i < b->n; ++i)
         {
-            const HostBussiBatch* h = b->h_blocks + i;
-            for (;;)
-            {
-                if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) == want)
-                    break;
-                const hipError_t q = hipStreamQuery(b->last_stream);
-                if (q == hipErrorNotReady)
-                    continue;
-                if (q != hipSuccess)
-                    return (int)q;
-                if (__atomic_load_n(&h->ready, __ATOMIC_ACQUIRE) != want)
-                    return (int)hipErrorLaunchFailure; // a launch that never published
-                break;
-            }
+            const HostBussiBatch* h = b->h_blocks.host + i;
+            const StampWait w = wait_for_stamp(&h->ready, want, b->last_stream);
+            if (w.error != hipSuccess)
+                return (int)w.error;
+            if (!w.arrived)
+                return (int)hipErrorLaunchFailure; // a launch that never published
             bussi_state_out(out + i, h->state);
         }
     }
@@ -2385,9 +2120,9 @@ int cavmd_bussi_batch_reset(cavmd_bussi_batch* b, void* stream_)
         if (st != CAVMD_OK && st != CAVMD_ERR_BAD_PARAMS)
             return st;
     }
-    CAVMD_HIP_TRY(hipMemsetAsync(b->d_state, 0, sizeof(BussiDevice) * b->n, stream));
+    CAVMD_HIP_TRY(hipMemsetAsync(b->d_state.ptr, 0, sizeof(BussiDevice) * b->n, stream));
     for (size_t i = 0; i < b->n; ++i)
-        memset(&b->h_blocks[i].state, 0, sizeof(BussiDevice));
+        memset(&b->h_blocks.host[i].state, 0, sizeof(BussiDevice));
     std::fill(b->refused_seen.begin(), b->refused_seen.end(), (uint64_t)0);
     return CAVMD_OK;
 }
@@ -2396,7 +2131,7 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
 {
     if (!b || !out)
         return CAVMD_ERR_INVALID_VALUE;
-    *out = reinterpret_cast<const cavmd_bussi_device_state*>(b->d_state);
+    *out = reinterpret_cast<const cavmd_bussi_device_state*>(b->d_state.ptr);
     return CAVMD_OK;
 }
 

@@ -11,17 +11,10 @@
 #include <vector>
 
 #include "cavmd.h"
+#include "cavmd_host_support.hpp" // stream_capturing
 
 namespace
 {
-bool stream_capturing(hipStream_t stream)
-{
-    if (stream == nullptr) // the null stream cannot be captured
-        return false;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
 // waits for what was enqueued on `stream`; a capturing stream cannot be waited for
 int sync_uncaptured(hipStream_t stream)
 {
