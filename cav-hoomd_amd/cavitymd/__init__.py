@@ -15,11 +15,12 @@ from .batch import BatchEnergyHistory, CavityForceBatch
 from .thermostat_batch import BussiReservoirBatch
 from .recorder import BatchRecorder
 from .field_recorder import BatchFieldRecorder
+from .integrator_batch import VerletBatch
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, field_recorder, observables, recorder, replicas, synthetic, thermostat_batch, thermostats
+from . import _capi, field_recorder, integrator_batch, observables, recorder, replicas, synthetic, thermostat_batch, thermostats
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "field_recorder", "observables", "recorder", "replicas", "synthetic", "thermostat_batch", "thermostats",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "field_recorder", "integrator_batch", "observables", "recorder", "replicas", "synthetic", "thermostat_batch", "thermostats",
 ]
 __version__ = "0.1.0"

@@ -116,6 +116,26 @@ class FieldItem(ctypes.Structure):
                 ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 5)]
 
 
+class VerletItem(ctypes.Structure):
+    """cavmd_verlet_item (128 bytes): one system of an integrator batch; all pointers are DEVICE pointers."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_image", ctypes.c_void_p), ("d_vel", ctypes.c_void_p),
+                ("d_accel", ctypes.c_void_p), ("d_force", ctypes.c_void_p * 4), ("d_net_force", ctypes.c_void_p),
+                ("Lx", ctypes.c_double), ("Ly", ctypes.c_double), ("Lz", ctypes.c_double), ("N", ctypes.c_uint32),
+                ("langevin_index", ctypes.c_int32), ("reserved", ctypes.c_uint64 * 3)]
+
+
+class VerletInput(ctypes.Structure):
+    """cavmd_verlet_input (64 bytes): one step's inputs of one item; the rows live in DEVICE memory."""
+    _fields_ = [("dt", ctypes.c_double), ("langevin_gamma", ctypes.c_double), ("langevin_coeff", ctypes.c_double),
+                ("uniform", ctypes.c_double * 3), ("skip", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+class VerletState(ctypes.Structure):
+    """cavmd_verlet_state (32 bytes): one item's counters."""
+    _fields_ = [("steps", ctypes.c_uint64), ("out_of_box", ctypes.c_uint64), ("langevin_reservoir", ctypes.c_double),
+                ("reserved", ctypes.c_double)]
+
+
 FIELD_MAX_WAVEVECTORS = 256
 FIELD_MAX_REFERENCES = 16
 BATCH_MAX_ITEMS = 65536
@@ -162,8 +182,25 @@ def field_item(position_ptr, position_stride, N) -> "FieldItem":
     return it
 
 
+def verlet_item(N, pos_ptr, image_ptr, vel_ptr, accel_ptr, force_ptrs, net_force_ptr, box_L, langevin_index=-1) -> "VerletItem":
+    it = VerletItem()
+    it.d_pos, it.d_image, it.d_vel, it.d_accel = pos_ptr or None, image_ptr or None, vel_ptr or None, accel_ptr or None
+    force_ptrs = list(force_ptrs)
+    if len(force_ptrs) > 4:
+        raise ValueError("at most four force arrays per system")
+    for k, p in enumerate(force_ptrs):
+        it.d_force[k] = p or None
+    it.d_net_force = net_force_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.N, it.langevin_index = int(N), int(langevin_index)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_verlet_item_check", "cavmd_verlet_input_make", "cavmd_verlet_create", "cavmd_verlet_destroy",
+    "cavmd_verlet_set_items", "cavmd_verlet_accelerations", "cavmd_verlet_step_one", "cavmd_verlet_step_two",
+    "cavmd_verlet_read", "cavmd_verlet_reset", "cavmd_verlet_state_device_ptr",
     "cavmd_field_recorder_item_check", "cavmd_field_recorder_create", "cavmd_field_recorder_destroy",
     "cavmd_field_recorder_set_items", "cavmd_field_recorder_record", "cavmd_field_recorder_rows", "cavmd_field_recorder_read",
     "cavmd_field_recorder_read_fields", "cavmd_field_recorder_reset", "cavmd_field_recorder_device_ptr",
@@ -364,6 +401,28 @@ def _declare(lib):
         lib.cavmd_field_recorder_reset.restype = ci
         lib.cavmd_field_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
         lib.cavmd_field_recorder_device_ptr.restype = ci
+        lib.cavmd_verlet_item_check.argtypes = [P(VerletItem)]
+        lib.cavmd_verlet_item_check.restype = ci
+        lib.cavmd_verlet_input_make.argtypes = [dbl, dbl, dbl, P(dbl * 3), P(VerletInput)]
+        lib.cavmd_verlet_input_make.restype = ci
+        lib.cavmd_verlet_create.argtypes = [vp, sz, P(VerletItem), P(vp)]
+        lib.cavmd_verlet_create.restype = ci
+        lib.cavmd_verlet_destroy.argtypes = [vp]
+        lib.cavmd_verlet_destroy.restype = ci
+        lib.cavmd_verlet_set_items.argtypes = [vp, sz, sz, P(VerletItem)]
+        lib.cavmd_verlet_set_items.restype = ci
+        lib.cavmd_verlet_accelerations.argtypes = [vp, vp]
+        lib.cavmd_verlet_accelerations.restype = ci
+        lib.cavmd_verlet_step_one.argtypes = [vp, vp, vp]
+        lib.cavmd_verlet_step_one.restype = ci
+        lib.cavmd_verlet_step_two.argtypes = [vp, vp, vp]
+        lib.cavmd_verlet_step_two.restype = ci
+        lib.cavmd_verlet_read.argtypes = [vp, vp, vp]
+        lib.cavmd_verlet_read.restype = ci
+        lib.cavmd_verlet_reset.argtypes = [vp, vp]
+        lib.cavmd_verlet_reset.restype = ci
+        lib.cavmd_verlet_state_device_ptr.argtypes = [vp, P(vp)]
+        lib.cavmd_verlet_state_device_ptr.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -921,3 +980,66 @@ class FieldRecorder(_ItemTableHandle):
         check(self._lib.cavmd_field_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)),
               "cavmd_field_recorder_device_ptr")
         return int(rec.value), int(rows.value)
+
+
+VERLET_STATE_DTYPE_FIELDS = [("steps", "<u8"), ("out_of_box", "<u8"), ("langevin_reservoir", "<f8"), ("reserved", "<f8")]
+
+
+def verlet_state_dtype():
+    """numpy structured dtype with the layout of cavmd_verlet_state (32 bytes)."""
+    import numpy as np
+    return np.dtype(VERLET_STATE_DTYPE_FIELDS)
+
+
+def verlet_item_check(item: VerletItem) -> int:
+    """Status cavmd_verlet_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_verlet_item_check(ctypes.byref(item)))
+
+
+def verlet_input_make(dt, gamma=0.0, kT=0.0, uniform=(0.0, 0.0, 0.0)) -> VerletInput:
+    """One input row with langevin_coeff = sqrt(6 gamma kT / dt) and the skip flag taken by the library (host arithmetic)."""
+    row = VerletInput()
+    u = (ctypes.c_double * 3)(*[float(x) for x in uniform])
+    check(load().cavmd_verlet_input_make(float(dt), float(gamma), float(kT), ctypes.byref(u), ctypes.byref(row)),
+          "cavmd_verlet_input_make")
+    return row
+
+
+class Verlet(_ItemTableHandle):
+    """Owns one cavmd_verlet: the two velocity-Verlet half-steps of B independent small systems, each ONE kernel launch, one
+    workgroup per system, the step's inputs read from device memory.  Launched by N descending."""
+    _ITEM, _PREFIX = VerletItem, "cavmd_verlet"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items):
+        self._create(workspace, items)
+
+    def accelerations(self, stream: int = 0) -> None:
+        """One kernel: a = F / m (and the net force) of every item from the force arrays as they are."""
+        check(self._lib.cavmd_verlet_accelerations(self._h, ctypes.c_void_p(stream)), "cavmd_verlet_accelerations")
+
+    def step_one(self, stream: int, inputs_ptr: int) -> None:
+        """One kernel: kick, drift and wrap of every item, inputs read from the n_items device rows when the kernel runs."""
+        check(self._lib.cavmd_verlet_step_one(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)),
+              "cavmd_verlet_step_one")
+
+    def step_two(self, stream: int, inputs_ptr: int) -> None:
+        """One kernel: net force, Langevin bath of the one coupled particle, acceleration and kick of every item."""
+        check(self._lib.cavmd_verlet_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)),
+              "cavmd_verlet_step_two")
+
+    def read(self, stream: int = 0):
+        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_verlet_state."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=verlet_state_dtype())
+        check(self._lib.cavmd_verlet_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
+              "cavmd_verlet_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_verlet_reset(self._h, ctypes.c_void_p(stream)), "cavmd_verlet_reset")
+
+    def state_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        check(self._lib.cavmd_verlet_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_verlet_state_device_ptr")
+        return int(p.value)

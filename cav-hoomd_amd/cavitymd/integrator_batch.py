@@ -1,0 +1,197 @@
+"""``VerletBatch`` -- the velocity-Verlet step of B independent small systems, each half-step ONE kernel launch.
+
+The reference has no integrator of its own: its driver gives the molecules to HOOMD-blue's ``ConstantVolume`` method and the
+one cavity particle to HOOMD-blue's ``Langevin`` method (``--molecular-bath bussi --cavity-bath langevin``, the default of
+examples/05_advanced_run.py:652, 677).  This class is the two half-steps of those methods (``cavmd_verlet_step_one`` /
+``cavmd_verlet_step_two``; the arithmetic is spelled out in include/cavmd.h) on the arrays a ``CavityForceBatch`` already
+evaluates, so that a captured graph of this package's kernels alone advances a trajectory::
+
+    integrator = VerletBatch(forces, velocities, langevin_index=500)
+    forces.compute(); integrator.prime()                  # a = F / m once, as HOOMD does at the start of a run
+    with torch.cuda.graph(graph):
+        integrator.draw_inputs(dt, gamma, kT)             # or set_inputs(...) in stream order before each replay
+        integrator.step_one()                             # v += a dt / 2; x += v dt; wrap
+        forces.compute()
+        integrator.step_two()                             # a = F / m (+ the cavity particle's bath); v += a dt / 2
+        recorder.record(); thermostat.draw_inputs(0, dt); thermostat.step_async()
+
+The step's inputs live in a ``(B, 8)`` float64 DEVICE tensor, ``inputs`` (row = dt, gamma, sqrt(6 gamma kT / dt), three
+variates uniform in [-1, 1), skip flag, one reserved word), read by both kernels when they run.  ``draw_inputs`` uses torch's
+generator, not HOOMD's RandomGenerator: the variates are not bit-comparable with a HOOMD run; everything after the draw is.
+The Langevin bath acts on at most one particle per system.  No CPU fallback: CPU tensors raise.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _capi
+from ._device import stream_handle
+
+
+def _device_tensor(t, what: str, columns: int):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError(f"VerletBatch needs the {what} arrays in GPU memory; no CPU fallback exists in this package")
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != columns or not t.is_contiguous():
+        raise ValueError(f"every {what} array must be a contiguous (N,{columns}) float64 tensor")
+    return t
+
+
+def _per_system(value, n: int, name: str):
+    if value is None or np.isscalar(value):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"{name}: one value, or one per system ({n}), not {len(value)}")
+    return value
+
+
+class VerletBatch:
+    """force_batch: the ``CavityForceBatch`` whose systems are integrated (positions, images and boxes are taken from its
+    system definitions, its force arrays are the first force of every system); velocities: one (N_k, 4) device tensor per
+    system (mass in column 3); extra_forces: None, or per system a list of up to three more (N_k, 4) force tensors, summed
+    after the cavity force in list order; langevin_index: None, one index, or one per system (None / -1: no bath);
+    net_forces: allocate ``net_forces`` and have step two (and ``prime``) write the summed force there."""
+
+    def __init__(self, force_batch, velocities, extra_forces=None, langevin_index=None, net_forces: bool = False):
+        velocities = list(velocities)
+        for v in velocities:
+            _device_tensor(v, "velocity", 4)   # CPU tensors are refused before anything else is looked at
+        B = len(force_batch)
+        if len(velocities) != B:
+            raise ValueError(f"velocities: one entry per system of the force batch ({B})")
+        extra_forces = [None] * B if extra_forces is None else list(extra_forces)
+        if len(extra_forces) != B:
+            raise ValueError("extra_forces: None, or one list per system")
+        extra_forces = [[] if e is None else list(e) for e in extra_forces]
+        langevin = [-1 if i is None else int(i) for i in _per_system(langevin_index, B, "langevin_index")]
+        sysdefs = force_batch._sysdefs
+        forces = force_batch.forces
+        dev = velocities[0].device if B else None
+        self._device = dev
+        self.accel, self.net_forces, items = [], ([] if net_forces else None), []
+        for k in range(B):
+            pd = sysdefs[k].getParticleData()
+            n = pd.getN()
+            v = velocities[k]
+            if v.device != dev or pd.device != dev:
+                raise ValueError("all systems of one integrator live on one device")
+            if v.shape[0] != n:
+                raise ValueError(f"system {k}: the velocity array has {v.shape[0]} rows, the force batch evaluates {n}")
+            if len(extra_forces[k]) > 3:
+                raise ValueError(f"system {k}: at most three extra force arrays")
+            for f in extra_forces[k]:
+                if _device_tensor(f, "force", 4).shape[0] != n or f.device != dev:
+                    raise ValueError(f"system {k}: an extra force array does not match the system")
+            a = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+            self.accel.append(a)
+            net = None
+            if net_forces:
+                net = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+                self.net_forces.append(net)
+            flist = [forces[k]] + extra_forces[k]
+            items.append(_capi.verlet_item(n, pd.getPositions().data_ptr() if n else 0, pd.getImages().data_ptr() if n else 0,
+                                           v.data_ptr() if n else 0, a.data_ptr() if n else 0,
+                                           [f.data_ptr() if n else 0 for f in flist], net.data_ptr() if (net is not None and n) else 0,
+                                           pd.getGlobalBox().getL(), langevin[k]))
+        self._force_batch, self._velocities, self._extra = force_batch, velocities, extra_forces
+        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self._ws = _capi.Workspace(1, device=self._dev_index)
+        self._verlet = _capi.Verlet(self._ws, items)
+        self.n_systems = B
+        self.inputs = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+        self.inputs[:, 6] = 1.0   # a non-zero skip word: every system is skipped until its inputs are set
+        self._pinned = torch.zeros((B, 8), dtype=torch.float64).pin_memory()
+        self._copy_done = None
+        self._stream = 0
+        torch.cuda.current_stream(dev).synchronize()   # accel, inputs and the states are zero before any stream steps
+
+    def _need(self):
+        if self._verlet is None:
+            raise RuntimeError("VerletBatch used after close()")
+
+    # -- the step's inputs -------------------------------------------------------------------------------------------------
+    def _rows(self, dt, gamma, kT, uniforms=None) -> np.ndarray:
+        """(B, 8) host rows made by cavmd_verlet_input_make; dt, gamma, kT: one number or one per system."""
+        B = self.n_systems
+        dts, gammas, kTs = (_per_system(x, B, name) for x, name in ((dt, "dt"), (gamma, "gamma"), (kT, "kT")))
+        u = np.zeros((B, 3)) if uniforms is None else np.asarray(uniforms, dtype=np.float64)
+        if u.shape != (B, 3):
+            raise ValueError(f"uniforms must have shape ({B}, 3)")
+        rows = (_capi.VerletInput * max(B, 1))()
+        for i in range(B):
+            rows[i] = _capi.verlet_input_make(dts[i], gammas[i], kTs[i], u[i])
+        return np.frombuffer(rows, dtype=np.float64).reshape(-1, 8)[:B].copy()
+
+    def set_inputs(self, dt, gamma=0.0, kT=0.0, uniforms=None) -> None:
+        """uniforms: None (no bath: zeros) or a (B, 3) host array of variates in [-1, 1).  The rows reach ``inputs`` with one
+        asynchronous copy on the current stream."""
+        self._need()
+        if self._copy_done is not None:
+            self._copy_done.synchronize()                       # the staging buffer's last copy has left it
+        self._pinned.numpy()[:] = self._rows(dt, gamma, kT, uniforms)
+        self.inputs.copy_(self._pinned, non_blocking=True)
+        self._copy_done = torch.cuda.Event()
+        self._copy_done.record(torch.cuda.current_stream(self._device))
+
+    def draw_inputs(self, dt, gamma, kT, generator=None) -> None:
+        """Fills ``inputs`` ON THE DEVICE, in stream order, with no host wait: the variates as ``2 * torch.rand - 1``, the rest
+        from host arithmetic (uploaded only when it changes).  Capturable together with the two half-steps."""
+        self._need()
+        const = self._rows(dt, gamma, kT)
+        key = const.tobytes()
+        if getattr(self, "_const_key", None) != key:
+            self._const_dev = torch.from_numpy(const).to(self._device)
+            self._const_key = key
+        u = torch.rand((self.n_systems, 3), dtype=torch.float64, device=self._device, generator=generator)
+        self.inputs.copy_(self._const_dev)
+        self.inputs[:, 3:6] = 2.0 * u - 1.0
+
+    # -- the launches ------------------------------------------------------------------------------------------------------
+    def _launch(self, call, stream, *args) -> None:
+        self._need()
+        handle = stream_handle(stream, self._device)
+        call(handle, *args)
+        self._stream = handle
+
+    def prime(self, stream=None) -> None:
+        """ONE kernel: ``accel`` = F / m from the force arrays as they are (after a ``force_batch.compute()``)."""
+        self._launch(self._verlet.accelerations, stream)
+
+    def step_one(self, stream=None) -> None:
+        """ONE kernel: v += (a / 2) dt, x += dt v, one wrap per axis with the image following.  May be captured."""
+        self._launch(self._verlet.step_one, stream, self.inputs.data_ptr())
+
+    def step_two(self, stream=None) -> None:
+        """ONE kernel: F = sum of the force arrays (+ the bath on the Langevin particle), a = F / m, v += (a / 2) dt."""
+        self._launch(self._verlet.step_two, stream, self.inputs.data_ptr())
+
+    def state(self, stream=None) -> np.ndarray:
+        """Per-system counters (``steps``, ``out_of_box``, ``langevin_reservoir``).  Default: waits for the whole device (a
+        graph replays on the stream it is launched on), then reads; never inside a capture."""
+        self._need()
+        if stream is None:
+            torch.cuda.synchronize(self._device)
+        return self._verlet.read(stream_handle(stream, self._device))
+
+    def reset(self, stream=None) -> None:
+        """Zero every system's counters, ordered on ``stream`` (default: torch's current stream)."""
+        self._need()
+        self._verlet.reset(stream_handle(stream, self._device))
+
+    @property
+    def verlet(self) -> _capi.Verlet:
+        return self._verlet
+
+    def close(self) -> None:
+        if getattr(self, "_verlet", None) is not None:
+            self._verlet.close()
+        if getattr(self, "_ws", None) is not None:
+            self._ws.close()
+        self._verlet = self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -154,6 +154,7 @@ struct cavmd_workspace
     unsigned bussi_batches = 0;         // live cavmd_bussi_batch objects created from this workspace (cavmd_destroy refuses)
     unsigned recorders = 0;             // live cavmd_recorder objects created from this workspace (the same)
     unsigned field_recorders = 0;       // live cavmd_field_recorder objects created from this workspace (the same)
+    unsigned verlets = 0;               // live cavmd_verlet objects created from this workspace (the same)
 };
 
 namespace
@@ -587,6 +588,8 @@ int cavmd_destroy(cavmd_workspace* ws)
     if (ws->recorders != 0)     // nor does a recorder
         return CAVMD_ERR_INVALID_VALUE;
     if (ws->field_recorders != 0) // nor a field recorder
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->verlets != 0)         // nor an integrator
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -2492,6 +2495,204 @@ int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream_)
 int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records, const uint64_t** rows)
 {
     return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
+}
+
+} // extern "C"
+
+// ---- the velocity-Verlet step of a batch of independent small systems, one launch per half-step (cavmd_verlet_batch_kernel.hpp) --
+struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N descending
+{
+    cavmd_workspace* ws = nullptr;
+    DeviceArray<VerletState> d_state; // n states, indexed by item
+
+    cavmd_verlet()
+        : ItemTable(cavmd_verlet_item_check, [](const cavmd_verlet_item& it) { return it.N; },
+                    uploaded_as_it_is<cavmd_verlet_item, VerletRow>)
+    {
+    }
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_verlet_item) == sizeof(VerletRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_verlet_item, d_pos) == offsetof(VerletRow, pos2)
+                  && offsetof(cavmd_verlet_item, d_image) == offsetof(VerletRow, image)
+                  && offsetof(cavmd_verlet_item, d_vel) == offsetof(VerletRow, vel2)
+                  && offsetof(cavmd_verlet_item, d_accel) == offsetof(VerletRow, accel)
+                  && offsetof(cavmd_verlet_item, d_force) == offsetof(VerletRow, force2)
+                  && offsetof(cavmd_verlet_item, d_net_force) == offsetof(VerletRow, net2)
+                  && offsetof(cavmd_verlet_item, Lx) == offsetof(VerletRow, Lx)
+                  && offsetof(cavmd_verlet_item, N) == offsetof(VerletRow, n)
+                  && offsetof(cavmd_verlet_item, langevin_index) == offsetof(VerletRow, langevin),
+              "integrator item layout");
+static_assert(sizeof(cavmd_verlet_input) == sizeof(VerletInput) && offsetof(cavmd_verlet_input, dt) == offsetof(VerletInput, dt)
+                  && offsetof(cavmd_verlet_input, langevin_gamma) == offsetof(VerletInput, gamma)
+                  && offsetof(cavmd_verlet_input, langevin_coeff) == offsetof(VerletInput, coeff)
+                  && offsetof(cavmd_verlet_input, uniform) == offsetof(VerletInput, uniform)
+                  && offsetof(cavmd_verlet_input, skip) == offsetof(VerletInput, skip),
+              "integrator input layout");
+static_assert(sizeof(cavmd_verlet_state) == sizeof(VerletState) && offsetof(cavmd_verlet_state, steps) == offsetof(VerletState, steps)
+                  && offsetof(cavmd_verlet_state, out_of_box) == offsetof(VerletState, out_of_box)
+                  && offsetof(cavmd_verlet_state, langevin_reservoir) == offsetof(VerletState, reservoir),
+              "the integrator states are read out as they are");
+static_assert(sizeof(((cavmd_verlet_item*)nullptr)->d_force) / sizeof(void*) == kVerletMaxForces, "force arrays per item");
+
+// one launch of n_items workgroups of one of the three kernels
+template <class Kernel>
+int verlet_launch(cavmd_verlet* v, hipStream_t stream, Kernel kernel, const cavmd_verlet_input* d_inputs)
+{
+    DeviceGuard guard(v->device);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)v->n), dim3(256), 0, stream, v->d_rows, v->d_order,
+                       reinterpret_cast<const VerletInput*>(d_inputs), v->d_state.ptr);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    v->enqueued_on(stream);
+    return CAVMD_OK;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_verlet_item_check(const cavmd_verlet_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 3; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_image & 3) || ((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_accel & 7)
+        || ((uintptr_t)it->d_net_force & 15))
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < kVerletMaxForces; ++k)
+    {
+        if ((uintptr_t)it->d_force[k] & 15)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (k > 0 && it->d_force[k] && !it->d_force[k - 1]) // the list ends at the first NULL
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    if (it->N != 0 && (!it->d_pos || !it->d_image || !it->d_vel || !it->d_accel || !it->d_force[0]))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->langevin_index < -1 || (it->langevin_index >= 0 && (uint32_t)it->langevin_index >= it->N))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_input_make(double dt, double gamma, double kT, const double uniform[3], cavmd_verlet_input* row)
+{
+    if (!row || !uniform)
+        return CAVMD_ERR_INVALID_VALUE;
+    memset(row, 0, sizeof(*row));
+    row->dt = dt;
+    row->langevin_gamma = gamma;
+    // TwoStepLangevin: coeff = sqrt(6 gamma T / deltaT) [HOOMD upstream, not in checkout]
+    row->langevin_coeff = (gamma != 0.0 && dt != 0.0) ? sqrt(6.0 * gamma * kT / dt) : 0.0;
+    for (int c = 0; c < 3; ++c)
+        row->uniform[c] = uniform[c];
+    row->skip = (dt == 0.0) ? 1u : 0u;
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_item* h_items, cavmd_verlet** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+        return CAVMD_ERR_INVALID_VALUE;
+    const int st = check_items(h_items, n_items, cavmd_verlet_item_check);
+    if (st != CAVMD_OK)
+        return st;
+    cavmd_verlet* v = new (std::nothrow) cavmd_verlet();
+    if (!v)
+        return (int)hipErrorOutOfMemory;
+    v->adopt(ws->device, h_items, n_items);
+
+    DeviceGuard guard(v->device);
+    hipError_t e = v->upload();
+    if (e == hipSuccess)
+        e = v->d_state.alloc_zeroed(n_items);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // the memset is done before any stream of the caller's steps
+    if (e != hipSuccess)
+    {
+        cavmd_verlet_destroy(v);
+        return (int)e;
+    }
+    v->ws = ws;
+    ws->verlets += 1;
+    *out = v;
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_destroy(cavmd_verlet* v)
+{
+    if (!v)
+        return CAVMD_OK;
+    DeviceGuard guard(v->device);
+    v->quiesce_and_free();
+    if (v->ws)
+        v->ws->verlets -= 1;
+    delete v;
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_set_items(cavmd_verlet* v, size_t first, size_t count, const cavmd_verlet_item* h_items)
+{
+    return v ? v->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_verlet_accelerations(cavmd_verlet* v, void* stream_)
+{
+    if (!v)
+        return CAVMD_ERR_INVALID_VALUE;
+    return verlet_launch(v, (hipStream_t)stream_, verlet_step_two_kernel<256, true>, nullptr);
+}
+
+int cavmd_verlet_step_one(cavmd_verlet* v, void* stream_, const cavmd_verlet_input* d_inputs)
+{
+    if (!v || !d_inputs || ((uintptr_t)d_inputs & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    return verlet_launch(v, (hipStream_t)stream_, verlet_step_one_kernel<256>, d_inputs);
+}
+
+int cavmd_verlet_step_two(cavmd_verlet* v, void* stream_, const cavmd_verlet_input* d_inputs)
+{
+    if (!v || !d_inputs || ((uintptr_t)d_inputs & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    return verlet_launch(v, (hipStream_t)stream_, verlet_step_two_kernel<256, false>, d_inputs);
+}
+
+int cavmd_verlet_read(cavmd_verlet* v, void* stream_, cavmd_verlet_state* out)
+{
+    if (!v || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(v->device);
+    const int st = sync_uncaptured((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(hipMemcpy(out, v->d_state.ptr, sizeof(VerletState) * v->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_reset(cavmd_verlet* v, void* stream_)
+{
+    if (!v)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(v->device);
+    CAVMD_HIP_TRY(hipMemsetAsync(v->d_state.ptr, 0, sizeof(VerletState) * v->n, (hipStream_t)stream_));
+    return CAVMD_OK;
+}
+
+int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out)
+{
+    if (!v || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = reinterpret_cast<const cavmd_verlet_state*>(v->d_state.ptr);
+    return CAVMD_OK;
 }
 
 } // extern "C"

@@ -26,7 +26,8 @@
 //        cavmd_batch_kernel.hpp (many small systems in one launch, one workgroup each),
 //        cavmd_persistent_kernel.hpp (the single-launch evaluation), cavmd_observable_kernels.hpp (rows f2-f4),
 //        cavmd_bussi_batch_kernel.hpp (the thermostat step of many small systems in one launch, one workgroup each),
-//        cavmd_recorder_kernel.hpp (their per-step observables appended to a time series in device memory, one launch).
+//        cavmd_recorder_kernel.hpp (their per-step observables appended to a time series in device memory, one launch),
+//        cavmd_verlet_batch_kernel.hpp (their velocity-Verlet half-steps, one launch each).
 #pragma once
 
 #include "cavmd_reduce.hpp"
@@ -37,3 +38,4 @@
 #include "cavmd_bussi_batch_kernel.hpp"
 #include "cavmd_recorder_kernel.hpp"
 #include "cavmd_field_recorder_kernel.hpp"
+#include "cavmd_verlet_batch_kernel.hpp"

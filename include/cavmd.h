@@ -677,6 +677,103 @@ CAVMD_API int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream);
 CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records,
                                               const uint64_t** rows);
 
+/* ---- the velocity-Verlet step of a batch, two launches per step: what makes the captured sequence a complete MD step ------ */
+/* The reference has no integrator of its own: its driver gives the molecules to HOOMD-blue's ConstantVolume method and the one
+ * cavity particle to HOOMD-blue's Langevin method (--molecular-bath bussi --cavity-bath langevin, the default of
+ * examples/05_advanced_run.py:652, 677).  This section is the two half-steps of those methods for B registered systems, each
+ * half ONE kernel, one 256-thread workgroup per system, all per-step inputs read from DEVICE memory when the kernel RUNS.  A
+ * captured step is then {cavmd_verlet_step_one, cavmd_batch_compute, cavmd_verlet_step_two, cavmd_recorder_record,
+ * cavmd_field_recorder_record, cavmd_bussi_batch_step}, and it follows an adaptive dt and fresh variates on replay.  Systems
+ * are independent: no workgroup waits for another one, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ *
+ * The arithmetic restates TwoStepConstantVolume / TwoStepLangevin of HOOMD-blue 4.x [HOOMD upstream, not in checkout]; the
+ * expressions below ARE the contract.  Every operation is one IEEE fp64 rounding, no FMA; per particle j and component c:
+ *   step one   (a row with skip != 0, or an item with N == 0, leaves the item untouched)
+ *     1. v_c = v_c + (0.5 * a_c) * dt
+ *     2. x_c = x_c + dt * v_c
+ *     3. one wrap per axis, hi = L_c * 0.5, lo = -hi: if x_c >= hi then x_c -= L_c and the image is incremented, otherwise if
+ *        x_c < lo then x_c += L_c and the image is decremented
+ *     4. a component still outside [lo, hi) afterwards (NaN included) is counted in out_of_box; it is not repaired
+ *   step two   (the same rows are left untouched)
+ *     1. minv = 1.0 / m
+ *     2. F_c = ((f0_c + f1_c) + f2_c) + f3_c over the force arrays present
+ *     3. d_net_force, if given, receives (F_x, F_y, F_z, the same left-to-right sum of .w)
+ *     4. for j == langevin_index with langevin_gamma != 0, v being the velocity from BEFORE the kick:
+ *        bd_c = uniform_c * langevin_coeff - langevin_gamma * v_c;  F_c = F_c + bd_c;
+ *        tally = (bd_x * v_x + bd_y * v_y) + bd_z * v_z;  langevin_reservoir = langevin_reservoir - tally * dt
+ *     5. a_c = F_c * minv, stored to d_accel
+ *     6. v_c = v_c + (0.5 * a_c) * dt
+ *     7. steps += 1
+ *   cavmd_verlet_accelerations is 1, 2, 3 and 5 only: no Langevin, no kick, nothing counted, no input row.
+ * pos.w (the type tag) and vel.w (the mass) are never written.  Out of scope: Langevin on more than one particle per system
+ * (3 N variates per step), rotational degrees of freedom, triclinic boxes. */
+typedef struct cavmd_verlet_item         /* 128 B; all pointers DEVICE pointers; the arrays of one item must not overlap */
+{
+    cavmd_double4* d_pos;                /* HOOMD Scalar4 positions (wrapped), type tag in .w; 16-byte aligned */
+    cavmd_int3* d_image;                 /* 4-byte aligned */
+    cavmd_double4* d_vel;                /* HOOMD Scalar4 velocities, mass in .w; 16-byte aligned */
+    double* d_accel;                     /* packed N x 3 (HOOMD's Scalar3), caller-owned, 8-byte aligned: written by
+                                            cavmd_verlet_accelerations / step_two, read by step_one */
+    const cavmd_double4* d_force[4];     /* summed left to right; [0] non-NULL when N > 0; the list ends at the first NULL;
+                                            16-byte aligned */
+    cavmd_double4* d_net_force;          /* NULL, or receives the sum (16-byte aligned) */
+    double Lx, Ly, Lz;
+    uint32_t N;                          /* 0 is legal: nothing of the item is read or written; <= CAVMD_BATCH_MAX_ITEM_N */
+    int32_t langevin_index;              /* -1: none; else < N: the particle coupled to the Langevin bath */
+    uint64_t reserved[3];                /* must be 0 */
+} cavmd_verlet_item;
+typedef struct cavmd_verlet_input        /* 64 B; one row per item, in DEVICE memory, owned by the caller */
+{
+    double dt;
+    double langevin_gamma;               /* 0: no bath this step */
+    double langevin_coeff;               /* sqrt(6 gamma kT / dt), taken on the host (cavmd_verlet_input_make) */
+    double uniform[3];                   /* three variates uniform in [-1, 1) */
+    uint64_t skip;                       /* != 0: dt == 0, the item is left untouched by both half-steps */
+    uint64_t reserved;
+} cavmd_verlet_input;
+typedef struct cavmd_verlet_state        /* 32 B; one per item, in device memory */
+{
+    uint64_t steps;                      /* second half-steps applied */
+    uint64_t out_of_box;                 /* coordinates left outside the box by step one (a dt or a force gone wrong) */
+    double langevin_reservoir;           /* HOOMD's reservoir energy of the Langevin method: - sum of tally * dt */
+    double reserved;
+} cavmd_verlet_state;
+typedef struct cavmd_verlet cavmd_verlet; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * reserved != 0, a misaligned array, a null d_pos / d_image / d_vel / d_accel / d_force[0] with N > 0, a non-NULL d_force entry
+ * after a NULL one, a langevin_index below -1 or not below N; CAVMD_ERR_CAPACITY for N above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_verlet_item_check(const cavmd_verlet_item* item);
+/* Fills one input row on the HOST: langevin_coeff = sqrt(6 * gamma * kT / dt) (0 for gamma == 0 or dt == 0), skip = (dt == 0),
+ * as c = exp(-deltaT / tau) is taken on the host for the thermostat batch.  Needs no device.  CAVMD_ERR_INVALID_VALUE for a
+ * null `uniform` or `row`.  The caller copies rows to its device array. */
+CAVMD_API int cavmd_verlet_input_make(double dt, double gamma, double kT, const double uniform[3], cavmd_verlet_input* row);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), copies the table to the device of `ws` (set-up time)
+ * and allocates one zeroed state per item on the device.  cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while
+ * an integrator of the workspace is alive.  Without a device there is no workspace, hence no integrator. */
+CAVMD_API int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_item* h_items, cavmd_verlet** out);
+/* Synchronises the stream of the last launch (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_verlet_destroy(cavmd_verlet* v);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
+ * changed if a row is refused; the items' states are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and
+ * for a range outside the batch. */
+CAVMD_API int cavmd_verlet_set_items(cavmd_verlet* v, size_t first, size_t count, const cavmd_verlet_item* h_items);
+/* Each of the three calls below enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host
+ * wait; may be captured into a hipGraph.  Workgroups start in order of N descending (ties in item order).  d_inputs: n_items
+ * rows in DEVICE memory (CAVMD_ERR_INVALID_VALUE if null or not 8-byte aligned), read when the kernel RUNS: the caller
+ * refreshes that buffer, in stream order, between replays; the pointer itself is frozen at capture.  Both half-steps of one
+ * step must see the same rows.  One integrator serves one host thread and one stream at a time. */
+/* a = F / m from the force arrays as they are (and the net force, if asked for): what HOOMD does once at the start of a run. */
+CAVMD_API int cavmd_verlet_accelerations(cavmd_verlet* v, void* stream);
+CAVMD_API int cavmd_verlet_step_one(cavmd_verlet* v, void* stream, const cavmd_verlet_input* d_inputs);
+CAVMD_API int cavmd_verlet_step_two(cavmd_verlet* v, void* stream, const cavmd_verlet_input* d_inputs);
+/* Synchronises `stream`, then out = the n_items states.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
+CAVMD_API int cavmd_verlet_read(cavmd_verlet* v, void* stream, cavmd_verlet_state* out);
+/* Zero the states of all items (ordered on `stream`). */
+CAVMD_API int cavmd_verlet_reset(cavmd_verlet* v, void* stream);
+/* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out);
+
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
 CAVMD_API int cavmd_profile_enable(cavmd_workspace* ws, int on);
