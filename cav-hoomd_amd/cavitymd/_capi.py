@@ -136,6 +136,38 @@ class VerletState(ctypes.Structure):
                 ("reserved", ctypes.c_double)]
 
 
+class MolecularPair(ctypes.Structure):
+    """cavmd_molecular_pair (64 bytes): one entry of the pair table, made by cavmd_molecular_pair_make."""
+    _fields_ = [("lj1", ctypes.c_double), ("lj2", ctypes.c_double), ("lj1_12", ctypes.c_double), ("lj2_6", ctypes.c_double),
+                ("rcutsq", ctypes.c_double), ("eshift", ctypes.c_double), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class MolecularBondParams(ctypes.Structure):
+    """cavmd_molecular_bond_params (16 bytes)."""
+    _fields_ = [("K", ctypes.c_double), ("r0", ctypes.c_double)]
+
+
+class MolecularParams(ctypes.Structure):
+    """cavmd_molecular_params (4240 bytes)."""
+    _fields_ = [("n_types", ctypes.c_uint32), ("n_bond_types", ctypes.c_uint32), ("reserved", ctypes.c_uint64),
+                ("pair", (MolecularPair * 8) * 8), ("bond", MolecularBondParams * 8)]
+
+
+class MolecularBond(ctypes.Structure):
+    """cavmd_molecular_bond (12 bytes)."""
+    _fields_ = [("a", ctypes.c_uint32), ("b", ctypes.c_uint32), ("type", ctypes.c_uint32)]
+
+
+class MolecularItem(ctypes.Structure):
+    """cavmd_molecular_item (64 bytes): d_pos / d_force are DEVICE pointers, h_bonds a HOST pointer read during create /
+    set_items only."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_force", ctypes.c_void_p), ("h_bonds", ctypes.c_void_p), ("Lx", ctypes.c_double),
+                ("Ly", ctypes.c_double), ("Lz", ctypes.c_double), ("N", ctypes.c_uint32), ("n_bonds", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64)]
+
+
+MOLECULAR_MAX_ITEM_N = 2048
+MOLECULAR_MAX_BONDS = 4
 FIELD_MAX_WAVEVECTORS = 256
 FIELD_MAX_REFERENCES = 16
 BATCH_MAX_ITEMS = 65536
@@ -196,8 +228,24 @@ def verlet_item(N, pos_ptr, image_ptr, vel_ptr, accel_ptr, force_ptrs, net_force
     return it
 
 
+def molecular_item(N, pos_ptr, force_ptr, box_L, bonds=None) -> "MolecularItem":
+    """bonds: None or an (n_bonds, 3) array of (a, b, bond type); the item keeps the array alive (``_bonds``) for the call
+    that reads it."""
+    import numpy as np
+    it = MolecularItem()
+    it.d_pos, it.d_force = pos_ptr or None, force_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.N = int(N)
+    b = np.zeros((0, 3), dtype=np.uint32) if bonds is None else np.ascontiguousarray(bonds, dtype=np.uint32).reshape(-1, 3)
+    it._bonds = b
+    it.h_bonds, it.n_bonds = (b.ctypes.data if len(b) else None), len(b)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_molecular_pair_make", "cavmd_molecular_params_check", "cavmd_molecular_item_check", "cavmd_molecular_order",
+    "cavmd_molecular_create", "cavmd_molecular_destroy", "cavmd_molecular_set_items", "cavmd_molecular_compute",
     "cavmd_verlet_item_check", "cavmd_verlet_input_make", "cavmd_verlet_create", "cavmd_verlet_destroy",
     "cavmd_verlet_set_items", "cavmd_verlet_accelerations", "cavmd_verlet_step_one", "cavmd_verlet_step_two",
     "cavmd_verlet_read", "cavmd_verlet_reset", "cavmd_verlet_state_device_ptr",
@@ -423,6 +471,22 @@ def _declare(lib):
         lib.cavmd_verlet_reset.restype = ci
         lib.cavmd_verlet_state_device_ptr.argtypes = [vp, P(vp)]
         lib.cavmd_verlet_state_device_ptr.restype = ci
+        lib.cavmd_molecular_pair_make.argtypes = [dbl, dbl, dbl, ci, P(MolecularPair)]
+        lib.cavmd_molecular_pair_make.restype = ci
+        lib.cavmd_molecular_params_check.argtypes = [P(MolecularParams)]
+        lib.cavmd_molecular_params_check.restype = ci
+        lib.cavmd_molecular_item_check.argtypes = [P(MolecularParams), P(MolecularItem)]
+        lib.cavmd_molecular_item_check.restype = ci
+        lib.cavmd_molecular_order.argtypes = [P(ci), P(ci)]
+        lib.cavmd_molecular_order.restype = ci
+        lib.cavmd_molecular_create.argtypes = [vp, P(MolecularParams), sz, P(MolecularItem), P(vp)]
+        lib.cavmd_molecular_create.restype = ci
+        lib.cavmd_molecular_destroy.argtypes = [vp]
+        lib.cavmd_molecular_destroy.restype = ci
+        lib.cavmd_molecular_set_items.argtypes = [vp, sz, sz, P(MolecularItem)]
+        lib.cavmd_molecular_set_items.restype = ci
+        lib.cavmd_molecular_compute.argtypes = [vp, vp]
+        lib.cavmd_molecular_compute.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -1043,3 +1107,69 @@ class Verlet(_ItemTableHandle):
         p = ctypes.c_void_p()
         check(self._lib.cavmd_verlet_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_verlet_state_device_ptr")
         return int(p.value)
+
+
+def molecular_order():
+    """(ROWS, S): the particles a workgroup of the molecular force kernel owns and the partial sums per particle, as the
+    library was compiled (S = CAVMD_MOLECULAR_J_SPLIT fixes the published summation order)."""
+    rows, split = ctypes.c_int(), ctypes.c_int()
+    check(load().cavmd_molecular_order(ctypes.byref(rows), ctypes.byref(split)), "cavmd_molecular_order")
+    return int(rows.value), int(split.value)
+
+
+def molecular_pair_make(epsilon, sigma, r_cut, shift=True) -> MolecularPair:
+    """One entry of the pair table with the constants taken by the library (host arithmetic)."""
+    out = MolecularPair()
+    check(load().cavmd_molecular_pair_make(float(epsilon), float(sigma), float(r_cut), 1 if shift else 0, ctypes.byref(out)),
+          "cavmd_molecular_pair_make")
+    return out
+
+
+def molecular_params(n_types, harmonic, lj, shift=True) -> MolecularParams:
+    """harmonic: {bond type: (K, r0)}; lj: {(type a, type b): (epsilon, sigma, r_cut)}, entered symmetrically; type pairs that
+    are not listed keep rcutsq = 0 and do not interact."""
+    prm = MolecularParams()
+    prm.n_types = int(n_types)
+    prm.n_bond_types = (max(int(t) for t in harmonic) + 1) if harmonic else 0
+    for t, (K, r0) in harmonic.items():
+        if not 0 <= int(t) < 8:
+            raise ValueError("bond types are 0 .. 7")
+        prm.bond[int(t)].K, prm.bond[int(t)].r0 = float(K), float(r0)
+    for (a, b), (epsilon, sigma, r_cut) in lj.items():
+        if not (0 <= int(a) < 8 and 0 <= int(b) < 8):
+            raise ValueError("particle types are 0 .. 7")
+        pair = molecular_pair_make(epsilon, sigma, r_cut, shift)
+        prm.pair[int(a)][int(b)] = pair
+        prm.pair[int(b)][int(a)] = pair
+    return prm
+
+
+def molecular_params_check(params: MolecularParams) -> int:
+    return int(load().cavmd_molecular_params_check(ctypes.byref(params)))
+
+
+def molecular_item_check(params: MolecularParams, item: MolecularItem) -> int:
+    """Status cavmd_molecular_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_molecular_item_check(ctypes.byref(params), ctypes.byref(item)))
+
+
+class Molecular(_ItemTableHandle):
+    """Owns one cavmd_molecular: the harmonic bonds and Lennard-Jones pairs of B independent small systems in ONE kernel
+    launch, ceil(N / ROWS) workgroups per system, all pairs out of LDS.  Workgroups start by N descending."""
+    _ITEM, _PREFIX = MolecularItem, "cavmd_molecular"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, params: MolecularParams, items):
+        self.params = params
+        self._ws = workspace
+        self._lib = workspace._lib
+        items = list(items)
+        self.n_items = len(items)
+        self.sizes = [self._size(it) for it in items]
+        self._h = ctypes.c_void_p()
+        check(self._lib.cavmd_molecular_create(workspace.handle, ctypes.byref(params), self.n_items, self._array(items),
+                                               ctypes.byref(self._h)), "cavmd_molecular_create")
+
+    def compute(self, stream: int = 0) -> None:
+        """One kernel: every entry of every item's force array."""
+        check(self._lib.cavmd_molecular_compute(self._h, ctypes.c_void_p(stream)), "cavmd_molecular_compute")

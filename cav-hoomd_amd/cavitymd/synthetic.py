@@ -149,3 +149,44 @@ def perturb(cfg: dict, step_seed: int, amplitude: float = 1e-3) -> dict:
     out = dict(cfg)
     out["position"], out["image"] = position, image
     return out
+
+
+# ---- molecular forces: the bond list of the diatomics, and a start without Lennard-Jones overlaps ---------------------------
+def diatomic_bonds(cfg: dict):
+    """(bonds, bond_typeid) of a ``diatomic_box`` / ``diatomic_lattice`` config: atoms 2m and 2m + 1 form molecule m; bond
+    type 0 = 'O-O', 1 = 'N-N' (the molecule's particle type), as the reference's snapshot names them."""
+    typeid = np.asarray(cfg["typeid"])
+    n_mol = int(np.count_nonzero(typeid != cfg["L_typeid"])) // 2
+    first = 2 * np.arange(n_mol, dtype=np.int32)
+    return np.stack([first, first + 1], axis=1), typeid[first].astype(np.int32)
+
+
+def diatomic_lattice(n_side: int, spacing: float, seed: int, params: dict | None = None, name: str = "diatomic_lattice") -> dict:
+    """n_side^3 diatomics (O-O and N-N alternating) with their centres on a cubic lattice of ``spacing`` in a box of
+    n_side * spacing, at their bond lengths, randomly oriented, plus the photon: atoms of different molecules are at least
+    ``spacing`` minus one bond length apart, so a spacing of 8 bohr or more starts without Lennard-Jones overlaps
+    (sigma <= 6.23 bohr).  N = 2 n_side^3 + 1; all images are 0."""
+    rng = np.random.default_rng(seed)
+    params = params or default_params()
+    kT = PhysicalConstants.KB_HARTREE_PER_K * DEFAULT_TEMPERATURE
+    n_mol = n_side**3
+    L = n_side * float(spacing)
+    box = np.array([L] * 3)
+    grid = np.stack(np.meshgrid(*[np.arange(n_side)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    centre = (grid + 0.5) * spacing - L / 2
+    direction = rng.normal(size=(n_mol, 3))
+    direction /= np.linalg.norm(direction, axis=1, keepdims=True)
+    species = (grid.sum(axis=1) % 2).astype(np.int32)  # 0 = O-O, 1 = N-N, a checkerboard
+    bond = np.where(species == 0, BOND_OO, BOND_NN)[:, None]
+    r = np.empty((2 * n_mol, 3))
+    r[0::2] = centre + 0.5 * bond * direction
+    r[1::2] = centre - 0.5 * bond * direction
+    delta = rng.uniform(0.1, 0.5, size=n_mol)
+    charge = np.empty(2 * n_mol)
+    charge[0::2] = delta
+    charge[1::2] = -delta
+    typeid = np.repeat(species, 2).astype(np.int32)
+    position, image = wrap(r, box)
+    position, typeid, charge, image = _append_photon(rng, position, typeid, charge, image, box, params, False, kT)
+    return {"name": name, "seed": seed, "position": position, "typeid": typeid, "charge": charge, "image": image,
+            "types": list(TYPES), "box": tuple(box), "L_typeid": L_TYPEID, "params": params, "finite_q": False}

@@ -155,6 +155,7 @@ struct cavmd_workspace
     unsigned recorders = 0;             // live cavmd_recorder objects created from this workspace (the same)
     unsigned field_recorders = 0;       // live cavmd_field_recorder objects created from this workspace (the same)
     unsigned verlets = 0;               // live cavmd_verlet objects created from this workspace (the same)
+    unsigned moleculars = 0;            // live cavmd_molecular objects created from this workspace (the same)
 };
 
 namespace
@@ -590,6 +591,8 @@ int cavmd_destroy(cavmd_workspace* ws)
     if (ws->field_recorders != 0) // nor a field recorder
         return CAVMD_ERR_INVALID_VALUE;
     if (ws->verlets != 0)         // nor an integrator
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->moleculars != 0)      // nor a molecular force batch
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -2692,6 +2695,364 @@ int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** ou
     if (!v || !out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = reinterpret_cast<const cavmd_verlet_state*>(v->d_state.ptr);
+    return CAVMD_OK;
+}
+
+} // extern "C"
+
+// ---- harmonic bonds and Lennard-Jones pairs of a batch of independent small systems in ONE launch (cavmd_molecular_batch_kernel.hpp) --
+namespace
+{
+constexpr int kMolecularJSplit = CAVMD_MOLECULAR_J_SPLIT;
+constexpr unsigned kMolecularRows = kMolecularBlock / kMolecularJSplit;
+static_assert(kMolecularJSplit == 1 || kMolecularJSplit == 4 || kMolecularJSplit == 16, "S is one of the measured candidates");
+static_assert(sizeof(cavmd_molecular_pair) == sizeof(MolecularPair) && sizeof(cavmd_molecular_params) == sizeof(MolecularParams)
+                  && offsetof(cavmd_molecular_pair, lj1) == 0 && offsetof(cavmd_molecular_pair, lj2) == 8
+                  && offsetof(cavmd_molecular_pair, lj1_12) == 16 && offsetof(cavmd_molecular_pair, lj2_6) == 24
+                  && offsetof(cavmd_molecular_pair, rcutsq) == 32 && offsetof(cavmd_molecular_pair, eshift) == 40
+                  && offsetof(cavmd_molecular_params, n_types) == offsetof(MolecularParams, n_types)
+                  && offsetof(cavmd_molecular_params, n_bond_types) == offsetof(MolecularParams, n_bond_types)
+                  && offsetof(cavmd_molecular_params, pair) == offsetof(MolecularParams, pair)
+                  && offsetof(cavmd_molecular_params, bond) == offsetof(MolecularParams, bond),
+              "the molecular parameters are uploaded as they are");
+static_assert(sizeof(cavmd_molecular_item) == 64 && sizeof(cavmd_molecular_bond) == 12, "molecular item layout");
+static_assert(CAVMD_MOLECULAR_MAX_TYPES == kMolecularMaxTypes && CAVMD_MOLECULAR_MAX_BONDS == kMolecularMaxBonds
+                  && CAVMD_MOLECULAR_MAX_BOND_TYPES == 8,
+              "the header's limits are the kernel's");
+static_assert(molecular_lds_bytes(CAVMD_MOLECULAR_MAX_ITEM_N) <= 64 * 1024, "the largest system fits the LDS a kernel gets without opt-in");
+static_assert(CAVMD_MOLECULAR_MAX_ITEM_N <= 0xFFFF, "a partner index takes the low 16 bits of a slot");
+
+bool finite_nonnegative(double x)
+{
+    return isfinite(x) && x >= 0.0;
+}
+
+// The status of one item; `prm` NULL: only what can be said without the parameters (bond types and the cut-offs are not
+// looked at).  `slots`, if given, receives the item's partner table: four slots a particle, partner | bond type << 16, filled
+// from slot 0 in the order of the bond list.
+int molecular_item_status(const cavmd_molecular_params* prm, const cavmd_molecular_item* it, std::vector<uint32_t>* slots)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_force & 15) || ((uintptr_t)it->h_bonds & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N != 0 && (!it->d_pos || !it->d_force))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->n_bonds != 0 && !it->h_bonds)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_MOLECULAR_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    if (it->N != 0)
+    {
+        const double L[3] = {it->Lx, it->Ly, it->Lz};
+        for (double l : L)
+            if (!(isfinite(l) && l > 0.0))
+                return CAVMD_ERR_INVALID_VALUE;
+        if (prm)
+        {
+            const double h = std::min(L[0], std::min(L[1], L[2])) * 0.5;
+            for (unsigned a = 0; a < prm->n_types; ++a)
+                for (unsigned b = 0; b < prm->n_types; ++b)
+                    if (prm->pair[a][b].rcutsq > h * h)
+                        return CAVMD_ERR_INVALID_VALUE;
+        }
+    }
+    std::vector<uint8_t> count(it->N, 0);
+    if (slots)
+        slots->assign((size_t)it->N * kMolecularMaxBonds, kMolecularNoPartner);
+    for (uint32_t k = 0; k < it->n_bonds; ++k)
+    {
+        const cavmd_molecular_bond& bd = it->h_bonds[k];
+        if (bd.a >= it->N || bd.b >= it->N || bd.a == bd.b)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (prm ? bd.type >= prm->n_bond_types : bd.type >= CAVMD_MOLECULAR_MAX_BOND_TYPES)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (count[bd.a] >= kMolecularMaxBonds || count[bd.b] >= kMolecularMaxBonds)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (slots)
+        {
+            (*slots)[(size_t)bd.a * kMolecularMaxBonds + count[bd.a]] = bd.b | (bd.type << 16);
+            (*slots)[(size_t)bd.b * kMolecularMaxBonds + count[bd.b]] = bd.a | (bd.type << 16);
+        }
+        count[bd.a] += 1;
+        count[bd.b] += 1;
+    }
+    return CAVMD_OK;
+}
+
+MolecularRow molecular_row(const cavmd_molecular_item& it)
+{
+    MolecularRow r;
+    memset(&r, 0, sizeof(r));
+    r.pos2 = reinterpret_cast<const v2d*>(it.d_pos);
+    r.force2 = reinterpret_cast<v2d*>(it.d_force);
+    r.Lx = it.Lx;
+    r.Ly = it.Ly;
+    r.Lz = it.Lz;
+    r.n = it.N;
+    return r;
+}
+} // namespace
+
+struct cavmd_molecular : ItemTable<cavmd_molecular_item, MolecularRow> // workgroups by N descending
+{
+    cavmd_workspace* ws = nullptr;
+    cavmd_molecular_params params;
+    DeviceArray<MolecularParams> d_params;
+    DeviceArray<MolecularHeader> d_header;    // never reallocated: captured launches find the tables below through it
+    DeviceArray<uint4> d_blocks, d_partners;  // replaced together by set_items
+    std::vector<std::vector<uint32_t>> slots; // per item: its partner table (the bond lists are not kept)
+    unsigned n_blocks = 0;
+    unsigned lds_n = 2; // particles the next launch has LDS for: the largest N, rounded up to even
+
+    cavmd_molecular()
+        : ItemTable([](const cavmd_molecular_item* it) { return molecular_item_status(nullptr, it, nullptr); },
+                    [](const cavmd_molecular_item& it) { return it.N; }, molecular_row)
+    {
+    }
+
+    // the host's tables for `sizes` and `launch` (items by N descending), into fresh device arrays; committed by publish()
+    hipError_t build(const std::vector<unsigned>& sizes, const std::vector<unsigned>& launch,
+                     const std::vector<std::vector<uint32_t>>& all_slots, DeviceArray<uint4>* blocks, DeviceArray<uint4>* partners,
+                     MolecularHeader* header, unsigned* new_lds_n) const
+    {
+        std::vector<uint32_t> base(sizes.size());
+        std::vector<uint32_t> pool;
+        unsigned largest = 0;
+        for (size_t i = 0; i < sizes.size(); ++i)
+        {
+            base[i] = (uint32_t)(pool.size() / kMolecularMaxBonds);
+            pool.insert(pool.end(), all_slots[i].begin(), all_slots[i].end());
+            largest = std::max(largest, sizes[i]);
+        }
+        std::vector<uint4> table;
+        for (unsigned item : launch)
+            for (unsigned f = 0; f < sizes[item]; f += kMolecularRows)
+                table.push_back(make_uint4(item, f, base[item], 0u));
+        hipError_t e = blocks->alloc(std::max<size_t>(table.size(), 1));
+        if (e == hipSuccess && !table.empty())
+            e = hipMemcpy(blocks->ptr, table.data(), sizeof(uint4) * table.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = partners->alloc(std::max<size_t>(pool.size() / kMolecularMaxBonds, 1));
+        if (e == hipSuccess && !pool.empty())
+            e = hipMemcpy(partners->ptr, pool.data(), sizeof(uint32_t) * pool.size(), hipMemcpyHostToDevice);
+        memset(header, 0, sizeof(*header));
+        header->blocks = blocks->ptr;
+        header->partners = partners->ptr;
+        header->n_blocks = (unsigned)table.size();
+        *new_lds_n = std::max(2u, (largest + 1u) & ~1u);
+        return e;
+    }
+
+    hipError_t publish(DeviceArray<uint4>&& blocks, DeviceArray<uint4>&& partners, const MolecularHeader& header, unsigned new_lds_n)
+    {
+        const hipError_t e = hipMemcpy(d_header.ptr, &header, sizeof(header), hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return e;
+        d_blocks = std::move(blocks); // the old tables are freed here: nothing in flight reads them (the caller has waited)
+        d_partners = std::move(partners);
+        n_blocks = header.n_blocks;
+        lds_n = new_lds_n;
+        return hipSuccess;
+    }
+};
+
+extern "C"
+{
+
+int cavmd_molecular_pair_make(double epsilon, double sigma, double r_cut, int shift, cavmd_molecular_pair* out)
+{
+    if (!out || !finite_nonnegative(epsilon) || !finite_nonnegative(sigma) || !finite_nonnegative(r_cut))
+        return CAVMD_ERR_INVALID_VALUE;
+    cavmd_molecular_pair p;
+    memset(&p, 0, sizeof(p));
+    const double s2 = sigma * sigma;
+    const double s6 = (s2 * s2) * s2;
+    p.lj2 = (4.0 * epsilon) * s6;
+    p.lj1 = p.lj2 * s6;
+    p.lj1_12 = 12.0 * p.lj1;
+    p.lj2_6 = 6.0 * p.lj2;
+    p.rcutsq = r_cut * r_cut;
+    p.eshift = 0.0;
+    if (shift && p.rcutsq > 0.0)
+    {
+        const double r2inv = 1.0 / p.rcutsq;
+        const double r6inv = (r2inv * r2inv) * r2inv;
+        p.eshift = r6inv * ((p.lj1 * r6inv) - p.lj2);
+    }
+    if (!isfinite(p.lj1_12) || !isfinite(p.lj2_6) || !isfinite(p.rcutsq) || !isfinite(p.eshift))
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = p;
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_params_check(const cavmd_molecular_params* prm)
+{
+    if (!prm || prm->n_types > CAVMD_MOLECULAR_MAX_TYPES || prm->n_bond_types > CAVMD_MOLECULAR_MAX_BOND_TYPES || prm->reserved != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (unsigned a = 0; a < prm->n_types; ++a)
+        for (unsigned b = 0; b < prm->n_types; ++b)
+        {
+            const cavmd_molecular_pair& p = prm->pair[a][b];
+            if (!finite_nonnegative(p.lj1) || !finite_nonnegative(p.lj2) || !finite_nonnegative(p.lj1_12) || !finite_nonnegative(p.lj2_6)
+                || !finite_nonnegative(p.rcutsq) || !isfinite(p.eshift) || p.reserved[0] != 0 || p.reserved[1] != 0)
+                return CAVMD_ERR_INVALID_VALUE;
+            if (memcmp(&p, &prm->pair[b][a], sizeof(p)) != 0)
+                return CAVMD_ERR_INVALID_VALUE;
+        }
+    for (unsigned k = 0; k < prm->n_bond_types; ++k)
+        if (!finite_nonnegative(prm->bond[k].K) || !finite_nonnegative(prm->bond[k].r0))
+            return CAVMD_ERR_INVALID_VALUE;
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_item_check(const cavmd_molecular_params* prm, const cavmd_molecular_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    const int st = cavmd_molecular_params_check(prm);
+    if (st != CAVMD_OK)
+        return st;
+    return molecular_item_status(prm, it, nullptr);
+}
+
+int cavmd_molecular_order(int* rows, int* j_split)
+{
+    if (rows)
+        *rows = (int)kMolecularRows;
+    if (j_split)
+        *j_split = kMolecularJSplit;
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_params* prm, size_t n_items, const cavmd_molecular_item* h_items,
+                           cavmd_molecular** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !prm || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+        return CAVMD_ERR_INVALID_VALUE;
+    int st = cavmd_molecular_params_check(prm);
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<std::vector<uint32_t>> slots(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        st = molecular_item_status(prm, h_items + i, &slots[i]);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    cavmd_molecular* m = new (std::nothrow) cavmd_molecular();
+    if (!m)
+        return (int)hipErrorOutOfMemory;
+    m->params = *prm;
+    m->adopt(ws->device, h_items, n_items);
+    std::vector<unsigned> sizes(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        m->items[i].h_bonds = nullptr; // the caller's lists are not kept
+        m->items[i].n_bonds = 0;
+        sizes[i] = m->items[i].N;
+    }
+    m->slots.swap(slots);
+
+    DeviceGuard guard(m->device);
+    DeviceArray<uint4> blocks, partners;
+    MolecularHeader header;
+    unsigned lds_n = 2;
+    hipError_t e = m->upload();
+    if (e == hipSuccess)
+        e = m->d_params.alloc(1);
+    if (e == hipSuccess)
+        e = hipMemcpy(m->d_params.ptr, prm, sizeof(*prm), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = m->d_header.alloc_zeroed(1);
+    if (e == hipSuccess)
+        e = m->build(sizes, m->order, m->slots, &blocks, &partners, &header, &lds_n);
+    if (e == hipSuccess)
+        e = m->publish(std::move(blocks), std::move(partners), header, lds_n);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess)
+    {
+        cavmd_molecular_destroy(m);
+        return (int)e;
+    }
+    m->ws = ws;
+    ws->moleculars += 1;
+    *out = m;
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_destroy(cavmd_molecular* m)
+{
+    if (!m)
+        return CAVMD_OK;
+    DeviceGuard guard(m->device);
+    m->quiesce_and_free();
+    if (m->ws)
+        m->ws->moleculars -= 1;
+    delete m;
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_set_items(cavmd_molecular* m, size_t first, size_t count, const cavmd_molecular_item* h_items)
+{
+    if (!m || !h_items || count == 0 || first >= m->n || count > m->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    std::vector<std::vector<uint32_t>> new_slots(m->slots);
+    std::vector<cavmd_molecular_item> rows(h_items, h_items + count);
+    std::vector<unsigned> sizes(m->n);
+    for (size_t i = 0; i < m->n; ++i)
+        sizes[i] = m->items[i].N;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = molecular_item_status(&m->params, h_items + i, &new_slots[first + i]);
+        if (st != CAVMD_OK)
+            return st;
+        rows[i].h_bonds = nullptr; // the caller's lists are not kept
+        rows[i].n_bonds = 0;
+        sizes[first + i] = rows[i].N;
+    }
+    DeviceGuard guard(m->device);
+    if (m->enqueued)
+    {
+        if (stream_capturing(m->last_stream))
+            return CAVMD_ERR_INVALID_VALUE; // nothing below may run during a capture
+        CAVMD_HIP_TRY(hipStreamSynchronize(m->last_stream));
+    }
+    // the new tables go to fresh device arrays first, then the rows, then the 32-byte header that points to the tables
+    std::vector<cavmd_molecular_item> all(m->items);
+    std::copy(rows.begin(), rows.end(), all.begin() + first);
+    const std::vector<unsigned> launch = launch_order(all, m->key);
+    DeviceArray<uint4> blocks, partners;
+    MolecularHeader header;
+    unsigned lds_n = 2;
+    CAVMD_HIP_TRY(m->build(sizes, launch, new_slots, &blocks, &partners, &header, &lds_n));
+    const int st = m->set_items(first, count, rows.data());
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(m->publish(std::move(blocks), std::move(partners), header, lds_n));
+    m->slots.swap(new_slots);
+    return CAVMD_OK;
+}
+
+int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
+{
+    if (!m)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(m->device);
+    hipLaunchKernelGGL((molecular_force_kernel<kMolecularBlock, kMolecularJSplit>), dim3(std::max(m->n_blocks, 1u)),
+                       dim3(kMolecularBlock), molecular_lds_bytes(m->lds_n), stream, m->d_rows, m->d_header.ptr, m->d_params.ptr,
+                       m->lds_n);
+    const int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    m->enqueued_on(stream);
     return CAVMD_OK;
 }
 

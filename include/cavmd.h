@@ -774,6 +774,113 @@ CAVMD_API int cavmd_verlet_reset(cavmd_verlet* v, void* stream);
 /* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out);
 
+/* ---- harmonic bonds and Lennard-Jones pairs of a batch in ONE launch: the molecular forces of the captured step ------------ */
+/* The reference's driver builds every run from the cavity force plus hoomd.md.bond.Harmonic and hoomd.md.pair.LJ(mode='shift')
+ * with the neighbour list excluding bonded pairs (examples/05_advanced_run.py:556-596).  This section is those two forces for B
+ * registered systems of at most CAVMD_MOLECULAR_MAX_ITEM_N particles each, in ONE kernel: a system of N particles gets
+ * ceil(N / ROWS) workgroups, each stages x, y, z and the type id of its WHOLE system into LDS (28 B a particle: 56 KiB at the
+ * cap, inside the 64 KiB a kernel gets without opt-in; larger systems need a cell list, which is not built here) and each of
+ * its ROWS particles walks all j.  No neighbour list, no Newton's-third-law halving, no atomics, no workgroup waits for
+ * another one (hence no CAVMD_ERR_SYNC_TIMEOUT), every loop is bounded by N, and EVERY entry of an item's force array is
+ * written (zeros for the photon and for particles that interact with nothing: no memset pass).  The result is a further force
+ * array of cavmd_verlet_item.d_force.  Electrostatics (PPPM, a real-space Ewald term) are out of scope.
+ *
+ * The arithmetic restates EvaluatorPairLJ, EvaluatorBondHarmonic and BoxDim::minImage of HOOMD-blue 4.x from knowledge
+ * [HOOMD upstream, not in checkout]: parity with HOOMD-blue itself is NOT pinned by anything in this repository; the
+ * expressions below ARE the contract.  Every operation is one IEEE fp64 rounding, no FMA; division and sqrt are correctly
+ * rounded.  For particle i with stored (wrapped) coordinates x_i and type id t_i (the low 32 bits of pos.w):
+ *   minimum image, per axis c:   d_c = x_i,c - x_j,c;  h = L_c * 0.5;  if (d_c >= h) d_c -= L_c; else if (d_c < -h) d_c += L_c
+ *                                rsq = (d_x * d_x + d_y * d_y) + d_z * d_z
+ *   bonds of i, B starting from (0, 0, 0, 0), in the order of i's partner table (the bonds that name i, in list order):
+ *                                r = sqrt(rsq);  fdivr = K * (r0 / r - 1);  e = (0.5 * K) * ((r0 - r) * (r0 - r))
+ *                                B_c = B_c + d_c * fdivr;  B_w = B_w + 0.5 * e
+ *   pair (i, j) contributes only if j != i, j is not a bond partner of i, t_i < n_types and t_j < n_types (an out-of-range id
+ *   never indexes the table) and rsq < rcutsq[t_i][t_j] (strict: rcutsq == 0 switches a type pair off); then
+ *                                r2inv = 1 / rsq;  r6inv = (r2inv * r2inv) * r2inv
+ *                                fdivr = (r2inv * r6inv) * ((lj1_12 * r6inv) - lj2_6)
+ *                                e = r6inv * ((lj1 * r6inv) - lj2) - eshift
+ *                                p_c = p_c + d_c * fdivr;  p_w = p_w + 0.5 * e          (a skipped pair adds nothing)
+ *   summation order of the pair part, S = CAVMD_MOLECULAR_J_SPLIT: partial s (0 <= s < S) starts from 0 and is the left-to-
+ *   right sum over j = s, s + S, s + 2 S, ...;  P = ((p_0 + p_1) + p_2) + ... + p_(S-1)
+ *   F_i = B_i + P_i, component-wise, .w (the particle's share of the potential energy) included.
+ * The pair constants come from cavmd_molecular_pair_make, so that the kernel and a mirror of it start from the same bits:
+ *   s2 = sigma * sigma;  s6 = (s2 * s2) * s2;  lj2 = (4 * epsilon) * s6;  lj1 = lj2 * s6;  lj1_12 = 12 * lj1;  lj2_6 = 6 * lj2
+ *   rcutsq = r_cut * r_cut;  eshift = 0 without shift or with r_cut == 0, else the pair energy r6inv * ((lj1 * r6inv) - lj2)
+ *   at rsq = rcutsq, in the operations above. */
+#define CAVMD_MOLECULAR_MAX_ITEM_N 2048 /* 28 B x 2048 = 56 KiB of LDS */
+#define CAVMD_MOLECULAR_MAX_TYPES 8
+#define CAVMD_MOLECULAR_MAX_BOND_TYPES 8
+#define CAVMD_MOLECULAR_MAX_BONDS 4     /* bonds on one particle */
+#ifndef CAVMD_MOLECULAR_J_SPLIT         /* S, one of 1, 4, 16: a compile-time constant of the library, never a run-time tunable, */
+#define CAVMD_MOLECULAR_J_SPLIT 16      /* to be settled by profiles/molecular_batch/README.md; ROWS = 256 / S (cavmd_molecular_order) */
+#endif
+typedef struct cavmd_molecular_pair      /* 64 B; made by cavmd_molecular_pair_make */
+{
+    double lj1, lj2, lj1_12, lj2_6, rcutsq, eshift;
+    uint64_t reserved[2];                /* must be 0 */
+} cavmd_molecular_pair;
+typedef struct cavmd_molecular_bond_params /* 16 B */
+{
+    double K, r0;
+} cavmd_molecular_bond_params;
+typedef struct cavmd_molecular_params    /* 4240 B */
+{
+    uint32_t n_types;                    /* <= 8; type ids at or above it interact with nothing */
+    uint32_t n_bond_types;               /* <= 8 */
+    uint64_t reserved;                   /* must be 0 */
+    cavmd_molecular_pair pair[8][8];     /* symmetric: pair[a][b] and pair[b][a] hold the same bits, for a, b < n_types */
+    cavmd_molecular_bond_params bond[8];
+} cavmd_molecular_params;
+typedef struct cavmd_molecular_bond      /* 12 B */
+{
+    uint32_t a, b, type;
+} cavmd_molecular_bond;
+typedef struct cavmd_molecular_item      /* 64 B */
+{
+    const cavmd_double4* d_pos;          /* DEVICE: HOOMD Scalar4 positions (wrapped), type id in .w; 16-byte aligned */
+    cavmd_double4* d_force;              /* DEVICE: N entries, all written by every launch; 16-byte aligned */
+    const cavmd_molecular_bond* h_bonds; /* HOST: n_bonds triples, read during create / set_items only; 4-byte aligned */
+    double Lx, Ly, Lz;
+    uint32_t N;                          /* 0 is legal: the item gets no workgroup; <= CAVMD_MOLECULAR_MAX_ITEM_N */
+    uint32_t n_bonds;
+    uint64_t reserved;                   /* must be 0 */
+} cavmd_molecular_item;
+typedef struct cavmd_molecular cavmd_molecular; /* opaque; belongs to the workspace it was created from */
+
+/* The four functions below are host arithmetic and need no device. */
+/* Fills one entry of the pair table as spelled out above.  CAVMD_ERR_INVALID_VALUE for a null `out` or a non-finite or
+ * negative epsilon, sigma or r_cut (or a product of them that overflows). */
+CAVMD_API int cavmd_molecular_pair_make(double epsilon, double sigma, double r_cut, int shift, cavmd_molecular_pair* out);
+/* CAVMD_ERR_INVALID_VALUE for null, n_types or n_bond_types above 8, reserved words != 0, and among the entries in use: a
+ * constant that is not finite or is negative (eshift may be negative), an asymmetric pair table. */
+CAVMD_API int cavmd_molecular_params_check(const cavmd_molecular_params* params);
+/* One item against the parameters it will be used with.  CAVMD_ERR_CAPACITY for N above CAVMD_MOLECULAR_MAX_ITEM_N;
+ * CAVMD_ERR_INVALID_VALUE for null arguments, parameters cavmd_molecular_params_check refuses, reserved != 0, a null (with
+ * N > 0) or misaligned d_pos / d_force, a null (with n_bonds > 0) or misaligned h_bonds, box lengths that are not finite and
+ * positive (with N > 0), any rcutsq in use above (min(L) * 0.5)^2 (the minimum image is then not the only one), a bond index
+ * not below N, a bond with a == b, a bond type not below n_bond_types, more than CAVMD_MOLECULAR_MAX_BONDS bonds on a particle. */
+CAVMD_API int cavmd_molecular_item_check(const cavmd_molecular_params* params, const cavmd_molecular_item* item);
+/* ROWS (particles a workgroup owns) and S (partial sums per particle) the library was compiled with; either may be NULL. */
+CAVMD_API int cavmd_molecular_order(int* rows, int* j_split);
+/* Validates parameters and the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), builds the workgroup -> (item, first
+ * particle) table (items by N descending, ties in item order; none for N == 0) and every particle's partner table from the
+ * bond lists, and copies them to the device of `ws` (set-up time).  The library, not the caller, builds the partner tables: a
+ * bad index is refused here and never becomes an out-of-bounds read.  The bond lists are not referenced after the call.
+ * cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while a molecular batch of the workspace is alive. */
+CAVMD_API int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_params* params, size_t n_items,
+                                     const cavmd_molecular_item* h_items, cavmd_molecular** out);
+/* Synchronises the stream of the last launch (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_molecular_destroy(cavmd_molecular* m);
+/* Replaces rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
+ * changed if a row is refused.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the
+ * batch.  A launch captured BEFORE the call keeps its number of workgroups and its LDS size: on replay it evaluates the new
+ * table as far as its workgroups reach and fills the forces of a system larger than its LDS with NaN; capture again after a
+ * call that changes the sizes. */
+CAVMD_API int cavmd_molecular_set_items(cavmd_molecular* m, size_t first, size_t count, const cavmd_molecular_item* h_items);
+/* Enqueues exactly ONE kernel on `stream`: no allocation, no copy, no host wait; may be captured into a hipGraph.  One batch
+ * serves one host thread and one stream at a time. */
+CAVMD_API int cavmd_molecular_compute(cavmd_molecular* m, void* stream);
+
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
 CAVMD_API int cavmd_profile_enable(cavmd_workspace* ws, int on);
