@@ -166,6 +166,18 @@ class MolecularItem(ctypes.Structure):
                 ("reserved", ctypes.c_uint64)]
 
 
+class CoulombItem(ctypes.Structure):
+    """cavmd_coulomb_item (96 bytes): d_pos / d_charge / d_force are DEVICE pointers, h_exclusions a HOST pointer (bond-list
+    format, type ignored) read during create / set_items only."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_charge", ctypes.c_void_p), ("d_force", ctypes.c_void_p),
+                ("h_exclusions", ctypes.c_void_p), ("Lx", ctypes.c_double), ("Ly", ctypes.c_double), ("Lz", ctypes.c_double),
+                ("kappa", ctypes.c_double), ("r_cut", ctypes.c_double), ("k_cut", ctypes.c_double), ("N", ctypes.c_uint32),
+                ("n_exclusions", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
+COULOMB_MAX_ITEM_N = 2048
+COULOMB_MAX_K = 4096
+COULOMB_MAX_EXCLUSIONS = 4
 MOLECULAR_MAX_ITEM_N = 2048
 MOLECULAR_MAX_BONDS = 4
 FIELD_MAX_WAVEVECTORS = 256
@@ -242,8 +254,31 @@ def molecular_item(N, pos_ptr, force_ptr, box_L, bonds=None) -> "MolecularItem":
     return it
 
 
+def coulomb_item(N, pos_ptr, charge_ptr, force_ptr, box_L, kappa, r_cut, k_cut, exclusions=None) -> "CoulombItem":
+    """exclusions: None or an (n, 2) or (n, 3) array of pairs (a third column is ignored); the item keeps the array alive
+    (``_exclusions``) for the call that reads it."""
+    import numpy as np
+    it = CoulombItem()
+    it.d_pos, it.d_charge, it.d_force = pos_ptr or None, charge_ptr or None, force_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.kappa, it.r_cut, it.k_cut = float(kappa), float(r_cut), float(k_cut)
+    it.N = int(N)
+    e = np.zeros((0, 3), dtype=np.uint32)
+    if exclusions is not None and len(exclusions):
+        pairs = np.asarray(exclusions, dtype=np.uint32)
+        pairs = pairs.reshape(-1, pairs.shape[-1] if pairs.ndim == 2 else 2)
+        e = np.zeros((len(pairs), 3), dtype=np.uint32)
+        e[:, :2] = pairs[:, :2]
+    it._exclusions = e
+    it.h_exclusions, it.n_exclusions = (e.ctypes.data if len(e) else None), len(e)
+    return it
+
+
 # every symbol include/cavmd.h exports; tests check the header and the library against this list
 EXPORTED_SYMBOLS = (
+    "cavmd_coulomb_item_check", "cavmd_coulomb_k_count", "cavmd_coulomb_parameters", "cavmd_coulomb_order",
+    "cavmd_coulomb_create", "cavmd_coulomb_destroy", "cavmd_coulomb_set_items", "cavmd_coulomb_compute",
+    "cavmd_coulomb_structure_device_ptr",
     "cavmd_molecular_pair_make", "cavmd_molecular_params_check", "cavmd_molecular_item_check", "cavmd_molecular_order",
     "cavmd_molecular_create", "cavmd_molecular_destroy", "cavmd_molecular_set_items", "cavmd_molecular_compute",
     "cavmd_verlet_item_check", "cavmd_verlet_input_make", "cavmd_verlet_create", "cavmd_verlet_destroy",
@@ -487,6 +522,24 @@ def _declare(lib):
         lib.cavmd_molecular_set_items.restype = ci
         lib.cavmd_molecular_compute.argtypes = [vp, vp]
         lib.cavmd_molecular_compute.restype = ci
+        lib.cavmd_coulomb_item_check.argtypes = [P(CoulombItem)]
+        lib.cavmd_coulomb_item_check.restype = ci
+        lib.cavmd_coulomb_k_count.argtypes = [P(CoulombItem), P(ctypes.c_uint32)]
+        lib.cavmd_coulomb_k_count.restype = ci
+        lib.cavmd_coulomb_parameters.argtypes = [dbl, dbl, P(dbl), P(dbl)]
+        lib.cavmd_coulomb_parameters.restype = ci
+        lib.cavmd_coulomb_order.argtypes = [P(ci)] * 4
+        lib.cavmd_coulomb_order.restype = ci
+        lib.cavmd_coulomb_create.argtypes = [vp, sz, P(CoulombItem), P(vp)]
+        lib.cavmd_coulomb_create.restype = ci
+        lib.cavmd_coulomb_destroy.argtypes = [vp]
+        lib.cavmd_coulomb_destroy.restype = ci
+        lib.cavmd_coulomb_set_items.argtypes = [vp, sz, sz, P(CoulombItem)]
+        lib.cavmd_coulomb_set_items.restype = ci
+        lib.cavmd_coulomb_compute.argtypes = [vp, vp]
+        lib.cavmd_coulomb_compute.restype = ci
+        lib.cavmd_coulomb_structure_device_ptr.argtypes = [vp, P(vp), P(P(ctypes.c_uint32))]
+        lib.cavmd_coulomb_structure_device_ptr.restype = ci
         lib.cavmd_profile_enable.argtypes = [vp, ci]
         lib.cavmd_profile_enable.restype = ci
         lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
@@ -1173,3 +1226,53 @@ class Molecular(_ItemTableHandle):
     def compute(self, stream: int = 0) -> None:
         """One kernel: every entry of every item's force array."""
         check(self._lib.cavmd_molecular_compute(self._h, ctypes.c_void_p(stream)), "cavmd_molecular_compute")
+
+
+def coulomb_order(lib=None):
+    """(ROWS, S, KROWS, T): the particles a workgroup of the Coulomb force kernel owns and the lanes that share one, the
+    k-vectors a workgroup of the structure-factor kernel owns and the lanes that share one, as the library was compiled."""
+    v = [ctypes.c_int() for _ in range(4)]
+    check((lib or load()).cavmd_coulomb_order(*[ctypes.byref(x) for x in v]), "cavmd_coulomb_order")
+    return tuple(int(x.value) for x in v)
+
+
+def coulomb_parameters(r_cut, accuracy):
+    """(kappa, k_cut) = (sqrt(-ln accuracy) / r_cut, 2 kappa sqrt(-ln accuracy)) (host arithmetic)."""
+    kappa, k_cut = ctypes.c_double(), ctypes.c_double()
+    check(load().cavmd_coulomb_parameters(float(r_cut), float(accuracy), ctypes.byref(kappa), ctypes.byref(k_cut)),
+          "cavmd_coulomb_parameters")
+    return float(kappa.value), float(k_cut.value)
+
+
+def coulomb_item_check(item: CoulombItem) -> int:
+    """Status cavmd_coulomb_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_coulomb_item_check(ctypes.byref(item)))
+
+
+def coulomb_k_count(item: CoulombItem) -> int:
+    """K, the kept k-vectors of an item the library accepts; raises CavmdError otherwise."""
+    K = ctypes.c_uint32()
+    check(load().cavmd_coulomb_k_count(ctypes.byref(item), ctypes.byref(K)), "cavmd_coulomb_k_count")
+    return int(K.value)
+
+
+class Coulomb(_ItemTableHandle):
+    """Owns one cavmd_coulomb: the Ewald Coulomb forces of B independent small systems in TWO kernel launches (structure
+    factors, ceil(K / KROWS) workgroups per system; forces, ceil(N / ROWS)).  Workgroups start by N descending."""
+    _ITEM, _PREFIX = CoulombItem, "cavmd_coulomb"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items):
+        self._create(workspace, items)
+
+    def compute(self, stream: int = 0) -> None:
+        """Two kernels: every structure factor, then every entry of every item's force array."""
+        check(self._lib.cavmd_coulomb_compute(self._h, ctypes.c_void_p(stream)), "cavmd_coulomb_compute")
+
+    def structure_device_ptr(self):
+        """(device address of the structure-factor table, per-item offsets in entries of two doubles): item i owns K_i + 1
+        entries, {A, B} per k-vector and then {Q, 0}.  Valid until the next set_items / close."""
+        p, off = ctypes.c_void_p(), ctypes.POINTER(ctypes.c_uint32)()
+        check(self._lib.cavmd_coulomb_structure_device_ptr(self._h, ctypes.byref(p), ctypes.byref(off)),
+              "cavmd_coulomb_structure_device_ptr")
+        return int(p.value), [int(off[i]) for i in range(self.n_items)]

@@ -1,0 +1,134 @@
+"""``CoulombForceBatch`` -- the Ewald Coulomb forces of B independent small systems in TWO kernel launches.
+
+The reference's driver adds the pair of forces returned by ``make_pppm_coulomb_forces`` over the bond-excluding neighbour list
+(examples/05_advanced_run.py:598-608): HOOMD-blue's PPPM, a mesh approximation of the Ewald sum.  For systems of at most 2048
+particles the sum itself is cheaper than a mesh, so this class is the Ewald sum (``cavmd_coulomb_compute``; the expressions are
+spelled out in include/cavmd.h): real space over all pairs out of LDS, reciprocal space as a direct sum over the kept
+k-vectors.  It is the twin of ``MolecularForceBatch``, and its force arrays are further forces of the integrator's items::
+
+    coulomb = CoulombForceBatch(sysdefs, exclusions=bonds, r_cut=12.0, accuracy=1e-6)
+    integrator = VerletBatch(cavity, velocities, extra_forces=[[m, c] for m, c in zip(molecular.forces, coulomb.forces)])
+    with torch.cuda.graph(graph):
+        integrator.step_one(); cavity.compute(); molecular.compute(); coulomb.compute(); integrator.step_two()
+
+Parity with HOOMD-blue's PPPM is not pinned: what separates the two is PPPM's discretisation error.  No CPU fallback: CPU
+tensors raise.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _capi
+from ._device import stream_handle
+
+
+class CoulombForceBatch:
+    """sysdefs: the systems (positions, charges -- ``getCharges()`` -- and boxes are taken from them; all on one GPU);
+    exclusions: per system an (n, 2) integer array of pairs whose Coulomb interaction is removed (the bonds), or None;
+    r_cut: the real-space cut-off, at most half the shortest box length; then either ``accuracy`` (kappa and k_cut follow from
+    ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``."""
+
+    def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None):
+        self._sysdefs = list(sysdefs)
+        if not self._sysdefs:
+            raise ValueError("a batch needs at least one system")
+        pds = [s.getParticleData() for s in self._sysdefs]
+        for pd in pds:
+            for t in (pd.getPositions(), pd.getCharges()):
+                if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+                    raise RuntimeError("CoulombForceBatch needs the position and charge arrays in GPU memory; no CPU fallback "
+                                       "exists in this package")
+        if (accuracy is None) == (kappa is None or k_cut is None) or (accuracy is not None and (kappa is not None or k_cut is not None)):
+            raise ValueError("give either accuracy or both kappa and k_cut")
+        if accuracy is not None:
+            kappa, k_cut = _capi.coulomb_parameters(r_cut, accuracy)
+        self.r_cut, self.kappa, self.k_cut = float(r_cut), float(kappa), float(k_cut)
+        dev = pds[0].device
+        if any(pd.device != dev for pd in pds):
+            raise ValueError("all systems of one batch live on one device")
+        B = len(pds)
+        exclusions = [None] * B if exclusions is None else list(exclusions)
+        if len(exclusions) != B:
+            raise ValueError(f"exclusions: one array per system ({B})")
+        self._device = dev
+        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        sizes = [pd.getN() for pd in pds]
+        self._sizes = sizes
+        # one allocation behind all force arrays: the energy is then one segmented sum
+        self._pool = torch.zeros((max(sum(sizes), 1), 4), dtype=torch.float64, device=dev)
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self._force = [self._pool[int(starts[k]):int(starts[k + 1])] for k in range(B)]
+        self._lengths = torch.tensor(sizes, dtype=torch.int64, device=dev)
+        self._charges = []
+        items = []
+        for k, pd in enumerate(pds):
+            e = np.zeros((0, 2), dtype=np.int64) if exclusions[k] is None else np.asarray(exclusions[k], dtype=np.int64).reshape(-1, 2)
+            if len(e) and (e.min() < 0 or e.max() >= 2**32):
+                raise ValueError(f"system {k}: negative exclusion index")
+            q = pd.getCharges()
+            if q.dtype != torch.float64 or not q.is_contiguous():
+                raise ValueError(f"system {k}: charges are a contiguous float64 tensor")
+            self._charges.append(q)
+            n = sizes[k]
+            items.append(_capi.coulomb_item(n, pd.getPositions().data_ptr() if n else 0, q.data_ptr() if n else 0,
+                                            self._force[k].data_ptr() if n else 0, pd.getGlobalBox().getL(), self.kappa, self.r_cut,
+                                            self.k_cut, e))
+        self.k_counts = []
+        for k, it in enumerate(items):
+            try:
+                self.k_counts.append(_capi.coulomb_k_count(it))
+            except _capi.CavmdError as e:
+                if e.status == _capi.CAVMD_ERR_CAPACITY and sizes[k] <= _capi.COULOMB_MAX_ITEM_N:
+                    raise ValueError(f"system {k}: k_cut = {self.k_cut:.4g} keeps more than {_capi.COULOMB_MAX_K} k-vectors in its box; "
+                                     "ask for a coarser accuracy or a larger r_cut") from e
+                raise
+        self._ws = _capi.Workspace(1, device=self._dev_index)
+        self._coulomb = _capi.Coulomb(self._ws, items)
+        self.n_systems = B
+        torch.cuda.current_stream(dev).synchronize()   # the zeroed pool is there before any stream computes
+
+    def __len__(self) -> int:
+        return self.n_systems
+
+    def _need(self):
+        if self._coulomb is None:
+            raise RuntimeError("CoulombForceBatch used after close()")
+
+    def compute(self, timestep: int = 0, stream=None) -> None:
+        """TWO kernels on ``stream`` (default: torch's current stream): every entry of every system's force array.  May be
+        captured.  ``timestep`` is accepted for signature compatibility with ``CavityForceBatch.compute``; it is not used."""
+        self._need()
+        self._coulomb.compute(stream_handle(stream, self._device))
+
+    @property
+    def forces(self):
+        """Per-system (N_k, 4) float64 device tensors: force in columns 0-2, the particle's share of the Coulomb energy in
+        column 3."""
+        return list(self._force)
+
+    def potential_energy(self) -> torch.Tensor:
+        """(B,) device tensor: the Coulomb energy of every system, the sum of its ``.w`` column, ordered on torch's current
+        stream (the kernels keep no totals across workgroups)."""
+        self._need()
+        w = self._pool[:sum(self._sizes), 3]
+        if len(set(self._sizes)) == 1 and self._sizes[0] > 0:
+            return w.reshape(self.n_systems, self._sizes[0]).sum(dim=1)
+        return torch.segment_reduce(w.contiguous(), "sum", lengths=self._lengths)
+
+    @property
+    def coulomb(self) -> _capi.Coulomb:
+        return self._coulomb
+
+    def close(self) -> None:
+        if getattr(self, "_coulomb", None) is not None:
+            self._coulomb.close()
+        if getattr(self, "_ws", None) is not None:
+            self._ws.close()
+        self._coulomb = self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

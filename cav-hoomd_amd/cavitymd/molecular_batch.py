@@ -13,7 +13,7 @@ neighbour list is needed.  Its force arrays are further forces of the integrator
         integrator.step_one(); cavity.compute(); molecular.compute(); integrator.step_two()
 
 Type pairs that are not listed do not interact (the driver switches every pair with the photon 'L' off).  Electrostatics are
-not part of it.  The expressions restate HOOMD-blue 4.x from knowledge; parity with HOOMD-blue itself is not pinned.  No CPU
+``CoulombForceBatch``'s, a further force array of the same integrator.  The expressions restate HOOMD-blue 4.x from knowledge; parity with HOOMD-blue itself is not pinned.  No CPU
 fallback: CPU tensors raise.
 """
 from __future__ import annotations

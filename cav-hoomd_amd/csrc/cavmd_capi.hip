@@ -156,6 +156,7 @@ struct cavmd_workspace
     unsigned field_recorders = 0;       // live cavmd_field_recorder objects created from this workspace (the same)
     unsigned verlets = 0;               // live cavmd_verlet objects created from this workspace (the same)
     unsigned moleculars = 0;            // live cavmd_molecular objects created from this workspace (the same)
+    unsigned coulombs = 0;              // live cavmd_coulomb objects created from this workspace (the same)
 };
 
 namespace
@@ -593,6 +594,8 @@ int cavmd_destroy(cavmd_workspace* ws)
     if (ws->verlets != 0)         // nor an integrator
         return CAVMD_ERR_INVALID_VALUE;
     if (ws->moleculars != 0)      // nor a molecular force batch
+        return CAVMD_ERR_INVALID_VALUE;
+    if (ws->coulombs != 0)        // nor a Coulomb force batch
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -3053,6 +3056,456 @@ int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
     if (st != CAVMD_OK)
         return st;
     m->enqueued_on(stream);
+    return CAVMD_OK;
+}
+
+} // extern "C"
+
+// ---- Ewald Coulomb forces of a batch of independent small systems in TWO launches (cavmd_coulomb_batch_kernel.hpp) ------------
+namespace
+{
+constexpr int kCoulombJSplit = CAVMD_COULOMB_J_SPLIT;
+constexpr int kCoulombKSplit = CAVMD_COULOMB_K_SPLIT;
+constexpr unsigned kCoulombRows = kCoulombBlock / kCoulombJSplit;
+constexpr unsigned kCoulombKRows = kCoulombBlock / kCoulombKSplit;
+static_assert(kCoulombJSplit == 1 || kCoulombJSplit == 4 || kCoulombJSplit == 16 || kCoulombJSplit == 64, "S is one of the candidates");
+static_assert(kCoulombKSplit == 1 || kCoulombKSplit == 4 || kCoulombKSplit == 16 || kCoulombKSplit == 64, "T is one of the candidates");
+static_assert(sizeof(cavmd_coulomb_item) == 96, "coulomb item layout");
+static_assert(CAVMD_COULOMB_MAX_EXCLUSIONS == kCoulombMaxExclusions, "the header's limit is the kernel's");
+static_assert(coulomb_lds_bytes(CAVMD_COULOMB_MAX_ITEM_N) <= 64 * 1024, "the largest system fits the LDS a kernel gets without opt-in");
+constexpr double kCoulombPi = 3.141592653589793;
+constexpr double kCoulombSqrtPi = 1.7724538509055159;
+
+// The kept k-vectors of an item (whose box and cut-offs have been checked), in the contract's order; stops at `limit` + 1.
+// Every loop visits kept vectors and one more per row, so the work is bounded by the limit whatever k_cut is.
+void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<CoulombK>* out, size_t* count)
+{
+    const double two_pi = 2.0 * kCoulombPi;
+    const double kc2 = it.k_cut * it.k_cut;
+    const double V = (it.Lx * it.Ly) * it.Lz;
+    const double four_kappa2 = 4.0 * (it.kappa * it.kappa);
+    size_t K = 0;
+    auto component = [&](long m, double L) { return (two_pi * (double)m) / L; };
+    for (long mx = 0;; ++mx)
+    {
+        const double kx = component(mx, it.Lx);
+        const double kxx = kx * kx;
+        if (!(kxx <= kc2))
+            break;
+        if (mx > (long)limit + 1)
+        {
+            *count = limit + 1;
+            return;
+        }
+        // every (mx, my) in range keeps at least one vector, and so does every mz in range: a search that runs past the limit
+        // has already decided the answer
+        long My = 0;
+        while (true)
+        {
+            const double ky = component(My + 1, it.Ly);
+            if (!(kxx + ky * ky <= kc2))
+                break;
+            if (++My > (long)limit + 1)
+            {
+                *count = limit + 1;
+                return;
+            }
+        }
+        for (long my = -My; my <= My; ++my)
+        {
+            if (mx == 0 && my < 0)
+                continue;
+            const double ky = component(my, it.Ly);
+            const double kxy = kxx + ky * ky;
+            long Mz = 0;
+            while (true)
+            {
+                const double kz = component(Mz + 1, it.Lz);
+                if (!(kxy + kz * kz <= kc2))
+                    break;
+                if (++Mz > (long)limit + 1)
+                {
+                    *count = limit + 1;
+                    return;
+                }
+            }
+            for (long mz = -Mz; mz <= Mz; ++mz)
+            {
+                if (mx == 0 && my == 0 && mz <= 0)
+                    continue;
+                const double kz = component(mz, it.Lz);
+                const double k2 = kxy + kz * kz;
+                if (!(k2 > 0.0 && k2 <= kc2))
+                    continue;
+                if (++K > limit)
+                {
+                    *count = K;
+                    return;
+                }
+                if (out)
+                    out->push_back(CoulombK {kx, ky, kz, ((4.0 * kCoulombPi) / V) * exp(-k2 / four_kappa2) / k2});
+            }
+        }
+    }
+    *count = K;
+}
+
+// The status of one item.  `slots`, if given, receives the item's partner table (four slots a particle, filled from slot 0 in
+// the order of the exclusion list), `ktab` its k-table.
+int coulomb_item_status(const cavmd_coulomb_item* it, std::vector<uint32_t>* slots, std::vector<CoulombK>* ktab, size_t* out_K)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_force & 15) || ((uintptr_t)it->d_charge & 7) || ((uintptr_t)it->h_exclusions & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N != 0 && (!it->d_pos || !it->d_force || !it->d_charge))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->n_exclusions != 0 && !it->h_exclusions)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_COULOMB_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    if (it->N != 0)
+    {
+        const double L[3] = {it->Lx, it->Ly, it->Lz};
+        for (double l : L)
+            if (!(isfinite(l) && l > 0.0))
+                return CAVMD_ERR_INVALID_VALUE;
+        if (!(isfinite(it->kappa) && it->kappa > 0.0) || !finite_nonnegative(it->r_cut) || !finite_nonnegative(it->k_cut))
+            return CAVMD_ERR_INVALID_VALUE;
+        const double h = std::min(L[0], std::min(L[1], L[2])) * 0.5;
+        if (it->r_cut * it->r_cut > h * h)
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    std::vector<uint8_t> count(it->N, 0);
+    if (slots)
+        slots->assign((size_t)it->N * kCoulombMaxExclusions, kCoulombNoPartner);
+    for (uint32_t k = 0; k < it->n_exclusions; ++k)
+    {
+        const cavmd_molecular_bond& ex = it->h_exclusions[k];
+        if (ex.a >= it->N || ex.b >= it->N || ex.a == ex.b)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (count[ex.a] >= kCoulombMaxExclusions || count[ex.b] >= kCoulombMaxExclusions)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (slots)
+        {
+            (*slots)[(size_t)ex.a * kCoulombMaxExclusions + count[ex.a]] = ex.b;
+            (*slots)[(size_t)ex.b * kCoulombMaxExclusions + count[ex.b]] = ex.a;
+        }
+        count[ex.a] += 1;
+        count[ex.b] += 1;
+    }
+    size_t K = 0;
+    if (ktab)
+        ktab->clear();
+    if (it->N != 0)
+    {
+        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, ktab, &K);
+        if (K > CAVMD_COULOMB_MAX_K)
+            return CAVMD_ERR_CAPACITY;
+    }
+    if (out_K)
+        *out_K = K;
+    return CAVMD_OK;
+}
+
+CoulombRow coulomb_row(const cavmd_coulomb_item& it)
+{
+    CoulombRow r;
+    memset(&r, 0, sizeof(r));
+    r.pos2 = reinterpret_cast<const v2d*>(it.d_pos);
+    r.charge = it.d_charge;
+    r.force2 = reinterpret_cast<v2d*>(it.d_force);
+    r.Lx = it.Lx;
+    r.Ly = it.Ly;
+    r.Lz = it.Lz;
+    r.kappa = it.kappa;
+    r.rcutsq = it.r_cut * it.r_cut;
+    r.n = it.N;
+    if (it.N != 0)
+    {
+        size_t K = 0;
+        coulomb_k_vectors(it, CAVMD_COULOMB_MAX_K, nullptr, &K); // the item has been checked: K <= CAVMD_COULOMB_MAX_K
+        r.n_k = (unsigned)K;
+        r.self_c = it.kappa / kCoulombSqrtPi;
+        r.bg_c = kCoulombPi / ((2.0 * ((it.Lx * it.Ly) * it.Lz)) * (it.kappa * it.kappa));
+    }
+    return r;
+}
+
+// what set_items replaces together
+struct CoulombTables
+{
+    DeviceArray<uint4> k_blocks, blocks, partners;
+    DeviceArray<CoulombK> ktab;
+    DeviceArray<v2d> structure;
+    std::vector<uint32_t> offsets; // per item: its first entry of ktab / structure
+    CoulombHeader header;
+    unsigned lds_n = 2;
+};
+} // namespace
+
+struct cavmd_coulomb : ItemTable<cavmd_coulomb_item, CoulombRow> // workgroups by N descending
+{
+    cavmd_workspace* ws = nullptr;
+    DeviceArray<CoulombHeader> d_header;      // never reallocated: captured launches find the tables through it
+    CoulombTables tables;                     // replaced as a whole by set_items
+    std::vector<std::vector<uint32_t>> slots; // per item: its partner table (the exclusion lists are not kept)
+    std::vector<std::vector<CoulombK>> ktabs; // per item: its k-table
+
+    cavmd_coulomb()
+        : ItemTable([](const cavmd_coulomb_item* it) { return coulomb_item_status(it, nullptr, nullptr, nullptr); },
+                    [](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row)
+    {
+    }
+
+    // the host's tables for `sizes` and `launch` (items by N descending), into fresh device arrays; committed by publish()
+    hipError_t build(const std::vector<unsigned>& sizes, const std::vector<unsigned>& launch,
+                     const std::vector<std::vector<uint32_t>>& all_slots, const std::vector<std::vector<CoulombK>>& all_k,
+                     CoulombTables* t) const
+    {
+        const size_t B = sizes.size();
+        std::vector<uint32_t> partner_base(B), pool;
+        std::vector<CoulombK> kpool;
+        t->offsets.assign(B, 0);
+        unsigned largest = 0;
+        for (size_t i = 0; i < B; ++i)
+        {
+            partner_base[i] = (uint32_t)(pool.size() / kCoulombMaxExclusions);
+            pool.insert(pool.end(), all_slots[i].begin(), all_slots[i].end());
+            t->offsets[i] = (uint32_t)kpool.size();
+            kpool.insert(kpool.end(), all_k[i].begin(), all_k[i].end());
+            kpool.push_back(CoulombK {0.0, 0.0, 0.0, 0.0}); // the slot of {Q, 0}
+            largest = std::max(largest, sizes[i]);
+        }
+        std::vector<uint4> k_table, table;
+        for (unsigned item : launch)
+        {
+            if (sizes[item] == 0)
+                continue;
+            for (unsigned f = 0; f < all_k[item].size(); f += kCoulombKRows)
+                k_table.push_back(make_uint4(item, f, t->offsets[item], 0u));
+            for (unsigned f = 0; f < sizes[item]; f += kCoulombRows)
+                table.push_back(make_uint4(item, f, partner_base[item], t->offsets[item]));
+        }
+        auto upload = [](auto* dst, const auto& src) {
+            hipError_t e = dst->alloc(std::max<size_t>(src.size(), 1));
+            if (e == hipSuccess && !src.empty())
+                e = hipMemcpy(dst->ptr, src.data(), sizeof(src[0]) * src.size(), hipMemcpyHostToDevice);
+            return e;
+        };
+        hipError_t e = upload(&t->k_blocks, k_table);
+        if (e == hipSuccess)
+            e = upload(&t->blocks, table);
+        if (e == hipSuccess)
+            e = upload(&t->ktab, kpool);
+        if (e == hipSuccess)
+            e = t->structure.alloc_zeroed(kpool.size());
+        if (e == hipSuccess)
+        {
+            e = t->partners.alloc(std::max<size_t>(pool.size() / kCoulombMaxExclusions, 1));
+            if (e == hipSuccess && !pool.empty())
+                e = hipMemcpy(t->partners.ptr, pool.data(), sizeof(uint32_t) * pool.size(), hipMemcpyHostToDevice);
+        }
+        memset(&t->header, 0, sizeof(t->header));
+        t->header.k_blocks = t->k_blocks.ptr;
+        t->header.blocks = t->blocks.ptr;
+        t->header.partners = t->partners.ptr;
+        t->header.ktab = t->ktab.ptr;
+        t->header.structure = t->structure.ptr;
+        t->header.n_k_blocks = (unsigned)k_table.size();
+        t->header.n_blocks = (unsigned)table.size();
+        t->lds_n = std::max(2u, (largest + 1u) & ~1u);
+        return e;
+    }
+
+    hipError_t publish(CoulombTables&& t)
+    {
+        const hipError_t e = hipMemcpy(d_header.ptr, &t.header, sizeof(t.header), hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return e;
+        tables = std::move(t); // the old tables are freed here: nothing in flight reads them (the caller has waited)
+        return hipSuccess;
+    }
+};
+
+extern "C"
+{
+
+int cavmd_coulomb_item_check(const cavmd_coulomb_item* it)
+{
+    return coulomb_item_status(it, nullptr, nullptr, nullptr);
+}
+
+int cavmd_coulomb_k_count(const cavmd_coulomb_item* it, uint32_t* out_K)
+{
+    if (!out_K)
+        return CAVMD_ERR_INVALID_VALUE;
+    size_t K = 0;
+    const int st = coulomb_item_status(it, nullptr, nullptr, &K);
+    if (st != CAVMD_OK)
+        return st;
+    *out_K = (uint32_t)K;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_parameters(double r_cut, double accuracy, double* kappa, double* k_cut)
+{
+    if (!kappa || !k_cut || !(isfinite(r_cut) && r_cut > 0.0) || !(accuracy > 0.0 && accuracy < 1.0))
+        return CAVMD_ERR_INVALID_VALUE;
+    const double s = sqrt(-log(accuracy));
+    *kappa = s / r_cut;
+    *k_cut = (2.0 * *kappa) * s;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_order(int* rows, int* j_split, int* k_rows, int* k_split)
+{
+    if (rows)
+        *rows = (int)kCoulombRows;
+    if (j_split)
+        *j_split = kCoulombJSplit;
+    if (k_rows)
+        *k_rows = (int)kCoulombKRows;
+    if (k_split)
+        *k_split = kCoulombKSplit;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulomb_item* h_items, cavmd_coulomb** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+        return CAVMD_ERR_INVALID_VALUE;
+    std::vector<std::vector<uint32_t>> slots(n_items);
+    std::vector<std::vector<CoulombK>> ktabs(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const int st = coulomb_item_status(h_items + i, &slots[i], &ktabs[i], nullptr);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    cavmd_coulomb* c = new (std::nothrow) cavmd_coulomb();
+    if (!c)
+        return (int)hipErrorOutOfMemory;
+    c->adopt(ws->device, h_items, n_items);
+    std::vector<unsigned> sizes(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        c->items[i].h_exclusions = nullptr; // the caller's lists are not kept
+        c->items[i].n_exclusions = 0;
+        sizes[i] = c->items[i].N;
+    }
+    c->slots.swap(slots);
+    c->ktabs.swap(ktabs);
+
+    DeviceGuard guard(c->device);
+    CoulombTables t;
+    hipError_t e = c->upload();
+    if (e == hipSuccess)
+        e = c->d_header.alloc_zeroed(1);
+    if (e == hipSuccess)
+        e = c->build(sizes, c->order, c->slots, c->ktabs, &t);
+    if (e == hipSuccess)
+        e = c->publish(std::move(t));
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess)
+    {
+        cavmd_coulomb_destroy(c);
+        return (int)e;
+    }
+    c->ws = ws;
+    ws->coulombs += 1;
+    *out = c;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_destroy(cavmd_coulomb* c)
+{
+    if (!c)
+        return CAVMD_OK;
+    DeviceGuard guard(c->device);
+    c->quiesce_and_free();
+    if (c->ws)
+        c->ws->coulombs -= 1;
+    delete c;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items)
+{
+    if (!c || !h_items || count == 0 || first >= c->n || count > c->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    std::vector<std::vector<uint32_t>> new_slots(c->slots);
+    std::vector<std::vector<CoulombK>> new_ktabs(c->ktabs);
+    std::vector<cavmd_coulomb_item> rows(h_items, h_items + count);
+    std::vector<unsigned> sizes(c->n);
+    for (size_t i = 0; i < c->n; ++i)
+        sizes[i] = c->items[i].N;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const int st = coulomb_item_status(h_items + i, &new_slots[first + i], &new_ktabs[first + i], nullptr);
+        if (st != CAVMD_OK)
+            return st;
+        rows[i].h_exclusions = nullptr; // the caller's lists are not kept
+        rows[i].n_exclusions = 0;
+        sizes[first + i] = rows[i].N;
+    }
+    DeviceGuard guard(c->device);
+    if (c->enqueued)
+    {
+        if (stream_capturing(c->last_stream))
+            return CAVMD_ERR_INVALID_VALUE; // nothing below may run during a capture
+        CAVMD_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    }
+    // the new tables go to fresh device arrays first, then the rows, then the 64-byte header that points to the tables
+    std::vector<cavmd_coulomb_item> all(c->items);
+    std::copy(rows.begin(), rows.end(), all.begin() + first);
+    const std::vector<unsigned> launch = launch_order(all, c->key);
+    CoulombTables t;
+    CAVMD_HIP_TRY(c->build(sizes, launch, new_slots, new_ktabs, &t));
+    const int st = c->set_items(first, count, rows.data());
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(c->publish(std::move(t)));
+    c->slots.swap(new_slots);
+    c->ktabs.swap(new_ktabs);
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
+{
+    if (!c)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(c->device);
+    const CoulombTables& t = c->tables;
+    hipLaunchKernelGGL((coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>), dim3(std::max(t.header.n_k_blocks, 1u)),
+                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows, c->d_header.ptr, t.lds_n);
+    int st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    hipLaunchKernelGGL((coulomb_force_kernel<kCoulombBlock, kCoulombJSplit>), dim3(std::max(t.header.n_blocks, 1u)),
+                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows, c->d_header.ptr, t.lds_n);
+    st = hip_status(hipGetLastError());
+    if (st != CAVMD_OK)
+        return st;
+    c->enqueued_on(stream);
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets)
+{
+    if (!c || (!out && !h_offsets))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (out)
+        *out = reinterpret_cast<const double*>(c->tables.structure.ptr);
+    if (h_offsets)
+        *h_offsets = c->tables.offsets.data();
     return CAVMD_OK;
 }
 

@@ -1,0 +1,311 @@
+// cavmd_coulomb_batch_kernel.hpp -- Ewald Coulomb forces of a batch of independent small systems in TWO launches: the
+// electrostatics next to cavmd_molecular_batch_kernel.hpp's bonds and Lennard-Jones pairs, between cavmd_verlet_batch_kernel.hpp's
+// two half-steps.
+//
+// The reference's driver takes its electrostatics from HOOMD-blue's PPPM (make_pppm_coulomb_forces over the bond-excluding
+// neighbour list, examples/05_advanced_run.py:598-608).  PPPM approximates the Ewald sum on a mesh; at N <= 2048 the sum itself
+// is cheaper than a mesh and needs no FFT, so this file IS the Ewald sum, with the expressions of include/cavmd.h as the
+// contract.  What separates it from a PPPM run is PPPM's discretisation error, which nothing in this repository measures.
+//
+//   1. coulomb_structure_kernel: a system with K kept k-vectors gets ceil(K / KROWS) workgroups.  Each stages x, y, z, q of
+//      its WHOLE system into LDS (32 B a particle); T = BLOCK / KROWS adjacent lanes share one k-vector, lane t walks
+//      j = t, t + T, ... and the group folds S(k) = sum_j q_j exp(i k.x_j) left to right with shuffles.  Lane 0 stores it.
+//   2. coulomb_force_kernel: ceil(n / ROWS) workgroups per system, the same LDS image; S = BLOCK / ROWS adjacent lanes share
+//      particle i and split first the j-walk (real-space term inside the cut-off, exclusion term for the listed partners, and
+//      the total charge Q on the way) and then the k-walk (S(k) of launch 1 and the library's table of k and a_k out of global
+//      memory), fold left to right with shuffles, and lane 0 adds the self and background terms and stores.
+//
+// LDS is four arrays of doubles (x, y, z, q), not 32-byte records: the S (or T) lanes of a group read S consecutive doubles
+// with one ds_read_b64 -- S distinct banks, every other lane of the wave a broadcast -- where records would put j and j + 8 on
+// one bank.  No atomics, no workgroup waits for another one, every loop is bounded by n or K, every LDS index is below n (the
+// partner tables are built and checked by the library), and every slot and every force entry is written by its owner.
+#pragma once
+
+#include "cavmd_reduce.hpp"
+
+#pragma clang fp contract(off)
+
+namespace cavmd
+{
+constexpr int kCoulombBlock = 256;
+constexpr int kCoulombMaxExclusions = 4;
+constexpr unsigned kCoulombNoPartner = 0xFFFFFFFFu;
+
+// One system as the kernels read it.
+struct CoulombRow
+{
+    const v2d* pos2;
+    const double* charge;
+    v2d* force2;
+    double Lx, Ly, Lz;
+    double kappa;   // > 0
+    double rcutsq;  // r_cut * r_cut
+    double self_c;  // kappa / sqrt(pi)
+    double bg_c;    // pi / (2 V kappa^2)
+    unsigned n;
+    unsigned n_k; // K, the kept k-vectors
+    uint64_t pad;
+};
+static_assert(sizeof(CoulombRow) == 96, "one coulomb row = 96 bytes");
+
+// One kept k-vector, built by the library on the host: k and a_k = (4 pi / V) exp(-k^2 / (4 kappa^2)) / k^2.
+struct CoulombK
+{
+    double kx, ky, kz, a;
+};
+static_assert(sizeof(CoulombK) == 32, "one k-table entry = 32 bytes");
+
+// What the launches find their tables through.  The block lives in device memory at an address that never changes, so captured
+// launches follow the tables set_items builds:
+//   k_blocks[b] = {item, first k of the workgroup, first entry of the item's k-table, 0}                        (launch 1)
+//   blocks[b]   = {item, first particle, first entry of the item's partner table, first entry of its k-table}   (launch 2)
+//   partners[p] = the four slots of one particle, kCoulombNoPartner when empty, filled from slot 0
+//   ktab[e], structure[e]: an item owns n_k + 1 consecutive entries; structure[base + k] = {A, B} of k-vector k, and
+//   structure[base + n_k] = {Q, 0} (written by launch 2: it is the value the background term used).
+struct CoulombHeader
+{
+    const uint4* k_blocks;
+    const uint4* blocks;
+    const uint4* partners;
+    const CoulombK* ktab;
+    v2d* structure;
+    unsigned n_k_blocks;
+    unsigned n_blocks;
+    uint64_t pad[2];
+};
+static_assert(sizeof(CoulombHeader) == 64, "coulomb launch header = 64 bytes");
+
+// bytes of dynamic LDS either launch needs for systems of up to lds_n particles
+constexpr size_t coulomb_lds_bytes(unsigned lds_n)
+{
+    return (size_t)lds_n * 32;
+}
+
+// the minimum image of cavmd_molecular_batch_kernel.hpp, rule for rule
+__device__ __forceinline__ double coulomb_min_image(double d, double L, double h)
+{
+    if (d >= h)
+        d -= L;
+    else if (d < -h)
+        d += L;
+    return d;
+}
+
+// x, y, z, q of the n particles of `row` into the four LDS arrays
+template <int BLOCK>
+__device__ __forceinline__ void coulomb_stage(const CoulombRow* __restrict__ row, unsigned n, double* __restrict__ sx,
+                                              double* __restrict__ sy, double* __restrict__ sz, double* __restrict__ sq)
+{
+    const v2d* __restrict__ pos2 = row->pos2;
+    const double* __restrict__ charge = row->charge;
+    for (unsigned j = threadIdx.x; j < n; j += BLOCK)
+    {
+        const v2d xy = pos2[2 * (size_t)j], zw = pos2[2 * (size_t)j + 1];
+        sx[j] = xy.x;
+        sy[j] = xy.y;
+        sz[j] = zw.x;
+        sq[j] = charge[j];
+    }
+    __syncthreads();
+}
+
+// lds_n: the particles the launch has LDS for (frozen with the launch, as the LDS size is).  A system beyond it -- a table
+// rewritten after the capture -- gets NaN structure factors here and NaN forces from launch 2, never an out-of-bounds access.
+template <int BLOCK, int T>
+__global__ __launch_bounds__(BLOCK) void coulomb_structure_kernel(const CoulombRow* __restrict__ rows,
+                                                                  const CoulombHeader* __restrict__ hdr, unsigned lds_n)
+{
+    static_assert(T >= 1 && T <= kWave && (T & (T - 1)) == 0 && BLOCK % T == 0, "T lanes of one wave share a k-vector");
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_coulomb[];
+    if (blockIdx.x >= hdr->n_k_blocks)
+        return; // a launch captured for a larger table
+    const uint4 blk = hdr->k_blocks[blockIdx.x];
+    const unsigned item = __builtin_amdgcn_readfirstlane(blk.x);
+    const unsigned first = __builtin_amdgcn_readfirstlane(blk.y);
+    const unsigned base = __builtin_amdgcn_readfirstlane(blk.z);
+    const CoulombRow* __restrict__ row = rows + item;
+    const unsigned n = row->n, n_k = row->n_k;
+    const unsigned r = threadIdx.x / T, t = threadIdx.x % T;
+    const unsigned k = first + r;
+    const bool owner = (k < n_k);
+    v2d* __restrict__ out = hdr->structure + (size_t)base;
+    if (n > lds_n)
+    {
+        if (owner && t == 0)
+        {
+            const double nan = __builtin_nan("");
+            const v2d bad = {nan, nan};
+            out[k] = bad;
+        }
+        return;
+    }
+    double* __restrict__ sx = reinterpret_cast<double*>(s_coulomb);
+    double* __restrict__ sy = sx + lds_n;
+    double* __restrict__ sz = sy + lds_n;
+    double* __restrict__ sq = sz + lds_n;
+    coulomb_stage<BLOCK>(row, n, sx, sy, sz, sq);
+
+    // lanes past the end walk nothing and write nothing, but take part in the shuffles
+    CoulombK kv = {0.0, 0.0, 0.0, 0.0};
+    if (owner)
+        kv = hdr->ktab[(size_t)base + k];
+    double a = 0.0, b = 0.0;
+    const unsigned j_end = owner ? n : 0u;
+    for (unsigned j = t; j < j_end; j += T)
+    {
+        const double theta = (kv.kx * sx[j] + kv.ky * sy[j]) + kv.kz * sz[j];
+        double sn, cs;
+        sincos(theta, &sn, &cs);
+        const double q = sq[j];
+        a = a + q * cs;
+        b = b + q * sn;
+    }
+    // A = ((a_0 + a_1) + a_2) + ...: every lane of the group folds the same T values in the same order
+    double A = __shfl(a, 0, T), B = __shfl(b, 0, T);
+#pragma unroll 1
+    for (int u = 1; u < T; ++u)
+    {
+        A = A + __shfl(a, u, T);
+        B = B + __shfl(b, u, T);
+    }
+    if (owner && t == 0)
+    {
+        const v2d AB = {A, B};
+        out[k] = AB;
+    }
+}
+
+template <int BLOCK, int S>
+__global__ __launch_bounds__(BLOCK) void coulomb_force_kernel(const CoulombRow* __restrict__ rows,
+                                                              const CoulombHeader* __restrict__ hdr, unsigned lds_n)
+{
+    static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_coulomb[];
+    if (blockIdx.x >= hdr->n_blocks)
+        return; // a launch captured for a larger table
+    const uint4 blk = hdr->blocks[blockIdx.x];
+    const unsigned item = __builtin_amdgcn_readfirstlane(blk.x);
+    const unsigned first = __builtin_amdgcn_readfirstlane(blk.y);
+    const unsigned partner_base = __builtin_amdgcn_readfirstlane(blk.z);
+    const unsigned k_base = __builtin_amdgcn_readfirstlane(blk.w);
+    const CoulombRow* __restrict__ row = rows + item;
+    const unsigned n = row->n, n_k = row->n_k;
+    v2d* __restrict__ force2 = row->force2;
+    const unsigned r = threadIdx.x / S, s = threadIdx.x % S;
+    const unsigned i = first + r;
+    const bool owner = (i < n);
+    if (n > lds_n)
+    {
+        if (owner && s == 0)
+        {
+            const double nan = __builtin_nan("");
+            const v2d bad = {nan, nan};
+            force2[2 * (size_t)i] = bad;
+            force2[2 * (size_t)i + 1] = bad;
+        }
+        return;
+    }
+    double* __restrict__ sx = reinterpret_cast<double*>(s_coulomb);
+    double* __restrict__ sy = sx + lds_n;
+    double* __restrict__ sz = sy + lds_n;
+    double* __restrict__ sq = sz + lds_n;
+    coulomb_stage<BLOCK>(row, n, sx, sy, sz, sq);
+
+    const double Lx = row->Lx, Ly = row->Ly, Lz = row->Lz;
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5;
+    const double kappa = row->kappa, rcutsq = row->rcutsq;
+    const double two_self_c = 2.0 * row->self_c; // 2 kappa / sqrt(pi)
+    const unsigned ii = owner ? i : 0u;          // lanes past the end walk nothing and write nothing, but take part in the shuffles
+    const double xi = sx[ii], yi = sy[ii], zi = sz[ii], qi = sq[ii];
+    uint4 slots = {kCoulombNoPartner, kCoulombNoPartner, kCoulombNoPartner, kCoulombNoPartner};
+    if (owner)
+        slots = hdr->partners[(size_t)partner_base + i];
+
+    // real space: partial s of particle i, and of the total charge
+    double px = 0.0, py = 0.0, pz = 0.0, pw = 0.0, pq = 0.0;
+    const unsigned j_end = owner ? n : 0u;
+    for (unsigned j = s; j < j_end; j += S)
+    {
+        const double qj = sq[j];
+        pq = pq + qj;
+        if (j == i)
+            continue;
+        const bool excluded = (j == slots.x) | (j == slots.y) | (j == slots.z) | (j == slots.w);
+        const double dx = coulomb_min_image(xi - sx[j], Lx, hx);
+        const double dy = coulomb_min_image(yi - sy[j], Ly, hy);
+        const double dz = coulomb_min_image(zi - sz[j], Lz, hz);
+        const double rsq = (dx * dx + dy * dy) + dz * dz;
+        if (!excluded && !(rsq < rcutsq))
+            continue;
+        const double rr = sqrt(rsq);
+        const double kr = kappa * rr;
+        const double g = two_self_c * exp(-(kr * kr));
+        const double qq = qi * qj;
+        double e, fdivr;
+        if (excluded)
+        {
+            const double u = erf(kr) / rr;
+            e = -(qq * u);
+            fdivr = -(qq * (u - g)) / rsq;
+        }
+        else
+        {
+            const double u = erfc(kr) / rr;
+            e = qq * u;
+            fdivr = (qq * (u + g)) / rsq;
+        }
+        px = px + dx * fdivr;
+        py = py + dy * fdivr;
+        pz = pz + dz * fdivr;
+        pw = pw + 0.5 * e;
+    }
+
+    // reciprocal space: partial s over k = s, s + S, ...; the factors q_i and 2 q_i are applied once, to the partial
+    double rx = 0.0, ry = 0.0, rz = 0.0, rw = 0.0;
+    const unsigned k_end = owner ? n_k : 0u;
+    const CoulombK* __restrict__ ktab = hdr->ktab + (size_t)k_base;
+    const v2d* __restrict__ structure = hdr->structure + (size_t)k_base;
+    for (unsigned k = s; k < k_end; k += S)
+    {
+        const CoulombK kv = ktab[k];
+        const v2d AB = structure[k];
+        const double theta = (kv.kx * xi + kv.ky * yi) + kv.kz * zi;
+        double sn, cs;
+        sincos(theta, &sn, &cs);
+        const double f = kv.a * (AB.x * sn - AB.y * cs);
+        rx = rx + kv.kx * f;
+        ry = ry + kv.ky * f;
+        rz = rz + kv.kz * f;
+        rw = rw + kv.a * (AB.x * cs + AB.y * sn);
+    }
+    const double qi2 = 2.0 * qi;
+    px = px + qi2 * rx;
+    py = py + qi2 * ry;
+    pz = pz + qi2 * rz;
+    pw = pw + qi * rw;
+
+    // P = ((p0 + p1) + p2) + ...: every lane of the group folds the same S values in the same order
+    double Px = __shfl(px, 0, S), Py = __shfl(py, 0, S), Pz = __shfl(pz, 0, S), Pw = __shfl(pw, 0, S), Q = __shfl(pq, 0, S);
+#pragma unroll 1
+    for (int u = 1; u < S; ++u)
+    {
+        Px = Px + __shfl(px, u, S);
+        Py = Py + __shfl(py, u, S);
+        Pz = Pz + __shfl(pz, u, S);
+        Pw = Pw + __shfl(pw, u, S);
+        Q = Q + __shfl(pq, u, S);
+    }
+    if (!owner || s != 0)
+        return;
+    // self and background
+    Pw = (Pw - row->self_c * (qi * qi)) - row->bg_c * (qi * Q);
+    const v2d Fxy = {Px, Py}, Fzw = {Pz, Pw};
+    force2[2 * (size_t)i] = Fxy;
+    force2[2 * (size_t)i + 1] = Fzw;
+    if (i == 0)
+    {
+        const v2d Q0 = {Q, 0.0};
+        hdr->structure[(size_t)k_base + n_k] = Q0;
+    }
+}
+} // namespace cavmd

@@ -28,7 +28,8 @@
 //        cavmd_bussi_batch_kernel.hpp (the thermostat step of many small systems in one launch, one workgroup each),
 //        cavmd_recorder_kernel.hpp (their per-step observables appended to a time series in device memory, one launch),
 //        cavmd_verlet_batch_kernel.hpp (their velocity-Verlet half-steps, one launch each),
-//        cavmd_molecular_batch_kernel.hpp (their harmonic bonds and Lennard-Jones pairs, one launch, all pairs out of LDS).
+//        cavmd_molecular_batch_kernel.hpp (their harmonic bonds and Lennard-Jones pairs, one launch, all pairs out of LDS),
+//        cavmd_coulomb_batch_kernel.hpp (their Ewald Coulomb forces, two launches: structure factors, then forces).
 #pragma once
 
 #include "cavmd_reduce.hpp"
@@ -41,3 +42,4 @@
 #include "cavmd_field_recorder_kernel.hpp"
 #include "cavmd_verlet_batch_kernel.hpp"
 #include "cavmd_molecular_batch_kernel.hpp"
+#include "cavmd_coulomb_batch_kernel.hpp"

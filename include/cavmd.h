@@ -783,7 +783,7 @@ CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_
  * its ROWS particles walks all j.  No neighbour list, no Newton's-third-law halving, no atomics, no workgroup waits for
  * another one (hence no CAVMD_ERR_SYNC_TIMEOUT), every loop is bounded by N, and EVERY entry of an item's force array is
  * written (zeros for the photon and for particles that interact with nothing: no memset pass).  The result is a further force
- * array of cavmd_verlet_item.d_force.  Electrostatics (PPPM, a real-space Ewald term) are out of scope.
+ * array of cavmd_verlet_item.d_force.  Electrostatics are the next section's (cavmd_coulomb_*).
  *
  * The arithmetic restates EvaluatorPairLJ, EvaluatorBondHarmonic and BoxDim::minImage of HOOMD-blue 4.x from knowledge
  * [HOOMD upstream, not in checkout]: parity with HOOMD-blue itself is NOT pinned by anything in this repository; the
@@ -880,6 +880,102 @@ CAVMD_API int cavmd_molecular_set_items(cavmd_molecular* m, size_t first, size_t
 /* Enqueues exactly ONE kernel on `stream`: no allocation, no copy, no host wait; may be captured into a hipGraph.  One batch
  * serves one host thread and one stream at a time. */
 CAVMD_API int cavmd_molecular_compute(cavmd_molecular* m, void* stream);
+
+/* ---- Ewald Coulomb forces of a batch in TWO launches: the electrostatics of the captured step ------------------------------ */
+/* The reference's driver adds the pair of forces returned by make_pppm_coulomb_forces over the bond-excluding neighbour list
+ * (examples/05_advanced_run.py:598-608): HOOMD-blue's PPPM.  PPPM approximates the Ewald sum on a mesh (32^3, order 6, its own
+ * choice of kappa in the driver).  Systems here have at most CAVMD_COULOMB_MAX_ITEM_N particles, where the sum itself is
+ * cheaper than a mesh and needs no FFT, so this section IS the Ewald sum: real space over all pairs out of LDS, reciprocal
+ * space as a direct sum over the K kept k-vectors.  Parity with HOOMD-blue's PPPM is NOT pinned by anything in this
+ * repository [HOOMD upstream, not in checkout]: what separates the two is PPPM's discretisation error, which nobody has
+ * measured.  The expressions below ARE the contract.  Units are HOOMD's: the pair energy is q_i q_j / r.
+ *
+ * A system: stored (wrapped) positions x, charges q (type ids play no part; the photon takes part through its charge, 0 in the
+ * driver's systems), an orthorhombic box L, V = (Lx * Ly) * Lz, kappa > 0, r_cut with r_cut^2 <= (min(L) * 0.5)^2, k_cut >= 0,
+ * and an exclusion list of at most CAVMD_COULOMB_MAX_EXCLUSIONS partners per particle.
+ *   real space, for j != i:      d = the minimum image of x_i - x_j by the molecular section's rule;  rsq = (d_x d_x + d_y d_y)
+ *                                + d_z d_z;  r = sqrt(rsq);  g = (2 kappa / sqrt(pi)) exp(-(kappa r)^2)
+ *     j not excluded and rsq < r_cut^2 (strict):   e = q_i q_j erfc(kappa r) / r;   f/r = q_i q_j (erfc(kappa r) / r + g) / rsq
+ *     j an exclusion partner of i (no cut-off):    e = -q_i q_j erf(kappa r) / r;   f/r = -q_i q_j (erf(kappa r) / r - g) / rsq
+ *                                (erf itself, never erfc - 1);  F_i += d * (f/r);  w_i += 0.5 * e
+ *   reciprocal space:            H = the integer triples m with mx > 0, or mx == 0 and my > 0, or mx == my == 0 and mz > 0;
+ *                                k_c = (2 pi * m_c) / L_c;  k2 = (kx kx + ky ky) + kz kz, kept if 0 < k2 <= k_cut * k_cut, in
+ *                                the order mx, then my, then mz ascending (K of them: cavmd_coulomb_k_count)
+ *                                a_k = (4 pi / V) exp(-k2 / (4 kappa^2)) / k2  (host arithmetic, the library's table)
+ *                                S(k) = sum_j q_j exp(i k.x_j) = A + i B;  theta = k.x_i
+ *                                F_i += 2 q_i a_k k (A sin theta - B cos theta);  w_i += q_i a_k (A cos theta + B sin theta)
+ *   self and background:         Q = sum_j q_j, taken on the device;  w_i += -(kappa / sqrt(pi)) q_i^2 - pi q_i Q / (2 V kappa^2)
+ * Arithmetic is NOT fixed bit for bit: the device's erfc, erf, exp and sincos do not round like any host library's.  The
+ * contract is the expressions, to the rounding bound tests/coulomb_mirror.py derives.  What is fixed: no FMA contraction, no
+ * atomics, and fold orders that depend on nothing but the compile-time splits below -- the same input gives the same bits on
+ * every launch and on every graph replay.
+ *
+ * Two launches per evaluation, and no workgroup ever waits for another one (hence no CAVMD_ERR_SYNC_TIMEOUT):
+ *   1. structure factors: a system gets ceil(K / KROWS) workgroups (none for K == 0); each stages x, y, z, q of its WHOLE system
+ *      into LDS (32 B a particle, 64 KiB at the cap), T = 256 / KROWS lanes share a k-vector and split the walk over j, and
+ *      S(k) goes to a table the library owns (16 B per k; every slot written by its owner, no memset pass).
+ *   2. forces: ceil(N / ROWS) workgroups per system with the same LDS image; S = 256 / ROWS lanes share particle i and split the
+ *      walk over j (real-space and exclusion terms, and Q) and the walk over k (S(k) and the library's table of k and a_k),
+ *      fold left to right, and lane 0 adds the self and background terms.  EVERY entry of an item's force array is written
+ *      by every evaluation; the entry of a particle with q == 0 compares equal to zero. */
+#define CAVMD_COULOMB_MAX_ITEM_N 2048    /* the molecular cap; 32 B x 2048 = 64 KiB of LDS */
+#define CAVMD_COULOMB_MAX_K 4096         /* kept k-vectors of one item */
+#define CAVMD_COULOMB_MAX_EXCLUSIONS 4   /* exclusion partners of one particle */
+#ifndef CAVMD_COULOMB_J_SPLIT            /* S, one of 1, 4, 16, 64: lanes that share a particle in launch 2; ROWS = 256 / S */
+#define CAVMD_COULOMB_J_SPLIT 16
+#endif
+#ifndef CAVMD_COULOMB_K_SPLIT            /* T, one of 1, 4, 16, 64: lanes that share a k-vector in launch 1; KROWS = 256 / T */
+#define CAVMD_COULOMB_K_SPLIT 4          /* both are compile-time constants of the library (profiles/coulomb_batch/README.md) */
+#endif
+typedef struct cavmd_coulomb_item        /* 96 B */
+{
+    const cavmd_double4* d_pos;          /* DEVICE: HOOMD Scalar4 positions (wrapped), .w ignored; 16-byte aligned */
+    const double* d_charge;              /* DEVICE: N charges, read when the kernels run; 8-byte aligned */
+    cavmd_double4* d_force;              /* DEVICE: N entries, all written by every evaluation; 16-byte aligned */
+    const cavmd_molecular_bond* h_exclusions; /* HOST: n_exclusions pairs in the bond-list format, `type` ignored; read during
+                                            create / set_items only; 4-byte aligned */
+    double Lx, Ly, Lz;
+    double kappa, r_cut, k_cut;
+    uint32_t N;                          /* 0 is legal: the item gets no workgroup; <= CAVMD_COULOMB_MAX_ITEM_N */
+    uint32_t n_exclusions;
+    uint64_t reserved;                   /* must be 0 */
+} cavmd_coulomb_item;
+typedef struct cavmd_coulomb cavmd_coulomb; /* opaque; belongs to the workspace it was created from */
+
+/* The four functions below are host arithmetic and need no device. */
+/* CAVMD_ERR_CAPACITY for N above CAVMD_COULOMB_MAX_ITEM_N or more than CAVMD_COULOMB_MAX_K kept k-vectors;
+ * CAVMD_ERR_INVALID_VALUE for a null item, reserved != 0, a null (with N > 0) or misaligned d_pos / d_charge / d_force, a null
+ * (with n_exclusions > 0) or misaligned h_exclusions, an exclusion index not below N, an exclusion with a == b, more than
+ * CAVMD_COULOMB_MAX_EXCLUSIONS partners on a particle, and with N > 0: box lengths that are not finite and positive, a kappa
+ * that is not finite and positive, an r_cut or k_cut that is negative or not finite, r_cut^2 above (min(L) * 0.5)^2. */
+CAVMD_API int cavmd_coulomb_item_check(const cavmd_coulomb_item* item);
+/* K of an item cavmd_coulomb_item_check accepts (0 for N == 0); its status otherwise. */
+CAVMD_API int cavmd_coulomb_k_count(const cavmd_coulomb_item* item, uint32_t* out_K);
+/* kappa = sqrt(-ln accuracy) / r_cut and k_cut = 2 kappa sqrt(-ln accuracy): both truncation errors are then of the order of
+ * `accuracy`.  CAVMD_ERR_INVALID_VALUE for null outputs, an r_cut that is not finite and positive, an accuracy outside (0, 1). */
+CAVMD_API int cavmd_coulomb_parameters(double r_cut, double accuracy, double* kappa, double* k_cut);
+/* ROWS and S of launch 2, KROWS and T of launch 1, as the library was compiled; any may be NULL. */
+CAVMD_API int cavmd_coulomb_order(int* rows, int* j_split, int* k_rows, int* k_split);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), builds both workgroup tables (items by N descending,
+ * ties in item order), every particle's partner table from the exclusion lists and every item's table of k and a_k, and copies
+ * them to the device of `ws` (set-up time).  The exclusion lists are not referenced after the call.  cavmd_destroy answers
+ * CAVMD_ERR_INVALID_VALUE and frees nothing while a Coulomb batch of the workspace is alive. */
+CAVMD_API int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulomb_item* h_items, cavmd_coulomb** out);
+/* Synchronises the stream of the last launch (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_coulomb_destroy(cavmd_coulomb* c);
+/* Replaces rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
+ * changed if a row is refused.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the
+ * batch.  Launches captured BEFORE the call keep their numbers of workgroups and their LDS size: on replay they evaluate the new
+ * tables as far as their workgroups reach and fill the forces of a system larger than their LDS with NaN; capture again after
+ * a call that changes N or K. */
+CAVMD_API int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items);
+/* Enqueues exactly TWO kernels on `stream`: no allocation, no copy, no host wait; may be captured into a hipGraph.  One batch
+ * serves one host thread and one stream at a time. */
+CAVMD_API int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream);
+/* Device address of the structure-factor table, for consumers that stay on the GPU, and (either may be NULL) the HOST array of
+ * n_items offsets into it: item i owns K_i + 1 entries of two doubles from offset[i] on, {A, B} of its k-vectors in the order
+ * above and then {Q, 0}.  Both are valid until the next cavmd_coulomb_set_items or cavmd_coulomb_destroy. */
+CAVMD_API int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets);
 
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */

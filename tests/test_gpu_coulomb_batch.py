@@ -1,0 +1,309 @@
+"""Ewald Coulomb forces of a batch of independent small systems in two launches (cavmd_coulomb_*, cavitymd.CoulombForceBatch) on
+the GPU.  Run with `-m gpu` on an MI355X.
+
+The contract is the list of expressions in include/cavmd.h; tests/coulomb_mirror.py restates it in numpy and derives, alongside,
+the rounding bound a correct fp64 evaluation stays within (tests/test_coulomb_abi.py checks that mirror against physics):
+  1. one ragged batch within the mirror's bound, entry by entry, with every edge of the contract planted and counted;
+  2. the rock-salt cell through CoulombForceBatch: the Madelung constant, independent of the mirror;
+  3. systems do not see each other, set_items moves results with the items, and an evaluation repeats bit for bit;
+  4. {step one, cavity, molecular, Coulomb, step two} replayed from a graph against the same steps enqueued eagerly;
+  5. the energy of an NVE run with bonds, Lennard-Jones and Coulomb is conserved to velocity Verlet's second order."""
+import numpy as np
+import pytest
+import torch
+
+import cavitymd
+import coulomb_mirror as mirror
+from cavitymd import _capi, synthetic
+from test_gpu_molecular_batch import HARMONIC, LJ, KT, _same, _stream, _thermal
+
+pytestmark = pytest.mark.gpu
+
+MADELUNG = 1.7475645946331822
+
+
+# ---- 1. one ragged batch --------------------------------------------------------------------------------------------------------
+R_CUT, KAPPA = 3.0, 1.0
+
+
+def _ragged_system(k, n, K, rng):
+    """Host arrays of item k: random wrapped positions and charges in a box with three different lengths (Lx = 8 exactly; Ly
+    and Lz stretched until a k_cut keeps exactly K vectors), and as many of the planted edges as the system has particles for."""
+    box, k_cut = mirror.box_and_k_cut_for((8.0, 10.0 + 2.0 * (k % 2), 16.0), K)
+    x = rng.uniform(-0.5, 0.5, (n, 3)) * np.array(box)
+    q = rng.uniform(-1.0, 1.0, n)
+    planted = [
+        # (index, position)
+        (0, (0.0, 0.0, 0.0)), (1, (3.0, 0.0, 0.0)),                                # rsq == r_cut^2 exactly: skipped
+        (2, (0.0, 1.0, 5.0)), (3, (np.nextafter(3.0, 0.0), 1.0, 5.0)),             # its neighbour one ulp inside: contributes
+        (4, (-2.0, -3.0, 7.0)), (5, (2.0, -3.0, 7.0)),                             # d == -L/2 seen from 4, +L/2 seen from 5
+        (8, (1.0, 3.0, -5.0)), (9, (1.0, 3.0, -3.8)),                              # excluded inside the cut-off: erf term only
+        (10, (3.5, -1.0, -7.0)), (11, (-3.5, -1.0, -7.0)),                         # an exclusion across the periodic boundary
+        (12, (-1.0, -4.0, 2.0)), (13, (-1.0, -4.0, 3.0)), (14, (-1.0, -3.0, 2.0)), (15, (-2.0, -4.0, 2.0)),
+        (16, (-1.0, -4.0, 1.0)),                                                   # 12 has four exclusions
+    ]
+    for i, pos in planted:
+        if i < n:
+            x[i] = pos
+    for i in (0, 1, 2, 3, 4, 5):                                                   # the edge pairs carry charges that count
+        if i < n:
+            q[i] = 0.5 + 0.1 * i
+    if n > 17:
+        q[17] = 0.0                                                                # a particle without charge
+        q[max(n // 2, 18)] = 0.0
+    ex = [(8, 9), (10, 11), (12, 13), (14, 12), (12, 15), (16, 12)]
+    ex = [e for e in ex if max(e) < n]
+    ex += [(i, i + 1) for i in range(20, n - 1, 7)]                                # ordinary exclusions among the random ones
+    return {"N": n, "K": K, "box": box, "k_cut": k_cut, "x": x, "q": q, "ex": np.array(ex, dtype=np.uint32).reshape(-1, 2)}
+
+
+def test_one_ragged_batch_stays_within_the_mirror_bound():
+    ROWS, S, KROWS, T = _capi.coulomb_order()
+    sizes = (0, 1, 2, ROWS - 1, ROWS, ROWS + 1, 501, 2047, 2048)
+    counts = (0, 1, 4096, KROWS - 1, KROWS, KROWS + 1, 300, 0, 200)
+    rng = np.random.default_rng(20261018)
+    systems = [_ragged_system(k, n, K, rng) for k, (n, K) in enumerate(zip(sizes, counts))]
+    pos, charge, force = [], [], []
+    for s in systems:
+        p = np.zeros((max(s["N"], 1), 4))
+        p[:s["N"], :3] = s["x"]
+        p[:, 3] = 123.0                                                            # .w is ignored
+        pos.append(torch.from_numpy(p).cuda())
+        charge.append(torch.from_numpy(np.concatenate([s["q"], [0.0]])).cuda())
+        force.append(torch.full((max(s["N"], 1), 4), 7.0, dtype=torch.float64, device="cuda"))
+    ws = _capi.Workspace(1)
+    items = [_capi.coulomb_item(s["N"], pos[k].data_ptr() if s["N"] else 0, charge[k].data_ptr() if s["N"] else 0,
+                                force[k].data_ptr() if s["N"] else 0, s["box"], KAPPA, R_CUT, s["k_cut"], s["ex"])
+             for k, s in enumerate(systems)]
+    assert [_capi.coulomb_k_count(it) for it in items] == [0 if s["N"] == 0 else s["K"] for s in systems]
+    batch = _capi.Coulomb(ws, items)
+    assert batch.launch_order == sorted(range(len(sizes)), key=lambda i: -sizes[i])
+    batch.compute(_stream())
+    torch.cuda.synchronize()
+    ptr, offsets = batch.structure_device_ptr()
+    assert ptr and offsets == list(np.cumsum([0] + [(0 if s["N"] == 0 else s["K"]) + 1 for s in systems])[:-1])
+    trace, worst = {}, 0.0
+    for k, s in enumerate(systems):
+        want, bound = mirror.forces(s["x"], s["q"], s["box"], KAPPA, R_CUT, s["k_cut"], s["ex"], trace)
+        got = force[k].cpu().numpy()[:s["N"]]
+        assert got.shape == want.shape and np.isfinite(got).all(), k
+        err = np.abs(got - want)
+        ratio = float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0
+        worst = max(worst, ratio)
+        print(f"\nitem {k}: N = {s['N']}, K = {s['K']}, largest error / bound = {ratio:.4f}, largest error = {err.max() if s['N'] else 0:.3e}")
+        assert (err <= bound).all(), (k, s["N"], s["K"], ratio)
+        if s["N"] == 0:
+            assert (force[k].cpu().numpy() == 7.0).all()                           # an empty item: nothing is written
+        if s["N"] > 17:
+            for i in (17, max(s["N"] // 2, 18)):                                   # no charge: an entry that compares equal to 0
+                assert s["q"][i] == 0.0 and (got[i] == 0.0).all(), (k, i)
+    print(f"\nlargest error / bound of the batch: {worst:.4f}")
+    # every planted edge was met, by every system large enough to carry it
+    big = sum(1 for n in sizes if n > 17)
+    assert trace["rsq_equals_rcutsq"] >= 2 * big and trace["just_inside_cutoff"] >= 2 * big
+    assert trace["d_equals_plus_half"] >= big and trace["d_equals_minus_half"] >= big
+    assert trace["excluded_pair_inside_cutoff"] >= 2 * big and trace["exclusion_across_boundary"] >= 2 * big
+    assert trace["four_exclusions"] >= big and trace["zero_charge"] >= 2 * big
+    # ... and behaved as the contract says: the first four planted particles alone, without a reciprocal part
+    s = systems[sizes.index(501)]
+    F, _ = mirror.forces(s["x"][:4], s["q"][:4], s["box"], KAPPA, R_CUT, 0.0)
+    assert not F[0, :3].any() and not F[1, :3].any()                               # rsq == r_cut^2, and 0-2 / 1-3 are farther
+    assert F[2, 0] != 0.0 and F[2, 0] == -F[3, 0]                                  # one ulp inside: the term is there
+    # the exclusion removes the pair's whole Coulomb interaction: erf term and no erfc term
+    two = mirror.forces(s["x"][8:10], [1.0, 1.0], s["box"], KAPPA, R_CUT, 0.0, [(0, 1)])[0]
+    r = 1.2
+    from scipy.special import erf
+    assert np.isclose(two[:, 3].sum() + 2.0 * KAPPA / mirror.SQRT_PI + np.pi / (np.prod(s["box"]) * KAPPA ** 2) * 2.0,
+                      -erf(KAPPA * r) / r, rtol=1e-13)
+    batch.close()
+    ws.close()
+
+
+# ---- 2. rock salt -----------------------------------------------------------------------------------------------------------------
+def _system(position, charge, box):
+    n = len(charge)
+    pd = cavitymd.ParticleData.from_arrays(np.asarray(position, dtype=np.float64), np.zeros(n, dtype=np.int32), np.asarray(charge),
+                                           np.zeros((n, 3), dtype=np.int32), ["O", "N", "L"], box, device="cuda")
+    return cavitymd.SystemDefinition(pd)
+
+
+def test_rock_salt_gives_the_madelung_constant():
+    g = np.arange(4)
+    ijk = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)
+    q = np.where(ijk.sum(axis=1) % 2 == 0, 1.0, -1.0)
+    coulomb = cavitymd.CoulombForceBatch([_system(ijk - 2.0, q, (4.0, 4.0, 4.0))], None, r_cut=2.0, kappa=2.0, k_cut=18.209)
+    assert coulomb.k_counts == [3309]
+    coulomb.compute()
+    E = float(coulomb.potential_energy()[0])
+    F = coulomb.forces[0].cpu().numpy()
+    madelung = -2.0 * E / 64
+    print(f"\nMadelung constant on the GPU: {madelung!r}, off by {madelung - MADELUNG:.3e}; largest force {np.abs(F[:, :3]).max():.3e}")
+    assert abs(madelung - MADELUNG) <= 2e-7
+    assert np.abs(F[:, :3]).max() < 1e-12
+    assert np.allclose(F[:, 3], F[0, 3], rtol=1e-12)                               # every ion carries the same share
+    coulomb.close()
+    with pytest.raises(ValueError):
+        cavitymd.CoulombForceBatch([_system(ijk - 2.0, q, (4.0, 4.0, 4.0))], None, r_cut=2.0, accuracy=1e-6, kappa=2.0)
+
+
+# ---- 3. independence ------------------------------------------------------------------------------------------------------------
+def _lattice_batch(n_sides, seeds, spacing=8.0):
+    cfgs = [synthetic.diatomic_lattice(n, spacing, seed=s) for n, s in zip(n_sides, seeds)]
+    sysdefs = [cavitymd.SystemDefinition(cavitymd.ParticleData.from_arrays(c["position"], c["typeid"], c["charge"], c["image"],
+                                                                           c["types"], c["box"], device="cuda")) for c in cfgs]
+    bonds = [synthetic.diatomic_bonds(c) for c in cfgs]
+    return cfgs, sysdefs, [b[0] for b in bonds], [b[1] for b in bonds]
+
+
+def test_systems_do_not_see_each_other_and_set_items_moves_results():
+    cfgs, sysdefs, bonds, _ = _lattice_batch((4, 3, 4, 2), (1, 2, 3, 4))
+    coulomb = cavitymd.CoulombForceBatch(sysdefs, bonds, r_cut=8.0, accuracy=1e-4)   # smallest box 16 bohr; largest 32: K = 3000-odd
+    coulomb.compute()
+    clean = [f.cpu().numpy().copy() for f in coulomb.forces]
+    assert all(np.isfinite(f).all() and f[:-1, :3].any() and not f[-1].any() for f in clean)   # the photon has no charge
+    coulomb.compute()                                                              # the same input gives the same bits
+    assert all(_same(f.cpu().numpy(), c) for f, c in zip(coulomb.forces, clean))
+    sysdefs[1].getParticleData().getPositions()[10, 1] = float("nan")
+    coulomb.compute()
+    after = [f.cpu().numpy().copy() for f in coulomb.forces]
+    for k in (0, 2, 3):
+        assert _same(after[k], clean[k]), k
+    assert np.isnan(after[1][:-1, 3]).all()                                        # S(k) carries the NaN to every charge of item 1
+    sysdefs[1].getParticleData().getPositions()[10, 1] = float(cfgs[1]["position"][10, 1])
+    # swap items 0 and 3 (N = 129 and 17), each keeping its slot's force array: the results follow the items
+    n = [len(c["charge"]) for c in cfgs]
+    out = [torch.zeros((129, 4), dtype=torch.float64, device="cuda") for _ in range(2)]
+
+    def item(k, force, ex=None):
+        pd = sysdefs[k].getParticleData()
+        return _capi.coulomb_item(n[k], pd.getPositions().data_ptr(), pd.getCharges().data_ptr(), force.data_ptr(), cfgs[k]["box"],
+                                  coulomb.kappa, coulomb.r_cut, coulomb.k_cut, bonds[k] if ex is None else ex)
+
+    torch.cuda.synchronize()
+    coulomb.coulomb.set_items(0, [item(3, out[0])])
+    coulomb.coulomb.set_items(3, [item(0, out[1])])
+    assert coulomb.coulomb.sizes == [17, 55, 129, 129]
+    coulomb.compute()
+    torch.cuda.synchronize()
+    assert _same(out[0].cpu().numpy()[:17], clean[3]) and _same(out[1].cpu().numpy(), clean[0])
+    assert _same(coulomb.forces[1].cpu().numpy(), clean[1]) and _same(coulomb.forces[2].cpu().numpy(), clean[2])
+    with pytest.raises(_capi.CavmdError) as e:                                     # an index beyond the new N: nothing changes
+        coulomb.coulomb.set_items(0, [item(3, out[0], np.array([[0, 17]]))])
+    assert e.value.status == _capi.CAVMD_ERR_INVALID_VALUE
+    assert coulomb._ws._lib.cavmd_destroy(coulomb._ws.handle) == _capi.CAVMD_ERR_INVALID_VALUE
+    coulomb.compute()
+    torch.cuda.synchronize()
+    assert _same(out[0].cpu().numpy()[:17], clean[3])
+    coulomb.close()
+
+
+# ---- 4. capture -------------------------------------------------------------------------------------------------------------------
+def _md(cfgs, sysdefs, bonds, bond_typeid, r_cut, accuracy):
+    """cavity force, molecular force, Coulomb force and integrator over `sysdefs`, with thermal velocities"""
+    velocities, masses = [], []
+    for c in cfgs:
+        v0, mass = _thermal(c)
+        masses.append(torch.from_numpy(mass).cuda())
+        velocities.append(torch.from_numpy(np.concatenate([v0, mass[:, None]], axis=1)).cuda())
+    cavity = cavitymd.CavityForceBatch(sysdefs, [c["params"] for c in cfgs])
+    lj = {pair: dict(p, r_cut=min(p["r_cut"], r_cut)) for pair, p in LJ.items()}
+    mol = cavitymd.MolecularForceBatch(sysdefs, bonds, bond_typeid, HARMONIC, lj)
+    coulomb = cavitymd.CoulombForceBatch(sysdefs, bonds, r_cut=r_cut, accuracy=accuracy)
+    integrator = cavitymd.VerletBatch(cavity, velocities, extra_forces=[[m, c] for m, c in zip(mol.forces, coulomb.forces)])
+    return cavity, mol, coulomb, integrator, velocities, masses
+
+
+def test_captured_step_replays_like_the_eager_one():
+    STEPS, dt = 8, 10.0
+    results = []
+    for captured in (False, True):
+        cfgs, sysdefs, bonds, bond_typeid = _lattice_batch((3, 2), (11, 12))
+        cavity, mol, coulomb, integrator, velocities, _ = _md(cfgs, sysdefs, bonds, bond_typeid, 8.0, 1e-5)
+        integrator.set_inputs(dt)
+        cavity.compute()
+        mol.compute()
+        coulomb.compute()
+        integrator.prime()
+        torch.cuda.synchronize()
+
+        def step():
+            integrator.step_one()
+            cavity.compute()
+            mol.compute()
+            coulomb.compute()
+            integrator.step_two()
+
+        if captured:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step()
+            assert integrator.state()["steps"].tolist() == [0, 0]                  # capturing ran nothing
+            for _ in range(STEPS):
+                graph.replay()
+        else:
+            for _ in range(STEPS):
+                step()
+        torch.cuda.synchronize()
+        results.append([(sd.getParticleData().getPositions().cpu().numpy().tobytes(), velocities[k].cpu().numpy().tobytes(),
+                         coulomb.forces[k].cpu().numpy().tobytes()) for k, sd in enumerate(sysdefs)])
+        assert integrator.state()["steps"].tolist() == [STEPS] * 2
+        moved = coulomb.forces[0].cpu().numpy()
+        assert np.isfinite(moved).all() and moved[:-1, :3].any()
+        integrator.close()
+        coulomb.close()
+        mol.close()
+        cavity.close()
+    assert results[0] == results[1]
+
+
+# ---- 5. energy ----------------------------------------------------------------------------------------------------------------------
+def _dimers(seed):
+    """12 charged dimers and the photon: the first 12 molecules of a 3 x 3 x 3 lattice, in its 24-bohr box"""
+    c = synthetic.diatomic_lattice(3, 8.0, seed=seed)
+    keep = list(range(24)) + [len(c["charge"]) - 1]
+    c = dict(c, position=c["position"][keep], typeid=c["typeid"][keep], charge=c["charge"][keep], image=c["image"][keep])
+    sysdef = cavitymd.SystemDefinition(cavitymd.ParticleData.from_arrays(c["position"], c["typeid"], c["charge"], c["image"], c["types"],
+                                                                         c["box"], device="cuda"))
+    bonds, bond_typeid = synthetic.diatomic_bonds(c)
+    return c, sysdef, bonds, bond_typeid
+
+
+def test_nve_energy_is_conserved_to_second_order():
+    """NVE, 12 charged dimers plus the photon with bonds, Lennard-Jones and Coulomb (and the cavity force the integrator is
+    built on), no bath, no thermostat; H = KE + the cavity energies + both sums of .w, read eagerly every step.  The drift is
+    max |H(t) - H(0)| over the 200 steps at dt and over the same time (400 steps) at dt / 2: velocity Verlet's second order
+    makes their ratio 4, and the test asks for [3, 5]."""
+    DT, STEPS = 10.0, 200
+    drift = {}
+    for dt, steps in ((DT, STEPS), (0.5 * DT, 2 * STEPS)):
+        c, sysdef, bonds, bond_typeid = _dimers(31)
+        assert len(bonds) == 12 and len(c["charge"]) == 25
+        cavity, mol, coulomb, integrator, velocities, masses = _md([c], [sysdef], [bonds], [bond_typeid], 12.0, 1e-8)
+
+        def hamiltonian():
+            ke = 0.5 * (masses[0] * (velocities[0][:, :3] ** 2).sum(dim=1)).sum()
+            return float(ke) + float(cavity.energies().sum()) + float(mol.potential_energy()[0]) + float(coulomb.potential_energy()[0])
+
+        integrator.set_inputs(dt)
+        cavity.compute()
+        mol.compute()
+        coulomb.compute()
+        integrator.prime()
+        H = [hamiltonian()]
+        for _ in range(steps):
+            integrator.step_one()
+            cavity.compute()
+            mol.compute()
+            coulomb.compute()
+            integrator.step_two()
+            H.append(hamiltonian())
+        H = np.array(H)
+        drift[dt] = float(np.abs(H - H[0]).max())
+        assert integrator.state()["out_of_box"].tolist() == [0] and np.isfinite(H).all()
+        integrator.close()
+        coulomb.close()
+        mol.close()
+        cavity.close()
+    ratio = drift[DT] / drift[0.5 * DT]
+    print(f"\nenergy drift over {STEPS} steps at dt = {DT}: {drift[DT]:.4e}; at dt / 2: {drift[0.5 * DT]:.4e}; ratio {ratio:.4f}")
+    assert 3.0 <= ratio <= 5.0, (drift, ratio)
