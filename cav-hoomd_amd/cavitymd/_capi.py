@@ -317,6 +317,9 @@ def build(force: bool = False) -> str:
         subprocess.run(["make", "-C", CSRC_DIR, "-s", "libcavmd.so"] + (["-B"] if force else []), check=True)
     # the same library with the test hooks compiled in (fault injection; loaded by tests only, see load_hooks_build)
     subprocess.run(["make", "-C", CSRC_DIR, "-s", "libcavmd_hooks.so"], check=True)
+    # the product library with the lane splits the default build does not cover (loaded by tests only, see load_split_variant);
+    # make rebuilds each only when stale
+    subprocess.run(["make", "-C", CSRC_DIR, "-s", "-j3", "split_variants"], check=True)
     # the pybind11 flavour of the shim (cavitymd._cavitymd); make rebuilds it only when stale
     subprocess.run(["make", "-C", CSRC_DIR, "-s", "pymod"], check=True)
     return LIB_PATH
@@ -350,6 +353,29 @@ def load_hooks_build():
                 raise ImportError(f"{HOOKS_LIB_PATH} is missing: build it with `make -C {CSRC_DIR} hooks`")
             _hooks_lib = _declare(ctypes.CDLL(HOOKS_LIB_PATH))
         return _hooks_lib
+
+
+# name -> (CAVMD_MOLECULAR_J_SPLIT, CAVMD_COULOMB_J_SPLIT, CAVMD_COULOMB_K_SPLIT) of libcavmd_split_<name>.so (csrc/Makefile)
+SPLIT_VARIANTS = {"a": (1, 1, 1), "b": (4, 4, 16), "c": (16, 64, 64)}
+_split_libs = {}
+
+
+def split_variant_path(name: str) -> str:
+    if name not in SPLIT_VARIANTS:
+        raise ValueError(f"no split variant {name!r}: one of {sorted(SPLIT_VARIANTS)}")
+    return os.path.join(CSRC_DIR, f"libcavmd_split_{name}.so")
+
+
+def load_split_variant(name: str):
+    """TESTS ONLY: libcavmd_split_<name>.so, the same sources compiled with other lane splits (SPLIT_VARIANTS), so that every
+    value include/cavmd.h allows runs in some test.  The product path never loads one."""
+    path = split_variant_path(name)
+    with _lock:
+        if name not in _split_libs:
+            if not os.path.exists(path):
+                raise ImportError(f"{path} is missing: build it with `make -C {CSRC_DIR} split_variants`")
+            _split_libs[name] = _declare(ctypes.CDLL(path))
+        return _split_libs[name]
 
 
 def _declare(lib):
@@ -623,10 +649,13 @@ def _destroy_deferred_outside_capture() -> None:
 class Workspace:
     """Owns one cavmd_workspace (scratch for partial sums + the 192-byte result block)."""
 
-    def __init__(self, max_N: int, device: int = -1, hooks: bool = False):
+    def __init__(self, max_N: int, device: int = -1, hooks: bool = False, lib=None):
+        """lib: TESTS ONLY, a library loaded by load_split_variant; what is created from the workspace runs that build."""
         if not _capturing():
             _destroy_deferred()
-        self._lib = load_hooks_build() if hooks else load()
+        if lib is not None and hooks:
+            raise ValueError("either the hooks build or a given library")
+        self._lib = lib if lib is not None else (load_hooks_build() if hooks else load())
         self._h = ctypes.c_void_p()
         check(self._lib.cavmd_create(int(device), int(max_N), ctypes.byref(self._h)), "cavmd_create")
         self.max_N = int(max_N)
@@ -1162,11 +1191,11 @@ class Verlet(_ItemTableHandle):
         return int(p.value)
 
 
-def molecular_order():
+def molecular_order(lib=None):
     """(ROWS, S): the particles a workgroup of the molecular force kernel owns and the partial sums per particle, as the
     library was compiled (S = CAVMD_MOLECULAR_J_SPLIT fixes the published summation order)."""
     rows, split = ctypes.c_int(), ctypes.c_int()
-    check(load().cavmd_molecular_order(ctypes.byref(rows), ctypes.byref(split)), "cavmd_molecular_order")
+    check((lib or load()).cavmd_molecular_order(ctypes.byref(rows), ctypes.byref(split)), "cavmd_molecular_order")
     return int(rows.value), int(split.value)
 
 

@@ -873,9 +873,13 @@ CAVMD_API int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_
 CAVMD_API int cavmd_molecular_destroy(cavmd_molecular* m);
 /* Replaces rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
  * changed if a row is refused.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the
- * batch.  A launch captured BEFORE the call keeps its number of workgroups and its LDS size: on replay it evaluates the new
- * table as far as its workgroups reach and fills the forces of a system larger than its LDS with NaN; capture again after a
- * call that changes the sizes. */
+ * batch.  A launch captured BEFORE the call keeps its number of workgroups and its LDS size (that of the largest N it was
+ * captured with).  On replay it walks the NEW workgroup table (items by N descending, ties in item order, ceil(N / ROWS)
+ * workgroups each) from the front as far as its captured number of workgroups reaches: the rows of the force arrays those
+ * workgroups own are written -- NaN in all four components for a system larger than the captured LDS, never an out-of-bounds
+ * access -- and every other entry is left as it was; workgroups beyond the new table do nothing.  The replay is right in full
+ * when no item needs more workgroups or more LDS than the launch was captured with; capture again after a call that changes
+ * the sizes.  A replay is not a launch the library knows of: the caller waits for replays in flight before this call. */
 CAVMD_API int cavmd_molecular_set_items(cavmd_molecular* m, size_t first, size_t count, const cavmd_molecular_item* h_items);
 /* Enqueues exactly ONE kernel on `stream`: no allocation, no copy, no host wait; may be captured into a hipGraph.  One batch
  * serves one host thread and one stream at a time. */
@@ -965,9 +969,17 @@ CAVMD_API int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const ca
 CAVMD_API int cavmd_coulomb_destroy(cavmd_coulomb* c);
 /* Replaces rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
  * changed if a row is refused.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the
- * batch.  Launches captured BEFORE the call keep their numbers of workgroups and their LDS size: on replay they evaluate the new
- * tables as far as their workgroups reach and fill the forces of a system larger than their LDS with NaN; capture again after
- * a call that changes N or K. */
+ * batch.  Launches captured BEFORE the call keep their numbers of workgroups and their LDS size (that of the largest N they
+ * were captured with).  On replay each walks its NEW workgroup table (items by N descending, ties in item order; ceil(K / KROWS)
+ * workgroups each in launch 1, ceil(N / ROWS) in launch 2) from the front as far as its captured number of workgroups reaches;
+ * workgroups beyond the new table do nothing.  Launch 2 writes the rows of the force arrays its workgroups own -- NaN in all
+ * four components for a system larger than the captured LDS (launch 1 gives it NaN structure factors), never an out-of-bounds
+ * access -- and leaves every other entry as it was.  Launch 1 writes the S(k) slots its workgroups own; a slot it does not
+ * reach keeps the 0 this call allocates the table with, so after a call that RAISES a K the forces of an item with such a
+ * slot are finite and are NOT the Ewald sum: its k-sum is short, and nothing flags it.  The replay is right in full when no
+ * item needs more workgroups in either launch or more LDS than the launches were captured with (a smaller N or K is fine);
+ * capture again after a call that changes N or K.  A replay is not a launch the library knows of: the caller waits for
+ * replays in flight before this call. */
 CAVMD_API int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items);
 /* Enqueues exactly TWO kernels on `stream`: no allocation, no copy, no host wait; may be captured into a hipGraph.  One batch
  * serves one host thread and one stream at a time. */

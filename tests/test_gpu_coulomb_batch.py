@@ -8,6 +8,8 @@ the rounding bound a correct fp64 evaluation stays within (tests/test_coulomb_ab
   3. systems do not see each other, set_items moves results with the items, and an evaluation repeats bit for bit;
   4. {step one, cavity, molecular, Coulomb, step two} replayed from a graph against the same steps enqueued eagerly;
   5. the energy of an NVE run with bonds, Lennard-Jones and Coulomb is conserved to velocity Verlet's second order."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -57,10 +59,16 @@ def _ragged_system(k, n, K, rng):
     return {"N": n, "K": K, "box": box, "k_cut": k_cut, "x": x, "q": q, "ex": np.array(ex, dtype=np.uint32).reshape(-1, 2)}
 
 
-def test_one_ragged_batch_stays_within_the_mirror_bound():
-    ROWS, S, KROWS, T = _capi.coulomb_order()
-    sizes = (0, 1, 2, ROWS - 1, ROWS, ROWS + 1, 501, 2047, 2048)
-    counts = (0, 1, 4096, KROWS - 1, KROWS, KROWS + 1, 300, 0, 200)
+def _k_count(lib, item) -> int:
+    K = ctypes.c_uint32()
+    _capi.check(lib.cavmd_coulomb_k_count(ctypes.byref(item), ctypes.byref(K)), "cavmd_coulomb_k_count")
+    return int(K.value)
+
+
+def ragged_batch_stays_within_the_mirror_bound(lib, sizes, counts, repeat=False):
+    """One batch of systems of `sizes` particles (501 among them) and `counts` kept k-vectors, created on the loaded library
+    `lib`, entry by entry within the mirror's bound -> the largest error / bound.  repeat: a second compute on unchanged input
+    must repeat the first bit for bit."""
     rng = np.random.default_rng(20261018)
     systems = [_ragged_system(k, n, K, rng) for k, (n, K) in enumerate(zip(sizes, counts))]
     pos, charge, force = [], [], []
@@ -71,11 +79,11 @@ def test_one_ragged_batch_stays_within_the_mirror_bound():
         pos.append(torch.from_numpy(p).cuda())
         charge.append(torch.from_numpy(np.concatenate([s["q"], [0.0]])).cuda())
         force.append(torch.full((max(s["N"], 1), 4), 7.0, dtype=torch.float64, device="cuda"))
-    ws = _capi.Workspace(1)
+    ws = _capi.Workspace(1, lib=lib)
     items = [_capi.coulomb_item(s["N"], pos[k].data_ptr() if s["N"] else 0, charge[k].data_ptr() if s["N"] else 0,
                                 force[k].data_ptr() if s["N"] else 0, s["box"], KAPPA, R_CUT, s["k_cut"], s["ex"])
              for k, s in enumerate(systems)]
-    assert [_capi.coulomb_k_count(it) for it in items] == [0 if s["N"] == 0 else s["K"] for s in systems]
+    assert [_k_count(lib, it) for it in items] == [0 if s["N"] == 0 else s["K"] for s in systems]
     batch = _capi.Coulomb(ws, items)
     assert batch.launch_order == sorted(range(len(sizes)), key=lambda i: -sizes[i])
     batch.compute(_stream())
@@ -100,6 +108,7 @@ def test_one_ragged_batch_stays_within_the_mirror_bound():
     print(f"\nlargest error / bound of the batch: {worst:.4f}")
     # every planted edge was met, by every system large enough to carry it
     big = sum(1 for n in sizes if n > 17)
+    assert sum(1 for n in sizes if n > 19) >= 2                                    # or the counts below would ask for nothing
     assert trace["rsq_equals_rcutsq"] >= 2 * big and trace["just_inside_cutoff"] >= 2 * big
     assert trace["d_equals_plus_half"] >= big and trace["d_equals_minus_half"] >= big
     assert trace["excluded_pair_inside_cutoff"] >= 2 * big and trace["exclusion_across_boundary"] >= 2 * big
@@ -115,8 +124,20 @@ def test_one_ragged_batch_stays_within_the_mirror_bound():
     from scipy.special import erf
     assert np.isclose(two[:, 3].sum() + 2.0 * KAPPA / mirror.SQRT_PI + np.pi / (np.prod(s["box"]) * KAPPA ** 2) * 2.0,
                       -erf(KAPPA * r) / r, rtol=1e-13)
+    if repeat:
+        first = [f.cpu().numpy() for f in force]
+        batch.compute(_stream())
+        torch.cuda.synchronize()
+        assert all(_same(f.cpu().numpy(), g) for f, g in zip(force, first))
     batch.close()
     ws.close()
+    return worst
+
+
+def test_one_ragged_batch_stays_within_the_mirror_bound():
+    ROWS, S, KROWS, T = _capi.coulomb_order()
+    ragged_batch_stays_within_the_mirror_bound(_capi.load(), (0, 1, 2, ROWS - 1, ROWS, ROWS + 1, 501, 2047, 2048),
+                                               (0, 1, 4096, KROWS - 1, KROWS, KROWS + 1, 300, 0, 200))
 
 
 # ---- 2. rock salt -----------------------------------------------------------------------------------------------------------------

@@ -86,16 +86,17 @@ def _pos4(s):
     return pos
 
 
-def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
-    ROWS, S = _capi.molecular_order()
-    sizes = (0, 1, 2, ROWS - 1, ROWS, ROWS + 1, 501, 2047, 2048)
+def ragged_batch_equals_the_mirror_bit_for_bit(lib, sizes, repeat=False):
+    """One batch of systems of `sizes` particles (501 among them), created on the loaded library `lib`, against the mirror run
+    with that build's S.  repeat: a second compute on unchanged input must repeat the first bit for bit."""
+    S = _capi.molecular_order(lib)[1]
     rng = np.random.default_rng(20241018)
     prm = _ragged_params()
     tab = mirror.tables(prm)
     systems = [_ragged_system(k, n, rng) for k, n in enumerate(sizes)]
     pos = [torch.from_numpy(_pos4(s)).cuda() for s in systems]
     force = [torch.full((max(s["N"], 1), 4), 7.0, dtype=torch.float64, device="cuda") for s in systems]
-    ws = _capi.Workspace(1)
+    ws = _capi.Workspace(1, lib=lib)
     batch = _capi.Molecular(ws, prm, [_capi.molecular_item(s["N"], pos[k].data_ptr() if s["N"] else 0,
                                                            force[k].data_ptr() if s["N"] else 0, s["box"], s["bonds"])
                                       for k, s in enumerate(systems)])
@@ -115,6 +116,7 @@ def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
                 assert s["t"][i] in (7, -1, PHOTON) and not got[i].any(), (k, i)
     # every planted edge was met, by every system large enough to carry it
     big = sum(1 for n in sizes if n > 19)
+    assert big >= 2                                                              # or the counts below would ask for nothing
     assert trace["rsq_equals_rcutsq"] >= 2 * big and trace["just_inside_cutoff"] >= 2 * big
     assert trace["d_equals_plus_half"] >= big and trace["d_equals_minus_half"] >= big
     assert trace["bonded_pair_inside_cutoff"] >= 2 * big and trace["bond_across_boundary"] >= 3 * big
@@ -125,8 +127,18 @@ def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
     F = mirror.forces(only["x"], only["t"], only["box"], tab, only["bonds"], S)
     assert not F[0].any() and not F[1].any()                                     # rsq == rcutsq, and 0-2 / 1-3 are farther
     assert F[2, 0] != 0.0 and F[2, 0] == -F[3, 0]                                 # one ulp inside: the term is there
+    if repeat:
+        first = [f.cpu().numpy() for f in force]
+        batch.compute(_stream())
+        torch.cuda.synchronize()
+        assert all(_same(f.cpu().numpy(), g) for f, g in zip(force, first))
     batch.close()
     ws.close()
+
+
+def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
+    ROWS, S = _capi.molecular_order()
+    ragged_batch_equals_the_mirror_bit_for_bit(_capi.load(), (0, 1, 2, ROWS - 1, ROWS, ROWS + 1, 501, 2047, 2048))
 
 
 # ---- 2. known answers -------------------------------------------------------------------------------------------------------------
