@@ -705,6 +705,15 @@ CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cav
  *     6. v_c = v_c + (0.5 * a_c) * dt
  *     7. steps += 1
  *   cavmd_verlet_accelerations is 1, 2, 3 and 5 only: no Langevin, no kick, nothing counted, no input row.
+ * What item 4 amounts to.  `uniform` must be FRESH for every step and every item: three new variates, uniform in [-1, 1)
+ * (mean 0, variance 1/3), independent of the item's velocity; variates from [0, 1), or the same three on every step, integrate
+ * without any sign of trouble and heat the particle to several kT.  For a particle of mass m that feels no force but the bath,
+ * with x = langevin_gamma * dt / (2 m), 0 < x < 1, the stationary state has, per component:
+ *     after step two   m <v^2> = kT, for any dt        (the kick is v' = (1 - x) v + n with <n^2> = x kT / m)
+ *     after step one   m <v^2> (1 - x) = kT            (the half-step velocity, the one item 4 reads)
+ *     langevin_reservoir grows by 3 gamma kT dt / (m (1 - x)) per step on average, because the tally is taken with the
+ *     velocity from BEFORE the kick, with which the step's variates are uncorrelated.
+ * (tests/langevin_twin.py derives the three; tests/test_gpu_langevin_batch.py holds the kernels to them.)
  * pos.w (the type tag) and vel.w (the mass) are never written.  Out of scope: Langevin on more than one particle per system
  * (3 N variates per step), rotational degrees of freedom, triclinic boxes. */
 typedef struct cavmd_verlet_item         /* 128 B; all pointers DEVICE pointers; the arrays of one item must not overlap */

@@ -1,0 +1,87 @@
+"""A free particle in the Langevin bath of include/cavmd.h (velocity-Verlet section, step two, item 4): a numpy twin of the run
+and the three closed forms it must reproduce.  What tests/test_langevin_twin.py checks on the host, and where the acceptance
+band of tests/test_gpu_langevin_batch.py comes from.
+
+The step itself is NOT restated here: it is ``mirror_step_one`` / ``mirror_step_two`` of tests/test_gpu_verlet_batch.py, the
+numpy mirror that the kernels are pinned to bit for bit.  Those functions are element-wise, so the whole ensemble goes through
+them at once: one "system" of N = 1 particle whose arrays carry a trailing axis of E independent members (``vel`` is
+(1, 4, E), ``uniform`` is (3, E), ``reservoir`` is (E,)).  Only the variates and the coefficient sqrt(6 gamma kT / dt) are
+this file's, both in numpy.
+
+The closed forms.  No force but the bath, mass m, x = gamma dt / (2 m), 0 < x < 1, per component, with <u^2> = 1/3 for u
+uniform in [-1, 1) and n = u coeff dt / (2 m), <n^2> = (6 gamma kT / dt) dt^2 / (12 m^2) = x kT / m:
+    step two   v' = h + (0.5 a) dt with a = (u coeff - gamma h) / m             =>  v' = (1 - x) h + n
+    step one   h' = v' + (0.5 a) dt with the same a, (0.5 a) dt = v' - h        =>  h' = (1 - 2 x) h + 2 n
+    stationary <h^2> = (1 - 2 x)^2 <h^2> + 4 x kT / m                          =>  <h^2> = (kT / m) / (1 - x)          (2)
+               <v'^2> = (1 - x)^2 <h^2> + x kT / m = (kT / m) ((1 - x) + x)    =>  m <v'^2> = kT for any dt            (1)
+    reservoir  -tally dt = -(bd . h) dt, bd_c = u_c coeff - gamma h_c, and u is drawn after h, <u h> = 0
+                                                                               =>  + 3 gamma <h^2> dt per step         (3)
+"""
+from types import SimpleNamespace
+
+import numpy as np
+
+from test_gpu_verlet_batch import mirror_step_one, mirror_step_two
+
+# the parameters of the issue's rehearsal; the GPU test uses the same, so that the band carries over
+KT, MASS, DT, GAMMA = 3.167e-4, 2.0, 4.0, 0.25
+MEMBERS, BURN_IN, COUNTED = 256, 64, 512
+BOX = (40.0, 40.0, 40.0)
+MISTAKES = ("variates_in_0_1", "same_variates_every_step", "tally_with_post_kick_velocity")
+
+
+def x_of(gamma=GAMMA, dt=DT, m=MASS) -> float:
+    return gamma * dt / (2.0 * m)
+
+
+def closed_forms(kT=KT, m=MASS, dt=DT, gamma=GAMMA):
+    """-> (<v^2> after step two, <v^2> after step one, growth of langevin_reservoir per step), the first two per component"""
+    x = x_of(gamma, dt, m)
+    assert 0.0 < x < 1.0
+    return kT / m, kT / (m * (1.0 - x)), 3.0 * gamma * kT * dt / (m * (1.0 - x))
+
+
+def ratios(sum_v2_full, sum_v2_half, samples, reservoir_gain, steps, kT=KT, m=MASS, dt=DT, gamma=GAMMA) -> np.ndarray:
+    """Measured over closed form, for the three.  sum_v2_*: sums of v_c^2 over `samples` (members x steps x 3 components);
+    reservoir_gain: mean over the members of what langevin_reservoir gained in `steps` steps."""
+    full, half, rate = closed_forms(kT, m, dt, gamma)
+    return np.array([sum_v2_full / samples / full, sum_v2_half / samples / half, reservoir_gain / steps / rate])
+
+
+def run(seed, mistake=None, members=MEMBERS, burn_in=BURN_IN, counted=COUNTED, kT=KT, m=MASS, dt=DT, gamma=GAMMA) -> np.ndarray:
+    """`members` free particles from rest through burn_in + counted steps -> the three ratios over the counted steps."""
+    assert mistake is None or mistake in MISTAKES
+    rng = np.random.default_rng(seed)
+    E = members
+    vel = np.zeros((1, 4, E))
+    vel[:, 3] = m
+    s = {"N": 1, "box": BOX, "pos": np.zeros((1, 4, E)), "vel": vel, "image": np.zeros((1, 3, E), dtype=np.int32),
+         "forces": [np.zeros((1, 4, E))], "net": None, "accel": np.zeros((1, 3, E)), "langevin": 0, "steps": 0, "out_of_box": 0,
+         "reservoir": np.zeros(E)}
+    row = SimpleNamespace(dt=dt, langevin_gamma=gamma, langevin_coeff=np.sqrt(6.0 * gamma * kT / dt), uniform=None, skip=0)
+    frozen = 2.0 * rng.random((3, E)) - 1.0
+    post_kick_reservoir = np.zeros(E)
+    sums = np.zeros(2)
+    start = None
+    for step in range(burn_in + counted):
+        if step == burn_in:
+            sums[:] = 0.0
+            start = (post_kick_reservoir if mistake == "tally_with_post_kick_velocity" else s["reservoir"]).copy()
+        if mistake == "variates_in_0_1":
+            row.uniform = rng.random((3, E))
+        elif mistake == "same_variates_every_step":
+            row.uniform = frozen
+        else:
+            row.uniform = 2.0 * rng.random((3, E)) - 1.0           # as VerletBatch.draw_inputs forms them
+        mirror_step_one(s, row)
+        half = s["vel"][0, :3].copy()
+        sums[1] += float((half * half).sum())
+        mirror_step_two(s, row)
+        full = s["vel"][0, :3]
+        sums[0] += float((full * full).sum())
+        if mistake == "tally_with_post_kick_velocity":              # the planted tally: bd . v with v from AFTER the kick
+            bd = row.uniform * row.langevin_coeff - gamma * half
+            post_kick_reservoir = post_kick_reservoir - (bd * full).sum(axis=0) * dt
+    assert s["steps"] == burn_in + counted and s["out_of_box"] == 0
+    end = post_kick_reservoir if mistake == "tally_with_post_kick_velocity" else s["reservoir"]
+    return ratios(sums[0], sums[1], 3 * E * counted, float((end - start).mean()), counted, kT, m, dt, gamma)
