@@ -829,22 +829,22 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What Batch, BussiBatch, Recorder and FieldRecorder share: a handle created from a workspace (kept alive here) over a
-    table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
+    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Molecular and Coulomb share: a handle created from a workspace
+    (kept alive here) over a table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
     the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
     _PREFIX = None  # entry points <prefix>_create, <prefix>_destroy, <prefix>_set_items
     _size = None    # item -> the size key of the launch order
 
-    def _create(self, workspace: Workspace, items, *args) -> None:
-        """<prefix>_create(workspace, n_items, items, *args, &handle)"""
+    def _create(self, workspace: Workspace, items, *args, before=()) -> None:
+        """<prefix>_create(workspace, *before, n_items, items, *args, &handle)"""
         self._ws = workspace
         self._lib = workspace._lib
         items = list(items)
         self.n_items = len(items)
         self.sizes = [self._size(it) for it in items]
         self._h = ctypes.c_void_p()
-        check(getattr(self._lib, self._PREFIX + "_create")(workspace.handle, self.n_items, self._array(items), *args,
+        check(getattr(self._lib, self._PREFIX + "_create")(workspace.handle, *before, self.n_items, self._array(items), *args,
                                                             ctypes.byref(self._h)), self._PREFIX + "_create")
 
     def _array(self, items):
@@ -1243,14 +1243,7 @@ class Molecular(_ItemTableHandle):
 
     def __init__(self, workspace: Workspace, params: MolecularParams, items):
         self.params = params
-        self._ws = workspace
-        self._lib = workspace._lib
-        items = list(items)
-        self.n_items = len(items)
-        self.sizes = [self._size(it) for it in items]
-        self._h = ctypes.c_void_p()
-        check(self._lib.cavmd_molecular_create(workspace.handle, ctypes.byref(params), self.n_items, self._array(items),
-                                               ctypes.byref(self._h)), "cavmd_molecular_create")
+        self._create(workspace, items, before=(ctypes.byref(params),))
 
     def compute(self, stream: int = 0) -> None:
         """One kernel: every entry of every item's force array."""

@@ -20,46 +20,30 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import stream_handle
+from ._force_batch import ForceBatchBase
 
 
-class CoulombForceBatch:
+class CoulombForceBatch(ForceBatchBase):
     """sysdefs: the systems (positions, charges -- ``getCharges()`` -- and boxes are taken from them; all on one GPU);
     exclusions: per system an (n, 2) integer array of pairs whose Coulomb interaction is removed (the bonds), or None;
     r_cut: the real-space cut-off, at most half the shortest box length; then either ``accuracy`` (kappa and k_cut follow from
-    ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``."""
+    ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``.  ``compute`` is TWO kernels; column 3 of a force array is the
+    particle's share of the Coulomb energy."""
 
     def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None):
-        self._sysdefs = list(sysdefs)
-        if not self._sysdefs:
-            raise ValueError("a batch needs at least one system")
-        pds = [s.getParticleData() for s in self._sysdefs]
-        for pd in pds:
-            for t in (pd.getPositions(), pd.getCharges()):
-                if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-                    raise RuntimeError("CoulombForceBatch needs the position and charge arrays in GPU memory; no CPU fallback "
-                                       "exists in this package")
+        pds = self._systems(sysdefs)
+        self._need_gpu(pds, lambda pd: (pd.getPositions(), pd.getCharges()), "position and charge")
         if (accuracy is None) == (kappa is None or k_cut is None) or (accuracy is not None and (kappa is not None or k_cut is not None)):
             raise ValueError("give either accuracy or both kappa and k_cut")
         if accuracy is not None:
             kappa, k_cut = _capi.coulomb_parameters(r_cut, accuracy)
         self.r_cut, self.kappa, self.k_cut = float(r_cut), float(kappa), float(k_cut)
-        dev = pds[0].device
-        if any(pd.device != dev for pd in pds):
-            raise ValueError("all systems of one batch live on one device")
+        self._one_device(pds)
         B = len(pds)
         exclusions = [None] * B if exclusions is None else list(exclusions)
         if len(exclusions) != B:
             raise ValueError(f"exclusions: one array per system ({B})")
-        self._device = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-        sizes = [pd.getN() for pd in pds]
-        self._sizes = sizes
-        # one allocation behind all force arrays: the energy is then one segmented sum
-        self._pool = torch.zeros((max(sum(sizes), 1), 4), dtype=torch.float64, device=dev)
-        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self._force = [self._pool[int(starts[k]):int(starts[k + 1])] for k in range(B)]
-        self._lengths = torch.tensor(sizes, dtype=torch.int64, device=dev)
+        sizes = self._allocate(pds)
         self._charges = []
         items = []
         for k, pd in enumerate(pds):
@@ -83,52 +67,8 @@ class CoulombForceBatch:
                     raise ValueError(f"system {k}: k_cut = {self.k_cut:.4g} keeps more than {_capi.COULOMB_MAX_K} k-vectors in its box; "
                                      "ask for a coarser accuracy or a larger r_cut") from e
                 raise
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        self._coulomb = _capi.Coulomb(self._ws, items)
-        self.n_systems = B
-        torch.cuda.current_stream(dev).synchronize()   # the zeroed pool is there before any stream computes
-
-    def __len__(self) -> int:
-        return self.n_systems
-
-    def _need(self):
-        if self._coulomb is None:
-            raise RuntimeError("CoulombForceBatch used after close()")
-
-    def compute(self, timestep: int = 0, stream=None) -> None:
-        """TWO kernels on ``stream`` (default: torch's current stream): every entry of every system's force array.  May be
-        captured.  ``timestep`` is accepted for signature compatibility with ``CavityForceBatch.compute``; it is not used."""
-        self._need()
-        self._coulomb.compute(stream_handle(stream, self._device))
-
-    @property
-    def forces(self):
-        """Per-system (N_k, 4) float64 device tensors: force in columns 0-2, the particle's share of the Coulomb energy in
-        column 3."""
-        return list(self._force)
-
-    def potential_energy(self) -> torch.Tensor:
-        """(B,) device tensor: the Coulomb energy of every system, the sum of its ``.w`` column, ordered on torch's current
-        stream (the kernels keep no totals across workgroups)."""
-        self._need()
-        w = self._pool[:sum(self._sizes), 3]
-        if len(set(self._sizes)) == 1 and self._sizes[0] > 0:
-            return w.reshape(self.n_systems, self._sizes[0]).sum(dim=1)
-        return torch.segment_reduce(w.contiguous(), "sum", lengths=self._lengths)
+        self._open(lambda ws: _capi.Coulomb(ws, items))
 
     @property
     def coulomb(self) -> _capi.Coulomb:
-        return self._coulomb
-
-    def close(self) -> None:
-        if getattr(self, "_coulomb", None) is not None:
-            self._coulomb.close()
-        if getattr(self, "_ws", None) is not None:
-            self._ws.close()
-        self._coulomb = self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._handle

@@ -151,12 +151,7 @@ struct cavmd_workspace
     uint64_t bussi_sequence = 0;
     uint64_t bussi_refused_seen = 0;  // refusals already reported to the caller
     hipStream_t bussi_stream = nullptr; // stream of the last enqueued step: the one whose idleness ends a wait for its flag
-    unsigned bussi_batches = 0;         // live cavmd_bussi_batch objects created from this workspace (cavmd_destroy refuses)
-    unsigned recorders = 0;             // live cavmd_recorder objects created from this workspace (the same)
-    unsigned field_recorders = 0;       // live cavmd_field_recorder objects created from this workspace (the same)
-    unsigned verlets = 0;               // live cavmd_verlet objects created from this workspace (the same)
-    unsigned moleculars = 0;            // live cavmd_molecular objects created from this workspace (the same)
-    unsigned coulombs = 0;              // live cavmd_coulomb objects created from this workspace (the same)
+    unsigned dependents = 0;            // live objects created from this workspace (ItemTable::attach): cavmd_destroy refuses
 };
 
 namespace
@@ -585,17 +580,7 @@ int cavmd_destroy(cavmd_workspace* ws)
 {
     if (!ws)
         return CAVMD_OK;
-    if (ws->bussi_batches != 0) // a thermostat batch outlives nothing of its workspace: destroy the batches first
-        return CAVMD_ERR_INVALID_VALUE;
-    if (ws->recorders != 0)     // nor does a recorder
-        return CAVMD_ERR_INVALID_VALUE;
-    if (ws->field_recorders != 0) // nor a field recorder
-        return CAVMD_ERR_INVALID_VALUE;
-    if (ws->verlets != 0)         // nor an integrator
-        return CAVMD_ERR_INVALID_VALUE;
-    if (ws->moleculars != 0)      // nor a molecular force batch
-        return CAVMD_ERR_INVALID_VALUE;
-    if (ws->coulombs != 0)        // nor a Coulomb force batch
+    if (ws->dependents != 0) // a thermostat batch, recorder, integrator or force batch outlives nothing of its workspace
         return CAVMD_ERR_INVALID_VALUE;
     DeviceGuard guard(ws->device);
     for (hipEvent_t ev : ws->events)
@@ -1671,7 +1656,7 @@ int cavmd_version(void)
 // nothing else.
 } // extern "C"
 
-#include "cavmd_item_table.hpp" // how the table of the four batch objects below lives on the host and on the device
+#include "cavmd_item_table.hpp" // how the tables of the seven objects below live on the host and on the device
 
 namespace
 {
@@ -1779,12 +1764,7 @@ int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_it
 
 int cavmd_batch_destroy(cavmd_batch* b)
 {
-    if (!b)
-        return CAVMD_OK;
-    DeviceGuard guard(b->device);
-    b->quiesce_and_free();
-    delete b; // the results and the ring go with their owners
-    return CAVMD_OK;
+    return destroy_table(b);
 }
 
 int cavmd_batch_set_items(cavmd_batch* b, size_t first, size_t count, const cavmd_batch_item* h_items)
@@ -1802,8 +1782,8 @@ int cavmd_batch_compute(cavmd_batch* b, void* stream_)
         b->captured = true;
     b->sequence += 1;
     HostResult* host = b->h_ring.dev + (b->sequence % b->depth) * b->n;
-    hipLaunchKernelGGL(cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, stream, b->d_rows,
-                       b->d_order, b->sequence, b->d_result.ptr, host);
+    hipLaunchKernelGGL(cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, stream, b->d_rows.ptr,
+                       b->d_order.ptr, b->sequence, b->d_result.ptr, host);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
     {
@@ -1924,7 +1904,6 @@ int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out)
 // ---- the Bussi thermostat step of a batch of independent small systems in one launch (cavmd_bussi_batch_kernel.hpp) ---------
 struct cavmd_bussi_batch : ItemTable<cavmd_bussi_batch_item, BussiBatchRow> // launched by n_members descending
 {
-    cavmd_workspace* ws = nullptr;
     std::vector<uint64_t> refused_seen;        // per item: refusals already reported to the caller
     DeviceArray<BussiDevice> d_state;          // n states, indexed by item
     MappedBlock<HostBussiBatch> h_blocks;      // n blocks, indexed by item
@@ -2025,22 +2004,14 @@ int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bu
         cavmd_bussi_batch_destroy(b);
         return (int)e;
     }
-    b->ws = ws;
-    ws->bussi_batches += 1;
+    b->attach(ws);
     *out = b;
     return CAVMD_OK;
 }
 
 int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
 {
-    if (!b)
-        return CAVMD_OK;
-    DeviceGuard guard(b->device);
-    b->quiesce_and_free();
-    if (b->ws)
-        b->ws->bussi_batches -= 1;
-    delete b;
-    return CAVMD_OK;
+    return destroy_table(b);
 }
 
 int cavmd_bussi_batch_set_items(cavmd_bussi_batch* b, size_t first, size_t count, const cavmd_bussi_batch_item* h_items)
@@ -2057,7 +2028,7 @@ int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_buss
     if (!b->captured && stream_capturing(stream))
         b->captured = true;
     b->sequence += 1;
-    hipLaunchKernelGGL(bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, stream, b->d_rows, b->d_order,
+    hipLaunchKernelGGL(bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, stream, b->d_rows.ptr, b->d_order.ptr,
                        reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state.ptr, b->h_blocks.dev);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
@@ -2150,7 +2121,6 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
 // launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
 struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_record>
 {
-    cavmd_workspace* ws = nullptr;
     uint64_t period = 1;
     double kB = 0.0;
 
@@ -2230,23 +2200,14 @@ int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recor
         cavmd_recorder_destroy(r);
         return (int)e;
     }
-    r->ws = ws;
-    ws->recorders += 1;
+    r->attach(ws);
     *out = r;
     return CAVMD_OK;
 }
 
 int cavmd_recorder_destroy(cavmd_recorder* r)
 {
-    if (!r)
-        return CAVMD_OK;
-    DeviceGuard guard(r->device);
-    r->quiesce_and_free();
-    r->free_series();
-    if (r->ws)
-        r->ws->recorders -= 1;
-    delete r;
-    return CAVMD_OK;
+    return destroy_table(r);
 }
 
 int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, const cavmd_recorder_item* h_items)
@@ -2260,8 +2221,8 @@ int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(r->device);
-    hipLaunchKernelGGL(recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows, r->d_order,
-                       (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series, r->d_counters);
+    hipLaunchKernelGGL(recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows.ptr, r->d_order.ptr,
+                       (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series.ptr, r->d_counters.ptr);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
@@ -2298,15 +2259,14 @@ int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, c
 // launched by N descending; kFldCounters words per item
 struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_field_record>
 {
-    cavmd_workspace* ws = nullptr;
     size_t n_k = 0;
     uint64_t period = 1;
     unsigned max_refs = 1;
     uint64_t interval = 0;
-    double* d_kvec = nullptr;       // n_k x 3
-    uint64_t* d_ref_rows = nullptr; // n x max_refs: the row each reference was taken at
-    double* d_now = nullptr;        // n x n_k x 2: the field of the last recorded call
-    double* d_refs = nullptr;       // n x max_refs x n_k x 2
+    DeviceArray<double> d_kvec;       // n_k x 3
+    DeviceArray<uint64_t> d_ref_rows; // n x max_refs: the row each reference was taken at
+    DeviceArray<double> d_now;        // n x n_k x 2: the field of the last recorded call
+    DeviceArray<double> d_refs;       // n x max_refs x n_k x 2
 
     cavmd_field_recorder()
         : SeriesTable(kFldCounters, cavmd_field_recorder_item_check, [](const cavmd_field_item& it) { return it.N; },
@@ -2381,26 +2341,17 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
     r->interval = reference_interval;
 
     DeviceGuard guard(r->device);
-    const size_t ref_row_bytes = sizeof(uint64_t) * n_items * max_references;
     hipError_t e = r->upload();
     if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_kvec, sizeof(double) * 3 * n_k);
-    if (e == hipSuccess)
-        e = hipMemcpy(r->d_kvec, h_wavevectors, sizeof(double) * 3 * n_k, hipMemcpyHostToDevice);
+        e = r->d_kvec.upload(h_wavevectors, 3 * n_k);
     if (e == hipSuccess)
         e = r->alloc_series();
     if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_ref_rows, ref_row_bytes);
+        e = r->d_ref_rows.alloc_zeroed(n_items * max_references);
     if (e == hipSuccess)
-        e = hipMemset(r->d_ref_rows, 0, ref_row_bytes);
+        e = r->d_now.alloc_zeroed(2 * n_k * n_items);
     if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_now, field_bytes * n_items);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_now, 0, field_bytes * n_items);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&r->d_refs, field_bytes * n_items * max_references);
-    if (e == hipSuccess)
-        e = hipMemset(r->d_refs, 0, field_bytes * n_items * max_references);
+        e = r->d_refs.alloc_zeroed(2 * n_k * n_items * max_references);
     if (e == hipSuccess)
         e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
     if (e != hipSuccess)
@@ -2408,26 +2359,14 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
         cavmd_field_recorder_destroy(r);
         return (int)e;
     }
-    r->ws = ws;
-    ws->field_recorders += 1;
+    r->attach(ws);
     *out = r;
     return CAVMD_OK;
 }
 
 int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
 {
-    if (!r)
-        return CAVMD_OK;
-    DeviceGuard guard(r->device);
-    r->quiesce_and_free();
-    r->free_series();
-    for (void* p : {(void*)r->d_kvec, (void*)r->d_ref_rows, (void*)r->d_now, (void*)r->d_refs})
-        if (p)
-            (void)hipFree(p);
-    if (r->ws)
-        r->ws->field_recorders -= 1;
-    delete r;
-    return CAVMD_OK;
+    return destroy_table(r);
 }
 
 int cavmd_field_recorder_set_items(cavmd_field_recorder* r, size_t first, size_t count, const cavmd_field_item* h_items)
@@ -2441,10 +2380,10 @@ int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const ui
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(r->device);
-    hipLaunchKernelGGL(field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows, r->d_order,
-                       (unsigned)r->n, r->d_kvec, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity, r->period,
-                       r->max_refs, r->interval, d_take_reference, r->d_series, r->d_counters, r->d_ref_rows, r->d_now,
-                       r->d_refs);
+    hipLaunchKernelGGL(field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows.ptr, r->d_order.ptr,
+                       (unsigned)r->n, r->d_kvec.ptr, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity, r->period,
+                       r->max_refs, r->interval, d_take_reference, r->d_series.ptr, r->d_counters.ptr, r->d_ref_rows.ptr,
+                       r->d_now.ptr, r->d_refs.ptr);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
@@ -2475,20 +2414,20 @@ int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, siz
     if (st != CAVMD_OK)
         return st;
     uint64_t rows = 0, refs = 0;
-    CAVMD_HIP_TRY(hipMemcpy(&rows, r->d_counters + (size_t)kFldRows * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    CAVMD_HIP_TRY(hipMemcpy(&rows, r->d_counters.ptr + (size_t)kFldRows * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (rows == 0)
         return CAVMD_ERR_NOT_COMPUTED;
-    CAVMD_HIP_TRY(hipMemcpy(&refs, r->d_counters + (size_t)kFldRefs * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    CAVMD_HIP_TRY(hipMemcpy(&refs, r->d_counters.ptr + (size_t)kFldRefs * r->n + item, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (refs > r->max_refs)
         return CAVMD_ERR_INVALID_VALUE;
     const size_t field_len = 2 * r->n_k;
     if (rho_now)
-        CAVMD_HIP_TRY(hipMemcpy(rho_now, r->d_now + item * field_len, sizeof(double) * field_len, hipMemcpyDeviceToHost));
+        CAVMD_HIP_TRY(hipMemcpy(rho_now, r->d_now.ptr + item * field_len, sizeof(double) * field_len, hipMemcpyDeviceToHost));
     if (rho_refs && refs)
-        CAVMD_HIP_TRY(hipMemcpy(rho_refs, r->d_refs + item * r->max_refs * field_len, sizeof(double) * field_len * refs,
+        CAVMD_HIP_TRY(hipMemcpy(rho_refs, r->d_refs.ptr + item * r->max_refs * field_len, sizeof(double) * field_len * refs,
                                 hipMemcpyDeviceToHost));
     if (ref_rows && refs)
-        CAVMD_HIP_TRY(hipMemcpy(ref_rows, r->d_ref_rows + item * r->max_refs, sizeof(uint64_t) * refs, hipMemcpyDeviceToHost));
+        CAVMD_HIP_TRY(hipMemcpy(ref_rows, r->d_ref_rows.ptr + item * r->max_refs, sizeof(uint64_t) * refs, hipMemcpyDeviceToHost));
     *n_refs = (uint32_t)refs;
     return CAVMD_OK;
 }
@@ -2508,7 +2447,6 @@ int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_r
 // ---- the velocity-Verlet step of a batch of independent small systems, one launch per half-step (cavmd_verlet_batch_kernel.hpp) --
 struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N descending
 {
-    cavmd_workspace* ws = nullptr;
     DeviceArray<VerletState> d_state; // n states, indexed by item
 
     cavmd_verlet()
@@ -2548,7 +2486,7 @@ template <class Kernel>
 int verlet_launch(cavmd_verlet* v, hipStream_t stream, Kernel kernel, const cavmd_verlet_input* d_inputs)
 {
     DeviceGuard guard(v->device);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)v->n), dim3(256), 0, stream, v->d_rows, v->d_order,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)v->n), dim3(256), 0, stream, v->d_rows.ptr, v->d_order.ptr,
                        reinterpret_cast<const VerletInput*>(d_inputs), v->d_state.ptr);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
@@ -2628,22 +2566,14 @@ int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_
         cavmd_verlet_destroy(v);
         return (int)e;
     }
-    v->ws = ws;
-    ws->verlets += 1;
+    v->attach(ws);
     *out = v;
     return CAVMD_OK;
 }
 
 int cavmd_verlet_destroy(cavmd_verlet* v)
 {
-    if (!v)
-        return CAVMD_OK;
-    DeviceGuard guard(v->device);
-    v->quiesce_and_free();
-    if (v->ws)
-        v->ws->verlets -= 1;
-    delete v;
-    return CAVMD_OK;
+    return destroy_table(v);
 }
 
 int cavmd_verlet_set_items(cavmd_verlet* v, size_t first, size_t count, const cavmd_verlet_item* h_items)
@@ -2704,6 +2634,7 @@ int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** ou
 } // extern "C"
 
 // ---- harmonic bonds and Lennard-Jones pairs of a batch of independent small systems in ONE launch (cavmd_molecular_batch_kernel.hpp) --
+// A LinkedTable (cavmd_item_table.hpp): what is below is the status of an item and how the device tables follow from the items.
 namespace
 {
 constexpr int kMolecularJSplit = CAVMD_MOLECULAR_J_SPLIT;
@@ -2731,8 +2662,7 @@ bool finite_nonnegative(double x)
 }
 
 // The status of one item; `prm` NULL: only what can be said without the parameters (bond types and the cut-offs are not
-// looked at).  `slots`, if given, receives the item's partner table: four slots a particle, partner | bond type << 16, filled
-// from slot 0 in the order of the bond list.
+// looked at).  `slots`, if given, receives the item's partner table: four slots a particle, partner | bond type << 16.
 int molecular_item_status(const cavmd_molecular_params* prm, const cavmd_molecular_item* it, std::vector<uint32_t>* slots)
 {
     if (!it)
@@ -2749,40 +2679,21 @@ int molecular_item_status(const cavmd_molecular_params* prm, const cavmd_molecul
         return CAVMD_ERR_CAPACITY;
     if (it->N != 0)
     {
-        const double L[3] = {it->Lx, it->Ly, it->Lz};
-        for (double l : L)
-            if (!(isfinite(l) && l > 0.0))
-                return CAVMD_ERR_INVALID_VALUE;
+        double cut_sq = 0.0;
+        if (!box_ok(it->Lx, it->Ly, it->Lz, &cut_sq))
+            return CAVMD_ERR_INVALID_VALUE;
         if (prm)
-        {
-            const double h = std::min(L[0], std::min(L[1], L[2])) * 0.5;
             for (unsigned a = 0; a < prm->n_types; ++a)
                 for (unsigned b = 0; b < prm->n_types; ++b)
-                    if (prm->pair[a][b].rcutsq > h * h)
+                    if (prm->pair[a][b].rcutsq > cut_sq)
                         return CAVMD_ERR_INVALID_VALUE;
-        }
     }
-    std::vector<uint8_t> count(it->N, 0);
-    if (slots)
-        slots->assign((size_t)it->N * kMolecularMaxBonds, kMolecularNoPartner);
+    const uint32_t n_bond_types = prm ? prm->n_bond_types : CAVMD_MOLECULAR_MAX_BOND_TYPES;
     for (uint32_t k = 0; k < it->n_bonds; ++k)
-    {
-        const cavmd_molecular_bond& bd = it->h_bonds[k];
-        if (bd.a >= it->N || bd.b >= it->N || bd.a == bd.b)
+        if (it->h_bonds[k].type >= n_bond_types)
             return CAVMD_ERR_INVALID_VALUE;
-        if (prm ? bd.type >= prm->n_bond_types : bd.type >= CAVMD_MOLECULAR_MAX_BOND_TYPES)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (count[bd.a] >= kMolecularMaxBonds || count[bd.b] >= kMolecularMaxBonds)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (slots)
-        {
-            (*slots)[(size_t)bd.a * kMolecularMaxBonds + count[bd.a]] = bd.b | (bd.type << 16);
-            (*slots)[(size_t)bd.b * kMolecularMaxBonds + count[bd.b]] = bd.a | (bd.type << 16);
-        }
-        count[bd.a] += 1;
-        count[bd.b] += 1;
-    }
-    return CAVMD_OK;
+    return partner_slots(it->N, it->h_bonds, it->n_bonds, kMolecularMaxBonds, kMolecularNoPartner,
+                         [](uint32_t partner, uint32_t type) { return partner | (type << 16); }, slots);
 }
 
 MolecularRow molecular_row(const cavmd_molecular_item& it)
@@ -2797,68 +2708,57 @@ MolecularRow molecular_row(const cavmd_molecular_item& it)
     r.n = it.N;
     return r;
 }
+
+// what set_items replaces together
+struct MolecularTables
+{
+    DeviceArray<uint4> blocks, partners;
+    MolecularHeader header;
+    unsigned lds_n = 2; // particles the next launch has LDS for
+};
 } // namespace
 
-struct cavmd_molecular : ItemTable<cavmd_molecular_item, MolecularRow> // workgroups by N descending
+// workgroups by N descending; per item its partner table
+struct cavmd_molecular final : LinkedTable<cavmd_molecular_item, MolecularRow, std::vector<uint32_t>, MolecularTables>
 {
-    cavmd_workspace* ws = nullptr;
     cavmd_molecular_params params;
     DeviceArray<MolecularParams> d_params;
-    DeviceArray<MolecularHeader> d_header;    // never reallocated: captured launches find the tables below through it
-    DeviceArray<uint4> d_blocks, d_partners;  // replaced together by set_items
-    std::vector<std::vector<uint32_t>> slots; // per item: its partner table (the bond lists are not kept)
-    unsigned n_blocks = 0;
-    unsigned lds_n = 2; // particles the next launch has LDS for: the largest N, rounded up to even
 
-    cavmd_molecular()
-        : ItemTable([](const cavmd_molecular_item* it) { return molecular_item_status(nullptr, it, nullptr); },
-                    [](const cavmd_molecular_item& it) { return it.N; }, molecular_row)
+    cavmd_molecular() : LinkedTable([](const cavmd_molecular_item& it) { return it.N; }, molecular_row) {}
+
+    int item_status(const cavmd_molecular_item* it, std::vector<uint32_t>* slots) const override
     {
+        return molecular_item_status(&params, it, slots);
     }
 
-    // the host's tables for `sizes` and `launch` (items by N descending), into fresh device arrays; committed by publish()
-    hipError_t build(const std::vector<unsigned>& sizes, const std::vector<unsigned>& launch,
-                     const std::vector<std::vector<uint32_t>>& all_slots, DeviceArray<uint4>* blocks, DeviceArray<uint4>* partners,
-                     MolecularHeader* header, unsigned* new_lds_n) const
+    void strip(cavmd_molecular_item* it) const override
     {
-        std::vector<uint32_t> base(sizes.size());
-        std::vector<uint32_t> pool;
+        it->h_bonds = nullptr;
+        it->n_bonds = 0;
+    }
+
+    hipError_t fill(const std::vector<cavmd_molecular_item>& all, const std::vector<unsigned>& launch,
+                    const std::vector<std::vector<uint32_t>>& slots, MolecularTables* t) const override
+    {
+        std::vector<uint32_t> base(all.size()), pool;
         unsigned largest = 0;
-        for (size_t i = 0; i < sizes.size(); ++i)
+        for (size_t i = 0; i < all.size(); ++i)
         {
-            base[i] = (uint32_t)(pool.size() / kMolecularMaxBonds);
-            pool.insert(pool.end(), all_slots[i].begin(), all_slots[i].end());
-            largest = std::max(largest, sizes[i]);
+            base[i] = pool_append(&pool, slots[i]) / kMolecularMaxBonds;
+            largest = std::max(largest, all[i].N);
         }
         std::vector<uint4> table;
         for (unsigned item : launch)
-            for (unsigned f = 0; f < sizes[item]; f += kMolecularRows)
-                table.push_back(make_uint4(item, f, base[item], 0u));
-        hipError_t e = blocks->alloc(std::max<size_t>(table.size(), 1));
-        if (e == hipSuccess && !table.empty())
-            e = hipMemcpy(blocks->ptr, table.data(), sizeof(uint4) * table.size(), hipMemcpyHostToDevice);
+            emit_blocks(&table, item, all[item].N, kMolecularRows, base[item], 0u);
+        hipError_t e = t->blocks.upload(table.data(), table.size());
         if (e == hipSuccess)
-            e = partners->alloc(std::max<size_t>(pool.size() / kMolecularMaxBonds, 1));
-        if (e == hipSuccess && !pool.empty())
-            e = hipMemcpy(partners->ptr, pool.data(), sizeof(uint32_t) * pool.size(), hipMemcpyHostToDevice);
-        memset(header, 0, sizeof(*header));
-        header->blocks = blocks->ptr;
-        header->partners = partners->ptr;
-        header->n_blocks = (unsigned)table.size();
-        *new_lds_n = std::max(2u, (largest + 1u) & ~1u);
+            e = t->partners.upload(pool.data(), pool.size());
+        memset(&t->header, 0, sizeof(t->header));
+        t->header.blocks = t->blocks.ptr;
+        t->header.partners = t->partners.ptr;
+        t->header.n_blocks = (unsigned)table.size();
+        t->lds_n = lds_particles(largest);
         return e;
-    }
-
-    hipError_t publish(DeviceArray<uint4>&& blocks, DeviceArray<uint4>&& partners, const MolecularHeader& header, unsigned new_lds_n)
-    {
-        const hipError_t e = hipMemcpy(d_header.ptr, &header, sizeof(header), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return e;
-        d_blocks = std::move(blocks); // the old tables are freed here: nothing in flight reads them (the caller has waited)
-        d_partners = std::move(partners);
-        n_blocks = header.n_blocks;
-        lds_n = new_lds_n;
-        return hipSuccess;
     }
 };
 
@@ -2941,106 +2841,33 @@ int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_params* pr
     int st = cavmd_molecular_params_check(prm);
     if (st != CAVMD_OK)
         return st;
-    std::vector<std::vector<uint32_t>> slots(n_items);
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        st = molecular_item_status(prm, h_items + i, &slots[i]);
-        if (st != CAVMD_OK)
-            return st;
-    }
     cavmd_molecular* m = new (std::nothrow) cavmd_molecular();
     if (!m)
         return (int)hipErrorOutOfMemory;
     m->params = *prm;
-    m->adopt(ws->device, h_items, n_items);
-    std::vector<unsigned> sizes(n_items);
-    for (size_t i = 0; i < n_items; ++i)
+    st = m->create(ws, h_items, n_items);
+    if (st == CAVMD_OK)
     {
-        m->items[i].h_bonds = nullptr; // the caller's lists are not kept
-        m->items[i].n_bonds = 0;
-        sizes[i] = m->items[i].N;
+        DeviceGuard guard(m->device);
+        st = hip_status(m->d_params.upload(prm, 1)); // a blocking copy: there before any launch
     }
-    m->slots.swap(slots);
-
-    DeviceGuard guard(m->device);
-    DeviceArray<uint4> blocks, partners;
-    MolecularHeader header;
-    unsigned lds_n = 2;
-    hipError_t e = m->upload();
-    if (e == hipSuccess)
-        e = m->d_params.alloc(1);
-    if (e == hipSuccess)
-        e = hipMemcpy(m->d_params.ptr, prm, sizeof(*prm), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = m->d_header.alloc_zeroed(1);
-    if (e == hipSuccess)
-        e = m->build(sizes, m->order, m->slots, &blocks, &partners, &header, &lds_n);
-    if (e == hipSuccess)
-        e = m->publish(std::move(blocks), std::move(partners), header, lds_n);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    if (e != hipSuccess)
+    if (st != CAVMD_OK)
     {
         cavmd_molecular_destroy(m);
-        return (int)e;
+        return st;
     }
-    m->ws = ws;
-    ws->moleculars += 1;
     *out = m;
     return CAVMD_OK;
 }
 
 int cavmd_molecular_destroy(cavmd_molecular* m)
 {
-    if (!m)
-        return CAVMD_OK;
-    DeviceGuard guard(m->device);
-    m->quiesce_and_free();
-    if (m->ws)
-        m->ws->moleculars -= 1;
-    delete m;
-    return CAVMD_OK;
+    return destroy_table(m);
 }
 
 int cavmd_molecular_set_items(cavmd_molecular* m, size_t first, size_t count, const cavmd_molecular_item* h_items)
 {
-    if (!m || !h_items || count == 0 || first >= m->n || count > m->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    std::vector<std::vector<uint32_t>> new_slots(m->slots);
-    std::vector<cavmd_molecular_item> rows(h_items, h_items + count);
-    std::vector<unsigned> sizes(m->n);
-    for (size_t i = 0; i < m->n; ++i)
-        sizes[i] = m->items[i].N;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = molecular_item_status(&m->params, h_items + i, &new_slots[first + i]);
-        if (st != CAVMD_OK)
-            return st;
-        rows[i].h_bonds = nullptr; // the caller's lists are not kept
-        rows[i].n_bonds = 0;
-        sizes[first + i] = rows[i].N;
-    }
-    DeviceGuard guard(m->device);
-    if (m->enqueued)
-    {
-        if (stream_capturing(m->last_stream))
-            return CAVMD_ERR_INVALID_VALUE; // nothing below may run during a capture
-        CAVMD_HIP_TRY(hipStreamSynchronize(m->last_stream));
-    }
-    // the new tables go to fresh device arrays first, then the rows, then the 32-byte header that points to the tables
-    std::vector<cavmd_molecular_item> all(m->items);
-    std::copy(rows.begin(), rows.end(), all.begin() + first);
-    const std::vector<unsigned> launch = launch_order(all, m->key);
-    DeviceArray<uint4> blocks, partners;
-    MolecularHeader header;
-    unsigned lds_n = 2;
-    CAVMD_HIP_TRY(m->build(sizes, launch, new_slots, &blocks, &partners, &header, &lds_n));
-    const int st = m->set_items(first, count, rows.data());
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(m->publish(std::move(blocks), std::move(partners), header, lds_n));
-    m->slots.swap(new_slots);
-    return CAVMD_OK;
+    return m ? m->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
@@ -3049,9 +2876,10 @@ int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(m->device);
-    hipLaunchKernelGGL((molecular_force_kernel<kMolecularBlock, kMolecularJSplit>), dim3(std::max(m->n_blocks, 1u)),
-                       dim3(kMolecularBlock), molecular_lds_bytes(m->lds_n), stream, m->d_rows, m->d_header.ptr, m->d_params.ptr,
-                       m->lds_n);
+    const MolecularTables& t = m->tables;
+    hipLaunchKernelGGL((molecular_force_kernel<kMolecularBlock, kMolecularJSplit>), dim3(std::max(t.header.n_blocks, 1u)),
+                       dim3(kMolecularBlock), molecular_lds_bytes(t.lds_n), stream, m->d_rows.ptr, m->d_header.ptr, m->d_params.ptr,
+                       t.lds_n);
     const int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
@@ -3062,6 +2890,7 @@ int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
 } // extern "C"
 
 // ---- Ewald Coulomb forces of a batch of independent small systems in TWO launches (cavmd_coulomb_batch_kernel.hpp) ------------
+// A LinkedTable as well: the status of an item with its k-vectors, and how the device tables follow from the items.
 namespace
 {
 constexpr int kCoulombJSplit = CAVMD_COULOMB_J_SPLIT;
@@ -3150,9 +2979,15 @@ void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<C
     *count = K;
 }
 
-// The status of one item.  `slots`, if given, receives the item's partner table (four slots a particle, filled from slot 0 in
-// the order of the exclusion list), `ktab` its k-table.
-int coulomb_item_status(const cavmd_coulomb_item* it, std::vector<uint32_t>* slots, std::vector<CoulombK>* ktab, size_t* out_K)
+// the tables derived from one item: its partner slots (four a particle, from the exclusion list) and its k-vectors
+struct CoulombDerived
+{
+    std::vector<uint32_t> slots;
+    std::vector<CoulombK> ktab;
+};
+
+// The status of one item.  `out`, if given, receives the item's derived tables, `out_K` the number of its k-vectors.
+int coulomb_item_status(const cavmd_coulomb_item* it, CoulombDerived* out, size_t* out_K)
 {
     if (!it)
         return CAVMD_ERR_INVALID_VALUE;
@@ -3168,40 +3003,24 @@ int coulomb_item_status(const cavmd_coulomb_item* it, std::vector<uint32_t>* slo
         return CAVMD_ERR_CAPACITY;
     if (it->N != 0)
     {
-        const double L[3] = {it->Lx, it->Ly, it->Lz};
-        for (double l : L)
-            if (!(isfinite(l) && l > 0.0))
-                return CAVMD_ERR_INVALID_VALUE;
+        double cut_sq = 0.0;
+        if (!box_ok(it->Lx, it->Ly, it->Lz, &cut_sq))
+            return CAVMD_ERR_INVALID_VALUE;
         if (!(isfinite(it->kappa) && it->kappa > 0.0) || !finite_nonnegative(it->r_cut) || !finite_nonnegative(it->k_cut))
             return CAVMD_ERR_INVALID_VALUE;
-        const double h = std::min(L[0], std::min(L[1], L[2])) * 0.5;
-        if (it->r_cut * it->r_cut > h * h)
+        if (it->r_cut * it->r_cut > cut_sq)
             return CAVMD_ERR_INVALID_VALUE;
     }
-    std::vector<uint8_t> count(it->N, 0);
-    if (slots)
-        slots->assign((size_t)it->N * kCoulombMaxExclusions, kCoulombNoPartner);
-    for (uint32_t k = 0; k < it->n_exclusions; ++k)
-    {
-        const cavmd_molecular_bond& ex = it->h_exclusions[k];
-        if (ex.a >= it->N || ex.b >= it->N || ex.a == ex.b)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (count[ex.a] >= kCoulombMaxExclusions || count[ex.b] >= kCoulombMaxExclusions)
-            return CAVMD_ERR_INVALID_VALUE;
-        if (slots)
-        {
-            (*slots)[(size_t)ex.a * kCoulombMaxExclusions + count[ex.a]] = ex.b;
-            (*slots)[(size_t)ex.b * kCoulombMaxExclusions + count[ex.b]] = ex.a;
-        }
-        count[ex.a] += 1;
-        count[ex.b] += 1;
-    }
+    const int st = partner_slots(it->N, it->h_exclusions, it->n_exclusions, kCoulombMaxExclusions, kCoulombNoPartner,
+                                 [](uint32_t partner, uint32_t) { return partner; }, out ? &out->slots : nullptr);
+    if (st != CAVMD_OK)
+        return st;
     size_t K = 0;
-    if (ktab)
-        ktab->clear();
+    if (out)
+        out->ktab.clear();
     if (it->N != 0)
     {
-        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, ktab, &K);
+        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, out ? &out->ktab : nullptr, &K);
         if (K > CAVMD_COULOMB_MAX_K)
             return CAVMD_ERR_CAPACITY;
     }
@@ -3246,68 +3065,54 @@ struct CoulombTables
 };
 } // namespace
 
-struct cavmd_coulomb : ItemTable<cavmd_coulomb_item, CoulombRow> // workgroups by N descending
+// workgroups by N descending
+struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, CoulombDerived, CoulombTables>
 {
-    cavmd_workspace* ws = nullptr;
-    DeviceArray<CoulombHeader> d_header;      // never reallocated: captured launches find the tables through it
-    CoulombTables tables;                     // replaced as a whole by set_items
-    std::vector<std::vector<uint32_t>> slots; // per item: its partner table (the exclusion lists are not kept)
-    std::vector<std::vector<CoulombK>> ktabs; // per item: its k-table
+    cavmd_coulomb() : LinkedTable([](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row) {}
 
-    cavmd_coulomb()
-        : ItemTable([](const cavmd_coulomb_item* it) { return coulomb_item_status(it, nullptr, nullptr, nullptr); },
-                    [](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row)
+    int item_status(const cavmd_coulomb_item* it, CoulombDerived* out) const override
     {
+        return coulomb_item_status(it, out, nullptr);
     }
 
-    // the host's tables for `sizes` and `launch` (items by N descending), into fresh device arrays; committed by publish()
-    hipError_t build(const std::vector<unsigned>& sizes, const std::vector<unsigned>& launch,
-                     const std::vector<std::vector<uint32_t>>& all_slots, const std::vector<std::vector<CoulombK>>& all_k,
-                     CoulombTables* t) const
+    void strip(cavmd_coulomb_item* it) const override
     {
-        const size_t B = sizes.size();
+        it->h_exclusions = nullptr;
+        it->n_exclusions = 0;
+    }
+
+    hipError_t fill(const std::vector<cavmd_coulomb_item>& all, const std::vector<unsigned>& launch,
+                    const std::vector<CoulombDerived>& d, CoulombTables* t) const override
+    {
+        const size_t B = all.size();
         std::vector<uint32_t> partner_base(B), pool;
         std::vector<CoulombK> kpool;
         t->offsets.assign(B, 0);
         unsigned largest = 0;
         for (size_t i = 0; i < B; ++i)
         {
-            partner_base[i] = (uint32_t)(pool.size() / kCoulombMaxExclusions);
-            pool.insert(pool.end(), all_slots[i].begin(), all_slots[i].end());
-            t->offsets[i] = (uint32_t)kpool.size();
-            kpool.insert(kpool.end(), all_k[i].begin(), all_k[i].end());
+            partner_base[i] = pool_append(&pool, d[i].slots) / kCoulombMaxExclusions;
+            t->offsets[i] = pool_append(&kpool, d[i].ktab);
             kpool.push_back(CoulombK {0.0, 0.0, 0.0, 0.0}); // the slot of {Q, 0}
-            largest = std::max(largest, sizes[i]);
+            largest = std::max(largest, all[i].N);
         }
         std::vector<uint4> k_table, table;
         for (unsigned item : launch)
         {
-            if (sizes[item] == 0)
+            if (all[item].N == 0)
                 continue;
-            for (unsigned f = 0; f < all_k[item].size(); f += kCoulombKRows)
-                k_table.push_back(make_uint4(item, f, t->offsets[item], 0u));
-            for (unsigned f = 0; f < sizes[item]; f += kCoulombRows)
-                table.push_back(make_uint4(item, f, partner_base[item], t->offsets[item]));
+            emit_blocks(&k_table, item, (unsigned)d[item].ktab.size(), kCoulombKRows, t->offsets[item], 0u);
+            emit_blocks(&table, item, all[item].N, kCoulombRows, partner_base[item], t->offsets[item]);
         }
-        auto upload = [](auto* dst, const auto& src) {
-            hipError_t e = dst->alloc(std::max<size_t>(src.size(), 1));
-            if (e == hipSuccess && !src.empty())
-                e = hipMemcpy(dst->ptr, src.data(), sizeof(src[0]) * src.size(), hipMemcpyHostToDevice);
-            return e;
-        };
-        hipError_t e = upload(&t->k_blocks, k_table);
+        hipError_t e = t->k_blocks.upload(k_table.data(), k_table.size());
         if (e == hipSuccess)
-            e = upload(&t->blocks, table);
+            e = t->blocks.upload(table.data(), table.size());
         if (e == hipSuccess)
-            e = upload(&t->ktab, kpool);
+            e = t->ktab.upload(kpool.data(), kpool.size());
         if (e == hipSuccess)
             e = t->structure.alloc_zeroed(kpool.size());
         if (e == hipSuccess)
-        {
-            e = t->partners.alloc(std::max<size_t>(pool.size() / kCoulombMaxExclusions, 1));
-            if (e == hipSuccess && !pool.empty())
-                e = hipMemcpy(t->partners.ptr, pool.data(), sizeof(uint32_t) * pool.size(), hipMemcpyHostToDevice);
-        }
+            e = t->partners.upload(pool.data(), pool.size());
         memset(&t->header, 0, sizeof(t->header));
         t->header.k_blocks = t->k_blocks.ptr;
         t->header.blocks = t->blocks.ptr;
@@ -3316,17 +3121,8 @@ struct cavmd_coulomb : ItemTable<cavmd_coulomb_item, CoulombRow> // workgroups b
         t->header.structure = t->structure.ptr;
         t->header.n_k_blocks = (unsigned)k_table.size();
         t->header.n_blocks = (unsigned)table.size();
-        t->lds_n = std::max(2u, (largest + 1u) & ~1u);
+        t->lds_n = lds_particles(largest);
         return e;
-    }
-
-    hipError_t publish(CoulombTables&& t)
-    {
-        const hipError_t e = hipMemcpy(d_header.ptr, &t.header, sizeof(t.header), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return e;
-        tables = std::move(t); // the old tables are freed here: nothing in flight reads them (the caller has waited)
-        return hipSuccess;
     }
 };
 
@@ -3335,7 +3131,7 @@ extern "C"
 
 int cavmd_coulomb_item_check(const cavmd_coulomb_item* it)
 {
-    return coulomb_item_status(it, nullptr, nullptr, nullptr);
+    return coulomb_item_status(it, nullptr, nullptr);
 }
 
 int cavmd_coulomb_k_count(const cavmd_coulomb_item* it, uint32_t* out_K)
@@ -3343,7 +3139,7 @@ int cavmd_coulomb_k_count(const cavmd_coulomb_item* it, uint32_t* out_K)
     if (!out_K)
         return CAVMD_ERR_INVALID_VALUE;
     size_t K = 0;
-    const int st = coulomb_item_status(it, nullptr, nullptr, &K);
+    const int st = coulomb_item_status(it, nullptr, &K);
     if (st != CAVMD_OK)
         return st;
     *out_K = (uint32_t)K;
@@ -3380,101 +3176,27 @@ int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulom
     *out = nullptr;
     if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
         return CAVMD_ERR_INVALID_VALUE;
-    std::vector<std::vector<uint32_t>> slots(n_items);
-    std::vector<std::vector<CoulombK>> ktabs(n_items);
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        const int st = coulomb_item_status(h_items + i, &slots[i], &ktabs[i], nullptr);
-        if (st != CAVMD_OK)
-            return st;
-    }
     cavmd_coulomb* c = new (std::nothrow) cavmd_coulomb();
     if (!c)
         return (int)hipErrorOutOfMemory;
-    c->adopt(ws->device, h_items, n_items);
-    std::vector<unsigned> sizes(n_items);
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        c->items[i].h_exclusions = nullptr; // the caller's lists are not kept
-        c->items[i].n_exclusions = 0;
-        sizes[i] = c->items[i].N;
-    }
-    c->slots.swap(slots);
-    c->ktabs.swap(ktabs);
-
-    DeviceGuard guard(c->device);
-    CoulombTables t;
-    hipError_t e = c->upload();
-    if (e == hipSuccess)
-        e = c->d_header.alloc_zeroed(1);
-    if (e == hipSuccess)
-        e = c->build(sizes, c->order, c->slots, c->ktabs, &t);
-    if (e == hipSuccess)
-        e = c->publish(std::move(t));
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    if (e != hipSuccess)
+    const int st = c->create(ws, h_items, n_items);
+    if (st != CAVMD_OK)
     {
         cavmd_coulomb_destroy(c);
-        return (int)e;
+        return st;
     }
-    c->ws = ws;
-    ws->coulombs += 1;
     *out = c;
     return CAVMD_OK;
 }
 
 int cavmd_coulomb_destroy(cavmd_coulomb* c)
 {
-    if (!c)
-        return CAVMD_OK;
-    DeviceGuard guard(c->device);
-    c->quiesce_and_free();
-    if (c->ws)
-        c->ws->coulombs -= 1;
-    delete c;
-    return CAVMD_OK;
+    return destroy_table(c);
 }
 
 int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items)
 {
-    if (!c || !h_items || count == 0 || first >= c->n || count > c->n - first)
-        return CAVMD_ERR_INVALID_VALUE;
-    std::vector<std::vector<uint32_t>> new_slots(c->slots);
-    std::vector<std::vector<CoulombK>> new_ktabs(c->ktabs);
-    std::vector<cavmd_coulomb_item> rows(h_items, h_items + count);
-    std::vector<unsigned> sizes(c->n);
-    for (size_t i = 0; i < c->n; ++i)
-        sizes[i] = c->items[i].N;
-    for (size_t i = 0; i < count; ++i)
-    {
-        const int st = coulomb_item_status(h_items + i, &new_slots[first + i], &new_ktabs[first + i], nullptr);
-        if (st != CAVMD_OK)
-            return st;
-        rows[i].h_exclusions = nullptr; // the caller's lists are not kept
-        rows[i].n_exclusions = 0;
-        sizes[first + i] = rows[i].N;
-    }
-    DeviceGuard guard(c->device);
-    if (c->enqueued)
-    {
-        if (stream_capturing(c->last_stream))
-            return CAVMD_ERR_INVALID_VALUE; // nothing below may run during a capture
-        CAVMD_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    }
-    // the new tables go to fresh device arrays first, then the rows, then the 64-byte header that points to the tables
-    std::vector<cavmd_coulomb_item> all(c->items);
-    std::copy(rows.begin(), rows.end(), all.begin() + first);
-    const std::vector<unsigned> launch = launch_order(all, c->key);
-    CoulombTables t;
-    CAVMD_HIP_TRY(c->build(sizes, launch, new_slots, new_ktabs, &t));
-    const int st = c->set_items(first, count, rows.data());
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(c->publish(std::move(t)));
-    c->slots.swap(new_slots);
-    c->ktabs.swap(new_ktabs);
-    return CAVMD_OK;
+    return c ? c->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
@@ -3485,12 +3207,12 @@ int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
     DeviceGuard guard(c->device);
     const CoulombTables& t = c->tables;
     hipLaunchKernelGGL((coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>), dim3(std::max(t.header.n_k_blocks, 1u)),
-                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows, c->d_header.ptr, t.lds_n);
+                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
     int st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;
     hipLaunchKernelGGL((coulomb_force_kernel<kCoulombBlock, kCoulombJSplit>), dim3(std::max(t.header.n_blocks, 1u)),
-                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows, c->d_header.ptr, t.lds_n);
+                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
     st = hip_status(hipGetLastError());
     if (st != CAVMD_OK)
         return st;

@@ -81,16 +81,6 @@ constexpr size_t coulomb_lds_bytes(unsigned lds_n)
     return (size_t)lds_n * 32;
 }
 
-// the minimum image of cavmd_molecular_batch_kernel.hpp, rule for rule
-__device__ __forceinline__ double coulomb_min_image(double d, double L, double h)
-{
-    if (d >= h)
-        d -= L;
-    else if (d < -h)
-        d += L;
-    return d;
-}
-
 // x, y, z, q of the n particles of `row` into the four LDS arrays
 template <int BLOCK>
 __device__ __forceinline__ void coulomb_stage(const CoulombRow* __restrict__ row, unsigned n, double* __restrict__ sx,
@@ -231,9 +221,9 @@ __global__ __launch_bounds__(BLOCK) void coulomb_force_kernel(const CoulombRow* 
         if (j == i)
             continue;
         const bool excluded = (j == slots.x) | (j == slots.y) | (j == slots.z) | (j == slots.w);
-        const double dx = coulomb_min_image(xi - sx[j], Lx, hx);
-        const double dy = coulomb_min_image(yi - sy[j], Ly, hy);
-        const double dz = coulomb_min_image(zi - sz[j], Lz, hz);
+        const double dx = min_image(xi - sx[j], Lx, hx);
+        const double dy = min_image(yi - sy[j], Ly, hy);
+        const double dz = min_image(zi - sz[j], Lz, hz);
         const double rsq = (dx * dx + dy * dy) + dz * dz;
         if (!excluded && !(rsq < rcutsq))
             continue;

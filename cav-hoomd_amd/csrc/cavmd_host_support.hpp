@@ -174,6 +174,19 @@ struct DeviceArray
         return e;
     }
 
+    // a fresh array holding the `count` Ss at `src`, reinterpreted as Ts; at least one T, so that ptr is not NULL afterwards
+    template <class S>
+    hipError_t upload(const S* src, size_t count)
+    {
+        const size_t bytes = sizeof(S) * count;
+        hipError_t e = alloc(bytes < sizeof(T) ? 1 : bytes / sizeof(T));
+        if (e == hipSuccess && bytes)
+            e = hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            free();
+        return e;
+    }
+
     void free()
     {
         if (ptr)

@@ -1,9 +1,12 @@
-// Host-only: what the "batch of small systems in one launch" objects of cavmd_capi.hip share -- how a table of items lives on
-// the host and on the device (ItemTable) and, for the two recorders, the per-item ring of records behind it (SeriesTable).
-// cavmd_capi.hip includes this once, after its DeviceGuard and CAVMD_HIP_TRY, which the code below uses.
+// Host-only: what the seven "batch of small systems" objects of cavmd_capi.hip share -- how a table of items lives on the host
+// and on the device and how the object is tied to its workspace (ItemTable); for the two recorders, the per-item ring of records
+// behind it (SeriesTable); for the two force batches, the tables derived from the items that their kernels find through a
+// header at a fixed device address and that set_items replaces together (LinkedTable).
+// cavmd_capi.hip includes this once, after cavmd_workspace, DeviceGuard and CAVMD_HIP_TRY, which the code below uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -11,7 +14,7 @@
 #include <vector>
 
 #include "cavmd.h"
-#include "cavmd_host_support.hpp" // stream_capturing
+#include "cavmd_host_support.hpp" // stream_capturing, DeviceArray
 
 namespace
 {
@@ -70,10 +73,11 @@ struct ItemTable
     Row (*const to_row)(const Item&);
     int device = -1;
     size_t n = 0;
-    std::vector<Item> items;     // host copy of the table, as the caller gave it
-    std::vector<unsigned> order; // items by key descending, stable
-    Row* d_rows = nullptr;
-    unsigned* d_order = nullptr;
+    cavmd_workspace* ws = nullptr; // the workspace this object was attached to: cavmd_destroy refuses while it lives
+    std::vector<Item> items;       // host copy of the table, as the caller gave it
+    std::vector<unsigned> order;   // items by key descending, stable
+    DeviceArray<Row> d_rows;
+    DeviceArray<unsigned> d_order;
     hipStream_t last_stream = nullptr;
     bool enqueued = false; // some launch was enqueued: last_stream means something
 
@@ -90,20 +94,28 @@ struct ItemTable
         order = launch_order(items, key);
     }
 
-    // allocates and fills d_rows, then d_order (the caller holds the DeviceGuard and frees through quiesce_and_free)
+    // allocates and fills d_rows, then d_order (the caller holds the DeviceGuard)
     hipError_t upload()
     {
         std::vector<Row> rows(n);
         for (size_t i = 0; i < n; ++i)
             rows[i] = to_row(items[i]);
-        hipError_t e = hipMalloc((void**)&d_rows, sizeof(Row) * n);
-        if (e == hipSuccess)
-            e = hipMemcpy(d_rows, rows.data(), sizeof(Row) * n, hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMalloc((void**)&d_order, sizeof(unsigned) * n);
-        if (e == hipSuccess)
-            e = hipMemcpy(d_order, order.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice);
-        return e;
+        const hipError_t e = d_rows.upload(rows.data(), n);
+        return e == hipSuccess ? d_order.upload(order.data(), n) : e;
+    }
+
+    // a complete object is tied to the workspace it was created from
+    void attach(cavmd_workspace* w)
+    {
+        ws = w;
+        ws->dependents += 1;
+    }
+
+    void detach()
+    {
+        if (ws)
+            ws->dependents -= 1;
+        ws = nullptr;
     }
 
     // after a launch on `stream` went through
@@ -113,54 +125,97 @@ struct ItemTable
         enqueued = true;
     }
 
-    int set_items(size_t first, size_t count, const Item* h_items)
+    // THE wait for the launches in flight, which read the table and write the object's results (the caller holds the
+    // DeviceGuard); a stream that is being captured cannot be waited for
+    int wait_idle()
     {
-        if (!h_items || count == 0 || first >= n || count > n - first)
-            return CAVMD_ERR_INVALID_VALUE;
-        const int st = check_items(h_items, count, check);
+        return enqueued ? sync_uncaptured(last_stream) : CAVMD_OK;
+    }
+
+    bool within(size_t first, size_t count, const Item* h_items) const
+    {
+        return h_items && count != 0 && first < n && count <= n - first;
+    }
+
+    // A replacement of items [first, first + count) goes in three steps, so that an object with more to replace than rows can
+    // put its own device writes between them: stage() waits for the launches in flight (or refuses) and builds the new table
+    // and order aside, write() copies order and rows to the device, commit() makes the host agree.
+    struct Staged
+    {
+        std::vector<Item> items;
+        std::vector<unsigned> order;
+        std::vector<Row> rows; // of the replaced items
+    };
+
+    int stage(size_t first, size_t count, const Item* h_items, Staged* s)
+    {
+        const int st = wait_idle();
         if (st != CAVMD_OK)
             return st;
-        DeviceGuard guard(device);
-        if (enqueued)
-        {
-            if (stream_capturing(last_stream))
-                return CAVMD_ERR_INVALID_VALUE;
-            CAVMD_HIP_TRY(hipStreamSynchronize(last_stream)); // launches in flight read the rows this call rewrites
-        }
-        // the new table and order are built aside and committed only after both copies went through: a failed copy leaves the
-        // host's view and (up to the rows already overwritten by a copy that died half-way) the device's as they were
-        std::vector<Item> new_items(items);
-        std::vector<Row> rows(count);
+        s->items = items;
+        s->rows.resize(count);
         for (size_t i = 0; i < count; ++i)
         {
-            new_items[first + i] = h_items[i];
-            rows[i] = to_row(h_items[i]);
+            s->items[first + i] = h_items[i];
+            s->rows[i] = to_row(h_items[i]);
         }
-        const std::vector<unsigned> new_order = launch_order(new_items, key);
-        CAVMD_HIP_TRY(hipMemcpy(d_order, new_order.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));
-        const hipError_t e = hipMemcpy(d_rows + first, rows.data(), sizeof(Row) * count, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-        {
-            (void)hipMemcpy(d_order, order.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice); // the old order back
-            return (int)e;
-        }
-        items.swap(new_items);
-        order = new_order;
+        s->order = launch_order(s->items, key);
         return CAVMD_OK;
     }
 
-    // the launches in flight read the table and write the object's results: let them finish (a capturing stream cannot be
-    // waited for), then free the table (the caller holds the DeviceGuard)
-    void quiesce_and_free()
+    // a failed copy leaves the device's table as it was, up to the rows already overwritten by a copy that died half-way
+    int write(size_t first, const Staged& s)
     {
-        if (enqueued && !stream_capturing(last_stream))
-            (void)hipStreamSynchronize(last_stream);
-        if (d_rows)
-            (void)hipFree(d_rows);
-        if (d_order)
-            (void)hipFree(d_order);
+        CAVMD_HIP_TRY(hipMemcpy(d_order.ptr, s.order.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));
+        const hipError_t e = hipMemcpy(d_rows.ptr + first, s.rows.data(), sizeof(Row) * s.rows.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            (void)hipMemcpy(d_order.ptr, order.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice); // the old order back
+        return hip_status(e);
+    }
+
+    void commit(Staged&& s)
+    {
+        items.swap(s.items);
+        order.swap(s.order);
+    }
+
+    int set_items(size_t first, size_t count, const Item* h_items)
+    {
+        if (!within(first, count, h_items))
+            return CAVMD_ERR_INVALID_VALUE;
+        int st = check_items(h_items, count, check);
+        if (st != CAVMD_OK)
+            return st;
+        DeviceGuard guard(device);
+        Staged s;
+        st = stage(first, count, h_items, &s);
+        if (st == CAVMD_OK)
+            st = write(first, s);
+        if (st == CAVMD_OK)
+            commit(std::move(s)); // only now: a failed copy leaves the host's view as it was
+        return st;
+    }
+
+    // before the object goes: let the launches in flight finish (the caller holds the DeviceGuard; a capturing stream cannot
+    // be waited for, and then nothing of it runs)
+    void quiesce()
+    {
+        (void)wait_idle();
     }
 };
+
+// The end of every object built on an item table: guard, quiesce, detach, delete -- the buffers go with their owners.
+template <class Table>
+int destroy_table(Table* t)
+{
+    if (!t)
+        return CAVMD_OK;
+    DeviceGuard guard(t->device);
+    t->quiesce();
+    t->detach();
+    delete t;
+    return CAVMD_OK;
+}
 
 // An item table whose launches append Records to a time series in device memory: per item a ring of `capacity` records and
 // `n_counters` words, the words kept as n_counters arrays of n with the rows-written array first.
@@ -169,8 +224,8 @@ struct SeriesTable : ItemTable<Item, Row>
 {
     const unsigned n_counters;
     size_t capacity = 0;
-    Record* d_series = nullptr;     // n x capacity records, item-major
-    uint64_t* d_counters = nullptr; // n_counters arrays of n words
+    DeviceArray<Record> d_series;     // n x capacity records, item-major
+    DeviceArray<uint64_t> d_counters; // n_counters arrays of n words
 
     SeriesTable(unsigned n_counters_, int (*check_)(const Item*), unsigned (*key_)(const Item&), Row (*to_row_)(const Item&))
         : ItemTable<Item, Row>(check_, key_, to_row_), n_counters(n_counters_)
@@ -180,24 +235,8 @@ struct SeriesTable : ItemTable<Item, Row>
     // allocates and zeroes the series, then the counters
     hipError_t alloc_series()
     {
-        const size_t series_bytes = sizeof(Record) * this->n * capacity;
-        const size_t counter_bytes = sizeof(uint64_t) * n_counters * this->n;
-        hipError_t e = hipMalloc((void**)&d_series, series_bytes);
-        if (e == hipSuccess)
-            e = hipMemset(d_series, 0, series_bytes);
-        if (e == hipSuccess)
-            e = hipMalloc((void**)&d_counters, counter_bytes);
-        if (e == hipSuccess)
-            e = hipMemset(d_counters, 0, counter_bytes);
-        return e;
-    }
-
-    void free_series()
-    {
-        if (d_series)
-            (void)hipFree(d_series);
-        if (d_counters)
-            (void)hipFree(d_counters);
+        const hipError_t e = d_series.alloc_zeroed(this->n * capacity);
+        return e == hipSuccess ? d_counters.alloc_zeroed((size_t)n_counters * this->n) : e;
     }
 
     int rows(hipStream_t stream, uint64_t* out)
@@ -206,7 +245,7 @@ struct SeriesTable : ItemTable<Item, Row>
         const int st = sync_uncaptured(stream);
         if (st != CAVMD_OK)
             return st;
-        CAVMD_HIP_TRY(hipMemcpy(out, d_counters, sizeof(uint64_t) * this->n, hipMemcpyDeviceToHost));
+        CAVMD_HIP_TRY(hipMemcpy(out, d_counters.ptr, sizeof(uint64_t) * this->n, hipMemcpyDeviceToHost));
         return CAVMD_OK;
     }
 
@@ -218,7 +257,7 @@ struct SeriesTable : ItemTable<Item, Row>
         if (st != CAVMD_OK)
             return st;
         std::vector<uint64_t> written(n_items);
-        CAVMD_HIP_TRY(hipMemcpy(written.data(), d_counters + first_item, sizeof(uint64_t) * n_items, hipMemcpyDeviceToHost));
+        CAVMD_HIP_TRY(hipMemcpy(written.data(), d_counters.ptr + first_item, sizeof(uint64_t) * n_items, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < n_items; ++k)
         {
             if (written[k] == 0)
@@ -233,7 +272,7 @@ struct SeriesTable : ItemTable<Item, Row>
         const size_t rec = sizeof(Record);
         const size_t slot0 = (size_t)(first_row % capacity);
         const size_t run0 = std::min(n_rows, capacity - slot0);
-        const Record* src = d_series + first_item * capacity;
+        const Record* src = d_series.ptr + first_item * capacity;
         CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
         if (run0 < n_rows)
             CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, capacity * rec, (n_rows - run0) * rec, n_items,
@@ -244,7 +283,7 @@ struct SeriesTable : ItemTable<Item, Row>
     int reset(hipStream_t stream)
     {
         DeviceGuard guard(this->device);
-        CAVMD_HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(uint64_t) * n_counters * this->n, stream));
+        CAVMD_HIP_TRY(hipMemsetAsync(d_counters.ptr, 0, sizeof(uint64_t) * n_counters * this->n, stream));
         return CAVMD_OK;
     }
 
@@ -253,9 +292,174 @@ struct SeriesTable : ItemTable<Item, Row>
         if (!records && !rows_written)
             return CAVMD_ERR_INVALID_VALUE;
         if (records)
-            *records = d_series;
+            *records = d_series.ptr;
         if (rows_written)
-            *rows_written = d_counters;
+            *rows_written = d_counters.ptr;
+        return CAVMD_OK;
+    }
+};
+
+// ---- derived tables behind a header ----------------------------------------------------------------------------------------
+// The helpers of the objects whose kernels read, besides the rows, tables the library derives from each item.
+
+// a periodic box: three finite positive edges; *cut_sq = (half the shortest edge)^2, the largest squared cut-off under which
+// the minimum image is the only image in range
+bool box_ok(double Lx, double Ly, double Lz, double* cut_sq)
+{
+    const double L[3] = {Lx, Ly, Lz};
+    for (double l : L)
+        if (!(isfinite(l) && l > 0.0))
+            return false;
+    const double h = std::min(L[0], std::min(L[1], L[2])) * 0.5;
+    *cut_sq = h * h;
+    return true;
+}
+
+// The partner slots of N particles from a host pair list: `cap` slots a particle, `empty` where there is no partner, filled
+// from slot 0 in list order with word(partner, type of the pair).  Refuses an index >= N, a pair of a particle with itself and
+// a particle's (cap + 1)-th partner.  `slots` NULL: the status alone.
+int partner_slots(uint32_t N, const cavmd_molecular_bond* pairs, uint32_t n_pairs, unsigned cap, uint32_t empty,
+                  uint32_t (*word)(uint32_t partner, uint32_t type), std::vector<uint32_t>* slots)
+{
+    std::vector<uint8_t> count(N, 0);
+    if (slots)
+        slots->assign((size_t)N * cap, empty);
+    for (uint32_t k = 0; k < n_pairs; ++k)
+    {
+        const cavmd_molecular_bond& p = pairs[k];
+        if (p.a >= N || p.b >= N || p.a == p.b)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (count[p.a] >= cap || count[p.b] >= cap)
+            return CAVMD_ERR_INVALID_VALUE;
+        if (slots)
+        {
+            (*slots)[(size_t)p.a * cap + count[p.a]] = word(p.b, p.type);
+            (*slots)[(size_t)p.b * cap + count[p.b]] = word(p.a, p.type);
+        }
+        count[p.a] += 1;
+        count[p.b] += 1;
+    }
+    return CAVMD_OK;
+}
+
+// appends an item's part to the pool of all items; returns where it starts
+template <class T>
+uint32_t pool_append(std::vector<T>* pool, const std::vector<T>& part)
+{
+    const size_t base = pool->size();
+    pool->insert(pool->end(), part.begin(), part.end());
+    return (uint32_t)base;
+}
+
+// one entry per workgroup of an item with `count` particles (or k-vectors), `rows` of them a workgroup: {item, first, z, w}
+void emit_blocks(std::vector<uint4>* table, unsigned item, unsigned count, unsigned rows, unsigned z, unsigned w)
+{
+    for (unsigned first = 0; first < count; first += rows)
+        table->push_back(make_uint4(item, first, z, w));
+}
+
+// particles a launch gets LDS for: the largest N of the table, rounded up to even, at least 2
+unsigned lds_particles(unsigned largest)
+{
+    return std::max(2u, (largest + 1u) & ~1u);
+}
+
+// An item table with, per item, host tables derived from it (Derived: partner slots, k-vectors) and, pooled over the items,
+// device tables (Tables: the arrays, their `header` and `lds_n`) that the kernels find through a header at a device address
+// that never changes -- so a launch captured before set_items follows the new tables.  The object names what is its own: the
+// status of one item, what of an item is not kept, and how the device tables follow from items, launch order and derived
+// tables.  Creation, replacement and the moment the old arrays are freed are here, once.
+template <class Item, class Row, class Derived, class Tables>
+struct LinkedTable : ItemTable<Item, Row>
+{
+    using Base = ItemTable<Item, Row>;
+    DeviceArray<decltype(Tables::header)> d_header; // never reallocated
+    Tables tables;                                  // replaced as a whole
+    std::vector<Derived> derived;                   // per item (the caller's lists are not kept)
+
+    // (no `check`: the items of this table pass item_status instead)
+    LinkedTable(unsigned (*key_)(const Item&), Row (*to_row_)(const Item&)) : Base(nullptr, key_, to_row_) {}
+
+    // the status of one item, writing its derived tables into `out` unless that is NULL
+    virtual int item_status(const Item* it, Derived* out) const = 0;
+    // takes the caller's host lists out of an item that is kept
+    virtual void strip(Item* it) const = 0;
+    // fills fresh device arrays and t->header, t->lds_n for `all` items launched in the order `launch`
+    virtual hipError_t fill(const std::vector<Item>& all, const std::vector<unsigned>& launch, const std::vector<Derived>& d,
+                            Tables* t) const = 0;
+
+    int check_into(const Item* h_items, size_t count, Derived* out) const
+    {
+        for (size_t i = 0; i < count; ++i)
+        {
+            const int st = item_status(h_items + i, out + i);
+            if (st != CAVMD_OK)
+                return st;
+        }
+        return CAVMD_OK;
+    }
+
+    hipError_t copy_header(const Tables& t)
+    {
+        return hipMemcpy(d_header.ptr, &t.header, sizeof(t.header), hipMemcpyHostToDevice);
+    }
+
+    // the whole of create after the object's own arguments: a status other than CAVMD_OK leaves an object to be destroyed
+    int create(cavmd_workspace* w, const Item* h_items, size_t n_items)
+    {
+        this->device = w->device; // whoever destroys the object holds the guard of this device
+        derived.resize(n_items);
+        const int st = check_into(h_items, n_items, derived.data());
+        if (st != CAVMD_OK)
+            return st;
+        this->adopt(w->device, h_items, n_items);
+        for (Item& it : this->items)
+            strip(&it);
+        DeviceGuard guard(this->device);
+        hipError_t e = this->upload();
+        if (e == hipSuccess)
+            e = d_header.alloc_zeroed(1);
+        if (e == hipSuccess)
+            e = fill(this->items, this->order, derived, &tables);
+        if (e == hipSuccess)
+            e = copy_header(tables);
+        if (e == hipSuccess)
+            e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's computes
+        if (e == hipSuccess)
+            this->attach(w);
+        return hip_status(e);
+    }
+
+    // (hides ItemTable's: the rows are only a part of what is replaced here)
+    int set_items(size_t first, size_t count, const Item* h_items)
+    {
+        if (!this->within(first, count, h_items))
+            return CAVMD_ERR_INVALID_VALUE;
+        std::vector<Derived> new_derived(derived);
+        int st = check_into(h_items, count, new_derived.data() + first);
+        if (st != CAVMD_OK)
+            return st;
+        std::vector<Item> kept(h_items, h_items + count);
+        for (Item& it : kept)
+            strip(&it);
+        DeviceGuard guard(this->device);
+        typename Base::Staged s;
+        st = this->stage(first, count, kept.data(), &s); // refuses during a capture: nothing below may run in one
+        if (st != CAVMD_OK)
+            return st;
+        // device writes: the new tables into fresh arrays, then order and rows, then the header that points to the tables
+        Tables t;
+        CAVMD_HIP_TRY(fill(s.items, s.order, new_derived, &t));
+        st = this->write(first, s);
+        if (st != CAVMD_OK)
+            return st;
+        CAVMD_HIP_TRY(copy_header(t));
+        // The one commit of the host's state, after the last device copy went through.  A copy that failed above returned with
+        // the host's view as it was; on the device a failed header copy leaves the new order and rows next to the old header
+        // and its (still allocated) old tables, until a set_items over the same items goes through.
+        this->commit(std::move(s));
+        derived.swap(new_derived);
+        tables = std::move(t); // the old arrays are freed here: nothing in flight reads them (stage() has waited)
         return CAVMD_OK;
     }
 };

@@ -75,15 +75,6 @@ constexpr size_t molecular_lds_bytes(unsigned lds_n)
     return (size_t)lds_n * 28 + sizeof(double) * kMolecularMaxTypes * kMolecularMaxTypes * kMolecularPairWords;
 }
 
-__device__ __forceinline__ double molecular_min_image(double d, double L, double h)
-{
-    if (d >= h)
-        d -= L;
-    else if (d < -h)
-        d += L;
-    return d;
-}
-
 // lds_n: the particles the launch has LDS for (frozen with the launch, as the LDS size is); a system beyond it -- a table
 // rewritten after the capture -- gets NaN forces, never an out-of-bounds access.
 template <int BLOCK, int S>
@@ -164,9 +155,9 @@ __global__ __launch_bounds__(BLOCK) void molecular_force_kernel(const MolecularR
         const bool excluded = (j == i) | (j == partner[0]) | (j == partner[1]) | (j == partner[2]) | (j == partner[3]);
         if (excluded || tj >= n_types)
             continue;
-        const double dx = molecular_min_image(xi - sx[j], Lx, hx);
-        const double dy = molecular_min_image(yi - sy[j], Ly, hy);
-        const double dz = molecular_min_image(zi - sz[j], Lz, hz);
+        const double dx = min_image(xi - sx[j], Lx, hx);
+        const double dy = min_image(yi - sy[j], Ly, hy);
+        const double dz = min_image(zi - sz[j], Lz, hz);
         const double rsq = (dx * dx + dy * dy) + dz * dz;
         const double* __restrict__ c = s_pair_i + tj * kMolecularPairWords;
         if (rsq < c[4])
@@ -203,9 +194,9 @@ __global__ __launch_bounds__(BLOCK) void molecular_force_kernel(const MolecularR
         const unsigned p = partner[k], bt = slot[k] >> 16;
         if (p >= n || bt >= n_bond_types) // an empty slot; the library's tables hold nothing else that fails this
             continue;
-        const double dx = molecular_min_image(xi - sx[p], Lx, hx);
-        const double dy = molecular_min_image(yi - sy[p], Ly, hy);
-        const double dz = molecular_min_image(zi - sz[p], Lz, hz);
+        const double dx = min_image(xi - sx[p], Lx, hx);
+        const double dy = min_image(yi - sy[p], Ly, hy);
+        const double dz = min_image(zi - sz[p], Lz, hz);
         const double rsq = (dx * dx + dy * dy) + dz * dz;
         const double K = prm->bond[bt][0], r0 = prm->bond[bt][1];
         const double rr = sqrt(rsq);

@@ -370,4 +370,15 @@ __device__ __forceinline__ Accum block_reduce(Accum a)
         return block_reduce_generic<BLOCK>(a);
 }
 
+// ---- minimum image ------------------------------------------------------------------------------------------------
+// The image of a separation d along an edge of length L, h = L / 2, that BoxDim::minImage of HOOMD-blue 4.x picks for an
+// orthorhombic periodic box (restated from knowledge; include/cavmd.h carries it as the contract of the two force batches).
+__device__ __forceinline__ double min_image(double d, double L, double h)
+{
+    if (d >= h)
+        d -= L;
+    else if (d < -h)
+        d += L;
+    return d;
+}
 } // namespace cavmd

@@ -5,7 +5,8 @@ The contract is the list of expressions in include/cavmd.h; tests/coulomb_mirror
 the rounding bound a correct fp64 evaluation stays within (tests/test_coulomb_abi.py checks that mirror against physics):
   1. one ragged batch within the mirror's bound, entry by entry, with every edge of the contract planted and counted;
   2. the rock-salt cell through CoulombForceBatch: the Madelung constant, independent of the mirror;
-  3. systems do not see each other, set_items moves results with the items, and an evaluation repeats bit for bit;
+  3. systems do not see each other, set_items moves results with the items (one at a time, and several at once with a larger
+     largest N, a refused call and an item that becomes empty), and an evaluation repeats bit for bit;
   4. {step one, cavity, molecular, Coulomb, step two} replayed from a graph against the same steps enqueued eagerly;
   5. the energy of an NVE run with bonds, Lennard-Jones and Coulomb is conserved to velocity Verlet's second order."""
 import ctypes
@@ -215,6 +216,76 @@ def test_systems_do_not_see_each_other_and_set_items_moves_results():
     coulomb.compute()
     torch.cuda.synchronize()
     assert _same(out[0].cpu().numpy()[:17], clean[3])
+    coulomb.close()
+
+
+def test_set_items_grows_the_middle_refuses_whole_and_empties_an_item():
+    """set_items over two items in the middle that raises the largest N (and with it the LDS of a launch and the number of
+    workgroups of both launches); then a call that is refused at its second item, whose good first item must leave no trace;
+    then an item that becomes empty.  Expected values: the mirror (within the bound it returns) for new systems, and what the
+    same systems gave before the call."""
+    cfgs, sysdefs, bonds, _ = _lattice_batch((2, 2, 3, 2), (1, 2, 3, 4))
+    spare_cfgs, spare_sysdefs, spare_bonds, _ = _lattice_batch((4, 2), (5, 6))
+    coulomb = cavitymd.CoulombForceBatch(sysdefs, bonds, r_cut=8.0, accuracy=1e-4)   # smallest box 16 bohr
+    batch = coulomb.coulomb
+    assert batch.sizes == [17, 17, 55, 17] and batch.launch_order == [2, 0, 1, 3]
+    coulomb.compute()
+    first = [f.cpu().numpy().copy() for f in coulomb.forces]
+    assert all(np.isfinite(f).all() and f[:-1, :3].any() for f in first)
+
+    def item(c, sd, ex, force):
+        pd = sd.getParticleData()
+        return _capi.coulomb_item(len(c["charge"]), pd.getPositions().data_ptr(), pd.getCharges().data_ptr(), force.data_ptr(),
+                                  c["box"], coulomb.kappa, coulomb.r_cut, coulomb.k_cut, ex)
+
+    def offsets_for(k_counts):
+        return list(np.cumsum([0] + [K + 1 for K in k_counts])[:-1])
+
+    assert batch.structure_device_ptr()[1] == offsets_for(coulomb.k_counts)
+
+    # grow in the middle: items 1 and 2 become the spare systems of 129 and 17 particles, each with a fresh output array
+    out = [torch.zeros((len(c["charge"]), 4), dtype=torch.float64, device="cuda") for c in spare_cfgs]
+    new_items = [item(spare_cfgs[j], spare_sysdefs[j], spare_bonds[j], out[j]) for j in range(2)]
+    k_counts = [coulomb.k_counts[0]] + [_capi.coulomb_k_count(it) for it in new_items] + [coulomb.k_counts[3]]
+    torch.cuda.synchronize()
+    batch.set_items(1, new_items)
+    assert batch.sizes == [17, 129, 17, 17] and batch.launch_order == [1, 0, 2, 3]
+    grown_offsets = batch.structure_device_ptr()[1]
+    assert grown_offsets == offsets_for(k_counts) and k_counts[1] > k_counts[2] > 0
+    coulomb.compute()
+    torch.cuda.synchronize()
+    assert _same(coulomb.forces[0].cpu().numpy(), first[0]) and _same(coulomb.forces[3].cpu().numpy(), first[3])
+    grown = [o.cpu().numpy().copy() for o in out]
+    for j, c in enumerate(spare_cfgs):
+        want, bound = mirror.forces(c["position"], c["charge"], c["box"], coulomb.kappa, coulomb.r_cut, coulomb.k_cut, spare_bonds[j])
+        err = np.abs(grown[j] - want)
+        print(f"\nnew item {1 + j}: N = {len(c['charge'])}, K = {k_counts[1 + j]}, largest error / bound = "
+              f"{float((err[bound > 0] / bound[bound > 0]).max()):.4f}")
+        assert grown[j].shape == want.shape and np.isfinite(grown[j]).all() and (err <= bound).all(), j
+
+    # a refused call changes nothing: its first item (the N = 55 system) is good, its second names particle N
+    scratch = [torch.zeros((55, 4), dtype=torch.float64, device="cuda"), torch.zeros((17, 4), dtype=torch.float64, device="cuda")]
+    with pytest.raises(_capi.CavmdError) as e:
+        batch.set_items(1, [item(cfgs[2], sysdefs[2], bonds[2], scratch[0]),
+                            item(cfgs[3], sysdefs[3], np.concatenate([bonds[3], [[0, 17]]]), scratch[1])])
+    assert e.value.status == _capi.CAVMD_ERR_INVALID_VALUE
+    assert batch.sizes == [17, 129, 17, 17] and batch.structure_device_ptr()[1] == grown_offsets
+    coulomb.compute()
+    torch.cuda.synchronize()
+    assert _same(coulomb.forces[0].cpu().numpy(), first[0]) and _same(coulomb.forces[3].cpu().numpy(), first[3])
+    assert _same(out[0].cpu().numpy(), grown[0]) and _same(out[1].cpu().numpy(), grown[1])
+    assert not scratch[0].cpu().numpy().any() and not scratch[1].cpu().numpy().any()
+
+    # item 0 becomes empty: its old force array is no longer written, the others do not notice
+    batch.set_items(0, [_capi.coulomb_item(0, 0, 0, 0, cfgs[0]["box"], coulomb.kappa, coulomb.r_cut, coulomb.k_cut, None)])
+    assert batch.sizes == [0, 129, 17, 17] and batch.launch_order == [1, 2, 3, 0]
+    offsets = batch.structure_device_ptr()[1]
+    assert offsets == offsets_for([0] + k_counts[1:]) and offsets[1] - offsets[0] == 1
+    coulomb.compute()
+    torch.cuda.synchronize()
+    assert _same(coulomb.forces[0].cpu().numpy(), first[0])
+    assert _same(out[0].cpu().numpy(), grown[0]) and _same(out[1].cpu().numpy(), grown[1])
+    assert _same(coulomb.forces[3].cpu().numpy(), first[3])
     coulomb.close()
 
 

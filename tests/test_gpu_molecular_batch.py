@@ -5,7 +5,8 @@ The contract is the list of expressions in include/cavmd.h; tests/molecular_mirr
 the published summation order, and every "bit for bit" check compares uint64 views:
   1. one ragged batch against the mirror, with every edge of the contract planted and counted;
   2. the closed-form answers through MolecularForceBatch, independent of the mirror;
-  3. systems do not see each other, and set_items moves results with the items;
+  3. systems do not see each other, and set_items moves results with the items -- one at a time, and several at once with a
+     larger largest N, a refused call and an item that becomes empty;
   4. {step one, cavity force, molecular force, step two} replayed from a graph against the same steps enqueued eagerly;
   5. the energy of an NVE run is conserved to velocity Verlet's second order, as a CPU twin's is."""
 import numpy as np
@@ -231,6 +232,67 @@ def test_systems_do_not_see_each_other_and_set_items_moves_results():
     mol.compute()
     torch.cuda.synchronize()
     assert _same(out[0].cpu().numpy()[:17], clean[3])
+    mol.close()
+
+
+def test_set_items_grows_the_middle_refuses_whole_and_empties_an_item():
+    """set_items over two items in the middle that raises the largest N (and with it the LDS of a launch and the number of
+    workgroups); then a call that is refused at its second item, whose good first item must leave no trace; then an item that
+    becomes empty.  Expected values: the mirror for new systems, and what the same systems gave before the call."""
+    ROWS, S = _capi.molecular_order()
+    cfgs, sysdefs, bonds, bond_typeid = _lattice_batch((2, 2, 3, 2), (1, 2, 3, 4))
+    spare_cfgs, spare_sysdefs, spare_bonds, spare_bond_typeid = _lattice_batch((4, 2), (5, 6))
+    lj = {pair: dict(p, r_cut=8.0) for pair, p in LJ.items()}                    # the smallest box is 16 bohr
+    mol = cavitymd.MolecularForceBatch(sysdefs, bonds, bond_typeid, HARMONIC, lj)
+    batch = mol.molecular
+    assert batch.sizes == [17, 17, 55, 17] and batch.launch_order == [2, 0, 1, 3]
+    mol.compute()
+    first = [f.cpu().numpy().copy() for f in mol.forces]
+    assert all(np.isfinite(f).all() and f[:-1, :3].any() for f in first)
+
+    def item(c, sd, b, t, force, bad=False):
+        triples = np.concatenate([b, t[:, None]], axis=1)
+        if bad:
+            triples = np.concatenate([triples, [[0, len(c["charge"]), 0]]])         # a pair index equal to N
+        return _capi.molecular_item(len(c["charge"]), sd.getParticleData().getPositions().data_ptr(), force.data_ptr(), c["box"],
+                                    triples)
+
+    # grow in the middle: items 1 and 2 become the spare systems of 129 and 17 particles, each with a fresh output array
+    out = [torch.zeros((len(c["charge"]), 4), dtype=torch.float64, device="cuda") for c in spare_cfgs]
+    torch.cuda.synchronize()
+    batch.set_items(1, [item(spare_cfgs[j], spare_sysdefs[j], spare_bonds[j], spare_bond_typeid[j], out[j]) for j in range(2)])
+    assert batch.sizes == [17, 129, 17, 17] and batch.launch_order == [1, 0, 2, 3]
+    mol.compute()
+    torch.cuda.synchronize()
+    assert _same(mol.forces[0].cpu().numpy(), first[0]) and _same(mol.forces[3].cpu().numpy(), first[3])
+    tab = mirror.tables(mol.params)
+    grown = [o.cpu().numpy().copy() for o in out]
+    for j, c in enumerate(spare_cfgs):
+        triples = np.concatenate([spare_bonds[j], spare_bond_typeid[j][:, None]], axis=1)
+        want = mirror.forces(c["position"], c["typeid"], c["box"], tab, triples, S)
+        assert grown[j].shape == want.shape and _same(grown[j], want), (j, np.abs(grown[j] - want).max())
+
+    # a refused call changes nothing: its first item (the N = 55 system) is good, its second names particle N
+    scratch = [torch.zeros((55, 4), dtype=torch.float64, device="cuda"), torch.zeros((17, 4), dtype=torch.float64, device="cuda")]
+    with pytest.raises(_capi.CavmdError) as e:
+        batch.set_items(1, [item(cfgs[2], sysdefs[2], bonds[2], bond_typeid[2], scratch[0]),
+                            item(cfgs[3], sysdefs[3], bonds[3], bond_typeid[3], scratch[1], bad=True)])
+    assert e.value.status == _capi.CAVMD_ERR_INVALID_VALUE
+    assert batch.sizes == [17, 129, 17, 17]
+    mol.compute()
+    torch.cuda.synchronize()
+    assert _same(mol.forces[0].cpu().numpy(), first[0]) and _same(mol.forces[3].cpu().numpy(), first[3])
+    assert _same(out[0].cpu().numpy(), grown[0]) and _same(out[1].cpu().numpy(), grown[1])
+    assert not scratch[0].cpu().numpy().any() and not scratch[1].cpu().numpy().any()
+
+    # item 0 becomes empty: its old force array is no longer written, the others do not notice
+    batch.set_items(0, [_capi.molecular_item(0, 0, 0, cfgs[0]["box"], None)])
+    assert batch.sizes == [0, 129, 17, 17] and batch.launch_order == [1, 2, 3, 0]
+    mol.compute()
+    torch.cuda.synchronize()
+    assert _same(mol.forces[0].cpu().numpy(), first[0])
+    assert _same(out[0].cpu().numpy(), grown[0]) and _same(out[1].cpu().numpy(), grown[1])
+    assert _same(mol.forces[3].cpu().numpy(), first[3])
     mol.close()
 
 
