@@ -274,35 +274,113 @@ def coulomb_item(N, pos_ptr, charge_ptr, force_ptr, box_L, kappa, r_cut, k_cut, 
     return it
 
 
-# every symbol include/cavmd.h exports; tests check the header and the library against this list
-EXPORTED_SYMBOLS = (
-    "cavmd_coulomb_item_check", "cavmd_coulomb_k_count", "cavmd_coulomb_parameters", "cavmd_coulomb_order",
-    "cavmd_coulomb_create", "cavmd_coulomb_destroy", "cavmd_coulomb_set_items", "cavmd_coulomb_compute",
-    "cavmd_coulomb_structure_device_ptr",
-    "cavmd_molecular_pair_make", "cavmd_molecular_params_check", "cavmd_molecular_item_check", "cavmd_molecular_order",
-    "cavmd_molecular_create", "cavmd_molecular_destroy", "cavmd_molecular_set_items", "cavmd_molecular_compute",
-    "cavmd_verlet_item_check", "cavmd_verlet_input_make", "cavmd_verlet_create", "cavmd_verlet_destroy",
-    "cavmd_verlet_set_items", "cavmd_verlet_accelerations", "cavmd_verlet_step_one", "cavmd_verlet_step_two",
-    "cavmd_verlet_read", "cavmd_verlet_reset", "cavmd_verlet_state_device_ptr",
-    "cavmd_field_recorder_item_check", "cavmd_field_recorder_create", "cavmd_field_recorder_destroy",
-    "cavmd_field_recorder_set_items", "cavmd_field_recorder_record", "cavmd_field_recorder_rows", "cavmd_field_recorder_read",
-    "cavmd_field_recorder_read_fields", "cavmd_field_recorder_reset", "cavmd_field_recorder_device_ptr",
-    "cavmd_recorder_item_check", "cavmd_recorder_create", "cavmd_recorder_destroy", "cavmd_recorder_set_items",
-    "cavmd_recorder_record", "cavmd_recorder_rows", "cavmd_recorder_read", "cavmd_recorder_reset", "cavmd_recorder_device_ptr",
-    "cavmd_bussi_batch_item_check", "cavmd_bussi_batch_input_make", "cavmd_bussi_batch_create", "cavmd_bussi_batch_destroy",
-    "cavmd_bussi_batch_set_items", "cavmd_bussi_batch_step", "cavmd_bussi_batch_last_sequence", "cavmd_bussi_batch_read",
-    "cavmd_bussi_batch_reset", "cavmd_bussi_batch_state_device_ptr",
-    "cavmd_batch_item_check", "cavmd_batch_create", "cavmd_batch_destroy", "cavmd_batch_set_items", "cavmd_batch_compute",
-    "cavmd_batch_last_sequence", "cavmd_batch_results_read", "cavmd_batch_results_at", "cavmd_batch_energies_at",
-    "cavmd_batch_results_device_ptr",
-    "cavmd_make_params", "cavmd_create", "cavmd_destroy", "cavmd_compute_hoomd", "cavmd_compute_soa",
-    "cavmd_energies", "cavmd_result_read", "cavmd_result_device_ptr", "cavmd_last_sequence", "cavmd_result_at",
-    "cavmd_energies_at", "cavmd_set_wavevectors", "cavmd_density_field",
-    "cavmd_density_field_read", "cavmd_cavity_mode", "cavmd_force_mass_sum", "cavmd_kinetic_energy", "cavmd_scale_velocities",
-    "cavmd_bussi_step_device", "cavmd_bussi_device_read", "cavmd_bussi_device_reset",
-    "cavmd_bussi_rescale_factor", "cavmd_bussi_step", "cavmd_profile_enable", "cavmd_profile_read", "cavmd_profile_samples",
-    "cavmd_set_tunable", "cavmd_get_tunable", "cavmd_device_info", "cavmd_error_string", "cavmd_version",
-)
+_vp, _sz, _dbl, _ci, _cstr = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_char_p
+_u32, _u64, _P = ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER
+
+# Every symbol include/cavmd.h exports, in the header's order: symbol -> (restype, argtypes).  Tests check the header and the
+# library against this table, down to the number of parameters: without a prototype ctypes passes a pointer as a C int.
+_PROTOTYPES = {
+    "cavmd_make_params": (Params, [_dbl, _dbl, _dbl]),
+    "cavmd_create": (_ci, [_ci, _sz, _P(_vp)]),
+    "cavmd_destroy": (_ci, [_vp]),
+    "cavmd_compute_hoomd": (_ci, [_vp, _vp, _sz, _vp, _vp, _vp, _dbl, _dbl, _dbl, _ci, _P(Params), _vp]),
+    "cavmd_compute_soa": (_ci, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _dbl, _dbl, _ci, _P(Params), _vp,
+                                 _sz, _vp, _sz]),
+    "cavmd_energies": (_ci, [_vp, _P(_dbl * 3)]),
+    "cavmd_result_read": (_ci, [_vp, _P(Result)]),
+    "cavmd_result_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_last_sequence": (_ci, [_vp, _P(_u64)]),
+    "cavmd_result_at": (_ci, [_vp, _u64, _P(Result)]),
+    "cavmd_energies_at": (_ci, [_vp, _u64, _P(_dbl * 3)]),
+    "cavmd_batch_item_check": (_ci, [_P(BatchItem)]),
+    "cavmd_batch_create": (_ci, [_vp, _sz, _P(BatchItem), _ci, _P(_vp)]),
+    "cavmd_batch_destroy": (_ci, [_vp]),
+    "cavmd_batch_set_items": (_ci, [_vp, _sz, _sz, _P(BatchItem)]),
+    "cavmd_batch_compute": (_ci, [_vp, _vp]),
+    "cavmd_batch_last_sequence": (_ci, [_vp, _P(_u64)]),
+    "cavmd_batch_results_read": (_ci, [_vp, _P(Result)]),
+    "cavmd_batch_results_at": (_ci, [_vp, _u64, _P(Result)]),
+    "cavmd_batch_energies_at": (_ci, [_vp, _u64, _vp]),
+    "cavmd_batch_results_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_set_wavevectors": (_ci, [_vp, _sz, _vp]),
+    "cavmd_density_field": (_ci, [_vp, _vp, _sz, _vp, _sz]),
+    "cavmd_density_field_read": (_ci, [_vp, _vp]),
+    "cavmd_cavity_mode": (_ci, [_vp, _vp, _vp, _dbl, _P(_dbl * 4)]),
+    "cavmd_force_mass_sum": (_ci, [_vp, _vp, _sz, _vp, _vp, _P(_dbl)]),
+    "cavmd_kinetic_energy": (_ci, [_vp, _vp, _vp, _vp, _sz, _P(_dbl)]),
+    "cavmd_scale_velocities": (_ci, [_vp, _vp, _vp, _vp, _sz, _dbl]),
+    "cavmd_bussi_rescale_factor": (_ci, [_dbl] * 7 + [_P(_dbl)]),
+    "cavmd_bussi_step": (_ci, [_P(BussiReservoirState), _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _P(_dbl * 4), _P(_dbl * 2)]),
+    "cavmd_bussi_step_device": (_ci, [_vp, _vp, _vp, _vp, _sz] + [_dbl] * 6),
+    "cavmd_bussi_device_read": (_ci, [_vp, _P(BussiDeviceState)]),
+    "cavmd_bussi_device_reset": (_ci, [_vp, _vp]),
+    "cavmd_bussi_batch_item_check": (_ci, [_P(BussiBatchItem)]),
+    "cavmd_bussi_batch_input_make": (_ci, [_dbl] * 5 + [_P(BussiBatchInput)]),
+    "cavmd_bussi_batch_create": (_ci, [_vp, _sz, _P(BussiBatchItem), _P(_vp)]),
+    "cavmd_bussi_batch_destroy": (_ci, [_vp]),
+    "cavmd_bussi_batch_set_items": (_ci, [_vp, _sz, _sz, _P(BussiBatchItem)]),
+    "cavmd_bussi_batch_step": (_ci, [_vp, _vp, _vp]),
+    "cavmd_bussi_batch_last_sequence": (_ci, [_vp, _P(_u64)]),
+    "cavmd_bussi_batch_read": (_ci, [_vp, _P(BussiDeviceState)]),
+    "cavmd_bussi_batch_reset": (_ci, [_vp, _vp]),
+    "cavmd_bussi_batch_state_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_recorder_item_check": (_ci, [_P(RecorderItem)]),
+    "cavmd_recorder_create": (_ci, [_vp, _sz, _P(RecorderItem), _sz, _u64, _dbl, _P(_vp)]),
+    "cavmd_recorder_destroy": (_ci, [_vp]),
+    "cavmd_recorder_set_items": (_ci, [_vp, _sz, _sz, _P(RecorderItem)]),
+    "cavmd_recorder_record": (_ci, [_vp, _vp]),
+    "cavmd_recorder_rows": (_ci, [_vp, _vp, _vp]),
+    "cavmd_recorder_read": (_ci, [_vp, _vp, _sz, _sz, _u64, _sz, _vp]),
+    "cavmd_recorder_reset": (_ci, [_vp, _vp]),
+    "cavmd_recorder_device_ptr": (_ci, [_vp, _P(_vp), _P(_vp)]),
+    "cavmd_field_recorder_item_check": (_ci, [_P(FieldItem)]),
+    "cavmd_field_recorder_create": (_ci, [_vp, _sz, _P(FieldItem), _sz, _vp, _sz, _u64, _u32, _u64, _P(_vp)]),
+    "cavmd_field_recorder_destroy": (_ci, [_vp]),
+    "cavmd_field_recorder_set_items": (_ci, [_vp, _sz, _sz, _P(FieldItem)]),
+    "cavmd_field_recorder_record": (_ci, [_vp, _vp, _vp]),
+    "cavmd_field_recorder_rows": (_ci, [_vp, _vp, _vp]),
+    "cavmd_field_recorder_read": (_ci, [_vp, _vp, _sz, _sz, _u64, _sz, _vp]),
+    "cavmd_field_recorder_read_fields": (_ci, [_vp, _vp, _sz, _vp, _vp, _vp, _P(_u32)]),
+    "cavmd_field_recorder_reset": (_ci, [_vp, _vp]),
+    "cavmd_field_recorder_device_ptr": (_ci, [_vp, _P(_vp), _P(_vp)]),
+    "cavmd_verlet_item_check": (_ci, [_P(VerletItem)]),
+    "cavmd_verlet_input_make": (_ci, [_dbl, _dbl, _dbl, _P(_dbl * 3), _P(VerletInput)]),
+    "cavmd_verlet_create": (_ci, [_vp, _sz, _P(VerletItem), _P(_vp)]),
+    "cavmd_verlet_destroy": (_ci, [_vp]),
+    "cavmd_verlet_set_items": (_ci, [_vp, _sz, _sz, _P(VerletItem)]),
+    "cavmd_verlet_accelerations": (_ci, [_vp, _vp]),
+    "cavmd_verlet_step_one": (_ci, [_vp, _vp, _vp]),
+    "cavmd_verlet_step_two": (_ci, [_vp, _vp, _vp]),
+    "cavmd_verlet_read": (_ci, [_vp, _vp, _vp]),
+    "cavmd_verlet_reset": (_ci, [_vp, _vp]),
+    "cavmd_verlet_state_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_molecular_pair_make": (_ci, [_dbl, _dbl, _dbl, _ci, _P(MolecularPair)]),
+    "cavmd_molecular_params_check": (_ci, [_P(MolecularParams)]),
+    "cavmd_molecular_item_check": (_ci, [_P(MolecularParams), _P(MolecularItem)]),
+    "cavmd_molecular_order": (_ci, [_P(_ci), _P(_ci)]),
+    "cavmd_molecular_create": (_ci, [_vp, _P(MolecularParams), _sz, _P(MolecularItem), _P(_vp)]),
+    "cavmd_molecular_destroy": (_ci, [_vp]),
+    "cavmd_molecular_set_items": (_ci, [_vp, _sz, _sz, _P(MolecularItem)]),
+    "cavmd_molecular_compute": (_ci, [_vp, _vp]),
+    "cavmd_coulomb_item_check": (_ci, [_P(CoulombItem)]),
+    "cavmd_coulomb_k_count": (_ci, [_P(CoulombItem), _P(_u32)]),
+    "cavmd_coulomb_parameters": (_ci, [_dbl, _dbl, _P(_dbl), _P(_dbl)]),
+    "cavmd_coulomb_order": (_ci, [_P(_ci)] * 4),
+    "cavmd_coulomb_create": (_ci, [_vp, _sz, _P(CoulombItem), _P(_vp)]),
+    "cavmd_coulomb_destroy": (_ci, [_vp]),
+    "cavmd_coulomb_set_items": (_ci, [_vp, _sz, _sz, _P(CoulombItem)]),
+    "cavmd_coulomb_compute": (_ci, [_vp, _vp]),
+    "cavmd_coulomb_structure_device_ptr": (_ci, [_vp, _P(_vp), _P(_P(_u32))]),
+    "cavmd_profile_enable": (_ci, [_vp, _ci]),
+    "cavmd_profile_read": (_ci, [_vp, _P(_dbl * 3), _P(_u64)]),
+    "cavmd_profile_samples": (_ci, [_vp, _vp, _sz, _P(_sz)]),
+    "cavmd_set_tunable": (_ci, [_vp, _cstr, _ci]),
+    "cavmd_get_tunable": (_ci, [_vp, _cstr, _P(_ci)]),
+    "cavmd_device_info": (_ci, [_vp, _P(_ci), _P(_ci), _cstr, _sz]),
+    "cavmd_error_string": (_cstr, [_ci]),
+    "cavmd_version": (_ci, []),
+}
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
 _lib = None
 _lock = threading.Lock()
@@ -379,210 +457,11 @@ def load_split_variant(name: str):
 
 
 def _declare(lib):
-    if True:
-        vp, sz, dbl, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int
-        P = ctypes.POINTER
-        lib.cavmd_make_params.argtypes = [dbl, dbl, dbl]
-        lib.cavmd_make_params.restype = Params
-        lib.cavmd_create.argtypes = [ci, sz, P(vp)]
-        lib.cavmd_create.restype = ci
-        lib.cavmd_destroy.argtypes = [vp]
-        lib.cavmd_destroy.restype = ci
-        lib.cavmd_compute_hoomd.argtypes = [vp, vp, sz, vp, vp, vp, dbl, dbl, dbl, ci, P(Params), vp]
-        lib.cavmd_compute_hoomd.restype = ci
-        lib.cavmd_compute_soa.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, dbl, dbl, dbl, ci, P(Params), vp,
-                                          sz, vp, sz]
-        lib.cavmd_compute_soa.restype = ci
-        lib.cavmd_energies.argtypes = [vp, P(dbl * 3)]
-        lib.cavmd_energies.restype = ci
-        lib.cavmd_result_read.argtypes = [vp, P(Result)]
-        lib.cavmd_result_read.restype = ci
-        lib.cavmd_result_device_ptr.argtypes = [vp, P(vp)]
-        lib.cavmd_result_device_ptr.restype = ci
-        lib.cavmd_last_sequence.argtypes = [vp, P(ctypes.c_uint64)]
-        lib.cavmd_last_sequence.restype = ci
-        lib.cavmd_result_at.argtypes = [vp, ctypes.c_uint64, P(Result)]
-        lib.cavmd_result_at.restype = ci
-        lib.cavmd_energies_at.argtypes = [vp, ctypes.c_uint64, P(dbl * 3)]
-        lib.cavmd_energies_at.restype = ci
-        u64 = ctypes.c_uint64
-        lib.cavmd_batch_item_check.argtypes = [P(BatchItem)]
-        lib.cavmd_batch_item_check.restype = ci
-        lib.cavmd_batch_create.argtypes = [vp, sz, P(BatchItem), ci, P(vp)]
-        lib.cavmd_batch_create.restype = ci
-        lib.cavmd_batch_destroy.argtypes = [vp]
-        lib.cavmd_batch_destroy.restype = ci
-        lib.cavmd_batch_set_items.argtypes = [vp, sz, sz, P(BatchItem)]
-        lib.cavmd_batch_set_items.restype = ci
-        lib.cavmd_batch_compute.argtypes = [vp, vp]
-        lib.cavmd_batch_compute.restype = ci
-        lib.cavmd_batch_last_sequence.argtypes = [vp, P(u64)]
-        lib.cavmd_batch_last_sequence.restype = ci
-        lib.cavmd_batch_results_read.argtypes = [vp, P(Result)]
-        lib.cavmd_batch_results_read.restype = ci
-        lib.cavmd_batch_results_at.argtypes = [vp, u64, P(Result)]
-        lib.cavmd_batch_results_at.restype = ci
-        lib.cavmd_batch_energies_at.argtypes = [vp, u64, vp]
-        lib.cavmd_batch_energies_at.restype = ci
-        lib.cavmd_batch_results_device_ptr.argtypes = [vp, P(vp)]
-        lib.cavmd_batch_results_device_ptr.restype = ci
-        lib.cavmd_set_wavevectors.argtypes = [vp, sz, vp]
-        lib.cavmd_set_wavevectors.restype = ci
-        lib.cavmd_density_field.argtypes = [vp, vp, sz, vp, sz]
-        lib.cavmd_density_field.restype = ci
-        lib.cavmd_density_field_read.argtypes = [vp, vp]
-        lib.cavmd_density_field_read.restype = ci
-        lib.cavmd_cavity_mode.argtypes = [vp, vp, vp, dbl, P(dbl * 4)]
-        lib.cavmd_cavity_mode.restype = ci
-        lib.cavmd_force_mass_sum.argtypes = [vp, vp, sz, vp, vp, P(dbl)]
-        lib.cavmd_force_mass_sum.restype = ci
-        lib.cavmd_kinetic_energy.argtypes = [vp, vp, vp, vp, sz, P(dbl)]
-        lib.cavmd_kinetic_energy.restype = ci
-        lib.cavmd_scale_velocities.argtypes = [vp, vp, vp, vp, sz, dbl]
-        lib.cavmd_scale_velocities.restype = ci
-        lib.cavmd_bussi_rescale_factor.argtypes = [dbl] * 7 + [P(dbl)]
-        lib.cavmd_bussi_rescale_factor.restype = ci
-        lib.cavmd_bussi_step.argtypes = [P(BussiReservoirState), dbl, dbl, dbl, dbl, dbl, dbl, dbl, P(dbl * 4), P(dbl * 2)]
-        lib.cavmd_bussi_step.restype = ci
-        lib.cavmd_bussi_step_device.argtypes = [vp, vp, vp, vp, sz] + [dbl] * 6
-        lib.cavmd_bussi_step_device.restype = ci
-        lib.cavmd_bussi_device_read.argtypes = [vp, P(BussiDeviceState)]
-        lib.cavmd_bussi_device_read.restype = ci
-        lib.cavmd_bussi_device_reset.argtypes = [vp, vp]
-        lib.cavmd_bussi_device_reset.restype = ci
-        lib.cavmd_bussi_batch_item_check.argtypes = [P(BussiBatchItem)]
-        lib.cavmd_bussi_batch_item_check.restype = ci
-        lib.cavmd_bussi_batch_input_make.argtypes = [dbl] * 5 + [P(BussiBatchInput)]
-        lib.cavmd_bussi_batch_input_make.restype = ci
-        lib.cavmd_bussi_batch_create.argtypes = [vp, sz, P(BussiBatchItem), P(vp)]
-        lib.cavmd_bussi_batch_create.restype = ci
-        lib.cavmd_bussi_batch_destroy.argtypes = [vp]
-        lib.cavmd_bussi_batch_destroy.restype = ci
-        lib.cavmd_bussi_batch_set_items.argtypes = [vp, sz, sz, P(BussiBatchItem)]
-        lib.cavmd_bussi_batch_set_items.restype = ci
-        lib.cavmd_bussi_batch_step.argtypes = [vp, vp, vp]
-        lib.cavmd_bussi_batch_step.restype = ci
-        lib.cavmd_bussi_batch_last_sequence.argtypes = [vp, P(u64)]
-        lib.cavmd_bussi_batch_last_sequence.restype = ci
-        lib.cavmd_bussi_batch_read.argtypes = [vp, P(BussiDeviceState)]
-        lib.cavmd_bussi_batch_read.restype = ci
-        lib.cavmd_bussi_batch_reset.argtypes = [vp, vp]
-        lib.cavmd_bussi_batch_reset.restype = ci
-        lib.cavmd_bussi_batch_state_device_ptr.argtypes = [vp, P(vp)]
-        lib.cavmd_bussi_batch_state_device_ptr.restype = ci
-        lib.cavmd_recorder_item_check.argtypes = [P(RecorderItem)]
-        lib.cavmd_recorder_item_check.restype = ci
-        lib.cavmd_recorder_create.argtypes = [vp, sz, P(RecorderItem), sz, u64, dbl, P(vp)]
-        lib.cavmd_recorder_create.restype = ci
-        lib.cavmd_recorder_destroy.argtypes = [vp]
-        lib.cavmd_recorder_destroy.restype = ci
-        lib.cavmd_recorder_set_items.argtypes = [vp, sz, sz, P(RecorderItem)]
-        lib.cavmd_recorder_set_items.restype = ci
-        lib.cavmd_recorder_record.argtypes = [vp, vp]
-        lib.cavmd_recorder_record.restype = ci
-        lib.cavmd_recorder_rows.argtypes = [vp, vp, vp]
-        lib.cavmd_recorder_rows.restype = ci
-        lib.cavmd_recorder_read.argtypes = [vp, vp, sz, sz, u64, sz, vp]
-        lib.cavmd_recorder_read.restype = ci
-        lib.cavmd_recorder_reset.argtypes = [vp, vp]
-        lib.cavmd_recorder_reset.restype = ci
-        lib.cavmd_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
-        lib.cavmd_recorder_device_ptr.restype = ci
-    if hasattr(lib, "cavmd_field_recorder_create"):
-        u32 = ctypes.c_uint32
-        lib.cavmd_field_recorder_item_check.argtypes = [P(FieldItem)]
-        lib.cavmd_field_recorder_item_check.restype = ci
-        lib.cavmd_field_recorder_create.argtypes = [vp, sz, P(FieldItem), sz, vp, sz, u64, u32, u64, P(vp)]
-        lib.cavmd_field_recorder_create.restype = ci
-        lib.cavmd_field_recorder_destroy.argtypes = [vp]
-        lib.cavmd_field_recorder_destroy.restype = ci
-        lib.cavmd_field_recorder_set_items.argtypes = [vp, sz, sz, P(FieldItem)]
-        lib.cavmd_field_recorder_set_items.restype = ci
-        lib.cavmd_field_recorder_record.argtypes = [vp, vp, vp]
-        lib.cavmd_field_recorder_record.restype = ci
-        lib.cavmd_field_recorder_rows.argtypes = [vp, vp, vp]
-        lib.cavmd_field_recorder_rows.restype = ci
-        lib.cavmd_field_recorder_read.argtypes = [vp, vp, sz, sz, u64, sz, vp]
-        lib.cavmd_field_recorder_read.restype = ci
-        lib.cavmd_field_recorder_read_fields.argtypes = [vp, vp, sz, vp, vp, vp, P(u32)]
-        lib.cavmd_field_recorder_read_fields.restype = ci
-        lib.cavmd_field_recorder_reset.argtypes = [vp, vp]
-        lib.cavmd_field_recorder_reset.restype = ci
-        lib.cavmd_field_recorder_device_ptr.argtypes = [vp, P(vp), P(vp)]
-        lib.cavmd_field_recorder_device_ptr.restype = ci
-        lib.cavmd_verlet_item_check.argtypes = [P(VerletItem)]
-        lib.cavmd_verlet_item_check.restype = ci
-        lib.cavmd_verlet_input_make.argtypes = [dbl, dbl, dbl, P(dbl * 3), P(VerletInput)]
-        lib.cavmd_verlet_input_make.restype = ci
-        lib.cavmd_verlet_create.argtypes = [vp, sz, P(VerletItem), P(vp)]
-        lib.cavmd_verlet_create.restype = ci
-        lib.cavmd_verlet_destroy.argtypes = [vp]
-        lib.cavmd_verlet_destroy.restype = ci
-        lib.cavmd_verlet_set_items.argtypes = [vp, sz, sz, P(VerletItem)]
-        lib.cavmd_verlet_set_items.restype = ci
-        lib.cavmd_verlet_accelerations.argtypes = [vp, vp]
-        lib.cavmd_verlet_accelerations.restype = ci
-        lib.cavmd_verlet_step_one.argtypes = [vp, vp, vp]
-        lib.cavmd_verlet_step_one.restype = ci
-        lib.cavmd_verlet_step_two.argtypes = [vp, vp, vp]
-        lib.cavmd_verlet_step_two.restype = ci
-        lib.cavmd_verlet_read.argtypes = [vp, vp, vp]
-        lib.cavmd_verlet_read.restype = ci
-        lib.cavmd_verlet_reset.argtypes = [vp, vp]
-        lib.cavmd_verlet_reset.restype = ci
-        lib.cavmd_verlet_state_device_ptr.argtypes = [vp, P(vp)]
-        lib.cavmd_verlet_state_device_ptr.restype = ci
-        lib.cavmd_molecular_pair_make.argtypes = [dbl, dbl, dbl, ci, P(MolecularPair)]
-        lib.cavmd_molecular_pair_make.restype = ci
-        lib.cavmd_molecular_params_check.argtypes = [P(MolecularParams)]
-        lib.cavmd_molecular_params_check.restype = ci
-        lib.cavmd_molecular_item_check.argtypes = [P(MolecularParams), P(MolecularItem)]
-        lib.cavmd_molecular_item_check.restype = ci
-        lib.cavmd_molecular_order.argtypes = [P(ci), P(ci)]
-        lib.cavmd_molecular_order.restype = ci
-        lib.cavmd_molecular_create.argtypes = [vp, P(MolecularParams), sz, P(MolecularItem), P(vp)]
-        lib.cavmd_molecular_create.restype = ci
-        lib.cavmd_molecular_destroy.argtypes = [vp]
-        lib.cavmd_molecular_destroy.restype = ci
-        lib.cavmd_molecular_set_items.argtypes = [vp, sz, sz, P(MolecularItem)]
-        lib.cavmd_molecular_set_items.restype = ci
-        lib.cavmd_molecular_compute.argtypes = [vp, vp]
-        lib.cavmd_molecular_compute.restype = ci
-        lib.cavmd_coulomb_item_check.argtypes = [P(CoulombItem)]
-        lib.cavmd_coulomb_item_check.restype = ci
-        lib.cavmd_coulomb_k_count.argtypes = [P(CoulombItem), P(ctypes.c_uint32)]
-        lib.cavmd_coulomb_k_count.restype = ci
-        lib.cavmd_coulomb_parameters.argtypes = [dbl, dbl, P(dbl), P(dbl)]
-        lib.cavmd_coulomb_parameters.restype = ci
-        lib.cavmd_coulomb_order.argtypes = [P(ci)] * 4
-        lib.cavmd_coulomb_order.restype = ci
-        lib.cavmd_coulomb_create.argtypes = [vp, sz, P(CoulombItem), P(vp)]
-        lib.cavmd_coulomb_create.restype = ci
-        lib.cavmd_coulomb_destroy.argtypes = [vp]
-        lib.cavmd_coulomb_destroy.restype = ci
-        lib.cavmd_coulomb_set_items.argtypes = [vp, sz, sz, P(CoulombItem)]
-        lib.cavmd_coulomb_set_items.restype = ci
-        lib.cavmd_coulomb_compute.argtypes = [vp, vp]
-        lib.cavmd_coulomb_compute.restype = ci
-        lib.cavmd_coulomb_structure_device_ptr.argtypes = [vp, P(vp), P(P(ctypes.c_uint32))]
-        lib.cavmd_coulomb_structure_device_ptr.restype = ci
-        lib.cavmd_profile_enable.argtypes = [vp, ci]
-        lib.cavmd_profile_enable.restype = ci
-        lib.cavmd_profile_read.argtypes = [vp, P(dbl * 3), P(ctypes.c_uint64)]
-        lib.cavmd_profile_read.restype = ci
-        lib.cavmd_profile_samples.argtypes = [vp, vp, sz, P(sz)]
-        lib.cavmd_profile_samples.restype = ci
-        lib.cavmd_set_tunable.argtypes = [vp, ctypes.c_char_p, ci]
-        lib.cavmd_set_tunable.restype = ci
-        lib.cavmd_get_tunable.argtypes = [vp, ctypes.c_char_p, P(ci)]
-        lib.cavmd_get_tunable.restype = ci
-        lib.cavmd_device_info.argtypes = [vp, P(ci), P(ci), ctypes.c_char_p, sz]
-        lib.cavmd_device_info.restype = ci
-        lib.cavmd_error_string.argtypes = [ci]
-        lib.cavmd_error_string.restype = ctypes.c_char_p
-        lib.cavmd_version.argtypes = []
-        lib.cavmd_version.restype = ci
-        return lib
+    """Gives every exported symbol of ``lib`` (the product, hooks or a split-variant build) its prototype."""
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def error_string(status: int) -> str:

@@ -6,13 +6,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _capi
-from ._device import stream_handle
+from ._device import HandleOwner, one_device, stream_handle
 
 
-class ForceBatchBase:
-    _handle = _ws = None
-
+class ForceBatchBase(HandleOwner):
     def _systems(self, sysdefs):
         """The particle data of ``sysdefs`` (kept alive here); an empty batch raises."""
         self._sysdefs = list(sysdefs)
@@ -29,11 +26,7 @@ class ForceBatchBase:
                                        "this package")
 
     def _one_device(self, pds) -> None:
-        dev = pds[0].device
-        if any(pd.device != dev for pd in pds):
-            raise ValueError("all systems of one batch live on one device")
-        self._device = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self._device = one_device(pds, "batch")
 
     def _allocate(self, pds):
         """The force arrays, views of one allocation (the energy is then one segmented sum); returns the sizes."""
@@ -45,26 +38,20 @@ class ForceBatchBase:
         self._lengths = torch.tensor(sizes, dtype=torch.int64, device=self._device)
         return sizes
 
-    def _open(self, make_handle) -> None:
+    def _open(self, device, make_handle) -> None:
         """``make_handle(workspace)`` creates the library object over the items."""
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        self._handle = make_handle(self._ws)
+        super()._open(device, make_handle)
         self.n_systems = len(self._sizes)
         torch.cuda.current_stream(self._device).synchronize()   # the zeroed pool is there before any stream computes
 
     def __len__(self) -> int:
         return self.n_systems
 
-    def _need(self):
-        if self._handle is None:
-            raise RuntimeError(f"{type(self).__name__} used after close()")
-
     def compute(self, timestep: int = 0, stream=None) -> None:
         """The object's launches on ``stream`` (default: torch's current stream): every entry of every system's force array.
         May be captured.  ``timestep`` is accepted for signature compatibility with ``CavityForceBatch.compute``; it is not
         used."""
-        self._need()
-        self._handle.compute(stream_handle(stream, self._device))
+        self._need().compute(stream_handle(stream, self._dev_index))
 
     @property
     def forces(self):
@@ -80,16 +67,3 @@ class ForceBatchBase:
         if len(set(self._sizes)) == 1 and self._sizes[0] > 0:
             return w.reshape(self.n_systems, self._sizes[0]).sum(dim=1)
         return torch.segment_reduce(w.contiguous(), "sum", lengths=self._lengths)
-
-    def close(self) -> None:
-        if self._handle is not None:
-            self._handle.close()
-        if self._ws is not None:
-            self._ws.close()
-        self._handle = self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

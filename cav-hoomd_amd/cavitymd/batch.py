@@ -25,8 +25,7 @@ import torch
 
 from . import _capi
 from ._capi import CavmdError
-
-_raw_current_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+from ._device import HandleOwner, stream_handle
 
 
 def _as_params(p) -> _capi.Params:
@@ -76,7 +75,7 @@ class BatchEnergyHistory:
         return self._read(0)
 
 
-class CavityForceBatch:
+class CavityForceBatch(HandleOwner):
     """B systems (``SystemDefinition``s whose arrays live on one GPU), one launch per ``compute()``.  Owns the workspace,
     the batch and the force arrays."""
 
@@ -96,10 +95,8 @@ class CavityForceBatch:
             raise RuntimeError("CavityForceBatch requires every system's particle data in the memory of one GPU (got "
                                f"'{dev}'); no CPU fallback exists in this package")
         self._device = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self._force = [torch.empty((pd.getN(), 4), dtype=torch.float64, device=dev) for pd in pds]
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        self._batch = _capi.Batch(self._ws, [self._item(k) for k in range(len(pds))], history_depth)
+        self._open(dev, lambda ws: _capi.Batch(ws, [self._item(k) for k in range(len(pds))], history_depth))
 
     def _item(self, k: int) -> _capi.BatchItem:
         pd = self._sysdefs[k].getParticleData()
@@ -122,7 +119,7 @@ class CavityForceBatch:
         stream of the last evaluation).  Default: all."""
         idx = range(len(self)) if indices is None else sorted(int(i) for i in indices)
         for k in idx:
-            self._batch.set_items(k, [self._item(k)])
+            self._need().set_items(k, [self._item(k)])
 
     def setParams(self, k: int, omegac: float, couplstr: float, phmass: float = 1.0) -> None:
         self._params[k] = _capi.make_params(omegac, couplstr, phmass)
@@ -132,12 +129,7 @@ class CavityForceBatch:
     def compute(self, timestep: int = 0, stream=None) -> None:
         """Enqueue ONE kernel that evaluates every system, on ``stream`` (default: torch's current stream).  ``timestep`` is
         accepted for signature compatibility with ``CavityForceComputeHIP.compute`` only; it is not used."""
-        if stream is None:
-            handle = _raw_current_stream(self._dev_index) if _raw_current_stream is not None \
-                else torch.cuda.current_stream(self._device).cuda_stream
-        else:
-            handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        self._batch.compute(handle)
+        self._need().compute(stream_handle(stream, self._dev_index))
 
     # -- results --------------------------------------------------------------------------------------------------
     @property
@@ -146,38 +138,30 @@ class CavityForceBatch:
         return list(self._force)
 
     def last_sequence(self) -> int:
-        return self._batch.last_sequence()
+        return self._need().last_sequence()
 
     def energies(self):
         """(B, 3) array of the last evaluation: harmonic, coupling, dipole-self energy per system."""
         import numpy as np
-        return np.array([r.energy[:] for r in self._batch.results()], dtype=np.float64).reshape(len(self), 3)
+        return np.array([r.energy[:] for r in self._need().results()], dtype=np.float64).reshape(len(self), 3)
 
     def energies_at(self, sequence: int):
-        return self._batch.energies_at(sequence)
+        return self._need().energies_at(sequence)
 
     def results(self):
-        return self._batch.results()
+        return self._need().results()
 
     def results_at(self, sequence: int):
-        return self._batch.results_at(sequence)
+        return self._need().results_at(sequence)
 
     def history(self, depth=None) -> BatchEnergyHistory:
         """Record-then-drain bookkeeping over this batch's result ring.  ``depth`` (if given) must not exceed the ring the
         batch was created with (``history_depth``): that many steps may be recorded between drains."""
-        if depth is not None and int(depth) > self._batch.history_depth:
-            raise ValueError(f"history depth {depth} exceeds the batch's result ring ({self._batch.history_depth}); "
+        if depth is not None and int(depth) > self._need().history_depth:
+            raise ValueError(f"history depth {depth} exceeds the batch's result ring ({self._need().history_depth}); "
                              "create the batch with a larger history_depth")
         return BatchEnergyHistory(self)
 
     @property
     def batch(self) -> _capi.Batch:
-        return self._batch
-
-    @property
-    def workspace(self) -> _capi.Workspace:
-        return self._ws
-
-    def close(self) -> None:
-        self._batch.close()
-        self._ws.close()
+        return self._handle

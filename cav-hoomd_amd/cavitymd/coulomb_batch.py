@@ -67,7 +67,7 @@ class CoulombForceBatch(ForceBatchBase):
                     raise ValueError(f"system {k}: k_cut = {self.k_cut:.4g} keeps more than {_capi.COULOMB_MAX_K} k-vectors in its box; "
                                      "ask for a coarser accuracy or a larger r_cut") from e
                 raise
-        self._open(lambda ws: _capi.Coulomb(ws, items))
+        self._open(self._device, lambda ws: _capi.Coulomb(ws, items))
 
     @property
     def coulomb(self) -> _capi.Coulomb:

@@ -31,17 +31,9 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import stream_handle
+from ._device import device_tensor, one_device, stream_handle
 from .recorder import _SeriesRecorder
 from .observables import generate_fibonacci_sphere
-
-
-def _position_tensor(t):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError("BatchFieldRecorder needs the position arrays in GPU memory; no CPU fallback exists in this package")
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] not in (3, 4) or not t.is_contiguous():
-        raise ValueError("every position array must be a contiguous (N,3) or (N,4) float64 tensor (WRAPPED positions)")
-    return t
 
 
 class BatchFieldRecorder(_SeriesRecorder):
@@ -55,30 +47,20 @@ class BatchFieldRecorder(_SeriesRecorder):
     def __init__(self, positions, wavevectors=None, kmag: float = 1.0, num_wavevectors: int = 50, capacity: int = 4096,
                  period: int = 1, max_references: int = 10, reference_interval: int = 10000):
         positions = list(positions)
-        for t in positions:
-            _position_tensor(t)   # CPU tensors are refused before anything else is looked at
+        for t in positions:   # CPU tensors are refused before anything else is looked at
+            device_tensor(t, "BatchFieldRecorder", "position", (3, 4), " (WRAPPED positions)")
         if not positions:
             raise ValueError("BatchFieldRecorder needs at least one system")
-        dev = positions[0].device
-        if any(t.device != dev for t in positions):
-            raise ValueError("all systems of one field recorder live on one device")
+        dev = one_device(positions, "field recorder")
         if wavevectors is None:
             wavevectors = float(kmag) * generate_fibonacci_sphere(int(num_wavevectors))
         self.wavevectors = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)
-        self._device = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self._positions = positions
         items = [_capi.field_item(t.data_ptr() if t.shape[0] else 0, t.shape[1] * 8, t.shape[0]) for t in positions]
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        try:
-            self._recorder = _capi.FieldRecorder(self._ws, items, self.wavevectors, capacity, period, max_references,
-                                                 reference_interval)
-        except Exception:
-            self._ws.close()
-            self._ws = None
-            raise
+        self._open(dev, lambda ws: _capi.FieldRecorder(ws, items, self.wavevectors, capacity, period, max_references,
+                                                       reference_interval))
         self.n_systems = len(positions)
-        self.n_k = self._recorder.n_k
+        self.n_k = self._handle.n_k
         self.capacity, self.period = int(capacity), int(period)
         self.max_references, self.reference_interval = int(max_references), int(reference_interval)
         self._take = None
@@ -87,7 +69,7 @@ class BatchFieldRecorder(_SeriesRecorder):
         """ONE kernel launch on ``stream`` (default: torch's current stream): nothing is waited for; may be captured.
         take_reference: None, or a uint32 / int32 device tensor of B words read when the kernel RUNS (so a captured call
         sees what the tensor holds at each replay): non-zero asks that system to take a reference at this call."""
-        self._need()
+        recorder = self._need()
         ptr = 0
         if take_reference is not None:
             t = take_reference
@@ -98,7 +80,7 @@ class BatchFieldRecorder(_SeriesRecorder):
                 raise ValueError("take_reference: a contiguous int32 / uint32 tensor with one word per system")
             self._take = t   # kept alive for the kernel (and for the graph that captured it)
             ptr = t.data_ptr()
-        self._recorder.record(stream_handle(stream, self._device), ptr)
+        recorder.record(stream_handle(stream, self._dev_index), ptr)
 
     def read(self, first=0, count=None, stream=None) -> np.ndarray:
         """Structured array of shape (B, n), dtype mirroring ``cavmd_field_record``: rows first .. first + count - 1 (0-based
@@ -109,14 +91,4 @@ class BatchFieldRecorder(_SeriesRecorder):
     def fields(self, item: int, stream=None):
         """(rho_now, rho_refs, ref_rows) of one system: the field of its last recorded call (complex, (n_k,)), its stored
         reference fields ((n_refs, n_k)) and the row each was taken at -- what a checkpoint of the tracker needs."""
-        self._need()
-        return self._recorder.read_fields(self._read_stream(stream), int(item))
-
-    def reset(self, stream=None) -> None:
-        """Forget rows, counters and references of every system, ordered on ``stream`` (default: torch's current stream)."""
-        self._need()
-        self._recorder.reset(stream_handle(stream, self._device))
-
-    @property
-    def recorder(self) -> _capi.FieldRecorder:
-        return self._recorder
+        return self._need().read_fields(self._read_stream(stream), int(item))

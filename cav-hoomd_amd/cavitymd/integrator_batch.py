@@ -26,27 +26,10 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import stream_handle
+from ._device import HandleOwner, StepInputs, device_tensor, per_system, stream_handle
 
 
-def _device_tensor(t, what: str, columns: int):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError(f"VerletBatch needs the {what} arrays in GPU memory; no CPU fallback exists in this package")
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != columns or not t.is_contiguous():
-        raise ValueError(f"every {what} array must be a contiguous (N,{columns}) float64 tensor")
-    return t
-
-
-def _per_system(value, n: int, name: str):
-    if value is None or np.isscalar(value):
-        return [value] * n
-    value = list(value)
-    if len(value) != n:
-        raise ValueError(f"{name}: one value, or one per system ({n}), not {len(value)}")
-    return value
-
-
-class VerletBatch:
+class VerletBatch(HandleOwner):
     """force_batch: the ``CavityForceBatch`` whose systems are integrated (positions, images and boxes are taken from its
     system definitions, its force arrays are the first force of every system); velocities: one (N_k, 4) device tensor per
     system (mass in column 3); extra_forces: None, or per system a list of up to three more (N_k, 4) force tensors, summed
@@ -56,7 +39,7 @@ class VerletBatch:
     def __init__(self, force_batch, velocities, extra_forces=None, langevin_index=None, net_forces: bool = False):
         velocities = list(velocities)
         for v in velocities:
-            _device_tensor(v, "velocity", 4)   # CPU tensors are refused before anything else is looked at
+            device_tensor(v, "VerletBatch", "velocity")   # CPU tensors are refused before anything else is looked at
         B = len(force_batch)
         if len(velocities) != B:
             raise ValueError(f"velocities: one entry per system of the force batch ({B})")
@@ -64,11 +47,10 @@ class VerletBatch:
         if len(extra_forces) != B:
             raise ValueError("extra_forces: None, or one list per system")
         extra_forces = [[] if e is None else list(e) for e in extra_forces]
-        langevin = [-1 if i is None else int(i) for i in _per_system(langevin_index, B, "langevin_index")]
+        langevin = [-1 if i is None else int(i) for i in per_system(langevin_index, B, "langevin_index")]
         sysdefs = force_batch._sysdefs
         forces = force_batch.forces
         dev = velocities[0].device if B else None
-        self._device = dev
         self.accel, self.net_forces, items = [], ([] if net_forces else None), []
         for k in range(B):
             pd = sysdefs[k].getParticleData()
@@ -81,7 +63,7 @@ class VerletBatch:
             if len(extra_forces[k]) > 3:
                 raise ValueError(f"system {k}: at most three extra force arrays")
             for f in extra_forces[k]:
-                if _device_tensor(f, "force", 4).shape[0] != n or f.device != dev:
+                if device_tensor(f, "VerletBatch", "force").shape[0] != n or f.device != dev:
                     raise ValueError(f"system {k}: an extra force array does not match the system")
             a = torch.zeros((n, 3), dtype=torch.float64, device=dev)
             self.accel.append(a)
@@ -95,26 +77,18 @@ class VerletBatch:
                                            [f.data_ptr() if n else 0 for f in flist], net.data_ptr() if (net is not None and n) else 0,
                                            pd.getGlobalBox().getL(), langevin[k]))
         self._force_batch, self._velocities, self._extra = force_batch, velocities, extra_forces
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        self._verlet = _capi.Verlet(self._ws, items)
+        self._open(dev, lambda ws: _capi.Verlet(ws, items))
         self.n_systems = B
-        self.inputs = torch.zeros((B, 8), dtype=torch.float64, device=dev)
-        self.inputs[:, 6] = 1.0   # a non-zero skip word: every system is skipped until its inputs are set
-        self._pinned = torch.zeros((B, 8), dtype=torch.float64).pin_memory()
-        self._copy_done = None
+        self._step_inputs = StepInputs(B, dev, skip_column=6)
+        self.inputs = self._step_inputs.tensor
         self._stream = 0
         torch.cuda.current_stream(dev).synchronize()   # accel, inputs and the states are zero before any stream steps
-
-    def _need(self):
-        if self._verlet is None:
-            raise RuntimeError("VerletBatch used after close()")
 
     # -- the step's inputs -------------------------------------------------------------------------------------------------
     def _rows(self, dt, gamma, kT, uniforms=None) -> np.ndarray:
         """(B, 8) host rows made by cavmd_verlet_input_make; dt, gamma, kT: one number or one per system."""
         B = self.n_systems
-        dts, gammas, kTs = (_per_system(x, B, name) for x, name in ((dt, "dt"), (gamma, "gamma"), (kT, "kT")))
+        dts, gammas, kTs = (per_system(x, B, name) for x, name in ((dt, "dt"), (gamma, "gamma"), (kT, "kT")))
         u = np.zeros((B, 3)) if uniforms is None else np.asarray(uniforms, dtype=np.float64)
         if u.shape != (B, 3):
             raise ValueError(f"uniforms must have shape ({B}, 3)")
@@ -127,71 +101,48 @@ class VerletBatch:
         """uniforms: None (no bath: zeros) or a (B, 3) host array of variates in [-1, 1).  The rows reach ``inputs`` with one
         asynchronous copy on the current stream."""
         self._need()
-        if self._copy_done is not None:
-            self._copy_done.synchronize()                       # the staging buffer's last copy has left it
-        self._pinned.numpy()[:] = self._rows(dt, gamma, kT, uniforms)
-        self.inputs.copy_(self._pinned, non_blocking=True)
-        self._copy_done = torch.cuda.Event()
-        self._copy_done.record(torch.cuda.current_stream(self._device))
+        self._step_inputs.upload(self._rows(dt, gamma, kT, uniforms))
 
     def draw_inputs(self, dt, gamma, kT, generator=None) -> None:
         """Fills ``inputs`` ON THE DEVICE, in stream order, with no host wait: the variates as ``2 * torch.rand - 1``, the rest
         from host arithmetic (uploaded only when it changes).  Capturable together with the two half-steps."""
         self._need()
         const = self._rows(dt, gamma, kT)
-        key = const.tobytes()
-        if getattr(self, "_const_key", None) != key:
-            self._const_dev = torch.from_numpy(const).to(self._device)
-            self._const_key = key
         u = torch.rand((self.n_systems, 3), dtype=torch.float64, device=self._device, generator=generator)
-        self.inputs.copy_(self._const_dev)
+        self._step_inputs.fill_constants(const)
         self.inputs[:, 3:6] = 2.0 * u - 1.0
 
     # -- the launches ------------------------------------------------------------------------------------------------------
     def _launch(self, call, stream, *args) -> None:
-        self._need()
-        handle = stream_handle(stream, self._device)
-        call(handle, *args)
+        verlet = self._need()
+        handle = stream_handle(stream, self._dev_index)
+        call(verlet, handle, *args)
         self._stream = handle
 
     def prime(self, stream=None) -> None:
         """ONE kernel: ``accel`` = F / m from the force arrays as they are (after a ``force_batch.compute()``)."""
-        self._launch(self._verlet.accelerations, stream)
+        self._launch(_capi.Verlet.accelerations, stream)
 
     def step_one(self, stream=None) -> None:
         """ONE kernel: v += (a / 2) dt, x += dt v, one wrap per axis with the image following.  May be captured."""
-        self._launch(self._verlet.step_one, stream, self.inputs.data_ptr())
+        self._launch(_capi.Verlet.step_one, stream, self.inputs.data_ptr())
 
     def step_two(self, stream=None) -> None:
         """ONE kernel: F = sum of the force arrays (+ the bath on the Langevin particle), a = F / m, v += (a / 2) dt."""
-        self._launch(self._verlet.step_two, stream, self.inputs.data_ptr())
+        self._launch(_capi.Verlet.step_two, stream, self.inputs.data_ptr())
 
     def state(self, stream=None) -> np.ndarray:
         """Per-system counters (``steps``, ``out_of_box``, ``langevin_reservoir``).  Default: waits for the whole device (a
         graph replays on the stream it is launched on), then reads; never inside a capture."""
-        self._need()
+        verlet = self._need()
         if stream is None:
             torch.cuda.synchronize(self._device)
-        return self._verlet.read(stream_handle(stream, self._device))
+        return verlet.read(stream_handle(stream, self._dev_index))
 
     def reset(self, stream=None) -> None:
         """Zero every system's counters, ordered on ``stream`` (default: torch's current stream)."""
-        self._need()
-        self._verlet.reset(stream_handle(stream, self._device))
+        self._need().reset(stream_handle(stream, self._dev_index))
 
     @property
     def verlet(self) -> _capi.Verlet:
-        return self._verlet
-
-    def close(self) -> None:
-        if getattr(self, "_verlet", None) is not None:
-            self._verlet.close()
-        if getattr(self, "_ws", None) is not None:
-            self._ws.close()
-        self._verlet = self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._handle

@@ -65,7 +65,7 @@ class MolecularForceBatch(ForceBatchBase):
             n = sizes[k]
             items.append(_capi.molecular_item(n, pd.getPositions().data_ptr() if n else 0,
                                               self._force[k].data_ptr() if n else 0, pd.getGlobalBox().getL(), triples))
-        self._open(lambda ws: _capi.Molecular(ws, self.params, items))
+        self._open(self._device, lambda ws: _capi.Molecular(ws, self.params, items))
 
     @property
     def molecular(self) -> _capi.Molecular:

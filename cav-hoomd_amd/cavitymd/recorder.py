@@ -26,66 +26,52 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import member_indices, stream_handle
+from ._device import HandleOwner, device_tensor, member_indices, stream_handle
 from .utils import PhysicalConstants
 
 
 def _device_tensor(t, what: str):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError(f"BatchRecorder needs the {what} arrays in GPU memory; no CPU fallback exists in this package")
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
-        raise ValueError(f"every {what} array must be a contiguous (N,4) float64 tensor (HOOMD Scalar4)")
-    return t
+    return device_tensor(t, "BatchRecorder", what, note=" (HOOMD Scalar4)")
 
 
-class _SeriesRecorder:
-    """What ``BatchRecorder`` and ``BatchFieldRecorder`` share: the stream a read waits for, the default window of
-    ``read()`` and the release.  A subclass sets ``_device``, ``_ws``, ``_recorder``, ``n_systems``, ``capacity`` and
-    ``_record_dtype`` (a function that gives the numpy dtype of one row)."""
-    _recorder = _ws = None
-
-    def _need(self):
-        if self._recorder is None:
-            raise RuntimeError(f"{type(self).__name__} used after close()")
+class _SeriesRecorder(HandleOwner):
+    """What ``BatchRecorder`` and ``BatchFieldRecorder`` share: the stream a read waits for and the default window of
+    ``read()``.  A subclass opens its recorder and sets ``n_systems``, ``capacity`` and ``_record_dtype`` (a function that
+    gives the numpy dtype of one row)."""
 
     def _read_stream(self, stream) -> int:
         """The stream a read synchronises.  Default: the whole device first (a graph replays on the stream it is launched
         on, which need not be the one ``record`` was captured on), then torch's current stream."""
         if stream is None:
             torch.cuda.synchronize(self._device)
-        return stream_handle(stream, self._device)
+        return stream_handle(stream, self._dev_index)
 
     def rows(self, stream=None) -> np.ndarray:
         """Rows written per system since creation / reset, behind a synchronisation (see ``read``)."""
-        self._need()
-        return self._recorder.rows(self._read_stream(stream))
+        return self._need().rows(self._read_stream(stream))
 
     def _read(self, first, count, stream) -> np.ndarray:
         """first=None: the oldest row still held; count=None: up to the last row every system has."""
-        self._need()
+        recorder = self._need()
         handle = self._read_stream(stream)
         if first is None or count is None:
-            rows = self._recorder.rows(handle)
+            rows = recorder.rows(handle)
             if first is None:
                 first = max(int(rows.max()) - self.capacity, 0)
             if count is None:
                 count = int(rows.min()) - int(first)
             if count <= 0:
                 return np.zeros((self.n_systems, 0), dtype=self._record_dtype())
-        return self._recorder.read(handle, 0, self.n_systems, int(first), int(count))
+        return recorder.read(handle, 0, self.n_systems, int(first), int(count))
 
-    def close(self) -> None:
-        if self._recorder is not None:
-            self._recorder.close()
-        if self._ws is not None:
-            self._ws.close()
-        self._recorder = self._ws = None
+    def reset(self, stream=None) -> None:
+        """Zero every system's counters (a field recorder's references with them), ordered on ``stream`` (default: torch's
+        current stream)."""
+        self._need().reset(stream_handle(stream, self._dev_index))
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @property
+    def recorder(self):
+        return self._handle
 
 
 class BatchRecorder(_SeriesRecorder):
@@ -123,8 +109,6 @@ class BatchRecorder(_SeriesRecorder):
             dev = force_batch.forces[0].device
             if dev.type != "cuda":
                 raise RuntimeError("BatchRecorder needs its arrays in GPU memory; no CPU fallback exists in this package")
-        self._device = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self._force_batch = force_batch
         self._velocities, self._net_forces, self._members = velocities, net_forces, []
         results = force_batch.batch.results_device_ptr()
@@ -143,8 +127,7 @@ class BatchRecorder(_SeriesRecorder):
                                              f.data_ptr() if (f is not None and n) else 0,
                                              mt.data_ptr() if (mt is not None and n_members) else 0,
                                              n if (v is not None and f is not None) else 0, n_members))
-        self._ws = _capi.Workspace(1, device=self._dev_index)
-        self._recorder = _capi.Recorder(self._ws, items, capacity, period, kB)
+        self._open(dev, lambda ws: _capi.Recorder(ws, items, capacity, period, kB))
         self.n_systems = B
         self.capacity, self.period = int(capacity), int(period)
         self._stream = 0
@@ -152,9 +135,9 @@ class BatchRecorder(_SeriesRecorder):
 
     def record(self, stream=None) -> None:
         """ONE kernel launch on ``stream`` (default: torch's current stream): nothing is waited for; may be captured."""
-        self._need()
-        handle = stream_handle(stream, self._device)
-        self._recorder.record(handle)
+        recorder = self._need()
+        handle = stream_handle(stream, self._dev_index)
+        recorder.record(handle)
         self._stream = handle
 
     def read(self, first=None, count=None, stream=None) -> np.ndarray:
@@ -162,12 +145,3 @@ class BatchRecorder(_SeriesRecorder):
         of recorded rows) of every system.  Default: everything still held.  Waits for the device (or, if given, for
         ``stream`` only); works the same before, between and after the replays of a graph, never inside a capture."""
         return self._read(first, count, stream)
-
-    def reset(self, stream=None) -> None:
-        """Zero every system's counters, ordered on ``stream`` (default: torch's current stream)."""
-        self._need()
-        self._recorder.reset(stream_handle(stream, self._device))
-
-    @property
-    def recorder(self) -> _capi.Recorder:
-        return self._recorder

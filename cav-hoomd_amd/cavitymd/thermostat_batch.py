@@ -23,27 +23,17 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import member_indices, stream_handle
+from ._device import HandleOwner, StepInputs, device_tensor, member_indices, one_device, per_system, stream_handle
 
 
-def _per_system(value, n: int, name: str):
-    if callable(value) or np.isscalar(value):
-        return [value] * n
-    value = list(value)
-    if len(value) != n:
-        raise ValueError(f"{name}: one value, or one per system ({n}), not {len(value)}")
-    return value
+class BussiReservoirBatch(HandleOwner):
+    _unusable = "used before attach()"
 
-
-class BussiReservoirBatch:
     def __init__(self, kT, tau=0.0):
         self.kT = kT    # a number, a callable of the timestep, or one of either per system
         self.tau = tau  # a number or one per system
-        self._batch = None
-        self._ws = None
         self.inputs = None
         self._stream = 0
-        self._copy_done = None
 
     # -- attachment ----------------------------------------------------------------------------------------------------------
     def attach(self, velocities, translational_dof, members=None) -> None:
@@ -53,18 +43,12 @@ class BussiReservoirBatch:
         if not velocities:
             raise ValueError("BussiReservoirBatch.attach: no systems")
         for v in velocities:
-            if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
-                raise RuntimeError("BussiReservoirBatch needs the velocity arrays in GPU memory; no CPU fallback exists in "
-                                   "this package")
-            if v.dtype != torch.float64 or v.dim() != 2 or v.shape[1] != 4 or not v.is_contiguous():
-                raise ValueError("every velocity array must be a contiguous (N,4) float64 tensor (HOOMD Scalar4, mass in .w)")
+            device_tensor(v, "BussiReservoirBatch", "velocity", note=" (HOOMD Scalar4, mass in .w)")
         B = len(velocities)
-        dev = velocities[0].device
-        if any(v.device != dev for v in velocities):
-            raise ValueError("all systems of one batch live on one device")
-        self._dof = [float(d) for d in _per_system(translational_dof, B, "translational_dof")]
-        self._kT = _per_system(self.kT, B, "kT")
-        self._tau = [float(t) for t in _per_system(self.tau, B, "tau")]
+        dev = one_device(velocities, "batch")
+        self._dof = [float(d) for d in per_system(translational_dof, B, "translational_dof")]
+        self._kT = per_system(self.kT, B, "kT", callables=True)
+        self._tau = [float(t) for t in per_system(self.tau, B, "tau")]
         members = [None] * B if members is None else list(members)
         if len(members) != B:
             raise ValueError("members: None, or one entry per system")
@@ -78,12 +62,11 @@ class BussiReservoirBatch:
             items.append(_capi.bussi_batch_item(v.data_ptr() if v.shape[0] else 0,
                                                 mt.data_ptr() if (mt is not None and n) else 0, n, dof))
         self._velocities = velocities
-        self._ws = _capi.Workspace(1, device=dev.index if dev.index is not None else -1)
-        self._batch = _capi.BussiBatch(self._ws, items)
+        self.detach()
+        self._open(dev, lambda ws: _capi.BussiBatch(ws, items))
         self.n_systems = B
-        self.inputs = torch.zeros((B, 8), dtype=torch.float64, device=dev)
-        self.inputs[:, 4] = 1.0   # a non-zero skip word: every system is skipped until its inputs are set
-        self._pinned = torch.zeros((B, 8), dtype=torch.float64).pin_memory()
+        self._step_inputs = StepInputs(B, dev, skip_column=4)
+        self.inputs = self._step_inputs.tensor
         self._dof_dev = torch.tensor(self._dof, dtype=torch.float64, device=dev)
         self._shape = torch.clamp((self._dof_dev - 1.0) / 2.0, min=0.5)   # gamma shape where dof > 1; unused elsewhere
         self._has_normal = self._dof_dev != 0
@@ -91,15 +74,8 @@ class BussiReservoirBatch:
         torch.cuda.current_stream(dev).synchronize()
 
     def detach(self) -> None:
-        if self._batch is not None:
-            self._batch.close()
-        if self._ws is not None:
-            self._ws.close()
-        self._batch = self._ws = self.inputs = None
-
-    def _need(self):
-        if self._batch is None:
-            raise RuntimeError("BussiReservoirBatch used before attach()")
+        self.close()
+        self.inputs = None
 
     def _set_T(self, timestep: int):
         return [float(k(timestep)) if callable(k) else float(k) for k in self._kT]
@@ -112,17 +88,12 @@ class BussiReservoirBatch:
         v = np.asarray(variates, dtype=np.float64)
         if v.shape != (self.n_systems, 2):
             raise ValueError(f"variates must have shape ({self.n_systems}, 2)")
-        if self._copy_done is not None:
-            self._copy_done.synchronize()                       # the staging buffer's last copy has left it
         rows = (_capi.BussiBatchInput * self.n_systems)()
         lib = _capi.load()
         for i, (T, tau) in enumerate(zip(self._set_T(timestep), self._tau)):
             _capi.check(lib.cavmd_bussi_batch_input_make(float(deltaT), T, tau, float(v[i, 0]), float(v[i, 1]),
                                                          ctypes.byref(rows[i])), "cavmd_bussi_batch_input_make")
-        self._pinned.numpy()[:] = np.frombuffer(rows, dtype=np.float64).reshape(self.n_systems, 8)
-        self.inputs.copy_(self._pinned, non_blocking=True)
-        self._copy_done = torch.cuda.Event()
-        self._copy_done.record(torch.cuda.current_stream(self.inputs.device))
+        self._step_inputs.upload(np.frombuffer(rows, dtype=np.float64).reshape(self.n_systems, 8))
 
     def draw_inputs(self, timestep: int, deltaT: float, generator=None) -> None:
         """Fills ``inputs`` ON THE DEVICE, in stream order, with no host wait: normal variates from torch.randn, gamma variates
@@ -138,14 +109,10 @@ class BussiReservoirBatch:
             row = _capi.bussi_batch_input_make(deltaT, T[i], self._tau[i], 0.0, 0.0)
             const[i, 2], const[i, 3] = row.c, row.set_T
             const[i, 4] = np.array([row.skip], dtype=np.uint64).view(np.float64)[0]
-        key = const.tobytes()
-        if getattr(self, "_const_key", None) != key:            # c, kT, skip change rarely: uploaded only then
-            self._const_dev = torch.from_numpy(const).to(dev)
-            self._const_key = key
         normal = torch.randn(B, dtype=torch.float64, device=dev, generator=generator)
         gamma = torch._standard_gamma(self._shape)
         zero = torch.zeros((), dtype=torch.float64, device=dev)
-        self.inputs.copy_(self._const_dev)
+        self._step_inputs.fill_constants(const)                 # c, kT, skip
         self.inputs[:, 0] = torch.where(self._has_normal, normal, zero)
         self.inputs[:, 1] = torch.where(self._has_gamma, gamma, zero)
 
@@ -153,21 +120,20 @@ class BussiReservoirBatch:
     def step_async(self, stream=None) -> None:
         """ONE kernel launch: kinetic energy -> alpha -> counters -> velocities *= alpha for every system, from ``inputs`` as
         it is when the kernel runs.  Nothing is waited for; may be captured into a graph."""
-        self._need()
-        handle = stream_handle(stream, self.inputs.device)
-        self._batch.step(handle, self.inputs.data_ptr())
+        batch = self._need()
+        handle = stream_handle(stream, self._dev_index)
+        batch.step(handle, self.inputs.data_ptr())
         self._stream = handle
 
     def device_state(self):
         """Per-system counters after the last enqueued step (waits for that step's stamps, nothing else).  Raises
         CavmdError(CAVMD_ERR_BAD_PARAMS) once after a step that was refused for zero kinetic energy."""
-        self._need()
-        return self._batch.read()
+        return self._need().read()
 
     def _field(self, name: str) -> np.ndarray:
-        if self._batch is None:
+        if self._handle is None:
             return np.zeros(0)
-        states, _ = self._batch.read(raise_refused=False)
+        states, _ = self._handle.read(raise_refused=False)
         return np.array([getattr(s, name) for s in states], dtype=np.float64)
 
     # -- the reference's loggable quantities, one entry per system -------------------------------------------------------------
@@ -196,5 +162,4 @@ class BussiReservoirBatch:
         return self.instantaneous_reservoir_translational + self.instantaneous_reservoir_rotational
 
     def reset_reservoir_energy(self) -> None:
-        self._need()
-        self._batch.reset(self._stream)
+        self._need().reset(self._stream)

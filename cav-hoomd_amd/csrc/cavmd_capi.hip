@@ -1690,6 +1690,17 @@ struct cavmd_batch : ItemTable<cavmd_batch_item, BatchRow> // launched by N desc
     bool captured = false; // some evaluation was enqueued into a stream capture: the stamps cannot tell replays apart
 
     cavmd_batch() : ItemTable(cavmd_batch_item_check, [](const cavmd_batch_item& it) { return it.N; }, batch_row) {}
+
+    static constexpr bool tied = false; // the one object cavmd_destroy does not wait for (include/cavmd.h)
+    int capacity_status(size_t n_items) const
+    {
+        return (size_t)depth * n_items * sizeof(HostResult) > kBatchRingMaxBytes ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        const hipError_t e = d_result.alloc_zeroed(n);
+        return e == hipSuccess ? h_ring.alloc((size_t)depth * n) : e;
+    }
 };
 
 namespace
@@ -1728,38 +1739,9 @@ int cavmd_batch_item_check(const cavmd_batch_item* it)
 int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_item* h_items, int history_depth,
                        cavmd_batch** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || history_depth < 2
-        || history_depth > (int)kResultHistoryMax)
-        return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_batch_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    const size_t ring_blocks = (size_t)history_depth * n_items;
-    if (ring_blocks * sizeof(HostResult) > kBatchRingMaxBytes)
-        return CAVMD_ERR_CAPACITY;
-
-    cavmd_batch* b = new (std::nothrow) cavmd_batch();
-    if (!b)
-        return (int)hipErrorOutOfMemory;
-    b->adopt(ws->device, h_items, n_items);
-    b->depth = (unsigned)history_depth;
-
-    DeviceGuard guard(b->device);
-    hipError_t e = b->upload();
-    if (e == hipSuccess)
-        e = b->d_result.alloc_zeroed(n_items);
-    if (e == hipSuccess)
-        e = b->h_ring.alloc(ring_blocks);
-    if (e != hipSuccess)
-    {
-        cavmd_batch_destroy(b);
-        return (int)e;
-    }
-    *out = b;
-    return CAVMD_OK;
+    const bool args_ok = history_depth >= 2 && history_depth <= (int)kResultHistoryMax;
+    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE,
+                        [&](cavmd_batch* b) { b->depth = (unsigned)history_depth; });
 }
 
 int cavmd_batch_destroy(cavmd_batch* b)
@@ -1777,21 +1759,15 @@ int cavmd_batch_compute(cavmd_batch* b, void* stream_)
     if (!b)
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(b->device);
     if (!b->captured && stream_capturing(stream))
         b->captured = true;
     b->sequence += 1;
     HostResult* host = b->h_ring.dev + (b->sequence % b->depth) * b->n;
-    hipLaunchKernelGGL(cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, stream, b->d_rows.ptr,
-                       b->d_order.ptr, b->sequence, b->d_result.ptr, host);
-    const int st = hip_status(hipGetLastError());
+    const int st = b->launch(stream, cavity_batch_kernel<kBatchBlock>, dim3((unsigned)b->n), dim3(kBatchBlock), 0, b->d_rows.ptr,
+                             b->d_order.ptr, b->sequence, b->d_result.ptr, host);
     if (st != CAVMD_OK)
-    {
         b->sequence -= 1;
-        return st;
-    }
-    b->enqueued_on(stream);
-    return CAVMD_OK;
+    return st;
 }
 
 int cavmd_batch_last_sequence(cavmd_batch* b, uint64_t* out)
@@ -1915,6 +1891,13 @@ struct cavmd_bussi_batch : ItemTable<cavmd_bussi_batch_item, BussiBatchRow> // l
                     uploaded_as_it_is<cavmd_bussi_batch_item, BussiBatchRow>)
     {
     }
+
+    hipError_t alloc_own()
+    {
+        refused_seen.assign(n, 0);
+        const hipError_t e = d_state.alloc_zeroed(n);
+        return e == hipSuccess ? h_blocks.alloc(n) : e;
+    }
 };
 
 namespace
@@ -1979,34 +1962,7 @@ int cavmd_bussi_batch_input_make(double deltaT, double set_T, double tau, double
 int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bussi_batch_item* h_items,
                              cavmd_bussi_batch** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
-        return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_bussi_batch_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    cavmd_bussi_batch* b = new (std::nothrow) cavmd_bussi_batch();
-    if (!b)
-        return (int)hipErrorOutOfMemory;
-    b->adopt(ws->device, h_items, n_items);
-    b->refused_seen.assign(n_items, 0);
-
-    DeviceGuard guard(b->device);
-    hipError_t e = b->upload();
-    if (e == hipSuccess)
-        e = b->d_state.alloc_zeroed(n_items);
-    if (e == hipSuccess)
-        e = b->h_blocks.alloc(n_items);
-    if (e != hipSuccess)
-    {
-        cavmd_bussi_batch_destroy(b);
-        return (int)e;
-    }
-    b->attach(ws);
-    *out = b;
-    return CAVMD_OK;
+    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_bussi_batch*) {});
 }
 
 int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)
@@ -2024,20 +1980,14 @@ int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream_, const cavmd_buss
     if (!b || !d_inputs || ((uintptr_t)d_inputs & 7))
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(b->device);
     if (!b->captured && stream_capturing(stream))
         b->captured = true;
     b->sequence += 1;
-    hipLaunchKernelGGL(bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, stream, b->d_rows.ptr, b->d_order.ptr,
-                       reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state.ptr, b->h_blocks.dev);
-    const int st = hip_status(hipGetLastError());
+    const int st = b->launch(stream, bussi_batch_kernel<256>, dim3((unsigned)b->n), dim3(256), 0, b->d_rows.ptr, b->d_order.ptr,
+                             reinterpret_cast<const BussiBatchInput*>(d_inputs), b->sequence, b->d_state.ptr, b->h_blocks.dev);
     if (st != CAVMD_OK)
-    {
         b->sequence -= 1;
-        return st;
-    }
-    b->enqueued_on(stream);
-    return CAVMD_OK;
+    return st;
 }
 
 int cavmd_bussi_batch_last_sequence(cavmd_bussi_batch* b, uint64_t* out)
@@ -2119,6 +2069,11 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
 
 // ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
 // launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
+namespace
+{
+constexpr size_t kRecorderMaxBytes = (size_t)1 << 30; // of one recorder's series (and, for a field recorder, its fields)
+}
+
 struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_record>
 {
     uint64_t period = 1;
@@ -2130,11 +2085,19 @@ struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_reco
                       uploaded_as_it_is<cavmd_recorder_item, RecorderRow>)
     {
     }
+
+    int capacity_status(size_t n_items) const
+    {
+        return capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        return alloc_series();
+    }
 };
 
 namespace
 {
-constexpr size_t kRecorderMaxBytes = (size_t)1 << 30;
 static_assert(sizeof(cavmd_record) == 128 && offsetof(cavmd_record, energy) == 16 && offsetof(cavmd_record, cavity_kinetic) == 88,
               "record layout");
 static_assert(sizeof(cavmd_recorder_item) == sizeof(RecorderRow), "the item table is uploaded as it is");
@@ -2170,39 +2133,12 @@ int cavmd_recorder_item_check(const cavmd_recorder_item* it)
 int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recorder_item* h_items, size_t capacity,
                           uint64_t period, double kB, cavmd_recorder** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || capacity == 0 || period == 0 || !(kB > 0.0)
-        || !std::isfinite(kB))
-        return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_recorder_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    if (capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items)
-        return CAVMD_ERR_CAPACITY;
-    cavmd_recorder* r = new (std::nothrow) cavmd_recorder();
-    if (!r)
-        return (int)hipErrorOutOfMemory;
-    r->adopt(ws->device, h_items, n_items);
-    r->capacity = capacity;
-    r->period = period;
-    r->kB = kB;
-
-    DeviceGuard guard(r->device);
-    hipError_t e = r->upload();
-    if (e == hipSuccess)
-        e = r->alloc_series();
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
-    if (e != hipSuccess)
-    {
-        cavmd_recorder_destroy(r);
-        return (int)e;
-    }
-    r->attach(ws);
-    *out = r;
-    return CAVMD_OK;
+    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
+    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_recorder* r) {
+        r->capacity = capacity;
+        r->period = period;
+        r->kB = kB;
+    });
 }
 
 int cavmd_recorder_destroy(cavmd_recorder* r)
@@ -2219,15 +2155,8 @@ int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
 {
     if (!r)
         return CAVMD_ERR_INVALID_VALUE;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(r->device);
-    hipLaunchKernelGGL(recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows.ptr, r->d_order.ptr,
-                       (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series.ptr, r->d_counters.ptr);
-    const int st = hip_status(hipGetLastError());
-    if (st != CAVMD_OK)
-        return st;
-    r->enqueued_on(stream);
-    return CAVMD_OK;
+    return r->launch((hipStream_t)stream_, recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, r->d_rows.ptr,
+                     r->d_order.ptr, (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series.ptr, r->d_counters.ptr);
 }
 
 int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
@@ -2263,6 +2192,7 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
     uint64_t period = 1;
     unsigned max_refs = 1;
     uint64_t interval = 0;
+    const double* h_kvec = nullptr;   // the caller's wavevectors: read by create only
     DeviceArray<double> d_kvec;       // n_k x 3
     DeviceArray<uint64_t> d_ref_rows; // n x max_refs: the row each reference was taken at
     DeviceArray<double> d_now;        // n x n_k x 2: the field of the last recorded call
@@ -2272,6 +2202,27 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
         : SeriesTable(kFldCounters, cavmd_field_recorder_item_check, [](const cavmd_field_item& it) { return it.N; },
                       uploaded_as_it_is<cavmd_field_item, FieldRow>)
     {
+    }
+
+    // series + fields (the current one and the references) within the recorder's cap
+    int capacity_status(size_t n_items) const
+    {
+        const size_t fields = sizeof(double) * 2 * n_k * ((size_t)max_refs + 1) * n_items;
+        return fields > kRecorderMaxBytes || capacity > (kRecorderMaxBytes - fields) / sizeof(cavmd_field_record) / n_items
+                   ? CAVMD_ERR_CAPACITY
+                   : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        hipError_t e = d_kvec.upload(h_kvec, 3 * n_k);
+        h_kvec = nullptr;
+        if (e == hipSuccess)
+            e = alloc_series();
+        if (e == hipSuccess)
+            e = d_ref_rows.alloc_zeroed(n * max_refs);
+        if (e == hipSuccess)
+            e = d_now.alloc_zeroed(2 * n_k * n);
+        return e == hipSuccess ? d_refs.alloc_zeroed(2 * n_k * n * max_refs) : e;
     }
 };
 
@@ -2311,57 +2262,18 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
                                 const double* h_wavevectors, size_t capacity, uint64_t period, uint32_t max_references,
                                 uint64_t reference_interval, cavmd_field_recorder** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || !h_wavevectors || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS || n_k == 0
-        || n_k > CAVMD_FIELD_MAX_WAVEVECTORS || capacity == 0 || period == 0 || max_references == 0
-        || max_references > CAVMD_FIELD_MAX_REFERENCES)
-        return CAVMD_ERR_INVALID_VALUE;
-    for (size_t i = 0; i < 3 * n_k; ++i)
-        if (!std::isfinite(h_wavevectors[i]))
-            return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_field_recorder_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    // series + fields (the current one and the references) within the recorder's cap
-    const size_t field_bytes = sizeof(double) * 2 * n_k;
-    const size_t fields_per_item = field_bytes * ((size_t)max_references + 1);
-    if (fields_per_item * n_items > kRecorderMaxBytes
-        || capacity > (kRecorderMaxBytes - fields_per_item * n_items) / sizeof(cavmd_field_record) / n_items)
-        return CAVMD_ERR_CAPACITY;
-    cavmd_field_recorder* r = new (std::nothrow) cavmd_field_recorder();
-    if (!r)
-        return (int)hipErrorOutOfMemory;
-    r->adopt(ws->device, h_items, n_items);
-    r->n_k = n_k;
-    r->capacity = capacity;
-    r->period = period;
-    r->max_refs = max_references;
-    r->interval = reference_interval;
-
-    DeviceGuard guard(r->device);
-    hipError_t e = r->upload();
-    if (e == hipSuccess)
-        e = r->d_kvec.upload(h_wavevectors, 3 * n_k);
-    if (e == hipSuccess)
-        e = r->alloc_series();
-    if (e == hipSuccess)
-        e = r->d_ref_rows.alloc_zeroed(n_items * max_references);
-    if (e == hipSuccess)
-        e = r->d_now.alloc_zeroed(2 * n_k * n_items);
-    if (e == hipSuccess)
-        e = r->d_refs.alloc_zeroed(2 * n_k * n_items * max_references);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's records
-    if (e != hipSuccess)
-    {
-        cavmd_field_recorder_destroy(r);
-        return (int)e;
-    }
-    r->attach(ws);
-    *out = r;
-    return CAVMD_OK;
+    bool args_ok = h_wavevectors && n_k != 0 && n_k <= CAVMD_FIELD_MAX_WAVEVECTORS && capacity != 0 && period != 0
+        && max_references != 0 && max_references <= CAVMD_FIELD_MAX_REFERENCES;
+    for (size_t i = 0; args_ok && i < 3 * n_k; ++i)
+        args_ok = std::isfinite(h_wavevectors[i]);
+    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_field_recorder* r) {
+        r->n_k = n_k;
+        r->h_kvec = h_wavevectors;
+        r->capacity = capacity;
+        r->period = period;
+        r->max_refs = max_references;
+        r->interval = reference_interval;
+    });
 }
 
 int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
@@ -2378,17 +2290,10 @@ int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const ui
 {
     if (!r || ((uintptr_t)d_take_reference & 3))
         return CAVMD_ERR_INVALID_VALUE;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(r->device);
-    hipLaunchKernelGGL(field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, stream, r->d_rows.ptr, r->d_order.ptr,
-                       (unsigned)r->n, r->d_kvec.ptr, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity, r->period,
-                       r->max_refs, r->interval, d_take_reference, r->d_series.ptr, r->d_counters.ptr, r->d_ref_rows.ptr,
-                       r->d_now.ptr, r->d_refs.ptr);
-    const int st = hip_status(hipGetLastError());
-    if (st != CAVMD_OK)
-        return st;
-    r->enqueued_on(stream);
-    return CAVMD_OK;
+    return r->launch((hipStream_t)stream_, field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, r->d_rows.ptr,
+                     r->d_order.ptr, (unsigned)r->n, r->d_kvec.ptr, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity,
+                     r->period, r->max_refs, r->interval, d_take_reference, r->d_series.ptr, r->d_counters.ptr, r->d_ref_rows.ptr,
+                     r->d_now.ptr, r->d_refs.ptr);
 }
 
 int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream_, uint64_t* out)
@@ -2454,6 +2359,19 @@ struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N d
                     uploaded_as_it_is<cavmd_verlet_item, VerletRow>)
     {
     }
+
+    hipError_t alloc_own()
+    {
+        return d_state.alloc_zeroed(n);
+    }
+
+    // one launch of n workgroups of one of the three kernels
+    template <class Kernel>
+    int launch_step(void* stream, Kernel kernel, const cavmd_verlet_input* d_inputs)
+    {
+        return launch((hipStream_t)stream, kernel, dim3((unsigned)n), dim3(256), 0, d_rows.ptr, d_order.ptr,
+                      reinterpret_cast<const VerletInput*>(d_inputs), d_state.ptr);
+    }
 };
 
 namespace
@@ -2480,20 +2398,6 @@ static_assert(sizeof(cavmd_verlet_state) == sizeof(VerletState) && offsetof(cavm
                   && offsetof(cavmd_verlet_state, langevin_reservoir) == offsetof(VerletState, reservoir),
               "the integrator states are read out as they are");
 static_assert(sizeof(((cavmd_verlet_item*)nullptr)->d_force) / sizeof(void*) == kVerletMaxForces, "force arrays per item");
-
-// one launch of n_items workgroups of one of the three kernels
-template <class Kernel>
-int verlet_launch(cavmd_verlet* v, hipStream_t stream, Kernel kernel, const cavmd_verlet_input* d_inputs)
-{
-    DeviceGuard guard(v->device);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)v->n), dim3(256), 0, stream, v->d_rows.ptr, v->d_order.ptr,
-                       reinterpret_cast<const VerletInput*>(d_inputs), v->d_state.ptr);
-    const int st = hip_status(hipGetLastError());
-    if (st != CAVMD_OK)
-        return st;
-    v->enqueued_on(stream);
-    return CAVMD_OK;
-}
 } // namespace
 
 extern "C"
@@ -2542,33 +2446,7 @@ int cavmd_verlet_input_make(double dt, double gamma, double kT, const double uni
 
 int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_item* h_items, cavmd_verlet** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
-        return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_verlet_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    cavmd_verlet* v = new (std::nothrow) cavmd_verlet();
-    if (!v)
-        return (int)hipErrorOutOfMemory;
-    v->adopt(ws->device, h_items, n_items);
-
-    DeviceGuard guard(v->device);
-    hipError_t e = v->upload();
-    if (e == hipSuccess)
-        e = v->d_state.alloc_zeroed(n_items);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize(); // the memset is done before any stream of the caller's steps
-    if (e != hipSuccess)
-    {
-        cavmd_verlet_destroy(v);
-        return (int)e;
-    }
-    v->attach(ws);
-    *out = v;
-    return CAVMD_OK;
+    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_verlet*) {});
 }
 
 int cavmd_verlet_destroy(cavmd_verlet* v)
@@ -2585,21 +2463,21 @@ int cavmd_verlet_accelerations(cavmd_verlet* v, void* stream_)
 {
     if (!v)
         return CAVMD_ERR_INVALID_VALUE;
-    return verlet_launch(v, (hipStream_t)stream_, verlet_step_two_kernel<256, true>, nullptr);
+    return v->launch_step(stream_, verlet_step_two_kernel<256, true>, nullptr);
 }
 
 int cavmd_verlet_step_one(cavmd_verlet* v, void* stream_, const cavmd_verlet_input* d_inputs)
 {
     if (!v || !d_inputs || ((uintptr_t)d_inputs & 7))
         return CAVMD_ERR_INVALID_VALUE;
-    return verlet_launch(v, (hipStream_t)stream_, verlet_step_one_kernel<256>, d_inputs);
+    return v->launch_step(stream_, verlet_step_one_kernel<256>, d_inputs);
 }
 
 int cavmd_verlet_step_two(cavmd_verlet* v, void* stream_, const cavmd_verlet_input* d_inputs)
 {
     if (!v || !d_inputs || ((uintptr_t)d_inputs & 7))
         return CAVMD_ERR_INVALID_VALUE;
-    return verlet_launch(v, (hipStream_t)stream_, verlet_step_two_kernel<256, false>, d_inputs);
+    return v->launch_step(stream_, verlet_step_two_kernel<256, false>, d_inputs);
 }
 
 int cavmd_verlet_read(cavmd_verlet* v, void* stream_, cavmd_verlet_state* out)
@@ -2737,6 +2615,12 @@ struct cavmd_molecular final : LinkedTable<cavmd_molecular_item, MolecularRow, s
         it->n_bonds = 0;
     }
 
+    hipError_t alloc_own()
+    {
+        const hipError_t e = LinkedTable::alloc_own();
+        return e == hipSuccess ? d_params.upload(&params, 1) : e; // a blocking copy: there before any launch
+    }
+
     hipError_t fill(const std::vector<cavmd_molecular_item>& all, const std::vector<unsigned>& launch,
                     const std::vector<std::vector<uint32_t>>& slots, MolecularTables* t) const override
     {
@@ -2833,31 +2717,7 @@ int cavmd_molecular_order(int* rows, int* j_split)
 int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_params* prm, size_t n_items, const cavmd_molecular_item* h_items,
                            cavmd_molecular** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !prm || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
-        return CAVMD_ERR_INVALID_VALUE;
-    int st = cavmd_molecular_params_check(prm);
-    if (st != CAVMD_OK)
-        return st;
-    cavmd_molecular* m = new (std::nothrow) cavmd_molecular();
-    if (!m)
-        return (int)hipErrorOutOfMemory;
-    m->params = *prm;
-    st = m->create(ws, h_items, n_items);
-    if (st == CAVMD_OK)
-    {
-        DeviceGuard guard(m->device);
-        st = hip_status(m->d_params.upload(prm, 1)); // a blocking copy: there before any launch
-    }
-    if (st != CAVMD_OK)
-    {
-        cavmd_molecular_destroy(m);
-        return st;
-    }
-    *out = m;
-    return CAVMD_OK;
+    return create_table(ws, n_items, h_items, out, cavmd_molecular_params_check(prm), [&](cavmd_molecular* m) { m->params = *prm; });
 }
 
 int cavmd_molecular_destroy(cavmd_molecular* m)
@@ -2874,17 +2734,10 @@ int cavmd_molecular_compute(cavmd_molecular* m, void* stream_)
 {
     if (!m)
         return CAVMD_ERR_INVALID_VALUE;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(m->device);
     const MolecularTables& t = m->tables;
-    hipLaunchKernelGGL((molecular_force_kernel<kMolecularBlock, kMolecularJSplit>), dim3(std::max(t.header.n_blocks, 1u)),
-                       dim3(kMolecularBlock), molecular_lds_bytes(t.lds_n), stream, m->d_rows.ptr, m->d_header.ptr, m->d_params.ptr,
-                       t.lds_n);
-    const int st = hip_status(hipGetLastError());
-    if (st != CAVMD_OK)
-        return st;
-    m->enqueued_on(stream);
-    return CAVMD_OK;
+    return m->launch((hipStream_t)stream_, molecular_force_kernel<kMolecularBlock, kMolecularJSplit>,
+                     dim3(std::max(t.header.n_blocks, 1u)), dim3(kMolecularBlock), molecular_lds_bytes(t.lds_n), m->d_rows.ptr,
+                     m->d_header.ptr, m->d_params.ptr, t.lds_n);
 }
 
 } // extern "C"
@@ -3171,22 +3024,7 @@ int cavmd_coulomb_order(int* rows, int* j_split, int* k_rows, int* k_split)
 
 int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulomb_item* h_items, cavmd_coulomb** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
-        return CAVMD_ERR_INVALID_VALUE;
-    cavmd_coulomb* c = new (std::nothrow) cavmd_coulomb();
-    if (!c)
-        return (int)hipErrorOutOfMemory;
-    const int st = c->create(ws, h_items, n_items);
-    if (st != CAVMD_OK)
-    {
-        cavmd_coulomb_destroy(c);
-        return st;
-    }
-    *out = c;
-    return CAVMD_OK;
+    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_coulomb*) {});
 }
 
 int cavmd_coulomb_destroy(cavmd_coulomb* c)
@@ -3204,20 +3042,15 @@ int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
     if (!c)
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(c->device);
     const CoulombTables& t = c->tables;
-    hipLaunchKernelGGL((coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>), dim3(std::max(t.header.n_k_blocks, 1u)),
-                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
-    int st = hip_status(hipGetLastError());
+    const size_t lds = coulomb_lds_bytes(t.lds_n);
+    // two launches, each noted once it is in flight: a refused second one leaves the first to be waited for
+    const int st = c->launch(stream, coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>, dim3(std::max(t.header.n_k_blocks, 1u)),
+                             dim3(kCoulombBlock), lds, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
     if (st != CAVMD_OK)
         return st;
-    hipLaunchKernelGGL((coulomb_force_kernel<kCoulombBlock, kCoulombJSplit>), dim3(std::max(t.header.n_blocks, 1u)),
-                       dim3(kCoulombBlock), coulomb_lds_bytes(t.lds_n), stream, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
-    st = hip_status(hipGetLastError());
-    if (st != CAVMD_OK)
-        return st;
-    c->enqueued_on(stream);
-    return CAVMD_OK;
+    return c->launch(stream, coulomb_force_kernel<kCoulombBlock, kCoulombJSplit>, dim3(std::max(t.header.n_blocks, 1u)),
+                     dim3(kCoulombBlock), lds, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
 }
 
 int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets)

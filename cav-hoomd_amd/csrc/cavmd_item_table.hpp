@@ -1,8 +1,9 @@
 // Host-only: what the seven "batch of small systems" objects of cavmd_capi.hip share -- how a table of items lives on the host
-// and on the device and how the object is tied to its workspace (ItemTable); for the two recorders, the per-item ring of records
-// behind it (SeriesTable); for the two force batches, the tables derived from the items that their kernels find through a
-// header at a fixed device address and that set_items replaces together (LinkedTable).
-// cavmd_capi.hip includes this once, after cavmd_workspace, DeviceGuard and CAVMD_HIP_TRY, which the code below uses.
+// and on the device, how the object is created (create_table), launched (ItemTable::launch), tied to its workspace and released
+// (destroy_table); for the two recorders, the per-item ring of records behind it (SeriesTable); for the two force batches, the
+// tables derived from the items that their kernels find through a header at a fixed device address and that set_items
+// replaces together (LinkedTable).
+// cavmd_capi.hip includes this once, after cavmd_workspace, DeviceGuard, hip_status and CAVMD_HIP_TRY, which the code below uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <new>
 #include <vector>
 
 #include "cavmd.h"
@@ -94,6 +96,21 @@ struct ItemTable
         order = launch_order(items, key);
     }
 
+    // What create_table asks of an object; one that has more to say hides these.
+    static constexpr bool tied = true; // attached to the workspace it was created from
+    int check_new(const Item* h_items, size_t n_items)
+    {
+        return check_items(h_items, n_items, check);
+    }
+    int capacity_status(size_t) const // called after the items passed: CAVMD_ERR_CAPACITY for a ring or series too large
+    {
+        return CAVMD_OK;
+    }
+    hipError_t alloc_own() // the object's buffers beyond rows and order (the caller holds the DeviceGuard)
+    {
+        return hipSuccess;
+    }
+
     // allocates and fills d_rows, then d_order (the caller holds the DeviceGuard)
     hipError_t upload()
     {
@@ -118,11 +135,20 @@ struct ItemTable
         ws = nullptr;
     }
 
-    // after a launch on `stream` went through
-    void enqueued_on(hipStream_t stream)
+    // THE launch of the objects built on an item table: under the guard of the table's device, with the launch error as the
+    // status; a launch that went through is noted, so that wait_idle() waits for its stream
+    template <class Kernel, class... Args>
+    int launch(hipStream_t stream, Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, Args... args)
     {
-        last_stream = stream;
-        enqueued = true;
+        DeviceGuard guard(device);
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+        const int st = hip_status(hipGetLastError());
+        if (st == CAVMD_OK)
+        {
+            last_stream = stream;
+            enqueued = true;
+        }
+        return st;
     }
 
     // THE wait for the launches in flight, which read the table and write the object's results (the caller holds the
@@ -214,6 +240,50 @@ int destroy_table(Table* t)
     t->quiesce();
     t->detach();
     delete t;
+    return CAVMD_OK;
+}
+
+// The beginning of every object built on an item table, for `args`, the status of the entry point's own arguments, and
+// `init`, which sets the object's own fields from them.  In this order: the arguments, the items, the capacity rule; then the
+// table and the object's buffers on the device, ONE device synchronise (the zeroing memsets are done before any stream of
+// the caller's, a non-blocking one included, launches), the tie to the workspace.  Any failure destroys what was built.
+template <class Table, class Item, class Init>
+int create_table(cavmd_workspace* ws, size_t n_items, const Item* h_items, Table** out, int args, Init init)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (args != CAVMD_OK)
+        return args;
+    Table* t = new (std::nothrow) Table();
+    if (!t)
+        return (int)hipErrorOutOfMemory;
+    t->device = ws->device; // whoever destroys the object holds the guard of this device
+    init(t);
+    int st = t->check_new(h_items, n_items);
+    if (st == CAVMD_OK)
+        st = t->capacity_status(n_items);
+    if (st == CAVMD_OK)
+    {
+        t->adopt(ws->device, h_items, n_items);
+        DeviceGuard guard(t->device);
+        hipError_t e = t->upload();
+        if (e == hipSuccess)
+            e = t->alloc_own();
+        if (e == hipSuccess)
+            e = hipDeviceSynchronize();
+        st = hip_status(e);
+    }
+    if (st != CAVMD_OK)
+    {
+        destroy_table(t);
+        return st;
+    }
+    if (Table::tied)
+        t->attach(ws);
+    *out = t;
     return CAVMD_OK;
 }
 
@@ -404,30 +474,27 @@ struct LinkedTable : ItemTable<Item, Row>
         return hipMemcpy(d_header.ptr, &t.header, sizeof(t.header), hipMemcpyHostToDevice);
     }
 
-    // the whole of create after the object's own arguments: a status other than CAVMD_OK leaves an object to be destroyed
-    int create(cavmd_workspace* w, const Item* h_items, size_t n_items)
+    // create_table's hooks (hiding ItemTable's): the items pass item_status, which fills `derived`; what is kept of them has
+    // the caller's lists taken out; header and tables follow rows and order
+    int check_new(const Item* h_items, size_t n_items)
     {
-        this->device = w->device; // whoever destroys the object holds the guard of this device
         derived.resize(n_items);
-        const int st = check_into(h_items, n_items, derived.data());
-        if (st != CAVMD_OK)
-            return st;
-        this->adopt(w->device, h_items, n_items);
+        return check_into(h_items, n_items, derived.data());
+    }
+
+    void adopt(int device_, const Item* h_items, size_t n_items)
+    {
+        Base::adopt(device_, h_items, n_items);
         for (Item& it : this->items)
             strip(&it);
-        DeviceGuard guard(this->device);
-        hipError_t e = this->upload();
-        if (e == hipSuccess)
-            e = d_header.alloc_zeroed(1);
+    }
+
+    hipError_t alloc_own()
+    {
+        hipError_t e = d_header.alloc_zeroed(1);
         if (e == hipSuccess)
             e = fill(this->items, this->order, derived, &tables);
-        if (e == hipSuccess)
-            e = copy_header(tables);
-        if (e == hipSuccess)
-            e = hipDeviceSynchronize(); // the memsets are done before any stream of the caller's computes
-        if (e == hipSuccess)
-            this->attach(w);
-        return hip_status(e);
+        return e == hipSuccess ? copy_header(tables) : e;
     }
 
     // (hides ItemTable's: the rows are only a part of what is replaced here)

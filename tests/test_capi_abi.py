@@ -23,6 +23,37 @@ def test_header_declares_what_python_binds(capi):
     assert _declared_symbols() == sorted(capi.EXPORTED_SYMBOLS)
 
 
+def _declared_parameter_counts():
+    """name -> number of parameters of every function include/cavmd.h declares: the commas outside any parentheses of its
+    parameter list, plus one; `void` or nothing is 0."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    counts = {}
+    for m in re.finditer(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_\w+)\s*\(", text):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = text[i]
+            depth += (c == "(") - (c == ")")
+            commas += (c == "," and depth == 1)
+            i += 1
+        params = text[m.end():i - 1].strip()
+        counts[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    return counts
+
+
+def test_every_declared_function_has_a_prototype_with_the_declared_number_of_parameters(capi):
+    """Without argtypes ctypes passes a 64-bit pointer as a C int: every build the package loads gives every function the
+    header declares a prototype, and the prototype has as many parameters as the declaration."""
+    counts = _declared_parameter_counts()
+    assert sorted(counts) == _declared_symbols() and counts["cavmd_version"] == 0 and counts["cavmd_compute_soa"] == 20
+    libs = [capi.load(), capi.load_hooks_build()] + [capi.load_split_variant(name) for name in sorted(capi.SPLIT_VARIANTS)]
+    for lib in libs:
+        for name, n in counts.items():
+            argtypes = getattr(lib, name).argtypes
+            assert argtypes is not None, f"{name} has no prototype"
+            assert len(argtypes) == n, f"{name}: {len(argtypes)} argtypes, {n} parameters declared"
+
+
 def test_library_exports_every_declared_symbol(capi):
     lib = ctypes.CDLL(capi.LIB_PATH)
     for name in _declared_symbols():
