@@ -1,0 +1,100 @@
+"""What the no-GPU checks of include/cavmd.h and the libraries share (tests/batch_objects.py, the per-object
+tests/test_*_abi.py, tests/test_capi_abi.py): reading the header, listing a library's exports, building and running a C99
+caller, parsing the layouts it prints -- and one good item per batch object, which the refusal tests start from."""
+import os
+import re
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+HEADER = os.path.join(ROOT, "include", "cavmd.h")
+
+
+def header_text() -> str:
+    """include/cavmd.h with its comments stripped"""
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def declared(prefix: str = "cavmd_"):
+    """the entry points the header declares under `prefix`, sorted"""
+    return sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(%s\w*)\s*\(" % re.escape(prefix), header_text())))
+
+
+def exported(path: str):
+    """the text symbols `nm -D --defined-only` lists for the library at `path`"""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if " T " in line}
+
+
+_C99_OUTPUT = {}
+
+
+def run_c99(name: str, capi, tmp_path) -> str:
+    """Builds tests/c_abi/<name>.c as C99 with -pedantic -Wall -Wextra -Werror against include/cavmd.h, links it with
+    libcavmd.so and runs it; the exit status must be 0.  Returns what it printed.  A program is built and run once per session:
+    a second caller gets the first run's output."""
+    if name in _C99_OUTPUT:
+        return _C99_OUTPUT[name]
+    src = os.path.join(ROOT, "tests", "c_abi", name + ".c")
+    exe = str(tmp_path / name)
+    libdir = os.path.dirname(capi.LIB_PATH)
+    cc = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src,
+                         "-o", exe, "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (name, out.returncode, out.stdout, out.stderr[-2000:])
+    _C99_OUTPUT[name] = out.stdout
+    return out.stdout
+
+
+def c_layouts(stdout: str):
+    """(sizes, offsets) from the lines tests/c_abi/abi_print.h writes: `sizeof <which> <n>` gives sizes[which] and
+    `<which>.<field> <offset>` gives offsets[which][field]."""
+    sizes = {which: int(n) for which, n in re.findall(r"^sizeof (\w+) (\d+)$", stdout, flags=re.M)}
+    offsets = {which: {} for which in sizes}
+    for which, field, off in re.findall(r"^(\w+)\.(\w+) (\d+)$", stdout, flags=re.M):
+        offsets[which][field] = int(off)
+    return sizes, offsets
+
+
+def bits(x) -> int:
+    return int(np.float64(x).view(np.uint64))
+
+
+# ---- one good item per batch object: the `good` of its row in batch_objects.OBJECTS, and what the refusal matrices
+# of the per-object modules vary ----------------------------------------------------------------------------------------------
+def good_batch(capi, n=501):
+    return capi.batch_item(n, 0x10000, 0x20000, 0x30000, 0x40000, (40.0, 40.0, 40.0), 2, capi.make_params(0.0091, 1e-3, 1.0))
+
+
+def good_bussi_batch(capi, n=501, dof=1500.0):
+    return capi.bussi_batch_item(0x10000, 0x20000, n, dof)
+
+
+def good_recorder(capi, N=501, n_members=501):
+    return capi.recorder_item(0x10000, 0x20000, 0x30000, 0x40000, N, n_members)
+
+
+def good_field_recorder(capi):
+    return capi.field_item(0x10000, 24, 501)
+
+
+def good_verlet(capi, n=501, forces=(0x50000,), net=0, langevin=-1):
+    return capi.verlet_item(n, 0x10000, 0x20004, 0x30000, 0x40008, forces, net, (10.0, 11.0, 12.0), langevin)
+
+
+def molecular_params(capi, r_cut=3.0):
+    return capi.molecular_params(3, {0: (0.7, 2.2), 1: (1.4, 2.0)},
+                                 {(0, 0): (1e-3, 2.0, r_cut), (0, 1): (2e-3, 1.5, r_cut), (1, 1): (5e-4, 1.0, 0.5 * r_cut)})
+
+
+def good_molecular(capi, n=501, bonds=((0, 1, 0), (2, 3, 1)), box=(8.0, 9.0, 10.0)):
+    return capi.molecular_item(n, 0x10000, 0x20000, box, np.array(bonds, dtype=np.uint32).reshape(-1, 3))
+
+
+COULOMB_BOX = (8.0, 9.0, 10.0)
+
+
+def good_coulomb(capi, n=501, exclusions=((0, 1), (2, 3)), box=COULOMB_BOX, kappa=0.9, r_cut=4.0, k_cut=3.0):
+    return capi.coulomb_item(n, 0x10000, 0x30000, 0x20000, box, kappa, r_cut, k_cut, np.array(exclusions, dtype=np.uint32).reshape(-1, 2))

@@ -1,11 +1,13 @@
-/* batch_abi_check.c -- the batch part of include/cavmd.h consumed as plain C99 (tests/test_batch_abi.py builds it with
- * -pedantic -Werror and runs it).  Needs no GPU: it checks the layout of cavmd_batch_item, the per-item validation
- * (cavmd_batch_item_check is host arithmetic) and that every entry point refuses null arguments. */
-#include <stddef.h>
-#include <stdio.h>
+/* batch_abi_check.c -- the batch part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py builds it with
+ * -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of cavmd_batch_item and cavmd_params for the test to
+ * compare with the ctypes structures, and checks the per-item validation (cavmd_batch_item_check is host arithmetic) and that
+ * every entry point refuses null arguments. */
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
+
+#define OFF(which, type, field) ABI_OFF(which, cavmd_##type, field)
 
 int main(void)
 {
@@ -15,10 +17,23 @@ int main(void)
     const cavmd_result* dp = NULL;
     uint64_t seq = 0;
     double e[3];
-    if (sizeof(cavmd_batch_item) != 128 || offsetof(cavmd_batch_item, d_force) != 24 || offsetof(cavmd_batch_item, Lx) != 32
-        || offsetof(cavmd_batch_item, params) != 56 || offsetof(cavmd_batch_item, N) != 88
-        || offsetof(cavmd_batch_item, L_typeid) != 92 || offsetof(cavmd_batch_item, reserved) != 96)
-        return 1;
+    ABI_SIZE(item, cavmd_batch_item);
+    ABI_SIZE(params, cavmd_params);
+    OFF(item, batch_item, d_pos);
+    OFF(item, batch_item, d_charge);
+    OFF(item, batch_item, d_image);
+    OFF(item, batch_item, d_force);
+    OFF(item, batch_item, Lx);
+    OFF(item, batch_item, Ly);
+    OFF(item, batch_item, Lz);
+    OFF(item, batch_item, params);
+    OFF(item, batch_item, N);
+    OFF(item, batch_item, L_typeid);
+    OFF(item, batch_item, reserved);
+    OFF(params, params, omegac);
+    OFF(params, params, couplstr);
+    OFF(params, params, K);
+    OFF(params, params, phmass);
     if (CAVMD_BATCH_MAX_ITEMS != 65536 || CAVMD_BATCH_MAX_ITEM_N != 65536)
         return 2;
     if (cavmd_version() != CAVMD_VERSION_MAJOR * 1000 + CAVMD_VERSION_MINOR || CAVMD_VERSION_MINOR != 2)

@@ -1,13 +1,14 @@
-/* bussi_batch_abi_check.c -- the thermostat-batch part of include/cavmd.h consumed as plain C99 (tests/test_bussi_batch_abi.py
- * builds it with -pedantic -Werror and runs it).  Needs no GPU: it checks the layouts of cavmd_bussi_batch_item and
- * cavmd_bussi_batch_input, the per-item validation and the input row maker (host arithmetic), and that every entry point
- * refuses null arguments. */
+/* bussi_batch_abi_check.c -- the thermostat-batch part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py
+ * builds it with -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of cavmd_bussi_batch_item,
+ * cavmd_bussi_batch_input and cavmd_bussi_device_state for the test to compare with the ctypes structures, and checks the
+ * per-item validation and the input row maker (host arithmetic), and that every entry point refuses null arguments. */
 #include <math.h>
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
+
+#define OFF(which, type, field) ABI_OFF(which, cavmd_bussi_##type, field)
 
 int main(void)
 {
@@ -17,18 +18,27 @@ int main(void)
     cavmd_bussi_device_state st;
     const cavmd_bussi_device_state* dp = NULL;
     uint64_t seq = 0;
-    if (sizeof(cavmd_bussi_batch_item) != 64 || offsetof(cavmd_bussi_batch_item, d_vel) != 0
-        || offsetof(cavmd_bussi_batch_item, d_members) != 8 || offsetof(cavmd_bussi_batch_item, n_members) != 16
-        || offsetof(cavmd_bussi_batch_item, reserved0) != 20 || offsetof(cavmd_bussi_batch_item, dof_translational) != 24
-        || offsetof(cavmd_bussi_batch_item, reserved) != 32)
-        return 1;
-    if (sizeof(cavmd_bussi_batch_input) != 64 || offsetof(cavmd_bussi_batch_input, normal_variate) != 0
-        || offsetof(cavmd_bussi_batch_input, gamma_variate) != 8 || offsetof(cavmd_bussi_batch_input, c) != 16
-        || offsetof(cavmd_bussi_batch_input, set_T) != 24 || offsetof(cavmd_bussi_batch_input, skip) != 32
-        || offsetof(cavmd_bussi_batch_input, reserved) != 40)
-        return 2;
-    if (sizeof(cavmd_bussi_device_state) != 48)
-        return 3;
+    ABI_SIZE(item, cavmd_bussi_batch_item);
+    ABI_SIZE(input, cavmd_bussi_batch_input);
+    ABI_SIZE(state, cavmd_bussi_device_state);
+    OFF(item, batch_item, d_vel);
+    OFF(item, batch_item, d_members);
+    OFF(item, batch_item, n_members);
+    OFF(item, batch_item, reserved0);
+    OFF(item, batch_item, dof_translational);
+    OFF(item, batch_item, reserved);
+    OFF(input, batch_input, normal_variate);
+    OFF(input, batch_input, gamma_variate);
+    OFF(input, batch_input, c);
+    OFF(input, batch_input, set_T);
+    OFF(input, batch_input, skip);
+    OFF(input, batch_input, reserved);
+    OFF(state, device_state, reservoir_translational);
+    OFF(state, device_state, instantaneous_translational);
+    OFF(state, device_state, last_alpha);
+    OFF(state, device_state, last_kinetic_energy);
+    OFF(state, device_state, steps);
+    OFF(state, device_state, refused);
     if (cavmd_version() != CAVMD_VERSION_MAJOR * 1000 + CAVMD_VERSION_MINOR || CAVMD_VERSION_MINOR != 2)
         return 4;
     memset(&it, 0, sizeof(it));

@@ -1,15 +1,14 @@
-/* coulomb_abi_check.c -- the Coulomb part of include/cavmd.h consumed as plain C99 (tests/test_coulomb_abi.py builds it with
+/* coulomb_abi_check.c -- the Coulomb part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py builds it with
  * -pedantic -Werror and runs it).  Needs no GPU: it prints the layout of cavmd_coulomb_item as "name offset" lines for the test
  * to compare with the ctypes structure, and checks the host arithmetic (item check, k count, parameters) and that every entry
  * point refuses null arguments. */
 #include <math.h>
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
 
-#define OFF(field) printf("item." #field " %u\n", (unsigned)offsetof(cavmd_coulomb_item, field))
+#define OFF(field) ABI_OFF(item, cavmd_coulomb_item, field)
 
 int main(void)
 {
@@ -21,7 +20,7 @@ int main(void)
     uint32_t K = 77;
     double kappa = 0.0, k_cut = 0.0;
     int rows = 0, split = 0, k_rows = 0, k_split = 0;
-    printf("sizeof item %u\n", (unsigned)sizeof(cavmd_coulomb_item));
+    ABI_SIZE(item, cavmd_coulomb_item);
     OFF(d_pos);
     OFF(d_charge);
     OFF(d_force);
@@ -122,6 +121,19 @@ int main(void)
     if (cavmd_coulomb_set_items(NULL, 0, 1, &it) != CAVMD_ERR_INVALID_VALUE || cavmd_coulomb_compute(NULL, NULL) != CAVMD_ERR_INVALID_VALUE
         || cavmd_coulomb_structure_device_ptr(NULL, &structure, &offsets) != CAVMD_ERR_INVALID_VALUE)
         return 24;
+    {
+        cavmd_workspace* ws = NULL;
+        const int s = cavmd_create(-1, 1000, &ws);
+        if (s == CAVMD_OK)
+        {
+            printf("device present\n");
+            cavmd_destroy(ws);
+        }
+        else if (s == CAVMD_ERR_NO_DEVICE && ws == NULL)
+            printf("no device: no workspace, hence no Coulomb batch\n");
+        else
+            return 25;
+    }
     printf("COULOMB-ABI-OK\n");
     return 0;
 }

@@ -1,12 +1,13 @@
 /* field_recorder_abi_check.c -- the field-recorder part of include/cavmd.h consumed as plain C99
- * (tests/test_field_recorder_abi.py builds it with -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of
+ * (tests/batch_objects.py builds it with -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of
  * cavmd_field_record and cavmd_field_item as the C compiler sees them, and checks the per-item validation (host arithmetic)
  * and that every entry point refuses null arguments. */
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
+
+#define OFF(which, field) ABI_OFF(which, cavmd_field_##which, field)
 
 int main(void)
 {
@@ -18,13 +19,19 @@ int main(void)
     uint64_t rows = 0;
     uint32_t n_refs = 0;
     double k[3] = {0.0, 0.0, 1.0};
-    printf("record %u %u %u %u %u %u %u\n", (unsigned)sizeof(cavmd_field_record), (unsigned)offsetof(cavmd_field_record, call),
-           (unsigned)offsetof(cavmd_field_record, n_references), (unsigned)offsetof(cavmd_field_record, took_reference),
-           (unsigned)offsetof(cavmd_field_record, rho2), (unsigned)offsetof(cavmd_field_record, reserved),
-           (unsigned)offsetof(cavmd_field_record, F));
-    printf("item %u %u %u %u %u %u\n", (unsigned)sizeof(cavmd_field_item), (unsigned)offsetof(cavmd_field_item, d_position),
-           (unsigned)offsetof(cavmd_field_item, position_stride), (unsigned)offsetof(cavmd_field_item, N),
-           (unsigned)offsetof(cavmd_field_item, reserved0), (unsigned)offsetof(cavmd_field_item, reserved));
+    ABI_SIZE(record, cavmd_field_record);
+    ABI_SIZE(item, cavmd_field_item);
+    OFF(record, call);
+    OFF(record, n_references);
+    OFF(record, took_reference);
+    OFF(record, rho2);
+    OFF(record, reserved);
+    OFF(record, F);
+    OFF(item, d_position);
+    OFF(item, position_stride);
+    OFF(item, N);
+    OFF(item, reserved0);
+    OFF(item, reserved);
     printf("limits %d %d\n", CAVMD_FIELD_MAX_WAVEVECTORS, CAVMD_FIELD_MAX_REFERENCES);
     memset(&it, 0, sizeof(it));
     memset(&rec, 0, sizeof(rec));

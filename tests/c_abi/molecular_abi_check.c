@@ -1,14 +1,13 @@
-/* molecular_abi_check.c -- the molecular-force part of include/cavmd.h consumed as plain C99 (tests/test_molecular_abi.py builds
+/* molecular_abi_check.c -- the molecular-force part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py builds
  * it with -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of cavmd_molecular_pair, _bond_params, _params,
  * _bond and _item as "name offset" lines for the test to compare with the ctypes structures, and checks the pair maker, the two
  * validations (host arithmetic) and that every entry point refuses null arguments. */
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
 
-#define OFF(type, field) printf(#type "." #field " %u\n", (unsigned)offsetof(cavmd_molecular_##type, field))
+#define OFF(which, field) ABI_OFF(which, cavmd_molecular_##which, field)
 
 int main(void)
 {
@@ -18,9 +17,11 @@ int main(void)
     cavmd_molecular_bond bonds[2];
     cavmd_molecular* m = NULL;
     int rows = 0, split = 0;
-    printf("sizeof pair %u bond_params %u params %u bond %u item %u\n", (unsigned)sizeof(cavmd_molecular_pair),
-           (unsigned)sizeof(cavmd_molecular_bond_params), (unsigned)sizeof(cavmd_molecular_params),
-           (unsigned)sizeof(cavmd_molecular_bond), (unsigned)sizeof(cavmd_molecular_item));
+    ABI_SIZE(pair, cavmd_molecular_pair);
+    ABI_SIZE(bond_params, cavmd_molecular_bond_params);
+    ABI_SIZE(params, cavmd_molecular_params);
+    ABI_SIZE(bond, cavmd_molecular_bond);
+    ABI_SIZE(item, cavmd_molecular_item);
     OFF(pair, lj1);
     OFF(pair, lj2);
     OFF(pair, lj1_12);
@@ -142,6 +143,19 @@ int main(void)
     if (cavmd_molecular_set_items(NULL, 0, 1, &it) != CAVMD_ERR_INVALID_VALUE
         || cavmd_molecular_compute(NULL, NULL) != CAVMD_ERR_INVALID_VALUE)
         return 27;
+    {
+        cavmd_workspace* ws = NULL;
+        const int s = cavmd_create(-1, 1000, &ws);
+        if (s == CAVMD_OK)
+        {
+            printf("device present\n");
+            cavmd_destroy(ws);
+        }
+        else if (s == CAVMD_ERR_NO_DEVICE && ws == NULL)
+            printf("no device: no workspace, hence no molecular batch\n");
+        else
+            return 28;
+    }
     printf("MOLECULAR-ABI-OK\n");
     return 0;
 }

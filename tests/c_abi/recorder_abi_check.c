@@ -1,13 +1,14 @@
-/* recorder_abi_check.c -- the recorder part of include/cavmd.h consumed as plain C99 (tests/test_recorder_abi.py builds it with
- * -pedantic -Werror and runs it).  Needs no GPU: it checks the layouts of cavmd_record and cavmd_recorder_item, the per-item
- * validation (host arithmetic), the refusals of cavmd_recorder_create's scalar arguments and that every entry point refuses
- * null arguments. */
+/* recorder_abi_check.c -- the recorder part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py builds it
+ * with -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of cavmd_record and cavmd_recorder_item for the
+ * test to compare with the ctypes structures, and checks the per-item validation (host arithmetic), the refusals of
+ * cavmd_recorder_create's scalar arguments and that every entry point refuses null arguments. */
 #include <math.h>
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
+
+#define OFF(which, type, field) ABI_OFF(which, cavmd_##type, field)
 
 int main(void)
 {
@@ -17,17 +18,25 @@ int main(void)
     const cavmd_record* dr = NULL;
     const uint64_t* drows = NULL;
     uint64_t rows = 0;
-    if (sizeof(cavmd_record) != 128 || offsetof(cavmd_record, call) != 0 || offsetof(cavmd_record, eval_sequence) != 8
-        || offsetof(cavmd_record, energy) != 16 || offsetof(cavmd_record, total_dipole) != 40 || offsetof(cavmd_record, q) != 64
-        || offsetof(cavmd_record, cavity_kinetic) != 88 || offsetof(cavmd_record, cavity_temperature) != 96
-        || offsetof(cavmd_record, kinetic_energy) != 104 || offsetof(cavmd_record, force_mass_sum) != 112
-        || offsetof(cavmd_record, reserved) != 120)
-        return 1;
-    if (sizeof(cavmd_recorder_item) != 64 || offsetof(cavmd_recorder_item, d_result) != 0
-        || offsetof(cavmd_recorder_item, d_vel) != 8 || offsetof(cavmd_recorder_item, d_net_force) != 16
-        || offsetof(cavmd_recorder_item, d_members) != 24 || offsetof(cavmd_recorder_item, N) != 32
-        || offsetof(cavmd_recorder_item, n_members) != 36 || offsetof(cavmd_recorder_item, reserved) != 40)
-        return 2;
+    ABI_SIZE(record, cavmd_record);
+    ABI_SIZE(item, cavmd_recorder_item);
+    OFF(record, record, call);
+    OFF(record, record, eval_sequence);
+    OFF(record, record, energy);
+    OFF(record, record, total_dipole);
+    OFF(record, record, q);
+    OFF(record, record, cavity_kinetic);
+    OFF(record, record, cavity_temperature);
+    OFF(record, record, kinetic_energy);
+    OFF(record, record, force_mass_sum);
+    OFF(record, record, reserved);
+    OFF(item, recorder_item, d_result);
+    OFF(item, recorder_item, d_vel);
+    OFF(item, recorder_item, d_net_force);
+    OFF(item, recorder_item, d_members);
+    OFF(item, recorder_item, N);
+    OFF(item, recorder_item, n_members);
+    OFF(item, recorder_item, reserved);
     if (cavmd_version() != CAVMD_VERSION_MAJOR * 1000 + CAVMD_VERSION_MINOR || CAVMD_VERSION_MINOR != 2)
         return 3;
     memset(&it, 0, sizeof(it));

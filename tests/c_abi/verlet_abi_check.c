@@ -1,15 +1,14 @@
-/* verlet_abi_check.c -- the integrator part of include/cavmd.h consumed as plain C99 (tests/test_verlet_abi.py builds it with
+/* verlet_abi_check.c -- the integrator part of include/cavmd.h consumed as plain C99 (tests/batch_objects.py builds it with
  * -pedantic -Werror and runs it).  Needs no GPU: it prints the layouts of cavmd_verlet_item, cavmd_verlet_input and
  * cavmd_verlet_state as "name offset" lines for the test to compare with the ctypes structures, and checks the per-item
  * validation, the input row maker (host arithmetic) and that every entry point refuses null arguments. */
 #include <math.h>
-#include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "abi_print.h"
 #include "cavmd.h"
 
-#define OFF(type, field) printf(#type "." #field " %u\n", (unsigned)offsetof(cavmd_verlet_##type, field))
+#define OFF(which, field) ABI_OFF(which, cavmd_verlet_##which, field)
 
 int main(void)
 {
@@ -19,8 +18,9 @@ int main(void)
     cavmd_verlet* v = NULL;
     const cavmd_verlet_state* dp = NULL;
     const double u[3] = {0.25, -0.5, 0.75};
-    printf("sizeof item %u input %u state %u\n", (unsigned)sizeof(cavmd_verlet_item), (unsigned)sizeof(cavmd_verlet_input),
-           (unsigned)sizeof(cavmd_verlet_state));
+    ABI_SIZE(item, cavmd_verlet_item);
+    ABI_SIZE(input, cavmd_verlet_input);
+    ABI_SIZE(state, cavmd_verlet_state);
     OFF(item, d_pos);
     OFF(item, d_image);
     OFF(item, d_vel);
@@ -111,6 +111,19 @@ int main(void)
         || cavmd_verlet_reset(NULL, NULL) != CAVMD_ERR_INVALID_VALUE
         || cavmd_verlet_state_device_ptr(NULL, &dp) != CAVMD_ERR_INVALID_VALUE)
         return 23;
+    {
+        cavmd_workspace* ws = NULL;
+        const int s = cavmd_create(-1, 1000, &ws);
+        if (s == CAVMD_OK)
+        {
+            printf("device present\n");
+            cavmd_destroy(ws);
+        }
+        else if (s == CAVMD_ERR_NO_DEVICE && ws == NULL)
+            printf("no device: no workspace, hence no integrator batch\n");
+        else
+            return 24;
+    }
     printf("VERLET-ABI-OK\n");
     return 0;
 }

@@ -20,7 +20,9 @@ import numpy as np
 import pytest
 import torch
 
+from abi_support import bits as _bits
 from cavitymd import _capi, thermostats
+from gpu_support import same_or_both_nan as _same
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bussi_reference_golden.npz")
 
@@ -58,15 +60,6 @@ class Call:
     @property
     def c_agrees(self) -> bool:
         return _bits(self.c_here) == _bits(self.c)
-
-
-def _bits(x) -> int:
-    return int(np.float64(x).view(np.uint64))
-
-
-def _same(a, b) -> bool:
-    """Same bits (so -0.0 != 0.0), or both NaN (NaN payloads are not part of any contract)."""
-    return _bits(a) == _bits(b) or (math.isnan(a) and math.isnan(b))
 
 
 CASES = [Call(FIX["case_in"][i], FIX["case_out"][i], str(FIX["case_name"][i])) for i in range(FIX["case_in"].shape[0])]

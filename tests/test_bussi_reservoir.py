@@ -20,6 +20,7 @@ import torch
 
 import cavitymd
 from cavitymd import _capi, thermostats
+from gpu_support import same_bits_on_device as _bits_equal
 
 
 @pytest.fixture(scope="module")
@@ -287,10 +288,6 @@ def _gpu_velocities(n, seed):
     v[:n, 3] = torch.rand((n,), generator=g, dtype=torch.float64, device="cuda") * 3e4 + 1.0
     v[n:] = float("nan")
     return v
-
-
-def _bits_equal(a, b):
-    return torch.equal(a.view(torch.int64), b.view(torch.int64))
 
 
 def _scaled(old, idx, n, alpha):

@@ -5,18 +5,11 @@ import os
 import re
 import subprocess
 
-import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
-
-
-def _declared_symbols():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_\w+)\s*\(", text)))
+from abi_support import HEADER, ROOT, exported, header_text, run_c99
+from abi_support import declared as _declared_symbols
 
 
 def test_header_declares_what_python_binds(capi):
@@ -26,8 +19,7 @@ def test_header_declares_what_python_binds(capi):
 def _declared_parameter_counts():
     """name -> number of parameters of every function include/cavmd.h declares: the commas outside any parentheses of its
     parameter list, plus one; `void` or nothing is 0."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"//[^\n]*", "", header_text())
     counts = {}
     for m in re.finditer(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_\w+)\s*\(", text):
         depth, commas, i = 1, 0, m.end()
@@ -59,9 +51,7 @@ def test_library_exports_every_declared_symbol(capi):
     for name in _declared_symbols():
         assert hasattr(lib, name), f"{name} declared in include/cavmd.h but not exported by libcavmd.so"
     # and nothing but the ABI leaks out of the shared object
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    stray = {s for s in exported if not s.startswith("cavmd_") and not s.startswith("_")}
+    stray = {s for s in exported(capi.LIB_PATH) if not s.startswith("cavmd_") and not s.startswith("_")}
     assert not stray, stray
 
 
@@ -173,24 +163,17 @@ def test_no_product_kernel_uses_scratch_memory(capi):
 def test_header_is_plain_c_and_links(capi, tmp_path):
     """include/cavmd.h must be consumable by a C compiler (the boundary is a C ABI: no C++ types, no torch types): a C99
     program (tests/c_abi/abi_check.c) is built with -pedantic -Werror against the header, linked with libcavmd.so and run."""
-    src = os.path.join(ROOT, "tests", "c_abi", "abi_check.c")
-    exe = str(tmp_path / "abi_check")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe,
-                    "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], check=True, capture_output=True, text=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "C-ABI-OK" in out.stdout, (out.returncode, out.stdout, out.stderr[-2000:])
+    stdout = run_c99("abi_check", capi, tmp_path)
+    assert "C-ABI-OK" in stdout, stdout
     if not torch.cuda.is_available():
-        assert "refused with CAVMD_ERR_NO_DEVICE" in out.stdout
+        assert "refused with CAVMD_ERR_NO_DEVICE" in stdout
 
 
 def test_the_product_library_carries_no_test_hooks(capi):
     """The fault-injecting instantiations of the single-launch kernel (FAULT = true) and the debug_* tunables that drive them
     exist in libcavmd_hooks.so only (`make hooks`, -DCAVMD_TEST_HOOKS); the library a caller links has neither, so no caller
     can make a production workspace stall."""
-    import subprocess
     from cavitymd import _capi
-    nm = "/opt/rocm/lib/llvm/bin/llvm-nm"
     fault = "cavity_persistent_kernelILi256ELi2ELi0ELb1E"       # <256, 2, 0, FAULT = true, ...>
 
     def kernel_names(path):
@@ -204,7 +187,6 @@ def test_the_product_library_carries_no_test_hooks(capi):
                  b"debug_skip_publish"):
         assert name not in kernel_names(_capi.LIB_PATH), name
         assert name in kernel_names(_capi.HOOKS_LIB_PATH), name
-    assert os.path.exists(nm) or True
 
 
 @pytest.mark.gpu

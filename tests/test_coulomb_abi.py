@@ -1,36 +1,31 @@
-"""The Coulomb force batch (cavmd_coulomb_*) on a machine WITHOUT a GPU: the header declares and both libraries export the nine
-entry points and nothing stray, the version is still 2, the layout agrees between C and ctypes, every refusal works without a
-device, the k-vector count equals the mirror's enumeration, the Python class refuses CPU tensors -- and the mirror itself
-(tests/coulomb_mirror.py), which the GPU tests compare the kernels with, is checked against physics: the Madelung constant of
-rock salt, independence of the splitting parameter kappa with and without a net charge, and F = -dE/dx."""
+"""What is specific to the Coulomb force batch (cavmd_coulomb_*) on a machine WITHOUT a GPU: the limits and the origin of the
+expressions the header states, the order the library answers, every refusal of the item check, the k-vector count against the
+mirror's enumeration, the parameter formula -- and the mirror itself (tests/coulomb_mirror.py), which the GPU tests compare
+the kernels with, against physics: the Madelung constant of rock salt, independence of the splitting parameter kappa with and
+without a net charge, and F = -dE/dx.  Header, exports, layouts, null arguments, launch order, Python surface and deferred
+destroy are the shared checks of tests/batch_objects.py, called here with this object's row."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import batch_objects as checks
 import coulomb_mirror as mirror
+from abi_support import COULOMB_BOX as BOX
+from abi_support import HEADER, header_text
+from abi_support import good_coulomb as _good
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
-COULOMB = ("cavmd_coulomb_item_check", "cavmd_coulomb_k_count", "cavmd_coulomb_parameters", "cavmd_coulomb_order",
-           "cavmd_coulomb_create", "cavmd_coulomb_destroy", "cavmd_coulomb_set_items", "cavmd_coulomb_compute",
-           "cavmd_coulomb_structure_device_ptr")
 MADELUNG = 1.7475645946331822
+ROW = checks.ROWS["coulomb"]
 
 
-# ---- 1. header, libraries, binary -------------------------------------------------------------------------------------
+# ---- 1. header and limits ---------------------------------------------------------------------------------------------
 def test_header_declares_the_nine_entry_points_and_keeps_the_version():
-    raw = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_coulomb_\w+)\s*\(", text)))
-    assert len(COULOMB) == 9 and declared == sorted(COULOMB)
-    assert re.search(r"#define\s+CAVMD_VERSION_MINOR\s+2\b", text)
+    checks.header_declares_exactly_the_entry_points(ROW)
+    raw, text = open(HEADER).read(), header_text()
     assert re.search(r"#define\s+CAVMD_COULOMB_MAX_ITEM_N\s+2048\b", text) and re.search(r"#define\s+CAVMD_COULOMB_MAX_K\s+4096\b", text)
-    assert "typedef struct cavmd_coulomb cavmd_coulomb;" in text
     section = raw[raw.index("Ewald Coulomb forces of a batch"):]
     assert "[HOOMD upstream, not in checkout]" in section and "NOT pinned" in section and "discretisation error" in section
     molecular = raw[raw.index("harmonic bonds and Lennard-Jones pairs of a batch"):raw.index("Ewald Coulomb forces of a batch")]
@@ -38,53 +33,21 @@ def test_header_declares_the_nine_entry_points_and_keeps_the_version():
 
 
 def test_libraries_export_them_and_nothing_stray(capi):
-    for path in (capi.LIB_PATH, capi.HOOKS_LIB_PATH):
-        lib = ctypes.CDLL(path)
-        for name in COULOMB:
-            assert hasattr(lib, name), (path, name)
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert {s for s in exported if s.startswith("cavmd_coulomb")} == set(COULOMB), path
-        assert not {s for s in exported if not s.startswith("cavmd_") and not s.startswith("_")}, path
-    for name in COULOMB:
-        assert name in capi.EXPORTED_SYMBOLS
-    assert capi.load().cavmd_version() == 2
-    blob = open(capi.LIB_PATH, "rb").read()
-    assert b"coulomb_structure_kernel" in blob and b"coulomb_force_kernel" in blob and b"gfx950" in blob
+    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
     rows, split, k_rows, k_split = capi.coulomb_order()
     assert split in (1, 4, 16, 64) and rows * split == 256 and k_split in (1, 4, 16, 64) and k_rows * k_split == 256
 
 
-# ---- 2. layout ------------------------------------------------------------------------------------------------------------
 def test_c_layout_equals_the_ctypes_one(capi, tmp_path):
-    """tests/c_abi/coulomb_abi_check.c, built as C99 with -pedantic -Werror, prints sizeof and offsetof of every field as the C
-    compiler sees them; they equal the ctypes structure field by field.  It also runs the refusals seen from C."""
-    src = os.path.join(ROOT, "tests", "c_abi", "coulomb_abi_check.c")
-    exe = str(tmp_path / "coulomb_abi_check")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src,
-                         "-o", exe, "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "COULOMB-ABI-OK" in out.stdout, (out.returncode, out.stdout, out.stderr[-2000:])
-    assert int(re.search(r"sizeof item (\d+)", out.stdout).group(1)) == ctypes.sizeof(capi.CoulombItem) == 96
-    seen = {field: int(off) for field, off in re.findall(r"^item\.(\w+) (\d+)$", out.stdout, flags=re.M)}
-    assert seen == {name: getattr(capi.CoulombItem, name).offset for name, *_ in capi.CoulombItem._fields_}
-    assert seen["Lx"] == 32 and seen["kappa"] == 56 and seen["N"] == 80
-    limits = tuple(int(x) for x in re.search(r"limits (\d+) (\d+) (\d+) (\d+) (\d+)", out.stdout).groups())
+    """... and tests/c_abi/coulomb_abi_check.c prints the header's limits and what cavmd_coulomb_order answers a C caller"""
+    stdout = checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
+    limits = tuple(int(x) for x in re.search(r"limits (\d+) (\d+) (\d+) (\d+) (\d+)", stdout).groups())
     assert limits[:3] == (capi.COULOMB_MAX_ITEM_N, capi.COULOMB_MAX_K, capi.COULOMB_MAX_EXCLUSIONS) == (2048, 4096, 4)
-    order = tuple(int(x) for x in re.search(r"order (\d+) (\d+) (\d+) (\d+)", out.stdout).groups())
+    order = tuple(int(x) for x in re.search(r"order (\d+) (\d+) (\d+) (\d+)", stdout).groups())
     assert order == capi.coulomb_order() and limits[3:] == (order[1], order[3])
 
 
-# ---- 3. refusals and counts ---------------------------------------------------------------------------------------------
-BOX = (8.0, 9.0, 10.0)
-
-
-def _good(capi, n=501, exclusions=((0, 1), (2, 3)), box=BOX, kappa=0.9, r_cut=4.0, k_cut=3.0):
-    return capi.coulomb_item(n, 0x10000, 0x30000, 0x20000, box, kappa, r_cut, k_cut, np.array(exclusions, dtype=np.uint32).reshape(-1, 2))
-
-
+# ---- 2. refusals and counts ---------------------------------------------------------------------------------------------
 def test_item_check_refusals(capi):
     lib = capi.load()
     INV, CAP = capi.CAVMD_ERR_INVALID_VALUE, capi.CAVMD_ERR_CAPACITY
@@ -177,40 +140,22 @@ def test_parameters_follow_the_formula(capi):
 
 
 def test_null_handles_are_refused_without_a_device(capi):
-    lib = capi.load()
-    INV = capi.CAVMD_ERR_INVALID_VALUE
-    it = _good(capi)
-    out = ctypes.c_void_p(123)
-    assert lib.cavmd_coulomb_create(None, 1, ctypes.byref(it), ctypes.byref(out)) == INV and not out.value
-    assert lib.cavmd_coulomb_create(None, 1, ctypes.byref(it), None) == INV
-    assert lib.cavmd_coulomb_destroy(None) == 0
-    assert lib.cavmd_coulomb_set_items(None, 0, 1, ctypes.byref(it)) == INV
-    assert lib.cavmd_coulomb_compute(None, None) == INV
-    assert lib.cavmd_coulomb_structure_device_ptr(None, None, None) == INV
-    assert lib.cavmd_coulomb_order(None, None, None, None) == 0
+    checks.null_arguments_are_refused_without_a_device(ROW, capi)
+    assert capi.load().cavmd_coulomb_order(None, None, None, None) == 0
 
 
-# ---- 4. the Python surface ----------------------------------------------------------------------------------------------
+# ---- 3. the Python surface ------------------------------------------------------------------------------------------------
 def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
     import cavitymd
     from cavitymd import synthetic
-    assert "CoulombForceBatch" in cavitymd.__all__
-    assert cavitymd.CoulombForceBatch is cavitymd.coulomb_batch.CoulombForceBatch
-    for name in ("compute", "potential_energy", "close"):
-        assert callable(getattr(cavitymd.CoulombForceBatch, name)), name
-    assert isinstance(cavitymd.CoulombForceBatch.forces, property)
-    for name in ("compute", "set_items", "close", "structure_device_ptr"):
-        assert callable(getattr(capi.Coulomb, name)), name
+    checks.python_class_is_exported_and_refuses_cpu_tensors(ROW, capi)
     cfg = synthetic.diatomic_lattice(2, 8.0, seed=3)
-    bonds, _ = synthetic.diatomic_bonds(cfg)
     pd = cavitymd.ParticleData.from_arrays(cfg["position"], cfg["typeid"], cfg["charge"], cfg["image"], cfg["types"], cfg["box"],
                                            device="cpu")
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.CoulombForceBatch([cavitymd.SystemDefinition(pd)], [bonds], r_cut=6.0, accuracy=1e-6)
     assert isinstance(pd.getCharges(), torch.Tensor)
 
 
-# ---- 5. the mirror against physics ------------------------------------------------------------------------------------------
+# ---- 4. the mirror against physics ------------------------------------------------------------------------------------------
 def test_mirror_gives_the_madelung_constant_of_rock_salt():
     g = np.arange(4)
     ijk = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)

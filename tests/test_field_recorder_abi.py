@@ -1,32 +1,23 @@
-"""The field recorder (cavmd_field_recorder_*) on a machine WITHOUT a GPU: the header declares and both libraries export the
-ten entry points, the record and item layouts agree between the header as a C compiler reads it, ctypes and numpy, the
-per-item validation and the refusals of create's scalar arguments work without a device, nothing can be created without one,
-and the Python class refuses CPU tensors."""
+"""What is specific to the field recorder (cavmd_field_recorder_*) on a machine WITHOUT a GPU: the contract and the limits the
+header states, the per-item validation and the refusals of create's scalar arguments (host arithmetic).  Header, exports,
+layouts, null arguments, launch order, Python surface and deferred destroy are the shared checks of tests/batch_objects.py,
+called here with this object's row."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
-import torch
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
-FIELD = ("cavmd_field_recorder_item_check", "cavmd_field_recorder_create", "cavmd_field_recorder_destroy",
-         "cavmd_field_recorder_set_items", "cavmd_field_recorder_record", "cavmd_field_recorder_rows",
-         "cavmd_field_recorder_read", "cavmd_field_recorder_read_fields", "cavmd_field_recorder_reset",
-         "cavmd_field_recorder_device_ptr")
+import batch_objects as checks
+from abi_support import HEADER, header_text
+
+ROW = checks.ROWS["field_recorder"]
 
 
 def test_header_declares_the_entry_points_and_states_the_contract():
-    raw = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_field_recorder_\w+)\s*\(", text)))
-    assert declared == sorted(FIELD)
+    checks.header_declares_exactly_the_entry_points(ROW)
+    raw, text = open(HEADER).read(), header_text()
     assert re.search(r"#define\s+CAVMD_FIELD_MAX_WAVEVECTORS\s+256\b", text)
     assert re.search(r"#define\s+CAVMD_FIELD_MAX_REFERENCES\s+16\b", text)
-    assert "typedef struct cavmd_field_recorder cavmd_field_recorder;" in text
     start = raw.index("density field and F(k,t) of a batch, recorded on the device")
     section = " ".join(raw[start:raw.index("cavmd_field_recorder_device_ptr(")].replace("*", " ").split())
     for phrase in ("analysis.py:260-418", ":380-414", "bit for bit", "no FMA", "AFTER step 2", "depends on (N, n_k) ONLY",
@@ -35,45 +26,11 @@ def test_header_declares_the_entry_points_and_states_the_contract():
     assert "FieldAutocorrelationTracker" in raw[:raw.index("#ifndef CAVMD_H_")]   # the reference-interface table at the top
 
 
-def test_libraries_export_them_and_carry_the_kernel(capi):
-    for path in (capi.LIB_PATH, capi.HOOKS_LIB_PATH):
-        lib = ctypes.CDLL(path)
-        for name in FIELD:
-            assert hasattr(lib, name), (path, name)
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert {s for s in exported if s.startswith("cavmd_field_recorder")} == set(FIELD), path
-    assert set(FIELD) <= set(capi.EXPORTED_SYMBOLS)
-    blob = open(capi.LIB_PATH, "rb").read()
-    assert b"field_recorder_batch_kernel" in blob and b"gfx950" in blob
-
-
 def test_layouts_match_between_c_ctypes_and_numpy(capi, tmp_path):
-    """tests/c_abi/field_recorder_abi_check.c prints sizes and offsets as a C99 compiler sees the header."""
-    src = os.path.join(ROOT, "tests", "c_abi", "field_recorder_abi_check.c")
-    exe = str(tmp_path / "field_recorder_abi_check")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src,
-                         "-o", exe, "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "FIELD-RECORDER-ABI-OK" in out.stdout, (out.returncode, out.stdout, out.stderr[-2000:])
-    if not torch.cuda.is_available():
-        assert "no device: no workspace, hence no field recorder" in out.stdout
-    lines = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in out.stdout.splitlines() if l.split()[0] in
-             ("record", "item", "limits")}
-    R, I = capi.FieldRecord, capi.FieldItem
-    assert lines["record"] == [160, 0, 8, 12, 16, 24, 32]
-    assert lines["record"] == [ctypes.sizeof(R), R.call.offset, R.n_references.offset, R.took_reference.offset, R.rho2.offset,
-                               R.reserved.offset, R.F.offset]
-    assert lines["item"] == [64, 0, 8, 16, 20, 24]
-    assert lines["item"] == [ctypes.sizeof(I), I.d_position.offset, I.position_stride.offset, I.N.offset, I.reserved0.offset,
-                             I.reserved.offset]
-    assert lines["limits"] == [capi.FIELD_MAX_WAVEVECTORS, capi.FIELD_MAX_REFERENCES] == [256, 16]
-    dt = capi.field_record_dtype()
-    assert dt.itemsize == 160 and dt["F"].shape == (16,)
-    for name, _ in R._fields_:
-        assert dt.fields[name][1] == getattr(R, name).offset, name
+    """... and the limits as a C99 compiler sees them (tests/c_abi/field_recorder_abi_check.c) are the ones Python restates"""
+    stdout = checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
+    limits = re.search(r"^limits (\d+) (\d+)$", stdout, flags=re.M)
+    assert [int(x) for x in limits.groups()] == [capi.FIELD_MAX_WAVEVECTORS, capi.FIELD_MAX_REFERENCES] == [256, 16]
 
 
 def test_item_check_verdicts(capi):
@@ -141,69 +98,14 @@ def test_create_refuses_its_scalar_arguments_before_it_touches_a_device(capi):
     assert create(2, bad_row, 50, kp, 8, 1, 1) == INV
 
 
+# ---- the checks every batch object gets (tests/batch_objects.py), on this object's row ---------------------------------------
+def test_libraries_export_them_and_carry_the_kernel(capi):
+    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
+
+
 def test_null_handles_are_refused_without_a_device(capi):
-    lib = capi.load()
-    INV = capi.CAVMD_ERR_INVALID_VALUE
-    it = capi.field_item(0x10000, 24, 501)
-    kv = np.zeros((1, 3))
-    out = ctypes.c_void_p(123)
-    rows, n = ctypes.c_uint64(), ctypes.c_uint32()
-    rec = capi.FieldRecord()
-    args = (1, ctypes.byref(it), 1, ctypes.c_void_p(kv.ctypes.data), 8, 1, 1, 0)
-    assert lib.cavmd_field_recorder_create(None, *args, ctypes.byref(out)) == INV and not out.value
-    assert lib.cavmd_field_recorder_create(None, *args, None) == INV
-    assert lib.cavmd_field_recorder_destroy(None) == 0
-    assert lib.cavmd_field_recorder_set_items(None, 0, 1, ctypes.byref(it)) == INV
-    assert lib.cavmd_field_recorder_record(None, None, None) == INV
-    assert lib.cavmd_field_recorder_rows(None, None, ctypes.byref(rows)) == INV
-    assert lib.cavmd_field_recorder_read(None, None, 0, 1, 0, 1, ctypes.byref(rec)) == INV
-    assert lib.cavmd_field_recorder_read_fields(None, None, 0, None, None, None, ctypes.byref(n)) == INV
-    assert lib.cavmd_field_recorder_reset(None, None) == INV
-    assert lib.cavmd_field_recorder_device_ptr(None, ctypes.byref(out), ctypes.byref(out)) == INV
-
-
-@pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
-def test_no_device_no_workspace_no_field_recorder(capi):
-    with pytest.raises(capi.CavmdError) as e:
-        capi.Workspace(1)
-    assert e.value.status == capi.CAVMD_ERR_NO_DEVICE
+    checks.null_arguments_are_refused_without_a_device(ROW, capi)
 
 
 def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
-    import cavitymd
-    assert "BatchFieldRecorder" in cavitymd.__all__
-    assert cavitymd.BatchFieldRecorder is cavitymd.field_recorder.BatchFieldRecorder
-    for name in ("record", "rows", "read", "fields", "reset", "close"):
-        assert callable(getattr(cavitymd.BatchFieldRecorder, name)), name
-    for name in ("record", "rows", "read", "read_fields", "reset", "set_items", "device_ptr", "close"):
-        assert callable(getattr(capi.FieldRecorder, name)), name
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.BatchFieldRecorder([torch.zeros((10, 3), dtype=torch.float64)])
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.BatchFieldRecorder([np.zeros((10, 4))])
-
-
-def test_deferred_destroy_takes_field_recorders_before_workspaces(capi, monkeypatch):
-    order = []
-
-    class Lib:
-        def cavmd_destroy(self, h):
-            order.append(("ws", h.value))
-            return 0
-
-        def cavmd_field_recorder_destroy(self, h):
-            order.append(("field_recorder", h.value))
-            return 0
-
-    ws = object.__new__(capi.Workspace)
-    ws._lib, ws._h = Lib(), ctypes.c_void_p(0x10)
-    r = object.__new__(capi.FieldRecorder)
-    r._lib, r._h, r._ws = ws._lib, ctypes.c_void_p(0x20), ws
-    monkeypatch.setattr(capi, "_capturing", lambda: True)
-    ws.close()
-    r.close()
-    assert order == [] and not r._h.value and not ws._h.value
-    monkeypatch.setattr(capi, "_capturing", lambda: False)
-    capi._destroy_deferred()
-    assert order == [("field_recorder", 0x20), ("ws", 0x10)]
-    assert not capi._deferred and not capi._deferred_children
+    checks.python_class_is_exported_and_refuses_cpu_tensors(ROW, capi)

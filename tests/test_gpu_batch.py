@@ -25,6 +25,7 @@ import torch
 
 import cavitymd
 from cavitymd import _capi, replicas, synthetic
+from parity_support import random_cfg as _random_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -32,20 +33,6 @@ ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 PRM = {"omegac": 0.0091, "couplstr": 1e-3, "phmass": 1.0}
 GUARD = 4                                    # guard rows (32 B each) before and after every force array
 GUARD_VALUE = -7.25
-
-
-def _random_cfg(n, seed, photon_at=None, L=(31.0, 17.5, 23.25), image_range=3, photon_charge=0.0):
-    """the recipe of tests/test_gpu_parity.py"""
-    rng = np.random.default_rng(seed)
-    pos = rng.uniform(-0.5, 0.5, (n, 3)) * np.asarray(L)
-    tid = rng.integers(0, 2, n).astype(np.int32)
-    charge = rng.uniform(-1, 1, n)
-    if photon_at is not None:
-        tid[photon_at] = 2
-        charge[photon_at] = photon_charge
-    image = rng.integers(-image_range, image_range + 1, (n, 3)).astype(np.int32)
-    return {"name": f"rand{n}", "seed": seed, "position": pos, "typeid": tid, "charge": charge, "image": image,
-            "types": ["O", "N", "L"], "box": L, "L_typeid": 2, "params": dict(PRM)}
 
 
 class Dev:

@@ -10,7 +10,8 @@ import torch
 
 import cavitymd
 from cavitymd import _capi
-from test_gpu_molecular_batch import HARMONIC, LJ, _same
+from gpu_support import same as _same
+from water_systems import HARMONIC, LJ
 
 pytestmark = pytest.mark.gpu
 

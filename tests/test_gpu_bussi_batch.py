@@ -20,25 +20,17 @@ import pytest
 import torch
 
 import cavitymd
+from abi_support import bits as _bits
 from cavitymd import _capi, synthetic, thermostats
+from gpu_support import same_bits_on_device as _same_bits
+from gpu_support import same_or_both_nan as _same
+from gpu_support import stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "bussi_reference_golden.npz")
 OK, BAD = _capi.CAVMD_OK, _capi.CAVMD_ERR_BAD_PARAMS
-
-
-def _bits(x) -> int:
-    return int(np.float64(x).view(np.uint64))
-
-
-def _same(a, b) -> bool:
-    return _bits(a) == _bits(b) or (math.isnan(a) and math.isnan(b))
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _rows_to_device(rows, dev_rows=None):
@@ -50,10 +42,6 @@ def _rows_to_device(rows, dev_rows=None):
         dev_rows.copy_(t)
         return dev_rows
     return t
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return bool(torch.equal(a.view(torch.int64), b.view(torch.int64)))
 
 
 def _single_read(ws):

@@ -22,8 +22,10 @@ import pytest
 import torch
 
 from cavitymd import _capi
+from gpu_support import bits as _bits
 from oracle import numpy_mirror as nm
-from test_gpu_parity import _random_cfg, check_parity, force_scales, forces_from_dipole, gpu_eval, ref_eval
+from parity_support import check_parity, force_scales, forces_from_dipole, gpu_eval, ref_eval
+from parity_support import random_cfg as _random_cfg
 
 gpu = pytest.mark.gpu
 
@@ -114,10 +116,6 @@ def soa_mirror(n, cus, tunables=None):
 
 # ---- one workspace, one set of device buffers, every call observed ---------------------------------------------------------------
 PAD = 512  # rows behind N that must stay NaN
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 class Rig:

@@ -20,6 +20,8 @@ import torch
 
 import cavitymd
 from cavitymd import _capi
+from gpu_support import same_bits as _same_bits
+from gpu_support import stream as _stream
 from oracle import observables as obs
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +30,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RAGGED_SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 501, 1024, 4097, 65536)
 NK_LIST = (1, 17, 50, 64, 65, 128, 256)
 INV, EXPIRED, NOT_COMPUTED = _capi.CAVMD_ERR_INVALID_VALUE, _capi.CAVMD_ERR_EXPIRED, _capi.CAVMD_ERR_NOT_COMPUTED
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _wavevectors(n_k, kmag=1.0):
@@ -54,10 +52,6 @@ def _F(ref, cur):
     for k in range(len(cur)):
         acc = acc + (np.float64(ref[k].real) * np.float64(cur[k].real) + np.float64(ref[k].imag) * np.float64(cur[k].imag))
     return acc / np.float64(len(cur))
-
-
-def _same_bits(a, b):
-    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
 
 
 def _expect_status(status, fn, *args):

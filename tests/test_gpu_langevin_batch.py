@@ -20,19 +20,13 @@ import torch
 import cavitymd
 import langevin_twin as twin
 from cavitymd import _capi
+from gpu_support import bits as _u64
+from gpu_support import same as _same
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 PARAMS = {"omegac": 9.1e-3, "couplstr": 1e-3, "phmass": 1.0}
-
-
-def _u64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b) -> bool:
-    return bool(np.array_equal(_u64(a), _u64(b)))
 
 
 def _free_systems(sizes, langevin, seed):
@@ -188,11 +182,8 @@ def test_a_captured_draw_is_fresh_on_every_replay():
 
 
 # ---- 3. the bath thermalises a free particle --------------------------------------------------------------------------------
-# The acceptance band of the three ratios (measured / closed form): 6 standard deviations across the 24 seeds of the HOST twin,
-# tests/langevin_twin.py at these very members, steps and parameters, as printed by tests/test_langevin_twin.py (which fails if
-# these literals are not that run's figures).  Not from a GPU run.  That run: seeds 0..23, standard deviations 0.00276, 0.00207,
-# 0.00134 around means 1.00009, 1.00012, 1.00021, worst single seed 0.0058 from 1.
-BAND = (0.0166, 0.0124, 0.0080)
+# The acceptance band of the three ratios (measured / closed form) comes from the HOST twin: tests/langevin_twin.py, BAND.
+BAND = twin.BAND
 
 
 def test_the_bath_thermalises_free_particles_from_one_graph():

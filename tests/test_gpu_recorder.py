@@ -23,6 +23,8 @@ import torch
 
 import cavitymd
 from cavitymd import _capi, observables as prod, synthetic
+from gpu_support import same as _same
+from gpu_support import stream as _stream
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -31,18 +33,6 @@ L_TYPEID = 1
 BOX = (40.0, 41.0, 42.0)
 FLOAT_COLUMNS = ("energy", "total_dipole", "q", "cavity_kinetic", "cavity_temperature", "kinetic_energy", "force_mass_sum",
                  "reserved")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b) -> bool:
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _cavity_mode_numpy(vel_row, kB):

@@ -4,7 +4,7 @@ force batch (cavmd_molecular_*) and the Ewald Coulomb batch (cavmd_coulomb_*).  
 The splits are compile-time constants, so a process only ever sees one of them in the product library.  The Makefile's
 `split_variants` builds the product three more times (cavitymd._capi.SPLIT_VARIANTS); with the default build every allowed
 value of CAVMD_MOLECULAR_J_SPLIT, CAVMD_COULOMB_J_SPLIT and CAVMD_COULOMB_K_SPLIT then runs here once:
-  1. each build's ragged batch against the mirrors (the helpers of test_gpu_molecular_batch.py and test_gpu_coulomb_batch.py),
+  1. each build's ragged batch against the mirrors (tests/molecular_ragged.py and tests/coulomb_ragged.py),
      at sizes on that build's own ROWS and KROWS boundaries, and a second compute repeating the first bit for bit;
   2. per build and per batch, a compute captured into a graph, a set_items outside any capture, and a replay of the OLD graph:
      same sizes and other arrays; a shrunk item; an item grown past the captured LDS; for Coulomb a smaller and a larger K;
@@ -16,16 +16,15 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_coulomb_batch as coulomb_tests
-import test_gpu_molecular_batch as molecular_tests
+import coulomb_ragged
+import molecular_ragged
 from cavitymd import _capi
-from test_gpu_molecular_batch import _same, _stream
+from gpu_support import same as _same
+from gpu_support import stream as _stream
+from split_builds import BUILDS, k_counts_for, k_values_for, replay_k_counts, sizes_for
 
 pytestmark = pytest.mark.gpu
 
-# build -> (CAVMD_MOLECULAR_J_SPLIT, CAVMD_COULOMB_J_SPLIT, CAVMD_COULOMB_K_SPLIT): the product library and csrc/Makefile's
-# split_variants
-BUILDS = {"product": (16, 16, 4), "a": (1, 1, 1), "b": (4, 4, 16), "c": (16, 64, 64)}
 SENTINEL = 7.0
 GUARD = 8   # rows of sentinel before, between and after the items' force arrays
 SPARE = 3   # rows a force array is longer than its item
@@ -44,48 +43,13 @@ def build(request):
     return request.param, lib
 
 
-# ---- the shapes (also checked without a GPU by test_split_variants_abi.py) -------------------------------------------------
-def _distinct(values):
-    out = []
-    for v in values:
-        if v >= 0 and v not in out:
-            out.append(v)
-    return tuple(out)
-
-
-def sizes_for(rows):
-    """N on the boundaries of a workgroup of `rows` particles, the wave (64: also the S = 64 group) and the production system
-    (501, which carries every planted edge)"""
-    return _distinct((0, 1, 2, rows - 1, rows, rows + 1, 2 * rows + 1, 63, 64, 65, 501))
-
-
-def k_values_for(k_rows):
-    """K on the boundaries of a workgroup of `k_rows` k-vectors.  mirror.box_and_k_cut_for finds a box for every one of them,
-    at all four KROWS and for both base boxes of _ragged_system (test_split_variants_abi.py checks it against each library's
-    own count), so none is replaced by a neighbour."""
-    return _distinct((0, 1, k_rows - 1, k_rows, k_rows + 1, 2 * k_rows + 1, 300))
-
-
-def k_counts_for(sizes, k_rows):
-    """the K values cycled over the items"""
-    values = k_values_for(k_rows)
-    return tuple(values[i % len(values)] for i in range(len(sizes)))
-
-
-def replay_k_counts(k_rows):
-    """K of the three items of the replay tests (two, three and one workgroup of launch 1), what item 1 shrinks to (one
-    workgroup) and what it grows to (at least two workgroups more than it was captured with)"""
-    grown = 300 if 300 > 3 * k_rows else 4 * k_rows + 1
-    return (k_rows + 1, 2 * k_rows + 1, k_rows - 1), k_rows, grown
-
-
 # ---- 1. every split against the mirrors ----------------------------------------------------------------------------------------
 def test_molecular_split_equals_the_mirror_bit_for_bit(build):
     name, lib = build
     ROWS, S = _capi.molecular_order(lib)
     sizes = sizes_for(ROWS)
     assert sum(1 for n in sizes if n > 19) >= 2 and {ROWS - 1, ROWS, ROWS + 1, 2 * ROWS + 1, 64, 501} <= set(sizes)
-    molecular_tests.ragged_batch_equals_the_mirror_bit_for_bit(lib, sizes, repeat=True)
+    molecular_ragged.ragged_batch_equals_the_mirror_bit_for_bit(lib, sizes, repeat=True)
 
 
 def test_coulomb_split_stays_within_the_mirror_bound(build):
@@ -100,7 +64,7 @@ def test_coulomb_split_stays_within_the_mirror_bound(build):
     kept = {K for n, K in zip(sizes, counts) if n > 0}
     assert {KROWS - 1, KROWS, KROWS + 1, 2 * KROWS + 1} <= kept and set(counts) == set(k_values_for(KROWS))
     assert any(0 < K < KROWS for K in kept) and any(KROWS < K <= 2 * KROWS for K in kept) and any(K > 2 * KROWS for K in kept)
-    worst = coulomb_tests.ragged_batch_stays_within_the_mirror_bound(lib, sizes, counts, repeat=True)
+    worst = coulomb_ragged.ragged_batch_stays_within_the_mirror_bound(lib, sizes, counts, repeat=True)
     print(f"\nbuild {name} (S = {S}, T = {T}): K per item {counts}, largest error / bound = {worst:.4f}")
 
 
@@ -149,13 +113,13 @@ class MolecularKind:
     def __init__(self, lib):
         self.lib = lib
         self.rows = _capi.molecular_order(lib)[0]
-        self.params = molecular_tests._ragged_params()
+        self.params = molecular_ragged.ragged_params()
 
     def system(self, k, n, rng, K=None, other_list=False):
-        s = molecular_tests._ragged_system(k, n, rng)
+        s = molecular_ragged.ragged_system(k, n, rng)
         if other_list:                                                           # the last ordinary bond gives way to another
             s["bonds"] = np.concatenate([s["bonds"][:-1], np.array([[n - 10, n - 8, 1]], dtype=np.uint32)])
-        s["pos"] = torch.from_numpy(molecular_tests._pos4(s)).cuda()
+        s["pos"] = torch.from_numpy(molecular_ragged.pos4(s)).cuda()
         return s
 
     def item(self, s, force_ptr):
@@ -173,7 +137,7 @@ class CoulombKind:
         self.rows, _, self.k_rows, _ = _capi.coulomb_order(lib)
 
     def system(self, k, n, rng, K=None, other_list=False):
-        s = coulomb_tests._ragged_system(k, n, K, rng)
+        s = coulomb_ragged.ragged_system(k, n, K, rng)
         if other_list:                                                           # the last ordinary exclusion gives way to another
             s["ex"] = np.concatenate([s["ex"][:-1], np.array([[n - 10, n - 8]], dtype=np.uint32)])
         p = np.zeros((n, 4))
@@ -182,9 +146,9 @@ class CoulombKind:
         return s
 
     def item(self, s, force_ptr):
-        it = _capi.coulomb_item(s["N"], s["pos"].data_ptr(), s["charge"].data_ptr(), force_ptr, s["box"], coulomb_tests.KAPPA,
-                                coulomb_tests.R_CUT, s["k_cut"], s["ex"])
-        assert coulomb_tests._k_count(self.lib, it) == s["K"]
+        it = _capi.coulomb_item(s["N"], s["pos"].data_ptr(), s["charge"].data_ptr(), force_ptr, s["box"], coulomb_ragged.KAPPA,
+                                coulomb_ragged.R_CUT, s["k_cut"], s["ex"])
+        assert coulomb_ragged.k_count(self.lib, it) == s["K"]
         return it
 
     def create(self, ws, items):

@@ -16,90 +16,20 @@ import torch
 
 import cavitymd
 from cavitymd import _capi, synthetic
+from gpu_support import bits as _u64
+from gpu_support import same as _same
+from gpu_support import stream as _stream
+from verlet_mirror import mirror_accelerations, mirror_step_one, mirror_step_two
 
 pytestmark = pytest.mark.gpu
 
 INV = _capi.CAVMD_ERR_INVALID_VALUE
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _u64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b) -> bool:
-    return bool(np.array_equal(_u64(a), _u64(b)))
-
-
 def _rows_array(rows) -> np.ndarray:
     """a list of VerletInput -> (B, 8) float64 holding their bytes"""
     arr = (_capi.VerletInput * len(rows))(*rows)
     return np.frombuffer(bytes(arr), dtype=np.float64).reshape(len(rows), 8).copy()
-
-
-# ---- the numpy mirror of the contract -----------------------------------------------------------------------------------------
-def mirror_net_force(forces):
-    F = forces[0].copy()
-    for f in forces[1:]:
-        F = F + f                                            # left to right, .w included
-    return F
-
-
-def mirror_accelerations(s) -> None:
-    """steps 1, 2, 3 and 5 of step two"""
-    if s["N"] == 0:
-        return
-    minv = 1.0 / s["vel"][:, 3]
-    F = mirror_net_force(s["forces"])
-    if s["net"] is not None:
-        s["net"] = F.copy()
-    s["accel"] = F[:, :3] * minv[:, None]
-
-
-def mirror_step_one(s, row, classify=None) -> None:
-    if s["N"] == 0 or row.skip:
-        return
-    dt = np.float64(row.dt)
-    for c in range(3):
-        L = np.float64(s["box"][c])
-        v = s["vel"][:, c] + (0.5 * s["accel"][:, c]) * dt
-        x = s["pos"][:, c] + dt * v
-        hi = L * 0.5
-        lo = -hi
-        if classify is not None:
-            classify(c, x, lo, hi, L)
-        up = x >= hi
-        down = ~up & (x < lo)
-        x = np.where(up, x - L, np.where(down, x + L, x))
-        s["image"][:, c] += up.astype(np.int32) - down.astype(np.int32)
-        s["out_of_box"] += int(np.count_nonzero(~((x >= lo) & (x < hi))))
-        s["vel"][:, c] = v
-        s["pos"][:, c] = x
-
-
-def mirror_step_two(s, row) -> None:
-    if s["N"] == 0 or row.skip:
-        return
-    dt, gamma, coeff = np.float64(row.dt), np.float64(row.langevin_gamma), np.float64(row.langevin_coeff)
-    minv = 1.0 / s["vel"][:, 3]
-    F = mirror_net_force(s["forces"])
-    if s["net"] is not None:
-        s["net"] = F.copy()
-    F = F[:, :3].copy()
-    j = s["langevin"]
-    if j >= 0 and gamma != 0.0:
-        v = s["vel"][j, :3].copy()                           # from BEFORE the kick
-        bd = np.array(row.uniform[:], dtype=np.float64) * coeff - gamma * v
-        F[j] = F[j] + bd
-        tally = (bd[0] * v[0] + bd[1] * v[1]) + bd[2] * v[2]
-        s["reservoir"] = s["reservoir"] - tally * dt
-    a = F * minv[:, None]
-    s["accel"] = a
-    s["vel"][:, :3] = s["vel"][:, :3] + (0.5 * a) * dt
-    s["steps"] += 1
 
 
 # ---- 1. one ragged batch --------------------------------------------------------------------------------------------------------

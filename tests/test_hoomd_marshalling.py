@@ -85,7 +85,8 @@ def test_energy_cache_is_keyed_on_the_evaluation_not_the_timestep():
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", ["hoomd_views", "packed"])
 def test_custom_route_marshalling_on_cuda_array_interface_exporters(ref, oracle_mod, layout):
-    from test_gpu_parity import _random_cfg, check_parity, ref_eval
+    from parity_support import check_parity, ref_eval
+    from parity_support import random_cfg as _random_cfg
     for n, photon_at in ((3000, 2999), (70_001, 5)):
         cfg = _random_cfg(n, seed=n + 17, photon_at=photon_at)
         dev = "cuda"

@@ -9,7 +9,6 @@ import numpy as np
 import pytest
 
 import langevin_twin as twin
-from test_gpu_langevin_batch import BAND
 
 SEEDS = tuple(range(24))
 NAMES = ("m <v^2> / kT after step two", "m <v^2> (1 - x) / kT after step one", "reservoir growth / closed form")
@@ -53,9 +52,9 @@ def test_the_contract_is_a_thermostat(runs, measured_band):
 
 def test_the_band_next_to_the_gpu_assertions_is_six_sigma_of_this_twin(measured_band):
     # the literals are these figures rounded to four decimals; they come from this host run, never from a GPU run
-    assert len(BAND) == 3
-    assert np.all(np.abs(np.asarray(BAND) - measured_band) <= 0.5e-4), (BAND, measured_band.tolist())
-    assert np.all(np.asarray(BAND) < 0.03)                                    # a band this tight is what (b) relies on
+    assert len(twin.BAND) == 3
+    assert np.all(np.abs(np.asarray(twin.BAND) - measured_band) <= 0.5e-4), (twin.BAND, measured_band.tolist())
+    assert np.all(np.asarray(twin.BAND) < 0.03)                                    # a band this tight is what (b) relies on
 
 
 @pytest.mark.parametrize("mistake", twin.MISTAKES)
@@ -63,4 +62,4 @@ def test_a_planted_mistake_leaves_the_band(mistake):
     for seed in SEEDS[:4]:
         r = twin.run(seed, mistake=mistake)
         print(f"{mistake}, seed {seed}: ratios {r.round(4).tolist()}")
-        assert np.any(np.abs(r - 1.0) > np.asarray(BAND)), (mistake, seed, r)
+        assert np.any(np.abs(r - 1.0) > np.asarray(twin.BAND)), (mistake, seed, r)

@@ -1,98 +1,49 @@
-"""The molecular force batch (cavmd_molecular_*) on a machine WITHOUT a GPU: the header declares and both libraries export the
-eight entry points and nothing stray, the version is still 2, the layouts agree between C and ctypes, every refusal works
-without a device, the pair maker equals the numpy mirror bit for bit, the Python class refuses CPU tensors -- and the mirror
-itself (tests/molecular_mirror.py), which the GPU tests compare the kernel with, gives the closed-form answers."""
+"""What is specific to the molecular force batch (cavmd_molecular_*) on a machine WITHOUT a GPU: the limits and the origin of the
+expressions the header states, the order the library answers, every refusal of the two validations, the pair maker against the
+numpy mirror bit for bit -- and the mirror itself (tests/molecular_mirror.py), which the GPU tests compare the kernel with,
+against the closed-form answers.  Header, exports, layouts, null arguments, launch order, Python surface and deferred destroy
+are the shared checks of tests/batch_objects.py, called here with this object's row."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 import torch
 
+import batch_objects as checks
 import molecular_mirror as mirror
+from abi_support import HEADER, header_text
+from abi_support import bits as _bits
+from abi_support import good_molecular as _good
+from abi_support import molecular_params as _params
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
-MOLECULAR = ("cavmd_molecular_pair_make", "cavmd_molecular_params_check", "cavmd_molecular_item_check", "cavmd_molecular_create",
-             "cavmd_molecular_destroy", "cavmd_molecular_set_items", "cavmd_molecular_compute", "cavmd_molecular_order")
-
-
-def _bits(x) -> int:
-    return int(np.float64(x).view(np.uint64))
+ROW = checks.ROWS["molecular"]
 
 
-# ---- 1. header, libraries, binary -------------------------------------------------------------------------------------
+# ---- 1. header and limits ---------------------------------------------------------------------------------------------
 def test_header_declares_the_eight_entry_points_and_keeps_the_version():
+    checks.header_declares_exactly_the_entry_points(ROW)
     raw = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_molecular_\w+)\s*\(", text)))
-    assert len(MOLECULAR) == 8 and declared == sorted(MOLECULAR)
-    assert re.search(r"#define\s+CAVMD_VERSION_MINOR\s+2\b", text)
-    assert re.search(r"#define\s+CAVMD_MOLECULAR_MAX_ITEM_N\s+2048\b", text)
-    assert "typedef struct cavmd_molecular cavmd_molecular;" in text
+    assert re.search(r"#define\s+CAVMD_MOLECULAR_MAX_ITEM_N\s+2048\b", header_text())
     section = raw[raw.index("harmonic bonds and Lennard-Jones pairs of a batch"):]
     assert "[HOOMD upstream, not in checkout]" in section and "NOT pinned" in section
 
 
 def test_libraries_export_them_and_nothing_stray(capi):
-    for path in (capi.LIB_PATH, capi.HOOKS_LIB_PATH):
-        lib = ctypes.CDLL(path)
-        for name in MOLECULAR:
-            assert hasattr(lib, name), (path, name)
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert {s for s in exported if s.startswith("cavmd_molecular")} == set(MOLECULAR), path
-        assert not {s for s in exported if not s.startswith("cavmd_") and not s.startswith("_")}, path
-    for name in MOLECULAR:
-        assert name in capi.EXPORTED_SYMBOLS
-    assert capi.load().cavmd_version() == 2
-    blob = open(capi.LIB_PATH, "rb").read()
-    assert b"molecular_force_kernel" in blob and b"gfx950" in blob
+    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
     rows, split = capi.molecular_order()
     assert split in (1, 4, 16) and rows * split == 256
 
 
-# ---- 2. layouts ---------------------------------------------------------------------------------------------------------
 def test_c_layouts_equal_the_ctypes_ones(capi, tmp_path):
-    """tests/c_abi/molecular_abi_check.c, built as C99 with -pedantic -Werror, prints sizeof and offsetof of every field as the
-    C compiler sees them; they equal the ctypes structures field by field.  It also runs the refusals seen from C."""
-    src = os.path.join(ROOT, "tests", "c_abi", "molecular_abi_check.c")
-    exe = str(tmp_path / "molecular_abi_check")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src,
-                         "-o", exe, "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "MOLECULAR-ABI-OK" in out.stdout, (out.returncode, out.stdout, out.stderr[-2000:])
-    structs = {"pair": capi.MolecularPair, "bond_params": capi.MolecularBondParams, "params": capi.MolecularParams,
-               "bond": capi.MolecularBond, "item": capi.MolecularItem}
-    sizes = re.search(r"sizeof pair (\d+) bond_params (\d+) params (\d+) bond (\d+) item (\d+)", out.stdout)
-    assert tuple(int(x) for x in sizes.groups()) == (64, 16, 4240, 12, 64)
-    assert tuple(ctypes.sizeof(structs[k]) for k in ("pair", "bond_params", "params", "bond", "item")) == (64, 16, 4240, 12, 64)
-    seen = {k: {} for k in structs}
-    for which, field, off in re.findall(r"^(pair|bond_params|params|bond|item)\.(\w+) (\d+)$", out.stdout, flags=re.M):
-        seen[which][field] = int(off)
-    for which, S in structs.items():
-        assert seen[which] == {name: getattr(S, name).offset for name, *_ in S._fields_}, which
-    assert seen["params"]["pair"] == 16 and seen["params"]["bond"] == 4112 and seen["item"]["N"] == 48
-    limits = tuple(int(x) for x in re.search(r"limits (\d+) (\d+) (\d+) (\d+) (\d+)", out.stdout).groups())
+    """... and tests/c_abi/molecular_abi_check.c prints the header's limits and what cavmd_molecular_order answers a C caller"""
+    stdout = checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
+    limits = tuple(int(x) for x in re.search(r"limits (\d+) (\d+) (\d+) (\d+) (\d+)", stdout).groups())
     assert limits[:4] == (capi.MOLECULAR_MAX_ITEM_N, 8, 8, capi.MOLECULAR_MAX_BONDS) == (2048, 8, 8, 4)
-    assert tuple(int(x) for x in re.search(r"order (\d+) (\d+)", out.stdout).groups()) == capi.molecular_order()
+    assert tuple(int(x) for x in re.search(r"order (\d+) (\d+)", stdout).groups()) == capi.molecular_order()
     assert limits[4] == capi.molecular_order()[1]
 
 
-# ---- 3. refusals ----------------------------------------------------------------------------------------------------------
-def _params(capi, r_cut=3.0):
-    return capi.molecular_params(3, {0: (0.7, 2.2), 1: (1.4, 2.0)},
-                                 {(0, 0): (1e-3, 2.0, r_cut), (0, 1): (2e-3, 1.5, r_cut), (1, 1): (5e-4, 1.0, 0.5 * r_cut)})
-
-
-def _good(capi, n=501, bonds=((0, 1, 0), (2, 3, 1)), box=(8.0, 9.0, 10.0)):
-    return capi.molecular_item(n, 0x10000, 0x20000, box, np.array(bonds, dtype=np.uint32).reshape(-1, 3))
-
-
+# ---- 2. refusals ----------------------------------------------------------------------------------------------------------
 def test_params_check_refusals(capi):
     lib = capi.load()
     INV = capi.CAVMD_ERR_INVALID_VALUE
@@ -182,19 +133,11 @@ def test_item_check_refusals(capi):
 
 
 def test_null_handles_are_refused_without_a_device(capi):
-    lib = capi.load()
-    INV = capi.CAVMD_ERR_INVALID_VALUE
-    prm, it = _params(capi), _good(capi)
-    out = ctypes.c_void_p(123)
-    assert lib.cavmd_molecular_create(None, ctypes.byref(prm), 1, ctypes.byref(it), ctypes.byref(out)) == INV and not out.value
-    assert lib.cavmd_molecular_create(None, ctypes.byref(prm), 1, ctypes.byref(it), None) == INV
-    assert lib.cavmd_molecular_destroy(None) == 0
-    assert lib.cavmd_molecular_set_items(None, 0, 1, ctypes.byref(it)) == INV
-    assert lib.cavmd_molecular_compute(None, None) == INV
-    assert lib.cavmd_molecular_order(None, None) == 0
+    checks.null_arguments_are_refused_without_a_device(ROW, capi)
+    assert capi.load().cavmd_molecular_order(None, None) == 0
 
 
-# ---- 4. the pair maker --------------------------------------------------------------------------------------------------
+# ---- 3. the pair maker --------------------------------------------------------------------------------------------------
 def test_pair_make_equals_the_mirror_bit_for_bit(capi):
     rng = np.random.default_rng(23)
     cases = [(0.00016685201, 6.230426584, 15.0), (0.000083426, 5.48277488, 15.0), (0.00025027802, 4.9832074319, 15.0),
@@ -222,26 +165,17 @@ def test_pair_make_equals_the_mirror_bit_for_bit(capi):
     assert tab["rcutsq"][2, 0] == 0.0 and tab["K"][1] == 1.4                  # unlisted pairs stay switched off
 
 
-# ---- 5. the Python surface ----------------------------------------------------------------------------------------------
+# ---- 4. the Python surface, and the lattice its CPU systems are made of ------------------------------------------------------
 def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
+    checks.python_class_is_exported_and_refuses_cpu_tensors(ROW, capi)
     import cavitymd
     from cavitymd import synthetic
-    assert "MolecularForceBatch" in cavitymd.__all__
-    assert cavitymd.MolecularForceBatch is cavitymd.molecular_batch.MolecularForceBatch
-    for name in ("compute", "potential_energy", "close"):
-        assert callable(getattr(cavitymd.MolecularForceBatch, name)), name
-    assert isinstance(cavitymd.MolecularForceBatch.forces, property)
-    for name in ("compute", "set_items", "close"):
-        assert callable(getattr(capi.Molecular, name)), name
     cfg = synthetic.diatomic_lattice(2, 8.0, seed=3)
     bonds, bond_typeid = synthetic.diatomic_bonds(cfg)
     assert len(cfg["charge"]) == 17 and bonds.tolist() == [[2 * m, 2 * m + 1] for m in range(8)]
     assert bond_typeid.tolist() == cfg["typeid"][0:16:2].tolist() and set(bond_typeid.tolist()) == {0, 1}
     pd = cavitymd.ParticleData.from_arrays(cfg["position"], cfg["typeid"], cfg["charge"], cfg["image"], cfg["types"], cfg["box"],
                                            device="cpu")
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.MolecularForceBatch([cavitymd.SystemDefinition(pd)], [bonds], [bond_typeid], harmonic={0: dict(k=1.0, r0=2.0)},
-                                     lj={("O", "O"): dict(epsilon=1e-4, sigma=6.0, r_cut=8.0)})
     assert isinstance(pd.getPositions(), torch.Tensor)
 
 
@@ -261,7 +195,7 @@ def test_lattice_has_no_overlaps_and_its_molecules_are_at_their_bond_lengths():
     assert r.min() >= 8.0 - synthetic.BOND_OO
 
 
-# ---- 6. the mirror's own known answers -----------------------------------------------------------------------------------
+# ---- 5. the mirror's own known answers -----------------------------------------------------------------------------------
 def _lj_only(capi, epsilon, sigma, r_cut):
     return mirror.tables(capi.molecular_params(1, {}, {(0, 0): (epsilon, sigma, r_cut)}))
 

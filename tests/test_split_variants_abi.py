@@ -1,20 +1,17 @@
 """The lane-split builds of the library (csrc/Makefile's `split_variants`, cavitymd._capi.load_split_variant) on a machine
 WITHOUT a GPU: with the product library they answer cavmd_molecular_order and cavmd_coulomb_order with the table below, the
 union of their answers is exactly what include/cavmd.h allows, they export what the product exports, and the splits do not
-leak into the host arithmetic.  tests/test_gpu_split_variants.py runs their kernels; the shapes it uses are checked here."""
+leak into the host arithmetic.  tests/test_gpu_split_variants.py runs their kernels; the shapes it uses (tests/split_builds.py) are checked here."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
 import coulomb_mirror as mirror
-from test_coulomb_abi import _good
-from test_gpu_split_variants import BUILDS, k_counts_for, k_values_for, replay_k_counts, sizes_for
-
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
+from abi_support import HEADER, exported
+from abi_support import good_coulomb as _good
+from split_builds import BUILDS, k_counts_for, k_values_for, replay_k_counts, sizes_for
 
 
 @pytest.fixture(scope="module")
@@ -55,14 +52,13 @@ def test_the_builds_cover_exactly_what_the_header_allows(capi, libs):
 
 
 def test_the_variants_export_what_the_product_exports(capi):
-    exported = {}
+    symbols = {}
     for name, path in _paths(capi).items():
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported[name] = {line.split()[-1] for line in out.splitlines() if " T " in line and line.split()[-1].startswith("cavmd_")}
+        symbols[name] = {s for s in exported(path) if s.startswith("cavmd_")}
         assert b"gfx950" in open(path, "rb").read(), name
-    assert exported["product"] == set(capi.EXPORTED_SYMBOLS)
+    assert symbols["product"] == set(capi.EXPORTED_SYMBOLS)
     for name in ("a", "b", "c"):
-        assert exported[name] == exported["product"], name
+        assert symbols[name] == symbols["product"], name
 
 
 def _k_count(lib, item):

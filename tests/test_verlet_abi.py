@@ -1,85 +1,26 @@
-"""The integrator batch (cavmd_verlet_*) on a machine WITHOUT a GPU: the header declares and both libraries export the eleven
-entry points and nothing stray, the version is still 2, the item, input and state layouts agree between C and ctypes, the
-per-item validation and the input-row maker work without a device, and the Python class refuses CPU tensors."""
+"""What is specific to the integrator batch (cavmd_verlet_*) on a machine WITHOUT a GPU: where the header says its expressions
+come from, the per-item validation and the input-row maker (host arithmetic).  Header, exports, layouts, null arguments,
+launch order, Python surface and deferred destroy are the shared checks of tests/batch_objects.py, called here with this
+object's row."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
-import pytest
-import torch
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-HEADER = os.path.join(ROOT, "include", "cavmd.h")
-VERLET = ("cavmd_verlet_item_check", "cavmd_verlet_input_make", "cavmd_verlet_create", "cavmd_verlet_destroy",
-          "cavmd_verlet_set_items", "cavmd_verlet_accelerations", "cavmd_verlet_step_one", "cavmd_verlet_step_two",
-          "cavmd_verlet_read", "cavmd_verlet_reset", "cavmd_verlet_state_device_ptr")
+import batch_objects as checks
+from abi_support import HEADER
+from abi_support import bits as _bits
+from abi_support import good_verlet as _good
 
-
-def _bits(x) -> int:
-    return int(np.float64(x).view(np.uint64))
+ROW = checks.ROWS["verlet"]
 
 
-# ---- 1. header, libraries, binary -------------------------------------------------------------------------------------
+# ---- 1. the header ------------------------------------------------------------------------------------------------------
 def test_header_declares_the_eleven_entry_points_and_keeps_the_version():
-    raw = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"CAVMD_API\s+[\w\s\*]+?\b(cavmd_verlet_\w+)\s*\(", text)))
-    assert len(VERLET) == 11 and declared == sorted(VERLET)
-    assert re.search(r"#define\s+CAVMD_VERSION_MINOR\s+2\b", text)
-    assert "typedef struct cavmd_verlet cavmd_verlet;" in text
-    assert "[HOOMD upstream, not in checkout]" in raw        # where the expressions come from is said where a C caller reads
+    checks.header_declares_exactly_the_entry_points(ROW)
+    assert "[HOOMD upstream, not in checkout]" in open(HEADER).read()      # where a C caller reads it
 
 
-def test_libraries_export_them_and_nothing_stray(capi):
-    for path in (capi.LIB_PATH, capi.HOOKS_LIB_PATH):
-        lib = ctypes.CDLL(path)
-        for name in VERLET:
-            assert hasattr(lib, name), (path, name)
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert {s for s in exported if s.startswith("cavmd_verlet")} == set(VERLET), path
-        assert not {s for s in exported if not s.startswith("cavmd_") and not s.startswith("_")}, path
-    for name in VERLET:
-        assert name in capi.EXPORTED_SYMBOLS
-    assert capi.load().cavmd_version() == 2
-    blob = open(capi.LIB_PATH, "rb").read()
-    assert b"verlet_step_one_kernel" in blob and b"verlet_step_two_kernel" in blob and b"gfx950" in blob
-
-
-# ---- 2. layouts ---------------------------------------------------------------------------------------------------------
-def test_c_layouts_equal_the_ctypes_ones(capi, tmp_path):
-    """tests/c_abi/verlet_abi_check.c, built as C99 with -pedantic -Werror, prints sizeof and offsetof of every field as the C
-    compiler sees them; they equal the ctypes structures field by field.  It also runs the refusals seen from C."""
-    src = os.path.join(ROOT, "tests", "c_abi", "verlet_abi_check.c")
-    exe = str(tmp_path / "verlet_abi_check")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), src,
-                         "-o", exe, "-L", libdir, "-lcavmd", "-lm", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "VERLET-ABI-OK" in out.stdout, (out.returncode, out.stdout, out.stderr[-2000:])
-    structs = {"item": capi.VerletItem, "input": capi.VerletInput, "state": capi.VerletState}
-    sizes = re.search(r"sizeof item (\d+) input (\d+) state (\d+)", out.stdout)
-    assert tuple(int(x) for x in sizes.groups()) == (128, 64, 32)
-    assert tuple(ctypes.sizeof(structs[k]) for k in ("item", "input", "state")) == (128, 64, 32)
-    seen = {k: {} for k in structs}
-    for which, field, off in re.findall(r"^(item|input|state)\.(\w+) (\d+)$", out.stdout, flags=re.M):
-        seen[which][field] = int(off)
-    for which, S in structs.items():
-        assert seen[which] == {name: getattr(S, name).offset for name, *_ in S._fields_}, which
-    assert seen["item"]["d_force"] == 32 and seen["item"]["N"] == 96 and seen["input"]["skip"] == 48
-    assert capi.verlet_state_dtype().itemsize == 32
-    assert [capi.verlet_state_dtype().fields[n][1] for n, _ in capi.VERLET_STATE_DTYPE_FIELDS] == \
-        [seen["state"][n] for n, _ in capi.VERLET_STATE_DTYPE_FIELDS]
-
-
-# ---- 3. refusals ----------------------------------------------------------------------------------------------------------
-def _good(capi, n=501, forces=(0x50000,), net=0, langevin=-1):
-    return capi.verlet_item(n, 0x10000, 0x20004, 0x30000, 0x40008, forces, net, (10.0, 11.0, 12.0), langevin)
-
-
+# ---- 2. refusals ----------------------------------------------------------------------------------------------------------
 def test_item_check_refusals(capi):
     lib = capi.load()
     INV, CAP = capi.CAVMD_ERR_INVALID_VALUE, capi.CAVMD_ERR_CAPACITY
@@ -130,25 +71,7 @@ def test_item_check_refusals(capi):
         assert chk(it) == INV, k
 
 
-def test_null_handles_are_refused_without_a_device(capi):
-    lib = capi.load()
-    INV = capi.CAVMD_ERR_INVALID_VALUE
-    it = _good(capi)
-    out = ctypes.c_void_p(123)
-    st = capi.VerletState()
-    assert lib.cavmd_verlet_create(None, 1, ctypes.byref(it), ctypes.byref(out)) == INV and not out.value
-    assert lib.cavmd_verlet_create(None, 1, ctypes.byref(it), None) == INV
-    assert lib.cavmd_verlet_destroy(None) == 0
-    assert lib.cavmd_verlet_set_items(None, 0, 1, ctypes.byref(it)) == INV
-    assert lib.cavmd_verlet_accelerations(None, None) == INV
-    assert lib.cavmd_verlet_step_one(None, None, ctypes.c_void_p(0x1000)) == INV
-    assert lib.cavmd_verlet_step_two(None, None, ctypes.c_void_p(0x1000)) == INV
-    assert lib.cavmd_verlet_read(None, None, ctypes.byref(st)) == INV
-    assert lib.cavmd_verlet_reset(None, None) == INV
-    assert lib.cavmd_verlet_state_device_ptr(None, ctypes.byref(out)) == INV
-
-
-# ---- 4. the input row ---------------------------------------------------------------------------------------------------
+# ---- 3. the input row ---------------------------------------------------------------------------------------------------
 def test_input_make_takes_the_coefficient_on_the_host(capi):
     rng = np.random.default_rng(17)
     cases = [(5.0, 0.01, 3.167e-4), (0.005, 1.0, 1.0), (1e-300, 1e-3, 1e-3), (41.341, 2.5e-5, 9.5e-4), (1.0, 1e300, 1e-300)]
@@ -169,24 +92,18 @@ def test_input_make_takes_the_coefficient_on_the_host(capi):
     assert lib.cavmd_verlet_input_make(1.0, 0.0, 0.0, None, ctypes.byref(capi.VerletInput())) == capi.CAVMD_ERR_INVALID_VALUE
 
 
-# ---- 5. the Python surface ----------------------------------------------------------------------------------------------
+# ---- the checks every batch object gets (tests/batch_objects.py), on this object's row ---------------------------------------
+def test_libraries_export_them_and_nothing_stray(capi):
+    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
+
+
+def test_c_layouts_equal_the_ctypes_ones(capi, tmp_path):
+    checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
+
+
+def test_null_handles_are_refused_without_a_device(capi):
+    checks.null_arguments_are_refused_without_a_device(ROW, capi)
+
+
 def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
-    import cavitymd
-    assert "VerletBatch" in cavitymd.__all__ and cavitymd.VerletBatch is cavitymd.integrator_batch.VerletBatch
-    for name in ("set_inputs", "draw_inputs", "prime", "step_one", "step_two", "state", "reset", "close"):
-        assert callable(getattr(cavitymd.VerletBatch, name)), name
-    for name in ("accelerations", "step_one", "step_two", "read", "reset", "set_items", "state_device_ptr", "close"):
-        assert callable(getattr(capi.Verlet, name)), name
-    b = object.__new__(capi.Verlet)
-    b.sizes = [501, 0, 2049, 501]
-    assert b.launch_order == [2, 0, 3, 1]
-
-    class NoBatch:                                     # never looked at: the CPU tensor is refused first
-        def __len__(self):
-            return 1
-
-    vel = torch.zeros((10, 4), dtype=torch.float64)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.VerletBatch(NoBatch(), [vel])
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        cavitymd.VerletBatch(NoBatch(), [np.zeros((10, 4))])
+    checks.python_class_is_exported_and_refuses_cpu_tensors(ROW, capi)
