@@ -388,18 +388,13 @@ _lock = threading.Lock()
 
 def build(force: bool = False) -> str:
     """Compile libcavmd.so for gfx950 with hipcc (cross-compiles without a GPU).  Idempotent."""
-    srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith((".hip", ".hpp")) and not f.startswith("microbench")]
-    srcs.append(os.path.normpath(os.path.join(CSRC_DIR, "..", "..", "include", "cavmd.h")))
-    stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
-    if force or stale:
-        subprocess.run(["make", "-C", CSRC_DIR, "-s", "libcavmd.so"] + (["-B"] if force else []), check=True)
-    # the same library with the test hooks compiled in (fault injection; loaded by tests only, see load_hooks_build)
-    subprocess.run(["make", "-C", CSRC_DIR, "-s", "libcavmd_hooks.so"], check=True)
-    # the product library with the lane splits the default build does not cover (loaded by tests only, see load_split_variant);
-    # make rebuilds each only when stale
-    subprocess.run(["make", "-C", CSRC_DIR, "-s", "-j3", "split_variants"], check=True)
-    # the pybind11 flavour of the shim (cavitymd._cavitymd); make rebuilds it only when stale
-    subprocess.run(["make", "-C", CSRC_DIR, "-s", "pymod"], check=True)
+    # One make call; make knows from the dependency files written next to the objects what is stale and rebuilds that alone:
+    # the product; the same library with the test hooks compiled in (fault injection; loaded by tests only, see
+    # load_hooks_build); the product with the lane splits the default build does not cover (loaded by tests only, see
+    # load_split_variant); the pybind11 flavour of the shim (cavitymd._cavitymd).
+    targets = ["libcavmd.so", "libcavmd_hooks.so", "split_variants", "pymod"]
+    jobs = min(16, os.cpu_count() or 1)
+    subprocess.run(["make", "-C", CSRC_DIR, "-s", f"-j{jobs}"] + (["-B"] if force else []) + targets, check=True)
     return LIB_PATH
 
 

@@ -1,0 +1,340 @@
+// cavmd_coulomb.hip -- cavmd_coulomb of include/cavmd.h: Ewald Coulomb forces of a batch of small systems in two launches.
+// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "cavmd.h"
+#include "cavmd_coulomb_batch_kernel.hpp"
+#include "cavmd_item_table.hpp"
+
+using namespace cavmd;
+
+// ---- Ewald Coulomb forces of a batch of independent small systems in TWO launches (cavmd_coulomb_batch_kernel.hpp) ------------
+// A LinkedTable as well: the status of an item with its k-vectors, and how the device tables follow from the items.
+namespace
+{
+constexpr int kCoulombJSplit = CAVMD_COULOMB_J_SPLIT;
+constexpr int kCoulombKSplit = CAVMD_COULOMB_K_SPLIT;
+constexpr unsigned kCoulombRows = kCoulombBlock / kCoulombJSplit;
+constexpr unsigned kCoulombKRows = kCoulombBlock / kCoulombKSplit;
+static_assert(kCoulombJSplit == 1 || kCoulombJSplit == 4 || kCoulombJSplit == 16 || kCoulombJSplit == 64, "S is one of the candidates");
+static_assert(kCoulombKSplit == 1 || kCoulombKSplit == 4 || kCoulombKSplit == 16 || kCoulombKSplit == 64, "T is one of the candidates");
+static_assert(sizeof(cavmd_coulomb_item) == 96, "coulomb item layout");
+static_assert(CAVMD_COULOMB_MAX_EXCLUSIONS == kCoulombMaxExclusions, "the header's limit is the kernel's");
+static_assert(coulomb_lds_bytes(CAVMD_COULOMB_MAX_ITEM_N) <= 64 * 1024, "the largest system fits the LDS a kernel gets without opt-in");
+constexpr double kCoulombPi = 3.141592653589793;
+constexpr double kCoulombSqrtPi = 1.7724538509055159;
+
+// The kept k-vectors of an item (whose box and cut-offs have been checked), in the contract's order; stops at `limit` + 1.
+// Every loop visits kept vectors and one more per row, so the work is bounded by the limit whatever k_cut is.
+void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<CoulombK>* out, size_t* count)
+{
+    const double two_pi = 2.0 * kCoulombPi;
+    const double kc2 = it.k_cut * it.k_cut;
+    const double V = (it.Lx * it.Ly) * it.Lz;
+    const double four_kappa2 = 4.0 * (it.kappa * it.kappa);
+    size_t K = 0;
+    auto component = [&](long m, double L) { return (two_pi * (double)m) / L; };
+    for (long mx = 0;; ++mx)
+    {
+        const double kx = component(mx, it.Lx);
+        const double kxx = kx * kx;
+        if (!(kxx <= kc2))
+            break;
+        if (mx > (long)limit + 1)
+        {
+            *count = limit + 1;
+            return;
+        }
+        // every (mx, my) in range keeps at least one vector, and so does every mz in range: a search that runs past the limit
+        // has already decided the answer
+        long My = 0;
+        while (true)
+        {
+            const double ky = component(My + 1, it.Ly);
+            if (!(kxx + ky * ky <= kc2))
+                break;
+            if (++My > (long)limit + 1)
+            {
+                *count = limit + 1;
+                return;
+            }
+        }
+        for (long my = -My; my <= My; ++my)
+        {
+            if (mx == 0 && my < 0)
+                continue;
+            const double ky = component(my, it.Ly);
+            const double kxy = kxx + ky * ky;
+            long Mz = 0;
+            while (true)
+            {
+                const double kz = component(Mz + 1, it.Lz);
+                if (!(kxy + kz * kz <= kc2))
+                    break;
+                if (++Mz > (long)limit + 1)
+                {
+                    *count = limit + 1;
+                    return;
+                }
+            }
+            for (long mz = -Mz; mz <= Mz; ++mz)
+            {
+                if (mx == 0 && my == 0 && mz <= 0)
+                    continue;
+                const double kz = component(mz, it.Lz);
+                const double k2 = kxy + kz * kz;
+                if (!(k2 > 0.0 && k2 <= kc2))
+                    continue;
+                if (++K > limit)
+                {
+                    *count = K;
+                    return;
+                }
+                if (out)
+                    out->push_back(CoulombK {kx, ky, kz, ((4.0 * kCoulombPi) / V) * exp(-k2 / four_kappa2) / k2});
+            }
+        }
+    }
+    *count = K;
+}
+
+// the tables derived from one item: its partner slots (four a particle, from the exclusion list) and its k-vectors
+struct CoulombDerived
+{
+    std::vector<uint32_t> slots;
+    std::vector<CoulombK> ktab;
+};
+
+// The status of one item.  `out`, if given, receives the item's derived tables, `out_K` the number of its k-vectors.
+int coulomb_item_status(const cavmd_coulomb_item* it, CoulombDerived* out, size_t* out_K)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_force & 15) || ((uintptr_t)it->d_charge & 7) || ((uintptr_t)it->h_exclusions & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N != 0 && (!it->d_pos || !it->d_force || !it->d_charge))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->n_exclusions != 0 && !it->h_exclusions)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_COULOMB_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    if (it->N != 0)
+    {
+        double cut_sq = 0.0;
+        if (!box_ok(it->Lx, it->Ly, it->Lz, &cut_sq))
+            return CAVMD_ERR_INVALID_VALUE;
+        if (!(isfinite(it->kappa) && it->kappa > 0.0) || !finite_nonnegative(it->r_cut) || !finite_nonnegative(it->k_cut))
+            return CAVMD_ERR_INVALID_VALUE;
+        if (it->r_cut * it->r_cut > cut_sq)
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    const int st = partner_slots(it->N, it->h_exclusions, it->n_exclusions, kCoulombMaxExclusions, kCoulombNoPartner,
+                                 [](uint32_t partner, uint32_t) { return partner; }, out ? &out->slots : nullptr);
+    if (st != CAVMD_OK)
+        return st;
+    size_t K = 0;
+    if (out)
+        out->ktab.clear();
+    if (it->N != 0)
+    {
+        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, out ? &out->ktab : nullptr, &K);
+        if (K > CAVMD_COULOMB_MAX_K)
+            return CAVMD_ERR_CAPACITY;
+    }
+    if (out_K)
+        *out_K = K;
+    return CAVMD_OK;
+}
+
+CoulombRow coulomb_row(const cavmd_coulomb_item& it)
+{
+    CoulombRow r;
+    memset(&r, 0, sizeof(r));
+    r.pos2 = reinterpret_cast<const v2d*>(it.d_pos);
+    r.charge = it.d_charge;
+    r.force2 = reinterpret_cast<v2d*>(it.d_force);
+    r.Lx = it.Lx;
+    r.Ly = it.Ly;
+    r.Lz = it.Lz;
+    r.kappa = it.kappa;
+    r.rcutsq = it.r_cut * it.r_cut;
+    r.n = it.N;
+    if (it.N != 0)
+    {
+        size_t K = 0;
+        coulomb_k_vectors(it, CAVMD_COULOMB_MAX_K, nullptr, &K); // the item has been checked: K <= CAVMD_COULOMB_MAX_K
+        r.n_k = (unsigned)K;
+        r.self_c = it.kappa / kCoulombSqrtPi;
+        r.bg_c = kCoulombPi / ((2.0 * ((it.Lx * it.Ly) * it.Lz)) * (it.kappa * it.kappa));
+    }
+    return r;
+}
+
+// what set_items replaces together
+struct CoulombTables
+{
+    DeviceArray<uint4> k_blocks, blocks, partners;
+    DeviceArray<CoulombK> ktab;
+    DeviceArray<v2d> structure;
+    std::vector<uint32_t> offsets; // per item: its first entry of ktab / structure
+    CoulombHeader header;
+    unsigned lds_n = 2;
+};
+} // namespace
+
+// workgroups by N descending
+struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, CoulombDerived, CoulombTables>
+{
+    cavmd_coulomb() : LinkedTable([](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row) {}
+
+    int item_status(const cavmd_coulomb_item* it, CoulombDerived* out) const override
+    {
+        return coulomb_item_status(it, out, nullptr);
+    }
+
+    void strip(cavmd_coulomb_item* it) const override
+    {
+        it->h_exclusions = nullptr;
+        it->n_exclusions = 0;
+    }
+
+    hipError_t fill(const std::vector<cavmd_coulomb_item>& all, const std::vector<unsigned>& launch,
+                    const std::vector<CoulombDerived>& d, CoulombTables* t) const override
+    {
+        const size_t B = all.size();
+        std::vector<uint32_t> partner_base(B), pool;
+        std::vector<CoulombK> kpool;
+        t->offsets.assign(B, 0);
+        unsigned largest = 0;
+        for (size_t i = 0; i < B; ++i)
+        {
+            partner_base[i] = pool_append(&pool, d[i].slots) / kCoulombMaxExclusions;
+            t->offsets[i] = pool_append(&kpool, d[i].ktab);
+            kpool.push_back(CoulombK {0.0, 0.0, 0.0, 0.0}); // the slot of {Q, 0}
+            largest = std::max(largest, all[i].N);
+        }
+        std::vector<uint4> k_table, table;
+        for (unsigned item : launch)
+        {
+            if (all[item].N == 0)
+                continue;
+            emit_blocks(&k_table, item, (unsigned)d[item].ktab.size(), kCoulombKRows, t->offsets[item], 0u);
+            emit_blocks(&table, item, all[item].N, kCoulombRows, partner_base[item], t->offsets[item]);
+        }
+        hipError_t e = t->k_blocks.upload(k_table.data(), k_table.size());
+        if (e == hipSuccess)
+            e = t->blocks.upload(table.data(), table.size());
+        if (e == hipSuccess)
+            e = t->ktab.upload(kpool.data(), kpool.size());
+        if (e == hipSuccess)
+            e = t->structure.alloc_zeroed(kpool.size());
+        if (e == hipSuccess)
+            e = t->partners.upload(pool.data(), pool.size());
+        memset(&t->header, 0, sizeof(t->header));
+        t->header.k_blocks = t->k_blocks.ptr;
+        t->header.blocks = t->blocks.ptr;
+        t->header.partners = t->partners.ptr;
+        t->header.ktab = t->ktab.ptr;
+        t->header.structure = t->structure.ptr;
+        t->header.n_k_blocks = (unsigned)k_table.size();
+        t->header.n_blocks = (unsigned)table.size();
+        t->lds_n = lds_particles(largest);
+        return e;
+    }
+};
+
+extern "C"
+{
+
+int cavmd_coulomb_item_check(const cavmd_coulomb_item* it)
+{
+    return coulomb_item_status(it, nullptr, nullptr);
+}
+
+int cavmd_coulomb_k_count(const cavmd_coulomb_item* it, uint32_t* out_K)
+{
+    if (!out_K)
+        return CAVMD_ERR_INVALID_VALUE;
+    size_t K = 0;
+    const int st = coulomb_item_status(it, nullptr, &K);
+    if (st != CAVMD_OK)
+        return st;
+    *out_K = (uint32_t)K;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_parameters(double r_cut, double accuracy, double* kappa, double* k_cut)
+{
+    if (!kappa || !k_cut || !(isfinite(r_cut) && r_cut > 0.0) || !(accuracy > 0.0 && accuracy < 1.0))
+        return CAVMD_ERR_INVALID_VALUE;
+    const double s = sqrt(-log(accuracy));
+    *kappa = s / r_cut;
+    *k_cut = (2.0 * *kappa) * s;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_order(int* rows, int* j_split, int* k_rows, int* k_split)
+{
+    if (rows)
+        *rows = (int)kCoulombRows;
+    if (j_split)
+        *j_split = kCoulombJSplit;
+    if (k_rows)
+        *k_rows = (int)kCoulombKRows;
+    if (k_split)
+        *k_split = kCoulombKSplit;
+    return CAVMD_OK;
+}
+
+int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulomb_item* h_items, cavmd_coulomb** out)
+{
+    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_coulomb*) {});
+}
+
+int cavmd_coulomb_destroy(cavmd_coulomb* c)
+{
+    return destroy_table(c);
+}
+
+int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items)
+{
+    return c ? c->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
+{
+    if (!c)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const CoulombTables& t = c->tables;
+    const size_t lds = coulomb_lds_bytes(t.lds_n);
+    // two launches, each noted once it is in flight: a refused second one leaves the first to be waited for
+    const int st = c->launch(stream, coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>, dim3(std::max(t.header.n_k_blocks, 1u)),
+                             dim3(kCoulombBlock), lds, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
+    if (st != CAVMD_OK)
+        return st;
+    return c->launch(stream, coulomb_force_kernel<kCoulombBlock, kCoulombJSplit>, dim3(std::max(t.header.n_blocks, 1u)),
+                     dim3(kCoulombBlock), lds, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
+}
+
+int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets)
+{
+    if (!c || (!out && !h_offsets))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (out)
+        *out = reinterpret_cast<const double*>(c->tables.structure.ptr);
+    if (h_offsets)
+        *h_offsets = c->tables.offsets.data();
+    return CAVMD_OK;
+}
+
+} // extern "C"

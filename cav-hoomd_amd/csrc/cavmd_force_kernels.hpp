@@ -2,6 +2,8 @@
 // scalars (reduce_partials_and_finalize), finalize_kernel and the force-map kernels.  Overview: cavmd_kernels.hpp.
 #pragma once
 
+#include <math.h>
+
 #include "cavmd_reduce.hpp"
 
 #pragma clang fp contract(off)
@@ -101,6 +103,22 @@ struct DeviceParams
     double gK;   // g / K            (src/CavityForceCompute.cc:183)
     double g2K;  // g * g / K        (src/CavityForceCompute.cc:176)
 };
+
+// (host) the quotients of a checked cavmd_params, and the check
+inline DeviceParams derive(const cavmd_params* p)
+{
+    DeviceParams d;
+    d.g = p->couplstr;
+    d.K = p->K;
+    d.gK = p->couplstr / p->K;                   // as `m_params.couplstr / m_params.K`, src/CavityForceCompute.cc:183
+    d.g2K = p->couplstr * p->couplstr / p->K;    // as `couplstr * couplstr / K`, :176 (host code is built -ffp-contract=off)
+    return d;
+}
+
+inline bool params_ok(const cavmd_params* p)
+{
+    return p && isfinite(p->omegac) && isfinite(p->couplstr) && isfinite(p->K) && isfinite(p->phmass) && p->K != 0.0;
+}
 
 // The speculatively fetched last particle (the driver appends the photon last), as plain scalars: handing the
 // layout's whole Raw aggregate through the prologue made hipcc keep it in a stack object (52 B of scratch stores per
@@ -692,6 +710,7 @@ constexpr int kSmallSystemLdsCharges = 4096; // charges the single-block kernel 
 // The reference's production system is N = 501 (examples/init-0.gsd, 500 SLURM replicas of it).  At that size two
 // launches are pure latency (~4 us each); a single block that reduces, finalises and maps in one go halves it.  Used
 // below kSmallSystemMaxN particles, where one CU's bandwidth is not yet the limit.
+constexpr int kSmallBlock = 256; // the block size both the workspace and the batch launch this body with: the two paths share bits
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void cavity_small_system_kernel(AosInput in, unsigned N, double Lx, double Ly, double Lz,
                                                                     DeviceParams prm, int L_typeid, uint64_t sequence,

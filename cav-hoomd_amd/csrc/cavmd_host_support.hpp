@@ -1,6 +1,6 @@
-// Host-only: what every object of cavmd_capi.hip builds on -- the capture query, the ONE wait for a stamp in mapped host
-// memory, the owners of mapped / pinned host blocks and of device arrays, and the step from a runtime value to a template
-// argument.  Nothing here launches a kernel or knows a workspace.
+// Host-only: what every unit of the library builds on -- the device guard and the step from a HIP error to a status, the
+// capture query, the ONE wait for a stamp in mapped host memory, the owners of mapped / pinned host blocks and of device
+// arrays, and the step from a runtime value to a template argument.  Nothing here launches a kernel or knows a workspace.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,8 +10,44 @@
 #include <type_traits>
 #include <utility>
 
+#include "cavmd.h"
+
 namespace
 {
+constexpr unsigned kResultHistoryMax = 16384; // deepest result ring: of a workspace ("result_history") and of a batch
+
+// ---- the device of an object, and HIP errors as statuses --------------------------------------------------------------------
+struct DeviceGuard
+{
+    int prev = -1;
+    bool switched = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev)
+        {
+            switched = (hipSetDevice(dev) == hipSuccess);
+        }
+    }
+    ~DeviceGuard()
+    {
+        if (switched)
+            (void)hipSetDevice(prev);
+    }
+};
+
+inline int hip_status(hipError_t e)
+{
+    return e == hipSuccess ? CAVMD_OK : (int)e;
+}
+
+#define CAVMD_HIP_TRY(expr)              \
+    do                                   \
+    {                                    \
+        hipError_t _e = (expr);          \
+        if (_e != hipSuccess)            \
+            return (int)_e;              \
+    } while (0)
+
 // ---- is `stream` being captured? --------------------------------------------------------------------------------------------
 // The null stream cannot be captured and costs no query (HOOMD-blue's and torch's default path).  `unknown` is a query that
 // failed: callers that must not enqueue into a capture treat it as one, callers that only skip a wait treat it as none.
@@ -72,12 +108,15 @@ inline StampWait wait_for_stamp(const uint64_t* stamp, uint64_t want, hipStream_
 {
     return wait_for_stamp(stamp, want, stream, [] { return false; });
 }
+} // namespace
 
 // ---- owners -----------------------------------------------------------------------------------------------------------------
 // Move-only; an owner is either empty or holds one live allocation, and a failed alloc leaves it empty.  Freed by free() or
 // with the owner; whoever destroys an owner holds the DeviceGuard of its device.  A group of buffers that belongs together
 // is allocated into local owners and moved into place once all of them are there: commit whole or not at all.
-
+// In the library's named namespace, not the anonymous one: struct cavmd_workspace, which two units define, has such members.
+namespace cavmd
+{
 // `count` zeroed Ts of pinned host memory; kMapped: mapped into the device's address space and coherent (the polled stamps
 // must not depend on HIP_HOST_COHERENT), `dev` being the device-side address of `host`
 template <class T, bool kMapped>
@@ -194,7 +233,10 @@ struct DeviceArray
         ptr = nullptr;
     }
 };
+} // namespace cavmd
 
+namespace
+{
 // ---- from a runtime value to a template argument ----------------------------------------------------------------------------
 // A kernel's variants are named by lists of the values a template parameter takes.  with_constant() calls f with the entry
 // equal to v as a std::integral_constant (with the LAST entry if none is: every caller's v comes from a checked tunable or
@@ -214,8 +256,7 @@ auto with_constant(IntList<V, Rest...>, int v, F&& f)
         return v == V ? f(std::integral_constant<int, V> {}) : with_constant(IntList<Rest...> {}, v, std::forward<F>(f));
 }
 
-// (Last entry first, and `auto` so that the body is instantiated where it is called: together they keep the kernels of
-// cavmd_capi.hip in the order in which they have always been emitted, so `make asm` stays diffable across commits.)
+// (last entry first)
 template <int V, int... Rest, class F>
 auto with_each_constant(IntList<V, Rest...>, F&& f)
 {

@@ -1,9 +1,10 @@
-// Host-only: what the seven "batch of small systems" objects of cavmd_capi.hip share -- how a table of items lives on the host
-// and on the device, how the object is created (create_table), launched (ItemTable::launch), tied to its workspace and released
-// (destroy_table); for the two recorders, the per-item ring of records behind it (SeriesTable); for the two force batches, the
-// tables derived from the items that their kernels find through a header at a fixed device address and that set_items
-// replaces together (LinkedTable).
-// cavmd_capi.hip includes this once, after cavmd_workspace, DeviceGuard, hip_status and CAVMD_HIP_TRY, which the code below uses.
+// Host-only: what the seven "batch of small systems" objects share, each in a unit of its own (cavmd_batch.hip,
+// cavmd_bussi_batch.hip, cavmd_recorder.hip, cavmd_field_recorder.hip, cavmd_verlet.hip, cavmd_molecular.hip,
+// cavmd_coulomb.hip) -- how a table of items lives on the host and on the device, how the object is created (create_table),
+// launched (ItemTable::launch), tied to its workspace and released (destroy_table); for the two recorders, the per-item ring
+// of records behind it (SeriesTable); for the two force batches, the tables derived from the items that their kernels find
+// through a header at a fixed device address and that set_items replaces together (LinkedTable).
+// Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,12 +17,24 @@
 #include <vector>
 
 #include "cavmd.h"
-#include "cavmd_host_support.hpp" // stream_capturing, DeviceArray
+#include "cavmd_host_support.hpp" // DeviceGuard, hip_status, CAVMD_HIP_TRY, stream_capturing, DeviceArray
+
+// What an object built on an item table needs of the workspace it was created from: the device, and the count of live
+// objects that cavmd_destroy refuses on.  cavmd_workspace_tie (cavmd_capi.hip) hands out the workspace's; it is called when
+// an object is created and never on a launch path.
+struct WorkspaceTie
+{
+    int device = -1;
+    unsigned dependents = 0; // live objects created from this workspace (ItemTable::attach)
+};
+__attribute__((visibility("hidden"))) WorkspaceTie* cavmd_workspace_tie(cavmd_workspace* ws);
 
 namespace
 {
+constexpr size_t kRecorderMaxBytes = (size_t)1 << 30; // of one recorder's series (and, for a field recorder, its fields)
+
 // waits for what was enqueued on `stream`; a capturing stream cannot be waited for
-int sync_uncaptured(hipStream_t stream)
+inline int sync_uncaptured(hipStream_t stream)
 {
     if (stream_capturing(stream))
         return CAVMD_ERR_INVALID_VALUE;
@@ -75,11 +88,11 @@ struct ItemTable
     Row (*const to_row)(const Item&);
     int device = -1;
     size_t n = 0;
-    cavmd_workspace* ws = nullptr; // the workspace this object was attached to: cavmd_destroy refuses while it lives
+    WorkspaceTie* tie = nullptr;   // of the workspace this object was attached to: cavmd_destroy refuses while it lives
     std::vector<Item> items;       // host copy of the table, as the caller gave it
     std::vector<unsigned> order;   // items by key descending, stable
-    DeviceArray<Row> d_rows;
-    DeviceArray<unsigned> d_order;
+    cavmd::DeviceArray<Row> d_rows;
+    cavmd::DeviceArray<unsigned> d_order;
     hipStream_t last_stream = nullptr;
     bool enqueued = false; // some launch was enqueued: last_stream means something
 
@@ -122,17 +135,17 @@ struct ItemTable
     }
 
     // a complete object is tied to the workspace it was created from
-    void attach(cavmd_workspace* w)
+    void attach(WorkspaceTie* w)
     {
-        ws = w;
-        ws->dependents += 1;
+        tie = w;
+        tie->dependents += 1;
     }
 
     void detach()
     {
-        if (ws)
-            ws->dependents -= 1;
-        ws = nullptr;
+        if (tie)
+            tie->dependents -= 1;
+        tie = nullptr;
     }
 
     // THE launch of the objects built on an item table: under the guard of the table's device, with the launch error as the
@@ -257,17 +270,18 @@ int create_table(cavmd_workspace* ws, size_t n_items, const Item* h_items, Table
         return CAVMD_ERR_INVALID_VALUE;
     if (args != CAVMD_OK)
         return args;
+    WorkspaceTie* const tie = cavmd_workspace_tie(ws);
     Table* t = new (std::nothrow) Table();
     if (!t)
         return (int)hipErrorOutOfMemory;
-    t->device = ws->device; // whoever destroys the object holds the guard of this device
+    t->device = tie->device; // whoever destroys the object holds the guard of this device
     init(t);
     int st = t->check_new(h_items, n_items);
     if (st == CAVMD_OK)
         st = t->capacity_status(n_items);
     if (st == CAVMD_OK)
     {
-        t->adopt(ws->device, h_items, n_items);
+        t->adopt(tie->device, h_items, n_items);
         DeviceGuard guard(t->device);
         hipError_t e = t->upload();
         if (e == hipSuccess)
@@ -282,7 +296,7 @@ int create_table(cavmd_workspace* ws, size_t n_items, const Item* h_items, Table
         return st;
     }
     if (Table::tied)
-        t->attach(ws);
+        t->attach(tie);
     *out = t;
     return CAVMD_OK;
 }
@@ -294,8 +308,8 @@ struct SeriesTable : ItemTable<Item, Row>
 {
     const unsigned n_counters;
     size_t capacity = 0;
-    DeviceArray<Record> d_series;     // n x capacity records, item-major
-    DeviceArray<uint64_t> d_counters; // n_counters arrays of n words
+    cavmd::DeviceArray<Record> d_series;     // n x capacity records, item-major
+    cavmd::DeviceArray<uint64_t> d_counters; // n_counters arrays of n words
 
     SeriesTable(unsigned n_counters_, int (*check_)(const Item*), unsigned (*key_)(const Item&), Row (*to_row_)(const Item&))
         : ItemTable<Item, Row>(check_, key_, to_row_), n_counters(n_counters_)
@@ -372,9 +386,14 @@ struct SeriesTable : ItemTable<Item, Row>
 // ---- derived tables behind a header ----------------------------------------------------------------------------------------
 // The helpers of the objects whose kernels read, besides the rows, tables the library derives from each item.
 
+inline bool finite_nonnegative(double x)
+{
+    return isfinite(x) && x >= 0.0;
+}
+
 // a periodic box: three finite positive edges; *cut_sq = (half the shortest edge)^2, the largest squared cut-off under which
 // the minimum image is the only image in range
-bool box_ok(double Lx, double Ly, double Lz, double* cut_sq)
+inline bool box_ok(double Lx, double Ly, double Lz, double* cut_sq)
 {
     const double L[3] = {Lx, Ly, Lz};
     for (double l : L)
@@ -388,7 +407,7 @@ bool box_ok(double Lx, double Ly, double Lz, double* cut_sq)
 // The partner slots of N particles from a host pair list: `cap` slots a particle, `empty` where there is no partner, filled
 // from slot 0 in list order with word(partner, type of the pair).  Refuses an index >= N, a pair of a particle with itself and
 // a particle's (cap + 1)-th partner.  `slots` NULL: the status alone.
-int partner_slots(uint32_t N, const cavmd_molecular_bond* pairs, uint32_t n_pairs, unsigned cap, uint32_t empty,
+inline int partner_slots(uint32_t N, const cavmd_molecular_bond* pairs, uint32_t n_pairs, unsigned cap, uint32_t empty,
                   uint32_t (*word)(uint32_t partner, uint32_t type), std::vector<uint32_t>* slots)
 {
     std::vector<uint8_t> count(N, 0);
@@ -422,14 +441,14 @@ uint32_t pool_append(std::vector<T>* pool, const std::vector<T>& part)
 }
 
 // one entry per workgroup of an item with `count` particles (or k-vectors), `rows` of them a workgroup: {item, first, z, w}
-void emit_blocks(std::vector<uint4>* table, unsigned item, unsigned count, unsigned rows, unsigned z, unsigned w)
+inline void emit_blocks(std::vector<uint4>* table, unsigned item, unsigned count, unsigned rows, unsigned z, unsigned w)
 {
     for (unsigned first = 0; first < count; first += rows)
         table->push_back(make_uint4(item, first, z, w));
 }
 
 // particles a launch gets LDS for: the largest N of the table, rounded up to even, at least 2
-unsigned lds_particles(unsigned largest)
+inline unsigned lds_particles(unsigned largest)
 {
     return std::max(2u, (largest + 1u) & ~1u);
 }
@@ -443,7 +462,7 @@ template <class Item, class Row, class Derived, class Tables>
 struct LinkedTable : ItemTable<Item, Row>
 {
     using Base = ItemTable<Item, Row>;
-    DeviceArray<decltype(Tables::header)> d_header; // never reallocated
+    cavmd::DeviceArray<decltype(Tables::header)> d_header; // never reallocated
     Tables tables;                                  // replaced as a whole
     std::vector<Derived> derived;                   // per item (the caller's lists are not kept)
 

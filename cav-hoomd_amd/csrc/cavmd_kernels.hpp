@@ -1,4 +1,5 @@
-// cavmd_kernels.hpp -- CDNA4 (gfx950) device code of the cavity-force path (umbrella header).
+// cavmd_kernels.hpp -- CDNA4 (gfx950) device code of the cavity-force path (umbrella header: for the two micro-benchmarks;
+// each unit of the library includes the kernel headers it launches from instead).
 //
 // An evaluation is ONE launch for 1024 < N <~ 2.4e6 (cavmd_persistent_kernel.hpp: both phases below in one grid of
 // co-resident blocks, charges kept in LDS between them), one single-block launch up to 1024 particles, and otherwise
@@ -25,6 +26,7 @@
 // Files: cavmd_reduce.hpp (double-double arithmetic, DPP, block trees), cavmd_force_kernels.hpp (the force path),
 //        cavmd_batch_kernel.hpp (many small systems in one launch, one workgroup each),
 //        cavmd_persistent_kernel.hpp (the single-launch evaluation), cavmd_observable_kernels.hpp (rows f2-f4),
+//        cavmd_cavity_mode_kernel.hpp (the one kernel that is no template: included only where it is launched),
 //        cavmd_bussi_batch_kernel.hpp (the thermostat step of many small systems in one launch, one workgroup each),
 //        cavmd_recorder_kernel.hpp (their per-step observables appended to a time series in device memory, one launch),
 //        cavmd_verlet_batch_kernel.hpp (their velocity-Verlet half-steps, one launch each),
@@ -37,6 +39,7 @@
 #include "cavmd_batch_kernel.hpp"
 #include "cavmd_persistent_kernel.hpp"
 #include "cavmd_observable_kernels.hpp"
+#include "cavmd_cavity_mode_kernel.hpp"
 #include "cavmd_bussi_batch_kernel.hpp"
 #include "cavmd_recorder_kernel.hpp"
 #include "cavmd_field_recorder_kernel.hpp"

@@ -1,0 +1,127 @@
+// cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory.
+// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "cavmd.h"
+#include "cavmd_recorder_kernel.hpp"
+#include "cavmd_item_table.hpp"
+
+using namespace cavmd;
+
+// ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
+// launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
+struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_record>
+{
+    uint64_t period = 1;
+    double kB = 0.0;
+
+    cavmd_recorder()
+        : SeriesTable(kRecCounters, cavmd_recorder_item_check,
+                      [](const cavmd_recorder_item& it) { return std::max(it.N, it.n_members); },
+                      uploaded_as_it_is<cavmd_recorder_item, RecorderRow>)
+    {
+    }
+
+    int capacity_status(size_t n_items) const
+    {
+        return capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        return alloc_series();
+    }
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_record) == 128 && offsetof(cavmd_record, energy) == 16 && offsetof(cavmd_record, cavity_kinetic) == 88,
+              "record layout");
+static_assert(sizeof(cavmd_recorder_item) == sizeof(RecorderRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_recorder_item, d_result) == offsetof(RecorderRow, res)
+                  && offsetof(cavmd_recorder_item, d_vel) == offsetof(RecorderRow, vel2)
+                  && offsetof(cavmd_recorder_item, d_net_force) == offsetof(RecorderRow, force2)
+                  && offsetof(cavmd_recorder_item, d_members) == offsetof(RecorderRow, members)
+                  && offsetof(cavmd_recorder_item, N) == offsetof(RecorderRow, N)
+                  && offsetof(cavmd_recorder_item, n_members) == offsetof(RecorderRow, n_members),
+              "recorder item layout");
+static_assert(CAVMD_BATCH_MAX_ITEM_N <= kRecorderMaxTiles * 256 * kRecorderUnroll, "one LDS partial per tile");
+static_assert(kRecRows == 0, "SeriesTable: the rows-written array is the first of the counters");
+} // namespace
+
+extern "C"
+{
+
+int cavmd_recorder_item_check(const cavmd_recorder_item* it)
+{
+    if (!it || !it->d_result)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 3; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_result & 15) || ((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_net_force & 15)
+        || ((uintptr_t)it->d_members & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N || it->n_members > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recorder_item* h_items, size_t capacity,
+                          uint64_t period, double kB, cavmd_recorder** out)
+{
+    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
+    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_recorder* r) {
+        r->capacity = capacity;
+        r->period = period;
+        r->kB = kB;
+    });
+}
+
+int cavmd_recorder_destroy(cavmd_recorder* r)
+{
+    return destroy_table(r);
+}
+
+int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, const cavmd_recorder_item* h_items)
+{
+    return r ? r->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
+{
+    if (!r)
+        return CAVMD_ERR_INVALID_VALUE;
+    return r->launch((hipStream_t)stream_, recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, r->d_rows.ptr,
+                     r->d_order.ptr, (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series.ptr, r->d_counters.ptr);
+}
+
+int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
+{
+    return (r && out) ? r->rows((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_recorder_read(cavmd_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
+                        cavmd_record* out)
+{
+    if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
+        return CAVMD_ERR_INVALID_VALUE;
+    return r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
+}
+
+int cavmd_recorder_reset(cavmd_recorder* r, void* stream_)
+{
+    return r ? r->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows)
+{
+    return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
+}
+
+} // extern "C"
