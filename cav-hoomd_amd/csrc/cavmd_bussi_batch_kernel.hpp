@@ -10,15 +10,16 @@
 // Bits: per item what cavmd_bussi_step_device gives that item alone on a device with at least kBussiBatchMaxTiles compute
 // units.  There the single path's first launch has one workgroup per tile of BLOCK * UNROLL members (grid = min(tiles, CUs)),
 // each leaving one double-double partial (kinetic_partial -> block_reduce_dd1), and its second launch folds them as "thread t
-// merges partials t, t + BLOCK, ...; then block_reduce_dd1".  The workgroup below walks the same tiles, reduces each with the
-// same tree into a partial kept in LDS, and folds them in that same order: same addends, same tree, same K.
+// merges partials t, t + BLOCK, ...; then block_reduce_dd1".  The workgroup below walks the same tiles (sum_tile_load) with the
+// same addend (kinetic_addend), reduces each with the same tree into a partial kept in LDS (tile_partial_to_lds), and folds
+// them in that same order: same addends, same tree, same K.
 #pragma once
 
 #include "cavmd_observable_kernels.hpp"
 
 namespace cavmd
 {
-constexpr int kBussiBatchUnroll = 4;      // members per lane and tile: the tile of cavmd_bussi_step_device (256 x 4)
+constexpr int kBussiBatchUnroll = kObservableUnroll; // members per lane and tile: the tile of cavmd_bussi_step_device
 constexpr unsigned kBussiBatchMaxTiles = 64; // CAVMD_BATCH_MAX_ITEM_N / (256 * 4)
 
 // One system of a thermostat batch as the kernel reads it: the layout of cavmd_bussi_batch_item (the table is uploaded as it is).
@@ -53,23 +54,12 @@ struct HostBussiBatch
 };
 static_assert(sizeof(HostBussiBatch) == 64, "one host block = 64 bytes");
 
-// tile t of the item into registers; padding slots: index -1, velocity 0, mass 0 (their term is 0, as in kinetic_partial)
+// tile t of the item into a ScaleTile: the sum's load, with the indices the rescale stores through
 template <int BLOCK, int UNROLL>
 __device__ __forceinline__ void bussi_batch_tile_load(const v2d* __restrict__ vel2, const unsigned* __restrict__ members,
                                                       unsigned n, unsigned t, ScaleTile<BLOCK, UNROLL>& r)
 {
-    const size_t base = (size_t)t * (BLOCK * UNROLL) + threadIdx.x;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-    {
-        const size_t k = base + (size_t)u * BLOCK;
-        const bool ok = k < n;
-        const v2d zero = {0.0, 0.0};
-        const size_t j = ok ? (members ? (size_t)members[k] : k) : 0;
-        r.j[u] = ok ? j : (size_t)-1;
-        r.xy[u] = ok ? vel2[2 * j] : zero;
-        r.zw[u] = ok ? vel2[2 * j + 1] : zero;
-    }
+    sum_tile_load<BLOCK, UNROLL>(vel2, members, n, t, r.xy, r.zw, r.j);
 }
 
 // blockIdx.x -> order[blockIdx.x] (items by n_members descending, sorted on the host) -> the row, fetched once per workgroup
@@ -113,14 +103,8 @@ __global__ __launch_bounds__(BLOCK) void bussi_batch_kernel(const BussiBatchRow*
         DD acc {0.0, 0.0};
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u)
-            dd_acc(acc.hi, acc.lo, r.zw[u].y * ((r.xy[u].x * r.xy[u].x + r.xy[u].y * r.xy[u].y) + r.zw[u].x * r.zw[u].x));
-        acc = block_reduce_dd1<BLOCK>(acc);
-        if (threadIdx.x == 0)
-        {
-            s_part[t][0] = acc.hi;
-            s_part[t][1] = acc.lo;
-        }
-        __syncthreads(); // block_reduce_dd1's LDS array is used again by the next tile / the fold; s_part becomes visible
+            dd_acc(acc.hi, acc.lo, kinetic_addend(r.zw[u].y, r.xy[u].x, r.xy[u].y, r.zw[u].x));
+        tile_partial_to_lds<BLOCK>(acc, s_part, t);
     }
     // the single path's second launch: thread t merges partials t, t + BLOCK, ... (at most one here), then the block tree --
     // also for ONE partial, which goes through thread 0 and a second tree exactly as it does there

@@ -280,10 +280,7 @@ __global__ __launch_bounds__(BLOCK) void field_recorder_batch_kernel(
             *c_refs = (uint64_t)n_refs + 1;
             *c_last = t;
         }
-        *c_rows = t + 1;
-        *c_slot = (slot + 1 >= capacity) ? 0 : slot + 1;
-        *c_calls = calls;
-        *c_phase = 0;
+        record_counters_store(c_rows, c_calls, c_phase, c_slot, t, slot, capacity, calls);
     }
 }
 } // namespace cavmd

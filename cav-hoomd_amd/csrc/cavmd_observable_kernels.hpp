@@ -395,6 +395,28 @@ struct HostMode
 // =====================================================================================================================
 namespace cavmd
 {
+// The tile of every scalar sum below and of the velocity rescale: BLOCK lanes x UNROLL entries per lane.  The single paths are
+// launched with it and the batch kernels walk an item in the same tiles; equal bits between them depend on that.
+constexpr int kObservableBlock = 256, kObservableUnroll = 4;
+
+// (x^2 + y^2) + z^2, one rounding per operation
+__device__ __forceinline__ double norm2(double x, double y, double z)
+{
+    return (x * x + y * y) + z * z;
+}
+
+// The cavity mode's four numbers (reference: CavityModeTracker.compute_cavity_properties, src/cavitymd/analysis.py:1324-1368)
+// from the photon's mass and velocity and the harmonic energy of the result block: v[0..3] = KE = 1/2 m v.v, PE, KE + PE,
+// temperature = (2/3) KE / k_B.  Called by cavity_mode_kernel and, per item, by recorder_batch_kernel.
+__device__ __forceinline__ void cavity_mode_numbers(double m, double vx, double vy, double vz, double pe, double kB,
+                                                    double (&v)[4])
+{
+    v[0] = 0.5 * m * norm2(vx, vy, vz);
+    v[1] = pe;
+    v[2] = v[0] + pe;
+    v[3] = (2.0 / 3.0) * v[0] / kB;
+}
+
 // One scalar handed to the host without a copy or a stream synchronisation: mapped, coherent pinned memory; the value is
 // stored first, then the call's sequence number is release-stored at system scope (the same hand-off as cavmd_result).
 struct HostScalar
@@ -437,6 +459,20 @@ __device__ __forceinline__ DD block_reduce_dd1(DD v)
     return v;
 }
 
+// A tile's tree, then its partial into LDS slot t for the fold that follows (a batch kernel's stand-in for one workgroup of the
+// single path's grid); the barrier makes the slot visible and frees block_reduce_dd1's LDS array for the next tree.
+template <int BLOCK>
+__device__ __forceinline__ void tile_partial_to_lds(DD acc, double (*part)[2], unsigned t)
+{
+    acc = block_reduce_dd1<BLOCK>(acc);
+    if (threadIdx.x == 0)
+    {
+        part[t][0] = acc.hi;
+        part[t][1] = acc.lo;
+    }
+    __syncthreads();
+}
+
 // One-launch tail of a scalar reduction: every block stores its double-double partial (8-byte agent-scope write-through
 // stores), drains them and takes a ticket; the block that draws the LAST ticket folds all partials in index order (thread t:
 // partials t, t + BLOCK, ...; then the block tree) -- a fixed order whichever block it is, so the result is bit-reproducible
@@ -477,6 +513,13 @@ __device__ __forceinline__ bool fold_by_last_block(DD& acc, double* __restrict__
     return true;
 }
 
+// |F_i| / m_i, the addend of force_mass_fused_kernel (non-temporal loads) and of recorder_batch_kernel (plain loads: the
+// thermostat reads the same velocities next); a padding slot adds 0 / 1
+__device__ __forceinline__ double force_mass_addend(const v2d& fxy, const v2d& fzw, const v2d& vzw)
+{
+    return sqrt(norm2(fxy.x, fxy.y, fzw.x)) / vzw.y;
+}
+
 template <int BLOCK, int UNROLL>
 __global__ __launch_bounds__(BLOCK) void force_mass_fused_kernel(const v2d* __restrict__ force2, const v2d* __restrict__ vel2,
                                                                  unsigned N, double* __restrict__ part,
@@ -505,10 +548,7 @@ __global__ __launch_bounds__(BLOCK) void force_mass_fused_kernel(const v2d* __re
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u)
-        {
-            const double n2 = (fxy[u].x * fxy[u].x + fxy[u].y * fxy[u].y) + fzw[u].x * fzw[u].x;
-            dd_acc(acc.hi, acc.lo, sqrt(n2) / vzw[u].y); // |F_i| / m_i; padding lanes add 0 / 1
-        }
+            dd_acc(acc.hi, acc.lo, force_mass_addend(fxy[u], fzw[u], vzw[u]));
     }
     acc = block_reduce_dd1<BLOCK>(acc);
     if (fold_by_last_block<BLOCK>(acc, part, ticket) && threadIdx.x == 0)
@@ -531,6 +571,35 @@ __global__ __launch_bounds__(BLOCK) void force_mass_fused_kernel(const v2d* __re
 // =====================================================================================================================
 namespace cavmd
 {
+// Tile t of a group (members == nullptr: particles 0 .. n-1) for a SUM: no branch, and a padding slot carries velocity 0 and
+// mass 0, so that its kinetic addend is 0.  Where `index` is given it gets the particle index of each slot, (size_t)-1 for
+// padding.  Called by recorder_batch_kernel and by bussi_batch_kernel, which also rescales from the tile and so keeps the
+// indices; kinetic_partial restates it.  scale_tile_load below is the rescale's own: it branches and leaves padding unset.
+template <int BLOCK, int UNROLL>
+__device__ __forceinline__ void sum_tile_load(const v2d* __restrict__ vel2, const unsigned* __restrict__ members, unsigned n,
+                                              unsigned t, v2d (&vxy)[UNROLL], v2d (&vzw)[UNROLL], size_t* index = nullptr)
+{
+    const size_t base = (size_t)t * (BLOCK * UNROLL) + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+    {
+        const size_t k = base + (size_t)u * BLOCK;
+        const bool ok = k < n;
+        const v2d zero = {0.0, 0.0};
+        const size_t j = ok ? (members ? (size_t)members[k] : k) : 0;
+        if (index)
+            index[u] = ok ? j : (size_t)-1;
+        vxy[u] = ok ? vel2[2 * j] : zero;
+        vzw[u] = ok ? vel2[2 * j + 1] : zero;
+    }
+}
+
+// m (vx^2 + vy^2 + vz^2): the addend of every kinetic energy here (kinetic_partial, recorder_batch_kernel, bussi_batch_kernel)
+__device__ __forceinline__ double kinetic_addend(double m, double vx, double vy, double vz)
+{
+    return m * norm2(vx, vy, vz);
+}
+
 // sum_j m_j (vx^2 + vy^2 + vz^2) over this block's tiles (tile t -> block t % gridDim.x), one double-double per lane
 template <int BLOCK, int UNROLL>
 __device__ __forceinline__ DD kinetic_partial(const v2d* __restrict__ vel2, const unsigned* __restrict__ members, unsigned n)
@@ -540,6 +609,7 @@ __device__ __forceinline__ DD kinetic_partial(const v2d* __restrict__ vel2, cons
     const unsigned tiles = (n + TILE - 1) / TILE;
     for (unsigned t = blockIdx.x; t < tiles; t += gridDim.x)
     {
+        // restates sum_tile_load: as a call it changes the register count of both kernels built on this (44 -> 42 VGPRs)
         const size_t base = (size_t)t * TILE + threadIdx.x;
         v2d vxy[UNROLL], vzw[UNROLL];
 #pragma unroll
@@ -555,7 +625,7 @@ __device__ __forceinline__ DD kinetic_partial(const v2d* __restrict__ vel2, cons
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u)
-            dd_acc(acc.hi, acc.lo, vzw[u].y * ((vxy[u].x * vxy[u].x + vxy[u].y * vxy[u].y) + vzw[u].x * vzw[u].x));
+            dd_acc(acc.hi, acc.lo, kinetic_addend(vzw[u].y, vxy[u].x, vxy[u].y, vzw[u].x));
     }
     return acc;
 }
@@ -758,4 +828,17 @@ __global__ __launch_bounds__(BLOCK) void bussi_rescale_fused_kernel(v2d* __restr
         return;
     scale_velocities_body<BLOCK, UNROLL>(vel2, members, n, alpha, &first);
 }
+
+// The counters of a recording batch kernel behind a recorded row (recorder_batch_kernel, field_recorder_batch_kernel), by
+// thread 0: one more row, the next slot of the ring, the call, phase 0.
+__device__ __forceinline__ void record_counters_store(uint64_t* __restrict__ c_rows, uint64_t* __restrict__ c_calls,
+                                                      uint64_t* __restrict__ c_phase, uint64_t* __restrict__ c_slot,
+                                                      uint64_t n_rows, uint64_t slot, uint64_t capacity, uint64_t calls)
+{
+    *c_rows = n_rows + 1;
+    *c_slot = (slot + 1 >= capacity) ? 0 : slot + 1;
+    *c_calls = calls;
+    *c_phase = 0;
+}
+
 } // namespace cavmd

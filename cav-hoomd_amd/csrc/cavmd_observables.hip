@@ -213,7 +213,7 @@ int cavmd_force_mass_sum(cavmd_workspace* ws, void* stream_, size_t N, const cav
         if (st0 != CAVMD_OK)
             return st0;
     }
-    constexpr int kBlock = 256, kUnroll = 4;
+    constexpr int kBlock = kObservableBlock, kUnroll = kObservableUnroll;
     // one block per CU: every block draws a ticket from ONE counter (~12 ns each, serialised at the memory side); with four
     // blocks per CU the 1024 tickets alone took 12 us
     const unsigned g = grid_for(N, kBlock * kUnroll, ws->num_cu, 1);
@@ -245,7 +245,7 @@ int cavmd_kinetic_energy(cavmd_workspace* ws, void* stream_, const cavmd_double4
         if (st0 != CAVMD_OK)
             return st0;
     }
-    constexpr int kBlock = 256, kUnroll = 4;
+    constexpr int kBlock = kObservableBlock, kUnroll = kObservableUnroll;
     const unsigned g = grid_for(n_members, kBlock * kUnroll, ws->num_cu, 1); // one ticket per CU, see cavmd_force_mass_sum
     double* d_out = ws->d_fm_part.ptr + 2 * (size_t)ws->max_parts;
     ws->fm_sequence += 1;
@@ -267,7 +267,7 @@ int cavmd_scale_velocities(cavmd_workspace* ws, void* stream_, cavmd_double4* d_
         return CAVMD_OK;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(ws->device);
-    constexpr int kBlock = 256, kUnroll = 4;
+    constexpr int kBlock = kObservableBlock, kUnroll = kObservableUnroll;
     const unsigned g = grid_for(n_members, kBlock * kUnroll, ws->num_cu, kScaleBlocksPerCu);
     hipLaunchKernelGGL((scale_velocities_kernel<kBlock, kUnroll>), dim3(g), dim3(kBlock), 0, stream, reinterpret_cast<v2d*>(d_vel),
                        d_members, (unsigned)n_members, alpha);
@@ -357,7 +357,7 @@ int cavmd_bussi_step_device(cavmd_workspace* ws, void* stream_, cavmd_double4* d
         if (st0 != CAVMD_OK)
             return st0;
     }
-    constexpr int kBlock = 256, kUnroll = 4;
+    constexpr int kBlock = kObservableBlock, kUnroll = kObservableUnroll;
     BussiStepArgs a;
     a.dof = dof_translational;
     a.c = (tau != 0.0) ? exp(-deltaT / tau) : 0.0; // :186-190

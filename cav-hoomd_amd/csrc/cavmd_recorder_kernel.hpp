@@ -8,19 +8,20 @@
 // replay appends a NEW row each time; the host reads the series when it likes, behind a stream synchronisation.  Workgroups
 // never wait for each other; the item's workgroup is the only writer of its counters and of its series (no atomics).
 //
-// Bits, per item: the result columns are the bytes of the cavmd_result block; the cavity mode is cavity_mode_kernel's
-// expression; kinetic_energy and force_mass_sum are what cavmd_kinetic_energy / cavmd_force_mass_sum give that item alone on a
-// device with at least kRecorderMaxTiles compute units: there kinetic_fused_kernel / force_mass_fused_kernel run one workgroup
-// per tile of BLOCK * UNROLL entries (grid = min(tiles, CUs)), each leaving one double-double partial (block_reduce_dd1), and
-// the last one folds them as "thread t merges partials t, t + BLOCK, ...; then block_reduce_dd1".  The workgroup below walks
-// the same tiles, reduces each with the same tree into a partial kept in LDS, and folds them in that same order.
+// Bits, per item: the result columns are the bytes of the cavmd_result block; the cavity mode is cavity_mode_numbers, which
+// cavity_mode_kernel calls too; kinetic_energy and force_mass_sum are what cavmd_kinetic_energy / cavmd_force_mass_sum give that
+// item alone on a device with at least kRecorderMaxTiles compute units: there kinetic_fused_kernel / force_mass_fused_kernel run
+// one workgroup per tile of BLOCK * UNROLL entries (grid = min(tiles, CUs)), each leaving one double-double partial
+// (block_reduce_dd1), and the last one folds them as "thread t merges partials t, t + BLOCK, ...; then block_reduce_dd1".  The
+// workgroup below walks the same tiles with the same addends (kinetic_addend, force_mass_addend), reduces each with the same
+// tree into a partial kept in LDS (tile_partial_to_lds), and folds them in that same order.
 #pragma once
 
 #include "cavmd_observable_kernels.hpp"
 
 namespace cavmd
 {
-constexpr int kRecorderUnroll = 4;          // entries per lane and tile: the tile of the two single paths (256 x 4)
+constexpr int kRecorderUnroll = kObservableUnroll; // entries per lane and tile: the tile of the two single paths
 constexpr unsigned kRecorderMaxTiles = 64;  // CAVMD_BATCH_MAX_ITEM_N / (256 * 4)
 
 // One system as the kernel reads it: the layout of cavmd_recorder_item (the table is uploaded as it is).
@@ -47,26 +48,7 @@ enum RecorderCounter
     kRecCounters = 4
 };
 
-// the (vx, vy) and (vz, m) halves of tile t's velocities; padding slots: velocity 0, mass 0 (their term is 0, as in
-// kinetic_partial)
-template <int BLOCK, int UNROLL>
-__device__ __forceinline__ void recorder_load_vel(const v2d* __restrict__ vel2, const unsigned* __restrict__ members, unsigned n,
-                                                  unsigned t, v2d (&vxy)[UNROLL], v2d (&vzw)[UNROLL])
-{
-    const size_t base = (size_t)t * (BLOCK * UNROLL) + threadIdx.x;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-    {
-        const size_t k = base + (size_t)u * BLOCK;
-        const bool ok = k < n;
-        const v2d zero = {0.0, 0.0};
-        const size_t j = ok ? (members ? (size_t)members[k] : k) : 0;
-        vxy[u] = ok ? vel2[2 * j] : zero;
-        vzw[u] = ok ? vel2[2 * j + 1] : zero;
-    }
-}
-
-// tile t's net forces; padding slots: force 0 (force_mass_fused_kernel's)
+// tile t's net forces; padding slots: force 0, as in force_mass_fused_kernel (whose loads are non-temporal)
 template <int BLOCK, int UNROLL>
 __device__ __forceinline__ void recorder_load_force(const v2d* __restrict__ force2, unsigned N, unsigned t, v2d (&fxy)[UNROLL],
                                                     v2d (&fzw)[UNROLL])
@@ -103,7 +85,7 @@ __device__ __forceinline__ DD recorder_kinetic_terms(const v2d (&vxy)[UNROLL], c
     DD acc {0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-        dd_acc(acc.hi, acc.lo, vzw[u].y * ((vxy[u].x * vxy[u].x + vxy[u].y * vxy[u].y) + vzw[u].x * vzw[u].x));
+        dd_acc(acc.hi, acc.lo, kinetic_addend(vzw[u].y, vxy[u].x, vxy[u].y, vzw[u].x));
     return acc;
 }
 
@@ -114,24 +96,8 @@ __device__ __forceinline__ DD recorder_force_mass_terms(const v2d (&fxy)[UNROLL]
     DD acc {0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-    {
-        const double n2 = (fxy[u].x * fxy[u].x + fxy[u].y * fxy[u].y) + fzw[u].x * fzw[u].x;
-        dd_acc(acc.hi, acc.lo, sqrt(n2) / vzw[u].y); // |F_i| / m_i
-    }
+        dd_acc(acc.hi, acc.lo, force_mass_addend(fxy[u], fzw[u], vzw[u]));
     return acc;
-}
-
-// the tile's tree, then its partial into LDS; the barrier frees block_reduce_dd1's LDS array for the next tree
-template <int BLOCK>
-__device__ __forceinline__ void recorder_tile_partial(DD acc, double (*part)[2], unsigned t)
-{
-    acc = block_reduce_dd1<BLOCK>(acc);
-    if (threadIdx.x == 0)
-    {
-        part[t][0] = acc.hi;
-        part[t][1] = acc.lo;
-    }
-    __syncthreads();
 }
 
 // the fold of fold_by_last_block: thread t merges partials t, t + BLOCK, ..., then the block tree; total in thread 0
@@ -169,6 +135,7 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
     uint64_t* __restrict__ c_slot = counters + (size_t)kRecSlot * n_items + item;
 
     // 1. does this call record?  Thread 0 alone reads the counters (it is also their only writer) and tells the others.
+    //    (field_recorder_batch_kernel restates this: as a shared function it changed both kernels' register counts.)
     uint64_t calls = 0, phase = 0;
     if (threadIdx.x == 0)
     {
@@ -202,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
         for (unsigned t = 0; t < tiles_ke; ++t)
         {
             v2d vxy[UNROLL], vzw[UNROLL], fxy[UNROLL], fzw[UNROLL], mzw[UNROLL];
-            recorder_load_vel<BLOCK, UNROLL>(vel2, nullptr, n_ke, t, vxy, vzw);
+            sum_tile_load<BLOCK, UNROLL>(vel2, nullptr, n_ke, t, vxy, vzw);
             recorder_load_force<BLOCK, UNROLL>(force2, n_fm, t, fxy, fzw);
             __builtin_amdgcn_sched_barrier(0);
             const size_t base = (size_t)t * TILE + threadIdx.x;
@@ -212,8 +179,8 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
                 const v2d one = {0.0, 1.0};
                 mzw[u] = (base + (size_t)u * BLOCK) < n_fm ? vzw[u] : one;
             }
-            recorder_tile_partial<BLOCK>(recorder_kinetic_terms<UNROLL>(vxy, vzw), s_ke, t);
-            recorder_tile_partial<BLOCK>(recorder_force_mass_terms<UNROLL>(fxy, fzw, mzw), s_fm, t);
+            tile_partial_to_lds<BLOCK>(recorder_kinetic_terms<UNROLL>(vxy, vzw), s_ke, t);
+            tile_partial_to_lds<BLOCK>(recorder_force_mass_terms<UNROLL>(fxy, fzw, mzw), s_fm, t);
         }
     }
     else
@@ -221,9 +188,9 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
         for (unsigned t = 0; t < tiles_ke; ++t)
         {
             v2d vxy[UNROLL], vzw[UNROLL];
-            recorder_load_vel<BLOCK, UNROLL>(vel2, members, n_ke, t, vxy, vzw);
+            sum_tile_load<BLOCK, UNROLL>(vel2, members, n_ke, t, vxy, vzw);
             __builtin_amdgcn_sched_barrier(0);
-            recorder_tile_partial<BLOCK>(recorder_kinetic_terms<UNROLL>(vxy, vzw), s_ke, t);
+            tile_partial_to_lds<BLOCK>(recorder_kinetic_terms<UNROLL>(vxy, vzw), s_ke, t);
         }
         for (unsigned t = 0; t < tiles_fm; ++t)
         {
@@ -231,13 +198,13 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
             recorder_load_force<BLOCK, UNROLL>(force2, n_fm, t, fxy, fzw);
             recorder_load_mass<BLOCK, UNROLL>(vel2, n_fm, t, mzw);
             __builtin_amdgcn_sched_barrier(0);
-            recorder_tile_partial<BLOCK>(recorder_force_mass_terms<UNROLL>(fxy, fzw, mzw), s_fm, t);
+            tile_partial_to_lds<BLOCK>(recorder_force_mass_terms<UNROLL>(fxy, fzw, mzw), s_fm, t);
         }
     }
     const DD ke = recorder_fold<BLOCK>(s_ke, tiles_ke);
     const DD fm = recorder_fold<BLOCK>(s_fm, tiles_fm);
 
-    // 3. the row: the evaluation's block as it is, the cavity mode (cavity_mode_kernel's expressions), the two sums
+    // 3. the row: the evaluation's block as it is, the cavity mode, the two sums
     if (threadIdx.x == 0)
     {
         const cavmd_result* __restrict__ res = row->res;
@@ -254,23 +221,19 @@ __global__ __launch_bounds__(BLOCK) void recorder_batch_kernel(const RecorderRow
             rec.q[k] = res->q[k];
         }
         const int p = res->photon_idx;
-        double cav_ke = 0.0, cav_T = 0.0;
+        double mode[4] = {0.0, 0.0, 0.0, 0.0};
         if (p >= 0 && vel2)
         {
             const v2d pxy = vel2[2 * (size_t)p], pzw = vel2[2 * (size_t)p + 1];
-            cav_ke = 0.5 * pzw.y * ((pxy.x * pxy.x + pxy.y * pxy.y) + pzw.x * pzw.x);
-            cav_T = (2.0 / 3.0) * cav_ke / kB;
+            cavity_mode_numbers(pzw.y, pxy.x, pxy.y, pzw.x, rec.energy[0], kB, mode);
         }
-        rec.cavity_kinetic = cav_ke;
-        rec.cavity_temperature = cav_T;
+        rec.cavity_kinetic = mode[0];
+        rec.cavity_temperature = mode[3];
         rec.kinetic_energy = 0.5 * (ke.hi + ke.lo);
         rec.force_mass_sum = fm.hi + fm.lo;
         rec.reserved = 0.0;
         series[(size_t)item * capacity + slot] = rec;
-        *c_rows = n_rows + 1;
-        *c_slot = (slot + 1 >= capacity) ? 0 : slot + 1;
-        *c_calls = calls;
-        *c_phase = 0;
+        record_counters_store(c_rows, c_calls, c_phase, c_slot, n_rows, slot, capacity, calls);
     }
 }
 } // namespace cavmd
