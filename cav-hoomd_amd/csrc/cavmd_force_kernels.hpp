@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "cavmd_reduce.hpp"
+#include "cavmd_tile_schedule.hpp"
 
 #pragma clang fp contract(off)
 
@@ -52,6 +53,12 @@ struct AosInputT
         }
         return r;
     }
+    // Every field of a row as an operand of an empty statement: the compiler places its counted wait for the row's loads here
+    // (loads return in order, so nothing issued after the row is waited for), and no later load is moved above it.
+    static __device__ __forceinline__ void landed(const Raw& r)
+    {
+        asm volatile("" : : "v"(r.xy), "v"(r.zw), "v"(r.c), "v"(r.ix), "v"(r.iy), "v"(r.iz) : "memory");
+    }
     static __device__ __forceinline__ double x(const Raw& r) { return r.xy.x; }
     static __device__ __forceinline__ double y(const Raw& r) { return r.xy.y; }
     static __device__ __forceinline__ double z(const Raw& r) { return r.zw.x; }
@@ -87,6 +94,10 @@ struct StridedInput
         r.iz = __builtin_nontemporal_load(im + 2);
         r.t = __builtin_nontemporal_load(reinterpret_cast<const int*>(tid + i * tid_stride));
         return r;
+    }
+    static __device__ __forceinline__ void landed(const Raw& r) // as AosInputT::landed
+    {
+        asm volatile("" : : "v"(r.px), "v"(r.py), "v"(r.pz), "v"(r.c), "v"(r.ix), "v"(r.iy), "v"(r.iz), "v"(r.t) : "memory");
     }
     static __device__ __forceinline__ double x(const Raw& r) { return r.px; }
     static __device__ __forceinline__ double y(const Raw& r) { return r.py; }
@@ -147,11 +158,10 @@ struct Partials
 };
 
 // ---- kernel 1: per-block partial dipole sums + photon search --------------------------------------
-// One tile = BLOCK * UNROLL particles; block b takes tiles b, b + grid, ...  All UNROLL particles' loads of a lane are
-// issued together (16 loads in flight per lane at UNROLL = 4; a scheduling barrier keeps hipcc from sinking them
-// behind each other's waits).  PIPE = 1 additionally double-buffers tiles: the next tile's loads are issued before
-// the current tile's arithmetic, so that the ~57 VALU operations per particle overlap with memory even at one wave
-// per SIMD.
+// One tile = BLOCK * UNROLL particles; block b takes tiles b, b + grid, ...  A lane keeps the loads of UNROLL particle rows in
+// flight and waits for one row at a time (accumulate_full_tiles below: the rolling loop), so that the ~57 VALU operations per
+// particle overlap with the block's own loads even at one wave per SIMD.  PIPE = 1 (micro-benchmark only) is the earlier
+// attempt at the same: whole tiles double-buffered, all of a tile's loads issued together and waited for together.
 template <class Input, int UNROLL>
 struct TileRegs
 {
@@ -203,6 +213,73 @@ __device__ __forceinline__ void tile_accumulate(const TileRegs<Input, UNROLL>& r
     }
 }
 
+// One row of a tile: what tile_accumulate does for row u, with the fast-path test taken per row.  Same bits: for a lane whose
+// particle is not L-typed Accum::add performs the same dd_acc(c * r) and only adds +0.0 to sx, sy, sz (never -0.0: they start at
+// +0.0 and only grow by sums) and keeps lmin and lcnt.
+template <class Input>
+__device__ __forceinline__ void row_accumulate(const typename Input::Raw& r, size_t i, double Lx, double Ly, double Lz,
+                                               int L_typeid, Accum& acc)
+{
+    if (!__any(Input::tag(r) == L_typeid))
+    {
+        const double c = r.c;
+        dd_acc(acc.hx, acc.lx, c * (Input::x(r) + (double)r.ix * Lx));
+        dd_acc(acc.hy, acc.ly, c * (Input::y(r) + (double)r.iy * Ly));
+        dd_acc(acc.hz, acc.lz, c * (Input::z(r) + (double)r.iz * Lz));
+    }
+    else
+    {
+        const double rx = Input::x(r) + (double)r.ix * Lx;
+        const double ry = Input::y(r) + (double)r.iy * Ly;
+        const double rz = Input::z(r) + (double)r.iz * Lz;
+        acc.add((unsigned)i, rx, ry, rz, r.c, Input::tag(r), L_typeid);
+    }
+}
+
+// The full tiles of one block, accumulated in tile order, then row order: exactly the operations of
+//     for k: tile_load(k); tile_accumulate(k)
+// on every lane.  UNROLL >= 2: the rolling loop of cavmd_tile_schedule.hpp -- a wave waits for one row at a time and has the
+// next tile's row on its way before it starts the arithmetic, at the plain loop's bytes in flight (the double buffer PIPE holds
+// two tiles in flight instead, which queued twice the bytes on the slowest paths and lost).  UNROLL == 1: a row is a tile,
+// rolling would BE that double buffer, so the plain loop stays.  row_hook(k, u, charge) runs once per row, before its
+// arithmetic (the single-launch kernel parks the charge in LDS; the reduction kernel does nothing).
+template <class Input, int BLOCK, int UNROLL, class RowHook>
+__device__ __forceinline__ void accumulate_full_tiles(const Input& in, const TileSchedule& sch, double Lx, double Ly, double Lz,
+                                                      int L_typeid, Accum& acc, RowHook&& row_hook)
+{
+    if constexpr (UNROLL == 1)
+    {
+        for (unsigned k = 0; k < sch.nfull; ++k)
+        {
+            const size_t base = tile_row_base(sch, k, 0, BLOCK) + threadIdx.x;
+            TileRegs<Input, 1> A;
+            tile_load<Input, BLOCK, 1>(in, base, A);
+            __builtin_amdgcn_sched_barrier(0);
+            row_hook(k, 0, A.raw[0].c);
+            tile_accumulate<Input, BLOCK, 1>(A, base, Lx, Ly, Lz, L_typeid, acc);
+        }
+    }
+    else
+    {
+        TileRegs<Input, UNROLL> R[2];
+        rolling_rows<UNROLL>(
+            sch, BLOCK,
+            [&](int set, int u, size_t base) {
+                R[set].raw[u] = in.load(base + threadIdx.x);
+                __builtin_amdgcn_sched_barrier(0); // the row's loads stay ahead of the arithmetic that follows
+            },
+            [&](int set, int u) {
+                __builtin_amdgcn_sched_barrier(0); // nothing of the row before is sunk behind this wait
+                Input::landed(R[set].raw[u]);
+                __builtin_amdgcn_sched_barrier(0); // and the next row's loads are not hoisted above it
+            },
+            [&](int set, int u, unsigned k, size_t base) {
+                row_hook(k, u, R[set].raw[u].c);
+                row_accumulate<Input>(R[set].raw[u], base + threadIdx.x, Lx, Ly, Lz, L_typeid, acc);
+            });
+    }
+}
+
 template <class Input, int BLOCK, int UNROLL, bool PIPE>
 __global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsigned N, double Lx, double Ly, double Lz,
                                                                 int L_typeid, Partials part)
@@ -212,16 +289,8 @@ __global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsign
     const unsigned full_tiles = N / TILE;
     const unsigned G = gridDim.x;
     if (!PIPE)
-    {
-        for (unsigned t = blockIdx.x; t < full_tiles; t += G)
-        {
-            const size_t base = (size_t)t * TILE + threadIdx.x;
-            TileRegs<Input, UNROLL> A;
-            tile_load<Input, BLOCK, UNROLL>(in, base, A);
-            __builtin_amdgcn_sched_barrier(0);
-            tile_accumulate<Input, BLOCK, UNROLL>(A, base, Lx, Ly, Lz, L_typeid, acc);
-        }
-    }
+        accumulate_full_tiles<Input, BLOCK, UNROLL>(in, strided_tiles(N, G, blockIdx.x, TILE), Lx, Ly, Lz, L_typeid, acc,
+                                                    [](unsigned, int, double) {});
     else
     {
         // ping-pong A/B so that no register copies are needed

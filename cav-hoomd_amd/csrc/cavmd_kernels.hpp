@@ -24,6 +24,7 @@
 // a given (N, launch geometry).  The kernel boundary is the only inter-workgroup hand-off.
 //
 // Files: cavmd_reduce.hpp (double-double arithmetic, DPP, block trees), cavmd_force_kernels.hpp (the force path),
+//        cavmd_tile_schedule.hpp (which rows of its tiles a reduction block loads and when: plain C++, the host can enumerate it),
 //        cavmd_batch_kernel.hpp (many small systems in one launch, one workgroup each),
 //        cavmd_persistent_kernel.hpp (the single-launch evaluation), cavmd_observable_kernels.hpp (rows f2-f4),
 //        cavmd_cavity_mode_kernel.hpp (the one kernel that is no template: included only where it is launched),

@@ -243,9 +243,10 @@ __device__ __forceinline__ BlockRange block_range(unsigned N, unsigned G, unsign
     else
     {
         const unsigned full_tiles = N / TILE;
-        r.first = (size_t)b * TILE;
-        r.step = (size_t)G * TILE;
-        r.nfull = full_tiles > b ? (full_tiles - b + G - 1) / G : 0;
+        const TileSchedule s = strided_tiles(N, G, b, TILE);
+        r.first = s.first;
+        r.step = s.step;
+        r.nfull = s.nfull;
         r.tail_base = (size_t)full_tiles * TILE;
         r.tail_count = (b == full_tiles % G) ? (unsigned)(N - r.tail_base) : 0;
     }
@@ -303,20 +304,11 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
     // ---- phase 1: partial dipole of this block's tiles; the charges of its first lds_slots tiles are parked in LDS ---------
     Accum acc;
     const BlockRange rg = block_range<TILE>(N, G, b, balanced);
-    for (unsigned slot = 0; slot < rg.nfull; ++slot)
-    {
-        const size_t base = rg.first + (size_t)slot * rg.step + tid;
-        TileRegs<AosInputT<2>, UNROLL> A;
-        tile_load<AosInputT<2>, BLOCK, UNROLL>(in, base, A);
-        __builtin_amdgcn_sched_barrier(0);
-        if (slot < lds_slots)
-        {
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-                s_charge[slot * TILE + u * BLOCK + tid] = A.raw[u].c;
-        }
-        tile_accumulate<AosInputT<2>, BLOCK, UNROLL>(A, base, Lx, Ly, Lz, L_typeid, acc);
-    }
+    accumulate_full_tiles<AosInputT<2>, BLOCK, UNROLL>(in, TileSchedule {rg.first, rg.step, rg.nfull}, Lx, Ly, Lz, L_typeid, acc,
+                                                       [&](unsigned slot, int u, double c) {
+                                                           if (slot < lds_slots)
+                                                               s_charge[slot * TILE + u * BLOCK + tid] = c;
+                                                       });
     if (rg.tail_count)
     {
         const size_t base = rg.tail_base + tid;
