@@ -528,7 +528,7 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
     st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
         return with_constant(kLoadPolicies, plan.nt_load, [&](auto nt) {
             using Input = AosInputT<decltype(nt)::value>;
-            return ls.launch(0, &dipole_partials_kernel<Input, kReduceBlock, decltype(u)::value, false>, plan.g1, kReduceBlock,
+            return ls.launch(0, &dipole_partials_kernel<Input, kReduceBlock, decltype(u)::value>, plan.g1, kReduceBlock,
                              Input {in.pos2, in.charge, in.image}, n, Lx, Ly, Lz, L_typeid, part);
         });
     });
@@ -624,7 +624,7 @@ int cavmd_compute_soa(cavmd_workspace* ws, void* stream_, size_t N, const double
 
     const EvalPlan plan = plan_evaluation(*ws, N, Layout::strided);
     int st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
-        return ls.launch(0, &dipole_partials_kernel<StridedInput, kReduceBlock, decltype(u)::value, false>, plan.g1, kReduceBlock,
+        return ls.launch(0, &dipole_partials_kernel<StridedInput, kReduceBlock, decltype(u)::value>, plan.g1, kReduceBlock,
                          in, n, Lx, Ly, Lz, L_typeid, part);
     });
     if (st != CAVMD_OK)

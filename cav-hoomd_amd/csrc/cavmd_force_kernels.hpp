@@ -160,8 +160,8 @@ struct Partials
 // ---- kernel 1: per-block partial dipole sums + photon search --------------------------------------
 // One tile = BLOCK * UNROLL particles; block b takes tiles b, b + grid, ...  A lane keeps the loads of UNROLL particle rows in
 // flight and waits for one row at a time (accumulate_full_tiles below: the rolling loop), so that the ~57 VALU operations per
-// particle overlap with the block's own loads even at one wave per SIMD.  PIPE = 1 (micro-benchmark only) is the earlier
-// attempt at the same: whole tiles double-buffered, all of a tile's loads issued together and waited for together.
+// particle overlap with the block's own loads even at one wave per SIMD.  (The earlier attempt at the same, whole tiles
+// double-buffered behind a PIPE template parameter, was last present in commit 1906464: DESIGN.md 3.8, profiles/rolling_tile/.)
 template <class Input, int UNROLL>
 struct TileRegs
 {
@@ -239,8 +239,8 @@ __device__ __forceinline__ void row_accumulate(const typename Input::Raw& r, siz
 // The full tiles of one block, accumulated in tile order, then row order: exactly the operations of
 //     for k: tile_load(k); tile_accumulate(k)
 // on every lane.  UNROLL >= 2: the rolling loop of cavmd_tile_schedule.hpp -- a wave waits for one row at a time and has the
-// next tile's row on its way before it starts the arithmetic, at the plain loop's bytes in flight (the double buffer PIPE holds
-// two tiles in flight instead, which queued twice the bytes on the slowest paths and lost).  UNROLL == 1: a row is a tile,
+// next tile's row on its way before it starts the arithmetic, at the plain loop's bytes in flight (a whole-tile double buffer
+// holds two tiles in flight instead, which queued twice the bytes on the slowest paths and lost).  UNROLL == 1: a row is a tile,
 // rolling would BE that double buffer, so the plain loop stays.  row_hook(k, u, charge) runs once per row, before its
 // arithmetic (the single-launch kernel parks the charge in LDS; the reduction kernel does nothing).
 template <class Input, int BLOCK, int UNROLL, class RowHook>
@@ -280,7 +280,34 @@ __device__ __forceinline__ void accumulate_full_tiles(const Input& in, const Til
     }
 }
 
-template <class Input, int BLOCK, int UNROLL, bool PIPE>
+// The ragged tile of one block: the `count` (< BLOCK * UNROLL) particles from `tile_base` on, bounds-checked, added in row order
+// after the full tiles.  row_hook(o, charge) runs once per row of every lane, o = the particle's offset within the tile, with
+// charge 0 for a lane beyond the end (the single-launch kernel parks it in LDS; the reduction kernel does nothing).
+template <class Input, int BLOCK, int UNROLL, class RowHook>
+__device__ __forceinline__ void accumulate_ragged_tile(const Input& in, size_t tile_base, unsigned count, double Lx, double Ly,
+                                                       double Lz, int L_typeid, Accum& acc, RowHook&& row_hook)
+{
+    const size_t base = tile_base + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+    {
+        const unsigned o = u * BLOCK + threadIdx.x;
+        double c = 0.0;
+        if (o < count)
+        {
+            const size_t i = base + (size_t)u * BLOCK;
+            const typename Input::Raw r = in.load(i);
+            const double rx = Input::x(r) + (double)r.ix * Lx;
+            const double ry = Input::y(r) + (double)r.iy * Ly;
+            const double rz = Input::z(r) + (double)r.iz * Lz;
+            acc.add((unsigned)i, rx, ry, rz, r.c, Input::tag(r), L_typeid);
+            c = r.c;
+        }
+        row_hook(o, c);
+    }
+}
+
+template <class Input, int BLOCK, int UNROLL>
 __global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsigned N, double Lx, double Ly, double Lz,
                                                                 int L_typeid, Partials part)
 {
@@ -288,33 +315,9 @@ __global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsign
     Accum acc;
     const unsigned full_tiles = N / TILE;
     const unsigned G = gridDim.x;
-    if (!PIPE)
-        accumulate_full_tiles<Input, BLOCK, UNROLL>(in, strided_tiles(N, G, blockIdx.x, TILE), Lx, Ly, Lz, L_typeid, acc,
-                                                    [](unsigned, int, double) {});
-    else
-    {
-        // ping-pong A/B so that no register copies are needed
-        TileRegs<Input, UNROLL> A, B;
-        unsigned t = blockIdx.x;
-        if (t < full_tiles)
-            tile_load<Input, BLOCK, UNROLL>(in, (size_t)t * TILE + threadIdx.x, A);
-        while (t < full_tiles)
-        {
-            if (t + G < full_tiles)
-                tile_load<Input, BLOCK, UNROLL>(in, (size_t)(t + G) * TILE + threadIdx.x, B);
-            __builtin_amdgcn_sched_barrier(0);
-            tile_accumulate<Input, BLOCK, UNROLL>(A, (size_t)t * TILE + threadIdx.x, Lx, Ly, Lz, L_typeid, acc);
-            t += G;
-            if (t >= full_tiles)
-                break;
-            if (t + G < full_tiles)
-                tile_load<Input, BLOCK, UNROLL>(in, (size_t)(t + G) * TILE + threadIdx.x, A);
-            __builtin_amdgcn_sched_barrier(0);
-            tile_accumulate<Input, BLOCK, UNROLL>(B, (size_t)t * TILE + threadIdx.x, Lx, Ly, Lz, L_typeid, acc);
-            t += G;
-        }
-    }
-    // ragged tail: one block takes it, bounds-checked
+    accumulate_full_tiles<Input, BLOCK, UNROLL>(in, strided_tiles(N, G, blockIdx.x, TILE), Lx, Ly, Lz, L_typeid, acc,
+                                                [](unsigned, int, double) {});
+    // ragged tail: one block takes it, bounds-checked (restates accumulate_ragged_tile: calling it moves instructions here)
     if (blockIdx.x == full_tiles % G)
     {
         const size_t base = (size_t)full_tiles * TILE + threadIdx.x;
@@ -614,8 +617,50 @@ struct MapScalars
     int photon, nL;
 };
 
-// Body shared by the three-launch and the fused force map.  Chunk k is 16 bytes: particle k>>1, half k&1.
-// Even chunk = (Fx, Fy) = ((-g c) Dq_x, (-g c) Dq_y), odd chunk = (Fz, w) = (0, 0); the photon's chunks carry F_L.
+// thread 0's Scalars -> LDS (s_m: 5 doubles, s_mi: 2 ints), and after the block's barrier every thread's MapScalars from there
+__device__ __forceinline__ void park_scalars(double* s_m, int* s_mi, const Scalars& sc)
+{
+    s_m[0] = sc.Dq[0]; s_m[1] = sc.Dq[1]; s_m[2] = sc.f[0]; s_m[3] = sc.f[1]; s_m[4] = sc.f[2];
+    s_mi[0] = sc.photon;
+    s_mi[1] = sc.nL;
+}
+__device__ __forceinline__ MapScalars map_scalars_from_lds(const double* s_m, const int* s_mi)
+{
+    MapScalars m;
+    m.Dqx = s_m[0]; m.Dqy = s_m[1]; m.Fx = s_m[2]; m.Fy = s_m[3]; m.Fz = s_m[4];
+    m.photon = s_mi[0];
+    m.nL = s_mi[1];
+    return m;
+}
+
+// The force-chunk rule.  Chunk k is 16 bytes: particle k >> 1, half k & 1 (`odd`); c is the particle's charge, ng = -g and
+// pchunk the photon's first chunk.  Even chunk = (Fx, Fy) = ((-g c) Dq_x, (-g c) Dq_y), odd chunk = (Fz, w) = (0, 0); the
+// photon's chunks carry F_L.  With several L-typed particles (degenerate) the reference gives a molecular force only to particles
+// whose type is not L (src/CavityForceCompute.cc:190-191): the sibling takes the particle's type tag.
+__device__ __forceinline__ v2d force_chunk(const MapScalars& m, double ng, double c, size_t k, bool odd, size_t pchunk)
+{
+    const v2d zero = {0.0, 0.0};
+    const double s = ng * c; // ((-g) * charge) * Dq, src/CavityForceCompute.cc:194
+    v2d v = {s * m.Dqx, s * m.Dqy};
+    v = odd ? zero : v;
+    if ((k | 1) == (pchunk | 1))
+        v = odd ? (v2d) {m.Fz, 0.0} : (v2d) {m.Fx, m.Fy};
+    return v;
+}
+__device__ __forceinline__ v2d force_chunk_typed(const MapScalars& m, double ng, double c, size_t k, bool odd, size_t pchunk,
+                                                 int tag, int L_typeid)
+{
+    const v2d zero = {0.0, 0.0};
+    const double s = ng * c;
+    v2d v = {s * m.Dqx, s * m.Dqy};
+    v = (odd || tag == L_typeid) ? zero : v;
+    if ((k | 1) == (pchunk | 1))
+        v = odd ? (v2d) {m.Fz, 0.0} : (v2d) {m.Fx, m.Fy};
+    return v;
+}
+
+// Body shared by the three-launch and the fused force map.  Its three chunk sites keep their own text of the rule above:
+// routed through force_chunk the compiler folds the photon test differently (profiles/single_launch_cleanup/README.md).
 // PRE: the caller has already loaded the charges of this block's first full tile into c_first (issued before its
 // prologue so that their latency is hidden behind it).
 template <int BLOCK, int UNROLL, int NT, bool PRE>
@@ -666,7 +711,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
             for (int u = 0; u < UNROLL; ++u)
             {
                 const size_t k = base + (size_t)u * BLOCK;
-                const double s = ng * c[u]; // ((-g) * charge) * Dq, src/CavityForceCompute.cc:194
+                const double s = ng * c[u]; // restates force_chunk (calling it changes this kernel's instructions)
                 v2d v = {s * m.Dqx, s * m.Dqy};
                 v = odd ? zero : v;
                 if ((k | 1) == (pchunk | 1))
@@ -683,7 +728,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
                 const size_t k = base + (size_t)u * BLOCK;
                 if (k < nchunks)
                 {
-                    const double s = ng * charge[k >> 1];
+                    const double s = ng * charge[k >> 1]; // restates force_chunk
                     v2d v = {s * m.Dqx, s * m.Dqy};
                     v = odd ? zero : v;
                     if ((k | 1) == (pchunk | 1))
@@ -701,7 +746,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
     {
         const size_t p = k >> 1;
         const int tag = __double2loint(pos2[2 * p + 1].y);
-        const double s = ng * charge[p];
+        const double s = ng * charge[p]; // restates force_chunk_typed
         v2d v = {s * m.Dqx, s * m.Dqy};
         v = (odd || tag == L_typeid) ? zero : v;
         if ((k | 1) == (pchunk | 1))
@@ -756,9 +801,7 @@ __global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(AosInput in,
     const Scalars sc = reduce_partials_and_finalize<AosInput, BLOCK>(in, N, nparts, Lx, Ly, Lz, prm, part, blockIdx.x == 0);
     if (threadIdx.x == 0)
     {
-        s_m[0] = sc.Dq[0]; s_m[1] = sc.Dq[1]; s_m[2] = sc.f[0]; s_m[3] = sc.f[1]; s_m[4] = sc.f[2];
-        s_mi[0] = sc.photon;
-        s_mi[1] = sc.nL;
+        park_scalars(s_m, s_mi, sc);
         if (blockIdx.x == 0)
         {
             write_result(res, sc, N, nparts, sequence);
@@ -766,10 +809,7 @@ __global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(AosInput in,
         }
     }
     __syncthreads();
-    MapScalars m;
-    m.Dqx = s_m[0]; m.Dqy = s_m[1]; m.Fx = s_m[2]; m.Fy = s_m[3]; m.Fz = s_m[4];
-    m.photon = s_mi[0];
-    m.nL = s_mi[1];
+    const MapScalars m = map_scalars_from_lds(s_m, s_mi);
     force_map_body<BLOCK, UNROLL, NT, true>(m, in.charge, in.pos2, N, prm.g, L_typeid, force2, c_first, reverse);
 }
 
@@ -876,9 +916,7 @@ __global__ __launch_bounds__(BLOCK) void force_map_strided_fused_kernel(StridedI
                                                                          blockIdx.x == 0);
     if (threadIdx.x == 0)
     {
-        s_m[0] = sc.Dq[0]; s_m[1] = sc.Dq[1]; s_m[2] = sc.f[0]; s_m[3] = sc.f[1]; s_m[4] = sc.f[2];
-        s_mi[0] = sc.photon;
-        s_mi[1] = sc.nL;
+        park_scalars(s_m, s_mi, sc);
         if (blockIdx.x == 0)
         {
             write_result(res, sc, N, nparts, sequence);
@@ -886,10 +924,7 @@ __global__ __launch_bounds__(BLOCK) void force_map_strided_fused_kernel(StridedI
         }
     }
     __syncthreads();
-    MapScalars m;
-    m.Dqx = s_m[0]; m.Dqy = s_m[1]; m.Fx = s_m[2]; m.Fy = s_m[3]; m.Fz = s_m[4];
-    m.photon = s_mi[0];
-    m.nL = s_mi[1];
+    const MapScalars m = map_scalars_from_lds(s_m, s_mi);
     force_map_strided_body<BLOCK, 4>(m, in, N, prm.g, L_typeid, force, force_stride, pe, pe_stride);
 }
 

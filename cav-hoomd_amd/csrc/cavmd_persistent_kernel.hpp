@@ -41,7 +41,7 @@
 
 #pragma clang fp contract(off)
 
-// Diagnostic hook (csrc/microbench.hip): per-block time stamps at numbered points of the kernel; nothing in the product.
+// Diagnostic hook (csrc/microbench_persistent.hip): per-block time stamps at numbered points of the kernel; nothing in the product.
 #ifndef CAVMD_PSTAMP
 #define CAVMD_PSTAMP(k)
 #endif
@@ -55,15 +55,14 @@ constexpr unsigned kRepairRounds = 4096; // the last block of a starved evaluati
 
 constexpr int kGroup = 16;           // blocks per first-level group = lanes of a DPP row
 constexpr unsigned kMaxPersistGrid = kGroup * kGroup;
-#ifndef CAVMD_GROUP_COPIES // (micro-benchmark sweeps only)
-#define CAVMD_GROUP_COPIES 8
-#endif
-#ifndef CAVMD_POLL_SLEEP
-#define CAVMD_POLL_SLEEP 1
-#endif
-constexpr unsigned kGroupCopies = CAVMD_GROUP_COPIES; // the group totals are published in 8 copies; block b polls copy b % 8, so a line of
+constexpr unsigned kGroupCopies = 8; // the group totals are published in 8 copies; block b polls copy b % 8, so a line of
                                      // group records has 32 pollers instead of 256 (a one-to-255 broadcast through one
                                      // line costs ~1 us more than through lines with 32 pollers: scripts/dev/pingpong.hip)
+constexpr int kPollSleep = 1;        // s_sleep argument between two poll rounds (copies and sleep swept in
+                                     // profiles/r03/handoff_knob_sweep.txt)
+// Measured and rejected, no longer in the tree (last present in commit 1906464; DESIGN.md 3.8 has one row each): the odd zero
+// chunks written during the hand-off (EARLYZ, profiles/r03/microbench_persistent_early_zero_chunks_*.txt), the hybrid
+// partition (profiles/r03/microbench_persistent_hybrid_partition_*.txt) and 512-thread blocks (profiles/r02/ab_block512.txt).
 
 struct SyncState
 {
@@ -177,8 +176,7 @@ __device__ __forceinline__ bool gather_records(const unsigned long long* slab, u
             break;
         if (spins >= max_rounds)
             return false;
-        if (CAVMD_POLL_SLEEP > 0)
-            __builtin_amdgcn_s_sleep(CAVMD_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(kPollSleep);
     }
 #pragma unroll
     for (int j = 0; j < ROUNDS; ++j)
@@ -204,30 +202,11 @@ struct BlockRange
     size_t first, step, tail_base;
     unsigned nfull, tail_count;
 };
-//   hybrid    (partition 2; MEASURED AND REJECTED in round 3, micro-benchmark only) the full rounds strided -- every block the
-//             same floor(full_tiles / G) tiles -- and what is left (fewer than G tiles' worth of particles) cut into G
-//             contiguous shares of whole 64-particle units, one ragged tile per block: equal work to within 64 particles AND
-//             the strided sweep for all but the last round.  20.5 vs 19.8 us at N = 1e6: the slowest block is not the one
-//             with a tile more (profiles/r03/microbench_persistent_hybrid_partition_*.txt).
 template <unsigned TILE>
 __device__ __forceinline__ BlockRange block_range(unsigned N, unsigned G, unsigned b, int balanced)
 {
     BlockRange r;
-    if (balanced == 2)
-    {
-        const unsigned rounds = (N / TILE) / G;
-        const size_t done = (size_t)rounds * G * TILE;
-        const unsigned long long U = ((unsigned long long)(N - done) + kWave - 1) / kWave;
-        const size_t s = done + (size_t)(U * b / G) * kWave;
-        size_t e = done + (size_t)(U * (b + 1) / G) * kWave;
-        e = e < N ? e : N;
-        r.first = (size_t)b * TILE;
-        r.step = (size_t)G * TILE;
-        r.nfull = rounds;
-        r.tail_base = s;
-        r.tail_count = (unsigned)(e > s ? e - s : 0);
-    }
-    else if (balanced)
+    if (balanced)
     {
         const unsigned long long U = ((unsigned long long)N + kWave - 1) / kWave;
         const size_t s = (size_t)(U * b / G) * kWave;
@@ -255,375 +234,283 @@ __device__ __forceinline__ BlockRange block_range(unsigned N, unsigned G, unsign
 
 extern __shared__ __attribute__((aligned(16))) double s_dyn_charge[];
 
-// EARLYZ (MEASURED AND REJECTED in round 3; instantiated by the micro-benchmark only, the library uses EARLYZ = 0): half of
-// every force entry -- the odd 16-byte chunk (F_z, w) = (0, 0) of every particle that is not the photon -- does not depend on
-// the total.  With EARLYZ waves 1..3 of a block write those chunks of the block's own tiles WHILE wave 0 runs the hand-off,
-// i.e. while the memory system would otherwise sit idle (~3-4 us per evaluation at N = 1e6), and phase 2 writes the even
-// chunks only (plus the photon's odd chunk, over the zero).  Result: 26.5 instead of 19.8 us at N = 1e6 (34.4 with
-// non-temporal early stores), slower at every size from 1e5 to 2e6 -- both passes store 16 bytes out of every 32, and the
-// memory side pays per line touched (profiles/r03/microbench_persistent_early_zero_chunks_*.txt).  Kept so that the table can
-// be reproduced (`CAVMD_TRY_EARLYZ=1 ./microbench_persistent`).
-template <int BLOCK, int UNROLL, int NT_STORE, bool FAULT = false, int EARLYZ = 0>
-__global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> in, unsigned N, double Lx, double Ly, double Lz,
-                                                                  DeviceParams prm, int L_typeid, SyncState st,
-                                                                  uint64_t sequence, cavmd_result* __restrict__ res,
-                                                                  HostResult* __restrict__ res_host,
-                                                                  v2d* __restrict__ force2, unsigned lds_slots, int balanced)
+// thread 0: park_scalars, plus whether the hand-off failed (s_mi: 3 ints here)
+__device__ __forceinline__ void park_scalars(double* s_m, int* s_mi, const Scalars& sc, bool ok)
 {
-    constexpr unsigned TILE = BLOCK * UNROLL; // particles per tile; the same tile is 2 * TILE force chunks
-    constexpr int MU = 2 * UNROLL;            // 16-byte chunk stores per thread and tile
-    __shared__ double s_m[5];
-    __shared__ int s_mi[3];
-    double* s_charge = s_dyn_charge;
-    const unsigned G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    park_scalars(s_m, s_mi, sc);
+    s_mi[2] = !ok;
+}
 
-    CAVMD_PSTAMP(0);
-    if constexpr (FAULT) // tests only: this block starts late, as if its CU had been held by another grid
-    {
-        if ((int)b == st.late_block)
-        {
-            const unsigned long long t0 = wall_clock64();
-            while (wall_clock64() - t0 < (unsigned long long)st.late_ticks)
-                __builtin_amdgcn_s_sleep(64);
-        }
-    }
-    // this evaluation's tag, and the speculative photon row (the driver appends the photon last)
-    const unsigned tag = __hip_atomic_load(st.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// ---- entry: what a block learns about its launch before it touches a particle ----------------------------------------------
+struct LaunchTag
+{
+    unsigned tag;   // this evaluation's tag: the epoch word
+    unsigned nonce; // this launch's own name, never 0
+    bool poisoned;  // an earlier evaluation could not be completed: this launch fails as a whole
+};
+__device__ __forceinline__ LaunchTag read_launch_tag(const SyncState& st, uint64_t sequence)
+{
+    LaunchTag lt;
+    lt.tag = __hip_atomic_load(st.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // The poison word holds the NONCE of the launch whose blocks raised it.  A nonce of another launch = an earlier evaluation
-    // that nobody could complete: this launch fails as a whole (see the end of the kernel).  This launch's own nonce = blocks of
-    // this very grid have given up while this one could not start: the bail path below, not a failure yet.
+    // that nobody could complete: this launch fails as a whole (give_up_and_maybe_repair).  This launch's own nonce = blocks of
+    // this very grid have given up while this one could not start: the bail path, not a failure yet.
     // The nonce: address of the launch's AQL dispatch packet (grid-uniform, an SGPR pair; consecutive dispatches of a queue --
     // replays of a captured graph included -- occupy different slots of its ring: 128 or 256 bytes apart on gfx950 / ROCm 7.2,
     // scripts/dev/dispatch_id_probe.hip) mixed with the host's sequence number; never 0.
-    const unsigned nonce = ((unsigned)((uintptr_t)__builtin_amdgcn_dispatch_ptr() >> 6) * 2654435761u
-                            ^ (unsigned)sequence * 40503u) | 1u;
+    lt.nonce = ((unsigned)((uintptr_t)__builtin_amdgcn_dispatch_ptr() >> 6) * 2654435761u ^ (unsigned)sequence * 40503u) | 1u;
     const unsigned poison = __hip_atomic_load(st.epoch + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool poisoned = poison != 0u && poison != nonce;
-    const PhotonRow guess = photon_row(in, (size_t)(N - 1));
+    lt.poisoned = poison != 0u && poison != lt.nonce;
+    return lt;
+}
 
-    // ---- phase 1: partial dipole of this block's tiles; the charges of its first lds_slots tiles are parked in LDS ---------
+// ---- phase 1: partial dipole of this block's tiles (every lane's share; the block tree follows); the charges of its first
+// lds_slots tiles are parked in LDS -------------------------------------------------------------------------------------------
+template <int BLOCK, int UNROLL>
+__device__ __forceinline__ Accum block_partial(const AosInputT<2>& in, const BlockRange& rg, double Lx, double Ly, double Lz,
+                                               int L_typeid, double* s_charge, unsigned lds_slots)
+{
+    constexpr unsigned TILE = BLOCK * UNROLL;
+    const unsigned tid = threadIdx.x;
     Accum acc;
-    const BlockRange rg = block_range<TILE>(N, G, b, balanced);
     accumulate_full_tiles<AosInputT<2>, BLOCK, UNROLL>(in, TileSchedule {rg.first, rg.step, rg.nfull}, Lx, Ly, Lz, L_typeid, acc,
                                                        [&](unsigned slot, int u, double c) {
                                                            if (slot < lds_slots)
                                                                s_charge[slot * TILE + u * BLOCK + tid] = c;
                                                        });
     if (rg.tail_count)
-    {
-        const size_t base = rg.tail_base + tid;
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u)
-        {
-            const unsigned o = u * BLOCK + tid;
-            double c = 0.0;
-            if (o < rg.tail_count)
-            {
-                const size_t i = base + (size_t)u * BLOCK;
-                const typename AosInputT<2>::Raw r = in.load(i);
-                const double rx = AosInputT<2>::x(r) + (double)r.ix * Lx;
-                const double ry = AosInputT<2>::y(r) + (double)r.iy * Ly;
-                const double rz = AosInputT<2>::z(r) + (double)r.iz * Lz;
-                acc.add((unsigned)i, rx, ry, rz, r.c, AosInputT<2>::tag(r), L_typeid);
-                c = r.c;
-            }
-            if (rg.nfull < lds_slots)
-                s_charge[rg.nfull * TILE + o] = c;
-        }
-    }
-    CAVMD_PSTAMP(1);
-    acc = block_reduce<BLOCK>(acc);
-    CAVMD_PSTAMP(2);
+        accumulate_ragged_tile<AosInputT<2>, BLOCK, UNROLL>(in, rg.tail_base, rg.tail_count, Lx, Ly, Lz, L_typeid, acc,
+                                                            [&](unsigned o, double c) {
+                                                                if (rg.nfull < lds_slots)
+                                                                    s_charge[rg.nfull * TILE + o] = c;
+                                                            });
+    return acc;
+}
 
-    // ---- hand-off: two-level all-reduce across the workgroups (wave 0; the other waves wait at the barrier below) ---------
-    __shared__ __attribute__((aligned(8))) unsigned s_words[kGroup * kGranulesPerRecord];
+// records -> total: lane l of wave 0 holds the l-th of <= 16 gathered records (identities beyond); their fixed fold, as
+// reduce_partials_and_finalize folds 16 consecutive partials
+__device__ __forceinline__ Accum fold_gathered(const Accum& o)
+{
+    Accum t;
+    t.merge(o);
+    return row_fold16(t);
+}
+
+// ---- hand-off: two-level all-reduce across the workgroups (wave 0; the other waves wait at the kernel's barrier) ------------
+// Publishes the block's partial `acc`, gathers and folds.  Gives the total and whether it is complete (wave-uniform); the
+// protocol is the one at the top of this file.  Gathering is not one function shared with the repair path: the normal second
+// level crosses workgroups (the leader publishes, everyone polls a copy), the repair's stays in one wave's LDS.
+struct HandOff
+{
+    Accum total;
+    bool ok;
+};
+template <bool FAULT>
+__device__ __forceinline__ HandOff hand_off(const SyncState& st, unsigned G, unsigned b, const LaunchTag& lt, const Accum& acc,
+                                            unsigned* s_words)
+{
+    const unsigned tag = lt.tag;
     unsigned long long* const block_slab = st.granules;
     unsigned long long* const group_slab = st.granules + (size_t)kMaxPersistGrid * kGranulesPerRecord;
-    if constexpr (EARLYZ != 0)
+    bool ok = !lt.poisoned;
+    bool silent = false;
+    if constexpr (FAULT) // tests only: this block never publishes, as if it were not resident
+        silent = ((int)b == st.silent_block);
+    if (!silent && !lt.poisoned)
+        publish_record(block_slab, kMaxPersistGrid, 1, b, tag, acc, s_words);
+    Accum o, t;
+    if (lt.poisoned)
     {
-        // waves 1 .. BLOCK/64 - 1: the (F_z, w) chunks of this block's tiles, tile by tile round-robin over those waves; a wave
-        // instruction stores 64 chunks 32 bytes apart (the odd halves of 2 KiB of force entries)
-        constexpr unsigned ZW = BLOCK / kWave - 1;
-        if (tid >= kWave)
+        // nothing is published, gathered or counted
+    }
+    else if (G <= (unsigned)kGroup)
+    {
+        // A grid of at most 16 blocks (N up to ~4000) is ONE group: every block gathers the block records itself, its own
+        // from registers -- one hop instead of two, and the same fold (the second level would only add zeros).
+        ok = gather_records(block_slab, 0, G, tag, s_words, o, st.spin_limit, (int)b, acc, st.epoch + 1);
+        CAVMD_PSTAMP(7);
+    }
+    else
+    {
+        if ((b & (kGroup - 1)) == 0)
         {
-            const unsigned w = tid / kWave - 1, lane = tid % kWave;
-            const v2d z = {0.0, 0.0};
-            for (unsigned slot = w; slot < rg.nfull; slot += ZW)
+            // Level 1: the first block of group b / 16 gathers the group's records (its own from registers), folds them
+            // and publishes the group total.  (Letting EVERY block take one look at its group on arrival, so that the
+            // last arriver folds without waiting to be seen, measured slower: 9.30 vs 9.15 us at N = 1e5, 19.9 vs 19.75 at
+            // 1e6 -- 240 extra gathers in flight when the last records land.)
+            const unsigned count = min(G - b, (unsigned)kGroup);
+            Accum o1, t1;
+            ok = gather_records(block_slab, b, count, tag, s_words, o1, st.spin_limit, 0, acc);
+            // (a group whose gather timed out publishes nothing: every block then times out on the group totals and
+            // the whole evaluation fails loudly, instead of a wrong total spreading with a valid tag)
+            if (ok)
             {
-                v2d* const f = force2 + 2 * (rg.first + (size_t)slot * rg.step) + 1;
+                t1.merge(o1); // restates fold_gathered (calling it here reorders the hand-off's instructions)
+                t1 = row_fold16(t1);
+                publish_record(group_slab, kGroup, kGroupCopies, b / kGroup, tag, t1, s_words);
+            }
+        }
+        CAVMD_PSTAMP(7);
+        ok = gather_records(group_slab + (size_t)(b % kGroupCopies) * kGroup * kGranulesPerRecord, 0,
+                            (G + kGroup - 1) / kGroup, tag, s_words, o, st.spin_limit, -1, acc, st.epoch + 1)
+             && ok;
+    }
+    t.merge(o); // restates fold_gathered
+    HandOff h;
+    h.total = row_fold16(t);
+    h.ok = ok;
+    CAVMD_PSTAMP(3);
+    return h;
+}
+
+// ---- the slow map, all from global memory: tiles t0, t0 + step, ...; NaN everywhere (poison), or the general rule -- no photon:
+// zeros (src/CavityForceCompute.cc:145-156); several L-typed particles: force_chunk_typed ---------------------------------------
+template <int BLOCK, int UNROLL, int NT_STORE>
+__device__ __forceinline__ void slow_map(const AosInputT<2>& in, unsigned N, double g, int L_typeid, v2d* __restrict__ force2,
+                                         unsigned t0, unsigned step, bool poison, const MapScalars& ms)
+{
+    constexpr unsigned TILE = BLOCK * UNROLL;
+    constexpr int MU = 2 * UNROLL;
+    const unsigned tid = threadIdx.x;
+    const size_t nchunks = 2 * (size_t)N;
+    const v2d zero = {0.0, 0.0};
+    const double nan = __builtin_nan("");
+    const double ng = -g;
+    const bool odd = tid & 1;
+    for (unsigned t = t0; (size_t)t * TILE < N; t += step)
+    {
 #pragma unroll
-                for (unsigned j = 0; j < TILE / kWave; ++j)
-                    store_chunk<(EARLYZ == 2 ? 1 : 0)>(f + 2 * (size_t)(j * kWave + lane), z);
-            }
-            if (rg.tail_count && w == rg.nfull % ZW)
+        for (int u = 0; u < MU; ++u)
+        {
+            const size_t k = (size_t)t * 2 * TILE + (size_t)u * BLOCK + tid;
+            if (k >= nchunks)
+                continue;
+            v2d v = zero;
+            if (poison)
+                v = (v2d) {nan, nan};
+            else if (ms.photon >= 0)
             {
-                v2d* const f = force2 + 2 * rg.tail_base + 1;
-                for (unsigned o = lane; o < rg.tail_count; o += kWave)
-                    store_chunk<(EARLYZ == 2 ? 1 : 0)>(f + 2 * (size_t)o, z);
+                const size_t p = k >> 1;
+                const int ptag = __double2loint(in.pos2[2 * p + 1].y);
+                v = force_chunk_typed(ms, ng, in.charge[p], k, odd, 2 * (size_t)ms.photon, ptag, L_typeid);
             }
+            store_chunk<NT_STORE>(force2 + k, v);
         }
     }
-    if (tid < kWave)
+}
+
+// ---- the bail path: this block gave up waiting, because some block of the grid was not resident (other grids hold the CUs) --
+// Loud by default: NaN over the block's own tiles and the failure flag.  Then the block LEAVES, which frees its CU for
+// the blocks that have not started.  Those find no group totals (the group leaders have left), give up in turn -- and
+// the last one to do so, which knows from the count that every block has published its record, completes the whole
+// evaluation alone: same records, same fold, same bits; a millisecond instead of microseconds, once, after which the
+// host keeps this workspace on two launches.  If some blocks did get the total while others gave up (a race of
+// microseconds after a wait of a third of a second), the count never completes and the evaluation stays failed.
+template <int BLOCK, int UNROLL, int NT_STORE>
+__device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<2>& in, unsigned N, double Lx, double Ly, double Lz,
+                                                         const DeviceParams& prm, int L_typeid, const SyncState& st,
+                                                         uint64_t sequence, cavmd_result* __restrict__ res,
+                                                         HostResult* __restrict__ res_host, v2d* __restrict__ force2,
+                                                         const LaunchTag& lt, const Accum& acc, const PhotonRow& guess,
+                                                         const MapScalars& m, double* s_m, int* s_mi, unsigned* s_words)
+{
+    const unsigned G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    const unsigned tag = lt.tag;
+    unsigned long long* const block_slab = st.granules;
+    __shared__ unsigned s_last;
+    slow_map<BLOCK, UNROLL, NT_STORE>(in, N, prm.g, L_typeid, force2, b, G, true, m);
+    __threadfence();
+    __syncthreads();
+    if (tid == 0)
     {
-        bool ok = !poisoned;
-        bool silent = false;
-#ifdef CAVMD_FAULT_SILENT_BLOCK // microbench only: this block never publishes, as if it were not resident
-        silent = (b == CAVMD_FAULT_SILENT_BLOCK);
-#endif
-        if constexpr (FAULT)
-            silent = silent || ((int)b == st.silent_block);
-        if (!silent && !poisoned)
-            publish_record(block_slab, kMaxPersistGrid, 1, b, tag, acc, s_words);
-        Accum o, t;
-        if (poisoned)
-        {
-            // nothing is published, gathered or counted
-        }
-        else if (G <= (unsigned)kGroup)
-        {
-            // A grid of at most 16 blocks (N up to ~4000) is ONE group: every block gathers the block records itself, its own
-            // from registers -- one hop instead of two, and the same fold (the second level would only add zeros).
-            ok = gather_records(block_slab, 0, G, tag, s_words, o, st.spin_limit, (int)b, acc, st.epoch + 1);
-            CAVMD_PSTAMP(7);
-        }
+        __hip_atomic_store(st.sync_error, kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // this evaluation's own slot says so too, tagged with its sequence (a repair below publishes the result over it)
+        __hip_atomic_store(&res_host->failed, (sequence << 2) | kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (lt.poisoned)
+            s_last = 0u; // a launch behind an evaluation nobody could complete: fail as a whole, touch nothing
         else
         {
-            if ((b & (kGroup - 1)) == 0)
-            {
-                // Level 1: the first block of group b / 16 gathers the group's records (its own from registers), folds them
-                // and publishes the group total.  (Letting EVERY block take one look at its group on arrival, so that the
-                // last arriver folds without waiting to be seen, measured slower: 9.30 vs 9.15 us at N = 1e5, 19.9 vs 19.75 at
-                // 1e6 -- 240 extra gathers in flight when the last records land.)
-                const unsigned count = min(G - b, (unsigned)kGroup);
-                Accum o1, t1;
-                ok = gather_records(block_slab, b, count, tag, s_words, o1, st.spin_limit, 0, acc);
-                // (a group whose gather timed out publishes nothing: every block then times out on the group totals and
-                // the whole evaluation fails loudly, instead of a wrong total spreading with a valid tag)
-                if (ok)
-                {
-                    t1.merge(o1);
-                    t1 = row_fold16(t1);
-                    publish_record(group_slab, kGroup, kGroupCopies, b / kGroup, tag, t1, s_words);
-                }
-            }
-            CAVMD_PSTAMP(7);
-            ok = gather_records(group_slab + (size_t)(b % kGroupCopies) * kGroup * kGranulesPerRecord, 0,
-                                (G + kGroup - 1) / kGroup, tag, s_words, o, st.spin_limit, -1, acc, st.epoch + 1)
-                 && ok;
+            // poison first (the counting atomic below orders it): it stays unless ALL blocks end up counted here, i.e.
+            // unless the last of them can put records, count and epoch back in order
+            __hip_atomic_store(st.epoch + 2, lt.nonce, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = __hip_atomic_fetch_add(st.epoch + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == G - 1;
         }
-        t.merge(o);
-        const Accum tot = row_fold16(t);
-        CAVMD_PSTAMP(3);
-        // The block that publishes cavmd_result (a system-scope release: ~0.6 us before its force stores can start) is the
-        // LAST block: it holds the fewest tiles (the ragged tail, or one tile less than the first blocks), so the detour is
-        // taken from its slack instead of from the kernel's critical path.
-        const bool publisher = (b == G - 1);
-        const Scalars sc = scalars_from_total<AosInputT<2>>(tot, guess, in, N, Lx, Ly, Lz, prm, publisher);
+    }
+    __syncthreads();
+    if (!s_last)
+        return;
+    __shared__ __attribute__((aligned(8))) unsigned s_groups[kGroup * kGranulesPerRecord];
+    if (tid < kWave)
+    {
+        bool ok = true;
+        Accum o;
+        if (G <= (unsigned)kGroup)
+            ok = gather_records(block_slab, 0, G, tag, s_words, o, kRepairRounds, -1, acc);
+        else
+        {
+            const unsigned ngroups = (G + kGroup - 1) / kGroup;
+            for (unsigned g = 0; g < ngroups; ++g)
+            {
+                Accum o1;
+                ok = gather_records(block_slab, g * kGroup, min(G - g * kGroup, (unsigned)kGroup), tag, s_words, o1,
+                                    kRepairRounds, -1, acc)
+                     && ok;
+                const Accum t1 = fold_gathered(o1);
+                if (tid == 0)
+                    record_to_lds(s_groups + g * kGranulesPerRecord, t1);
+            }
+            // same wave: LDS operations complete in order, no barrier needed
+            if (tid < ngroups)
+                record_from_lds(s_groups + tid * kGranulesPerRecord, o);
+        }
+        const Accum tot = fold_gathered(o);
+        const Scalars sc = scalars_from_total<AosInputT<2>>(tot, guess, in, N, Lx, Ly, Lz, prm, true);
         if (tid == 0)
         {
-            s_m[0] = sc.Dq[0]; s_m[1] = sc.Dq[1]; s_m[2] = sc.f[0]; s_m[3] = sc.f[1]; s_m[4] = sc.f[2];
-            s_mi[0] = sc.photon;
-            s_mi[1] = sc.nL;
-            s_mi[2] = !ok;
-            if (publisher && ok)
+            park_scalars(s_m, s_mi, sc, ok);
+            if (ok)
             {
-                // every block has published, hence read the epoch: advance it for the next launch (0 is never a tag)
-                __hip_atomic_store(st.epoch, tag + 1u ? tag + 1u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                // the verdict first, the result's ready flag (a release) after it: a host that sees the result sees "repaired"
+                __hip_atomic_store(st.sync_error, kSyncRepaired, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 write_result(res, sc, N, G, sequence);
                 publish_to_host(res_host, sc, N, G, sequence);
             }
         }
     }
-    CAVMD_PSTAMP(4);
     __syncthreads();
-    CAVMD_PSTAMP(5);
-    MapScalars m;
-    m.Dqx = s_m[0]; m.Dqy = s_m[1]; m.Fx = s_m[2]; m.Fy = s_m[3]; m.Fz = s_m[4];
-    m.photon = s_mi[0];
-    m.nL = s_mi[1];
-    const bool bad = s_mi[2];
-
-    // ---- phase 2: forces of this block's own tiles, charges from LDS ------------------------------------------------------
-    const size_t nchunks = 2 * (size_t)N;
-    const v2d zero = {0.0, 0.0};
-    // The slow map, all from global memory: tiles t0, t0 + step, ...; NaN everywhere (poison), or the general rule -- no photon:
-    // zeros (src/CavityForceCompute.cc:145-156); several L-typed particles: the type tag has to be read, only non-L particles
-    // get a molecular force (:190-191).
-    auto slow_map = [&](unsigned t0, unsigned step, bool poison, const MapScalars& ms) {
-        const double nan = __builtin_nan("");
-        const double ng = -prm.g;
-        const bool odd = tid & 1;
-        for (unsigned t = t0; (size_t)t * TILE < N; t += step)
-        {
-#pragma unroll
-            for (int u = 0; u < MU; ++u)
-            {
-                const size_t k = (size_t)t * 2 * TILE + (size_t)u * BLOCK + tid;
-                if (k >= nchunks)
-                    continue;
-                v2d v = zero;
-                if (poison)
-                    v = (v2d) {nan, nan};
-                else if (ms.photon >= 0)
-                {
-                    const size_t p = k >> 1;
-                    const int ptag = __double2loint(in.pos2[2 * p + 1].y);
-                    const double s = ng * in.charge[p];
-                    v = (v2d) {s * ms.Dqx, s * ms.Dqy};
-                    v = (odd || ptag == L_typeid) ? zero : v;
-                    if (p == (size_t)ms.photon)
-                        v = odd ? (v2d) {ms.Fz, 0.0} : (v2d) {ms.Fx, ms.Fy};
-                }
-                store_chunk<NT_STORE>(force2 + k, v);
-            }
-        }
-    };
-    if (bad)
+    const MapScalars mr = map_scalars_from_lds(s_m, s_mi);
+    if (!s_mi[2]) // over the other blocks' NaN: their stores were fenced before they were counted
+        slow_map<BLOCK, UNROLL, NT_STORE>(in, N, prm.g, L_typeid, force2, 0, 1, false, mr);
+    if (tid == 0)
     {
-        // ---- this block gave up waiting: some block of the grid was not resident (other grids hold the CUs) -----------------
-        // Loud by default: NaN over the block's own tiles and the failure flag.  Then the block LEAVES, which frees its CU for
-        // the blocks that have not started.  Those find no group totals (the group leaders have left), give up in turn -- and
-        // the last one to do so, which knows from the count that every block has published its record, completes the whole
-        // evaluation alone: same records, same fold, same bits; a millisecond instead of microseconds, once, after which the
-        // host keeps this workspace on two launches.  If some blocks did get the total while others gave up (a race of
-        // microseconds after a wait of a third of a second), the count never completes and the evaluation stays failed.
-        __shared__ unsigned s_last;
-        slow_map(b, G, true, m);
-        __threadfence();
-        __syncthreads();
-        if (tid == 0)
-        {
-            __hip_atomic_store(st.sync_error, kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            // this evaluation's own slot says so too, tagged with its sequence (a repair below publishes the result over it)
-            __hip_atomic_store(&res_host->failed, (sequence << 2) | kSyncFailed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (poisoned)
-                s_last = 0u; // a launch behind an evaluation nobody could complete: fail as a whole, touch nothing
-            else
-            {
-                // poison first (the counting atomic below orders it): it stays unless ALL blocks end up counted here, i.e.
-                // unless the last of them can put records, count and epoch back in order
-                __hip_atomic_store(st.epoch + 2, nonce, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                s_last = __hip_atomic_fetch_add(st.epoch + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == G - 1;
-            }
-        }
-        __syncthreads();
-        if (!s_last)
-            return;
-        __shared__ __attribute__((aligned(8))) unsigned s_groups[kGroup * kGranulesPerRecord];
-        if (tid < kWave)
-        {
-            bool ok = true;
-            Accum o, t;
-            if (G <= (unsigned)kGroup)
-                ok = gather_records(block_slab, 0, G, tag, s_words, o, kRepairRounds, -1, acc);
-            else
-            {
-                const unsigned ngroups = (G + kGroup - 1) / kGroup;
-                for (unsigned g = 0; g < ngroups; ++g)
-                {
-                    Accum o1, t1;
-                    ok = gather_records(block_slab, g * kGroup, min(G - g * kGroup, (unsigned)kGroup), tag, s_words, o1,
-                                        kRepairRounds, -1, acc)
-                         && ok;
-                    t1.merge(o1);
-                    t1 = row_fold16(t1);
-                    if (tid == 0)
-                        record_to_lds(s_groups + g * kGranulesPerRecord, t1);
-                }
-                // same wave: LDS operations complete in order, no barrier needed
-                if (tid < ngroups)
-                    record_from_lds(s_groups + tid * kGranulesPerRecord, o);
-            }
-            t.merge(o);
-            const Accum tot = row_fold16(t);
-            const Scalars sc = scalars_from_total<AosInputT<2>>(tot, guess, in, N, Lx, Ly, Lz, prm, true);
-            if (tid == 0)
-            {
-                s_m[0] = sc.Dq[0]; s_m[1] = sc.Dq[1]; s_m[2] = sc.f[0]; s_m[3] = sc.f[1]; s_m[4] = sc.f[2];
-                s_mi[0] = sc.photon;
-                s_mi[1] = sc.nL;
-                s_mi[2] = !ok;
-                if (ok)
-                {
-                    // the verdict first, the result's ready flag (a release) after it: a host that sees the result sees "repaired"
-                    __hip_atomic_store(st.sync_error, kSyncRepaired, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    write_result(res, sc, N, G, sequence);
-                    publish_to_host(res_host, sc, N, G, sequence);
-                }
-            }
-        }
-        __syncthreads();
-        MapScalars mr;
-        mr.Dqx = s_m[0]; mr.Dqy = s_m[1]; mr.Fx = s_m[2]; mr.Fy = s_m[3]; mr.Fz = s_m[4];
-        mr.photon = s_mi[0];
-        mr.nL = s_mi[1];
-        if (!s_mi[2])
-            slow_map(0, 1, false, mr); // over the other blocks' NaN: their stores were fenced before they were counted
-        if (tid == 0)
-        {
-            // every block has read the epoch and been counted, none is left in the hand-off: count, epoch and poison are put
-            // back in order for the next evaluation (whether or not THIS one could be completed: that is the starvation flag's to say)
-            __hip_atomic_store(st.epoch + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(st.epoch, tag + 1u ? tag + 1u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(st.epoch + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
+        // every block has read the epoch and been counted, none is left in the hand-off: count, epoch and poison are put
+        // back in order for the next evaluation (whether or not THIS one could be completed: that is the starvation flag's to say)
+        __hip_atomic_store(st.epoch + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(st.epoch, tag + 1u ? tag + 1u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(st.epoch + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (m.photon < 0 || m.nL > 1)
-    {
-        slow_map(b, G, false, m); // rare, from global memory
-        return;
-    }
+}
 
-    const double ng = -prm.g;
+// ---- phase 2: forces of this block's own tiles, charges from LDS: the resident tiles, the tiles beyond the LDS budget and the
+// ragged tile; every chunk by force_chunk (one photon exactly: the caller has sent the other cases to slow_map) ----------------
+template <int BLOCK, int UNROLL, int NT_STORE>
+__device__ __forceinline__ void map_own_tiles(const AosInputT<2>& in, const BlockRange& rg, const MapScalars& m, double g,
+                                              v2d* __restrict__ force2, const double* s_charge, unsigned lds_slots)
+{
+    constexpr unsigned TILE = BLOCK * UNROLL;
+    constexpr int MU = 2 * UNROLL; // 16-byte chunk stores per thread and tile
+    const unsigned tid = threadIdx.x;
+    const double ng = -g;
     const size_t pchunk = 2 * (size_t)m.photon; // photon's first chunk
-    if constexpr (EARLYZ != 0)
-    {
-        // the even chunks only: lane = particle, charges straight from LDS (or re-read beyond the LDS budget); the photon's
-        // lane also writes its odd chunk (F_z, 0) over the zero of the early pass (same workgroup, after the barrier above)
-        auto put = [&](size_t p, double c) {
-            const double s = ng * c;
-            v2d v = {s * m.Dqx, s * m.Dqy};
-            if (p == (size_t)m.photon)
-            {
-                v = (v2d) {m.Fx, m.Fy};
-                store_chunk<NT_STORE>(force2 + 2 * p + 1, (v2d) {m.Fz, 0.0});
-            }
-            store_chunk<NT_STORE>(force2 + 2 * p, v);
-        };
-        for (unsigned slot = 0; slot < rg.nfull; ++slot)
-        {
-            const size_t p0 = rg.first + (size_t)slot * rg.step + tid;
-            double c[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-                c[u] = slot < lds_slots ? s_charge[slot * TILE + u * BLOCK + tid]
-                                        : __builtin_nontemporal_load(in.charge + p0 + (size_t)u * BLOCK);
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-                put(p0 + (size_t)u * BLOCK, c[u]);
-        }
-        if (rg.tail_count)
-        {
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-            {
-                const unsigned o = u * BLOCK + tid;
-                if (o < rg.tail_count)
-                    put(rg.tail_base + o, rg.nfull < lds_slots ? s_charge[rg.nfull * TILE + o] : in.charge[rg.tail_base + o]);
-            }
-        }
-        CAVMD_PSTAMP(6);
-        return;
-    }
     const bool odd = tid & 1;                   // BLOCK is even, so the half is fixed per thread
+    const v2d zero = {0.0, 0.0};
     auto store_tile = [&](unsigned slot, const double (&c)[MU]) {
         const size_t base = 2 * (rg.first + (size_t)slot * rg.step) + tid;
 #pragma unroll
         for (int u = 0; u < MU; ++u)
         {
             const size_t k = base + (size_t)u * BLOCK;
-            const double s = ng * c[u]; // ((-g) * charge) * Dq, src/CavityForceCompute.cc:194
+            const double s = ng * c[u]; // restates force_chunk (calling it here costs the UNROLL = 1 kernels 2 VGPRs)
             v2d v = {s * m.Dqx, s * m.Dqy};
             v = odd ? zero : v;
             if ((k | 1) == (pchunk | 1))
@@ -687,15 +574,85 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
             {
                 const size_t k = base + (size_t)u * BLOCK;
                 const double cc = rg.nfull < lds_slots ? s_charge[rg.nfull * TILE + o] : in.charge[rg.tail_base + o];
-                const double s = ng * cc;
-                v2d v = {s * m.Dqx, s * m.Dqy};
-                v = odd ? zero : v;
-                if ((k | 1) == (pchunk | 1))
-                    v = odd ? (v2d) {m.Fz, 0.0} : (v2d) {m.Fx, m.Fy};
-                store_chunk<NT_STORE>(force2 + k, v);
+                store_chunk<NT_STORE>(force2 + k, force_chunk(m, ng, cc, k, odd, pchunk));
             }
         }
     }
+}
+
+// ---- the kernel: entry, phase 1, hand-off, scalars through LDS, then the bail path, the slow map or phase 2 -------------------
+template <int BLOCK, int UNROLL, int NT_STORE, bool FAULT = false>
+__global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> in, unsigned N, double Lx, double Ly, double Lz,
+                                                                  DeviceParams prm, int L_typeid, SyncState st,
+                                                                  uint64_t sequence, cavmd_result* __restrict__ res,
+                                                                  HostResult* __restrict__ res_host,
+                                                                  v2d* __restrict__ force2, unsigned lds_slots, int balanced)
+{
+    constexpr unsigned TILE = BLOCK * UNROLL; // particles per tile; the same tile is 2 * TILE force chunks
+    __shared__ double s_m[5];
+    __shared__ int s_mi[3];
+    double* s_charge = s_dyn_charge;
+    const unsigned G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+
+    CAVMD_PSTAMP(0);
+    if constexpr (FAULT) // tests only: this block starts late, as if its CU had been held by another grid
+    {
+        if ((int)b == st.late_block)
+        {
+            const unsigned long long t0 = wall_clock64();
+            while (wall_clock64() - t0 < (unsigned long long)st.late_ticks)
+                __builtin_amdgcn_s_sleep(64);
+        }
+    }
+    // this evaluation's tag, and the speculative photon row (the driver appends the photon last)
+    const LaunchTag lt = read_launch_tag(st, sequence);
+    const PhotonRow guess = photon_row(in, (size_t)(N - 1));
+
+    const BlockRange rg = block_range<TILE>(N, G, b, balanced);
+    Accum acc = block_partial<BLOCK, UNROLL>(in, rg, Lx, Ly, Lz, L_typeid, s_charge, lds_slots);
+    CAVMD_PSTAMP(1);
+    acc = block_reduce<BLOCK>(acc);
+    CAVMD_PSTAMP(2);
+
+    __shared__ __attribute__((aligned(8))) unsigned s_words[kGroup * kGranulesPerRecord];
+    if (tid < kWave)
+    {
+        const HandOff h = hand_off<FAULT>(st, G, b, lt, acc, s_words);
+        // The block that publishes cavmd_result (a system-scope release: ~0.6 us before its force stores can start) is the
+        // LAST block: it holds the fewest tiles (the ragged tail, or one tile less than the first blocks), so the detour is
+        // taken from its slack instead of from the kernel's critical path.
+        const bool publisher = (b == G - 1);
+        const Scalars sc = scalars_from_total<AosInputT<2>>(h.total, guess, in, N, Lx, Ly, Lz, prm, publisher);
+        if (tid == 0)
+        {
+            park_scalars(s_m, s_mi, sc, h.ok);
+            if (publisher && h.ok)
+            {
+                // every block has published, hence read the epoch: advance it for the next launch (0 is never a tag)
+                __hip_atomic_store(st.epoch, lt.tag + 1u ? lt.tag + 1u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                write_result(res, sc, N, G, sequence);
+                publish_to_host(res_host, sc, N, G, sequence);
+            }
+        }
+    }
+    CAVMD_PSTAMP(4);
+    __syncthreads();
+    CAVMD_PSTAMP(5);
+    const MapScalars m = map_scalars_from_lds(s_m, s_mi);
+    const bool bad = s_mi[2];
+
+    if (bad)
+    {
+        give_up_and_maybe_repair<BLOCK, UNROLL, NT_STORE>(in, N, Lx, Ly, Lz, prm, L_typeid, st, sequence, res, res_host, force2, lt,
+                                                          acc, guess, m, s_m, s_mi, s_words);
+        return;
+    }
+    if (m.photon < 0 || m.nL > 1)
+    {
+        slow_map<BLOCK, UNROLL, NT_STORE>(in, N, prm.g, L_typeid, force2, b, G, false, m); // rare, from global memory
+        return;
+    }
+    map_own_tiles<BLOCK, UNROLL, NT_STORE>(in, rg, m, prm.g, force2, s_charge, lds_slots);
     CAVMD_PSTAMP(6);
 }
 

@@ -206,27 +206,20 @@ int main(int argc, char** argv)
 
     std::vector<Variant> V;
     const double B1 = 52.0 * N, B2 = 40.0 * N;
-#define K1(NAME, BLOCK, UNROLL, PIPE, NTL, BPC)                                                                         \
+#define K1(NAME, BLOCK, UNROLL, NTL, BPC)                                                                               \
     V.push_back({NAME, B1, [&](int f) {                                                                                 \
                      const unsigned g1 = grid(N, BLOCK * UNROLL, BPC);                                                  \
                      if (NTL == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, BLOCK, UNROLL, PIPE>), dim3(g1), dim3(BLOCK), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
                      else if (NTL == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, BLOCK, UNROLL, PIPE>), dim3(g1), dim3(BLOCK), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, BLOCK, UNROLL, PIPE>), dim3(g1), dim3(BLOCK), 0, st, in_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_of(f), n, L, L, L, 2, part); \
                  }, {}})
-    K1("K1 simple nt2 bpc1", 256, 4, false, 2, 1);
-    K1("K1 simple nt2 bpc2", 256, 4, false, 2, 2);
-    K1("K1 simple nt2 bpc4", 256, 4, false, 2, 4);
-    K1("K1 simple nt2 bpc8", 256, 4, false, 2, 8);
-    K1("K1 dbuf   nt2 bpc1", 256, 4, true, 2, 1);
-    K1("K1 dbuf   nt2 bpc2", 256, 4, true, 2, 2);
-    K1("K1 dbuf   nt1 bpc1", 256, 4, true, 1, 1);
-    K1("K1 dbuf   nt1 bpc2", 256, 4, true, 1, 2);
-    K1("K1 dbuf u2 nt2 bpc2", 256, 2, true, 2, 2);
-    K1("K1 dbuf u2 nt2 bpc4", 256, 2, true, 2, 4);
-    K1("K1 dbuf b512 u2 nt2 bpc1", 512, 2, true, 2, 1);
+    K1("K1 simple nt2 bpc1", 256, 4, 2, 1);
+    K1("K1 simple nt2 bpc2", 256, 4, 2, 2);
+    K1("K1 simple nt2 bpc4", 256, 4, 2, 4);
+    K1("K1 simple nt2 bpc8", 256, 4, 2, 8);
     V.push_back({"READ ceiling (3 streams, same shapes) b256 u4 bpc8", B1, [&](int f) {
                      hipLaunchKernelGGL((read_ceiling_kernel<256, 4>), dim3(grid(N, 1024, 8)), dim3(256), 0, st, in_of(f), n, d_sink); }, {}});
     V.push_back({"READ flat 16B pos-array only b256 u4 bpc8", 32.0 * N, [&](int f) {
@@ -266,44 +259,44 @@ int main(int argc, char** argv)
     // ---- whole evaluations: reduce -> finalize -> map on the same frame, as cavmd_compute_hoomd enqueues them ----
     const double B = 92.0 * N;
     DeviceParams P; P.g = 1e-3; P.K = 0.0091 * 0.0091; P.gK = P.g / P.K; P.g2K = P.g * P.g / P.K;
-#define SEQ3(NAME, KB, KU, KP, KNT, KBPC, MB, MU, MNT, MBPC)                                                                \
+#define SEQ3(NAME, KB, KU, KNT, KBPC, MB, MU, MNT, MBPC)                                                                    \
     V.push_back({NAME, B, [&](int f) {                                                                                  \
                      const unsigned g1 = grid(N, KB * KU, KBPC);                                                        \
                      if (KNT == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
                      else if (KNT == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
                      hipLaunchKernelGGL((finalize_kernel<AosInput, 256>), dim3(1), dim3(256), 0, st, in_of(f), n, g1, L, L, L, P, part, 1ull, d_res, d_hres); \
                      hipLaunchKernelGGL((force_map_aos_kernel<MB, MU, MNT>), dim3(grid(2 * N, MB * MU, MBPC)), dim3(MB), 0, st, d_chg[f], (const v2d*)d_pos[f], n, 1e-3, 2, d_res, (v2d*)d_frc[f]); \
                  }, {}})
-#define SEQ2(NAME, KB, KU, KP, KNT, KBPC, MB, MU, MNT, MBPC)                                                                \
+#define SEQ2(NAME, KB, KU, KNT, KBPC, MB, MU, MNT, MBPC)                                                                    \
     V.push_back({NAME, B, [&](int f) {                                                                                  \
                      const unsigned g1 = grid(N, KB * KU, KBPC);                                                        \
                      if (KNT == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
                      else if (KNT == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU, KP>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
                      hipLaunchKernelGGL((force_map_aos_fused_kernel<MB, MU, MNT>), dim3(grid(2 * N, MB * MU, MBPC)), dim3(MB), 0, st, in_of(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false); \
                  }, {}})
     // NT = charge-load policy of the reduction (1 below 5e6 particles, 2 above), stores non-temporal
 #define SWEEP(NT)                                                                                                   \
-    SEQ2("SEQ2 prev: K1 u4 bpc1 | fused u4 bpc2 nts", 256, 4, false, NT, 1, 256, 4, true, 2);                       \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused u4 bpc2 nts", 256, 2, false, NT, 1, 256, 4, true, 2);                             \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc2 nts", 256, 2, false, NT, 1, 256, 8, true, 2);                             \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc3 nts", 256, 2, false, NT, 1, 256, 8, true, 3);                             \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc1 nts", 256, 2, false, NT, 1, 256, 8, true, 1);                             \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused u4 bpc3 nts", 256, 2, false, NT, 1, 256, 4, true, 3);                             \
-    SEQ2("SEQ2 K1 u1 bpc1 | fused u4 bpc2 nts", 256, 1, false, NT, 1, 256, 4, true, 2);                             \
-    SEQ2("SEQ2 K1 u1 bpc1 | fused u8 bpc2 nts", 256, 1, false, NT, 1, 256, 8, true, 2);                             \
-    SEQ2("SEQ2 K1 u1 bpc2 | fused u8 bpc2 nts", 256, 1, false, NT, 2, 256, 8, true, 2);                             \
-    SEQ2("SEQ2 K1 b512 u2 bpc1 | fused u8 bpc2 nts", 512, 2, false, NT, 1, 256, 8, true, 2);                        \
-    SEQ2("SEQ2 K1 b512 u1 bpc1 | fused u8 bpc2 nts", 512, 1, false, NT, 1, 256, 8, true, 2);                        \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused b512 u4 bpc1 nts", 256, 2, false, NT, 1, 512, 4, true, 1);                        \
-    SEQ2("SEQ2 K1 u2 bpc1 | fused b512 u8 bpc1 nts", 256, 2, false, NT, 1, 512, 8, true, 1);
+    SEQ2("SEQ2 prev: K1 u4 bpc1 | fused u4 bpc2 nts", 256, 4, NT, 1, 256, 4, true, 2);                              \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused u4 bpc2 nts", 256, 2, NT, 1, 256, 4, true, 2);                                    \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc2 nts", 256, 2, NT, 1, 256, 8, true, 2);                                    \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc3 nts", 256, 2, NT, 1, 256, 8, true, 3);                                    \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused u8 bpc1 nts", 256, 2, NT, 1, 256, 8, true, 1);                                    \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused u4 bpc3 nts", 256, 2, NT, 1, 256, 4, true, 3);                                    \
+    SEQ2("SEQ2 K1 u1 bpc1 | fused u4 bpc2 nts", 256, 1, NT, 1, 256, 4, true, 2);                                    \
+    SEQ2("SEQ2 K1 u1 bpc1 | fused u8 bpc2 nts", 256, 1, NT, 1, 256, 8, true, 2);                                    \
+    SEQ2("SEQ2 K1 u1 bpc2 | fused u8 bpc2 nts", 256, 1, NT, 2, 256, 8, true, 2);                                    \
+    SEQ2("SEQ2 K1 b512 u2 bpc1 | fused u8 bpc2 nts", 512, 2, NT, 1, 256, 8, true, 2);                               \
+    SEQ2("SEQ2 K1 b512 u1 bpc1 | fused u8 bpc2 nts", 512, 1, NT, 1, 256, 8, true, 2);                               \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused b512 u4 bpc1 nts", 256, 2, NT, 1, 512, 4, true, 1);                               \
+    SEQ2("SEQ2 K1 u2 bpc1 | fused b512 u8 bpc1 nts", 256, 2, NT, 1, 512, 8, true, 1);
     if (N <= 5000000) { SWEEP(1) } else { SWEEP(2) }
 
     // a valid result block for K2 (and initialised partials for finalize)

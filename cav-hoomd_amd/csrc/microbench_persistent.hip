@@ -135,134 +135,37 @@ int main(int argc, char** argv)
     while (unroll > 1 && N / ((size_t)256 * unroll) < (size_t)CU * 5 / 4)
         unroll >>= 1;
     const bool nts = N >= 200000;
-#define ALLOW1(UNR, NTS, EZ) CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, UNR, NTS, false, EZ>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
-#define ALLOW(UNR, NTS) do { ALLOW1(UNR, NTS, 0); ALLOW1(UNR, NTS, 1); ALLOW1(UNR, NTS, 2); } while (0)
+#define ALLOW(UNR, NTS) CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, UNR, NTS>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
     ALLOW(1, false); ALLOW(1, true); ALLOW(2, false); ALLOW(2, true);
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<512, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<512, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
 
-#if defined(CAVMD_FAULT_SILENT_BLOCK) || defined(CAVMD_FAULT_LATE_BLOCK)
-    {
-        // Fault injection, one launch.
-        //   silent block: a block never publishes its record.  Expected: every block gives up after its bounded wait, the last
-        //     one cannot complete the evaluation either (a record is missing): the kernel ends, sync_error = 1 (failed), no
-        //     result published, every force entry NaN.
-        //   late block: a block starts after all the others have given up (as if its CU had been held by another grid).
-        //     Expected: it gives up in turn, is the last to do so and completes the whole evaluation alone: sync_error = 2
-        //     (repaired), result published, forces and dipole bit for bit those of the two-launch path.
-        std::vector<double> h_f(4 * N, 0.0), h_want(4 * N, 0.0);
-        const unsigned g1 = grid(N, 256 * unroll, 1);
-        const size_t tile = 256 * unroll;
-        const size_t slots = ((N + tile - 1) / tile + g1 - 1) / g1;
-        // the two-launch path on the same frame: what a repaired evaluation has to reproduce
-        if (unroll == 2)
-            hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 2, false>), dim3(g1), dim3(256), 0, st, in1(0), n, L, L, L, 2, part);
-        else
-            hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 1, false>), dim3(g1), dim3(256), 0, st, in1(0), n, L, L, L, 2, part);
-        hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, false>), dim3(grid(2 * N, 1024, 2)), dim3(256), 0, st, in0(0), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[0], false);
-        CHECK(hipDeviceSynchronize());
-        cavmd_result want_res; CHECK(hipMemcpy(&want_res, d_res, sizeof(want_res), hipMemcpyDeviceToHost));
-        CHECK(hipMemcpy(h_want.data(), d_frc[0], 32 * N, hipMemcpyDeviceToHost));
-        CHECK(hipMemset(d_frc[0], 0x5A, 32 * N));
-        CHECK(hipMemset(d_hres, 0, sizeof(HostResult)));
-        CHECK(hipMemset(d_res, 0, sizeof(cavmd_result)));
-        hipEvent_t a, b2;
-        CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b2));
-        CHECK(hipEventRecord(a, st));
-#ifdef CAVMD_FAULT_LATE_BLOCK
-        SyncState fsync = sync;
-        fsync.spin_limit = 20000;                    // ~8 ms instead of ~0.3 s
-        fsync.late_block = CAVMD_FAULT_LATE_BLOCK;
-        fsync.late_ticks = 6000000;                  // 60 ms of the 100 MHz clock
-        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        if (unroll == 2)
-            hipLaunchKernelGGL((cavity_persistent_kernel<256, 2, true, true>), dim3(g1), dim3(256), slots * tile * 8, st, in2(0), n, L, L, L, P, 2, fsync, 7ull, d_res, d_hres, (v2d*)d_frc[0], (unsigned)slots, false);
-        else
-            hipLaunchKernelGGL((cavity_persistent_kernel<256, 1, true, true>), dim3(g1), dim3(256), slots * tile * 8, st, in2(0), n, L, L, L, P, 2, fsync, 7ull, d_res, d_hres, (v2d*)d_frc[0], (unsigned)slots, false);
-#else
-        if (unroll == 2)
-            hipLaunchKernelGGL((cavity_persistent_kernel<256, 2, true>), dim3(g1), dim3(256), slots * tile * 8, st, in2(0), n, L, L, L, P, 2, sync, 7ull, d_res, d_hres, (v2d*)d_frc[0], (unsigned)slots, false);
-        else
-            hipLaunchKernelGGL((cavity_persistent_kernel<256, 1, true>), dim3(g1), dim3(256), slots * tile * 8, st, in2(0), n, L, L, L, P, 2, sync, 7ull, d_res, d_hres, (v2d*)d_frc[0], (unsigned)slots, false);
-#endif
-        CHECK(hipEventRecord(b2, st));
-        CHECK(hipEventSynchronize(b2));
-        float ms; CHECK(hipEventElapsedTime(&ms, a, b2));
-        HostResult hr; CHECK(hipMemcpy(&hr, d_hres, sizeof(hr), hipMemcpyDeviceToHost));
-        unsigned sync_error; CHECK(hipMemcpy(&sync_error, d_syncerr, sizeof(sync_error), hipMemcpyDeviceToHost));
-        cavmd_result got_res; CHECK(hipMemcpy(&got_res, d_res, sizeof(got_res), hipMemcpyDeviceToHost));
-        unsigned after[3]; CHECK(hipMemcpy(after, d_epoch, 12, hipMemcpyDeviceToHost));
-        CHECK(hipMemcpy(h_f.data(), d_frc[0], 32 * N, hipMemcpyDeviceToHost));
-        size_t nan = 0, differ = 0;
-        for (size_t i = 0; i < h_f.size(); ++i) { nan += (h_f[i] != h_f[i]); differ += memcmp(&h_f[i], &h_want[i], 8) != 0; }
-        const bool same_dipole = memcmp(got_res.dipole, want_res.dipole, sizeof(got_res.dipole)) == 0
-                                 && memcmp(hr.result.dipole, want_res.dipole, sizeof(got_res.dipole)) == 0;
-#ifdef CAVMD_FAULT_SILENT_BLOCK
-        (void)differ; (void)same_dipole;
-        printf("fault injection (block %d silent, grid %u): kernel returned after %.1f ms, sync_error=%u, ready=%llu, slot failure word %llu, NaN force entries %zu of %zu, epoch %u, give-up count left %u, poison word %s\n",
-               CAVMD_FAULT_SILENT_BLOCK, g1, ms, sync_error, (unsigned long long)hr.ready, (unsigned long long)hr.failed, nan, h_f.size(), after[0], after[1], after[2] ? "set" : "clear");
-        // (with at most 16 blocks every block gathers the block records itself: the silent block, which has its own record in
-        // registers, completes its own tile and leaves; the others can never be complete -- a stuck give-up count and an epoch
-        // that was not advanced are what the host wipes before it would use the single launch again)
-        // (the result slot names the failed evaluation: sequence 7, tagged kSyncFailed)
-        return (sync_error == 1 && hr.failed == ((7ull << 2) | kSyncFailed) && nan >= h_f.size() - 4 * (size_t)tile && hr.ready == 0) ? 0 : 1;
-#else
-        printf("fault injection (block %d late, grid %u): kernel returned after %.1f ms, sync_error=%u, ready=%llu, NaN force entries %zu, force entries differing from the two-launch path %zu of %zu, dipole identical %d, epoch %u, give-up count left %u, poison word %s\n",
-               CAVMD_FAULT_LATE_BLOCK, g1, ms, sync_error, (unsigned long long)hr.ready, nan, differ, h_f.size(), (int)same_dipole, after[0], after[1], after[2] ? "set" : "clear");
-        return (sync_error == 2 && nan == 0 && differ == 0 && hr.ready == 7 && same_dipole && after[0] == 2 && after[1] == 0 && after[2] == 0) ? 0 : 1;
-#endif
-    }
-#endif
     std::vector<Variant> V;
     // the product's two-launch sequence
     V.push_back({"two launches (K1 nt1 bpc1 | fused map u4 bpc2)", [&](int f) {
                      const unsigned g1 = grid(N, 256 * unroll, 1);
                      if (unroll == 2)
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 2, false>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 2>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
                      else
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 1, false>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
+                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 1>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
                      const unsigned g2 = grid(2 * N, 1024, 2);
                      if (nts)
                          hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, true>), dim3(g2), dim3(256), 0, st, in0(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false);
                      else
                          hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, false>), dim3(g2), dim3(256), 0, st, in0(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false);
                  }, {}});
-    auto persist = [&](int f, int bpc, int balanced = 0, int earlyz = 0) {
+    auto persist = [&](int f, int bpc, int balanced = 0) {
         const unsigned g1 = grid(N, 256 * unroll, bpc);
         const size_t tile = 256 * unroll;
         size_t slots = ((N + tile - 1) / tile + g1 - 1) / g1;
         if (balanced == 1) { const size_t units = (N + 63) / 64; slots = (((units + g1 - 1) / g1) * 64 + tile - 1) / tile; }
-        if (balanced == 2) slots = (N / tile) / g1 + 1;
         const size_t cap = (156 * 1024 - 1024) / (tile * 8);
         const unsigned lds_slots = (unsigned)std::min(slots, cap);
         const size_t lds = (size_t)lds_slots * tile * 8;
-#define PL(UNR, NTS, EZ) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS, false, EZ>), dim3(g1), dim3(256), lds, st, in2(f), n, L, L, L, P, 2, sync, 1ull, d_res, d_hres, (v2d*)d_frc[f], lds_slots, balanced)
-#define PLZ(UNR, NTS) do { if (earlyz == 0) PL(UNR, NTS, 0); else if (earlyz == 1) PL(UNR, NTS, 1); else PL(UNR, NTS, 2); } while (0)
-        if (unroll == 2) { if (nts) PLZ(2, true); else PLZ(2, false); }
-        else { if (nts) PLZ(1, true); else PLZ(1, false); }
+#define PL(UNR, NTS) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS>), dim3(g1), dim3(256), lds, st, in2(f), n, L, L, L, P, 2, sync, 1ull, d_res, d_hres, (v2d*)d_frc[f], lds_slots, balanced)
+        if (unroll == 2) { if (nts) PL(2, true); else PL(2, false); }
+        else { if (nts) PL(1, true); else PL(1, false); }
     };
     V.push_back({"single launch, tiles dealt round-robin", [&](int f) { persist(f, 1, 0); }, {}});
     V.push_back({"single launch, balanced contiguous shares", [&](int f) { persist(f, 1, 1); }, {}});
-    V.push_back({"single launch, full rounds strided + last round split evenly", [&](int f) { persist(f, 1, 2); }, {}});
-    if (getenv("CAVMD_TRY_EARLYZ")) {
-        V.push_back({"single launch, zero chunks early (plain stores)", [&](int f) { persist(f, 1, 0, 1); }, {}});
-        V.push_back({"single launch, zero chunks early (nt stores)", [&](int f) { persist(f, 1, 0, 2); }, {}});
-    }
-    auto persist512 = [&](int f, int unr) {
-        const size_t tile = 512 * unr;
-        const unsigned g1 = grid(N, tile, 1);
-        size_t slots = ((N + tile - 1) / tile + g1 - 1) / g1;
-        const size_t cap = (156 * 1024 - 1024) / (tile * 8);
-        const unsigned lds_slots = (unsigned)std::min(slots, cap);
-        const size_t lds = (size_t)lds_slots * tile * 8;
-        if (unr == 1) hipLaunchKernelGGL((cavity_persistent_kernel<512, 1, true>), dim3(g1), dim3(512), lds, st, in2(f), n, L, L, L, P, 2, sync, 1ull, d_res, d_hres, (v2d*)d_frc[f], lds_slots, false);
-        else hipLaunchKernelGGL((cavity_persistent_kernel<512, 2, true>), dim3(g1), dim3(512), lds, st, in2(f), n, L, L, L, P, 2, sync, 1ull, d_res, d_hres, (v2d*)d_frc[f], lds_slots, false);
-    };
-    if (getenv("CAVMD_TRY_512")) {
-        V.push_back({"single launch, 512 threads x 1", [&](int f) { persist512(f, 1); }, {}});
-        V.push_back({"single launch, 512 threads x 2", [&](int f) { persist512(f, 2); }, {}});
-    }
 
     {
         // every variant must give the bits of the first one (the product's two-launch path) in every force entry -- except the
@@ -314,9 +217,9 @@ int main(int argc, char** argv)
     }
 
     // ---- time line of the single-launch kernel: per-block stamps, relative to the first block's start ----------------------
-    const int timeline_earlyz = getenv("CAVMD_TIMELINE_EARLYZ") ? atoi(getenv("CAVMD_TIMELINE_EARLYZ")) : 0;
-    const int timeline_partition = getenv("CAVMD_TIMELINE_PARTITION") ? atoi(getenv("CAVMD_TIMELINE_PARTITION")) : 0;
-    printf("time line of the variant with partition %d, EARLYZ %d\n", timeline_partition, timeline_earlyz);
+    // CAVMD_TIMELINE_PARTITION=1: the balanced partition instead of the strided one
+    const int timeline_partition = getenv("CAVMD_TIMELINE_PARTITION") && atoi(getenv("CAVMD_TIMELINE_PARTITION")) == 1;
+    printf("time line of the variant with partition %d\n", timeline_partition);
     for (int mode = 0; mode < 1; ++mode)
     {
         const unsigned g1 = grid(N, 256 * unroll, 1);
@@ -327,7 +230,7 @@ int main(int argc, char** argv)
         std::vector<int> xcc_frame(30, 0);
         for (int rep = 0; rep < 30; ++rep)
         {
-            for (int k = 0; k < 12; ++k) persist((rep + k) % frames, 1, timeline_partition, timeline_earlyz); // steady state: the stamps are those of the last launch
+            for (int k = 0; k < 12; ++k) persist((rep + k) % frames, 1, timeline_partition); // steady state: the stamps are those of the last launch
             CHECK(hipDeviceSynchronize());
             std::vector<unsigned long long> h(4096 * kStampSlots);
             CHECK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_pstamps), sizeof(unsigned long long) * h.size()));

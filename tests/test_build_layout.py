@@ -110,3 +110,30 @@ def test_batch_units_cannot_see_the_workspace():
                 readers[switch].add(os.path.basename(path))
     assert readers == {"CAVMD_TEST_HOOKS": {"cavmd_capi.hip"}, "CAVMD_MOLECULAR_J_SPLIT": {"cavmd_molecular.hip"},
                        "CAVMD_COULOMB_J_SPLIT": {"cavmd_coulomb.hip"}, "CAVMD_COULOMB_K_SPLIT": {"cavmd_coulomb.hip"}}
+
+
+def _conditional_names(path):
+    """every CAVMD_* name a preprocessor conditional of `path` tests (#if, #ifdef, #ifndef, #elif, defined(...))"""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S).replace("\\\n", " ")
+    names = set()
+    for line in text.splitlines():
+        line = re.sub(r"//.*", "", line)
+        if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+            names |= set(re.findall(r"\bCAVMD_\w+", line))
+    return names
+
+
+def test_compile_time_switches_are_the_ones_meant():
+    """The library's sources branch on six names and no more: the test hooks, the two stamp hooks of the micro-benchmarks
+    (empty in the product) and, in the public header the units compile against, the three lane splits.  A rejected variant or a
+    diagnostic behind a -D (fault injection, a cheaper accumulate, protocol constants) has no place in them: it would be one
+    flag away from the product."""
+    sources = [p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))
+               if not os.path.basename(p).startswith("microbench")]
+    assert len(sources) >= 26
+    in_csrc = set().union(*[_conditional_names(p) for p in sources])
+    assert in_csrc == {"CAVMD_TEST_HOOKS", "CAVMD_STAMP", "CAVMD_PSTAMP"}
+    in_header = _conditional_names(os.path.join(ROOT, "include", "cavmd.h")) - {"CAVMD_H_"}
+    assert in_header == {"CAVMD_MOLECULAR_J_SPLIT", "CAVMD_COULOMB_J_SPLIT", "CAVMD_COULOMB_K_SPLIT"}
+    for name in in_csrc | in_header:
+        assert not any(word in name for word in ("FAULT", "DIAG", "GROUP_COPIES", "POLL_SLEEP")), name

@@ -656,8 +656,8 @@ def test_single_launch_hand_off_under_load_and_reuse():
 
 
 def test_a_sync_timeout_is_reported_once_and_the_workspace_falls_back_to_two_launches():
-    """A single-launch evaluation whose blocks starve each other ends in a time-out (a real one is provoked by
-    `make microbench_persistent_fault`, profiles/r02/fault_injection.txt).  What the library does with it, exercised through the
+    """A single-launch evaluation whose blocks starve each other ends in a time-out (a real one is recorded in
+    profiles/r02/fault_injection.txt).  What the library does with it, exercised through the
     fault-injection tunable: the NEXT call (enqueue or result read) reports CAVMD_ERR_SYNC_TIMEOUT exactly once, enqueues
     nothing, invalidates the stale result, and from then on the workspace evaluates with two launches -- same bits."""
     n = 60_001

@@ -34,6 +34,6 @@ def test_the_kernels_use_the_enumerated_schedule():
     force = open(os.path.join(CSRC, "cavmd_force_kernels.hpp")).read()
     persistent = open(os.path.join(CSRC, "cavmd_persistent_kernel.hpp")).read()
     assert force.count("rolling_rows<UNROLL>(") == 1 and '#include "cavmd_tile_schedule.hpp"' in force
-    assert force.count("accumulate_full_tiles<Input, BLOCK, UNROLL>(") == 1     # dipole_partials_kernel, !PIPE
+    assert force.count("accumulate_full_tiles<Input, BLOCK, UNROLL>(") == 1     # dipole_partials_kernel
     assert persistent.count("accumulate_full_tiles<AosInputT<2>, BLOCK, UNROLL>(") == 1
     assert "tile_load<" not in persistent and "strided_tiles(N, G, b, TILE)" in persistent
