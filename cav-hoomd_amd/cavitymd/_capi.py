@@ -136,6 +136,22 @@ class VerletState(ctypes.Structure):
                 ("reserved", ctypes.c_double)]
 
 
+class DrawItem(ctypes.Structure):
+    """cavmd_draw_item (160 bytes): one system of a draw object; the four pointers are DEVICE pointers."""
+    _fields_ = [("d_verlet_row", ctypes.c_void_p), ("d_bussi_row", ctypes.c_void_p), ("d_records", ctypes.c_void_p),
+                ("d_rows", ctypes.c_void_p), ("capacity", ctypes.c_uint64), ("langevin_gamma", ctypes.c_double),
+                ("langevin_kT", ctypes.c_double), ("bussi_set_T", ctypes.c_double), ("bussi_tau", ctypes.c_double),
+                ("bussi_dof", ctypes.c_double), ("dt_initial", ctypes.c_double), ("tolerance_target", ctypes.c_double),
+                ("tolerance_initial", ctypes.c_double), ("tolerance_time_constant", ctypes.c_double),
+                ("dt_min", ctypes.c_double), ("dt_max", ctypes.c_double), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class DrawState(ctypes.Structure):
+    """cavmd_draw_state (64 bytes): one item's counters."""
+    _fields_ = [("draws", ctypes.c_uint64), ("dt", ctypes.c_double), ("elapsed", ctypes.c_double),
+                ("tolerance", ctypes.c_double), ("exhausted", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3)]
+
+
 class MolecularPair(ctypes.Structure):
     """cavmd_molecular_pair (64 bytes): one entry of the pair table, made by cavmd_molecular_pair_make."""
     _fields_ = [("lj1", ctypes.c_double), ("lj2", ctypes.c_double), ("lj1_12", ctypes.c_double), ("lj2_6", ctypes.c_double),
@@ -237,6 +253,20 @@ def verlet_item(N, pos_ptr, image_ptr, vel_ptr, accel_ptr, force_ptrs, net_force
     it.d_net_force = net_force_ptr or None
     it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
     it.N, it.langevin_index = int(N), int(langevin_index)
+    return it
+
+
+def draw_item(verlet_row_ptr=0, bussi_row_ptr=0, gamma=0.0, kT=0.0, set_T=0.0, tau=0.0, dof=0.0, dt=0.0, records_ptr=0,
+              rows_ptr=0, capacity=0, tolerance=0.0, tolerance_initial=0.0, tolerance_time_constant=0.0, dt_min=0.0,
+              dt_max=0.0) -> "DrawItem":
+    """records_ptr == 0: a fixed dt; otherwise the adaptive rule on that series with `tolerance` as its target."""
+    it = DrawItem()
+    it.d_verlet_row, it.d_bussi_row = verlet_row_ptr or None, bussi_row_ptr or None
+    it.d_records, it.d_rows, it.capacity = records_ptr or None, rows_ptr or None, int(capacity)
+    it.langevin_gamma, it.langevin_kT = float(gamma), float(kT)
+    it.bussi_set_T, it.bussi_tau, it.bussi_dof = float(set_T), float(tau), float(dof)
+    it.dt_initial, it.tolerance_target, it.tolerance_initial = float(dt), float(tolerance), float(tolerance_initial)
+    it.tolerance_time_constant, it.dt_min, it.dt_max = float(tolerance_time_constant), float(dt_min), float(dt_max)
     return it
 
 
@@ -354,6 +384,14 @@ _PROTOTYPES = {
     "cavmd_verlet_read": (_ci, [_vp, _vp, _vp]),
     "cavmd_verlet_reset": (_ci, [_vp, _vp]),
     "cavmd_verlet_state_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_draw_item_check": (_ci, [_P(DrawItem)]),
+    "cavmd_draw_create": (_ci, [_vp, _u64, _sz, _P(DrawItem), _P(_vp)]),
+    "cavmd_draw_destroy": (_ci, [_vp]),
+    "cavmd_draw_set_items": (_ci, [_vp, _sz, _sz, _P(DrawItem)]),
+    "cavmd_draw_fill": (_ci, [_vp, _vp]),
+    "cavmd_draw_read": (_ci, [_vp, _vp, _vp]),
+    "cavmd_draw_reset": (_ci, [_vp, _vp]),
+    "cavmd_draw_state_device_ptr": (_ci, [_vp, _P(_vp)]),
     "cavmd_molecular_pair_make": (_ci, [_dbl, _dbl, _dbl, _ci, _P(MolecularPair)]),
     "cavmd_molecular_params_check": (_ci, [_P(MolecularParams)]),
     "cavmd_molecular_item_check": (_ci, [_P(MolecularParams), _P(MolecularItem)]),
@@ -703,7 +741,7 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Molecular and Coulomb share: a handle created from a workspace
+    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Draw, Molecular and Coulomb share: a handle created from a workspace
     (kept alive here) over a table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
     the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -1062,6 +1100,54 @@ class Verlet(_ItemTableHandle):
     def state_device_ptr(self) -> int:
         p = ctypes.c_void_p()
         check(self._lib.cavmd_verlet_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_verlet_state_device_ptr")
+        return int(p.value)
+
+
+DRAW_STATE_DTYPE_FIELDS = [("draws", "<u8"), ("dt", "<f8"), ("elapsed", "<f8"), ("tolerance", "<f8"), ("exhausted", "<u8"),
+                           ("reserved", "<u8", (3,))]
+
+
+def draw_state_dtype():
+    """numpy structured dtype with the layout of cavmd_draw_state (64 bytes)."""
+    import numpy as np
+    return np.dtype(DRAW_STATE_DTYPE_FIELDS)
+
+
+def draw_item_check(item: DrawItem) -> int:
+    """Status cavmd_draw_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_draw_item_check(ctypes.byref(item)))
+
+
+class Draw(_ItemTableHandle):
+    """Owns one cavmd_draw: the integrator's and the thermostat's input rows of B independent small systems written by ONE
+    kernel launch per step, one lane per system, from a seeded counter-based generator, with the step's dt (fixed, or the
+    adaptive rule on the recorder's last row).  Items cost the same: launched in item order."""
+    _ITEM, _PREFIX = DrawItem, "cavmd_draw"
+    _size = staticmethod(lambda it: 0)
+
+    def __init__(self, workspace: Workspace, seed: int, items):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2**64:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_draw_create")
+        self._create(workspace, items, before=(self.seed,))
+
+    def fill(self, stream: int = 0) -> None:
+        """One kernel: both input rows, the counters and the dt of every item."""
+        check(self._lib.cavmd_draw_fill(self._h, ctypes.c_void_p(stream)), "cavmd_draw_fill")
+
+    def read(self, stream: int = 0):
+        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_draw_state."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=draw_state_dtype())
+        check(self._lib.cavmd_draw_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_draw_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_draw_reset(self._h, ctypes.c_void_p(stream)), "cavmd_draw_reset")
+
+    def state_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        check(self._lib.cavmd_draw_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_draw_state_device_ptr")
         return int(p.value)
 
 

@@ -21,7 +21,8 @@ so ``record()`` captured into a graph next to ``CavityForceBatch.compute``, ``Ba
 
 ``reference_interval`` counts recorded rows.  The reference's time-based ``reference_interval_ps`` under an adaptive timestep
 is the caller's policy: keep a uint32 tensor of B words on the device, set a word when that replica's clock passes its next
-reference time, and hand the tensor to ``record(take_reference=...)``; it is read when the kernel runs.
+reference time, and hand the tensor to ``record(take_reference=...)``; it is read when the kernel runs.  That clock exists
+on the device since ``StepDraw``: ``elapsed`` of its state (``cavmd_draw_state_device_ptr``) is the sum of every dt handed out.
 
 There is no CPU fallback: CPU tensors raise.
 """

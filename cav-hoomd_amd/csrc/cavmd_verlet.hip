@@ -1,5 +1,7 @@
-// cavmd_verlet.hip -- cavmd_verlet of include/cavmd.h: the velocity-Verlet half-steps of a batch of small systems, one launch each.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// cavmd_verlet.hip -- cavmd_verlet of include/cavmd.h: the velocity-Verlet half-steps of a batch of small systems, one launch
+// each; and cavmd_draw, which writes the input rows those half-steps (and the thermostat batch) read: seeded variates and the
+// step's dt, one launch per step.  Two of the eight objects built on an item table (cavmd_item_table.hpp); the workspace is
+// an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -9,6 +11,7 @@
 
 #include "cavmd.h"
 #include "cavmd_verlet_batch_kernel.hpp"
+#include "cavmd_draw_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -38,8 +41,68 @@ struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N d
     }
 };
 
+// ---- the step inputs of a batch drawn on the device, one launch per step (cavmd_draw_kernel.hpp) ------------------------------
+// the row of an item: the item, with the fixed-mode columns taken by the two input makers in its reserved words
+static DrawRow draw_row(const cavmd_draw_item& it)
+{
+    static_assert(sizeof(DrawRow) == sizeof(cavmd_draw_item), "a draw row is the item with two words filled in");
+    DrawRow r;
+    memcpy(&r, &it, sizeof(r));
+    const double zero[3] = {0.0, 0.0, 0.0};
+    cavmd_verlet_input v;
+    cavmd_bussi_batch_input b;
+    (void)cavmd_verlet_input_make(it.dt_initial, it.langevin_gamma, it.langevin_kT, zero, &v);
+    (void)cavmd_bussi_batch_input_make(it.dt_initial, it.bussi_set_T, it.bussi_tau, 0.0, 0.0, &b);
+    r.fixed_coeff = v.langevin_coeff;
+    r.fixed_c = b.c;
+    return r;
+}
+
+struct cavmd_draw : ItemTable<cavmd_draw_item, DrawRow> // items cost the same: launched in item order
+{
+    DeviceArray<DrawState> d_state; // n states, indexed by item
+    uint64_t seed = 0;
+
+    cavmd_draw() : ItemTable(cavmd_draw_item_check, [](const cavmd_draw_item&) { return 0u; }, draw_row) {}
+
+    hipError_t alloc_own()
+    {
+        return d_state.alloc_zeroed(n);
+    }
+};
+
 namespace
 {
+static_assert(offsetof(cavmd_draw_item, d_verlet_row) == offsetof(DrawRow, verlet_row)
+                  && offsetof(cavmd_draw_item, d_bussi_row) == offsetof(DrawRow, bussi_row)
+                  && offsetof(cavmd_draw_item, d_records) == offsetof(DrawRow, records)
+                  && offsetof(cavmd_draw_item, d_rows) == offsetof(DrawRow, rows)
+                  && offsetof(cavmd_draw_item, capacity) == offsetof(DrawRow, capacity)
+                  && offsetof(cavmd_draw_item, langevin_gamma) == offsetof(DrawRow, gamma)
+                  && offsetof(cavmd_draw_item, langevin_kT) == offsetof(DrawRow, kT)
+                  && offsetof(cavmd_draw_item, bussi_set_T) == offsetof(DrawRow, set_T)
+                  && offsetof(cavmd_draw_item, bussi_tau) == offsetof(DrawRow, tau)
+                  && offsetof(cavmd_draw_item, bussi_dof) == offsetof(DrawRow, dof)
+                  && offsetof(cavmd_draw_item, dt_initial) == offsetof(DrawRow, dt_initial)
+                  && offsetof(cavmd_draw_item, tolerance_target) == offsetof(DrawRow, tol_target)
+                  && offsetof(cavmd_draw_item, tolerance_initial) == offsetof(DrawRow, tol_initial)
+                  && offsetof(cavmd_draw_item, tolerance_time_constant) == offsetof(DrawRow, tol_time_constant)
+                  && offsetof(cavmd_draw_item, dt_min) == offsetof(DrawRow, dt_min)
+                  && offsetof(cavmd_draw_item, dt_max) == offsetof(DrawRow, dt_max)
+                  && offsetof(cavmd_draw_item, reserved) == offsetof(DrawRow, fixed_coeff),
+              "draw item layout");
+static_assert(sizeof(cavmd_draw_state) == sizeof(DrawState) && offsetof(cavmd_draw_state, draws) == offsetof(DrawState, draws)
+                  && offsetof(cavmd_draw_state, dt) == offsetof(DrawState, dt)
+                  && offsetof(cavmd_draw_state, elapsed) == offsetof(DrawState, elapsed)
+                  && offsetof(cavmd_draw_state, tolerance) == offsetof(DrawState, tolerance)
+                  && offsetof(cavmd_draw_state, exhausted) == offsetof(DrawState, exhausted),
+              "the draw states are read out as they are");
+static_assert(sizeof(cavmd_record) == sizeof(DrawRecord)
+                  && offsetof(cavmd_record, force_mass_sum) == offsetof(DrawRecord, force_mass_sum),
+              "the record column the adaptive rule reads");
+static_assert(offsetof(cavmd_verlet_input, skip) == 48 && offsetof(cavmd_bussi_batch_input, skip) == 32
+                  && sizeof(cavmd_bussi_batch_input) == 64,
+              "the rows the draw kernel writes word by word");
 static_assert(sizeof(cavmd_verlet_item) == sizeof(VerletRow), "the item table is uploaded as it is");
 static_assert(offsetof(cavmd_verlet_item, d_pos) == offsetof(VerletRow, pos2)
                   && offsetof(cavmd_verlet_item, d_image) == offsetof(VerletRow, image)
@@ -170,6 +233,85 @@ int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** ou
     if (!v || !out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = reinterpret_cast<const cavmd_verlet_state*>(v->d_state.ptr);
+    return CAVMD_OK;
+}
+
+// ---- cavmd_draw ------------------------------------------------------------------------------------------------------------
+int cavmd_draw_item_check(const cavmd_draw_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 4; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_verlet_row & 7) || ((uintptr_t)it->d_bussi_row & 7) || ((uintptr_t)it->d_records & 7)
+        || ((uintptr_t)it->d_rows & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (!it->d_verlet_row && !it->d_bussi_row)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->d_records && (!it->d_rows || it->capacity == 0))
+        return CAVMD_ERR_INVALID_VALUE;
+    const double values[] = {it->langevin_gamma,    it->langevin_kT,       it->bussi_set_T, it->bussi_tau,
+                             it->bussi_dof,         it->dt_initial,        it->tolerance_target,
+                             it->tolerance_initial, it->tolerance_time_constant, it->dt_min, it->dt_max};
+    for (double x : values)
+        if (!finite_nonnegative(x))
+            return CAVMD_ERR_INVALID_VALUE;
+    if (it->dt_min > it->dt_max)
+        return CAVMD_ERR_INVALID_VALUE;
+    return CAVMD_OK;
+}
+
+int cavmd_draw_create(cavmd_workspace* ws, uint64_t seed, size_t n_items, const cavmd_draw_item* h_items, cavmd_draw** out)
+{
+    return create_table(ws, n_items, h_items, out, CAVMD_OK, [seed](cavmd_draw* d) { d->seed = seed; });
+}
+
+int cavmd_draw_destroy(cavmd_draw* d)
+{
+    return destroy_table(d);
+}
+
+int cavmd_draw_set_items(cavmd_draw* d, size_t first, size_t count, const cavmd_draw_item* h_items)
+{
+    return d ? d->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_draw_fill(cavmd_draw* d, void* stream_)
+{
+    if (!d)
+        return CAVMD_ERR_INVALID_VALUE;
+    return d->launch((hipStream_t)stream_, draw_fill_kernel<kDrawBlock>, dim3((unsigned)((d->n + kDrawBlock - 1) / kDrawBlock)),
+                     dim3(kDrawBlock), 0, d->d_rows.ptr, (unsigned)d->n, (unsigned)d->seed, (unsigned)(d->seed >> 32),
+                     d->d_state.ptr);
+}
+
+int cavmd_draw_read(cavmd_draw* d, void* stream_, cavmd_draw_state* out)
+{
+    if (!d || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(d->device);
+    const int st = sync_uncaptured((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(hipMemcpy(out, d->d_state.ptr, sizeof(DrawState) * d->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_draw_reset(cavmd_draw* d, void* stream_)
+{
+    if (!d)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(d->device);
+    CAVMD_HIP_TRY(hipMemsetAsync(d->d_state.ptr, 0, sizeof(DrawState) * d->n, (hipStream_t)stream_));
+    return CAVMD_OK;
+}
+
+int cavmd_draw_state_device_ptr(cavmd_draw* d, const cavmd_draw_state** out)
+{
+    if (!d || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = reinterpret_cast<const cavmd_draw_state*>(d->d_state.ptr);
     return CAVMD_OK;
 }
 

@@ -514,7 +514,8 @@ typedef struct cavmd_record              /* 128 B, one per item and recorded cal
     double cavity_kinetic;    /* CavityModeTracker: KE; its PE is energy[0], its total is cavity_kinetic + energy[0] */
     double cavity_temperature;
     double kinetic_energy;    /* of the item's group, as cavmd_kinetic_energy */
-    double force_mass_sum;    /* as cavmd_force_mass_sum; dt = sqrt(tol / S) stays the caller's */
+    double force_mass_sum;    /* as cavmd_force_mass_sum; dt = sqrt(tol / S) stays the caller's, or is taken on the device
+                                 by cavmd_draw_fill (the section "the step inputs of a batch, drawn on the device") */
     double reserved;          /* 0 */
 } cavmd_record;
 
@@ -782,6 +783,116 @@ CAVMD_API int cavmd_verlet_read(cavmd_verlet* v, void* stream, cavmd_verlet_stat
 CAVMD_API int cavmd_verlet_reset(cavmd_verlet* v, void* stream);
 /* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out);
+
+/* ---- the step inputs of a batch, drawn on the device: seeded variates and an adaptive dt in ONE launch per step ------------- */
+/* What fills the two input tables above and below when a captured step replays: for every registered item, ONE kernel writes
+ * its cavmd_verlet_input row and its cavmd_bussi_batch_input row from a counter-based, seeded generator and computes the
+ * step's dt -- fixed, or the rule of the reference's AdaptiveTimestepUpdater (src/cavitymd/simulation.py:57-92) on the
+ * force_mass_sum the recorder wrote last.  A captured step is then {cavmd_draw_fill, cavmd_verlet_step_one, the forces,
+ * cavmd_verlet_step_two, cavmd_recorder_record, cavmd_field_recorder_record, cavmd_bussi_batch_step}: the same seed and items
+ * give the same trajectory of inputs, the dt never visits the host, and the elapsed time of every item is kept next to it.
+ * One LANE per item, 256-thread workgroups; no workgroup waits for another, hence no CAVMD_ERR_SYNC_TIMEOUT here.  The
+ * integrator and the thermostat are not changed: rows written by their callers in other ways keep working.
+ *
+ * The expressions below ARE the contract (tests/draw_mirror.py restates them).  One call for one item, `draws` being the
+ * item's counter in DEVICE memory when the kernel RUNS (read, then advanced by one: a graph replay draws a new block):
+ *   1. Generator.  Philox4x32-10 with the published constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ *      0xBB67AE85).  Key = (seed low, seed high).  Counter = (draws low, draws high, item index, purpose).  A block is the
+ *      four output words w0 .. w3 of one counter.  The purposes, none used twice:
+ *        0            w0,w1 -> uniform[0] and w2,w3 -> uniform[1] of the integrator row (the Langevin variates)
+ *        1            w0,w1 -> uniform[2]
+ *        2            the thermostat's normal variate (u1 from w0,w1; u2 from w2,w3)
+ *        3            w0,w1 -> the boost uniform of a gamma shape below 1
+ *        16 + 2 t     the normal x of gamma try t, t = 0 .. 15 (as purpose 2)
+ *        17 + 2 t     w0,w1 -> the acceptance uniform u of gamma try t
+ *      Known answers (counter, key -> output): 0 0 0 0, 0 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; ffffffff x4, ffffffff x2
+ *      -> 408f276d 41c83b0e a20bc7c6 6d5451fd; 243f6a88 85a308d3 13198a2e 03707344, a4093822 299f31d0 -> d16cfe09 94fdcceb
+ *      5001e420 24126ea1.
+ *   2. Words to doubles, exact: k = (w_hi << 21) | (w_lo >> 11) with w_hi the first word of the pair.  A uniform in [0, 1) is
+ *      k * 2^-53; a Langevin variate is 2 * that - 1, in [-1, 1) as step two demands; an argument of log is (k + 1) * 2^-53,
+ *      in (0, 1].
+ *   3. Normal: sqrt(-2 * log(u1)) * cospi(2 * u2), u1 an argument of log, u2 a uniform in [0, 1).
+ *   4. Gamma of shape a >= 1 (Marsaglia and Tsang 2000): d = a - 1/3, c = 1 / sqrt(9 d); try t: v = (1 + c x)^3 as
+ *      ((1 + c x) * (1 + c x)) * (1 + c x); accepted if v > 0 and log(u) < (((0.5 x) x + d) - d v) + d log(v); the variate is
+ *      d v of the first accepted try.  At most 16 tries; if all fail the variate is d and `exhausted` is incremented (the
+ *      acceptance is 0.95 at a = 1 and rises with a).  Shape a < 1: the shape-(a + 1) variate times u^(1/a), taken as
+ *      exp(log(u) / a), u the boost uniform as an argument of log.
+ *      bussi_dof as BussiReservoirBatch.draw_inputs has it: the normal is drawn where dof != 0 (else 0), the gamma variate of
+ *      shape (dof - 1) / 2 where dof > 1 (else 0).
+ *   5. dt.  Fixed mode (d_records NULL): dt = dt_initial; langevin_coeff and c are the bytes cavmd_verlet_input_make and
+ *      cavmd_bussi_batch_input_make give for it, taken on the HOST at create / set_items; `tolerance` is 0.  Adaptive mode:
+ *        tolerance = tolerance_time_constant != 0
+ *                        ? tolerance_target - (tolerance_target - tolerance_initial) * exp(-elapsed / tolerance_time_constant)
+ *                        : tolerance_target
+ *        rows = *d_rows;  rows == 0: dt = dt_initial;  otherwise S = d_records[(rows - 1) % capacity].force_mass_sum and
+ *        dt = S > 0 and finite ? min(max(sqrt(tolerance / S), dt_min), dt_max)
+ *                              : the last dt this object used for the item (dt_initial if draws == 0)
+ *        langevin_coeff = gamma != 0 and dt != 0 ? sqrt(((6 * gamma) * kT) / dt) : 0;   c = tau != 0 ? exp(-dt / tau) : 0
+ *      `elapsed` is in the caller's time units (the conversion to ps is the caller's), and so is tolerance_time_constant.
+ *      Division and square root are correctly rounded, every operation outside log / exp / cospi is one IEEE rounding, no FMA.
+ *   6. skip = (dt == 0) in both rows; draws += 1; elapsed = elapsed + dt (a plain left-to-right sum); the reserved words of
+ *      the rows written are 0.  A row whose destination is NULL is not written and its variates are not computed; the other
+ *      row's values do not depend on that.
+ *   7. A launch captured before a cavmd_draw_set_items finds the new items through the table; lanes beyond n_items leave. */
+typedef struct cavmd_draw_item           /* 160 B; all pointers DEVICE pointers */
+{
+    cavmd_verlet_input* d_verlet_row;    /* this item's row of the integrator's table, 8-byte aligned; NULL: not written */
+    cavmd_bussi_batch_input* d_bussi_row; /* this item's row of the thermostat's table, 8-byte aligned; NULL: not written;
+                                            both NULL is refused */
+    const cavmd_record* d_records;       /* NULL: fixed dt = dt_initial; else the item's series (cavmd_recorder_device_ptr's
+                                            records + item * capacity), 8-byte aligned */
+    const uint64_t* d_rows;              /* the item's row counter (cavmd_recorder_device_ptr's rows + item); required with
+                                            d_records, 8-byte aligned */
+    uint64_t capacity;                   /* of that series; > 0 with d_records */
+    double langevin_gamma;               /* the integrator row's constants; all doubles here finite and >= 0 */
+    double langevin_kT;
+    double bussi_set_T;                  /* the thermostat row's constants */
+    double bussi_tau;                    /* 0: c = 0 */
+    double bussi_dof;                    /* item 4 */
+    double dt_initial;                   /* the fixed dt; in adaptive mode the dt while nothing is recorded */
+    double tolerance_target;             /* adaptive mode */
+    double tolerance_initial;
+    double tolerance_time_constant;      /* 0: no ramp */
+    double dt_min, dt_max;               /* the clamp of the adaptive dt; dt_min <= dt_max */
+    uint64_t reserved[4];                /* must be 0 */
+} cavmd_draw_item;
+typedef struct cavmd_draw_state          /* 64 B; one per item, in device memory; written with plain stores by the item's lane */
+{
+    uint64_t draws;                      /* launches that wrote this item */
+    double dt;                           /* the last dt used */
+    double elapsed;                      /* the left-to-right sum of every dt handed out */
+    double tolerance;                    /* the last tolerance used (0 in fixed mode) */
+    uint64_t exhausted;                  /* gamma draws none of whose 16 tries was accepted */
+    uint64_t reserved[3];
+} cavmd_draw_state;
+typedef struct cavmd_draw cavmd_draw;    /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * reserved != 0, a pointer not 8-byte aligned, both destinations NULL, d_records without d_rows or with capacity 0, a
+ * non-finite or negative double, dt_min > dt_max. */
+CAVMD_API int cavmd_draw_item_check(const cavmd_draw_item* item);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), takes the fixed-mode columns, copies the table to
+ * the device of `ws` (set-up time) and allocates one zeroed state per item on the device.  cavmd_destroy answers
+ * CAVMD_ERR_INVALID_VALUE and frees nothing while a draw object of the workspace is alive.  Without a device there is no
+ * workspace, hence no draw object. */
+CAVMD_API int cavmd_draw_create(cavmd_workspace* ws, uint64_t seed, size_t n_items, const cavmd_draw_item* h_items,
+                                cavmd_draw** out);
+/* Synchronises the stream of the last launch (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_draw_destroy(cavmd_draw* d);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
+ * changed if a row is refused; the items' states are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and
+ * for a range outside the table. */
+CAVMD_API int cavmd_draw_set_items(cavmd_draw* d, size_t first, size_t count, const cavmd_draw_item* h_items);
+/* Enqueues exactly ONE kernel of ceil(n_items / 256) workgroups on `stream`, items in item order: no allocation, no copy, no
+ * host wait; may be captured into a hipGraph, and a replay draws like an eager call.  It must be ordered before the launches
+ * that read the rows and after the cavmd_recorder_record whose row it reads.  One draw object serves one stream at a time. */
+CAVMD_API int cavmd_draw_fill(cavmd_draw* d, void* stream);
+/* Synchronises `stream`, then out = the n_items states.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
+CAVMD_API int cavmd_draw_read(cavmd_draw* d, void* stream, cavmd_draw_state* out);
+/* Zero the states of all items (ordered on `stream`): the next launch draws block 0 again and elapsed restarts at 0. */
+CAVMD_API int cavmd_draw_reset(cavmd_draw* d, void* stream);
+/* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_draw_state_device_ptr(cavmd_draw* d, const cavmd_draw_state** out);
 
 /* ---- harmonic bonds and Lennard-Jones pairs of a batch in ONE launch: the molecular forces of the captured step ------------ */
 /* The reference's driver builds every run from the cavity force plus hoomd.md.bond.Harmonic and hoomd.md.pair.LJ(mode='shift')
