@@ -136,6 +136,18 @@ class VerletState(ctypes.Structure):
                 ("reserved", ctypes.c_double)]
 
 
+class BathItem(ctypes.Structure):
+    """cavmd_bath_item (64 bytes): the bath of one system of an integrator batch; d_gamma is a DEVICE pointer."""
+    _fields_ = [("d_gamma", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("kT", ctypes.c_double), ("N", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class BathState(ctypes.Structure):
+    """cavmd_bath_state (32 bytes): one item's counters."""
+    _fields_ = [("draws", ctypes.c_uint64), ("coupled", ctypes.c_uint64), ("reservoir", ctypes.c_double),
+                ("reserved", ctypes.c_double)]
+
+
 class DrawItem(ctypes.Structure):
     """cavmd_draw_item (160 bytes): one system of a draw object; the four pointers are DEVICE pointers."""
     _fields_ = [("d_verlet_row", ctypes.c_void_p), ("d_bussi_row", ctypes.c_void_p), ("d_records", ctypes.c_void_p),
@@ -253,6 +265,14 @@ def verlet_item(N, pos_ptr, image_ptr, vel_ptr, accel_ptr, force_ptrs, net_force
     it.d_net_force = net_force_ptr or None
     it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
     it.N, it.langevin_index = int(N), int(langevin_index)
+    return it
+
+
+def bath_item(gamma_ptr=0, N=0, kT=0.0, seed=0) -> "BathItem":
+    """gamma_ptr == 0 with N == 0: no bath on this item."""
+    it = BathItem()
+    it.d_gamma, it.N = gamma_ptr or None, int(N)
+    it.kT, it.seed = float(kT), int(seed)
     return it
 
 
@@ -384,6 +404,14 @@ _PROTOTYPES = {
     "cavmd_verlet_read": (_ci, [_vp, _vp, _vp]),
     "cavmd_verlet_reset": (_ci, [_vp, _vp]),
     "cavmd_verlet_state_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_bath_item_check": (_ci, [_P(BathItem)]),
+    "cavmd_bath_create": (_ci, [_vp, _sz, _P(BathItem), _P(_vp)]),
+    "cavmd_bath_destroy": (_ci, [_vp]),
+    "cavmd_bath_set_items": (_ci, [_vp, _sz, _sz, _P(BathItem)]),
+    "cavmd_bath_step_two": (_ci, [_vp, _vp, _vp]),
+    "cavmd_bath_read": (_ci, [_vp, _vp, _vp]),
+    "cavmd_bath_reset": (_ci, [_vp, _vp]),
+    "cavmd_bath_state_device_ptr": (_ci, [_vp, _P(_vp)]),
     "cavmd_draw_item_check": (_ci, [_P(DrawItem)]),
     "cavmd_draw_create": (_ci, [_vp, _u64, _sz, _P(DrawItem), _P(_vp)]),
     "cavmd_draw_destroy": (_ci, [_vp]),
@@ -533,6 +561,8 @@ _deferred = []
 # The same for the objects created from a workspace (batches, thermostat batches, recorders, field recorders), as
 # (destroy entry point, handle): always emptied before _deferred, the workspaces they were created from.
 _deferred_children = []
+# The same for the baths created from an integrator: always emptied before _deferred_children, the integrators among them.
+_deferred_baths = []
 
 
 def _capturing() -> bool:
@@ -545,6 +575,9 @@ def _capturing() -> bool:
 
 
 def _destroy_deferred() -> None:
+    while _deferred_baths:       # a bath goes before the integrator it was created from, whichever was closed first
+        destroy, h = _deferred_baths.pop()
+        destroy(h)
     while _deferred_children:
         destroy, h = _deferred_children.pop()
         destroy(h)
@@ -554,7 +587,7 @@ def _destroy_deferred() -> None:
 
 
 def _destroy_deferred_outside_capture() -> None:
-    if (_deferred_children or _deferred) and not _capturing():
+    if (_deferred_baths or _deferred_children or _deferred) and not _capturing():
         _destroy_deferred()
 
 
@@ -741,7 +774,7 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Draw, Molecular and Coulomb share: a handle created from a workspace
+    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Draw, Molecular and Coulomb share: a handle created from a workspace
     (kept alive here) over a table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
     the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -1100,6 +1133,69 @@ class Verlet(_ItemTableHandle):
     def state_device_ptr(self) -> int:
         p = ctypes.c_void_p()
         check(self._lib.cavmd_verlet_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_verlet_state_device_ptr")
+        return int(p.value)
+
+
+BATH_STATE_DTYPE_FIELDS = [("draws", "<u8"), ("coupled", "<u8"), ("reservoir", "<f8"), ("reserved", "<f8")]
+BATH_KEY_STRIDE = 0x9E3779B97F4A7C15
+
+
+def bath_state_dtype():
+    """numpy structured dtype with the layout of cavmd_bath_state (32 bytes)."""
+    import numpy as np
+    return np.dtype(BATH_STATE_DTYPE_FIELDS)
+
+
+def bath_item_check(item: BathItem) -> int:
+    """Status cavmd_bath_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_bath_item_check(ctypes.byref(item)))
+
+
+def bath_item_key(seed: int, i: int) -> int:
+    """The Philox key of item i under the object's seed: (seed + 0x9E3779B97F4A7C15 * (i + 1)) mod 2^64.  The stride is odd, so
+    the keys of 2^64 consecutive items are distinct."""
+    return (int(seed) + BATH_KEY_STRIDE * (int(i) + 1)) & 0xFFFFFFFFFFFFFFFF
+
+
+class Bath(_ItemTableHandle):
+    """Owns one cavmd_bath: the second half-step of an integrator batch with a Langevin bath on any set of particles of every
+    system, ONE kernel launch, the 3 N variates drawn inside it.  Created from a ``Verlet`` (kept alive here, with its
+    workspace) and closed before it; launched in the integrator's order."""
+    _ITEM, _PREFIX = BathItem, "cavmd_bath"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, verlet: "Verlet", items):
+        if verlet is None or not getattr(verlet, "_h", None) or not verlet._h.value:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_bath_create")
+        self._create(verlet, items)               # cavmd_bath_create(integrator, n_items, items, &handle)
+        self._verlet, self._ws = verlet, verlet._ws
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if _capturing():
+                _deferred_baths.append((self._lib.cavmd_bath_destroy, self._h))
+            else:
+                self._lib.cavmd_bath_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        _destroy_deferred_outside_capture()
+
+    def step_two(self, stream: int, inputs_ptr: int) -> None:
+        """One kernel, in place of ``Verlet.step_two``: net force, the row's and the group's baths, acceleration and kick."""
+        check(self._lib.cavmd_bath_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)), "cavmd_bath_step_two")
+
+    def read(self, stream: int = 0):
+        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_bath_state."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=bath_state_dtype())
+        check(self._lib.cavmd_bath_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_bath_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_bath_reset(self._h, ctypes.c_void_p(stream)), "cavmd_bath_reset")
+
+    def state_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        check(self._lib.cavmd_bath_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_bath_state_device_ptr")
         return int(p.value)
 
 

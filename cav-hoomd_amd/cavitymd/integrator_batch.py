@@ -18,7 +18,8 @@ evaluates, so that a captured graph of this package's kernels alone advances a t
 The step's inputs live in a ``(B, 8)`` float64 DEVICE tensor, ``inputs`` (row = dt, gamma, sqrt(6 gamma kT / dt), three
 variates uniform in [-1, 1), skip flag, one reserved word), read by both kernels when they run.  ``draw_inputs`` uses torch's
 generator, not HOOMD's RandomGenerator: the variates are not bit-comparable with a HOOMD run; everything after the draw is.
-The Langevin bath acts on at most one particle per system.  No CPU fallback: CPU tensors raise.
+The Langevin bath of this class acts on at most one particle per system; ``LangevinBathBatch`` (bath_batch.py) supplies step two
+with a bath on any set of particles.  No CPU fallback: CPU tensors raise.
 """
 from __future__ import annotations
 

@@ -1,7 +1,8 @@
 // cavmd_verlet.hip -- cavmd_verlet of include/cavmd.h: the velocity-Verlet half-steps of a batch of small systems, one launch
 // each; and cavmd_draw, which writes the input rows those half-steps (and the thermostat batch) read: seeded variates and the
-// step's dt, one launch per step.  Two of the eight objects built on an item table (cavmd_item_table.hpp); the workspace is
-// an incomplete type here.
+// step's dt, one launch per step; and cavmd_bath, created from an integrator, whose launch takes the place of the integrator's
+// second half-step with a Langevin bath on any set of particles.  Three of the nine objects built on an item table
+// (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -12,6 +13,7 @@
 #include "cavmd.h"
 #include "cavmd_verlet_batch_kernel.hpp"
 #include "cavmd_draw_kernel.hpp"
+#include "cavmd_bath_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -20,6 +22,7 @@ using namespace cavmd;
 struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N descending
 {
     DeviceArray<VerletState> d_state; // n states, indexed by item
+    unsigned baths = 0;               // live cavmd_bath objects created from this integrator: cavmd_verlet_destroy refuses on them
 
     cavmd_verlet()
         : ItemTable(cavmd_verlet_item_check, [](const cavmd_verlet_item& it) { return it.N; },
@@ -71,8 +74,31 @@ struct cavmd_draw : ItemTable<cavmd_draw_item, DrawRow> // items cost the same: 
     }
 };
 
+// ---- a Langevin bath on any set of particles of every item, drawn in step two (cavmd_bath_kernel.hpp) --------------------------
+// Item i belongs to item i of the integrator `v`, whose rows, launch order and states the one kernel reads as well; the launch
+// goes through the integrator's table, which notes the stream, and is noted here too.
+struct cavmd_bath : ItemTable<cavmd_bath_item, BathRow>
+{
+    DeviceArray<BathState> d_state; // n states, indexed by item
+    cavmd_verlet* v = nullptr;
+
+    cavmd_bath()
+        : ItemTable(cavmd_bath_item_check, [](const cavmd_bath_item& it) { return it.N; },
+                    uploaded_as_it_is<cavmd_bath_item, BathRow>)
+    {
+    }
+};
+
 namespace
 {
+static_assert(offsetof(cavmd_bath_item, d_gamma) == offsetof(BathRow, gamma) && offsetof(cavmd_bath_item, seed) == offsetof(BathRow, seed)
+                  && offsetof(cavmd_bath_item, kT) == offsetof(BathRow, kT) && offsetof(cavmd_bath_item, N) == offsetof(BathRow, n)
+                  && sizeof(cavmd_bath_item) == sizeof(BathRow),
+              "bath item layout");
+static_assert(sizeof(cavmd_bath_state) == sizeof(BathState) && offsetof(cavmd_bath_state, draws) == offsetof(BathState, draws)
+                  && offsetof(cavmd_bath_state, coupled) == offsetof(BathState, coupled)
+                  && offsetof(cavmd_bath_state, reservoir) == offsetof(BathState, reservoir),
+              "the bath states are read out as they are");
 static_assert(offsetof(cavmd_draw_item, d_verlet_row) == offsetof(DrawRow, verlet_row)
                   && offsetof(cavmd_draw_item, d_bussi_row) == offsetof(DrawRow, bussi_row)
                   && offsetof(cavmd_draw_item, d_records) == offsetof(DrawRow, records)
@@ -178,6 +204,8 @@ int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_
 
 int cavmd_verlet_destroy(cavmd_verlet* v)
 {
+    if (v && v->baths != 0) // as cavmd_destroy has it for its dependents: nothing is freed while a bath of this integrator lives
+        return CAVMD_ERR_INVALID_VALUE;
     return destroy_table(v);
 }
 
@@ -312,6 +340,118 @@ int cavmd_draw_state_device_ptr(cavmd_draw* d, const cavmd_draw_state** out)
     if (!d || !out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = reinterpret_cast<const cavmd_draw_state*>(d->d_state.ptr);
+    return CAVMD_OK;
+}
+
+// ---- cavmd_bath ------------------------------------------------------------------------------------------------------------
+int cavmd_bath_item_check(const cavmd_bath_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved0 != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 4; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    if ((uintptr_t)it->d_gamma & 7)
+        return CAVMD_ERR_INVALID_VALUE;
+    if ((it->d_gamma == nullptr) != (it->N == 0))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (!finite_nonnegative(it->kT))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_bath_create(cavmd_verlet* v, size_t n_items, const cavmd_bath_item* h_items, cavmd_bath** out)
+{
+    if (!out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = nullptr;
+    if (!v || !h_items || n_items != v->n)
+        return CAVMD_ERR_INVALID_VALUE;
+    const int st = check_items(h_items, n_items, cavmd_bath_item_check);
+    if (st != CAVMD_OK)
+        return st;
+    cavmd_bath* b = new (std::nothrow) cavmd_bath();
+    if (!b)
+        return (int)hipErrorOutOfMemory;
+    b->adopt(v->device, h_items, n_items);
+    hipError_t e;
+    {
+        DeviceGuard guard(b->device);
+        e = b->upload();
+        if (e == hipSuccess)
+            e = b->d_state.alloc_zeroed(b->n);
+        if (e == hipSuccess)
+            e = hipDeviceSynchronize(); // the zeroing memset is done before any stream of the caller's launches
+    }
+    if (e != hipSuccess)
+    {
+        destroy_table(b);
+        return hip_status(e);
+    }
+    b->v = v;
+    v->baths += 1;
+    *out = b;
+    return CAVMD_OK;
+}
+
+int cavmd_bath_destroy(cavmd_bath* b)
+{
+    if (b && b->v)
+        b->v->baths -= 1;
+    return destroy_table(b);
+}
+
+int cavmd_bath_set_items(cavmd_bath* b, size_t first, size_t count, const cavmd_bath_item* h_items)
+{
+    return b ? b->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_bath_step_two(cavmd_bath* b, void* stream_, const cavmd_verlet_input* d_inputs)
+{
+    if (!b || !d_inputs || ((uintptr_t)d_inputs & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    cavmd_verlet* v = b->v;
+    const int st = v->launch((hipStream_t)stream_, verlet_step_two_bath_kernel<256>, dim3((unsigned)v->n), dim3(256), 0, v->d_rows.ptr,
+                             v->d_order.ptr, reinterpret_cast<const VerletInput*>(d_inputs), v->d_state.ptr, b->d_rows.ptr,
+                             b->d_state.ptr);
+    if (st == CAVMD_OK) // the integrator has noted the stream; so does the bath, for its own set_items and destroy
+    {
+        b->last_stream = (hipStream_t)stream_;
+        b->enqueued = true;
+    }
+    return st;
+}
+
+int cavmd_bath_read(cavmd_bath* b, void* stream_, cavmd_bath_state* out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(b->device);
+    const int st = sync_uncaptured((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    CAVMD_HIP_TRY(hipMemcpy(out, b->d_state.ptr, sizeof(BathState) * b->n, hipMemcpyDeviceToHost));
+    return CAVMD_OK;
+}
+
+int cavmd_bath_reset(cavmd_bath* b, void* stream_)
+{
+    if (!b)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(b->device);
+    CAVMD_HIP_TRY(hipMemsetAsync(b->d_state.ptr, 0, sizeof(BathState) * b->n, (hipStream_t)stream_));
+    return CAVMD_OK;
+}
+
+int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out)
+{
+    if (!b || !out)
+        return CAVMD_ERR_INVALID_VALUE;
+    *out = reinterpret_cast<const cavmd_bath_state*>(b->d_state.ptr);
     return CAVMD_OK;
 }
 

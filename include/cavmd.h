@@ -715,8 +715,9 @@ CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cav
  *     langevin_reservoir grows by 3 gamma kT dt / (m (1 - x)) per step on average, because the tally is taken with the
  *     velocity from BEFORE the kick, with which the step's variates are uncorrelated.
  * (tests/langevin_twin.py derives the three; tests/test_gpu_langevin_batch.py holds the kernels to them.)
- * pos.w (the type tag) and vel.w (the mass) are never written.  Out of scope: Langevin on more than one particle per system
- * (3 N variates per step), rotational degrees of freedom, triclinic boxes. */
+ * pos.w (the type tag) and vel.w (the mass) are never written.  Langevin on more than one particle per system is the next
+ * section's (cavmd_bath_*: the 3 N variates are drawn inside step two).  Out of scope: rotational degrees of freedom, triclinic
+ * boxes. */
 typedef struct cavmd_verlet_item         /* 128 B; all pointers DEVICE pointers; the arrays of one item must not overlap */
 {
     cavmd_double4* d_pos;                /* HOOMD Scalar4 positions (wrapped), type tag in .w; 16-byte aligned */
@@ -783,6 +784,88 @@ CAVMD_API int cavmd_verlet_read(cavmd_verlet* v, void* stream, cavmd_verlet_stat
 CAVMD_API int cavmd_verlet_reset(cavmd_verlet* v, void* stream);
 /* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out);
+
+/* ---- a Langevin bath on any set of particles of a batch, drawn in step two: the driver's --molecular-bath langevin ------------ */
+/* The reference's driver has three choices for --molecular-bath (examples/05_advanced_run.py:649-666): `bussi` is the thermostat
+ * batch, `none` the integrator alone, and `langevin` HOOMD-blue's Langevin method on every molecular particle with
+ * tally_reservoir_energy=True.  This section is the third: an object created from an integrator whose ONE launch takes the
+ * place of cavmd_verlet_step_two in a step (it is never called in addition to it) and couples any subset of each item's
+ * particles to a bath.  The 3 N variates are drawn inside the kernel from the counter-based generator of the next section
+ * (Philox4x32-10, its item 1) and never touch memory; nothing new is launched.  A captured step is then {cavmd_draw_fill,
+ * cavmd_verlet_step_one, the forces, cavmd_bath_step_two, cavmd_recorder_record, ...}; for --molecular-bath langevin
+ * --cavity-bath langevin the cavity particle simply carries its own gamma in d_gamma.  d_net_force receives the forces WITHOUT
+ * any bath term, so the adaptive dt's force_mass_sum excludes the bath, as the reference's does.  One 256-thread workgroup per
+ * item, in the integrator's launch order; no workgroup waits for another, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ *
+ * The expressions below ARE the contract (tests/bath_mirror.py restates them); one IEEE fp64 rounding per operation, no FMA.
+ * Items 1, 2, 3, 5, 6 and 7 of step two are unchanged: a row with skip != 0, or an item with N == 0, leaves the item and its
+ * bath state untouched; d_net_force receives the sum of the force arrays; steps += 1.  Item 4 stays what it is for
+ * j == langevin_index with langevin_gamma != 0: that particle takes the ROW's bath and not this object's.  New, for every other
+ * particle j with j < the bath item's N and gamma_j > 0 (anything else, a NaN included, is not coupled and adds nothing), `draws`
+ * being the item's counter in DEVICE memory when the kernel RUNS:
+ *   1. Generator.  Philox4x32-10 as in the next section.  Key = (seed low, seed high) of the ITEM.  Counter = (draws low,
+ *      draws high, j, 0x80000000 + b), b = 0, 1: the fourth word keeps these counters apart from cavmd_draw's purposes (all below
+ *      48) even under equal keys.
+ *   2. Variates, as the next section's item 2: u_x from w0,w1 and u_y from w2,w3 of block 0, u_z from w0,w1 of block 1, each
+ *      2 * (k * 2^-53) - 1, in [-1, 1).
+ *   3. coeff_j = sqrt(((6 * gamma_j) * kT) / dt), division and square root correctly rounded.
+ *   4. bd_c = u_c * coeff_j - gamma_j * v_c with v from BEFORE the kick;  F_c = F_c + bd_c;
+ *      tally_j = (bd_x * v_x + bd_y * v_y) + bd_z * v_z
+ *   5. Per item: coupled = the number of such particles; T = the sum of their tally_j, a compensated (double-double) sum in an
+ *      order that depends on N only -- not on the batch, the item's place in it, the compute unit, or eager launch versus graph
+ *      replay -- rounded once, within 2 ulp of the exact sum of those addends;  reservoir = reservoir - T * dt;  draws += 1.
+ *      An item with d_gamma NULL has none of this done and none of its state written.
+ * Two properties.  An item without a bath (d_gamma NULL, or no gamma_j > 0) gets from cavmd_bath_step_two exactly the bytes
+ * cavmd_verlet_step_two gives it.  The closed forms of the Langevin paragraph above hold for every coupled free particle, with
+ * its own gamma_j and mass (tests/bath_twin.py; tests/test_gpu_bath_batch.py holds the kernel to them).
+ * The limits.  The variates are Philox with the counter layout published here, not HOOMD's RandomGenerator: no draw is
+ * bit-comparable with a HOOMD run; everything after the draw is held to the expressions above.  Rotational degrees of freedom
+ * and triclinic boxes stay out of scope. */
+typedef struct cavmd_bath_item           /* 64 B; pointers are DEVICE pointers */
+{
+    const double* d_gamma;   /* N doubles, 8-byte aligned, caller-owned: the friction of every particle (HOOMD's per-type gamma,
+                                spelled out per particle; a filter is "gamma 0 outside it").  NULL with N == 0: no bath on this item */
+    uint64_t seed;           /* the Philox key of THIS item: its variates do not depend on its place in a batch */
+    double kT;               /* finite, >= 0 */
+    uint32_t N;              /* doubles behind d_gamma; particles at or beyond it are not coupled; <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t reserved0;      /* 0 */
+    uint64_t reserved[4];    /* 0 */
+} cavmd_bath_item;
+typedef struct cavmd_bath_state          /* 32 B, one per item, device memory */
+{
+    uint64_t draws;          /* second half-steps this object applied to the item (the generator's step counter) */
+    uint64_t coupled;        /* particles that received the bath in the last such step */
+    double reservoir;        /* HOOMD's reservoir energy of the Langevin method, summed over the item's coupled particles */
+    double reserved;
+} cavmd_bath_state;
+typedef struct cavmd_bath cavmd_bath;    /* opaque; belongs to the integrator it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * reserved words that are not 0, a d_gamma not 8-byte aligned, d_gamma NULL with N != 0 or non-NULL with N == 0, a kT that is
+ * negative or not finite; CAVMD_ERR_CAPACITY for N above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_bath_item_check(const cavmd_bath_item* item);
+/* Item i of the bath belongs to item i of the integrator `v`: n_items must equal the integrator's item count
+ * (CAVMD_ERR_INVALID_VALUE otherwise, as for a null `v`, `h_items` or `out`).  Validates the rows in HOST memory, copies the table
+ * to the integrator's device (set-up time), allocates one zeroed state per item and synchronises the device.  While a bath lives,
+ * cavmd_verlet_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing: the rule cavmd_destroy has for its dependents. */
+CAVMD_API int cavmd_bath_create(cavmd_verlet* v, size_t n_items, const cavmd_bath_item* h_items, cavmd_bath** out);
+/* Synchronises the stream of the last cavmd_bath_step_two (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_bath_destroy(cavmd_bath* b);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last cavmd_bath_step_two;
+ * nothing is changed if a row is refused; the items' states are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being
+ * captured, and for a range outside the table. */
+CAVMD_API int cavmd_bath_set_items(cavmd_bath* b, size_t first, size_t count, const cavmd_bath_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`, in place of cavmd_verlet_step_two: the same argument checks
+ * (CAVMD_ERR_INVALID_VALUE for a null or not 8-byte aligned d_inputs), the same launch order (N descending), no allocation, no
+ * copy, no host wait; may be captured into a hipGraph, and a replay draws like an eager call.  The integrator notes the stream:
+ * cavmd_verlet_set_items and cavmd_verlet_destroy wait for it too. */
+CAVMD_API int cavmd_bath_step_two(cavmd_bath* b, void* stream, const cavmd_verlet_input* d_inputs);
+/* Synchronises `stream`, then out = the n_items states.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
+CAVMD_API int cavmd_bath_read(cavmd_bath* b, void* stream, cavmd_bath_state* out);
+/* Zero the states of all items (ordered on `stream`), `draws` included: after it the same variates come again. */
+CAVMD_API int cavmd_bath_reset(cavmd_bath* b, void* stream);
+/* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out);
 
 /* ---- the step inputs of a batch, drawn on the device: seeded variates and an adaptive dt in ONE launch per step ------------- */
 /* What fills the two input tables above and below when a captured step replays: for every registered item, ONE kernel writes
