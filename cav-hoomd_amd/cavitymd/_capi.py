@@ -148,6 +148,24 @@ class BathState(ctypes.Structure):
                 ("reserved", ctypes.c_double)]
 
 
+class LedgerItem(ctypes.Structure):
+    """cavmd_ledger_item (128 bytes): one system of an energy ledger; all pointers are DEVICE pointers."""
+    _fields_ = [("d_result", ctypes.c_void_p), ("d_vel", ctypes.c_void_p), ("d_members", ctypes.c_void_p),
+                ("n_members", ctypes.c_uint32), ("N", ctypes.c_uint32), ("d_energy", ctypes.c_void_p * 4),
+                ("d_reservoir", ctypes.c_void_p * 4), ("d_time", ctypes.c_void_p), ("dof", ctypes.c_double),
+                ("add_cavity_kinetic", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
+class LedgerRow(ctypes.Structure):
+    """cavmd_ledger_row (192 bytes): one row of an energy ledger's time series."""
+    _fields_ = [("call", ctypes.c_uint64), ("n_terms", ctypes.c_uint32), ("n_reservoirs", ctypes.c_uint32),
+                ("time", ctypes.c_double), ("potential", ctypes.c_double * 4), ("cavity", ctypes.c_double * 3),
+                ("cavity_potential", ctypes.c_double), ("potential_total", ctypes.c_double), ("kinetic_group", ctypes.c_double),
+                ("kinetic_cavity", ctypes.c_double), ("kinetic_total", ctypes.c_double), ("system_total", ctypes.c_double),
+                ("reservoir", ctypes.c_double * 4), ("reservoir_total", ctypes.c_double), ("universe_total", ctypes.c_double),
+                ("temperature", ctypes.c_double), ("reserved", ctypes.c_double)]
+
+
 class DrawItem(ctypes.Structure):
     """cavmd_draw_item (160 bytes): one system of a draw object; the four pointers are DEVICE pointers."""
     _fields_ = [("d_verlet_row", ctypes.c_void_p), ("d_bussi_row", ctypes.c_void_p), ("d_records", ctypes.c_void_p),
@@ -273,6 +291,20 @@ def bath_item(gamma_ptr=0, N=0, kT=0.0, seed=0) -> "BathItem":
     it = BathItem()
     it.d_gamma, it.N = gamma_ptr or None, int(N)
     it.kT, it.seed = float(kT), int(seed)
+    return it
+
+
+def ledger_item(result_ptr=0, vel_ptr=0, members_ptr=0, n_members=0, N=0, energy_ptrs=(), reservoir_ptrs=(), time_ptr=0, dof=0.0,
+                add_cavity_kinetic=0) -> "LedgerItem":
+    """One system of an energy ledger: up to four force arrays whose .w is summed and up to four addresses of one double."""
+    it = LedgerItem()
+    it.d_result, it.d_vel, it.d_members, it.d_time = result_ptr or None, vel_ptr or None, members_ptr or None, time_ptr or None
+    it.n_members, it.N = int(n_members), int(N)
+    for k, p in enumerate(energy_ptrs):
+        it.d_energy[k] = p or None
+    for k, p in enumerate(reservoir_ptrs):
+        it.d_reservoir[k] = p or None
+    it.dof, it.add_cavity_kinetic = float(dof), int(add_cavity_kinetic)
     return it
 
 
@@ -412,6 +444,15 @@ _PROTOTYPES = {
     "cavmd_bath_read": (_ci, [_vp, _vp, _vp]),
     "cavmd_bath_reset": (_ci, [_vp, _vp]),
     "cavmd_bath_state_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_ledger_item_check": (_ci, [_P(LedgerItem)]),
+    "cavmd_ledger_create": (_ci, [_vp, _sz, _P(LedgerItem), _sz, _u64, _dbl, _P(_vp)]),
+    "cavmd_ledger_destroy": (_ci, [_vp]),
+    "cavmd_ledger_set_items": (_ci, [_vp, _sz, _sz, _P(LedgerItem)]),
+    "cavmd_ledger_record": (_ci, [_vp, _vp]),
+    "cavmd_ledger_rows": (_ci, [_vp, _vp, _vp]),
+    "cavmd_ledger_read": (_ci, [_vp, _vp, _sz, _sz, _u64, _sz, _vp]),
+    "cavmd_ledger_reset": (_ci, [_vp, _vp]),
+    "cavmd_ledger_device_ptr": (_ci, [_vp, _P(_vp), _P(_vp)]),
     "cavmd_draw_item_check": (_ci, [_P(DrawItem)]),
     "cavmd_draw_create": (_ci, [_vp, _u64, _sz, _P(DrawItem), _P(_vp)]),
     "cavmd_draw_destroy": (_ci, [_vp]),
@@ -774,7 +815,7 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Draw, Molecular and Coulomb share: a handle created from a workspace
+    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Ledger, Draw, Molecular and Coulomb share: a handle created from a workspace
     (kept alive here) over a table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
     the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -1197,6 +1238,67 @@ class Bath(_ItemTableHandle):
         p = ctypes.c_void_p()
         check(self._lib.cavmd_bath_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_bath_state_device_ptr")
         return int(p.value)
+
+
+LEDGER_ROW_DTYPE_FIELDS = [("call", "<u8"), ("n_terms", "<u4"), ("n_reservoirs", "<u4"), ("time", "<f8"), ("potential", "<f8", (4,)),
+                           ("cavity", "<f8", (3,)), ("cavity_potential", "<f8"), ("potential_total", "<f8"),
+                           ("kinetic_group", "<f8"), ("kinetic_cavity", "<f8"), ("kinetic_total", "<f8"), ("system_total", "<f8"),
+                           ("reservoir", "<f8", (4,)), ("reservoir_total", "<f8"), ("universe_total", "<f8"),
+                           ("temperature", "<f8"), ("reserved", "<f8")]
+
+
+def ledger_row_dtype():
+    """numpy structured dtype with the layout of cavmd_ledger_row (192 bytes)."""
+    import numpy as np
+    return np.dtype(LEDGER_ROW_DTYPE_FIELDS)
+
+
+def ledger_item_check(item: LedgerItem) -> int:
+    """Status cavmd_ledger_create would give this row (host arithmetic only: needs no device)."""
+    return int(load().cavmd_ledger_item_check(ctypes.byref(item)))
+
+
+class Ledger(_ItemTableHandle):
+    """Owns one cavmd_ledger: every term of the conserved energy of B independent small systems appended, by ONE kernel launch
+    per call, to a time series in device memory whose write position lives on the device (a graph replay appends a new row).
+    Launched by max(N, n_members) descending."""
+    _ITEM, _PREFIX = LedgerItem, "cavmd_ledger"
+    _size = staticmethod(lambda it: max(int(it.N), int(it.n_members)))
+
+    def __init__(self, workspace: Workspace, items, capacity: int, period: int, kB: float):
+        self.capacity, self.period, self.kB = int(capacity), int(period), float(kB)
+        if self.capacity < 0 or self.period < 0:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_ledger_create")
+        self._create(workspace, items, self.capacity, self.period, self.kB)
+
+    def record(self, stream: int = 0) -> None:
+        """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
+        check(self._lib.cavmd_ledger_record(self._h, ctypes.c_void_p(stream)), "cavmd_ledger_record")
+
+    def rows(self, stream: int = 0):
+        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=np.uint64)
+        check(self._lib.cavmd_ledger_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_ledger_rows")
+        return out
+
+    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
+        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
+        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_ledger_row."""
+        import numpy as np
+        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=ledger_row_dtype())
+        check(self._lib.cavmd_ledger_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items), int(first_row),
+                                          int(n_rows), ctypes.c_void_p(out.ctypes.data)), "cavmd_ledger_read")
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_ledger_reset(self._h, ctypes.c_void_p(stream)), "cavmd_ledger_reset")
+
+    def device_ptr(self):
+        """(series, rows): device addresses of the series (item-major, `capacity` rows each) and of the row counters."""
+        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.cavmd_ledger_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)), "cavmd_ledger_device_ptr")
+        return int(rec.value), int(rows.value)
 
 
 DRAW_STATE_DTYPE_FIELDS = [("draws", "<u8"), ("dt", "<f8"), ("elapsed", "<f8"), ("tolerance", "<f8"), ("exhausted", "<u8"),

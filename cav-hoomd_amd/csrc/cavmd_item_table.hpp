@@ -1,8 +1,8 @@
-// Host-only: what the nine "batch of small systems" objects share, each in a unit of its own (cavmd_batch.hip,
+// Host-only: what the ten "batch of small systems" objects share, each in a unit of its own (cavmd_batch.hip,
 // cavmd_bussi_batch.hip, cavmd_recorder.hip, cavmd_field_recorder.hip, cavmd_verlet.hip, cavmd_molecular.hip,
 // cavmd_coulomb.hip) but cavmd_draw and cavmd_bath, which live with the integrator whose input rows the one writes and whose
-// second half-step the other supplies -- how a table of items lives on the host and on the device, how the object is created (create_table),
-// launched (ItemTable::launch), tied to its workspace and released (destroy_table); for the two recorders, the per-item ring
+// second half-step the other supplies, and cavmd_ledger, which lives with the recorder whose shape and kinetic sum it has -- how a table of items lives on the host and on the device, how the object is created (create_table),
+// launched (ItemTable::launch), tied to its workspace and released (destroy_table); for the two recorders and the ledger, the per-item ring
 // of records behind it (SeriesTable); for the two force batches, the tables derived from the items that their kernels find
 // through a header at a fixed device address and that set_items replaces together (LinkedTable).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.

@@ -1,5 +1,7 @@
-// cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory;
+// and cavmd_ledger, the energy ledger, which has the recorder's shape and calls its kinetic-energy code (two objects in one
+// unit, as cavmd_verlet.hip holds three).  Both are built on an item table (cavmd_item_table.hpp); the workspace is an
+// incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -10,6 +12,7 @@
 
 #include "cavmd.h"
 #include "cavmd_recorder_kernel.hpp"
+#include "cavmd_ledger_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -122,6 +125,129 @@ int cavmd_recorder_reset(cavmd_recorder* r, void* stream_)
 int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, const uint64_t** rows)
 {
     return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
+}
+
+} // extern "C"
+
+// ---- the energy ledger of a batch: every term of the conserved energy per step (cavmd_ledger_kernel.hpp) ----------------------
+// the recorder's shape: launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
+struct cavmd_ledger : SeriesTable<cavmd_ledger_item, LedgerItem, cavmd_ledger_row>
+{
+    uint64_t period = 1;
+    double kB = 0.0;
+
+    cavmd_ledger()
+        : SeriesTable(kRecCounters, cavmd_ledger_item_check,
+                      [](const cavmd_ledger_item& it) { return std::max(it.N, it.n_members); },
+                      uploaded_as_it_is<cavmd_ledger_item, LedgerItem>)
+    {
+    }
+
+    int capacity_status(size_t n_items) const
+    {
+        return capacity > kRecorderMaxBytes / sizeof(cavmd_ledger_row) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        return alloc_series();
+    }
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_ledger_row) == 192 && offsetof(cavmd_ledger_row, potential) == 24
+                  && offsetof(cavmd_ledger_row, reservoir) == 128 && offsetof(cavmd_ledger_row, reserved) == 184,
+              "ledger row layout");
+static_assert(sizeof(cavmd_ledger_item) == sizeof(LedgerItem), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_ledger_item, d_result) == offsetof(LedgerItem, res)
+                  && offsetof(cavmd_ledger_item, d_vel) == offsetof(LedgerItem, vel2)
+                  && offsetof(cavmd_ledger_item, d_members) == offsetof(LedgerItem, members)
+                  && offsetof(cavmd_ledger_item, n_members) == offsetof(LedgerItem, n_members)
+                  && offsetof(cavmd_ledger_item, N) == offsetof(LedgerItem, N)
+                  && offsetof(cavmd_ledger_item, d_energy) == offsetof(LedgerItem, energy)
+                  && offsetof(cavmd_ledger_item, d_reservoir) == offsetof(LedgerItem, reservoir)
+                  && offsetof(cavmd_ledger_item, d_time) == offsetof(LedgerItem, time)
+                  && offsetof(cavmd_ledger_item, dof) == offsetof(LedgerItem, dof)
+                  && offsetof(cavmd_ledger_item, add_cavity_kinetic) == offsetof(LedgerItem, add_cavity_kinetic),
+              "ledger item layout");
+static_assert(sizeof(((cavmd_ledger_item*)0)->d_energy) == sizeof(void*) * kLedgerTerms
+                  && sizeof(((cavmd_ledger_item*)0)->d_reservoir) == sizeof(void*) * kLedgerReservoirs,
+              "four terms, four reservoirs");
+} // namespace
+
+extern "C"
+{
+
+int cavmd_ledger_item_check(const cavmd_ledger_item* it)
+{
+    if (!it || it->reserved0 != 0 || it->reserved != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_result & 15) || ((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_members & 3)
+        || ((uintptr_t)it->d_time & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < kLedgerTerms; ++k)
+        if (((uintptr_t)it->d_energy[k] & 15) || (k > 0 && it->d_energy[k] && !it->d_energy[k - 1]))
+            return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < kLedgerReservoirs; ++k)
+        if (((uintptr_t)it->d_reservoir[k] & 7) || (k > 0 && it->d_reservoir[k] && !it->d_reservoir[k - 1]))
+            return CAVMD_ERR_INVALID_VALUE;
+    if (!finite_nonnegative(it->dof) || it->add_cavity_kinetic > 1)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N || it->n_members > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_ledger_create(cavmd_workspace* ws, size_t n_items, const cavmd_ledger_item* h_items, size_t capacity, uint64_t period,
+                        double kB, cavmd_ledger** out)
+{
+    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
+    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_ledger* l) {
+        l->capacity = capacity;
+        l->period = period;
+        l->kB = kB;
+    });
+}
+
+int cavmd_ledger_destroy(cavmd_ledger* l)
+{
+    return destroy_table(l);
+}
+
+int cavmd_ledger_set_items(cavmd_ledger* l, size_t first, size_t count, const cavmd_ledger_item* h_items)
+{
+    return l ? l->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_ledger_record(cavmd_ledger* l, void* stream_)
+{
+    if (!l)
+        return CAVMD_ERR_INVALID_VALUE;
+    return l->launch((hipStream_t)stream_, ledger_batch_kernel<256>, dim3((unsigned)l->n), dim3(256), 0, l->d_rows.ptr,
+                     l->d_order.ptr, (unsigned)l->n, (uint64_t)l->capacity, l->period, l->kB, l->d_series.ptr, l->d_counters.ptr);
+}
+
+int cavmd_ledger_rows(cavmd_ledger* l, void* stream_, uint64_t* out)
+{
+    return (l && out) ? l->rows((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_ledger_read(cavmd_ledger* l, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
+                      cavmd_ledger_row* out)
+{
+    if (!l || !out || n_items == 0 || n_rows == 0 || first_item >= l->n || n_items > l->n - first_item)
+        return CAVMD_ERR_INVALID_VALUE;
+    return l->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
+}
+
+int cavmd_ledger_reset(cavmd_ledger* l, void* stream_)
+{
+    return l ? l->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_ledger_device_ptr(cavmd_ledger* l, const cavmd_ledger_row** series, const uint64_t** rows)
+{
+    return l ? l->device_ptr(series, rows) : CAVMD_ERR_INVALID_VALUE;
 }
 
 } // extern "C"

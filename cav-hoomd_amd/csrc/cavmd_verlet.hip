@@ -1,7 +1,7 @@
 // cavmd_verlet.hip -- cavmd_verlet of include/cavmd.h: the velocity-Verlet half-steps of a batch of small systems, one launch
 // each; and cavmd_draw, which writes the input rows those half-steps (and the thermostat batch) read: seeded variates and the
 // step's dt, one launch per step; and cavmd_bath, created from an integrator, whose launch takes the place of the integrator's
-// second half-step with a Langevin bath on any set of particles.  Three of the nine objects built on an item table
+// second half-step with a Langevin bath on any set of particles.  Three of the ten objects built on an item table
 // (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,9 @@
 """A complete MD step of B replicas of the reference's model WITH all three forces of its driver, captured into ONE graph:
 velocity-Verlet step one, the cavity force, the harmonic bonds and Lennard-Jones pairs, the Ewald Coulomb forces (two launches),
-step two (with the Langevin bath on the cavity particle), the recorder and the Bussi thermostat -- eight kernels of this library
-per step for all replicas, plus the device-side draws of the variates.  It is examples/batch_molecular_md_in_one_graph.py with
+step two (with the Langevin bath on the cavity particle), the recorder, the energy ledger and the Bussi thermostat -- nine kernels
+of this library per step for all replicas, plus the device-side draws of the variates.  The ledger writes every term of the
+conserved energy per step -- the three potentials, the kinetic energies and what both baths took -- so the conserved quantity is
+a series, not a difference between the first and the last step.  It is examples/batch_molecular_md_in_one_graph.py with
 ``CoulombForceBatch`` as a third force array of the integrator's items: the charges that drive the cavity dipole now also act on
 each other.  The Coulomb forces are the Ewald sum HOOMD-blue's PPPM approximates; parity with a PPPM run is not pinned.
 
@@ -54,8 +56,8 @@ def main():
     recorder = cavitymd.BatchRecorder(cavity, velocities, capacity=max(steps, 1))
     thermostat = cavitymd.BussiReservoirBatch(kT=kT, tau=1000.0)           # the molecular bath; the photon has its own
     thermostat.attach(velocities, translational_dof=3.0 * len(molecules[0]) - 3.0, members=molecules)
-    potential = torch.zeros((max(steps, 1), B), dtype=torch.float64, device="cuda")
-    row = torch.zeros((), dtype=torch.int64, device="cuda")
+    ledger = cavitymd.BatchEnergyLedger(cavity, velocities, terms=[("molecular", molecular), ("coulomb", coulomb)],
+                                        reservoirs=[("bussi", thermostat), ("langevin", integrator)], capacity=max(steps, 1))
 
     def step():
         integrator.draw_inputs(dt, gamma=1e-3, kT=kT)                      # three uniforms per system, drawn on the device
@@ -65,8 +67,7 @@ def main():
         coulomb.compute()                                                  # two kernels: structure factors, then Coulomb forces
         integrator.step_two()                                              # one kernel: sum of the three, bath, a = F / m, kick
         recorder.record()                                                  # one kernel: one row per system into the series
-        potential.index_copy_(0, row.reshape(1), (molecular.potential_energy() + coulomb.potential_energy())[None])   # kept on the device
-        row.add_(1)
+        ledger.record()                                                    # one kernel: every term of the conserved energy
         thermostat.draw_inputs(0, dt)
         thermostat.step_async()                                            # one kernel: the thermostat step of all B systems
 
@@ -76,7 +77,6 @@ def main():
     integrator.prime()                                                     # a = F / m once, as HOOMD does at the start of a run
     integrator.draw_inputs(dt, gamma=1e-3, kT=kT)                          # warm-up of the draws outside the capture
     thermostat.draw_inputs(0, dt)
-    molecular.potential_energy() + coulomb.potential_energy()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -85,7 +85,8 @@ def main():
         graph.replay()
     state = integrator.state()
     series = recorder.read()                                               # (B, steps) rows, one copy after all the replays
-    U = potential.cpu().numpy().T                                          # (B, steps)
+    energy = ledger.read()                                                 # (B, steps) rows of the energy ledger
+    U = energy["molecular"] + energy["coulomb"]                            # (B, steps)
     print(f"B={B}: {int(state['steps'][0])} MD steps per system from one captured graph, "
           f"{int(state['out_of_box'].sum())} coordinates left outside a box")
     # the conserved quantity: H plus what the two baths took (the thermostat's reservoir and the Langevin method's)
@@ -98,6 +99,11 @@ def main():
     drift = (H[:, -1] + baths) - H[:, 0]
     print(f"drift of H + reservoirs over {steps} steps, relative to max |H|: worst system {np.abs(drift / scale).max():.3e}, "
           f"mean {np.abs(drift / scale).mean():.3e}")
+    # the same quantity as a series: the ledger's universe_total of every step (its reservoirs are those the step's kernels saw)
+    universe = energy["universe_total"]
+    excursion = np.abs(universe - universe[:, :1]).max(axis=1) / np.abs(energy["system_total"]).max(axis=1)
+    print(f"universe_total over the whole series, worst excursion from its first row relative to max |system_total|: worst system "
+          f"{excursion.max():.3e}, mean {excursion.mean():.3e}")
 
 
 if __name__ == "__main__":

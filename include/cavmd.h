@@ -27,6 +27,8 @@
  *                               src/cavitymd/analysis.py:425-, 1285-1417, 1424-; src/cavitymd/simulation.py:66-92
  *                                                                   cavmd_recorder_create / cavmd_recorder_record /
  *                                                                   cavmd_recorder_read (a time series in device memory)
+ *   EnergyTracker's row (every potential, kinetic and reservoir term, universe_total_energy), per step and replica
+ *                               src/cavitymd/analysis.py:425-1046   cavmd_ledger_create / cavmd_ledger_record / cavmd_ledger_read
  *   FieldAutocorrelationTracker, per step and replica
  *                               src/cavitymd/analysis.py:260-418    cavmd_field_recorder_create / cavmd_field_recorder_record /
  *                                                                   cavmd_field_recorder_read (rho(k), F(k,t), references)
@@ -866,6 +868,108 @@ CAVMD_API int cavmd_bath_read(cavmd_bath* b, void* stream, cavmd_bath_state* out
 CAVMD_API int cavmd_bath_reset(cavmd_bath* b, void* stream);
 /* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out);
+
+/* ---- the energy ledger of a batch: every term of the conserved energy per step, recorded on the device in ONE launch ---------- */
+/* What the reference's EnergyTracker (src/cavitymd/analysis.py:425-1046) writes per output step for every replica -- the
+ * potential of every force, the three cavity energies, the molecular, cavity and total kinetic energy, the system total, the
+ * reservoir energy of every bath and universe_total_energy, the column it marks [CONSERVED] -- as ONE launch for all systems that
+ * appends one 192-byte row per system to a time series kept in DEVICE memory.  One 256-thread workgroup per item; the write
+ * position lives on the device, so a hipGraph replay appends a NEW row each time, exactly as cavmd_recorder_record does, and the
+ * host reads the series when it likes.  Every pointer of an item is a DEVICE pointer that is read when the kernel RUNS: the .w
+ * column of the force arrays (each particle's share of the energy), the cavmd_result block, the velocities, and single doubles
+ * inside the state arrays of the objects above and below (&cavmd_bussi_device_state[i].reservoir_translational,
+ * &cavmd_verlet_state[i].langevin_reservoir, &cavmd_bath_state[i].reservoir, &cavmd_draw_state[i].elapsed).  The kernel writes
+ * nothing but the series and the counters; no workgroup waits for another, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ *
+ * The expressions in cavmd_ledger_row ARE the contract; one IEEE fp64 rounding per +, * and /, no FMA.  Per item and row:
+ *   - potential[t] is the sum of d_energy[t][j].w over j < N: a fixed-order compensated (double-double) sum rounded once, in an
+ *     order that depends on N only, within 2 ulp of the exact sum where sum |w| / |sum w| <= 2^40 (the bound stated for
+ *     cavmd_record's sums above); an absent term is +0;
+ *   - kinetic_group has the bits of cavmd_record.kinetic_energy and kinetic_cavity those of cavmd_record.cavity_kinetic, for the
+ *     same velocities, member list and result block;
+ *   - cavity[], reservoir[] and time are the bytes the pointers held when the kernel ran.
+ * temperature is the group's: (2 * KE) / (dof * kB).  The reference's own column, (2/3) * KE / (3 * n * kB) with n molecular
+ * particles (analysis.py's EnergyTracker), is this expression with dof = 9 n; the usual kinetic temperature is dof = 3 n.
+ * One .w per force array: the reference's harmonic / lj and ewald_short / ewald_long columns are not split here; a caller who
+ * wants them apart creates two force batches and names two terms. */
+typedef struct cavmd_ledger_row          /* 192 B, one per item and recorded call */
+{
+    uint64_t call;            /* 1-based index of the cavmd_ledger_record call (of this item) that wrote the row */
+    uint32_t n_terms;         /* the item's non-NULL d_energy entries */
+    uint32_t n_reservoirs;    /* the item's non-NULL d_reservoir entries */
+    double time;              /* *d_time, or 0 */
+    double potential[4];      /* sum of .w per term; absent terms +0 */
+    double cavity[3];         /* harmonic, coupling, dipole-self: bytes of cavmd_result.energy; 0 without d_result */
+    double cavity_potential;  /* (cavity[0] + cavity[1]) + cavity[2] */
+    double potential_total;   /* (((potential[0] + potential[1]) + potential[2]) + potential[3]) + cavity_potential */
+    double kinetic_group;     /* kinetic energy of the item's group */
+    double kinetic_cavity;    /* kinetic energy of the cavity particle (cavmd_result.photon_idx); 0 without one */
+    double kinetic_total;     /* kinetic_group + kinetic_cavity if add_cavity_kinetic, else kinetic_group */
+    double system_total;      /* kinetic_total + potential_total */
+    double reservoir[4];      /* the bytes each pointer held; absent reservoirs +0 */
+    double reservoir_total;   /* ((reservoir[0] + reservoir[1]) + reservoir[2]) + reservoir[3] */
+    double universe_total;    /* system_total + reservoir_total: the reference's [CONSERVED] column */
+    double temperature;       /* (2.0 * kinetic_group) / (dof * kB), or 0 where dof == 0 */
+    double reserved;          /* 0 */
+} cavmd_ledger_row;
+
+typedef struct cavmd_ledger_item         /* 128 B; all pointers DEVICE pointers, read when the kernel runs */
+{
+    const cavmd_result* d_result;        /* the cavity force's block, e.g. cavmd_batch_results_device_ptr + item; NULL: the three
+                                            cavity energies and kinetic_cavity are 0 (the driver's --no-cavity) */
+    const cavmd_double4* d_vel;          /* Scalar4 velocities, mass in .w; NULL: the kinetic columns are 0 */
+    const uint32_t* d_members;           /* group of kinetic_group, or NULL = 0 .. n_members-1 */
+    uint32_t n_members;                  /* <= CAVMD_BATCH_MAX_ITEM_N; 0 is legal (kinetic_group 0) */
+    uint32_t N;                          /* entries of every d_energy array; <= CAVMD_BATCH_MAX_ITEM_N; 0 is legal */
+    const cavmd_double4* d_energy[4];    /* Scalar4 force arrays of N entries whose .w is summed; no non-NULL entry after a NULL
+                                            one (cavmd_verlet_item.d_force's rule) */
+    const double* d_reservoir[4];        /* each the address of ONE double, 8-byte aligned; the same NULL rule */
+    const double* d_time;                /* e.g. &cavmd_draw_state[i].elapsed; NULL: time is 0 */
+    double dof;                          /* finite, >= 0: the degrees of freedom behind `temperature` */
+    uint32_t add_cavity_kinetic;         /* 0 or 1: 1 where the group leaves the cavity particle out */
+    uint32_t reserved0;                  /* must be 0 */
+    uint64_t reserved;                   /* must be 0 */
+} cavmd_ledger_item;
+typedef struct cavmd_ledger cavmd_ledger; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * reserved words that are not 0, a d_result / d_vel / d_energy[t] not 16-byte, a d_reservoir[r] / d_time not 8-byte or a
+ * d_members not 4-byte aligned, a non-NULL d_energy or d_reservoir entry after a NULL one, a dof that is negative or not finite,
+ * add_cavity_kinetic above 1; CAVMD_ERR_CAPACITY for N or n_members above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_ledger_item_check(const cavmd_ledger_item* item);
+/* As cavmd_recorder_create, with rows of 192 bytes: validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS),
+ * copies the table to the device of `ws` (set-up time) and allocates n_items x capacity rows plus the per-item counters in
+ * device memory, all zero.  Every `period`-th call of cavmd_ledger_record writes a row; an item keeps its last `capacity` rows.
+ * capacity >= 1, period >= 1, kB > 0 and finite (Hartree/K), else CAVMD_ERR_INVALID_VALUE; CAVMD_ERR_CAPACITY if the series
+ * would exceed 1 GiB.  cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while a ledger of the workspace is
+ * alive.  Without a device there is no workspace, hence no ledger. */
+CAVMD_API int cavmd_ledger_create(cavmd_workspace* ws, size_t n_items, const cavmd_ledger_item* h_items, size_t capacity,
+                                  uint64_t period, double kB, cavmd_ledger** out);
+/* Synchronises the stream of the last cavmd_ledger_record call (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_ledger_destroy(cavmd_ledger* l);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last record call; nothing is
+ * changed if a row is refused; counters and series are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured,
+ * and for a range outside the batch. */
+CAVMD_API int cavmd_ledger_set_items(cavmd_ledger* l, size_t first, size_t count, const cavmd_ledger_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait.  May be captured into a
+ * hipGraph, and a replay appends like an eager call: every item's call counter moves, and on every period-th call the item
+ * writes row number `rows` into slot rows % capacity of its series and moves `rows`.  Workgroups start in order of
+ * max(N, n_members) descending (ties in item order).  One ledger serves one stream at a time. */
+CAVMD_API int cavmd_ledger_record(cavmd_ledger* l, void* stream);
+/* Synchronises `stream`, then out[i] = rows written by item i since creation / the last reset.  CAVMD_ERR_INVALID_VALUE while
+ * `stream` is being captured. */
+CAVMD_API int cavmd_ledger_rows(cavmd_ledger* l, void* stream, uint64_t* out);
+/* Synchronises `stream`, then out[k * n_rows + j] = row first_row + j (0-based count of RECORDED rows) of item first_item + k;
+ * the statuses of cavmd_recorder_read: CAVMD_ERR_NOT_COMPUTED if an item asked for has never recorded,
+ * CAVMD_ERR_INVALID_VALUE for rows at or beyond the item's `rows`, n_rows or n_items 0, items outside the batch and while
+ * `stream` is being captured, CAVMD_ERR_EXPIRED if a requested row has been overwritten (row < rows - capacity). */
+CAVMD_API int cavmd_ledger_read(cavmd_ledger* l, void* stream, size_t first_item, size_t n_items, uint64_t first_row,
+                                size_t n_rows, cavmd_ledger_row* out);
+/* Zero all counters of all items (ordered on `stream`): the next recorded row is row 0, written by call 1. */
+CAVMD_API int cavmd_ledger_reset(cavmd_ledger* l, void* stream);
+/* Device addresses of the series (item-major: row j of item i at series[i * capacity + j % capacity]) and of the n_items row
+ * counters, for consumers that stay on the GPU.  Either out pointer may be NULL. */
+CAVMD_API int cavmd_ledger_device_ptr(cavmd_ledger* l, const cavmd_ledger_row** series, const uint64_t** rows);
 
 /* ---- the step inputs of a batch, drawn on the device: seeded variates and an adaptive dt in ONE launch per step ------------- */
 /* What fills the two input tables above and below when a captured step replays: for every registered item, ONE kernel writes
