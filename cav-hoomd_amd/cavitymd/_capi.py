@@ -815,12 +815,18 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Ledger, Draw, Molecular and Coulomb share: a handle created from a workspace
-    (kept alive here) over a table of items, released outside stream captures only.  A subclass names its item structure, its ``cavmd_*`` prefix and
-    the size the library sorts its launch order by.  Nothing here relies on ``__init__`` having run."""
+    """What the ten batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Ledger, Draw, Molecular and
+    Coulomb): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
+    only.  A subclass names its item structure, its ``cavmd_*`` prefix and the size the library sorts its launch order by.
+    Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
     _PREFIX = None  # entry points <prefix>_create, <prefix>_destroy, <prefix>_set_items
     _size = None    # item -> the size key of the launch order
+    _DEFERRED = "_deferred_children"  # the module's list that takes a handle closed during a stream capture
+
+    def _call(self, name, *args) -> None:
+        """<prefix>_<name>(handle, *args), its status checked; for what is not called per step"""
+        check(getattr(self._lib, f"{self._PREFIX}_{name}")(self._h, *args), f"{self._PREFIX}_{name}")
 
     def _create(self, workspace: Workspace, items, *args, before=()) -> None:
         """<prefix>_create(workspace, *before, n_items, items, *args, &handle)"""
@@ -851,7 +857,7 @@ class _ItemTableHandle:
         if getattr(self, "_h", None) is not None and self._h.value:
             destroy = getattr(self._lib, self._PREFIX + "_destroy")
             if _capturing():
-                _deferred_children.append((destroy, self._h))
+                globals()[self._DEFERRED].append((destroy, self._h))
             else:
                 destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -865,15 +871,97 @@ class _ItemTableHandle:
 
     def set_items(self, first: int, items) -> None:
         items = list(items)
-        check(getattr(self._lib, self._PREFIX + "_set_items")(self._h, int(first), len(items), self._array(items)),
-              self._PREFIX + "_set_items")
+        self._call("set_items", int(first), len(items), self._array(items))
         for k, it in enumerate(items):
             self.sizes[first + k] = self._size(it)
 
 
-def batch_item_check(item: BatchItem) -> int:
-    """Status cavmd_batch_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_batch_item_check(ctypes.byref(item)))
+class _SeriesHandle(_ItemTableHandle):
+    """A handle whose launches append rows to a time series in device memory (SeriesTable in csrc/cavmd_item_table.hpp).  A
+    subclass names the ctypes structure of one row."""
+    _RECORD = None
+
+    def rows(self, stream: int = 0):
+        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=np.uint64)
+        self._call("rows", ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data))
+        return out
+
+    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
+        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
+        `stream`: a structured array of shape (n_items, n_rows) with the layout of the row structure."""
+        import numpy as np
+        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=np.dtype(self._RECORD))
+        self._call("read", ctypes.c_void_p(stream), int(first_item), int(n_items), int(first_row), int(n_rows),
+                   ctypes.c_void_p(out.ctypes.data))
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        self._call("reset", ctypes.c_void_p(stream))
+
+    def device_ptr(self):
+        """(series, rows): device addresses of the series (item-major, `capacity` rows each) and of the row counters."""
+        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
+        self._call("device_ptr", ctypes.byref(rec), ctypes.byref(rows))
+        return int(rec.value), int(rows.value)
+
+
+class _StateHandle(_ItemTableHandle):
+    """A handle with one state per item in device memory (StateTable in csrc/cavmd_item_table.hpp).  A subclass names the
+    ctypes structure of one state."""
+    _STATE = None
+
+    def read(self, stream: int = 0):
+        """The n_items states after synchronising `stream`: a structured array with the layout of the state structure."""
+        import numpy as np
+        out = np.zeros(self.n_items, dtype=np.dtype(self._STATE))
+        self._call("read", ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data))
+        return out
+
+    def reset(self, stream: int = 0) -> None:
+        self._call("reset", ctypes.c_void_p(stream))
+
+    def state_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        self._call("state_device_ptr", ctypes.byref(p))
+        return int(p.value)
+
+
+def _item_check(prefix: str, what: str):
+    """<what>_item_check(item): the status <prefix>_create would give this row"""
+    def item_check(item) -> int:
+        return int(getattr(load(), prefix + "_item_check")(ctypes.byref(item)))
+    item_check.__name__ = item_check.__qualname__ = what + "_item_check"
+    item_check.__doc__ = f"Status {prefix}_create would give this row (host arithmetic only: needs no device)."
+    return item_check
+
+
+def _dtype_of(struct):
+    """<struct>_dtype(): the numpy structured dtype numpy derives from the ctypes structure, so the layout is stated once"""
+    def dtype():
+        import numpy as np
+        return np.dtype(struct)
+    dtype.__doc__ = f"numpy structured dtype with the layout of {struct.__doc__.split(':')[0]}."
+    return dtype
+
+
+batch_item_check = _item_check("cavmd_batch", "batch")
+bussi_batch_item_check = _item_check("cavmd_bussi_batch", "bussi_batch")
+recorder_item_check = _item_check("cavmd_recorder", "recorder")
+field_item_check = _item_check("cavmd_field_recorder", "field")
+verlet_item_check = _item_check("cavmd_verlet", "verlet")
+bath_item_check = _item_check("cavmd_bath", "bath")
+ledger_item_check = _item_check("cavmd_ledger", "ledger")
+draw_item_check = _item_check("cavmd_draw", "draw")
+coulomb_item_check = _item_check("cavmd_coulomb", "coulomb")
+
+record_dtype = _dtype_of(Record)
+field_record_dtype = _dtype_of(FieldRecord)
+verlet_state_dtype = _dtype_of(VerletState)
+bath_state_dtype = _dtype_of(BathState)
+ledger_row_dtype = _dtype_of(LedgerRow)
+draw_state_dtype = _dtype_of(DrawState)
 
 
 class Batch(_ItemTableHandle):
@@ -917,11 +1005,6 @@ class Batch(_ItemTableHandle):
         p = ctypes.c_void_p()
         check(self._lib.cavmd_batch_results_device_ptr(self._h, ctypes.byref(p)), "cavmd_batch_results_device_ptr")
         return int(p.value)
-
-
-def bussi_batch_item_check(item: BussiBatchItem) -> int:
-    """Status cavmd_bussi_batch_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_bussi_batch_item_check(ctypes.byref(item)))
 
 
 def bussi_batch_input_make(deltaT, set_T, tau, normal_variate, gamma_variate) -> BussiBatchInput:
@@ -970,27 +1053,11 @@ class BussiBatch(_ItemTableHandle):
         return int(p.value)
 
 
-RECORD_DTYPE_FIELDS = [("call", "<u8"), ("eval_sequence", "<u8"), ("energy", "<f8", (3,)), ("total_dipole", "<f8", (3,)),
-                       ("q", "<f8", (3,)), ("cavity_kinetic", "<f8"), ("cavity_temperature", "<f8"), ("kinetic_energy", "<f8"),
-                       ("force_mass_sum", "<f8"), ("reserved", "<f8")]
-
-
-def record_dtype():
-    """numpy structured dtype with the layout of cavmd_record (128 bytes)."""
-    import numpy as np
-    return np.dtype(RECORD_DTYPE_FIELDS)
-
-
-def recorder_item_check(item: RecorderItem) -> int:
-    """Status cavmd_recorder_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_recorder_item_check(ctypes.byref(item)))
-
-
-class Recorder(_ItemTableHandle):
+class Recorder(_SeriesHandle):
     """Owns one cavmd_recorder: the per-step observables of B independent small systems appended, by ONE kernel launch per
     call, to a time series in device memory whose write position lives on the device (a graph replay appends a new row).
     Launched by max(N, n_members) descending."""
-    _ITEM, _PREFIX = RecorderItem, "cavmd_recorder"
+    _ITEM, _PREFIX, _RECORD = RecorderItem, "cavmd_recorder", Record
     _size = staticmethod(lambda it: max(int(it.N), int(it.n_members)))
 
     def __init__(self, workspace: Workspace, items, capacity: int, period: int, kB: float):
@@ -1003,53 +1070,12 @@ class Recorder(_ItemTableHandle):
         """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
         check(self._lib.cavmd_recorder_record(self._h, ctypes.c_void_p(stream)), "cavmd_recorder_record")
 
-    def rows(self, stream: int = 0):
-        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=np.uint64)
-        check(self._lib.cavmd_recorder_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
-              "cavmd_recorder_rows")
-        return out
 
-    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
-        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
-        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_record."""
-        import numpy as np
-        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=record_dtype())
-        check(self._lib.cavmd_recorder_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items), int(first_row),
-                                            int(n_rows), ctypes.c_void_p(out.ctypes.data)), "cavmd_recorder_read")
-        return out
-
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_recorder_reset(self._h, ctypes.c_void_p(stream)), "cavmd_recorder_reset")
-
-    def device_ptr(self):
-        """(records, rows): device addresses of the series (item-major, `capacity` records each) and of the row counters."""
-        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
-        check(self._lib.cavmd_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)), "cavmd_recorder_device_ptr")
-        return int(rec.value), int(rows.value)
-
-
-FIELD_RECORD_DTYPE_FIELDS = [("call", "<u8"), ("n_references", "<u4"), ("took_reference", "<u4"), ("rho2", "<f8"),
-                             ("reserved", "<f8"), ("F", "<f8", (16,))]
-
-
-def field_record_dtype():
-    """numpy structured dtype with the layout of cavmd_field_record (160 bytes)."""
-    import numpy as np
-    return np.dtype(FIELD_RECORD_DTYPE_FIELDS)
-
-
-def field_item_check(item: FieldItem) -> int:
-    """Status cavmd_field_recorder_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_field_recorder_item_check(ctypes.byref(item)))
-
-
-class FieldRecorder(_ItemTableHandle):
+class FieldRecorder(_SeriesHandle):
     """Owns one cavmd_field_recorder: rho(k) of B independent small systems, its correlation with each system's stored
     reference fields and the reference bookkeeping, appended by ONE kernel launch per call to a time series in device memory
     (a graph replay appends a new row and takes references when they are due).  Launched by N descending."""
-    _ITEM, _PREFIX = FieldItem, "cavmd_field_recorder"
+    _ITEM, _PREFIX, _RECORD = FieldItem, "cavmd_field_recorder", FieldRecord
     _size = staticmethod(lambda it: int(it.N))
 
     def __init__(self, workspace: Workspace, items, wavevectors, capacity: int, period: int, max_references: int,
@@ -1071,24 +1097,6 @@ class FieldRecorder(_ItemTableHandle):
         check(self._lib.cavmd_field_recorder_record(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(take_reference_ptr)),
               "cavmd_field_recorder_record")
 
-    def rows(self, stream: int = 0):
-        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=np.uint64)
-        check(self._lib.cavmd_field_recorder_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
-              "cavmd_field_recorder_rows")
-        return out
-
-    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
-        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
-        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_field_record."""
-        import numpy as np
-        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=field_record_dtype())
-        check(self._lib.cavmd_field_recorder_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items),
-                                                  int(first_row), int(n_rows), ctypes.c_void_p(out.ctypes.data)),
-              "cavmd_field_recorder_read")
-        return out
-
     def read_fields(self, stream: int, item: int):
         """(rho_now, rho_refs, ref_rows) of one item after synchronising `stream`: complex arrays of shape (n_k,) and
         (n_refs, n_k), and the row each reference was taken at."""
@@ -1103,30 +1111,6 @@ class FieldRecorder(_ItemTableHandle):
               "cavmd_field_recorder_read_fields")
         return now.view(np.complex128), refs[:n.value].copy().view(np.complex128), ref_rows[:n.value].copy()
 
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_field_recorder_reset(self._h, ctypes.c_void_p(stream)), "cavmd_field_recorder_reset")
-
-    def device_ptr(self):
-        """(records, rows): device addresses of the series (item-major, `capacity` records each) and of the row counters."""
-        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
-        check(self._lib.cavmd_field_recorder_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)),
-              "cavmd_field_recorder_device_ptr")
-        return int(rec.value), int(rows.value)
-
-
-VERLET_STATE_DTYPE_FIELDS = [("steps", "<u8"), ("out_of_box", "<u8"), ("langevin_reservoir", "<f8"), ("reserved", "<f8")]
-
-
-def verlet_state_dtype():
-    """numpy structured dtype with the layout of cavmd_verlet_state (32 bytes)."""
-    import numpy as np
-    return np.dtype(VERLET_STATE_DTYPE_FIELDS)
-
-
-def verlet_item_check(item: VerletItem) -> int:
-    """Status cavmd_verlet_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_verlet_item_check(ctypes.byref(item)))
-
 
 def verlet_input_make(dt, gamma=0.0, kT=0.0, uniform=(0.0, 0.0, 0.0)) -> VerletInput:
     """One input row with langevin_coeff = sqrt(6 gamma kT / dt) and the skip flag taken by the library (host arithmetic)."""
@@ -1137,10 +1121,10 @@ def verlet_input_make(dt, gamma=0.0, kT=0.0, uniform=(0.0, 0.0, 0.0)) -> VerletI
     return row
 
 
-class Verlet(_ItemTableHandle):
+class Verlet(_StateHandle):
     """Owns one cavmd_verlet: the two velocity-Verlet half-steps of B independent small systems, each ONE kernel launch, one
     workgroup per system, the step's inputs read from device memory.  Launched by N descending."""
-    _ITEM, _PREFIX = VerletItem, "cavmd_verlet"
+    _ITEM, _PREFIX, _STATE = VerletItem, "cavmd_verlet", VerletState
     _size = staticmethod(lambda it: int(it.N))
 
     def __init__(self, workspace: Workspace, items):
@@ -1160,36 +1144,8 @@ class Verlet(_ItemTableHandle):
         check(self._lib.cavmd_verlet_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)),
               "cavmd_verlet_step_two")
 
-    def read(self, stream: int = 0):
-        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_verlet_state."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=verlet_state_dtype())
-        check(self._lib.cavmd_verlet_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)),
-              "cavmd_verlet_read")
-        return out
 
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_verlet_reset(self._h, ctypes.c_void_p(stream)), "cavmd_verlet_reset")
-
-    def state_device_ptr(self) -> int:
-        p = ctypes.c_void_p()
-        check(self._lib.cavmd_verlet_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_verlet_state_device_ptr")
-        return int(p.value)
-
-
-BATH_STATE_DTYPE_FIELDS = [("draws", "<u8"), ("coupled", "<u8"), ("reservoir", "<f8"), ("reserved", "<f8")]
 BATH_KEY_STRIDE = 0x9E3779B97F4A7C15
-
-
-def bath_state_dtype():
-    """numpy structured dtype with the layout of cavmd_bath_state (32 bytes)."""
-    import numpy as np
-    return np.dtype(BATH_STATE_DTYPE_FIELDS)
-
-
-def bath_item_check(item: BathItem) -> int:
-    """Status cavmd_bath_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_bath_item_check(ctypes.byref(item)))
 
 
 def bath_item_key(seed: int, i: int) -> int:
@@ -1198,11 +1154,12 @@ def bath_item_key(seed: int, i: int) -> int:
     return (int(seed) + BATH_KEY_STRIDE * (int(i) + 1)) & 0xFFFFFFFFFFFFFFFF
 
 
-class Bath(_ItemTableHandle):
+class Bath(_StateHandle):
     """Owns one cavmd_bath: the second half-step of an integrator batch with a Langevin bath on any set of particles of every
     system, ONE kernel launch, the 3 N variates drawn inside it.  Created from a ``Verlet`` (kept alive here, with its
     workspace) and closed before it; launched in the integrator's order."""
-    _ITEM, _PREFIX = BathItem, "cavmd_bath"
+    _ITEM, _PREFIX, _STATE = BathItem, "cavmd_bath", BathState
+    _DEFERRED = "_deferred_baths"                 # emptied before the integrators among _deferred_children
     _size = staticmethod(lambda it: int(it.N))
 
     def __init__(self, verlet: "Verlet", items):
@@ -1211,58 +1168,16 @@ class Bath(_ItemTableHandle):
         self._create(verlet, items)               # cavmd_bath_create(integrator, n_items, items, &handle)
         self._verlet, self._ws = verlet, verlet._ws
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if _capturing():
-                _deferred_baths.append((self._lib.cavmd_bath_destroy, self._h))
-            else:
-                self._lib.cavmd_bath_destroy(self._h)
-            self._h = ctypes.c_void_p()
-        _destroy_deferred_outside_capture()
-
     def step_two(self, stream: int, inputs_ptr: int) -> None:
         """One kernel, in place of ``Verlet.step_two``: net force, the row's and the group's baths, acceleration and kick."""
         check(self._lib.cavmd_bath_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)), "cavmd_bath_step_two")
 
-    def read(self, stream: int = 0):
-        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_bath_state."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=bath_state_dtype())
-        check(self._lib.cavmd_bath_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_bath_read")
-        return out
 
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_bath_reset(self._h, ctypes.c_void_p(stream)), "cavmd_bath_reset")
-
-    def state_device_ptr(self) -> int:
-        p = ctypes.c_void_p()
-        check(self._lib.cavmd_bath_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_bath_state_device_ptr")
-        return int(p.value)
-
-
-LEDGER_ROW_DTYPE_FIELDS = [("call", "<u8"), ("n_terms", "<u4"), ("n_reservoirs", "<u4"), ("time", "<f8"), ("potential", "<f8", (4,)),
-                           ("cavity", "<f8", (3,)), ("cavity_potential", "<f8"), ("potential_total", "<f8"),
-                           ("kinetic_group", "<f8"), ("kinetic_cavity", "<f8"), ("kinetic_total", "<f8"), ("system_total", "<f8"),
-                           ("reservoir", "<f8", (4,)), ("reservoir_total", "<f8"), ("universe_total", "<f8"),
-                           ("temperature", "<f8"), ("reserved", "<f8")]
-
-
-def ledger_row_dtype():
-    """numpy structured dtype with the layout of cavmd_ledger_row (192 bytes)."""
-    import numpy as np
-    return np.dtype(LEDGER_ROW_DTYPE_FIELDS)
-
-
-def ledger_item_check(item: LedgerItem) -> int:
-    """Status cavmd_ledger_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_ledger_item_check(ctypes.byref(item)))
-
-
-class Ledger(_ItemTableHandle):
+class Ledger(_SeriesHandle):
     """Owns one cavmd_ledger: every term of the conserved energy of B independent small systems appended, by ONE kernel launch
     per call, to a time series in device memory whose write position lives on the device (a graph replay appends a new row).
     Launched by max(N, n_members) descending."""
-    _ITEM, _PREFIX = LedgerItem, "cavmd_ledger"
+    _ITEM, _PREFIX, _RECORD = LedgerItem, "cavmd_ledger", LedgerRow
     _size = staticmethod(lambda it: max(int(it.N), int(it.n_members)))
 
     def __init__(self, workspace: Workspace, items, capacity: int, period: int, kB: float):
@@ -1275,52 +1190,12 @@ class Ledger(_ItemTableHandle):
         """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
         check(self._lib.cavmd_ledger_record(self._h, ctypes.c_void_p(stream)), "cavmd_ledger_record")
 
-    def rows(self, stream: int = 0):
-        """Rows written per item since creation / reset, after synchronising `stream` (a uint64 array of n_items)."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=np.uint64)
-        check(self._lib.cavmd_ledger_rows(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_ledger_rows")
-        return out
 
-    def read(self, stream: int, first_item: int, n_items: int, first_row: int, n_rows: int):
-        """Rows first_row .. first_row + n_rows - 1 of items first_item .. first_item + n_items - 1, after synchronising
-        `stream`: a structured array of shape (n_items, n_rows) with the layout of cavmd_ledger_row."""
-        import numpy as np
-        out = np.zeros((max(int(n_items), 0), max(int(n_rows), 0)), dtype=ledger_row_dtype())
-        check(self._lib.cavmd_ledger_read(self._h, ctypes.c_void_p(stream), int(first_item), int(n_items), int(first_row),
-                                          int(n_rows), ctypes.c_void_p(out.ctypes.data)), "cavmd_ledger_read")
-        return out
-
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_ledger_reset(self._h, ctypes.c_void_p(stream)), "cavmd_ledger_reset")
-
-    def device_ptr(self):
-        """(series, rows): device addresses of the series (item-major, `capacity` rows each) and of the row counters."""
-        rec, rows = ctypes.c_void_p(), ctypes.c_void_p()
-        check(self._lib.cavmd_ledger_device_ptr(self._h, ctypes.byref(rec), ctypes.byref(rows)), "cavmd_ledger_device_ptr")
-        return int(rec.value), int(rows.value)
-
-
-DRAW_STATE_DTYPE_FIELDS = [("draws", "<u8"), ("dt", "<f8"), ("elapsed", "<f8"), ("tolerance", "<f8"), ("exhausted", "<u8"),
-                           ("reserved", "<u8", (3,))]
-
-
-def draw_state_dtype():
-    """numpy structured dtype with the layout of cavmd_draw_state (64 bytes)."""
-    import numpy as np
-    return np.dtype(DRAW_STATE_DTYPE_FIELDS)
-
-
-def draw_item_check(item: DrawItem) -> int:
-    """Status cavmd_draw_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_draw_item_check(ctypes.byref(item)))
-
-
-class Draw(_ItemTableHandle):
+class Draw(_StateHandle):
     """Owns one cavmd_draw: the integrator's and the thermostat's input rows of B independent small systems written by ONE
     kernel launch per step, one lane per system, from a seeded counter-based generator, with the step's dt (fixed, or the
     adaptive rule on the recorder's last row).  Items cost the same: launched in item order."""
-    _ITEM, _PREFIX = DrawItem, "cavmd_draw"
+    _ITEM, _PREFIX, _STATE = DrawItem, "cavmd_draw", DrawState
     _size = staticmethod(lambda it: 0)
 
     def __init__(self, workspace: Workspace, seed: int, items):
@@ -1332,21 +1207,6 @@ class Draw(_ItemTableHandle):
     def fill(self, stream: int = 0) -> None:
         """One kernel: both input rows, the counters and the dt of every item."""
         check(self._lib.cavmd_draw_fill(self._h, ctypes.c_void_p(stream)), "cavmd_draw_fill")
-
-    def read(self, stream: int = 0):
-        """The n_items states after synchronising `stream`: a structured array with the layout of cavmd_draw_state."""
-        import numpy as np
-        out = np.zeros(self.n_items, dtype=draw_state_dtype())
-        check(self._lib.cavmd_draw_read(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data)), "cavmd_draw_read")
-        return out
-
-    def reset(self, stream: int = 0) -> None:
-        check(self._lib.cavmd_draw_reset(self._h, ctypes.c_void_p(stream)), "cavmd_draw_reset")
-
-    def state_device_ptr(self) -> int:
-        p = ctypes.c_void_p()
-        check(self._lib.cavmd_draw_state_device_ptr(self._h, ctypes.byref(p)), "cavmd_draw_state_device_ptr")
-        return int(p.value)
 
 
 def molecular_order(lib=None):
@@ -1422,11 +1282,6 @@ def coulomb_parameters(r_cut, accuracy):
     check(load().cavmd_coulomb_parameters(float(r_cut), float(accuracy), ctypes.byref(kappa), ctypes.byref(k_cut)),
           "cavmd_coulomb_parameters")
     return float(kappa.value), float(k_cut.value)
-
-
-def coulomb_item_check(item: CoulombItem) -> int:
-    """Status cavmd_coulomb_create would give this row (host arithmetic only: needs no device)."""
-    return int(load().cavmd_coulomb_item_check(ctypes.byref(item)))
 
 
 def coulomb_k_count(item: CoulombItem) -> int:

@@ -1,5 +1,5 @@
 // cavmd_batch.hip -- cavmd_batch of include/cavmd.h: the cavity force of a batch of small systems in one launch.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -97,7 +97,7 @@ int cavmd_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_batch_it
                        cavmd_batch** out)
 {
     const bool args_ok = history_depth >= 2 && history_depth <= (int)kResultHistoryMax;
-    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE,
+    return create_table(tie_of(ws), n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE,
                         [&](cavmd_batch* b) { b->depth = (unsigned)history_depth; });
 }
 

@@ -1,5 +1,5 @@
 // cavmd_bussi_batch.hip -- cavmd_bussi_batch of include/cavmd.h: the thermostat step of a batch of small systems in one launch.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -102,7 +102,7 @@ int cavmd_bussi_batch_input_make(double deltaT, double set_T, double tau, double
 int cavmd_bussi_batch_create(cavmd_workspace* ws, size_t n_items, const cavmd_bussi_batch_item* h_items,
                              cavmd_bussi_batch** out)
 {
-    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_bussi_batch*) {});
+    return create_table(tie_of(ws), n_items, h_items, out, CAVMD_OK, [](cavmd_bussi_batch*) {});
 }
 
 int cavmd_bussi_batch_destroy(cavmd_bussi_batch* b)

@@ -1,5 +1,5 @@
 // cavmd_coulomb.hip -- cavmd_coulomb of include/cavmd.h: Ewald Coulomb forces of a batch of small systems in two launches.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -297,7 +297,7 @@ int cavmd_coulomb_order(int* rows, int* j_split, int* k_rows, int* k_split)
 
 int cavmd_coulomb_create(cavmd_workspace* ws, size_t n_items, const cavmd_coulomb_item* h_items, cavmd_coulomb** out)
 {
-    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_coulomb*) {});
+    return create_table(tie_of(ws), n_items, h_items, out, CAVMD_OK, [](cavmd_coulomb*) {});
 }
 
 int cavmd_coulomb_destroy(cavmd_coulomb* c)

@@ -1,5 +1,6 @@
-// cavmd_field_recorder.hip -- cavmd_field_recorder of include/cavmd.h: density field and F(k,t) of a batch appended to a series in device memory.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// cavmd_field_recorder.hip -- cavmd_field_recorder of include/cavmd.h: density field and F(k,t) of a batch appended to a series
+// in device memory.  One of the ten objects built on an item table (cavmd_item_table.hpp), a SeriesTable; the workspace is an
+// incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -96,14 +97,15 @@ int cavmd_field_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd
         && max_references != 0 && max_references <= CAVMD_FIELD_MAX_REFERENCES;
     for (size_t i = 0; args_ok && i < 3 * n_k; ++i)
         args_ok = std::isfinite(h_wavevectors[i]);
-    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_field_recorder* r) {
-        r->n_k = n_k;
-        r->h_kvec = h_wavevectors;
-        r->capacity = capacity;
-        r->period = period;
-        r->max_refs = max_references;
-        r->interval = reference_interval;
-    });
+    return create_table(tie_of(ws), n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE,
+                        [&](cavmd_field_recorder* r) {
+                            r->n_k = n_k;
+                            r->h_kvec = h_wavevectors;
+                            r->capacity = capacity;
+                            r->period = period;
+                            r->max_refs = max_references;
+                            r->interval = reference_interval;
+                        });
 }
 
 int cavmd_field_recorder_destroy(cavmd_field_recorder* r)
@@ -134,9 +136,7 @@ int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream_, uint64_t* 
 int cavmd_field_recorder_read(cavmd_field_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row,
                               size_t n_rows, cavmd_field_record* out)
 {
-    if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
-        return CAVMD_ERR_INVALID_VALUE;
-    return r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
+    return r ? r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_field_recorder_read_fields(cavmd_field_recorder* r, void* stream_, size_t item, double* rho_now, double* rho_refs,

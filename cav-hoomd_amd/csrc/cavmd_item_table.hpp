@@ -1,10 +1,12 @@
-// Host-only: what the ten "batch of small systems" objects share, each in a unit of its own (cavmd_batch.hip,
-// cavmd_bussi_batch.hip, cavmd_recorder.hip, cavmd_field_recorder.hip, cavmd_verlet.hip, cavmd_molecular.hip,
-// cavmd_coulomb.hip) but cavmd_draw and cavmd_bath, which live with the integrator whose input rows the one writes and whose
-// second half-step the other supplies, and cavmd_ledger, which lives with the recorder whose shape and kinetic sum it has -- how a table of items lives on the host and on the device, how the object is created (create_table),
-// launched (ItemTable::launch), tied to its workspace and released (destroy_table); for the two recorders and the ledger, the per-item ring
-// of records behind it (SeriesTable); for the two force batches, the tables derived from the items that their kernels find
-// through a header at a fixed device address and that set_items replaces together (LinkedTable).
+// Host-only: what the ten "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
+// cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder and the ledger, which has its shape), cavmd_field_recorder.hip,
+// cavmd_verlet.hip (the integrator, the draw object that writes its input rows and the bath that supplies its second
+// half-step), cavmd_molecular.hip and cavmd_coulomb.hip.
+// ItemTable is how a table of items lives on the host and on the device; create_table makes an object and ties it to its
+// parent, ItemTable::launch launches it and destroy_table releases it.  Three flavours state what more an object keeps:
+// SeriesTable, a ring of records per item (the two recorders and the ledger); StateTable, one state per item (the
+// integrator, the draw object and the bath); LinkedTable, tables derived from the items that the kernels find through a
+// header at a fixed device address and that set_items replaces together (the two force batches).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once
 
@@ -20,15 +22,22 @@
 #include "cavmd.h"
 #include "cavmd_host_support.hpp" // DeviceGuard, hip_status, CAVMD_HIP_TRY, stream_capturing, DeviceArray
 
-// What an object built on an item table needs of the workspace it was created from: the device, and the count of live
-// objects that cavmd_destroy refuses on.  cavmd_workspace_tie (cavmd_capi.hip) hands out the workspace's; it is called when
-// an object is created and never on a launch path.
+// What an object built on an item table needs of the parent it was created from: the device, and the count of live objects
+// that the parent's destroy refuses on.  The parent is a workspace, or for a bath its integrator (cavmd_verlet::bath_tie).
+// cavmd_workspace_tie (cavmd_capi.hip) hands out the workspace's; it is called when an object is created and never on a
+// launch path.
 struct WorkspaceTie
 {
     int device = -1;
-    unsigned dependents = 0; // live objects created from this workspace (ItemTable::attach)
+    unsigned dependents = 0; // live objects created from this parent (ItemTable::attach)
 };
 __attribute__((visibility("hidden"))) WorkspaceTie* cavmd_workspace_tie(cavmd_workspace* ws);
+
+// the tie create_table takes from an entry point that is given a workspace
+inline WorkspaceTie* tie_of(cavmd_workspace* ws)
+{
+    return ws ? cavmd_workspace_tie(ws) : nullptr;
+}
 
 namespace
 {
@@ -89,7 +98,7 @@ struct ItemTable
     Row (*const to_row)(const Item&);
     int device = -1;
     size_t n = 0;
-    WorkspaceTie* tie = nullptr;   // of the workspace this object was attached to: cavmd_destroy refuses while it lives
+    WorkspaceTie* tie = nullptr;   // of the parent this object was attached to: the parent's destroy refuses while it lives
     std::vector<Item> items;       // host copy of the table, as the caller gave it
     std::vector<unsigned> order;   // items by key descending, stable
     cavmd::DeviceArray<Row> d_rows;
@@ -111,7 +120,7 @@ struct ItemTable
     }
 
     // What create_table asks of an object; one that has more to say hides these.
-    static constexpr bool tied = true; // attached to the workspace it was created from
+    static constexpr bool tied = true; // attached to the parent it was created from
     int check_new(const Item* h_items, size_t n_items)
     {
         return check_items(h_items, n_items, check);
@@ -135,7 +144,7 @@ struct ItemTable
         return e == hipSuccess ? d_order.upload(order.data(), n) : e;
     }
 
-    // a complete object is tied to the workspace it was created from
+    // a complete object is tied to the parent it was created from
     void attach(WorkspaceTie* w)
     {
         tie = w;
@@ -260,18 +269,18 @@ int destroy_table(Table* t)
 // The beginning of every object built on an item table, for `args`, the status of the entry point's own arguments, and
 // `init`, which sets the object's own fields from them.  In this order: the arguments, the items, the capacity rule; then the
 // table and the object's buffers on the device, ONE device synchronise (the zeroing memsets are done before any stream of
-// the caller's, a non-blocking one included, launches), the tie to the workspace.  Any failure destroys what was built.
+// the caller's, a non-blocking one included, launches), the tie to the parent.  Any failure destroys what was built.
+// `tie` is the parent's: an entry point that takes a workspace passes tie_of(ws).
 template <class Table, class Item, class Init>
-int create_table(cavmd_workspace* ws, size_t n_items, const Item* h_items, Table** out, int args, Init init)
+int create_table(WorkspaceTie* tie, size_t n_items, const Item* h_items, Table** out, int args, Init init)
 {
     if (!out)
         return CAVMD_ERR_INVALID_VALUE;
     *out = nullptr;
-    if (!ws || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
+    if (!tie || !h_items || n_items == 0 || n_items > CAVMD_BATCH_MAX_ITEMS)
         return CAVMD_ERR_INVALID_VALUE;
     if (args != CAVMD_OK)
         return args;
-    WorkspaceTie* const tie = cavmd_workspace_tie(ws);
     Table* t = new (std::nothrow) Table();
     if (!t)
         return (int)hipErrorOutOfMemory;
@@ -334,9 +343,10 @@ struct SeriesTable : ItemTable<Item, Row>
         return CAVMD_OK;
     }
 
-    // the caller has checked that the items lie within the table and that n_items and n_rows are not 0
     int read(hipStream_t stream, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows, Record* out)
     {
+        if (!out || n_items == 0 || n_rows == 0 || first_item >= this->n || n_items > this->n - first_item)
+            return CAVMD_ERR_INVALID_VALUE;
         DeviceGuard guard(this->device);
         const int st = sync_uncaptured(stream);
         if (st != CAVMD_OK)
@@ -380,6 +390,51 @@ struct SeriesTable : ItemTable<Item, Row>
             *records = d_series.ptr;
         if (rows_written)
             *rows_written = d_counters.ptr;
+        return CAVMD_OK;
+    }
+};
+
+// An item table with one State per item in device memory, zeroed at creation, which the launches update.  PublicState is the
+// ABI struct the entry point names; the object static_asserts that its layout is State's.
+template <class Item, class Row, class State>
+struct StateTable : ItemTable<Item, Row>
+{
+    cavmd::DeviceArray<State> d_state; // n states, indexed by item
+
+    using ItemTable<Item, Row>::ItemTable;
+
+    hipError_t alloc_own()
+    {
+        return d_state.alloc_zeroed(this->n);
+    }
+
+    template <class PublicState>
+    int read(hipStream_t stream, PublicState* out)
+    {
+        static_assert(sizeof(PublicState) == sizeof(State), "the states are read out as they are");
+        if (!out)
+            return CAVMD_ERR_INVALID_VALUE;
+        DeviceGuard guard(this->device);
+        const int st = sync_uncaptured(stream);
+        if (st != CAVMD_OK)
+            return st;
+        CAVMD_HIP_TRY(hipMemcpy(out, d_state.ptr, sizeof(State) * this->n, hipMemcpyDeviceToHost));
+        return CAVMD_OK;
+    }
+
+    int reset(hipStream_t stream)
+    {
+        DeviceGuard guard(this->device);
+        CAVMD_HIP_TRY(hipMemsetAsync(d_state.ptr, 0, sizeof(State) * this->n, stream));
+        return CAVMD_OK;
+    }
+
+    template <class PublicState>
+    int state_device_ptr(const PublicState** out)
+    {
+        if (!out)
+            return CAVMD_ERR_INVALID_VALUE;
+        *out = reinterpret_cast<const PublicState*>(d_state.ptr);
         return CAVMD_OK;
     }
 };

@@ -1,5 +1,5 @@
 // cavmd_molecular.hip -- cavmd_molecular of include/cavmd.h: bonds and Lennard-Jones pairs of a batch of small systems in one launch.
-// One of the seven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -217,7 +217,8 @@ int cavmd_molecular_order(int* rows, int* j_split)
 int cavmd_molecular_create(cavmd_workspace* ws, const cavmd_molecular_params* prm, size_t n_items, const cavmd_molecular_item* h_items,
                            cavmd_molecular** out)
 {
-    return create_table(ws, n_items, h_items, out, cavmd_molecular_params_check(prm), [&](cavmd_molecular* m) { m->params = *prm; });
+    return create_table(tie_of(ws), n_items, h_items, out, cavmd_molecular_params_check(prm),
+                        [&](cavmd_molecular* m) { m->params = *prm; });
 }
 
 int cavmd_molecular_destroy(cavmd_molecular* m)

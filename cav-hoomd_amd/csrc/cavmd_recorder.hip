@@ -1,7 +1,7 @@
 // cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory;
 // and cavmd_ledger, the energy ledger, which has the recorder's shape and calls its kinetic-energy code (two objects in one
-// unit, as cavmd_verlet.hip holds three).  Both are built on an item table (cavmd_item_table.hpp); the workspace is an
-// incomplete type here.
+// unit, as cavmd_verlet.hip holds three).  Two of the ten objects built on an item table (cavmd_item_table.hpp), each a
+// SeriesTable; what the two share beyond that is PeriodicSeries, below.  The workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -17,28 +17,59 @@
 
 using namespace cavmd;
 
-// ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
-// launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
-struct cavmd_recorder : SeriesTable<cavmd_recorder_item, RecorderRow, cavmd_record>
+namespace
+{
+// The shape the recorder and the ledger share: items with N particles and n_members group members, uploaded as they are and
+// launched by max(N, n_members) descending; kRecCounters words per item (rows, calls, phase, slot); on every period-th call
+// an item appends one Record, whose temperatures are taken with kB.
+template <class Item, class Row, class Record>
+struct PeriodicSeries : SeriesTable<Item, Row, Record>
 {
     uint64_t period = 1;
     double kB = 0.0;
 
-    cavmd_recorder()
-        : SeriesTable(kRecCounters, cavmd_recorder_item_check,
-                      [](const cavmd_recorder_item& it) { return std::max(it.N, it.n_members); },
-                      uploaded_as_it_is<cavmd_recorder_item, RecorderRow>)
+    explicit PeriodicSeries(int (*check_)(const Item*))
+        : SeriesTable<Item, Row, Record>(
+              kRecCounters, check_, [](const Item& it) { return std::max(it.N, it.n_members); }, uploaded_as_it_is<Item, Row>)
     {
     }
 
     int capacity_status(size_t n_items) const
     {
-        return capacity > kRecorderMaxBytes / sizeof(cavmd_record) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+        return this->capacity > kRecorderMaxBytes / sizeof(Record) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
     }
     hipError_t alloc_own()
     {
-        return alloc_series();
+        return this->alloc_series();
     }
+
+    // one launch of n workgroups of the object's kernel
+    template <class Kernel>
+    int record(void* stream, Kernel kernel)
+    {
+        return this->launch((hipStream_t)stream, kernel, dim3((unsigned)this->n), dim3(256), 0, this->d_rows.ptr,
+                            this->d_order.ptr, (unsigned)this->n, (uint64_t)this->capacity, period, kB, this->d_series.ptr,
+                            this->d_counters.ptr);
+    }
+};
+
+template <class Table, class Item>
+int create_periodic(cavmd_workspace* ws, size_t n_items, const Item* h_items, size_t capacity, uint64_t period, double kB,
+                    Table** out)
+{
+    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
+    return create_table(tie_of(ws), n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](Table* t) {
+        t->capacity = capacity;
+        t->period = period;
+        t->kB = kB;
+    });
+}
+} // namespace
+
+// ---- per-step observables of a batch recorded into a time series in device memory (cavmd_recorder_kernel.hpp) ----------------
+struct cavmd_recorder : PeriodicSeries<cavmd_recorder_item, RecorderRow, cavmd_record>
+{
+    cavmd_recorder() : PeriodicSeries(cavmd_recorder_item_check) {}
 };
 
 namespace
@@ -78,12 +109,7 @@ int cavmd_recorder_item_check(const cavmd_recorder_item* it)
 int cavmd_recorder_create(cavmd_workspace* ws, size_t n_items, const cavmd_recorder_item* h_items, size_t capacity,
                           uint64_t period, double kB, cavmd_recorder** out)
 {
-    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
-    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_recorder* r) {
-        r->capacity = capacity;
-        r->period = period;
-        r->kB = kB;
-    });
+    return create_periodic(ws, n_items, h_items, capacity, period, kB, out);
 }
 
 int cavmd_recorder_destroy(cavmd_recorder* r)
@@ -98,10 +124,7 @@ int cavmd_recorder_set_items(cavmd_recorder* r, size_t first, size_t count, cons
 
 int cavmd_recorder_record(cavmd_recorder* r, void* stream_)
 {
-    if (!r)
-        return CAVMD_ERR_INVALID_VALUE;
-    return r->launch((hipStream_t)stream_, recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, r->d_rows.ptr,
-                     r->d_order.ptr, (unsigned)r->n, (uint64_t)r->capacity, r->period, r->kB, r->d_series.ptr, r->d_counters.ptr);
+    return r ? r->record(stream_, recorder_batch_kernel<256>) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
@@ -112,9 +135,7 @@ int cavmd_recorder_rows(cavmd_recorder* r, void* stream_, uint64_t* out)
 int cavmd_recorder_read(cavmd_recorder* r, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
                         cavmd_record* out)
 {
-    if (!r || !out || n_items == 0 || n_rows == 0 || first_item >= r->n || n_items > r->n - first_item)
-        return CAVMD_ERR_INVALID_VALUE;
-    return r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
+    return r ? r->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_recorder_reset(cavmd_recorder* r, void* stream_)
@@ -130,27 +151,9 @@ int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, c
 } // extern "C"
 
 // ---- the energy ledger of a batch: every term of the conserved energy per step (cavmd_ledger_kernel.hpp) ----------------------
-// the recorder's shape: launched by max(N, n_members) descending; kRecCounters words per item: rows, calls, phase, slot
-struct cavmd_ledger : SeriesTable<cavmd_ledger_item, LedgerItem, cavmd_ledger_row>
+struct cavmd_ledger : PeriodicSeries<cavmd_ledger_item, LedgerItem, cavmd_ledger_row> // the recorder's shape
 {
-    uint64_t period = 1;
-    double kB = 0.0;
-
-    cavmd_ledger()
-        : SeriesTable(kRecCounters, cavmd_ledger_item_check,
-                      [](const cavmd_ledger_item& it) { return std::max(it.N, it.n_members); },
-                      uploaded_as_it_is<cavmd_ledger_item, LedgerItem>)
-    {
-    }
-
-    int capacity_status(size_t n_items) const
-    {
-        return capacity > kRecorderMaxBytes / sizeof(cavmd_ledger_row) / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
-    }
-    hipError_t alloc_own()
-    {
-        return alloc_series();
-    }
+    cavmd_ledger() : PeriodicSeries(cavmd_ledger_item_check) {}
 };
 
 namespace
@@ -201,12 +204,7 @@ int cavmd_ledger_item_check(const cavmd_ledger_item* it)
 int cavmd_ledger_create(cavmd_workspace* ws, size_t n_items, const cavmd_ledger_item* h_items, size_t capacity, uint64_t period,
                         double kB, cavmd_ledger** out)
 {
-    const bool args_ok = capacity != 0 && period != 0 && kB > 0.0 && std::isfinite(kB);
-    return create_table(ws, n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_ledger* l) {
-        l->capacity = capacity;
-        l->period = period;
-        l->kB = kB;
-    });
+    return create_periodic(ws, n_items, h_items, capacity, period, kB, out);
 }
 
 int cavmd_ledger_destroy(cavmd_ledger* l)
@@ -221,10 +219,7 @@ int cavmd_ledger_set_items(cavmd_ledger* l, size_t first, size_t count, const ca
 
 int cavmd_ledger_record(cavmd_ledger* l, void* stream_)
 {
-    if (!l)
-        return CAVMD_ERR_INVALID_VALUE;
-    return l->launch((hipStream_t)stream_, ledger_batch_kernel<256>, dim3((unsigned)l->n), dim3(256), 0, l->d_rows.ptr,
-                     l->d_order.ptr, (unsigned)l->n, (uint64_t)l->capacity, l->period, l->kB, l->d_series.ptr, l->d_counters.ptr);
+    return l ? l->record(stream_, ledger_batch_kernel<256>) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_ledger_rows(cavmd_ledger* l, void* stream_, uint64_t* out)
@@ -235,9 +230,7 @@ int cavmd_ledger_rows(cavmd_ledger* l, void* stream_, uint64_t* out)
 int cavmd_ledger_read(cavmd_ledger* l, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
                       cavmd_ledger_row* out)
 {
-    if (!l || !out || n_items == 0 || n_rows == 0 || first_item >= l->n || n_items > l->n - first_item)
-        return CAVMD_ERR_INVALID_VALUE;
-    return l->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out);
+    return l ? l->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_ledger_reset(cavmd_ledger* l, void* stream_)

@@ -2,7 +2,7 @@
 // each; and cavmd_draw, which writes the input rows those half-steps (and the thermostat batch) read: seeded variates and the
 // step's dt, one launch per step; and cavmd_bath, created from an integrator, whose launch takes the place of the integrator's
 // second half-step with a Langevin bath on any set of particles.  Three of the ten objects built on an item table
-// (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// (cavmd_item_table.hpp), each a StateTable; the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -19,20 +19,14 @@
 using namespace cavmd;
 
 // ---- the velocity-Verlet step of a batch of independent small systems, one launch per half-step (cavmd_verlet_batch_kernel.hpp) --
-struct cavmd_verlet : ItemTable<cavmd_verlet_item, VerletRow> // launched by N descending
+struct cavmd_verlet : StateTable<cavmd_verlet_item, VerletRow, VerletState> // launched by N descending
 {
-    DeviceArray<VerletState> d_state; // n states, indexed by item
-    unsigned baths = 0;               // live cavmd_bath objects created from this integrator: cavmd_verlet_destroy refuses on them
+    WorkspaceTie bath_tie; // the parent's tie of the cavmd_bath objects created from this integrator (cavmd_verlet_destroy)
 
     cavmd_verlet()
-        : ItemTable(cavmd_verlet_item_check, [](const cavmd_verlet_item& it) { return it.N; },
-                    uploaded_as_it_is<cavmd_verlet_item, VerletRow>)
+        : StateTable(cavmd_verlet_item_check, [](const cavmd_verlet_item& it) { return it.N; },
+                     uploaded_as_it_is<cavmd_verlet_item, VerletRow>)
     {
-    }
-
-    hipError_t alloc_own()
-    {
-        return d_state.alloc_zeroed(n);
     }
 
     // one launch of n workgroups of one of the three kernels
@@ -61,30 +55,23 @@ static DrawRow draw_row(const cavmd_draw_item& it)
     return r;
 }
 
-struct cavmd_draw : ItemTable<cavmd_draw_item, DrawRow> // items cost the same: launched in item order
+struct cavmd_draw : StateTable<cavmd_draw_item, DrawRow, DrawState> // items cost the same: launched in item order
 {
-    DeviceArray<DrawState> d_state; // n states, indexed by item
     uint64_t seed = 0;
 
-    cavmd_draw() : ItemTable(cavmd_draw_item_check, [](const cavmd_draw_item&) { return 0u; }, draw_row) {}
-
-    hipError_t alloc_own()
-    {
-        return d_state.alloc_zeroed(n);
-    }
+    cavmd_draw() : StateTable(cavmd_draw_item_check, [](const cavmd_draw_item&) { return 0u; }, draw_row) {}
 };
 
 // ---- a Langevin bath on any set of particles of every item, drawn in step two (cavmd_bath_kernel.hpp) --------------------------
 // Item i belongs to item i of the integrator `v`, whose rows, launch order and states the one kernel reads as well; the launch
 // goes through the integrator's table, which notes the stream, and is noted here too.
-struct cavmd_bath : ItemTable<cavmd_bath_item, BathRow>
+struct cavmd_bath : StateTable<cavmd_bath_item, BathRow, BathState> // tied to v->bath_tie
 {
-    DeviceArray<BathState> d_state; // n states, indexed by item
     cavmd_verlet* v = nullptr;
 
     cavmd_bath()
-        : ItemTable(cavmd_bath_item_check, [](const cavmd_bath_item& it) { return it.N; },
-                    uploaded_as_it_is<cavmd_bath_item, BathRow>)
+        : StateTable(cavmd_bath_item_check, [](const cavmd_bath_item& it) { return it.N; },
+                     uploaded_as_it_is<cavmd_bath_item, BathRow>)
     {
     }
 };
@@ -199,12 +186,13 @@ int cavmd_verlet_input_make(double dt, double gamma, double kT, const double uni
 
 int cavmd_verlet_create(cavmd_workspace* ws, size_t n_items, const cavmd_verlet_item* h_items, cavmd_verlet** out)
 {
-    return create_table(ws, n_items, h_items, out, CAVMD_OK, [](cavmd_verlet*) {});
+    return create_table(tie_of(ws), n_items, h_items, out, CAVMD_OK, [](cavmd_verlet* v) { v->bath_tie.device = v->device; });
 }
 
 int cavmd_verlet_destroy(cavmd_verlet* v)
 {
-    if (v && v->baths != 0) // as cavmd_destroy has it for its dependents: nothing is freed while a bath of this integrator lives
+    // as cavmd_destroy has it for its dependents: nothing is freed while a bath of this integrator lives
+    if (v && v->bath_tie.dependents != 0)
         return CAVMD_ERR_INVALID_VALUE;
     return destroy_table(v);
 }
@@ -237,31 +225,17 @@ int cavmd_verlet_step_two(cavmd_verlet* v, void* stream_, const cavmd_verlet_inp
 
 int cavmd_verlet_read(cavmd_verlet* v, void* stream_, cavmd_verlet_state* out)
 {
-    if (!v || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(v->device);
-    const int st = sync_uncaptured((hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(hipMemcpy(out, v->d_state.ptr, sizeof(VerletState) * v->n, hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return v ? v->read((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_verlet_reset(cavmd_verlet* v, void* stream_)
 {
-    if (!v)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(v->device);
-    CAVMD_HIP_TRY(hipMemsetAsync(v->d_state.ptr, 0, sizeof(VerletState) * v->n, (hipStream_t)stream_));
-    return CAVMD_OK;
+    return v ? v->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** out)
 {
-    if (!v || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = reinterpret_cast<const cavmd_verlet_state*>(v->d_state.ptr);
-    return CAVMD_OK;
+    return v ? v->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 // ---- cavmd_draw ------------------------------------------------------------------------------------------------------------
@@ -292,7 +266,7 @@ int cavmd_draw_item_check(const cavmd_draw_item* it)
 
 int cavmd_draw_create(cavmd_workspace* ws, uint64_t seed, size_t n_items, const cavmd_draw_item* h_items, cavmd_draw** out)
 {
-    return create_table(ws, n_items, h_items, out, CAVMD_OK, [seed](cavmd_draw* d) { d->seed = seed; });
+    return create_table(tie_of(ws), n_items, h_items, out, CAVMD_OK, [seed](cavmd_draw* d) { d->seed = seed; });
 }
 
 int cavmd_draw_destroy(cavmd_draw* d)
@@ -316,31 +290,17 @@ int cavmd_draw_fill(cavmd_draw* d, void* stream_)
 
 int cavmd_draw_read(cavmd_draw* d, void* stream_, cavmd_draw_state* out)
 {
-    if (!d || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(d->device);
-    const int st = sync_uncaptured((hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(hipMemcpy(out, d->d_state.ptr, sizeof(DrawState) * d->n, hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return d ? d->read((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_draw_reset(cavmd_draw* d, void* stream_)
 {
-    if (!d)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(d->device);
-    CAVMD_HIP_TRY(hipMemsetAsync(d->d_state.ptr, 0, sizeof(DrawState) * d->n, (hipStream_t)stream_));
-    return CAVMD_OK;
+    return d ? d->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_draw_state_device_ptr(cavmd_draw* d, const cavmd_draw_state** out)
 {
-    if (!d || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = reinterpret_cast<const cavmd_draw_state*>(d->d_state.ptr);
-    return CAVMD_OK;
+    return d ? d->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 // ---- cavmd_bath ------------------------------------------------------------------------------------------------------------
@@ -364,44 +324,15 @@ int cavmd_bath_item_check(const cavmd_bath_item* it)
     return CAVMD_OK;
 }
 
+// as create_table has it, with the integrator's bath_tie as the parent's: the bath counts among the integrator's dependents
 int cavmd_bath_create(cavmd_verlet* v, size_t n_items, const cavmd_bath_item* h_items, cavmd_bath** out)
 {
-    if (!out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = nullptr;
-    if (!v || !h_items || n_items != v->n)
-        return CAVMD_ERR_INVALID_VALUE;
-    const int st = check_items(h_items, n_items, cavmd_bath_item_check);
-    if (st != CAVMD_OK)
-        return st;
-    cavmd_bath* b = new (std::nothrow) cavmd_bath();
-    if (!b)
-        return (int)hipErrorOutOfMemory;
-    b->adopt(v->device, h_items, n_items);
-    hipError_t e;
-    {
-        DeviceGuard guard(b->device);
-        e = b->upload();
-        if (e == hipSuccess)
-            e = b->d_state.alloc_zeroed(b->n);
-        if (e == hipSuccess)
-            e = hipDeviceSynchronize(); // the zeroing memset is done before any stream of the caller's launches
-    }
-    if (e != hipSuccess)
-    {
-        destroy_table(b);
-        return hip_status(e);
-    }
-    b->v = v;
-    v->baths += 1;
-    *out = b;
-    return CAVMD_OK;
+    return create_table(v ? &v->bath_tie : nullptr, n_items, h_items, out,
+                        v && n_items == v->n ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [v](cavmd_bath* b) { b->v = v; });
 }
 
 int cavmd_bath_destroy(cavmd_bath* b)
 {
-    if (b && b->v)
-        b->v->baths -= 1;
     return destroy_table(b);
 }
 
@@ -428,31 +359,17 @@ int cavmd_bath_step_two(cavmd_bath* b, void* stream_, const cavmd_verlet_input* 
 
 int cavmd_bath_read(cavmd_bath* b, void* stream_, cavmd_bath_state* out)
 {
-    if (!b || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(b->device);
-    const int st = sync_uncaptured((hipStream_t)stream_);
-    if (st != CAVMD_OK)
-        return st;
-    CAVMD_HIP_TRY(hipMemcpy(out, b->d_state.ptr, sizeof(BathState) * b->n, hipMemcpyDeviceToHost));
-    return CAVMD_OK;
+    return b ? b->read((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_bath_reset(cavmd_bath* b, void* stream_)
 {
-    if (!b)
-        return CAVMD_ERR_INVALID_VALUE;
-    DeviceGuard guard(b->device);
-    CAVMD_HIP_TRY(hipMemsetAsync(b->d_state.ptr, 0, sizeof(BathState) * b->n, (hipStream_t)stream_));
-    return CAVMD_OK;
+    return b ? b->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
 }
 
 int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out)
 {
-    if (!b || !out)
-        return CAVMD_ERR_INVALID_VALUE;
-    *out = reinterpret_cast<const cavmd_bath_state*>(b->d_state.ptr);
-    return CAVMD_OK;
+    return b ? b->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 } // extern "C"

@@ -84,6 +84,27 @@ def good_verlet(capi, n=501, forces=(0x50000,), net=0, langevin=-1):
     return capi.verlet_item(n, 0x10000, 0x20004, 0x30000, 0x40008, forces, net, (10.0, 11.0, 12.0), langevin)
 
 
+def good_bath(capi, **kw):
+    args = dict(gamma_ptr=0x10008, N=501, kT=9.5e-4, seed=0x9E3779B97F4A7C15)
+    args.update(kw)
+    return capi.bath_item(**args)
+
+
+def good_ledger(capi, **kw):
+    args = dict(result_ptr=0x10000, vel_ptr=0x20000, members_ptr=0x30004, n_members=500, N=501, energy_ptrs=(0x40000, 0x50000),
+                reservoir_ptrs=(0x60008, 0x70008, 0x80008), time_ptr=0x90008, dof=1500.0, add_cavity_kinetic=1)
+    args.update(kw)
+    return capi.ledger_item(**args)
+
+
+def good_draw(capi, **kw):
+    args = dict(verlet_row_ptr=0x10000, bussi_row_ptr=0x20008, gamma=0.01, kT=9.5e-4, set_T=9.5e-4, tau=100.0, dof=1293.0,
+                dt=5.0, records_ptr=0x30000, rows_ptr=0x40008, capacity=64, tolerance=1e-3, tolerance_initial=1e-4,
+                tolerance_time_constant=1e4, dt_min=0.1, dt_max=50.0)
+    args.update(kw)
+    return capi.draw_item(**args)
+
+
 def molecular_params(capi, r_cut=3.0):
     return capi.molecular_params(3, {0: (0.7, 2.2), 1: (1.4, 2.0)},
                                  {(0, 0): (1e-3, 2.0, r_cut), (0, 1): (2e-3, 1.5, r_cut), (1, 1): (5e-4, 1.0, 0.5 * r_cut)})

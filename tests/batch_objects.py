@@ -1,4 +1,4 @@
-"""The seven batch objects of include/cavmd.h, one table and one implementation of each check a machine WITHOUT a GPU can make
+"""The ten batch objects of include/cavmd.h, one table and one implementation of each check a machine WITHOUT a GPU can make
 on all of them: the header declares and both libraries export each object's entry points and nothing stray, a C99 caller
 compiles, links and runs, the layouts agree between the C compiler, ctypes and numpy, null arguments are refused, the launch
 order is a stable descending sort, the Python class is exported and refuses CPU tensors, and a deferred destroy takes the
@@ -26,6 +26,11 @@ class NoBatch:
 
     def __len__(self):
         return 1
+
+
+class NoIntegrator:
+    """stands in for an integrator that is never looked at: the CPU tensor is refused first"""
+    n_systems = 1
 
 
 def _cpu_system(cavitymd, cfg):
@@ -67,6 +72,26 @@ def _verlet_on_cpu(cavitymd):
             lambda: cavitymd.VerletBatch(NoBatch(), [np.zeros((10, 4))])]
 
 
+def _bath_on_cpu(cavitymd):
+    return [lambda: cavitymd.LangevinBathBatch(NoIntegrator(), [torch.zeros(10, dtype=torch.float64)], 1.0, 3),
+            lambda: cavitymd.LangevinBathBatch(NoIntegrator(), [None, np.zeros(10)], 1.0, 3)]
+
+
+def _ledger_on_cpu(cavitymd):
+    vel = torch.zeros((10, 4), dtype=torch.float64)
+    return [lambda: cavitymd.BatchEnergyLedger(NoBatch(), [vel]),
+            lambda: cavitymd.BatchEnergyLedger(None, [vel]),
+            lambda: cavitymd.BatchEnergyLedger(None, [None], terms=[[vel]]),
+            lambda: cavitymd.BatchEnergyLedger(None, [np.zeros((10, 4))])]
+
+
+def _draw_on_cpu(cavitymd):
+    rows = torch.zeros((3, 8), dtype=torch.float64)
+    return [lambda: cavitymd.StepDraw(1, integrator=rows, dt=1.0),
+            lambda: cavitymd.StepDraw(1, thermostat=rows, set_T=1.0, tau=1.0, dof=3.0, dt=1.0),
+            lambda: cavitymd.StepDraw(1, integrator=np.zeros((3, 8)), dt=1.0)]
+
+
 def _molecular_on_cpu(cavitymd):
     sysdef, bonds, bond_typeid = _lattice(cavitymd)
     return [lambda: cavitymd.MolecularForceBatch([sysdef], [bonds], [bond_typeid], harmonic={0: dict(k=1.0, r0=2.0)},
@@ -83,11 +108,12 @@ def _row(name, skip=None, **kw):
                            program=name + "_abi_check", ok=name.upper().replace("_", "-") + "-ABI-OK", skip=skip or {}, **kw)
 
 
-# One row per object.  entry_points is spelled out: derived from the header or from _capi._PROTOTYPES it would check nothing.
+# One row per object, in the header's order (as _capi._PROTOTYPES is).  entry_points is spelled out: derived from the header or from _capi._PROTOTYPES it would check nothing.
 #   structs      which -> (ctypes structure, sizeof, {field: offset} pinned as literals); `which` is the C program's name for it
 #   dtypes       which -> the _capi function giving the numpy dtype of that structure
 #   no_device    the line the C program prints where cavmd_create finds no device
-#   create       (capi, item) -> what cavmd_<name>_create takes between the workspace and the out pointer
+#   create       (capi, item) -> what cavmd_<name>_create takes between the workspace (for the bath: the integrator) and the
+#                out pointer
 #   with_handle  (capi, item) -> {entry point: what it takes after the handle}; the rest of entry_points is without_handle
 #   on_cpu       cavitymd -> constructor calls with CPU tensors, each of which must raise "no CPU fallback"
 #   skip         {check letter: one-line reason} for a check that cannot apply to the object by its nature (none today)
@@ -176,6 +202,52 @@ OBJECTS = [
          cls="VerletBatch", module="integrator_batch",
          methods=("set_inputs", "draw_inputs", "prime", "step_one", "step_two", "state", "reset", "close"), properties=(),
          on_cpu=_verlet_on_cpu),
+    _row("bath",
+         entry_points=("item_check", "create", "destroy", "set_items", "step_two", "read", "reset", "state_device_ptr"),
+         kernels=(b"verlet_step_two_bath_kernel",), no_device="no device: no workspace, hence no integrator and no bath",
+         structs={"item": ("BathItem", 64, dict(d_gamma=0, seed=8, kT=16, N=24, reserved0=28, reserved=32)),
+                  "state": ("BathState", 32, dict(draws=0, coupled=8, reservoir=16, reserved=24))},
+         dtypes={"state": "bath_state_dtype"}, good=abi.good_bath, without_handle=("item_check",),
+         create=lambda capi, it: (1, byref(it)),
+         with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "step_two": (None, vp(0x1000)),
+                                       "read": (None, byref(capi.BathState())), "reset": (None,),
+                                       "state_device_ptr": (byref(vp()),)},
+         handle="Bath", handle_methods=("step_two", "read", "reset", "set_items", "state_device_ptr", "close"),
+         cls="LangevinBathBatch", module="bath_batch", methods=("step_two", "state", "reset", "close", "set_gammas"),
+         properties=("bath",), on_cpu=_bath_on_cpu),
+    _row("ledger",
+         entry_points=("item_check", "create", "destroy", "set_items", "record", "rows", "read", "reset", "device_ptr"),
+         kernels=(b"ledger_batch_kernel",), no_device="no device: no workspace, hence no ledger",
+         structs={"row": ("LedgerRow", 192, dict(call=0, n_terms=8, n_reservoirs=12, time=16, potential=24, cavity=56,
+                                                 cavity_potential=80, potential_total=88, kinetic_group=96, kinetic_cavity=104,
+                                                 kinetic_total=112, system_total=120, reservoir=128, reservoir_total=160,
+                                                 universe_total=168, temperature=176, reserved=184)),
+                  "item": ("LedgerItem", 128, dict(d_result=0, d_vel=8, d_members=16, n_members=24, N=28, d_energy=32,
+                                                   d_reservoir=64, d_time=96, dof=104, add_cavity_kinetic=112, reserved0=116,
+                                                   reserved=120))},
+         dtypes={"row": "ledger_row_dtype"}, good=abi.good_ledger, without_handle=("item_check",),
+         create=lambda capi, it: (1, byref(it), 8, 1, KB),
+         with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "record": (None,),
+                                       "rows": (None, byref(ctypes.c_uint64())),
+                                       "read": (None, 0, 1, 0, 1, byref(capi.LedgerRow())), "reset": (None,),
+                                       "device_ptr": (byref(vp()), byref(vp()))},
+         handle="Ledger", handle_methods=("record", "rows", "read", "reset", "set_items", "device_ptr", "close"),
+         cls="BatchEnergyLedger", module="ledger", methods=("record", "rows", "read", "reset", "close"), properties=(),
+         on_cpu=_ledger_on_cpu),
+    _row("draw",
+         entry_points=("item_check", "create", "destroy", "set_items", "fill", "read", "reset", "state_device_ptr"),
+         kernels=(b"draw_fill_kernel",), no_device="no device: no workspace, hence no draw object",
+         structs={"item": ("DrawItem", 160, dict(d_verlet_row=0, d_bussi_row=8, d_records=16, d_rows=24, capacity=32,
+                                                 langevin_gamma=40, bussi_set_T=56, dt_initial=80, tolerance_target=88, dt_min=112,
+                                                 dt_max=120, reserved=128)),
+                  "state": ("DrawState", 64, dict(draws=0, dt=8, elapsed=16, tolerance=24, exhausted=32, reserved=40))},
+         dtypes={"state": "draw_state_dtype"}, good=abi.good_draw, without_handle=("item_check",),
+         create=lambda capi, it: (7, 1, byref(it)),
+         with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "fill": (None,), "read": (None, byref(capi.DrawState())),
+                                       "reset": (None,), "state_device_ptr": (byref(vp()),)},
+         handle="Draw", handle_methods=("fill", "read", "reset", "set_items", "state_device_ptr", "close"),
+         cls="StepDraw", module="step_draw", methods=("fill", "state", "reset", "close"), properties=("draw",),
+         on_cpu=_draw_on_cpu),
     _row("molecular",
          entry_points=("pair_make", "params_check", "item_check", "create", "destroy", "set_items", "compute", "order"),
          kernels=(b"molecular_force_kernel",), no_device="no device: no workspace, hence no molecular batch",

@@ -1,4 +1,4 @@
-"""Every no-GPU check of tests/batch_objects.py on every row of its table: the seven batch objects of include/cavmd.h by the
+"""Every no-GPU check of tests/batch_objects.py on every row of its table: the ten batch objects of include/cavmd.h by the
 checks a to i.  What is specific to one object (refusal matrices, row makers, mirrors, header prose) is in its own
 tests/test_*_abi.py."""
 import pytest
@@ -11,11 +11,22 @@ from batch_objects import OBJECTS
 per_object = pytest.mark.parametrize("obj", OBJECTS, ids=[obj.name for obj in OBJECTS])
 
 
-def test_the_table_has_the_seven_objects(capi):
-    assert [obj.name for obj in OBJECTS] == ["batch", "bussi_batch", "recorder", "field_recorder", "verlet", "molecular", "coulomb"]
-    assert [len(obj.entry_points) for obj in OBJECTS] == [10, 10, 9, 10, 11, 8, 9]
+def test_the_table_has_the_ten_objects(capi):
+    names = ["batch", "bussi_batch", "recorder", "field_recorder", "verlet", "bath", "ledger", "draw", "molecular", "coulomb"]
+    assert [obj.name for obj in OBJECTS] == names
+    assert [len(obj.entry_points) for obj in OBJECTS] == [10, 10, 9, 10, 11, 8, 9, 8, 8, 9]
     handles = {getattr(capi, obj.handle) for obj in OBJECTS}
-    assert len(handles) == 7 and all(issubclass(h, capi._ItemTableHandle) for h in handles)
+    assert len(handles) == 10 and all(issubclass(h, capi._ItemTableHandle) for h in handles)
+    # the header's order, as _capi._PROTOTYPES has it
+    first = [list(capi._PROTOTYPES).index(obj.prefix + "_create") for obj in OBJECTS]
+    assert first == sorted(first), first
+
+
+def test_no_prefix_is_a_prefix_of_another():
+    """an entry point belongs to one object: cavmd_bath_ against cavmd_batch_, cavmd_recorder_ against cavmd_field_recorder_"""
+    for a in OBJECTS:
+        for b in OBJECTS:
+            assert a is b or not (a.prefix + "_").startswith(b.prefix + "_"), (a.prefix, b.prefix)
 
 
 # ---- a. the header ------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""The bath object (cavmd_bath_*) on a machine WITHOUT a GPU: the shared checks a to i of tests/batch_objects.py on a row for
-this object built here (none is skipped: the one difference, a create from an integrator instead of a workspace, is a first
-argument that is refused when it is NULL either way), every refusal of its item check, the mirror's variates
+"""What is specific to the bath object (cavmd_bath_*) on a machine WITHOUT a GPU (tests/test_batch_objects_abi.py runs the shared
+checks a to i on its row of tests/batch_objects.py; none is skipped: the one difference, a create from an integrator instead
+of a workspace, is a first argument that is refused when it is NULL either way): the header's prose, the further null-argument
+cases, a bath's deferred destroy before its integrator's, every refusal of its item check, the mirror's variates
 (tests/bath_mirror.py) against the known answers of Philox in the header, the derived per-item keys, and the host twin
 (tests/bath_twin.py) inside its band over 24 seeds and outside it with a frozen step counter."""
 import ctypes
@@ -14,42 +15,15 @@ import bath_mirror as mirror
 import bath_twin as twin
 import draw_mirror
 from abi_support import HEADER
+from abi_support import good_bath as _good
 
 byref, vp = ctypes.byref, ctypes.c_void_p
 
 
-def _good(capi, **kw):
-    args = dict(gamma_ptr=0x10008, N=501, kT=9.5e-4, seed=0x9E3779B97F4A7C15)
-    args.update(kw)
-    return capi.bath_item(**args)
+ROW = checks.ROWS["bath"]
 
 
-class NoIntegrator:
-    """stands in for an integrator that is never looked at: the CPU tensor is refused first"""
-    n_systems = 1
-
-
-def _on_cpu(cavitymd):
-    return [lambda: cavitymd.LangevinBathBatch(NoIntegrator(), [torch.zeros(10, dtype=torch.float64)], 1.0, 3),
-            lambda: cavitymd.LangevinBathBatch(NoIntegrator(), [None, np.zeros(10)], 1.0, 3)]
-
-
-ROW = checks._row(
-    "bath",
-    entry_points=("item_check", "create", "destroy", "set_items", "step_two", "read", "reset", "state_device_ptr"),
-    kernels=(b"verlet_step_two_bath_kernel",), no_device="no device: no workspace, hence no integrator and no bath",
-    structs={"item": ("BathItem", 64, dict(d_gamma=0, seed=8, kT=16, N=24, reserved0=28, reserved=32)),
-             "state": ("BathState", 32, dict(draws=0, coupled=8, reservoir=16, reserved=24))},
-    dtypes={"state": "bath_state_dtype"}, good=_good, without_handle=("item_check",),
-    create=lambda capi, it: (1, byref(it)),
-    with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "step_two": (None, vp(0x1000)),
-                                  "read": (None, byref(capi.BathState())), "reset": (None,), "state_device_ptr": (byref(vp()),)},
-    handle="Bath", handle_methods=("step_two", "read", "reset", "set_items", "state_device_ptr", "close"),
-    cls="LangevinBathBatch", module="bath_batch", methods=("step_two", "state", "reset", "close", "set_gammas"),
-    properties=("bath",), on_cpu=_on_cpu)
-
-
-# ---- the checks every batch object gets (tests/batch_objects.py a to i), on this object's row ----------------------------------
+# ---- what this object adds to the checks every batch object gets (tests/batch_objects.py a to i) ------------------------------
 def test_header_declares_the_eight_entry_points_and_the_contract():
     checks.header_declares_exactly_the_entry_points(ROW)
     text = open(HEADER).read()
@@ -58,21 +32,10 @@ def test_header_declares_the_eight_entry_points_and_the_contract():
                   "after it the same variates come again", "exactly the bytes"):
         assert words in text, words
     assert "Out of scope: Langevin on more than one particle" not in text
-    # no other object's prefix is a prefix of this one's, and the other way round (cavmd_bath_ against cavmd_batch_ included)
-    for other in checks.OBJECTS:
-        assert not (ROW.prefix + "_").startswith(other.prefix + "_") and not (other.prefix + "_").startswith(ROW.prefix + "_"), other.prefix
-
-
-def test_libraries_export_them_and_nothing_stray(capi):
-    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
 
 
 def test_the_version_is_still_2(capi):
-    checks.the_version_is_still_2(capi)
-
-
-def test_c_layouts_equal_the_ctypes_ones_and_the_numpy_dtype(capi, tmp_path):
-    checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
+    checks.the_version_is_still_2(capi)                                    # not a check on a row: it stays with each object
 
 
 def test_null_handles_are_refused_without_a_device(capi):
@@ -107,10 +70,6 @@ def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
 
     with pytest.raises(RuntimeError, match="used after close"):
         cavitymd.LangevinBathBatch(Closed(), [None], 1.0, 3)
-
-
-def test_deferred_destroy_takes_the_object_before_its_workspace(capi, monkeypatch):
-    checks.deferred_destroy_takes_the_object_before_its_workspace(ROW, capi, monkeypatch)
 
 
 def test_deferred_destroy_takes_a_bath_before_its_integrator(capi, monkeypatch):

@@ -95,7 +95,7 @@ def test_variants_share_what_they_should(tmp_path):
 
 
 def test_batch_units_cannot_see_the_workspace():
-    """The seven batch objects and the table layer they share reach a workspace through its WorkspaceTie alone; the switches
+    """The ten batch objects and the table layer they share reach a workspace through its WorkspaceTie alone; the switches
     of the variants are each read by one unit."""
     for name in [unit + ".hip" for unit in BATCH_UNITS] + ["cavmd_item_table.hpp"]:
         text = open(os.path.join(CSRC, name)).read()

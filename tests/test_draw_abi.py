@@ -1,5 +1,5 @@
-"""The draw object (cavmd_draw_*) on a machine WITHOUT a GPU: the shared checks a to i of tests/batch_objects.py on a row for
-this object built here, every refusal of its item check, the known answers of its generator through the numpy mirror
+"""What is specific to the draw object (cavmd_draw_*) on a machine WITHOUT a GPU (tests/test_batch_objects_abi.py runs the shared
+checks a to i on its row of tests/batch_objects.py): the header's prose, every refusal of its item check, the known answers of its generator through the numpy mirror
 (tests/draw_mirror.py), the mirror's fixed-mode rows against the library's two row makers byte for byte, and the mirror's
 moments and try counts."""
 import ctypes
@@ -12,67 +12,22 @@ import batch_objects as checks
 import draw_mirror as mirror
 from abi_support import HEADER
 from abi_support import bits as _bits
+from abi_support import good_draw as _good
 
-byref, vp = ctypes.byref, ctypes.c_void_p
-
-
-def _good(capi, **kw):
-    args = dict(verlet_row_ptr=0x10000, bussi_row_ptr=0x20008, gamma=0.01, kT=9.5e-4, set_T=9.5e-4, tau=100.0, dof=1293.0,
-                dt=5.0, records_ptr=0x30000, rows_ptr=0x40008, capacity=64, tolerance=1e-3, tolerance_initial=1e-4,
-                tolerance_time_constant=1e4, dt_min=0.1, dt_max=50.0)
-    args.update(kw)
-    return capi.draw_item(**args)
+ROW = checks.ROWS["draw"]
 
 
-def _on_cpu(cavitymd):
-    rows = torch.zeros((3, 8), dtype=torch.float64)
-    return [lambda: cavitymd.StepDraw(1, integrator=rows, dt=1.0),
-            lambda: cavitymd.StepDraw(1, thermostat=rows, set_T=1.0, tau=1.0, dof=3.0, dt=1.0),
-            lambda: cavitymd.StepDraw(1, integrator=np.zeros((3, 8)), dt=1.0)]
-
-
-ROW = checks._row(
-    "draw",
-    entry_points=("item_check", "create", "destroy", "set_items", "fill", "read", "reset", "state_device_ptr"),
-    kernels=(b"draw_fill_kernel",), no_device="no device: no workspace, hence no draw object",
-    structs={"item": ("DrawItem", 160, dict(d_verlet_row=0, d_bussi_row=8, d_records=16, d_rows=24, capacity=32, langevin_gamma=40,
-                                            bussi_set_T=56, dt_initial=80, tolerance_target=88, dt_min=112, dt_max=120,
-                                            reserved=128)),
-             "state": ("DrawState", 64, dict(draws=0, dt=8, elapsed=16, tolerance=24, exhausted=32, reserved=40))},
-    dtypes={"state": "draw_state_dtype"}, good=_good, without_handle=("item_check",),
-    create=lambda capi, it: (7, 1, byref(it)),
-    with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "fill": (None,), "read": (None, byref(capi.DrawState())),
-                                  "reset": (None,), "state_device_ptr": (byref(vp()),)},
-    handle="Draw", handle_methods=("fill", "read", "reset", "set_items", "state_device_ptr", "close"),
-    cls="StepDraw", module="step_draw", methods=("fill", "state", "reset", "close"), properties=("draw",), on_cpu=_on_cpu)
-
-
-# ---- the checks every batch object gets (tests/batch_objects.py a to i), on this object's row ----------------------------------
+# ---- what this object adds to the checks every batch object gets (tests/batch_objects.py a to i) ------------------------------
 def test_header_declares_the_eight_entry_points_and_the_contract():
     checks.header_declares_exactly_the_entry_points(ROW)
     text = open(HEADER).read()
     for words in ("Philox4x32-10", "0xD2511F53", "0xCD9E8D57", "0x9E3779B9", "0xBB67AE85", "6627e8d5 e169c58d bc57ac4c 9b00dbd8",
                   "cospi", "Marsaglia and Tsang", "src/cavitymd/simulation.py:57-92"):
         assert words in text, words
-    # no existing object's prefix is a prefix of this one's, and the other way round
-    for other in checks.OBJECTS:
-        assert not ROW.prefix.startswith(other.prefix) and not other.prefix.startswith(ROW.prefix), other.prefix
-
-
-def test_libraries_export_them_and_nothing_stray(capi):
-    checks.libraries_export_the_entry_points_and_nothing_stray(ROW, capi)
 
 
 def test_the_version_is_still_2(capi):
-    checks.the_version_is_still_2(capi)
-
-
-def test_c_layouts_equal_the_ctypes_ones_and_the_numpy_dtype(capi, tmp_path):
-    checks.c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(ROW, capi, tmp_path)
-
-
-def test_null_handles_are_refused_without_a_device(capi):
-    checks.null_arguments_are_refused_without_a_device(ROW, capi)
+    checks.the_version_is_still_2(capi)                                    # not a check on a row: it stays with each object
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
@@ -95,10 +50,6 @@ def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
     with pytest.raises(ValueError, match="an integrator, a thermostat or both"):
         cavitymd.StepDraw(1)
     assert "callable raises" in cavitymd.step_draw.__doc__
-
-
-def test_deferred_destroy_takes_the_object_before_its_workspace(capi, monkeypatch):
-    checks.deferred_destroy_takes_the_object_before_its_workspace(ROW, capi, monkeypatch)
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------

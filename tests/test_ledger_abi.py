@@ -1,5 +1,5 @@
-"""The energy ledger (cavmd_ledger_*) on a machine WITHOUT a GPU: the shared checks a to i of tests/batch_objects.py on a row for
-this object built here (none is skipped), every refusal of its item check with its status and the precedence among them, and
+"""What is specific to the energy ledger (cavmd_ledger_*) on a machine WITHOUT a GPU (tests/test_batch_objects_abi.py runs the
+shared checks a to i on its row of tests/batch_objects.py; none is skipped): the header's prose, every refusal of its item check with its status and the precedence among them, and
 the literal layouts of the two structures."""
 import ctypes
 
@@ -9,47 +9,13 @@ import torch
 
 import batch_objects as checks
 from abi_support import HEADER
+from abi_support import good_ledger as _good
 
-byref, vp = ctypes.byref, ctypes.c_void_p
-KB = 3.167e-6
-
-
-def _good(capi, **kw):
-    args = dict(result_ptr=0x10000, vel_ptr=0x20000, members_ptr=0x30004, n_members=500, N=501, energy_ptrs=(0x40000, 0x50000),
-                reservoir_ptrs=(0x60008, 0x70008, 0x80008), time_ptr=0x90008, dof=1500.0, add_cavity_kinetic=1)
-    args.update(kw)
-    return capi.ledger_item(**args)
+ROW = checks.ROWS["ledger"]
+ROW_FIELDS, ITEM_FIELDS = ROW.structs["row"][2], ROW.structs["item"][2]          # {field: offset}, pinned as literals in the row
 
 
-def _on_cpu(cavitymd):
-    vel = torch.zeros((10, 4), dtype=torch.float64)
-    return [lambda: cavitymd.BatchEnergyLedger(checks.NoBatch(), [vel]),
-            lambda: cavitymd.BatchEnergyLedger(None, [vel]),
-            lambda: cavitymd.BatchEnergyLedger(None, [None], terms=[[vel]]),
-            lambda: cavitymd.BatchEnergyLedger(None, [np.zeros((10, 4))])]
-
-
-ROW_FIELDS = dict(call=0, n_terms=8, n_reservoirs=12, time=16, potential=24, cavity=56, cavity_potential=80, potential_total=88,
-                  kinetic_group=96, kinetic_cavity=104, kinetic_total=112, system_total=120, reservoir=128, reservoir_total=160,
-                  universe_total=168, temperature=176, reserved=184)
-ITEM_FIELDS = dict(d_result=0, d_vel=8, d_members=16, n_members=24, N=28, d_energy=32, d_reservoir=64, d_time=96, dof=104,
-                   add_cavity_kinetic=112, reserved0=116, reserved=120)
-
-ROW = checks._row(
-    "ledger",
-    entry_points=("item_check", "create", "destroy", "set_items", "record", "rows", "read", "reset", "device_ptr"),
-    kernels=(b"ledger_batch_kernel",), no_device="no device: no workspace, hence no ledger",
-    structs={"row": ("LedgerRow", 192, ROW_FIELDS), "item": ("LedgerItem", 128, ITEM_FIELDS)},
-    dtypes={"row": "ledger_row_dtype"}, good=_good, without_handle=("item_check",),
-    create=lambda capi, it: (1, byref(it), 8, 1, KB),
-    with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "record": (None,), "rows": (None, byref(ctypes.c_uint64())),
-                                  "read": (None, 0, 1, 0, 1, byref(capi.LedgerRow())), "reset": (None,),
-                                  "device_ptr": (byref(vp()), byref(vp()))},
-    handle="Ledger", handle_methods=("record", "rows", "read", "reset", "set_items", "device_ptr", "close"),
-    cls="BatchEnergyLedger", module="ledger", methods=("record", "rows", "read", "reset", "close"), properties=(), on_cpu=_on_cpu)
-
-
-# ---- the checks every batch object gets (tests/batch_objects.py a to i), on this object's row ----------------------------------
+# ---- what this object adds to the checks every batch object gets (tests/batch_objects.py a to i) ------------------------------
 def test_header_declares_the_nine_entry_points_and_the_contract():
     checks.header_declares_exactly_the_entry_points(ROW)
     text = " ".join(open(HEADER).read().replace("*", " ").split())
@@ -63,9 +29,6 @@ def test_header_declares_the_nine_entry_points_and_the_contract():
     # the section stands after the bath's and before the draws'
     raw = open(HEADER).read()
     assert raw.index("cavmd_bath_state_device_ptr(") < raw.index("typedef struct cavmd_ledger_row") < raw.index("cavmd_draw_item_check(")
-    # no other object's prefix is a prefix of this one's, and the other way round
-    for other in checks.OBJECTS:
-        assert not (ROW.prefix + "_").startswith(other.prefix + "_") and not (other.prefix + "_").startswith(ROW.prefix + "_"), other.prefix
 
 
 def test_libraries_export_them_and_nothing_stray(capi):
@@ -77,7 +40,7 @@ def test_libraries_export_them_and_nothing_stray(capi):
 
 
 def test_the_version_is_still_2(capi):
-    checks.the_version_is_still_2(capi)
+    checks.the_version_is_still_2(capi)                                    # not a check on a row: it stays with each object
 
 
 def test_c_layouts_equal_the_ctypes_ones_and_the_numpy_dtype(capi, tmp_path):
@@ -87,10 +50,6 @@ def test_c_layouts_equal_the_ctypes_ones_and_the_numpy_dtype(capi, tmp_path):
         assert {name: getattr(S, name).offset for name, *_ in S._fields_} == fields
     dt = capi.ledger_row_dtype()
     assert dt.itemsize == 192 and {n: dt.fields[n][1] for n in dt.names} == ROW_FIELDS
-
-
-def test_null_handles_are_refused_without_a_device(capi):
-    checks.null_arguments_are_refused_without_a_device(ROW, capi)
 
 
 def test_launch_order_is_a_stable_descending_sort(capi):
@@ -108,10 +67,6 @@ def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
     assert order == sorted(order)                        # the captured step, in its launch order
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         cavitymd.ledger._reservoir_addresses(torch.zeros(3, dtype=torch.float64), 3)
-
-
-def test_deferred_destroy_takes_the_object_before_its_workspace(capi, monkeypatch):
-    checks.deferred_destroy_takes_the_object_before_its_workspace(ROW, capi, monkeypatch)
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------
