@@ -43,14 +43,20 @@ struct AosInputT
             r.iz = __builtin_nontemporal_load(im + 2);
         }
         else
-        {
-            r.xy = pos2[2 * i];
-            r.zw = pos2[2 * i + 1];
-            r.c = charge[i];
-            r.ix = im[0];
-            r.iy = im[1];
-            r.iz = im[2];
-        }
+            r = load_cached(i);
+        return r;
+    }
+    // Temporal loads whatever NT: for a row that every wave of the grid reads (speculative_photon_row).
+    __device__ __forceinline__ Raw load_cached(size_t i) const
+    {
+        Raw r;
+        const int* im = image + 3 * i;
+        r.xy = pos2[2 * i];
+        r.zw = pos2[2 * i + 1];
+        r.c = charge[i];
+        r.ix = im[0];
+        r.iy = im[1];
+        r.iz = im[2];
         return r;
     }
     // Every field of a row as an operand of an empty statement: the compiler places its counted wait for the row's loads here
@@ -93,6 +99,21 @@ struct StridedInput
         r.iy = __builtin_nontemporal_load(im + 1);
         r.iz = __builtin_nontemporal_load(im + 2);
         r.t = __builtin_nontemporal_load(reinterpret_cast<const int*>(tid + i * tid_stride));
+        return r;
+    }
+    __device__ __forceinline__ Raw load_cached(size_t i) const // as AosInputT::load_cached
+    {
+        Raw r;
+        const double* p = reinterpret_cast<const double*>(pos + i * pos_stride);
+        r.px = p[0];
+        r.py = p[1];
+        r.pz = p[2];
+        r.c = *reinterpret_cast<const double*>(chg + i * chg_stride);
+        const int* im = reinterpret_cast<const int*>(img + i * img_stride);
+        r.ix = im[0];
+        r.iy = im[1];
+        r.iz = im[2];
+        r.t = *reinterpret_cast<const int*>(tid + i * tid_stride);
         return r;
     }
     static __device__ __forceinline__ void landed(const Raw& r) // as AosInputT::landed
@@ -140,13 +161,34 @@ struct PhotonRow
     int ix, iy, iz;
 };
 template <class Input>
-__device__ __forceinline__ PhotonRow photon_row(const Input& in, size_t i)
+__device__ __forceinline__ PhotonRow as_photon_row(const typename Input::Raw& r)
 {
-    const typename Input::Raw r = in.load(i);
     PhotonRow p;
     p.x = Input::x(r); p.y = Input::y(r); p.z = Input::z(r);
     p.ix = r.ix; p.iy = r.iy; p.iz = r.iz;
     return p;
+}
+template <class Input>
+__device__ __forceinline__ PhotonRow photon_row(const Input& in, size_t i)
+{
+    return as_photon_row<Input>(in.load(i));
+}
+// The speculative row, fetched at kernel entry: row N - 1 through VECTOR loads, TEMPORAL ones.
+// Vector: the address is the same in every lane, and with a provably uniform address and __restrict__ const pointers the
+// compiler fetches the row with scalar loads.  Those return out of order, so every wait on them is a full lgkmcnt(0): the wait
+// for the last kernel arguments then also waits for this row -- an HBM miss with nothing else in flight, in front of the first
+// tile load.  The zero below comes out of a vector register the compiler cannot see into, so the index does not look uniform;
+// the loads go down the vector path, where they are older than every tile load, return in order ahead of them and cost the
+// counted waits of the tile loop nothing.  The row is first read after the reduction, in scalars_from_total.
+// Temporal: every wave of the grid asks for the same two lines at the same moment.  As non-temporal (streaming) loads those
+// requests made the single-launch step 0.2 us SLOWER than the scalar loads had been; as temporal loads, which the caches
+// keep, 0.3 us faster (profiles/early_first_load/README.md).
+template <class Input>
+__device__ __forceinline__ PhotonRow speculative_photon_row(const Input& in, unsigned N)
+{
+    unsigned opaque_zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(opaque_zero));
+    return as_photon_row<Input>(in.load_cached((size_t)(N - 1) + opaque_zero));
 }
 
 // Where the per-block partials live (SoA so the finalize kernel reads them coalesced).
@@ -255,6 +297,8 @@ __device__ __forceinline__ void accumulate_full_tiles(const Input& in, const Til
             TileRegs<Input, 1> A;
             tile_load<Input, BLOCK, 1>(in, base, A);
             __builtin_amdgcn_sched_barrier(0);
+            if (k == 0)
+                CAVMD_PSTAMP(8);
             row_hook(k, 0, A.raw[0].c);
             tile_accumulate<Input, BLOCK, 1>(A, base, Lx, Ly, Lz, L_typeid, acc);
         }
@@ -461,9 +505,10 @@ __device__ __forceinline__ Scalars reduce_partials_and_finalize(const Input& in,
                                                                 const Partials& part, bool want_energies)
 {
     // Speculative fetch of the last particle: the driver appends the photon last (examples/05_advanced_run.py:
-    // 497-505), so this usually removes a dependent memory round trip after the reduction.
+    // 497-505), so this usually removes a dependent memory round trip after the reduction.  Vector loads, in flight together
+    // with the partials' loads below (as scalar loads the row was two serial misses ahead of them).
     CAVMD_STAMP(0);
-    const PhotonRow guess = photon_row(in, (size_t)(N - 1));
+    const PhotonRow guess = speculative_photon_row(in, N);
 
     Accum acc;
     const unsigned s = part.stride;

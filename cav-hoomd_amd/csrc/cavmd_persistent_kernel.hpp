@@ -604,9 +604,15 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
                 __builtin_amdgcn_s_sleep(64);
         }
     }
-    // this evaluation's tag, and the speculative photon row (the driver appends the photon last)
+    // this evaluation's tag, and the speculative photon row (the driver appends the photon last): vector loads, issued here so
+    // that they are older than every tile load; nothing waits for them before scalars_from_total
     const LaunchTag lt = read_launch_tag(st, sequence);
-    const PhotonRow guess = photon_row(in, (size_t)(N - 1));
+    const PhotonRow guess = speculative_photon_row(in, N);
+    // The kernel arguments fetched last (L_typeid among them) are waited for HERE, where the scalar row's wait used to cover
+    // them; their lines are in the scalar cache by now.  Scalar loads return out of order, so the wait is a full lgkmcnt(0):
+    // left to the compiler it sits at L_typeid's first use, inside the tile loop, and there every row also waits for its
+    // own LDS store.
+    asm volatile("" : : "s"(L_typeid));
 
     const BlockRange rg = block_range<TILE>(N, G, b, balanced);
     Accum acc = block_partial<BLOCK, UNROLL>(in, rg, Lx, Ly, Lz, L_typeid, s_charge, lds_slots);

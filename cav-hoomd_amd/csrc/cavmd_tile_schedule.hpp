@@ -21,6 +21,12 @@
 #define CAVMD_HD inline
 #endif
 
+// Diagnostic hook (csrc/microbench_persistent.hip): per-block time stamps at numbered points; nothing in the product.  Point 8
+// is here: the rows of the block's first tile have been issued.
+#ifndef CAVMD_PSTAMP
+#define CAVMD_PSTAMP(k)
+#endif
+
 namespace cavmd
 {
 
@@ -78,6 +84,7 @@ CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue,
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
         issue(0, u, tile_row_base(s, 0, u, block));
+    CAVMD_PSTAMP(8);
     unsigned k = 0;
     for (; k + 2 < s.nfull; k += 2)
     {

@@ -1,6 +1,7 @@
 // microbench_persistent.hip -- developer tool (not part of the product or of bench.py): the single-launch evaluation
 // (cavmd_persistent_kernel.hpp) against the two-launch path, interleaved round by round on HBM-cold frames, plus a
-// per-block time line of the single-launch kernel (wall_clock64 stamps, 10 ns resolution).
+// per-block time line of the single-launch kernel (wall_clock64 stamps, 10 ns resolution): entry, first tile row issued,
+// phase 1 done, and the points of the hand-off and the map.
 //
 //   ./microbench_persistent [N=1000001] [frames=7] [rounds=9] [launches_per_round=20]
 #include <hip/hip_runtime.h>
@@ -16,7 +17,7 @@
 
 #include "cavmd.h"
 
-constexpr int kStampSlots = 8;
+constexpr int kStampSlots = 9;
 __device__ unsigned long long g_pstamps[4096 * kStampSlots];
 __device__ unsigned g_xcc[4096];
 #define CAVMD_PSTAMP(k)                                                \
@@ -223,9 +224,9 @@ int main(int argc, char** argv)
     for (int mode = 0; mode < 1; ++mode)
     {
         const unsigned g1 = grid(N, 256 * unroll, 1);
-        const char* names[8] = {"start", "phase1 done", "block tree done", "total in wave 0", "scalars in LDS",
-                                "barrier passed", "stores issued", "group level done"};
-        std::vector<std::vector<double>> med(8), mx(8), mnv(8);
+        const char* names[kStampSlots] = {"start", "phase1 done", "block tree done", "total in wave 0", "scalars in LDS",
+                                          "barrier passed", "stores issued", "group level done", "first tile row issued"};
+        std::vector<std::vector<double>> med(kStampSlots), mx(kStampSlots), mnv(kStampSlots);
         std::vector<std::vector<double>> xcc_p1(30, std::vector<double>(8, 0.0));
         std::vector<int> xcc_frame(30, 0);
         for (int rep = 0; rep < 30; ++rep)
@@ -271,10 +272,12 @@ int main(int argc, char** argv)
                 for (unsigned b = 0; b < 16 && b < g1; ++b) printf("%.2f ", (double)(h[b * kStampSlots + 4] - t0) * 0.01);
                 printf("\n");
             }
-            for (int k = 0; k < 8; ++k)
+            for (int k = 0; k < kStampSlots; ++k)
             {
                 std::vector<double> v(g1);
-                for (unsigned b = 0; b < g1; ++b) v[b] = (double)(h[b * kStampSlots + k] - t0) * 0.01; // 100 MHz -> us
+                // (a block without a full tile never reaches point 8: it counts with its start)
+                const unsigned with_tile = (unsigned)(N / (256 * unroll));
+                for (unsigned b = 0; b < g1; ++b) v[b] = (double)(h[b * kStampSlots + (k == 8 && b >= with_tile ? 0 : k)] - t0) * 0.01; // 100 MHz -> us
                 std::sort(v.begin(), v.end());
                 med[k].push_back(v[g1 / 2]); mx[k].push_back(v.back()); mnv[k].push_back(v.front());
             }
@@ -283,7 +286,7 @@ int main(int argc, char** argv)
         for (int rep = 0; rep < 30; ++rep) { printf("   run %2d (frame %d):", rep, xcc_frame[rep]); for (int x = 0; x < 8; ++x) printf(" %6.2f", xcc_p1[rep][x]); printf("\n"); }
         printf("time line, single launch, grid %u (us after the first block's start; median over 30 runs of the per-run min / median / max over blocks)\n",
                g1);
-        for (int k : {0, 1, 2, 7, 3, 4, 5, 6})
+        for (int k : {0, 8, 1, 2, 7, 3, 4, 5, 6})
         {
             std::sort(med[k].begin(), med[k].end()); std::sort(mx[k].begin(), mx[k].end()); std::sort(mnv[k].begin(), mnv[k].end());
             printf("  %-22s min %6.2f  median %6.2f  max %6.2f\n", names[k], mnv[k][15], med[k][15], mx[k][15]);
