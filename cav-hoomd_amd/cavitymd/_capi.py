@@ -148,6 +148,22 @@ class BathState(ctypes.Structure):
                 ("reserved", ctypes.c_double)]
 
 
+class ThermalizeItem(ctypes.Structure):
+    """cavmd_thermalize_item (160 bytes): the start of one system of a batch; all pointers are DEVICE pointers."""
+    _fields_ = [("d_vel", ctypes.c_void_p), ("d_members", ctypes.c_void_p), ("d_pos", ctypes.c_void_p),
+                ("d_image", ctypes.c_void_p), ("d_result", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("kT", ctypes.c_double),
+                ("N", ctypes.c_uint32), ("n_members", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("L", ctypes.c_double * 3), ("params", Params),
+                ("reserved", ctypes.c_uint64 * 4)]
+
+
+class ThermalizeState(ctypes.Structure):
+    """cavmd_thermalize_state (64 bytes): one item's counters."""
+    _fields_ = [("draws", ctypes.c_uint64), ("thermalised", ctypes.c_uint64), ("skipped", ctypes.c_uint64),
+                ("momentum", ctypes.c_double * 3), ("photon", ctypes.c_int32), ("reserved0", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64)]
+
+
 class LedgerItem(ctypes.Structure):
     """cavmd_ledger_item (128 bytes): one system of an energy ledger; all pointers are DEVICE pointers."""
     _fields_ = [("d_result", ctypes.c_void_p), ("d_vel", ctypes.c_void_p), ("d_members", ctypes.c_void_p),
@@ -291,6 +307,23 @@ def bath_item(gamma_ptr=0, N=0, kT=0.0, seed=0) -> "BathItem":
     it = BathItem()
     it.d_gamma, it.N = gamma_ptr or None, int(N)
     it.kT, it.seed = float(kT), int(seed)
+    return it
+
+
+THERMALIZE_ZERO_MOMENTUM, THERMALIZE_PLACE_PHOTON, THERMALIZE_FINITE_Q, THERMALIZE_PHOTON_VELOCITY = 1, 2, 4, 8
+THERMALIZE_TILE = 512
+
+
+def thermalize_item(vel_ptr=0, N=0, kT=0.0, seed=0, members_ptr=0, n_members=0, flags=0, pos_ptr=0, image_ptr=0, result_ptr=0,
+                    box_L=(0.0, 0.0, 0.0), params=None) -> "ThermalizeItem":
+    """members_ptr == 0: the default set (every particle but the photon the result block names)."""
+    it = ThermalizeItem()
+    it.d_vel, it.d_members, it.N, it.n_members = vel_ptr or None, members_ptr or None, int(N), int(n_members)
+    it.d_pos, it.d_image, it.d_result = pos_ptr or None, image_ptr or None, result_ptr or None
+    it.kT, it.seed, it.flags = float(kT), int(seed), int(flags)
+    it.L[0], it.L[1], it.L[2] = (float(x) for x in box_L)
+    if params is not None:
+        it.params = params
     return it
 
 
@@ -453,6 +486,15 @@ _PROTOTYPES = {
     "cavmd_ledger_read": (_ci, [_vp, _vp, _sz, _sz, _u64, _sz, _vp]),
     "cavmd_ledger_reset": (_ci, [_vp, _vp]),
     "cavmd_ledger_device_ptr": (_ci, [_vp, _P(_vp), _P(_vp)]),
+    # (the header declares these eight between the bath's and the ledger's, whose block stays directly behind the bath's here)
+    "cavmd_thermalize_item_check": (_ci, [_P(ThermalizeItem)]),
+    "cavmd_thermalize_create": (_ci, [_vp, _sz, _P(ThermalizeItem), _P(_vp)]),
+    "cavmd_thermalize_destroy": (_ci, [_vp]),
+    "cavmd_thermalize_set_items": (_ci, [_vp, _sz, _sz, _P(ThermalizeItem)]),
+    "cavmd_thermalize_run": (_ci, [_vp, _vp]),
+    "cavmd_thermalize_read": (_ci, [_vp, _vp, _vp]),
+    "cavmd_thermalize_reset": (_ci, [_vp, _vp]),
+    "cavmd_thermalize_state_device_ptr": (_ci, [_vp, _P(_vp)]),
     "cavmd_draw_item_check": (_ci, [_P(DrawItem)]),
     "cavmd_draw_create": (_ci, [_vp, _u64, _sz, _P(DrawItem), _P(_vp)]),
     "cavmd_draw_destroy": (_ci, [_vp]),
@@ -815,8 +857,8 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What the ten batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Ledger, Draw, Molecular and
-    Coulomb): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
+    """What the eleven batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Thermalize, Ledger, Draw,
+    Molecular and Coulomb): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
     only.  A subclass names its item structure, its ``cavmd_*`` prefix and the size the library sorts its launch order by.
     Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -952,6 +994,7 @@ recorder_item_check = _item_check("cavmd_recorder", "recorder")
 field_item_check = _item_check("cavmd_field_recorder", "field")
 verlet_item_check = _item_check("cavmd_verlet", "verlet")
 bath_item_check = _item_check("cavmd_bath", "bath")
+thermalize_item_check = _item_check("cavmd_thermalize", "thermalize")
 ledger_item_check = _item_check("cavmd_ledger", "ledger")
 draw_item_check = _item_check("cavmd_draw", "draw")
 coulomb_item_check = _item_check("cavmd_coulomb", "coulomb")
@@ -960,6 +1003,7 @@ record_dtype = _dtype_of(Record)
 field_record_dtype = _dtype_of(FieldRecord)
 verlet_state_dtype = _dtype_of(VerletState)
 bath_state_dtype = _dtype_of(BathState)
+thermalize_state_dtype = _dtype_of(ThermalizeState)
 ledger_row_dtype = _dtype_of(LedgerRow)
 draw_state_dtype = _dtype_of(DrawState)
 
@@ -1171,6 +1215,21 @@ class Bath(_StateHandle):
     def step_two(self, stream: int, inputs_ptr: int) -> None:
         """One kernel, in place of ``Verlet.step_two``: net force, the row's and the group's baths, acceleration and kick."""
         check(self._lib.cavmd_bath_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)), "cavmd_bath_step_two")
+
+
+class Thermalize(_StateHandle):
+    """Owns one cavmd_thermalize: the start of B independent small systems, ONE kernel launch, one workgroup per system: seeded
+    Maxwell-Boltzmann velocities on any set of particles, their momentum taken out, the photon's velocity and placement.
+    Launched by N descending."""
+    _ITEM, _PREFIX, _STATE = ThermalizeItem, "cavmd_thermalize", ThermalizeState
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items):
+        self._create(workspace, items)
+
+    def run(self, stream: int = 0) -> None:
+        """One kernel: the velocities, counters and photon of every item."""
+        check(self._lib.cavmd_thermalize_run(self._h, ctypes.c_void_p(stream)), "cavmd_thermalize_run")
 
 
 class Ledger(_SeriesHandle):

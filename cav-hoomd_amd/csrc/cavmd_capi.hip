@@ -1,7 +1,7 @@
 // cavmd_capi.hip -- the workspace of include/cavmd.h and the evaluation of the cavity force on it, on top of the kernels in
 // cavmd_force_kernels.hpp and cavmd_persistent_kernel.hpp: create and destroy, the dispatcher, the result ring and its
 // getters, profiling, tunables.  The rest of the header is in units of their own: cavmd_observables.hip, and seven units
-// for the ten batch objects ('Translation units and the build graph').  Whatever CAVMD_TEST_HOOKS guards is here,
+// for the eleven batch objects ('Translation units and the build graph').  Whatever CAVMD_TEST_HOOKS guards is here,
 // and only here.
 //
 // Host side of the replaced reference code: CavityForceComputeGPU::computeForces

@@ -1,5 +1,5 @@
 // cavmd_coulomb.hip -- cavmd_coulomb of include/cavmd.h: Ewald Coulomb forces of a batch of small systems in two launches.
-// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the eleven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>

@@ -1,5 +1,5 @@
 // cavmd_field_recorder.hip -- cavmd_field_recorder of include/cavmd.h: density field and F(k,t) of a batch appended to a series
-// in device memory.  One of the ten objects built on an item table (cavmd_item_table.hpp), a SeriesTable; the workspace is an
+// in device memory.  One of the eleven objects built on an item table (cavmd_item_table.hpp), a SeriesTable; the workspace is an
 // incomplete type here.
 #include <hip/hip_runtime.h>
 

@@ -1,11 +1,11 @@
-// Host-only: what the ten "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
+// Host-only: what the eleven "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
 // cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder and the ledger, which has its shape), cavmd_field_recorder.hip,
-// cavmd_verlet.hip (the integrator, the draw object that writes its input rows and the bath that supplies its second
-// half-step), cavmd_molecular.hip and cavmd_coulomb.hip.
+// cavmd_verlet.hip (the integrator, the draw object that writes its input rows, the bath that supplies its second
+// half-step and the thermalize object that starts a run), cavmd_molecular.hip and cavmd_coulomb.hip.
 // ItemTable is how a table of items lives on the host and on the device; create_table makes an object and ties it to its
 // parent, ItemTable::launch launches it and destroy_table releases it.  Three flavours state what more an object keeps:
 // SeriesTable, a ring of records per item (the two recorders and the ledger); StateTable, one state per item (the
-// integrator, the draw object and the bath); LinkedTable, tables derived from the items that the kernels find through a
+// integrator, the draw object, the bath and the thermalize object); LinkedTable, tables derived from the items that the kernels find through a
 // header at a fixed device address and that set_items replaces together (the two force batches).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once

@@ -1,5 +1,5 @@
 // cavmd_molecular.hip -- cavmd_molecular of include/cavmd.h: bonds and Lennard-Jones pairs of a batch of small systems in one launch.
-// One of the ten objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the eleven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>

@@ -1,6 +1,6 @@
 // cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory;
 // and cavmd_ledger, the energy ledger, which has the recorder's shape and calls its kinetic-energy code (two objects in one
-// unit, as cavmd_verlet.hip holds three).  Two of the ten objects built on an item table (cavmd_item_table.hpp), each a
+// unit, as cavmd_verlet.hip holds three).  Two of the eleven objects built on an item table (cavmd_item_table.hpp), each a
 // SeriesTable; what the two share beyond that is PeriodicSeries, below.  The workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,9 @@
 // cavmd_verlet.hip -- cavmd_verlet of include/cavmd.h: the velocity-Verlet half-steps of a batch of small systems, one launch
 // each; and cavmd_draw, which writes the input rows those half-steps (and the thermostat batch) read: seeded variates and the
 // step's dt, one launch per step; and cavmd_bath, created from an integrator, whose launch takes the place of the integrator's
-// second half-step with a Langevin bath on any set of particles.  Three of the ten objects built on an item table
-// (cavmd_item_table.hpp), each a StateTable; the workspace is an incomplete type here.
+// second half-step with a Langevin bath on any set of particles; and cavmd_thermalize, which starts a run: seeded momenta and
+// the photon's placement, one launch.  Four of the eleven objects built on an item table (cavmd_item_table.hpp), each a
+// StateTable; the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -14,6 +15,7 @@
 #include "cavmd_verlet_batch_kernel.hpp"
 #include "cavmd_draw_kernel.hpp"
 #include "cavmd_bath_kernel.hpp"
+#include "cavmd_thermalize_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -76,8 +78,46 @@ struct cavmd_bath : StateTable<cavmd_bath_item, BathRow, BathState> // tied to v
     }
 };
 
+// ---- the start of a batch: seeded momenta and the photon's placement, one launch (cavmd_thermalize_kernel.hpp) ----------------
+struct cavmd_thermalize : StateTable<cavmd_thermalize_item, ThermalizeRow, ThermalizeState> // launched by N descending
+{
+    cavmd_thermalize()
+        : StateTable(cavmd_thermalize_item_check, [](const cavmd_thermalize_item& it) { return it.N; },
+                     uploaded_as_it_is<cavmd_thermalize_item, ThermalizeRow>)
+    {
+    }
+};
+
 namespace
 {
+static_assert(offsetof(cavmd_thermalize_item, d_vel) == offsetof(ThermalizeRow, vel2)
+                  && offsetof(cavmd_thermalize_item, d_members) == offsetof(ThermalizeRow, members)
+                  && offsetof(cavmd_thermalize_item, d_pos) == offsetof(ThermalizeRow, pos2)
+                  && offsetof(cavmd_thermalize_item, d_image) == offsetof(ThermalizeRow, image)
+                  && offsetof(cavmd_thermalize_item, d_result) == offsetof(ThermalizeRow, res)
+                  && offsetof(cavmd_thermalize_item, seed) == offsetof(ThermalizeRow, seed)
+                  && offsetof(cavmd_thermalize_item, kT) == offsetof(ThermalizeRow, kT)
+                  && offsetof(cavmd_thermalize_item, N) == offsetof(ThermalizeRow, n)
+                  && offsetof(cavmd_thermalize_item, n_members) == offsetof(ThermalizeRow, n_members)
+                  && offsetof(cavmd_thermalize_item, flags) == offsetof(ThermalizeRow, flags)
+                  && offsetof(cavmd_thermalize_item, L) == offsetof(ThermalizeRow, L)
+                  && offsetof(cavmd_thermalize_item, params) == offsetof(ThermalizeRow, omegac)
+                  && offsetof(cavmd_thermalize_item, params) + offsetof(cavmd_params, couplstr) == offsetof(ThermalizeRow, couplstr)
+                  && offsetof(cavmd_thermalize_item, params) + offsetof(cavmd_params, K) == offsetof(ThermalizeRow, K)
+                  && sizeof(cavmd_thermalize_item) == sizeof(ThermalizeRow),
+              "thermalize item layout");
+static_assert(sizeof(cavmd_thermalize_state) == sizeof(ThermalizeState)
+                  && offsetof(cavmd_thermalize_state, draws) == offsetof(ThermalizeState, draws)
+                  && offsetof(cavmd_thermalize_state, thermalised) == offsetof(ThermalizeState, thermalised)
+                  && offsetof(cavmd_thermalize_state, skipped) == offsetof(ThermalizeState, skipped)
+                  && offsetof(cavmd_thermalize_state, momentum) == offsetof(ThermalizeState, momentum)
+                  && offsetof(cavmd_thermalize_state, photon) == offsetof(ThermalizeState, photon),
+              "the thermalize states are read out as they are");
+static_assert(CAVMD_THERMALIZE_ZERO_MOMENTUM == kThermalizeZeroMomentum && CAVMD_THERMALIZE_PLACE_PHOTON == kThermalizePlacePhoton
+                  && CAVMD_THERMALIZE_FINITE_Q == kThermalizeFiniteQ && CAVMD_THERMALIZE_PHOTON_VELOCITY == kThermalizePhotonVelocity
+                  && CAVMD_THERMALIZE_TILE == kThermalizeTile,
+              "the flags and the tile the header publishes");
+static_assert(offsetof(cavmd_result, photon_idx) == 136 && offsetof(cavmd_result, n_particles) == 144, "the result block's words");
 static_assert(offsetof(cavmd_bath_item, d_gamma) == offsetof(BathRow, gamma) && offsetof(cavmd_bath_item, seed) == offsetof(BathRow, seed)
                   && offsetof(cavmd_bath_item, kT) == offsetof(BathRow, kT) && offsetof(cavmd_bath_item, N) == offsetof(BathRow, n)
                   && sizeof(cavmd_bath_item) == sizeof(BathRow),
@@ -370,6 +410,85 @@ int cavmd_bath_reset(cavmd_bath* b, void* stream_)
 int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out)
 {
     return b ? b->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+// ---- cavmd_thermalize ------------------------------------------------------------------------------------------------------
+int cavmd_thermalize_item_check(const cavmd_thermalize_item* it)
+{
+    if (!it)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->reserved0 != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (int k = 0; k < 4; ++k)
+        if (it->reserved[k] != 0)
+            return CAVMD_ERR_INVALID_VALUE;
+    constexpr uint32_t known = CAVMD_THERMALIZE_ZERO_MOMENTUM | CAVMD_THERMALIZE_PLACE_PHOTON | CAVMD_THERMALIZE_FINITE_Q
+                               | CAVMD_THERMALIZE_PHOTON_VELOCITY;
+    if (it->flags & ~known)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_members & 3) || ((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_image & 3)
+        || ((uintptr_t)it->d_result & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N != 0 && !it->d_vel)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (!it->d_members && it->n_members != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    const double values[] = {it->kT,           it->L[0],          it->L[1],    it->L[2],
+                             it->params.omegac, it->params.couplstr, it->params.K, it->params.phmass};
+    for (double x : values)
+        if (!finite_nonnegative(x))
+            return CAVMD_ERR_INVALID_VALUE;
+    if ((it->flags & CAVMD_THERMALIZE_FINITE_Q) && !it->d_result)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->flags & CAVMD_THERMALIZE_PLACE_PHOTON)
+    {
+        if (!it->d_pos || !it->d_image || !it->d_result)
+            return CAVMD_ERR_INVALID_VALUE;
+        // the placement divides by every edge and by K
+        if (it->L[0] == 0.0 || it->L[1] == 0.0 || it->L[2] == 0.0 || it->params.K == 0.0)
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N || it->n_members > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_thermalize_create(cavmd_workspace* ws, size_t n_items, const cavmd_thermalize_item* h_items, cavmd_thermalize** out)
+{
+    return create_table(tie_of(ws), n_items, h_items, out, CAVMD_OK, [](cavmd_thermalize*) {});
+}
+
+int cavmd_thermalize_destroy(cavmd_thermalize* t)
+{
+    return destroy_table(t);
+}
+
+int cavmd_thermalize_set_items(cavmd_thermalize* t, size_t first, size_t count, const cavmd_thermalize_item* h_items)
+{
+    return t ? t->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_thermalize_run(cavmd_thermalize* t, void* stream_)
+{
+    if (!t)
+        return CAVMD_ERR_INVALID_VALUE;
+    return t->launch((hipStream_t)stream_, thermalize_batch_kernel<256>, dim3((unsigned)t->n), dim3(256), 0, t->d_rows.ptr,
+                     t->d_order.ptr, t->d_state.ptr);
+}
+
+int cavmd_thermalize_read(cavmd_thermalize* t, void* stream_, cavmd_thermalize_state* out)
+{
+    return t ? t->read((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_thermalize_reset(cavmd_thermalize* t, void* stream_)
+{
+    return t ? t->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_thermalize_state_device_ptr(cavmd_thermalize* t, const cavmd_thermalize_state** out)
+{
+    return t ? t->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
 }
 
 } // extern "C"

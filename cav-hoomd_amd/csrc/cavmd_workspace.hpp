@@ -1,6 +1,6 @@
 // Host-only: struct cavmd_workspace, and what BOTH units that see inside it use (cavmd_capi.hip: create, destroy, the
 // evaluation and its results, profiling, tunables; cavmd_observables.hip: the observables and the workspace thermostat).
-// No other unit includes this: the ten batch objects reach a workspace through its WorkspaceTie (cavmd_item_table.hpp).
+// No other unit includes this: the eleven batch objects reach a workspace through its WorkspaceTie (cavmd_item_table.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -869,6 +869,125 @@ CAVMD_API int cavmd_bath_reset(cavmd_bath* b, void* stream);
 /* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out);
 
+/* ---- the start of a batch: seeded momenta and the photon's placement in ONE launch: the driver's thermalize_system ------------- */
+/* The sections above and below cover every step of the reference driver's run; this one covers its start.  Before the first
+ * step the driver thermalises the molecular momenta and draws a velocity for the cavity particle
+ * (examples/05_advanced_run.py:710-750, thermalize_system), and it places the cavity particle at q = 0 or, with --finite-q, at
+ * -d g / omegac^2 with the z component zeroed, adds a thermal spread sqrt(kT / omegac^2) where g != 0, wraps the position and
+ * sets the image flags (:455-494, create_cavity_particle) -- all on the host, with one numpy generator walked through the
+ * systems in order.  Here ONE kernel does it for all items, one 256-thread workgroup per item in the launch order the other
+ * objects use (N descending, stable), reading the molecular dipole where it lives: in the item's result block of the cavity
+ * batch.  It is seeded and counted like the bath: the variates of an item are a function of (its seed, its `draws`, the
+ * particle, the component) alone, so a system's start does not depend on its place in a batch, and a captured launch draws a
+ * new block with every replay -- re-thermalising between segments of a run needs no host work.  No workgroup waits for another,
+ * hence no CAVMD_ERR_SYNC_TIMEOUT here.  The order of a start is {cavmd_batch_compute (the dipole), cavmd_thermalize_run,
+ * cavmd_batch_compute and the other forces again (a moved photon makes the earlier ones stale), cavmd_verlet_accelerations}.
+ *
+ * The expressions below ARE the contract (tests/thermalize_mirror.py restates them); one IEEE fp64 rounding per operation, no
+ * FMA; division and square root are correctly rounded.  One run of one item, `draws` being the item's counter in DEVICE memory
+ * when the kernel RUNS:
+ *   1. Generator.  Philox4x32-10 exactly as item 1 of "the step inputs of a batch" below, words to doubles as its item 2.  Key =
+ *      (seed low, seed high) of the ITEM.  Counter = (draws low, draws high, j, purpose).  Velocity component c = 0, 1, 2 of
+ *      particle j uses purpose 0xC0000000 + c; component c of the photon's position uses purpose 0xC0000008 + c, with j the
+ *      photon's index.  This range is apart from cavmd_draw's purposes (all below 48) and from the bath's (0x80000000 + b) even
+ *      under equal keys.  A normal n is that section's item 3, sqrt(-2 * log(u1)) * cospi(2 * u2) with u1 from w0,w1 (an
+ *      argument of log) and u2 from w2,w3 of ONE block: one block per normal.
+ *   2. Members.  The set is the list d_members[0 .. n_members), or with d_members NULL every j < N except the photon of item
+ *      4 (every j < N when item 4 names none).  For each j of the set with j < N and a mass m = d_vel[j].w that is finite and
+ *      > 0:  sigma = sqrt(kT / m);  v_c = sigma * n_c, c = 0, 1, 2.  .w keeps its bits: the row is written with one 16-byte
+ *      and one 8-byte store, as the integrator writes it.  Any other j of the set (an index >= N, which is never
+ *      dereferenced; a mass that is 0, negative, infinite or a NaN) leaves its row untouched and is counted in `skipped`;
+ *      `thermalised` is the number of rows written.  The indices of a list must be distinct: this is NOT checked, and two
+ *      entries naming one particle race.
+ *   3. CAVMD_THERMALIZE_ZERO_MOMENTUM.  P_c = the sum over the thermalised j of m * v_c, each addend rounded once; a
+ *      compensated (double-double) sum in an order that depends on N and the member list only -- entry k of the set belongs
+ *      to lane k mod 256 (tiles of CAVMD_THERMALIZE_TILE entries walked in order, a shuffle tree over the wave, the four waves
+ *      in wave order: the fold of the bath's tally), not on the batch, the item's place in it, the compute unit, or eager launch
+ *      versus graph replay -- rounded once, within 2 ulp of the exact sum of those addends.  Then, for every thermalised j,
+ *      v_c = v_c - (P_c / (double)thermalised) / m.  `momentum` = P; it is 0 when the flag is off or nothing was thermalised.
+ *      This restates HOOMD-blue 4.x ParticleGroup::thermalizeParticleMomenta (normal velocities of variance kT / m, then the
+ *      centre-of-mass momentum shared out as P / n per particle) FROM KNOWLEDGE: HOOMD is not in the checkout, and parity with
+ *      it is pinned by nothing.
+ *   4. The photon.  Only with d_result, and only if that block's n_particles == N and 0 <= photon_idx < N; otherwise `photon` =
+ *      -1 and nothing of this item is done, which is not an error (the no-photon rule of cavmd_compute_hoomd).  With p =
+ *      photon_idx, K and g = couplstr from `params`, d = the block's dipole, after every store of items 2 and 3:
+ *        CAVMD_THERMALIZE_PHOTON_VELOCITY   v_c = sqrt(kT / d_vel[p].w) * n_c with j = p and the velocity purposes; no
+ *                                           momentum term (the driver's :729 at mass 1); a mass that is not finite and > 0
+ *                                           leaves the row untouched
+ *        CAVMD_THERMALIZE_PLACE_PHOTON      x_c = FINITE_Q ? ((-d_c) * g) / K : 0 for c = 0, 1, and x_z = 0;
+ *                                           if g != 0:  x_c = x_c + sqrt(kT / K) * n_c for all three c (position purposes);
+ *                                           i_c = floor((x_c + L_c / 2) / L_c);  pos_c = x_c - i_c * L_c;
+ *                                           d_image[p] = i as int32;  d_pos[p].w keeps its bits
+ *      These are the driver's lines :464-494; at phmass = 1 (K = omegac^2) they are bit for bit the same expressions.  A list
+ *      that names p thermalises it as a member first; PHOTON_VELOCITY then overwrites that row.
+ *   5. Counters.  draws += 1 per run of an item, also when its set is empty; an item with N == 0 is untouched, its state
+ *      included.  cavmd_thermalize_reset zeroes the states, so the same variates come again.
+ * The limits.  The variates are Philox with the counter layout published here, not HOOMD's RandomGenerator and not numpy's: no
+ * start is bit-comparable with a HOOMD run; log and cospi are the device library's (tests/draw_mirror.py derives the bound
+ * between two implementations); everything else is held to the expressions above.  Angular momenta and triclinic boxes stay out
+ * of scope. */
+#define CAVMD_THERMALIZE_ZERO_MOMENTUM 1u  /* item 3 */
+#define CAVMD_THERMALIZE_PLACE_PHOTON 2u   /* item 4: position and image of the photon */
+#define CAVMD_THERMALIZE_FINITE_Q 4u       /* item 4: the displaced equilibrium; needs d_result */
+#define CAVMD_THERMALIZE_PHOTON_VELOCITY 8u /* item 4: the photon's velocity */
+#define CAVMD_THERMALIZE_TILE 512u         /* entries of a member set per tile of the kernel: T of item 3's order */
+typedef struct cavmd_thermalize_item     /* 160 B; all pointers DEVICE pointers */
+{
+    cavmd_double4* d_vel;          /* N rows, 16-byte aligned, mass in .w; required with N != 0 */
+    const uint32_t* d_members;     /* n_members indices, 4-byte aligned; NULL (with n_members 0): the default set of item 2.
+                                      Not NULL with n_members 0: the empty set */
+    cavmd_double4* d_pos;          /* the arrays of the cavity batch's item (16 / 4-byte aligned); required by PLACE_PHOTON */
+    cavmd_int3* d_image;
+    const cavmd_result* d_result;  /* this item's block of cavmd_batch_results_device_ptr, 8-byte aligned; NULL: no photon */
+    uint64_t seed;                 /* the Philox key of THIS item, as cavmd_bath_item.seed */
+    double kT;                     /* finite, >= 0 */
+    uint32_t N;                    /* <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t n_members;            /* <= CAVMD_BATCH_MAX_ITEM_N */
+    uint32_t flags;                /* CAVMD_THERMALIZE_* */
+    uint32_t reserved0;            /* 0 */
+    double L[3];                   /* the box edges; finite, >= 0, and > 0 with PLACE_PHOTON */
+    cavmd_params params;           /* 32 B; every field finite and >= 0, K > 0 with PLACE_PHOTON */
+    uint64_t reserved[4];          /* 0 */
+} cavmd_thermalize_item;
+typedef struct cavmd_thermalize_state    /* 64 B, one per item, device memory; only the item's workgroup writes it, plain stores */
+{
+    uint64_t draws;                /* runs of this item (the generator's counter) */
+    uint64_t thermalised;          /* rows item 2 wrote in the last run */
+    uint64_t skipped;              /* entries of the set it left untouched */
+    double momentum[3];            /* P of item 3 */
+    int32_t photon;                /* the photon of item 4 in the last run, -1 for none */
+    uint32_t reserved0;
+    uint64_t reserved;
+} cavmd_thermalize_state;
+typedef struct cavmd_thermalize cavmd_thermalize; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item,
+ * reserved words that are not 0, an unknown flag, a misaligned pointer, d_vel NULL with N != 0, d_members NULL with n_members
+ * != 0, a kT, box edge or params field that is negative or not finite, FINITE_Q without d_result, PLACE_PHOTON without d_pos,
+ * d_image or d_result, or with a box edge or K that is 0; CAVMD_ERR_CAPACITY for N or n_members above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_thermalize_item_check(const cavmd_thermalize_item* item);
+/* Validates the n_items rows in HOST memory (1 .. CAVMD_BATCH_MAX_ITEMS), copies the table to the device of `ws` (set-up time)
+ * and allocates one zeroed state per item on the device.  cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees nothing while
+ * a thermalize object of the workspace is alive.  Without a device there is no workspace, hence no thermalize object. */
+CAVMD_API int cavmd_thermalize_create(cavmd_workspace* ws, size_t n_items, const cavmd_thermalize_item* h_items,
+                                      cavmd_thermalize** out);
+/* Synchronises the stream of the last launch (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_thermalize_destroy(cavmd_thermalize* t);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last launch; nothing is
+ * changed if a row is refused; the items' states are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and
+ * for a range outside the table.  A launch captured earlier finds the new rows through the table. */
+CAVMD_API int cavmd_thermalize_set_items(cavmd_thermalize* t, size_t first, size_t count, const cavmd_thermalize_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait; may be captured into a
+ * hipGraph, and a replay draws like an eager call.  It must be ordered after the cavmd_batch_compute whose dipole it reads and
+ * before every launch that reads the velocities or the photon's position.  One object serves one stream at a time. */
+CAVMD_API int cavmd_thermalize_run(cavmd_thermalize* t, void* stream);
+/* Synchronises `stream`, then out = the n_items states.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
+CAVMD_API int cavmd_thermalize_read(cavmd_thermalize* t, void* stream, cavmd_thermalize_state* out);
+/* Zero the states of all items (ordered on `stream`), `draws` included: after it the same variates come again. */
+CAVMD_API int cavmd_thermalize_reset(cavmd_thermalize* t, void* stream);
+/* Device address of the n_items states (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_thermalize_state_device_ptr(cavmd_thermalize* t, const cavmd_thermalize_state** out);
+
 /* ---- the energy ledger of a batch: every term of the conserved energy per step, recorded on the device in ONE launch ---------- */
 /* What the reference's EnergyTracker (src/cavitymd/analysis.py:425-1046) writes per output step for every replica -- the
  * potential of every force, the three cavity energies, the molecular, cavity and total kinetic energy, the system total, the
