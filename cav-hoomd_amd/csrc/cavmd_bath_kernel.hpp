@@ -12,8 +12,12 @@
 //   bath       coeff_j = sqrt(((6 gamma_j) kT) / dt);  bd_c = u_c coeff_j - gamma_j v_c (v from BEFORE the kick);  F_c += bd_c;
 //              tally_j = (bd_x v_x + bd_y v_y) + bd_z v_z
 //   per item   coupled = their number;  T = the double-double sum of the tallies in an order fixed by N (lane-serial over the
-//              tiles, a shuffle tree over the wave, the four waves in wave order), rounded once;  reservoir -= T dt;  draws += 1
+//              tiles, then block_tally of cavmd_reduce.hpp: a shuffle tree over the wave, the four waves in wave order), rounded
+//              once;  reservoir -= T dt;  draws += 1
 // Everything else is verlet_step_two_kernel's, expression for expression, the bath of the row's one Langevin particle included.
+// It RESTATES that kernel's tile loop, and the counter layout of DrawStream::block (cavmd_draw_kernel.hpp): as one function for
+// both kernels, and with the blocks drawn through DrawStream, the captured step missed the timing bound against the parent
+// (profiles/shared_step_two/README.md), so tests/test_gpu_bath_batch.py still holds the two texts together byte for byte.
 // The variates never touch memory.  Philox, the division and the square root run on coupled lanes only.
 //
 // `draws` is read by every wave and written back by one thread of the same workgroup: every use of the value read lies in the
@@ -68,9 +72,6 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_bath_kernel(const Verle
 {
     constexpr int UNROLL = kBathUnroll;
     constexpr unsigned TILE = BLOCK * UNROLL;
-    constexpr int NW = BLOCK / kWave;
-    __shared__ double s_hi[NW], s_lo[NW];
-    __shared__ unsigned s_count[NW];
     const unsigned item = __builtin_amdgcn_readfirstlane(order[blockIdx.x]);
     const VerletRow* __restrict__ row = rows + item;
     const unsigned n = row->n;
@@ -186,6 +187,7 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_bath_kernel(const Verle
             else if (g[u] > 0.0) // NaN, 0, negative, beyond bath N: not coupled
             {
                 const double gj = g[u];
+                // the counter layout restates DrawStream::block (see above)
                 const uint4 w0 = draw_philox(make_uint4((unsigned)draws, (unsigned)(draws >> 32), j, kBathPurpose), key);
                 const uint4 w1 = draw_philox(make_uint4((unsigned)draws, (unsigned)(draws >> 32), j, kBathPurpose + 1u), key);
                 const double cj = sqrt(((6.0 * gj) * kT) / dt);
@@ -214,35 +216,15 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_bath_kernel(const Verle
     if (!gam) // (uniform over the workgroup)
         return;
 
-    // the item's tally: a shuffle tree over the wave (its total in lane 0), then the waves in wave order -- fixed by N alone
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1)
-    {
-        const double ohi = __shfl_down(t_hi, off, kWave), olo = __shfl_down(t_lo, off, kWave);
-        dd_merge(t_hi, t_lo, ohi, olo);
-        coupled += __shfl_down(coupled, off, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0)
-    {
-        s_hi[threadIdx.x / kWave] = t_hi;
-        s_lo[threadIdx.x / kWave] = t_lo;
-        s_count[threadIdx.x / kWave] = coupled;
-    }
-    __syncthreads(); // every wave's use of `draws` lies before this barrier, the store to it after
+    // the item's tally, in an order fixed by N alone; every wave's use of `draws` lies before the workgroup barrier inside
+    // block_tally, the store to it after
+    block_tally<BLOCK, 1, 1>(&t_hi, &t_lo, &coupled);
     if (threadIdx.x == 0)
     {
-        double hi = s_hi[0], lo = s_lo[0];
-        unsigned total = s_count[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w)
-        {
-            dd_merge(hi, lo, s_hi[w], s_lo[w]);
-            total += s_count[w];
-        }
-        const double T = hi + lo; // the one rounding of the sum
+        const double T = t_hi + t_lo; // the one rounding of the sum
         BathState* __restrict__ st = bath_state_all + item;
         st->draws = draws + 1;
-        st->coupled = total;
+        st->coupled = coupled;
         st->reservoir = st->reservoir - T * dt;
     }
 }

@@ -1,5 +1,6 @@
 // cavmd_reduce.hpp -- fixed-order compensated reductions on CDNA4: double-double (TwoSum) arithmetic, DPP cross-lane
-// movement, the per-lane accumulator of the dipole reduction and the block trees built from them.
+// movement, the per-lane accumulator of the dipole reduction and the block trees built from them; block_tally, the workgroup
+// sum of the bath's tally and of the start's momentum.
 // Part of the device code of libcavmd (see cavmd_kernels.hpp for the overview).
 #pragma once
 
@@ -357,6 +358,66 @@ __device__ __forceinline__ Accum block_reduce(Accum a)
         return block_reduce_256(a);
     else
         return block_reduce_generic<BLOCK>(a);
+}
+
+// ---- the workgroup tally ------------------------------------------------------------------------------------------
+// ND double-double sums and NC counts of per-thread values, in the order include/cavmd.h publishes for the bath's tally and the
+// start's momentum: a shuffle tree over the wave (off = 32 ... 1, the wave's total in lane 0), lane 0 of each wave to LDS, ONE
+// workgroup barrier, then thread 0 folds the waves 0, 1, ... in wave order.  The totals come back in thread 0's hi, lo and
+// count (other threads: unspecified).  Every thread of the workgroup calls it.
+template <int BLOCK, int ND, int NC>
+__device__ __forceinline__ void block_tally(double* hi, double* lo, unsigned* count)
+{
+    constexpr int NW = BLOCK / kWave;
+    __shared__ double s_hi[ND][NW], s_lo[ND][NW];
+    __shared__ unsigned s_count[NC][NW];
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+    {
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+        {
+            const double ohi = __shfl_down(hi[d], off, kWave), olo = __shfl_down(lo[d], off, kWave);
+            dd_merge(hi[d], lo[d], ohi, olo);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            count[c] += __shfl_down(count[c], off, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0)
+    {
+        const unsigned w = threadIdx.x / kWave;
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+        {
+            s_hi[d][w] = hi[d];
+            s_lo[d][w] = lo[d];
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            s_count[c][w] = count[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+        {
+            hi[d] = s_hi[d][0];
+            lo[d] = s_lo[d][0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w)
+                dd_merge(hi[d], lo[d], s_hi[d][w], s_lo[d][w]);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+        {
+            count[c] = s_count[c][0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w)
+                count[c] += s_count[c][w];
+        }
+    }
 }
 
 // ---- minimum image ------------------------------------------------------------------------------------------------

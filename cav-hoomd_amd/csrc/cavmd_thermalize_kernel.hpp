@@ -11,7 +11,8 @@
 //   members    for j of the list (or of the default set) with j < N and a finite mass m = vel.w > 0: v_c = sqrt(kT / m) * n_c;
 //              anything else is left as it is and counted
 //   momentum   P_c = the double-double sum of m * v_c in an order fixed by N and the list (lane-serial over the tiles of
-//              kThermalizeTile entries, a shuffle tree over the wave, the four waves in wave order), rounded once;
+//              kThermalizeTile entries, then block_tally of cavmd_reduce.hpp: a shuffle tree over the wave, the four waves in
+//              wave order), rounded once;
 //              v_c = v_c - (P_c / double(thermalised)) / m
 //   photon     v_c = sqrt(kT / m_p) * n_c;  x_c = finite_q ? ((-d_c) * g) / K : 0, x_z = 0;  x_c += sqrt(kT / K) * n_c if g != 0;
 //              i_c = floor((x_c + L_c / 2) / L_c);  pos_c = x_c - i_c * L_c;  image = i
@@ -94,6 +95,22 @@ __device__ __forceinline__ unsigned thermalize_entry(const unsigned* __restrict_
     return k;
 }
 
+// The velocity draw of particle j of mass m, for members and photon alike: sigma = sqrt(kT / m), three normals of purpose
+// 0xC0000000 + c, two stores (vel.w is never written).  Returns the three components.
+__device__ __forceinline__ double3 thermalize_velocity(DrawStream s, v2d* __restrict__ vel2, unsigned j, double kT, double m)
+{
+    s.item = j;
+    const double sigma = sqrt(kT / m);
+    double3 v;
+    v.x = sigma * s.normal(kThermalizePurposeVelocity);
+    v.y = sigma * s.normal(kThermalizePurposeVelocity + 1u);
+    v.z = sigma * s.normal(kThermalizePurposeVelocity + 2u);
+    const v2d vxy = {v.x, v.y};
+    vel2[2 * (size_t)j] = vxy;
+    reinterpret_cast<double*>(vel2)[4 * (size_t)j + 2] = v.z;
+    return v;
+}
+
 // blockIdx.x -> order[blockIdx.x] (items by N descending, sorted on the host) -> the row, fetched once per workgroup with scalar
 // loads.  States are indexed by ITEM, never by block.
 template <int BLOCK>
@@ -103,10 +120,7 @@ __global__ __launch_bounds__(BLOCK) void thermalize_batch_kernel(const Thermaliz
 {
     constexpr int UNROLL = kThermalizeUnroll;
     constexpr unsigned TILE = BLOCK * UNROLL;
-    constexpr int NW = BLOCK / kWave;
     static_assert(TILE == kThermalizeTile, "the tile the contract names");
-    __shared__ double s_hi[3][NW], s_lo[3][NW];
-    __shared__ unsigned s_done[NW], s_skip[NW];
     __shared__ double s_P[3];
     __shared__ unsigned s_total;
     const unsigned item = __builtin_amdgcn_readfirstlane(order[blockIdx.x]);
@@ -135,7 +149,7 @@ __global__ __launch_bounds__(BLOCK) void thermalize_batch_kernel(const Thermaliz
 
     // ---- pass one: the velocities, and this lane's share of the momentum (double-double) -----------------------------------
     double p_hi[3] = {0.0, 0.0, 0.0}, p_lo[3] = {0.0, 0.0, 0.0};
-    unsigned done = 0, skipped = 0;
+    unsigned counts[2] = {0, 0}; // thermalised, skipped
     for (unsigned t = 0; t < tiles; ++t)
     {
         unsigned j[UNROLL];
@@ -159,72 +173,31 @@ __global__ __launch_bounds__(BLOCK) void thermalize_batch_kernel(const Thermaliz
             const double m = write[u] ? vzw[u].y : 0.0;
             if (!write[u] || !thermalize_mass_ok(m))
             {
-                skipped += 1;
+                counts[1] += 1;
                 continue;
             }
-            DrawStream s = gen;
-            s.item = j[u];
-            const double sigma = sqrt(kT / m);
-            v2d vxy;
-            vxy.x = sigma * s.normal(kThermalizePurposeVelocity);
-            vxy.y = sigma * s.normal(kThermalizePurposeVelocity + 1u);
-            const double vz = sigma * s.normal(kThermalizePurposeVelocity + 2u);
-            vel2[2 * (size_t)j[u]] = vxy;
-            reinterpret_cast<double*>(vel2)[4 * (size_t)j[u] + 2] = vz; // vel.w is never written
+            const double3 v = thermalize_velocity(gen, vel2, j[u], kT, m);
             if (zero)
             {
-                dd_acc(p_hi[0], p_lo[0], m * vxy.x);
-                dd_acc(p_hi[1], p_lo[1], m * vxy.y);
-                dd_acc(p_hi[2], p_lo[2], m * vz);
+                dd_acc(p_hi[0], p_lo[0], m * v.x);
+                dd_acc(p_hi[1], p_lo[1], m * v.y);
+                dd_acc(p_hi[2], p_lo[2], m * v.z);
             }
-            done += 1;
+            counts[0] += 1;
         }
     }
 
-    // ---- the item's totals: a shuffle tree over the wave (its total in lane 0), then the waves in wave order -----------------
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1)
-    {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-        {
-            const double ohi = __shfl_down(p_hi[c], off, kWave), olo = __shfl_down(p_lo[c], off, kWave);
-            dd_merge(p_hi[c], p_lo[c], ohi, olo);
-        }
-        done += __shfl_down(done, off, kWave);
-        skipped += __shfl_down(skipped, off, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0)
-    {
-        const unsigned w = threadIdx.x / kWave;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-        {
-            s_hi[c][w] = p_hi[c];
-            s_lo[c][w] = p_lo[c];
-        }
-        s_done[w] = done;
-        s_skip[w] = skipped;
-    }
-    __syncthreads(); // every thread's use of `draws` lies before this barrier, the store to it after
+    // ---- the item's totals, in an order fixed by N and the list alone; every thread's use of `draws` lies before the barrier
+    // in block_tally, the store to it after -------------------------------------------------------------------------------------
+    block_tally<BLOCK, 3, 2>(p_hi, p_lo, counts);
     if (threadIdx.x == 0)
     {
-        unsigned total = s_done[0], skip = s_skip[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w)
-        {
-            total += s_done[w];
-            skip += s_skip[w];
-        }
+        const unsigned total = counts[0], skip = counts[1];
         double P[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
         {
-            double hi = s_hi[c][0], lo = s_lo[c][0];
-#pragma unroll
-            for (int w = 1; w < NW; ++w)
-                dd_merge(hi, lo, s_hi[c][w], s_lo[c][w]);
-            P[c] = (zero && total != 0) ? hi + lo : 0.0; // the one rounding of the sum
+            P[c] = (zero && total != 0) ? p_hi[c] + p_lo[c] : 0.0; // the one rounding of the sum
             s_P[c] = P[c];
         }
         s_total = total;
@@ -277,25 +250,17 @@ __global__ __launch_bounds__(BLOCK) void thermalize_batch_kernel(const Thermaliz
     // ---- the photon: its velocity (the driver's :729) and its placement (:464-494), one thread --------------------------------
     if (threadIdx.x != 0)
         return;
-    DrawStream s = gen;
-    s.item = (unsigned)photon;
     if (flags & kThermalizePhotonVelocity)
     {
         const double m = vel2[2 * (size_t)photon + 1].y;
         if (thermalize_mass_ok(m)) // no momentum term: the photon is not one of the members
-        {
-            const double sigma = sqrt(kT / m);
-            v2d vxy;
-            vxy.x = sigma * s.normal(kThermalizePurposeVelocity);
-            vxy.y = sigma * s.normal(kThermalizePurposeVelocity + 1u);
-            const double vz = sigma * s.normal(kThermalizePurposeVelocity + 2u);
-            vel2[2 * (size_t)photon] = vxy;
-            reinterpret_cast<double*>(vel2)[4 * (size_t)photon + 2] = vz;
-        }
+            thermalize_velocity(gen, vel2, (unsigned)photon, kT, m);
     }
     if (flags & kThermalizePlacePhoton)
     {
         const double g = row->couplstr, K = row->K;
+        DrawStream s = gen;
+        s.item = (unsigned)photon;
         double x[3] = {0.0, 0.0, 0.0};
         if (flags & kThermalizeFiniteQ)
         {

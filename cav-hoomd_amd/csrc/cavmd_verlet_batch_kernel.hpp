@@ -60,7 +60,9 @@ struct VerletState
 };
 static_assert(sizeof(VerletState) == 32, "one integrator state = 32 bytes");
 
-// sum over the workgroup of a per-thread count; the total is returned to thread 0 (other threads: unspecified)
+// sum over the workgroup of a per-thread count; the total is returned to thread 0 (other threads: unspecified).  It restates
+// block_tally of cavmd_reduce.hpp for no double and one count: as block_tally<BLOCK, 0, 1> it reordered 16 instruction lines
+// of verlet_step_one_kernel, which runs every step and was to keep its text (profiles/shared_step_two/README.md).
 template <int BLOCK>
 __device__ __forceinline__ unsigned verlet_block_count(unsigned c)
 {

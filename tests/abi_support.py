@@ -97,6 +97,15 @@ def good_ledger(capi, **kw):
     return capi.ledger_item(**args)
 
 
+def good_thermalize(capi, **kw):
+    args = dict(vel_ptr=0x10000, N=501, kT=9.5e-4, seed=0x9E3779B97F4A7C15, members_ptr=0x50004, n_members=500,
+                flags=capi.THERMALIZE_ZERO_MOMENTUM | capi.THERMALIZE_PLACE_PHOTON | capi.THERMALIZE_FINITE_Q
+                | capi.THERMALIZE_PHOTON_VELOCITY, pos_ptr=0x20000, image_ptr=0x30004, result_ptr=0x40008,
+                box_L=(40.0, 41.0, 42.0), params=capi.make_params(0.0091, 1e-3, 1.0))
+    args.update(kw)
+    return capi.thermalize_item(**args)
+
+
 def good_draw(capi, **kw):
     args = dict(verlet_row_ptr=0x10000, bussi_row_ptr=0x20008, gamma=0.01, kT=9.5e-4, set_T=9.5e-4, tau=100.0, dof=1293.0,
                 dt=5.0, records_ptr=0x30000, rows_ptr=0x40008, capacity=64, tolerance=1e-3, tolerance_initial=1e-4,

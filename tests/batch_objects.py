@@ -1,4 +1,4 @@
-"""The ten batch objects of include/cavmd.h, one table and one implementation of each check a machine WITHOUT a GPU can make
+"""The eleven batch objects of include/cavmd.h, one table and one implementation of each check a machine WITHOUT a GPU can make
 on all of them: the header declares and both libraries export each object's entry points and nothing stray, a C99 caller
 compiles, links and runs, the layouts agree between the C compiler, ctypes and numpy, null arguments are refused, the launch
 order is a stable descending sort, the Python class is exported and refuses CPU tensors, and a deferred destroy takes the
@@ -83,6 +83,13 @@ def _ledger_on_cpu(cavitymd):
             lambda: cavitymd.BatchEnergyLedger(None, [vel]),
             lambda: cavitymd.BatchEnergyLedger(None, [None], terms=[[vel]]),
             lambda: cavitymd.BatchEnergyLedger(None, [np.zeros((10, 4))])]
+
+
+def _thermalize_on_cpu(cavitymd):
+    vel = torch.zeros((10, 4), dtype=torch.float64)
+    return [lambda: cavitymd.BatchThermalizer([vel], 1.0, 3),
+            lambda: cavitymd.BatchThermalizer([vel], 1.0, 3, cavity=NoBatch(), place_photon=True),
+            lambda: cavitymd.BatchThermalizer([np.zeros((10, 4))], 1.0)]
 
 
 def _draw_on_cpu(cavitymd):
@@ -234,6 +241,21 @@ OBJECTS = [
          handle="Ledger", handle_methods=("record", "rows", "read", "reset", "set_items", "device_ptr", "close"),
          cls="BatchEnergyLedger", module="ledger", methods=("record", "rows", "read", "reset", "close"), properties=(),
          on_cpu=_ledger_on_cpu),
+    _row("thermalize",
+         entry_points=("item_check", "create", "destroy", "set_items", "run", "read", "reset", "state_device_ptr"),
+         kernels=(b"thermalize_batch_kernel",), no_device="no device: no workspace, hence no thermalize object",
+         structs={"item": ("ThermalizeItem", 160, dict(d_vel=0, d_members=8, d_pos=16, d_image=24, d_result=32, seed=40, kT=48,
+                                                       N=56, n_members=60, flags=64, reserved0=68, L=72, params=96, reserved=128)),
+                  "state": ("ThermalizeState", 64, dict(draws=0, thermalised=8, skipped=16, momentum=24, photon=48, reserved0=52,
+                                                        reserved=56))},
+         dtypes={"state": "thermalize_state_dtype"}, good=abi.good_thermalize, without_handle=("item_check",),
+         create=lambda capi, it: (1, byref(it)),
+         with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "run": (None,),
+                                       "read": (None, byref(capi.ThermalizeState())), "reset": (None,),
+                                       "state_device_ptr": (byref(vp()),)},
+         handle="Thermalize", handle_methods=("run", "read", "reset", "set_items", "state_device_ptr", "close"),
+         cls="BatchThermalizer", module="thermalize_batch", methods=("thermalize", "state", "reset", "close", "update"),
+         properties=("thermalizer",), on_cpu=_thermalize_on_cpu),
     _row("draw",
          entry_points=("item_check", "create", "destroy", "set_items", "fill", "read", "reset", "state_device_ptr"),
          kernels=(b"draw_fill_kernel",), no_device="no device: no workspace, hence no draw object",

@@ -11,27 +11,16 @@ import math
 import numpy as np
 
 import draw_mirror
+from draw_mirror import KEY_STRIDE, item_key  # noqa: F401  (the bath's callers take both from here)
 from verlet_mirror import mirror_net_force
 
 PURPOSE = 0x80000000
-KEY_STRIDE = 0x9E3779B97F4A7C15
-_MASK = np.uint64(0xFFFFFFFF)
-_U32 = np.uint64(32)
-
-
-def item_key(seed: int, i: int) -> int:
-    """the key LangevinBathBatch gives system i"""
-    return (int(seed) + KEY_STRIDE * (int(i) + 1)) % 2 ** 64
 
 
 def block(seed, draws, j, b):
     """The four words of counter (draws low, draws high, j, 0x80000000 + b) under the key (seed low, seed high); j an array."""
     j = np.asarray(j, dtype=np.uint64)
-    draws = np.uint64(draws)
-    counter = np.stack([np.full(j.shape, draws & _MASK), np.full(j.shape, draws >> _U32), j,
-                        np.full(j.shape, np.uint64(PURPOSE + b))], axis=-1)
-    seed = np.uint64(seed)
-    return draw_mirror.philox(counter, np.array([seed & _MASK, seed >> _U32], dtype=np.uint64))
+    return draw_mirror.block(seed, np.full(j.shape, draws, dtype=np.uint64), j, np.full(j.shape, PURPOSE + b, dtype=np.uint64))
 
 
 def variates(seed, draws, j):

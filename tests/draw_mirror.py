@@ -43,6 +43,12 @@ PURPOSE_LANGEVIN_XY, PURPOSE_LANGEVIN_Z, PURPOSE_NORMAL, PURPOSE_BOOST, PURPOSE_
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)
 _U32 = np.uint64(32)
+KEY_STRIDE = 0x9E3779B97F4A7C15
+
+
+def item_key(seed: int, i: int) -> int:
+    """the key LangevinBathBatch and BatchThermalizer give system i (_capi.bath_item_key)"""
+    return (int(seed) + KEY_STRIDE * (int(i) + 1)) % 2 ** 64
 
 
 def philox(counter, key):

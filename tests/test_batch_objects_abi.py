@@ -1,4 +1,4 @@
-"""Every no-GPU check of tests/batch_objects.py on every row of its table: the ten batch objects of include/cavmd.h by the
+"""Every no-GPU check of tests/batch_objects.py on every row of its table: the eleven batch objects of include/cavmd.h by the
 checks a to i.  What is specific to one object (refusal matrices, row makers, mirrors, header prose) is in its own
 tests/test_*_abi.py."""
 import pytest
@@ -11,12 +11,13 @@ from batch_objects import OBJECTS
 per_object = pytest.mark.parametrize("obj", OBJECTS, ids=[obj.name for obj in OBJECTS])
 
 
-def test_the_table_has_the_ten_objects(capi):
-    names = ["batch", "bussi_batch", "recorder", "field_recorder", "verlet", "bath", "ledger", "draw", "molecular", "coulomb"]
+def test_the_table_has_the_eleven_objects(capi):
+    names = ["batch", "bussi_batch", "recorder", "field_recorder", "verlet", "bath", "ledger", "thermalize", "draw", "molecular",
+             "coulomb"]
     assert [obj.name for obj in OBJECTS] == names
-    assert [len(obj.entry_points) for obj in OBJECTS] == [10, 10, 9, 10, 11, 8, 9, 8, 8, 9]
+    assert [len(obj.entry_points) for obj in OBJECTS] == [10, 10, 9, 10, 11, 8, 9, 8, 8, 8, 9]
     handles = {getattr(capi, obj.handle) for obj in OBJECTS}
-    assert len(handles) == 10 and all(issubclass(h, capi._ItemTableHandle) for h in handles)
+    assert len(handles) == 11 and all(issubclass(h, capi._ItemTableHandle) for h in handles)
     # the header's order, as _capi._PROTOTYPES has it
     first = [list(capi._PROTOTYPES).index(obj.prefix + "_create") for obj in OBJECTS]
     assert first == sorted(first), first

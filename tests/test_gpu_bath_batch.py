@@ -109,10 +109,10 @@ def _assert_bath_state(got, before, b, result, dt, where):
 
 
 # ---- 1. one ragged batch ------------------------------------------------------------------------------------------------------
-SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1025)
+SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1025, 257)
 PATTERNS = ("null", "all", "none", "every_third", "last", "short", "null", "negative_and_nan", "row_wins", "row_gamma_zero", "all",
-            "every_third")
-WANT_COUPLED = (0, 1, 0, 22, 1, 100, 0, 255, 510, 512, 513, 342)
+            "every_third", "long")
+WANT_COUPLED = (0, 1, 0, 22, 1, 100, 0, 255, 510, 512, 513, 342, 257)
 
 
 def _gamma_pattern(pattern, n, rng):
@@ -127,6 +127,8 @@ def _gamma_pattern(pattern, n, rng):
         g[:-1] = 0.0
     elif pattern == "short":
         g = g[:100]                                                          # bath N shorter than the system's: the tail is uncoupled
+    elif pattern == "long":
+        g = np.concatenate([g, rng.uniform(0.05, 0.4, 40)])                  # bath N longer than the system's: the excess is idle
     elif pattern == "negative_and_nan":
         g[3], g[n - 2] = -0.25, np.nan
     return g
@@ -136,7 +138,7 @@ def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
     rng = np.random.default_rng(20241019)
     B = len(SIZES)
     assert len(PATTERNS) == B == len(WANT_COUPLED) and set(PATTERNS) == {"null", "all", "none", "every_third", "last", "short",
-                                                                        "negative_and_nan", "row_wins", "row_gamma_zero"}
+                                                                        "long", "negative_and_nan", "row_wins", "row_gamma_zero"}
     systems, baths = [], []
     for k, (n, pattern) in enumerate(zip(SIZES, PATTERNS)):
         langevin = n // 2 if pattern in ("row_wins", "row_gamma_zero") else -1

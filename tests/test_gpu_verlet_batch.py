@@ -33,7 +33,7 @@ def _rows_array(rows) -> np.ndarray:
 
 
 # ---- 1. one ragged batch --------------------------------------------------------------------------------------------------------
-SIZES = (0, 1, 255, 256, 257, 501, 1024, 1025, 2049)
+SIZES = (0, 1, 255, 256, 257, 501, 1024, 1025, 2049, 511, 512, 513)     # step two's tile is 512 particles
 EDGES = ("at_hi", "at_lo", "above_hi", "below_lo", "far_outside")
 
 
@@ -106,7 +106,7 @@ def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
     SKIPPED = SIZES.index(257)
     dts = [(0.5, 0.25, 0.125)[k % 3] for k in range(len(SIZES))]
     systems = [_ragged_system(k, n, rng, dts[k]) for k, n in enumerate(SIZES)]
-    assert sorted(len(s["forces"]) for s in systems if s["N"]) == [1, 1, 2, 2, 2, 4, 4, 4]
+    assert sorted(len(s["forces"]) for s in systems if s["N"]) == [1, 1, 1, 2, 2, 2, 2, 4, 4, 4, 4]
     dev = [_to_device(s) for s in systems]
     ws = _capi.Workspace(1)
     batch = _capi.Verlet(ws, [_item(s, d) for s, d in zip(systems, dev)])
@@ -167,8 +167,8 @@ def test_one_ragged_batch_equals_the_mirror_bit_for_bit():
     for k, s in enumerate(systems):
         if s["N"] >= 5 and k != SKIPPED:
             assert s["out_of_box"] >= 3 and s["steps"] == 2, k                # the far particle of each axis: counted, not repaired
-    assert [s["langevin"] for s in systems] == [-1, 0, -1, 0, 256, -1, 0, 1024, -1]          # first, last, none
-    assert [k for k, s in enumerate(systems) if s["reservoir"] != 0.0] == [1, 3, 7]         # 4 is skipped, 6 has gamma == 0
+    assert [s["langevin"] for s in systems] == [-1, 0, -1, 0, 256, -1, 0, 1024, -1, 0, 511, -1]  # first, last, none
+    assert [k for k, s in enumerate(systems) if s["reservoir"] != 0.0] == [1, 3, 7, 9, 10]  # 4 is skipped, 6 has gamma == 0
     # the skipped item and the empty item: byte-identical to what they were after `accelerations`
     for k in (SKIPPED, 0):
         assert _device_bytes(dev[k]) == primed[k], k

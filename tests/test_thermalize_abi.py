@@ -1,6 +1,6 @@
-"""The thermalize object (cavmd_thermalize_*, cavitymd.BatchThermalizer) on a machine WITHOUT a GPU.  tests/batch_objects.py pins
-the table of the ten objects before it; this module defines the eleventh row itself and runs the same checks a to i on it, then
-what is specific to the object: the header's prose, every refusal of its item check, the mirror's counters
+"""What is specific to the thermalize object (cavmd_thermalize_*, cavitymd.BatchThermalizer) on a machine WITHOUT a GPU
+(tests/test_batch_objects_abi.py runs the shared checks a to i on its row of tests/batch_objects.py; none is skipped): the
+header's prose, the split variants' exports, the tile constant, every refusal of its item check, the mirror's counters
 (tests/thermalize_mirror.py) against the known answers of Philox in the header, the mirror's photon expressions against the
 driver's own numpy lines bit for bit, and the inputs of tests/test_gpu_thermalize_batch.py (tests/thermalize_cases.py) run
 through the mirror alone: inside the statistical bands, and without one ambiguous wrap."""
@@ -15,44 +15,15 @@ import draw_mirror
 import thermalize_cases as cases
 import thermalize_mirror as mirror
 from abi_support import HEADER, exported
+from abi_support import good_thermalize as _good
 
 byref, vp = ctypes.byref, ctypes.c_void_p
 
 
-def _good(capi, **kw):
-    args = dict(vel_ptr=0x10000, N=501, kT=9.5e-4, seed=0x9E3779B97F4A7C15, members_ptr=0x50004, n_members=500,
-                flags=capi.THERMALIZE_ZERO_MOMENTUM | capi.THERMALIZE_PLACE_PHOTON | capi.THERMALIZE_FINITE_Q
-                | capi.THERMALIZE_PHOTON_VELOCITY, pos_ptr=0x20000, image_ptr=0x30004, result_ptr=0x40008,
-                box_L=(40.0, 41.0, 42.0), params=capi.make_params(0.0091, 1e-3, 1.0))
-    args.update(kw)
-    return capi.thermalize_item(**args)
+ROW = checks.ROWS["thermalize"]
 
 
-def _on_cpu(cavitymd):
-    vel = torch.zeros((10, 4), dtype=torch.float64)
-    return [lambda: cavitymd.BatchThermalizer([vel], 1.0, 3),
-            lambda: cavitymd.BatchThermalizer([vel], 1.0, 3, cavity=checks.NoBatch(), place_photon=True),
-            lambda: cavitymd.BatchThermalizer([np.zeros((10, 4))], 1.0)]
-
-
-ROW = checks._row(
-    "thermalize",
-    entry_points=("item_check", "create", "destroy", "set_items", "run", "read", "reset", "state_device_ptr"),
-    kernels=(b"thermalize_batch_kernel",), no_device="no device: no workspace, hence no thermalize object",
-    structs={"item": ("ThermalizeItem", 160, dict(d_vel=0, d_members=8, d_pos=16, d_image=24, d_result=32, seed=40, kT=48, N=56,
-                                                  n_members=60, flags=64, reserved0=68, L=72, params=96, reserved=128)),
-             "state": ("ThermalizeState", 64, dict(draws=0, thermalised=8, skipped=16, momentum=24, photon=48, reserved0=52,
-                                                   reserved=56))},
-    dtypes={"state": "thermalize_state_dtype"}, good=_good, without_handle=("item_check",),
-    create=lambda capi, it: (1, byref(it)),
-    with_handle=lambda capi, it: {"set_items": (0, 1, byref(it)), "run": (None,), "read": (None, byref(capi.ThermalizeState())),
-                                  "reset": (None,), "state_device_ptr": (byref(vp()),)},
-    handle="Thermalize", handle_methods=("run", "read", "reset", "set_items", "state_device_ptr", "close"),
-    cls="BatchThermalizer", module="thermalize_batch", methods=("thermalize", "state", "reset", "close", "update"),
-    properties=("thermalizer",), on_cpu=_on_cpu)
-
-
-# ---- the checks every batch object gets (tests/batch_objects.py a to i), on this module's own row --------------------------------
+# ---- what this object adds to the checks every batch object gets (tests/batch_objects.py a to i) ------------------------------
 def test_header_declares_the_eight_entry_points_and_the_contract():
     checks.header_declares_exactly_the_entry_points(ROW)
     text = open(HEADER).read()
@@ -64,7 +35,8 @@ def test_header_declares_the_eight_entry_points_and_the_contract():
     assert "parity with it is pinned by nothing" in " ".join(text.replace("*", " ").split())
     # the new prefix is no prefix of another object's, nor another's of it
     for obj in checks.OBJECTS:
-        assert not (obj.prefix + "_").startswith(ROW.prefix + "_") and not (ROW.prefix + "_").startswith(obj.prefix + "_"), obj.prefix
+        assert obj is ROW or not ((obj.prefix + "_").startswith(ROW.prefix + "_") or (ROW.prefix + "_").startswith(obj.prefix + "_")), \
+            obj.prefix
 
 
 def test_libraries_export_the_entry_points_and_nothing_stray(capi):
@@ -75,7 +47,7 @@ def test_libraries_export_the_entry_points_and_nothing_stray(capi):
 
 
 def test_the_version_is_still_2(capi):
-    checks.the_version_is_still_2(capi)
+    checks.the_version_is_still_2(capi)                                    # not a check on a row: it stays with each object
 
 
 def test_c99_caller_runs_and_its_layouts_equal_ctypes_and_numpy(capi, tmp_path):
@@ -109,10 +81,6 @@ def test_python_class_is_exported_and_refuses_cpu_tensors(capi):
     assert order == sorted(order)                        # the order of a start
     assert "0x9E3779B97F4A7C15" in doc and "not HOOMD's RandomGenerator" in doc and "pinned by nothing" in doc
     assert [capi.bath_item_key(5, i) for i in range(4)] == [mirror.item_key(5, i) for i in range(4)]
-
-
-def test_deferred_destroy_takes_the_object_before_its_workspace(capi, monkeypatch):
-    checks.deferred_destroy_takes_the_object_before_its_workspace(ROW, capi, monkeypatch)
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------

@@ -25,19 +25,13 @@ import math
 import numpy as np
 
 import draw_mirror
-from draw_mirror import EPS, NORMAL_REL
+from draw_mirror import EPS, NORMAL_REL, item_key  # noqa: F401  (the thermalizer's callers take item_key from here)
 
 PURPOSE_VELOCITY = 0xC0000000
 PURPOSE_POSITION = 0xC0000008
 TILE = 512                          # CAVMD_THERMALIZE_TILE: entries of a member set per tile of the kernel
-KEY_STRIDE = 0x9E3779B97F4A7C15
 WRAP_MARGIN = 1e-9
 VELOCITY_REL = NORMAL_REL + EPS
-
-
-def item_key(seed: int, i: int) -> int:
-    """the key BatchThermalizer gives system i (the bath's rule)"""
-    return (int(seed) + KEY_STRIDE * (int(i) + 1)) % 2 ** 64
 
 
 def new_state():
