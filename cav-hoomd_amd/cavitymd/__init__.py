@@ -20,13 +20,14 @@ from .step_draw import StepDraw
 from .bath_batch import LangevinBathBatch
 from .thermalize_batch import BatchThermalizer
 from .ledger import BatchEnergyLedger
+from .trajectory import BatchTrajectoryRecorder
 from .molecular_batch import MolecularForceBatch
 from .coulomb_batch import CoulombForceBatch
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, bath_batch, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats
+from . import _capi, bath_batch, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats, trajectory
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "bath_batch", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "BatchTrajectoryRecorder", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "bath_batch", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats", "trajectory",
 ]
 __version__ = "0.1.0"

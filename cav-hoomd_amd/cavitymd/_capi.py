@@ -237,6 +237,29 @@ class CoulombItem(ctypes.Structure):
                 ("n_exclusions", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
 
 
+class TrajectoryItem(ctypes.Structure):
+    """cavmd_trajectory_item (64 bytes): one system of a trajectory object; the four pointers are DEVICE pointers."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_image", ctypes.c_void_p), ("d_vel", ctypes.c_void_p), ("d_time", ctypes.c_void_p),
+                ("Lx", ctypes.c_double), ("Ly", ctypes.c_double), ("Lz", ctypes.c_double), ("N", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32)]
+
+
+class TrajectoryHeader(ctypes.Structure):
+    """cavmd_trajectory_header (64 bytes): the start of every frame of a trajectory object's ring."""
+    _fields_ = [("call", ctypes.c_uint64), ("row", ctypes.c_uint64), ("time", ctypes.c_double), ("N", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("box", ctypes.c_double * 3), ("reserved", ctypes.c_uint64)]
+
+
+class TrajectoryLayout(ctypes.Structure):
+    """struct cavmd_trajectory_layout (48 bytes): where the sections of a frame of up to max_N particles lie."""
+    _fields_ = [("frame_bytes", ctypes.c_uint64), ("position_offset", ctypes.c_uint64), ("velocity_offset", ctypes.c_uint64),
+                ("image_offset", ctypes.c_uint64), ("max_N", ctypes.c_uint32), ("format", ctypes.c_uint32),
+                ("element_bytes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+TRAJECTORY_F64, TRAJECTORY_F32 = 0, 1
+TRAJECTORY_MAX_BYTES = 2 ** 32
+TRAJECTORY_FORCED, TRAJECTORY_HAS_VELOCITIES = 1, 2     # cavmd_trajectory_header.flags
 COULOMB_MAX_ITEM_N = 2048
 COULOMB_MAX_K = 4096
 COULOMB_MAX_EXCLUSIONS = 4
@@ -389,6 +412,15 @@ def coulomb_item(N, pos_ptr, charge_ptr, force_ptr, box_L, kappa, r_cut, k_cut, 
     return it
 
 
+def trajectory_item(pos_ptr=0, image_ptr=0, vel_ptr=0, time_ptr=0, box_L=(0.0, 0.0, 0.0), N=0) -> "TrajectoryItem":
+    """vel_ptr == 0: the velocity section of every frame is +0; time_ptr == 0: time is 0."""
+    it = TrajectoryItem()
+    it.d_pos, it.d_image, it.d_vel, it.d_time = pos_ptr or None, image_ptr or None, vel_ptr or None, time_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.N = int(N)
+    return it
+
+
 _vp, _sz, _dbl, _ci, _cstr = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_char_p
 _u32, _u64, _P = ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER
 
@@ -520,6 +552,16 @@ _PROTOTYPES = {
     "cavmd_coulomb_set_items": (_ci, [_vp, _sz, _sz, _P(CoulombItem)]),
     "cavmd_coulomb_compute": (_ci, [_vp, _vp]),
     "cavmd_coulomb_structure_device_ptr": (_ci, [_vp, _P(_vp), _P(_P(_u32))]),
+    "cavmd_trajectory_item_check": (_ci, [_P(TrajectoryItem)]),
+    "cavmd_trajectory_layout": (_ci, [_u32, _u32, _P(TrajectoryLayout)]),
+    "cavmd_trajectory_create": (_ci, [_vp, _sz, _P(TrajectoryItem), _u32, _u32, _sz, _u64, _dbl, _P(_vp)]),
+    "cavmd_trajectory_destroy": (_ci, [_vp]),
+    "cavmd_trajectory_set_items": (_ci, [_vp, _sz, _sz, _P(TrajectoryItem)]),
+    "cavmd_trajectory_record": (_ci, [_vp, _vp, _vp]),
+    "cavmd_trajectory_rows": (_ci, [_vp, _vp, _vp]),
+    "cavmd_trajectory_read": (_ci, [_vp, _vp, _sz, _sz, _u64, _sz, _vp]),
+    "cavmd_trajectory_reset": (_ci, [_vp, _vp]),
+    "cavmd_trajectory_device_ptr": (_ci, [_vp, _P(_vp), _P(_vp)]),
     "cavmd_profile_enable": (_ci, [_vp, _ci]),
     "cavmd_profile_read": (_ci, [_vp, _P(_dbl * 3), _P(_u64)]),
     "cavmd_profile_samples": (_ci, [_vp, _vp, _sz, _P(_sz)]),
@@ -857,8 +899,8 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What the eleven batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Thermalize, Ledger, Draw,
-    Molecular and Coulomb): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
+    """What the twelve batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Thermalize, Ledger, Draw,
+    Molecular, Coulomb and Trajectory): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
     only.  A subclass names its item structure, its ``cavmd_*`` prefix and the size the library sorts its launch order by.
     Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -998,6 +1040,7 @@ thermalize_item_check = _item_check("cavmd_thermalize", "thermalize")
 ledger_item_check = _item_check("cavmd_ledger", "ledger")
 draw_item_check = _item_check("cavmd_draw", "draw")
 coulomb_item_check = _item_check("cavmd_coulomb", "coulomb")
+trajectory_item_check = _item_check("cavmd_trajectory", "trajectory")
 
 record_dtype = _dtype_of(Record)
 field_record_dtype = _dtype_of(FieldRecord)
@@ -1006,6 +1049,7 @@ bath_state_dtype = _dtype_of(BathState)
 thermalize_state_dtype = _dtype_of(ThermalizeState)
 ledger_row_dtype = _dtype_of(LedgerRow)
 draw_state_dtype = _dtype_of(DrawState)
+trajectory_header_dtype = _dtype_of(TrajectoryHeader)
 
 
 class Batch(_ItemTableHandle):
@@ -1370,3 +1414,50 @@ class Coulomb(_ItemTableHandle):
         check(self._lib.cavmd_coulomb_structure_device_ptr(self._h, ctypes.byref(p), ctypes.byref(off)),
               "cavmd_coulomb_structure_device_ptr")
         return int(p.value), [int(off[i]) for i in range(self.n_items)]
+
+
+def trajectory_layout(max_N: int, format: int) -> TrajectoryLayout:
+    """Where the sections of a frame of up to max_N particles lie (host arithmetic); raises CavmdError where the library
+    refuses."""
+    out = TrajectoryLayout()
+    check(load().cavmd_trajectory_layout(int(max_N), int(format), ctypes.byref(out)), "cavmd_trajectory_layout")
+    return out
+
+
+def trajectory_frame_dtype(layout: TrajectoryLayout):
+    """numpy structured dtype of one frame: the header's columns at their offsets, then ``position`` and ``velocity`` as
+    (max_N, 3) float64 or float32 and ``image`` as (max_N, 3) int32 at the layout's offsets, itemsize frame_bytes."""
+    import numpy as np
+    head = np.dtype(TrajectoryHeader)
+    names, formats, offsets = list(head.names), [head.fields[n][0] for n in head.names], [head.fields[n][1] for n in head.names]
+    element = np.dtype("<f8") if layout.format == TRAJECTORY_F64 else np.dtype("<f4")
+    for name, fmt, off in (("position", element, layout.position_offset), ("velocity", element, layout.velocity_offset),
+                           ("image", np.dtype("<i4"), layout.image_offset)):
+        names.append(name)
+        formats.append(np.dtype((fmt, (int(layout.max_N), 3))))
+        offsets.append(int(off))
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": int(layout.frame_bytes)})
+
+
+class Trajectory(_SeriesHandle):
+    """Owns one cavmd_trajectory: frames of the positions, velocities and images of B independent small systems appended, by
+    ONE kernel launch per call, to a ring in device memory; whether a call writes a frame is decided on the device (a graph
+    replay records when a frame is due).  Launched by N descending."""
+    _ITEM, _PREFIX, _RECORD = TrajectoryItem, "cavmd_trajectory", None
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items, max_N: int, format: int, capacity: int, period: int = 1,
+                 time_interval: float = 0.0):
+        self.capacity, self.period, self.time_interval = int(capacity), int(period), float(time_interval)
+        self.max_N, self.format = int(max_N), int(format)
+        if self.capacity < 0 or self.period < 0 or not 0 <= self.max_N < 2**32 or not 0 <= self.format < 2**32:
+            raise CavmdError(CAVMD_ERR_INVALID_VALUE, error_string(CAVMD_ERR_INVALID_VALUE), "cavmd_trajectory_create")
+        self._create(workspace, items, self.max_N, self.format, self.capacity, self.period, self.time_interval)
+        self.layout = trajectory_layout(self.max_N, self.format)
+        self._RECORD = trajectory_frame_dtype(self.layout)   # what _SeriesHandle.read allocates: whole frames
+
+    def record(self, stream: int = 0, take_frame_ptr: int = 0) -> None:
+        """One kernel: every item's call counter moves; an item whose frame is due (or whose take word is set) appends one.
+        take_frame_ptr: 0 or the device address of n_items uint32 words read when the kernel runs."""
+        check(self._lib.cavmd_trajectory_record(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(take_frame_ptr)),
+              "cavmd_trajectory_record")

@@ -1,12 +1,12 @@
-// Host-only: what the eleven "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
-// cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder and the ledger, which has its shape), cavmd_field_recorder.hip,
-// cavmd_verlet.hip (the integrator, the draw object that writes its input rows, the bath that supplies its second
-// half-step and the thermalize object that starts a run), cavmd_molecular.hip and cavmd_coulomb.hip.
+// Host-only: what the twelve "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
+// cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder, the ledger, which has its shape, and the trajectory),
+// cavmd_field_recorder.hip, cavmd_verlet.hip (the integrator, the draw object that writes its input rows, the bath that
+// supplies its second half-step and the thermalize object that starts a run), cavmd_molecular.hip and cavmd_coulomb.hip.
 // ItemTable is how a table of items lives on the host and on the device; create_table makes an object and ties it to its
 // parent, ItemTable::launch launches it and destroy_table releases it.  Three flavours state what more an object keeps:
-// SeriesTable, a ring of records per item (the two recorders and the ledger); StateTable, one state per item (the
-// integrator, the draw object, the bath and the thermalize object); LinkedTable, tables derived from the items that the kernels find through a
-// header at a fixed device address and that set_items replaces together (the two force batches).
+// SeriesTable, a ring of records per item (the two recorders, the ledger and the trajectory); StateTable, one state per
+// item (the integrator, the draw object, the bath and the thermalize object); LinkedTable, tables derived from the items that
+// the kernels find through a header at a fixed device address and that set_items replaces together (the two force batches).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once
 
@@ -312,12 +312,15 @@ int create_table(WorkspaceTie* tie, size_t n_items, const Item* h_items, Table**
 }
 
 // An item table whose launches append Records to a time series in device memory: per item a ring of `capacity` records and
-// `n_counters` words, the words kept as n_counters arrays of n with the rows-written array first.
+// `n_counters` words, the words kept as n_counters arrays of n with the rows-written array first.  A record is `record_bytes`
+// long: sizeof(Record), or for an object whose record size is a run-time value (the trajectory's frames, Record = unsigned
+// char) what the object sets before alloc_series.
 template <class Item, class Row, class Record>
 struct SeriesTable : ItemTable<Item, Row>
 {
     const unsigned n_counters;
     size_t capacity = 0;
+    size_t record_bytes = sizeof(Record);    // a multiple of sizeof(Record)
     cavmd::DeviceArray<Record> d_series;     // n x capacity records, item-major
     cavmd::DeviceArray<uint64_t> d_counters; // n_counters arrays of n words
 
@@ -329,7 +332,7 @@ struct SeriesTable : ItemTable<Item, Row>
     // allocates and zeroes the series, then the counters
     hipError_t alloc_series()
     {
-        const hipError_t e = d_series.alloc_zeroed(this->n * capacity);
+        const hipError_t e = d_series.alloc_zeroed(this->n * capacity * (record_bytes / sizeof(Record)));
         return e == hipSuccess ? d_counters.alloc_zeroed((size_t)n_counters * this->n) : e;
     }
 
@@ -364,13 +367,14 @@ struct SeriesTable : ItemTable<Item, Row>
         }
         // row j of an item sits in slot j % capacity of that item's stretch: at most two runs of slots, each fetched for all
         // the items with one strided copy
-        const size_t rec = sizeof(Record);
+        const size_t rec = record_bytes;
         const size_t slot0 = (size_t)(first_row % capacity);
         const size_t run0 = std::min(n_rows, capacity - slot0);
-        const Record* src = d_series.ptr + first_item * capacity;
-        CAVMD_HIP_TRY(hipMemcpy2D(out, n_rows * rec, src + slot0, capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
+        const char* src = reinterpret_cast<const char*>(d_series.ptr) + first_item * capacity * rec;
+        char* dst = reinterpret_cast<char*>(out);
+        CAVMD_HIP_TRY(hipMemcpy2D(dst, n_rows * rec, src + slot0 * rec, capacity * rec, run0 * rec, n_items, hipMemcpyDeviceToHost));
         if (run0 < n_rows)
-            CAVMD_HIP_TRY(hipMemcpy2D(out + run0, n_rows * rec, src, capacity * rec, (n_rows - run0) * rec, n_items,
+            CAVMD_HIP_TRY(hipMemcpy2D(dst + run0 * rec, n_rows * rec, src, capacity * rec, (n_rows - run0) * rec, n_items,
                                       hipMemcpyDeviceToHost));
         return CAVMD_OK;
     }

@@ -1,7 +1,8 @@
 // cavmd_recorder.hip -- cavmd_recorder of include/cavmd.h: per-step observables of a batch appended to a series in device memory;
-// and cavmd_ledger, the energy ledger, which has the recorder's shape and calls its kinetic-energy code (two objects in one
-// unit, as cavmd_verlet.hip holds three).  Two of the eleven objects built on an item table (cavmd_item_table.hpp), each a
-// SeriesTable; what the two share beyond that is PeriodicSeries, below.  The workspace is an incomplete type here.
+// cavmd_ledger, the energy ledger, which has the recorder's shape and calls its kinetic-energy code; and cavmd_trajectory, whose
+// records are frames of positions, velocities and images (three objects in one unit, as cavmd_verlet.hip holds four).  Three of
+// the twelve objects built on an item table (cavmd_item_table.hpp), each a SeriesTable; what the first two share beyond that is
+// PeriodicSeries, below.  The workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -13,6 +14,7 @@
 #include "cavmd.h"
 #include "cavmd_recorder_kernel.hpp"
 #include "cavmd_ledger_kernel.hpp"
+#include "cavmd_trajectory_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -241,6 +243,195 @@ int cavmd_ledger_reset(cavmd_ledger* l, void* stream_)
 int cavmd_ledger_device_ptr(cavmd_ledger* l, const cavmd_ledger_row** series, const uint64_t** rows)
 {
     return l ? l->device_ptr(series, rows) : CAVMD_ERR_INVALID_VALUE;
+}
+
+} // extern "C"
+
+// ---- trajectory frames of a batch: positions, velocities and images per due call (cavmd_trajectory_kernel.hpp) ----------------
+struct cavmd_trajectory : SeriesTable<cavmd_trajectory_item, TrajectoryRow, unsigned char> // a record is a frame of layout.frame_bytes
+{
+    using Base = SeriesTable<cavmd_trajectory_item, TrajectoryRow, unsigned char>;
+    struct cavmd_trajectory_layout layout = {};
+    uint64_t period = 1;
+    double time_interval = 0.0;
+
+    cavmd_trajectory()
+        : Base(kTrajCounters, cavmd_trajectory_item_check, [](const cavmd_trajectory_item& it) { return (unsigned)it.N; },
+               uploaded_as_it_is<cavmd_trajectory_item, TrajectoryRow>)
+    {
+    }
+
+    // what the object asks of an item beyond cavmd_trajectory_item_check
+    int check_own(const cavmd_trajectory_item* h_items, size_t count) const
+    {
+        const int st = check_items(h_items, count, check);
+        if (st != CAVMD_OK)
+            return st;
+        for (size_t i = 0; i < count; ++i)
+            if (h_items[i].N > layout.max_N)
+                return CAVMD_ERR_CAPACITY;
+        for (size_t i = 0; i < count; ++i)
+            if (time_interval > 0.0 && !h_items[i].d_time)
+                return CAVMD_ERR_INVALID_VALUE;
+        return CAVMD_OK;
+    }
+
+    // create_table's hooks
+    int check_new(const cavmd_trajectory_item* h_items, size_t n_items)
+    {
+        return check_own(h_items, n_items);
+    }
+    int capacity_status(size_t n_items) const
+    {
+        return capacity > CAVMD_TRAJECTORY_MAX_BYTES / layout.frame_bytes / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+    hipError_t alloc_own()
+    {
+        record_bytes = (size_t)layout.frame_bytes;
+        return alloc_series();
+    }
+
+    // (hides ItemTable's: an item is also held against the object's max_N and rule)
+    int set_items(size_t first, size_t count, const cavmd_trajectory_item* h_items)
+    {
+        if (!within(first, count, h_items))
+            return CAVMD_ERR_INVALID_VALUE;
+        const int st = check_own(h_items, count);
+        return st == CAVMD_OK ? Base::set_items(first, count, h_items) : st;
+    }
+
+    template <class Kernel>
+    int record(void* stream, Kernel kernel, const uint32_t* d_take_frame)
+    {
+        const TrajectoryFrame frame {layout.frame_bytes, layout.velocity_offset, layout.image_offset};
+        return launch((hipStream_t)stream, kernel, dim3((unsigned)n), dim3(256), 0, d_rows.ptr, d_order.ptr, (unsigned)n,
+                      (uint64_t)capacity, period, time_interval, frame, d_take_frame, d_series.ptr, d_counters.ptr);
+    }
+};
+
+namespace
+{
+static_assert(sizeof(cavmd_trajectory_item) == sizeof(TrajectoryRow), "the item table is uploaded as it is");
+static_assert(offsetof(cavmd_trajectory_item, d_pos) == offsetof(TrajectoryRow, pos2)
+                  && offsetof(cavmd_trajectory_item, d_image) == offsetof(TrajectoryRow, image)
+                  && offsetof(cavmd_trajectory_item, d_vel) == offsetof(TrajectoryRow, vel2)
+                  && offsetof(cavmd_trajectory_item, d_time) == offsetof(TrajectoryRow, time)
+                  && offsetof(cavmd_trajectory_item, Lx) == offsetof(TrajectoryRow, L)
+                  && offsetof(cavmd_trajectory_item, N) == offsetof(TrajectoryRow, N),
+              "trajectory item layout");
+static_assert(sizeof(cavmd_trajectory_header) == sizeof(TrajectoryHeader) && sizeof(cavmd_trajectory_header) == kTrajHeaderBytes
+                  && offsetof(cavmd_trajectory_header, call) == offsetof(TrajectoryHeader, call)
+                  && offsetof(cavmd_trajectory_header, row) == offsetof(TrajectoryHeader, row)
+                  && offsetof(cavmd_trajectory_header, time) == offsetof(TrajectoryHeader, time)
+                  && offsetof(cavmd_trajectory_header, N) == offsetof(TrajectoryHeader, N)
+                  && offsetof(cavmd_trajectory_header, flags) == offsetof(TrajectoryHeader, flags)
+                  && offsetof(cavmd_trajectory_header, box) == offsetof(TrajectoryHeader, box)
+                  && offsetof(cavmd_trajectory_header, reserved) == offsetof(TrajectoryHeader, reserved),
+              "trajectory header layout");
+static_assert(sizeof(struct cavmd_trajectory_layout) == 48, "trajectory layout");
+static_assert(kTrajRows == 0, "SeriesTable: the rows-written array is the first of the counters");
+
+inline uint64_t pad16(uint64_t x)
+{
+    return (x + 15u) & ~(uint64_t)15u;
+}
+} // namespace
+
+extern "C"
+{
+
+int cavmd_trajectory_item_check(const cavmd_trajectory_item* it)
+{
+    if (!it || it->reserved0 != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (((uintptr_t)it->d_pos & 15) || ((uintptr_t)it->d_vel & 15) || ((uintptr_t)it->d_image & 3) || ((uintptr_t)it->d_time & 7))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (it->N > 0)
+    {
+        double cut_sq;
+        if (!it->d_pos || !it->d_image || !box_ok(it->Lx, it->Ly, it->Lz, &cut_sq))
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    if (it->N > CAVMD_BATCH_MAX_ITEM_N)
+        return CAVMD_ERR_CAPACITY;
+    return CAVMD_OK;
+}
+
+int cavmd_trajectory_layout(uint32_t max_N, uint32_t format, struct cavmd_trajectory_layout* out)
+{
+    if (!out || max_N < 1 || max_N > CAVMD_BATCH_MAX_ITEM_N || (format != CAVMD_TRAJECTORY_F64 && format != CAVMD_TRAJECTORY_F32))
+        return CAVMD_ERR_INVALID_VALUE;
+    const uint32_t e = format == CAVMD_TRAJECTORY_F64 ? 8 : 4;
+    const uint64_t section = pad16((uint64_t)3 * max_N * e);
+    out->position_offset = kTrajHeaderBytes;
+    out->velocity_offset = out->position_offset + section;
+    out->image_offset = out->velocity_offset + section;
+    out->frame_bytes = out->image_offset + pad16((uint64_t)12 * max_N);
+    out->max_N = max_N;
+    out->format = format;
+    out->element_bytes = e;
+    out->reserved = 0;
+    return CAVMD_OK;
+}
+
+int cavmd_trajectory_create(cavmd_workspace* ws, size_t n_items, const cavmd_trajectory_item* h_items, uint32_t max_N,
+                            uint32_t format, size_t capacity, uint64_t period, double time_interval, cavmd_trajectory** out)
+{
+    struct cavmd_trajectory_layout layout;
+    const bool args_ok = cavmd_trajectory_layout(max_N, format, &layout) == CAVMD_OK && capacity != 0 && period != 0
+                         && finite_nonnegative(time_interval) && !(time_interval > 0.0 && period != 1);
+    return create_table(tie_of(ws), n_items, h_items, out, args_ok ? CAVMD_OK : CAVMD_ERR_INVALID_VALUE, [&](cavmd_trajectory* t) {
+        t->layout = layout;
+        t->capacity = capacity;
+        t->period = period;
+        t->time_interval = time_interval;
+    });
+}
+
+int cavmd_trajectory_destroy(cavmd_trajectory* t)
+{
+    return destroy_table(t);
+}
+
+int cavmd_trajectory_set_items(cavmd_trajectory* t, size_t first, size_t count, const cavmd_trajectory_item* h_items)
+{
+    return t ? t->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_trajectory_record(cavmd_trajectory* t, void* stream_, const uint32_t* d_take_frame)
+{
+    if (!t || ((uintptr_t)d_take_frame & 3))
+        return CAVMD_ERR_INVALID_VALUE;
+    return t->layout.format == CAVMD_TRAJECTORY_F64
+               ? t->record(stream_, trajectory_batch_kernel<256, CAVMD_TRAJECTORY_F64>, d_take_frame)
+               : t->record(stream_, trajectory_batch_kernel<256, CAVMD_TRAJECTORY_F32>, d_take_frame);
+}
+
+int cavmd_trajectory_rows(cavmd_trajectory* t, void* stream_, uint64_t* out)
+{
+    return (t && out) ? t->rows((hipStream_t)stream_, out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_trajectory_read(cavmd_trajectory* t, void* stream_, size_t first_item, size_t n_items, uint64_t first_row, size_t n_rows,
+                          void* out)
+{
+    return t ? t->read((hipStream_t)stream_, first_item, n_items, first_row, n_rows, (unsigned char*)out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_trajectory_reset(cavmd_trajectory* t, void* stream_)
+{
+    return t ? t->reset((hipStream_t)stream_) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_trajectory_device_ptr(cavmd_trajectory* t, const void** series, const uint64_t** rows)
+{
+    if (!t || (!series && !rows))
+        return CAVMD_ERR_INVALID_VALUE;
+    const unsigned char* p = nullptr;
+    const int st = t->device_ptr(series ? &p : nullptr, rows);
+    if (st == CAVMD_OK && series)
+        *series = p;
+    return st;
 }
 
 } // extern "C"

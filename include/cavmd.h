@@ -32,6 +32,9 @@
  *   FieldAutocorrelationTracker, per step and replica
  *                               src/cavitymd/analysis.py:260-418    cavmd_field_recorder_create / cavmd_field_recorder_record /
  *                                                                   cavmd_field_recorder_read (rho(k), F(k,t), references)
+ *   hoomd.write.GSD (positions, images and velocities every output period, the initial frame first), per replica
+ *                               examples/05_advanced_run.py:1231-1246    cavmd_trajectory_create / cavmd_trajectory_record /
+ *                                                                   cavmd_trajectory_read (a ring of frames in device memory)
  *   CavityForceCompute::computeForces (the CPU semantics both follow)
  *                               src/CavityForceCompute.cc:134-208   (semantic contract, see below)
  *
@@ -1414,6 +1417,119 @@ CAVMD_API int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream);
  * n_items offsets into it: item i owns K_i + 1 entries of two doubles from offset[i] on, {A, B} of its k-vectors in the order
  * above and then {Q, 0}.  Both are valid until the next cavmd_coulomb_set_items or cavmd_coulomb_destroy. */
 CAVMD_API int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets);
+
+/* ---- trajectory frames of a batch: positions, velocities and images recorded on the device in ONE launch --------------------- */
+/* What the driver's hoomd.write.GSD (examples/05_advanced_run.py:1231-1246) saves every --gsd-output-period-ps, with the initial
+ * frame written first -- the positions, images and velocities of every replica -- as ONE launch for all systems that either
+ * appends one frame per system to a ring of frames kept in DEVICE memory, or moves the call counters and leaves.  One
+ * 256-thread workgroup per item.  Whether a frame is due is decided on the device, from words on the device (the item's
+ * counters, *d_time, the take word), so a call captured into a hipGraph records on the right replays, under an adaptive dt as
+ * well, and the host reads the ring when it likes.  Every pointer of an item is a DEVICE pointer that is read when the kernel
+ * RUNS.  The kernel writes nothing but the target slot and the item's five counter words (rows, calls, phase, slot, last_time);
+ * no atomics, and no workgroup waits for another, hence no CAVMD_ERR_SYNC_TIMEOUT here.
+ *
+ * The rule of one call, per item:
+ *   1. calls += 1; forced = d_take_frame != NULL && d_take_frame[item] != 0 (the word is only read, as d_take_reference is).
+ *   2. With time_interval == 0: phase += 1; due = phase >= period (cavmd_recorder_record's rule).
+ *      With time_interval > 0: t = *d_time; due = rows == 0 || t - last_time >= time_interval: one subtraction, one comparison,
+ *      so a NaN time is never due by it (the item's first call records whatever *d_time holds).  This is
+ *      _should_create_new_reference of src/cavitymd/analysis.py:366-378 with the first frame written at once, as the driver's
+ *      write_at_start.
+ *   3. If due || forced: the frame goes to slot rows % capacity; last_time = *d_time (or 0) and phase = 0, whatever the cause of
+ *      the frame; rows += 1.  Otherwise only calls and (by the step rule) phase move, and nothing else of the item is read.
+ *   4. An item with N == 0 records headers with N = 0 and touches no particle array.
+ *   5. cavmd_trajectory_reset zeroes the five counters; the next call under the time rule then records.
+ *
+ * A frame is a cavmd_trajectory_header and three sections (cavmd_trajectory_layout; every item of an object has this one
+ * layout): positions, velocities, images, each packed rows of three components (x, y, z per particle), not Scalar4.  The
+ * components of particles 0 .. N-1 are the stated conversions of pos.xyz, vel.xyz and image as those arrays are when the kernel
+ * runs; pos.w (the type tag) and vel.w (the mass) are never copied.  The bytes from the end of the 3 N components to the next
+ * 16-byte boundary of a section are written as zero; nothing else of the slot's sections is written (a slot that held a longer
+ * frame keeps that frame's tail behind them). */
+#define CAVMD_TRAJECTORY_F64 0 /* exact copies, 8 bytes per component */
+#define CAVMD_TRAJECTORY_F32 1 /* GSD's chunk types, 4 bytes per component: (float)x, IEEE round to nearest even; subnormal
+                                  results are kept, values beyond the float range become +-inf, NaN stays NaN */
+#define CAVMD_TRAJECTORY_MAX_BYTES 4294967296ull /* 2^32: of one object's ring, n_items x capacity x frame_bytes */
+
+typedef struct cavmd_trajectory_item     /* 64 B; all pointers DEVICE pointers, read when the kernel runs */
+{
+    const cavmd_double4* d_pos;          /* Scalar4 wrapped positions, 16-byte aligned; .w is the type tag and is never copied */
+    const cavmd_int3* d_image;           /* 4-byte aligned */
+    const cavmd_double4* d_vel;          /* Scalar4 velocities, mass in .w, never copied; NULL: the velocity section is +0 */
+    const double* d_time;                /* one double, 8-byte aligned, e.g. &cavmd_draw_state[i].elapsed; NULL: time is 0 */
+    double Lx, Ly, Lz;                   /* the box, copied into every header */
+    uint32_t N;                          /* particles; 0 is legal; <= the object's max_N */
+    uint32_t reserved0;                  /* must be 0 */
+} cavmd_trajectory_item;
+
+typedef struct cavmd_trajectory_header   /* 64 B, at the start of every frame */
+{
+    uint64_t call;            /* 1-based index of the cavmd_trajectory_record call (of this item) that wrote the frame */
+    uint64_t row;             /* 0-based frame number of the item */
+    double time;              /* *d_time, or 0 */
+    uint32_t N;               /* particles in this frame */
+    uint32_t flags;           /* bit 0: forced by the take word; bit 1: velocities present */
+    double box[3];            /* Lx, Ly, Lz */
+    uint64_t reserved;        /* 0 */
+} cavmd_trajectory_header;
+
+/* (a struct tag without a typedef: the function that fills it has its name, so C and C++ callers write `struct`) */
+struct cavmd_trajectory_layout           /* 48 B; with e = element_bytes and pad16(x) = x rounded up to a multiple of 16 */
+{
+    uint64_t frame_bytes;     /* image_offset + pad16(12 max_N) */
+    uint64_t position_offset; /* 64 */
+    uint64_t velocity_offset; /* 64 + pad16(3 max_N e) */
+    uint64_t image_offset;    /* velocity_offset + pad16(3 max_N e) */
+    uint32_t max_N;
+    uint32_t format;
+    uint32_t element_bytes;   /* 8 for CAVMD_TRAJECTORY_F64, 4 for CAVMD_TRAJECTORY_F32 */
+    uint32_t reserved;        /* 0 */
+};
+typedef struct cavmd_trajectory cavmd_trajectory; /* opaque; belongs to the workspace it was created from */
+
+/* Per-item validation of create / set_items; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE for a null item or
+ * reserved0 != 0, a d_pos / d_vel not 16-byte, a d_image not 4-byte or a d_time not 8-byte aligned, a null d_pos or d_image
+ * with N > 0, a box length that is not finite or not > 0 with N > 0; CAVMD_ERR_CAPACITY for N above CAVMD_BATCH_MAX_ITEM_N. */
+CAVMD_API int cavmd_trajectory_item_check(const cavmd_trajectory_item* item);
+/* The layout of a frame of up to max_N particles; host arithmetic only, needs no device.  CAVMD_ERR_INVALID_VALUE unless
+ * 1 <= max_N <= CAVMD_BATCH_MAX_ITEM_N, format is CAVMD_TRAJECTORY_F64 or CAVMD_TRAJECTORY_F32 and out is not NULL. */
+CAVMD_API int cavmd_trajectory_layout(uint32_t max_N, uint32_t format, struct cavmd_trajectory_layout* out);
+/* As cavmd_ledger_create, with frames of cavmd_trajectory_layout(max_N, format).frame_bytes: validates the n_items rows in HOST
+ * memory (1 .. CAVMD_BATCH_MAX_ITEMS; CAVMD_ERR_CAPACITY also for an item with N > max_N), copies the table to the device of
+ * `ws` (set-up time) and allocates n_items x capacity frames plus the per-item counters in device memory, all zero.
+ * CAVMD_ERR_INVALID_VALUE for capacity == 0 or period == 0, a time_interval that is negative or not finite, time_interval > 0
+ * with period != 1 or with an item whose d_time is NULL, and what cavmd_trajectory_layout refuses; CAVMD_ERR_CAPACITY if
+ * n_items x capacity x frame_bytes exceeds CAVMD_TRAJECTORY_MAX_BYTES.  cavmd_destroy answers CAVMD_ERR_INVALID_VALUE and frees
+ * nothing while a trajectory object of the workspace is alive.  Without a device there is no workspace, hence no object. */
+CAVMD_API int cavmd_trajectory_create(cavmd_workspace* ws, size_t n_items, const cavmd_trajectory_item* h_items, uint32_t max_N,
+                                      uint32_t format, size_t capacity, uint64_t period, double time_interval,
+                                      cavmd_trajectory** out);
+/* Synchronises the stream of the last cavmd_trajectory_record call (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_trajectory_destroy(cavmd_trajectory* t);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last record call; nothing is
+ * changed if a row is refused (CAVMD_ERR_CAPACITY for N > max_N, CAVMD_ERR_INVALID_VALUE for a NULL d_time under a
+ * time_interval > 0); counters and ring are kept.  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range
+ * outside the batch. */
+CAVMD_API int cavmd_trajectory_set_items(cavmd_trajectory* t, size_t first, size_t count, const cavmd_trajectory_item* h_items);
+/* Enqueues exactly ONE kernel of n_items workgroups on `stream`: no allocation, no copy, no host wait.  May be captured into a
+ * hipGraph, and a replay decides like an eager call, by the rule above.  d_take_frame is NULL or a DEVICE array of n_items
+ * uint32_t (4-byte aligned) read when the kernel runs.  Workgroups start in order of N descending (ties in item order).  One
+ * object serves one stream at a time. */
+CAVMD_API int cavmd_trajectory_record(cavmd_trajectory* t, void* stream, const uint32_t* d_take_frame);
+/* Synchronises `stream`, then out[i] = frames written by item i since creation / the last reset.  CAVMD_ERR_INVALID_VALUE while
+ * `stream` is being captured. */
+CAVMD_API int cavmd_trajectory_rows(cavmd_trajectory* t, void* stream, uint64_t* out);
+/* Synchronises `stream`, then fills out[(k * n_rows + j) * frame_bytes ...] with the whole frame first_row + j (0-based count
+ * of RECORDED frames) of item first_item + k; the statuses of cavmd_ledger_read: CAVMD_ERR_NOT_COMPUTED if an item asked for
+ * has never recorded, CAVMD_ERR_INVALID_VALUE for frames at or beyond the item's `rows`, n_rows or n_items 0, items outside the
+ * batch and while `stream` is being captured, CAVMD_ERR_EXPIRED if a requested frame has been overwritten. */
+CAVMD_API int cavmd_trajectory_read(cavmd_trajectory* t, void* stream, size_t first_item, size_t n_items, uint64_t first_row,
+                                    size_t n_rows, void* out);
+/* Zero the five counters of all items (ordered on `stream`): the next recorded frame is row 0, written by call 1. */
+CAVMD_API int cavmd_trajectory_reset(cavmd_trajectory* t, void* stream);
+/* Device addresses of the ring (item-major: frame j of item i at series + (i * capacity + j % capacity) * frame_bytes) and of
+ * the n_items row counters, for consumers that stay on the GPU (either may be NULL, not both). */
+CAVMD_API int cavmd_trajectory_device_ptr(cavmd_trajectory* t, const void** series, const uint64_t** rows);
 
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
