@@ -412,6 +412,21 @@ def coulomb_item(N, pos_ptr, charge_ptr, force_ptr, box_L, kappa, r_cut, k_cut, 
     return it
 
 
+SNAPSHOT_MAGIC = 0x3150414E53564143   # "CAVSNAP1"
+SNAPSHOT_VERSION = 1
+# CAVMD_SNAPSHOT_<OBJECT>: the `kind` of a blob, by the object's name in cavmd_snapshot_<object>_*
+SNAPSHOT_KINDS = {"verlet": 1, "bath": 2, "draw": 3, "thermalize": 4, "bussi_batch": 5, "recorder": 6, "ledger": 7,
+                  "trajectory": 8, "field_recorder": 9}
+
+
+class SnapshotHeader(ctypes.Structure):
+    """cavmd_snapshot_header (64 bytes): what every snapshot blob begins with."""
+    _fields_ = [("magic", ctypes.c_uint64), ("version", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("n_items", ctypes.c_uint32), ("n_counters", ctypes.c_uint32), ("capacity", ctypes.c_uint64),
+                ("record_bytes", ctypes.c_uint64), ("word", ctypes.c_uint32 * 2), ("bytes", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
 def trajectory_item(pos_ptr=0, image_ptr=0, vel_ptr=0, time_ptr=0, box_L=(0.0, 0.0, 0.0), N=0) -> "TrajectoryItem":
     """vel_ptr == 0: the velocity section of every frame is +0; time_ptr == 0: time is 0."""
     it = TrajectoryItem()
@@ -565,6 +580,34 @@ _PROTOTYPES = {
     "cavmd_profile_enable": (_ci, [_vp, _ci]),
     "cavmd_profile_read": (_ci, [_vp, _P(_dbl * 3), _P(_u64)]),
     "cavmd_profile_samples": (_ci, [_vp, _vp, _sz, _P(_sz)]),
+    "cavmd_snapshot_check": (_ci, [_vp, _sz, _P(SnapshotHeader)]),
+    "cavmd_snapshot_verlet_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_verlet_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_verlet_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_bath_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_bath_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_bath_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_draw_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_draw_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_draw_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_thermalize_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_thermalize_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_thermalize_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_bussi_batch_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_bussi_batch_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_bussi_batch_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_recorder_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_recorder_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_recorder_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_ledger_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_ledger_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_ledger_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_trajectory_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_trajectory_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_trajectory_load": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_field_recorder_bytes": (_ci, [_vp, _P(_sz)]),
+    "cavmd_snapshot_field_recorder_save": (_ci, [_vp, _vp, _vp, _sz]),
+    "cavmd_snapshot_field_recorder_load": (_ci, [_vp, _vp, _vp, _sz]),
     "cavmd_set_tunable": (_ci, [_vp, _cstr, _ci]),
     "cavmd_get_tunable": (_ci, [_vp, _cstr, _P(_ci)]),
     "cavmd_device_info": (_ci, [_vp, _P(_ci), _P(_ci), _cstr, _sz]),
@@ -960,7 +1003,46 @@ class _ItemTableHandle:
             self.sizes[first + k] = self._size(it)
 
 
-class _SeriesHandle(_ItemTableHandle):
+def snapshot_check(blob, expected: SnapshotHeader) -> int:
+    """Status cavmd_snapshot_<object>_load would give `blob` (a uint8 array or bytes) for an object whose header is `expected`,
+    from the blob's first 64 bytes (host arithmetic only: needs no device)."""
+    import numpy as np
+    b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, dtype=np.uint8)
+    return int(load().cavmd_snapshot_check(ctypes.c_void_p(b.ctypes.data) if b.size else None, int(b.size), ctypes.byref(expected)))
+
+
+class _Snapshots:
+    """What the nine handles whose launches write device state share (the state and the series handles, and BussiBatch): that
+    state as one blob in host memory, cavmd_snapshot_<object>_bytes / _save / _load of include/cavmd.h."""
+
+    def _snapshot(self, name):
+        return getattr(self._lib, "cavmd_snapshot_" + self._PREFIX[len("cavmd_"):] + "_" + name), \
+            "cavmd_snapshot_" + self._PREFIX[len("cavmd_"):] + "_" + name
+
+    def snapshot_bytes(self) -> int:
+        fn, where = self._snapshot("bytes")
+        n = ctypes.c_size_t()
+        check(fn(self._h, ctypes.byref(n)), where)
+        return int(n.value)
+
+    def snapshot_save(self, stream: int = 0):
+        """The object's device state after synchronising `stream`: header and arrays, a uint8 array."""
+        import numpy as np
+        out = np.zeros(self.snapshot_bytes(), dtype=np.uint8)
+        fn, where = self._snapshot("save")
+        check(fn(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(out.ctypes.data), int(out.size)), where)
+        return out
+
+    def snapshot_load(self, stream: int, blob) -> None:
+        """Puts a blob of ``snapshot_save`` back; one of another kind or shape raises CavmdError(CAVMD_ERR_INVALID_VALUE) and
+        leaves the object as it was."""
+        import numpy as np
+        b = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        fn, where = self._snapshot("load")
+        check(fn(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(b.ctypes.data) if b.size else None, int(b.size)), where)
+
+
+class _SeriesHandle(_ItemTableHandle, _Snapshots):
     """A handle whose launches append rows to a time series in device memory (SeriesTable in csrc/cavmd_item_table.hpp).  A
     subclass names the ctypes structure of one row."""
     _RECORD = None
@@ -991,7 +1073,7 @@ class _SeriesHandle(_ItemTableHandle):
         return int(rec.value), int(rows.value)
 
 
-class _StateHandle(_ItemTableHandle):
+class _StateHandle(_ItemTableHandle, _Snapshots):
     """A handle with one state per item in device memory (StateTable in csrc/cavmd_item_table.hpp).  A subclass names the
     ctypes structure of one state."""
     _STATE = None
@@ -1050,6 +1132,7 @@ thermalize_state_dtype = _dtype_of(ThermalizeState)
 ledger_row_dtype = _dtype_of(LedgerRow)
 draw_state_dtype = _dtype_of(DrawState)
 trajectory_header_dtype = _dtype_of(TrajectoryHeader)
+snapshot_header_dtype = _dtype_of(SnapshotHeader)
 
 
 class Batch(_ItemTableHandle):
@@ -1103,7 +1186,7 @@ def bussi_batch_input_make(deltaT, set_T, tau, normal_variate, gamma_variate) ->
     return row
 
 
-class BussiBatch(_ItemTableHandle):
+class BussiBatch(_ItemTableHandle, _Snapshots):
     """Owns one cavmd_bussi_batch: the translational Bussi thermostat step of B independent small systems as ONE kernel
     launch, one workgroup per system, its per-step inputs read from device memory.  Launched by n_members descending."""
     _ITEM, _PREFIX = BussiBatchItem, "cavmd_bussi_batch"

@@ -2,6 +2,8 @@
 they are given, the stream handle, the owner of a library handle with its workspace, and the step's input rows."""
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -102,6 +104,78 @@ class HandleOwner:
             self.close()
         except Exception:
             pass
+
+
+class Checkpointable:
+    """``state_dict`` / ``load_state_dict`` of the nine batch classes whose launches write device state (next to
+    ``HandleOwner``): the library object's snapshot blob (``cavmd_snapshot_*`` of include/cavmd.h) as one uint8 array under
+    ``"snapshot"``, plus the tensors the Python object itself owns and launches write, verbatim.  What the object was built
+    from -- the arrays of other owners, parameters, seeds -- is not in there: build the same object first, then load."""
+
+    def _state_tensors(self) -> dict:
+        """name -> a tensor, or a list of tensors (one per system), that this object owns and a launch writes"""
+        return {}
+
+    def _flat_state_tensors(self) -> dict:
+        flat = {}
+        for name, value in self._state_tensors().items():
+            if isinstance(value, torch.Tensor):
+                flat[name] = value
+            else:
+                flat.update({f"{name}.{k}": t for k, t in enumerate(value)})
+        return flat
+
+    def _host_driven(self, what: str) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what}() copies through the host: it cannot be captured")
+
+    def state_dict(self, stream=None) -> dict:
+        """{"snapshot": the blob, name: array, ...} as numpy arrays.  Default: waits for the whole device (a graph replays on
+        the stream it is launched on) first; with ``stream``, for that stream only.  Refused during a capture."""
+        handle = self._need()
+        self._host_driven("state_dict")
+        if stream is None:
+            torch.cuda.synchronize(self._device)
+        out = {"snapshot": handle.snapshot_save(stream_handle(stream, self._dev_index))}
+        for name, t in self._flat_state_tensors().items():
+            out[name] = t.detach().cpu().numpy()
+        return out
+
+    def check_state_dict(self, d) -> None:
+        """Raises ValueError unless ``d`` has exactly this object's names, tensors of its shapes and dtypes, and a blob of its
+        kind, system count and size.  Touches nothing (the library checks the blob's remaining words before it loads)."""
+        handle = self._need()
+        tensors = self._flat_state_tensors()
+        who = type(self).__name__
+        if set(d) != set(tensors) | {"snapshot"}:
+            raise ValueError(f"{who}: the state holds {sorted(d)}, the object {sorted(set(tensors) | {'snapshot'})}")
+        for name, t in tensors.items():
+            a = np.asarray(d[name])
+            if tuple(a.shape) != tuple(t.shape) or torch.from_numpy(np.zeros(0, dtype=a.dtype)).dtype != t.dtype:
+                raise ValueError(f"{who}: {name} is {a.dtype}{tuple(a.shape)} in the state, {t.dtype}{tuple(t.shape)} here")
+        blob = np.asarray(d["snapshot"])
+        if blob.dtype != np.uint8 or blob.ndim != 1 or blob.size < ctypes.sizeof(_capi.SnapshotHeader):
+            raise ValueError(f"{who}: the snapshot is no uint8 blob with a header")
+        head = _capi.SnapshotHeader.from_buffer_copy(blob[:ctypes.sizeof(_capi.SnapshotHeader)].tobytes())
+        kind = _capi.SNAPSHOT_KINDS[handle._PREFIX[len("cavmd_"):]]
+        if (head.magic, head.version, head.kind, head.n_items, head.bytes) != \
+                (_capi.SNAPSHOT_MAGIC, _capi.SNAPSHOT_VERSION, kind, handle.n_items, blob.size) \
+                or blob.size != handle.snapshot_bytes():
+            raise ValueError(f"{who}: the snapshot is of another object or shape")
+
+    def load_state_dict(self, d, stream=None) -> None:
+        """Puts a ``state_dict`` back: the names, shapes and dtypes are checked, then the library loads the blob (one it refuses
+        raises CavmdError and leaves everything as it was), then the tensors are written.  Device addresses do not change: a
+        graph captured before replays on the loaded state.  Refused during a capture."""
+        handle = self._need()
+        self._host_driven("load_state_dict")
+        self.check_state_dict(d)
+        if stream is None:
+            torch.cuda.synchronize(self._device)
+        handle.snapshot_load(stream_handle(stream, self._dev_index), np.asarray(d["snapshot"]))
+        for name, t in self._flat_state_tensors().items():
+            t.copy_(torch.from_numpy(np.ascontiguousarray(d[name])))
+        torch.cuda.current_stream(self._device).synchronize()
 
 
 class StepInputs:

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, per_system, stream_handle
+from ._device import Checkpointable, HandleOwner, per_system, stream_handle
 
 
 def _gamma_tensor(g, k: int):
@@ -52,7 +52,7 @@ def _gamma_tensor(g, k: int):
     return g
 
 
-class LangevinBathBatch(HandleOwner):
+class LangevinBathBatch(HandleOwner, Checkpointable):
     """integrator: the ``VerletBatch`` whose second half-step this object supplies; gammas: per system a ``(N_k,)`` float64
     device tensor of frictions (a particle with gamma 0, or beyond the tensor's end, is not coupled), or None for no bath on
     that system; kT: one number, or one per system; seed: 0 .. 2**64 - 1; seeds: None, or one Philox key per system."""

@@ -27,10 +27,10 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, StepInputs, device_tensor, per_system, stream_handle
+from ._device import Checkpointable, HandleOwner, StepInputs, device_tensor, per_system, stream_handle
 
 
-class VerletBatch(HandleOwner):
+class VerletBatch(HandleOwner, Checkpointable):
     """force_batch: the ``CavityForceBatch`` whose systems are integrated (positions, images and boxes are taken from its
     system definitions, its force arrays are the first force of every system); velocities: one (N_k, 4) device tensor per
     system (mass in column 3); extra_forces: None, or per system a list of up to three more (N_k, 4) force tensors, summed
@@ -143,6 +143,14 @@ class VerletBatch(HandleOwner):
     def reset(self, stream=None) -> None:
         """Zero every system's counters, ordered on ``stream`` (default: torch's current stream)."""
         self._need().reset(stream_handle(stream, self._dev_index))
+
+    def _state_tensors(self) -> dict:
+        """``accel`` (after a step with a bath it holds the random force and cannot be recomputed), ``inputs`` and, if there,
+        ``net_forces``: what ``state_dict`` saves next to the integrator's counters"""
+        own = {"accel": self.accel, "inputs": self.inputs}
+        if self.net_forces is not None:
+            own["net_forces"] = self.net_forces
+        return own
 
     @property
     def verlet(self) -> _capi.Verlet:

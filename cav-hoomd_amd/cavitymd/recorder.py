@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, device_tensor, member_indices, stream_handle
+from ._device import Checkpointable, HandleOwner, device_tensor, member_indices, stream_handle
 from .utils import PhysicalConstants
 
 
@@ -34,7 +34,7 @@ def _device_tensor(t, what: str):
     return device_tensor(t, "BatchRecorder", what, note=" (HOOMD Scalar4)")
 
 
-class _SeriesRecorder(HandleOwner):
+class _SeriesRecorder(HandleOwner, Checkpointable):
     """What ``BatchRecorder`` and ``BatchFieldRecorder`` share: the stream a read waits for and the default window of
     ``read()``.  A subclass opens its recorder and sets ``n_systems``, ``capacity`` and ``_record_dtype`` (a function that
     gives the numpy dtype of one row)."""

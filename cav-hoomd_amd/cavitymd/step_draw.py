@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, one_device, per_system, stream_handle
+from ._device import Checkpointable, HandleOwner, one_device, per_system, stream_handle
 
 _ROW_BYTES = 64
 _RECORD_BYTES = 128
@@ -48,7 +48,7 @@ def _inputs_of(owner, what: str):
     return t
 
 
-class StepDraw(HandleOwner):
+class StepDraw(HandleOwner, Checkpointable):
     """seed: 0 .. 2**64 - 1, the generator's key; integrator: a ``VerletBatch`` (or its ``inputs`` tensor) or None;
     thermostat: an attached ``BussiReservoirBatch`` (or its ``inputs`` tensor) or None -- at least one of the two;
     recorder: the ``BatchRecorder`` whose last row gives S, required with ``tolerance``.

@@ -34,12 +34,12 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, device_tensor, one_device, per_system, stream_handle
+from ._device import Checkpointable, HandleOwner, device_tensor, one_device, per_system, stream_handle
 
 _RESULT_BYTES = 192
 
 
-class BatchThermalizer(HandleOwner):
+class BatchThermalizer(HandleOwner, Checkpointable):
     """velocities: one ``(N_k, 4)`` float64 device tensor per system, mass in column 3; kT: one number, or one per system;
     seed: 0 .. 2**64 - 1; members: None, or per system None / an index array of the particles that receive a velocity (an
     index at or beyond N_k is skipped and counted); zero_momentum: take the total momentum out of them; cavity: the

@@ -23,10 +23,10 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import HandleOwner, StepInputs, device_tensor, member_indices, one_device, per_system, stream_handle
+from ._device import Checkpointable, HandleOwner, StepInputs, device_tensor, member_indices, one_device, per_system, stream_handle
 
 
-class BussiReservoirBatch(HandleOwner):
+class BussiReservoirBatch(HandleOwner, Checkpointable):
     _unusable = "used before attach()"
 
     def __init__(self, kT, tau=0.0):
@@ -160,6 +160,10 @@ class BussiReservoirBatch(HandleOwner):
     @property
     def instantaneous_reservoir_total(self) -> np.ndarray:
         return self.instantaneous_reservoir_translational + self.instantaneous_reservoir_rotational
+
+    def _state_tensors(self) -> dict:
+        """the input rows: what ``state_dict`` saves next to the per-system counters"""
+        return {"inputs": self.inputs}
 
     def reset_reservoir_energy(self) -> None:
         self._need().reset(self._stream)

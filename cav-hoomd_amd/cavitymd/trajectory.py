@@ -181,7 +181,8 @@ class BatchTrajectoryRecorder(_SeriesRecorder):
         """Writes frame ``row`` (default: the last) of every system in ``systems`` (default: all) back into the arrays it was
         taken from: x, y, z of the positions with the type tags kept, the images, and the velocities with the masses kept.
         For "f64" recorders only (an "f32" frame is not the state); host-driven, refused during a capture.  Forces and
-        accelerations are the caller's to evaluate again."""
+        accelerations are the caller's to evaluate again; to continue a run with the same bits, generators, baths and rings
+        included, use ``BatchCheckpoint`` (checkpoint.py)."""
         if self.format != _capi.TRAJECTORY_F64:
             raise RuntimeError('restore() needs exact frames: build the recorder with dtype="f64"')
         if torch.cuda.is_current_stream_capturing():

@@ -1,5 +1,5 @@
 // cavmd_bussi_batch.hip -- cavmd_bussi_batch of include/cavmd.h: the thermostat step of a batch of small systems in one launch.
-// One of the eleven objects built on an item table (cavmd_item_table.hpp); the workspace is an incomplete type here.
+// One of the objects built on an item table (cavmd_item_table.hpp), a StateTable; the workspace is an incomplete type here.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -18,25 +18,44 @@
 using namespace cavmd;
 
 // ---- the Bussi thermostat step of a batch of independent small systems in one launch (cavmd_bussi_batch_kernel.hpp) ---------
-struct cavmd_bussi_batch : ItemTable<cavmd_bussi_batch_item, BussiBatchRow> // launched by n_members descending
+// A StateTable for its n device states (d_state) and their snapshot; its read and reset are the entry points' own, which go
+// through the host blocks the kernel publishes to.
+struct cavmd_bussi_batch : StateTable<cavmd_bussi_batch_item, BussiBatchRow, BussiDevice> // launched by n_members descending
 {
     std::vector<uint64_t> refused_seen;        // per item: refusals already reported to the caller
-    DeviceArray<BussiDevice> d_state;          // n states, indexed by item
     MappedBlock<HostBussiBatch> h_blocks;      // n blocks, indexed by item
     uint64_t sequence = 0;
     bool captured = false; // some step was enqueued into a stream capture: the stamps cannot tell replays apart
+    bool loaded = false;   // a snapshot was loaded: the states mean something before the first step
 
     cavmd_bussi_batch()
-        : ItemTable(cavmd_bussi_batch_item_check, [](const cavmd_bussi_batch_item& it) { return it.n_members; },
-                    uploaded_as_it_is<cavmd_bussi_batch_item, BussiBatchRow>)
+        : StateTable(cavmd_bussi_batch_item_check, [](const cavmd_bussi_batch_item& it) { return it.n_members; },
+                     uploaded_as_it_is<cavmd_bussi_batch_item, BussiBatchRow>)
     {
     }
 
     hipError_t alloc_own()
     {
         refused_seen.assign(n, 0);
-        const hipError_t e = d_state.alloc_zeroed(n);
+        const hipError_t e = StateTable::alloc_own();
         return e == hipSuccess ? h_blocks.alloc(n) : e;
+    }
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return state_shape(CAVMD_SNAPSHOT_BUSSI_BATCH, 0, 0);
+    }
+
+    // the host's copies follow the loaded states (nothing is in flight: snapshot_load has waited): the blocks that a read
+    // outside a capture answers from, and the refusals counted in them, which count as reported
+    void snapshot_loaded(const char* const* sections)
+    {
+        for (size_t i = 0; i < n; ++i)
+        {
+            memcpy(&h_blocks.host[i].state, sections[0] + i * sizeof(BussiDevice), sizeof(BussiDevice));
+            refused_seen[i] = h_blocks.host[i].state.errors;
+        }
+        loaded = true;
     }
 };
 
@@ -143,10 +162,10 @@ int cavmd_bussi_batch_read(cavmd_bussi_batch* b, cavmd_bussi_device_state* out)
     if (!b || !out)
         return CAVMD_ERR_INVALID_VALUE;
     memset(out, 0, sizeof(*out) * b->n);
-    if (b->sequence == 0)
+    if (b->sequence == 0 && !b->loaded)
         return CAVMD_OK;
     DeviceGuard guard(b->device);
-    if (b->captured)
+    if (b->captured || b->sequence == 0) // (no step since a load: the loaded states, as the device holds them)
     {
         // graph replays: frozen sequence, unknown replay stream -> wait for the device and copy the device states
         CAVMD_HIP_TRY(hipDeviceSynchronize());
@@ -203,6 +222,21 @@ int cavmd_bussi_batch_state_device_ptr(cavmd_bussi_batch* b, const cavmd_bussi_d
         return CAVMD_ERR_INVALID_VALUE;
     *out = reinterpret_cast<const cavmd_bussi_device_state*>(b->d_state.ptr);
     return CAVMD_OK;
+}
+
+int cavmd_snapshot_bussi_batch_bytes(cavmd_bussi_batch* b, size_t* bytes)
+{
+    return snapshot_bytes(b, bytes);
+}
+
+int cavmd_snapshot_bussi_batch_save(cavmd_bussi_batch* b, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(b, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_bussi_batch_load(cavmd_bussi_batch* b, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(b, (hipStream_t)stream_, h_in, bytes);
 }
 
 } // extern "C"

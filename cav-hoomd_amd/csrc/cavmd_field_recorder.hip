@@ -54,6 +54,20 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
             e = d_now.alloc_zeroed(2 * n_k * n);
         return e == hipSuccess ? d_refs.alloc_zeroed(2 * n_k * n * max_refs) : e;
     }
+
+    // the series' two arrays, then what the object keeps beyond them (the wavevectors are create's, not state)
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return series_shape(CAVMD_SNAPSHOT_FIELD_RECORDER, (uint32_t)n_k, max_refs);
+    }
+    size_t snapshot_arrays(const void** arrays) const
+    {
+        const size_t first = SeriesTable::snapshot_arrays(arrays);
+        arrays[first] = d_ref_rows.ptr;
+        arrays[first + 1] = d_now.ptr;
+        arrays[first + 2] = d_refs.ptr;
+        return first + 3;
+    }
 };
 
 namespace
@@ -175,6 +189,21 @@ int cavmd_field_recorder_reset(cavmd_field_recorder* r, void* stream_)
 int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cavmd_field_record** records, const uint64_t** rows)
 {
     return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_snapshot_field_recorder_bytes(cavmd_field_recorder* r, size_t* bytes)
+{
+    return snapshot_bytes(r, bytes);
+}
+
+int cavmd_snapshot_field_recorder_save(cavmd_field_recorder* r, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(r, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_field_recorder_load(cavmd_field_recorder* r, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(r, (hipStream_t)stream_, h_in, bytes);
 }
 
 } // extern "C"

@@ -5,8 +5,10 @@
 // ItemTable is how a table of items lives on the host and on the device; create_table makes an object and ties it to its
 // parent, ItemTable::launch launches it and destroy_table releases it.  Three flavours state what more an object keeps:
 // SeriesTable, a ring of records per item (the two recorders, the ledger and the trajectory); StateTable, one state per
-// item (the integrator, the draw object, the bath and the thermalize object); LinkedTable, tables derived from the items that
-// the kernels find through a header at a fixed device address and that set_items replaces together (the two force batches).
+// item (the integrator, the draw object, the bath, the thermalize object and the thermostat batch); LinkedTable, tables derived
+// from the items that the kernels find through a header at a fixed device address and that set_items replaces together (the
+// two force batches).  What a SeriesTable or a StateTable holds on the device can be saved to a host blob and loaded back
+// (snapshot_bytes / snapshot_save / snapshot_load below, on the arithmetic of cavmd_snapshot.hpp).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once
 
@@ -21,6 +23,7 @@
 
 #include "cavmd.h"
 #include "cavmd_host_support.hpp" // DeviceGuard, hip_status, CAVMD_HIP_TRY, stream_capturing, DeviceArray
+#include "cavmd_snapshot.hpp"     // the blob's header, its sections and snapshot_check (host arithmetic, no HIP)
 
 // What an object built on an item table needs of the parent it was created from: the device, and the count of live objects
 // that the parent's destroy refuses on.  The parent is a workspace, or for a bath its integrator (cavmd_verlet::bath_tie).
@@ -251,6 +254,12 @@ struct ItemTable
     {
         (void)wait_idle();
     }
+
+    // what snapshot_load asks of an object once the device holds the blob's sections (`sections`: where each begins in the
+    // blob); one whose host keeps something derived from them hides this
+    void snapshot_loaded(const char* const*)
+    {
+    }
 };
 
 // The end of every object built on an item table: guard, quiesce, detach, delete -- the buffers go with their owners.
@@ -308,6 +317,83 @@ int create_table(WorkspaceTie* tie, size_t n_items, const Item* h_items, Table**
     if (Table::tied)
         t->attach(tie);
     *out = t;
+    return CAVMD_OK;
+}
+
+// ---- save and restore (include/cavmd.h; the blob's arithmetic is cavmd_snapshot.hpp's) ------------------------------------------
+// Written once for every flavour.  An object names its shape, snapshot_shape() -- a flavour's state_shape / series_shape with
+// the object's kind and words -- and the flavour (or the object, if it has more) its device arrays in the blob's order,
+// snapshot_arrays(); the sizes follow from the shape alone.
+template <class Table>
+int snapshot_bytes(Table* t, size_t* bytes)
+{
+    if (!t || !bytes)
+        return CAVMD_ERR_INVALID_VALUE;
+    *bytes = (size_t)t->snapshot_shape().bytes;
+    return CAVMD_OK;
+}
+
+template <class Table>
+int snapshot_save(Table* t, hipStream_t stream, void* h_out, size_t bytes)
+{
+    if (!t || !h_out)
+        return CAVMD_ERR_INVALID_VALUE;
+    const cavmd_snapshot_header h = t->snapshot_shape();
+    if ((uint64_t)bytes != h.bytes)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(t->device);
+    const int st = sync_uncaptured(stream);
+    if (st != CAVMD_OK)
+        return st;
+    uint64_t sizes[cavmd::kSnapshotMaxSections];
+    const void* arrays[cavmd::kSnapshotMaxSections];
+    const size_t count = cavmd::snapshot_sections(h, sizes);
+    if (t->snapshot_arrays(arrays) != count)
+        return CAVMD_ERR_INVALID_VALUE;
+    char* out = static_cast<char*>(h_out);
+    memcpy(out, &h, sizeof(h));
+    size_t at = sizeof(h);
+    for (size_t k = 0; k < count; ++k)
+    {
+        const size_t padded = (size_t)cavmd::snapshot_pad16(sizes[k]);
+        CAVMD_HIP_TRY(hipMemcpy(out + at, arrays[k], (size_t)sizes[k], hipMemcpyDeviceToHost));
+        memset(out + at + sizes[k], 0, padded - (size_t)sizes[k]);
+        at += padded;
+    }
+    return CAVMD_OK;
+}
+
+template <class Table>
+int snapshot_load(Table* t, hipStream_t stream, const void* h_in, size_t bytes)
+{
+    if (!t || !h_in || stream_capturing(stream))
+        return CAVMD_ERR_INVALID_VALUE;
+    const cavmd_snapshot_header h = t->snapshot_shape();
+    int st = cavmd::snapshot_check(h_in, bytes, &h);
+    if (st != CAVMD_OK)
+        return st;
+    uint64_t sizes[cavmd::kSnapshotMaxSections];
+    const void* arrays[cavmd::kSnapshotMaxSections];
+    const size_t count = cavmd::snapshot_sections(h, sizes);
+    if (t->snapshot_arrays(arrays) != count)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(t->device);
+    // the launches in flight: the object's own (set_items' wait), and what the caller replays on `stream`
+    st = t->wait_idle();
+    if (st == CAVMD_OK)
+        st = sync_uncaptured(stream);
+    if (st != CAVMD_OK)
+        return st;
+    const char* in = static_cast<const char*>(h_in);
+    const char* sections[cavmd::kSnapshotMaxSections];
+    size_t at = sizeof(h);
+    for (size_t k = 0; k < count; ++k)
+    {
+        sections[k] = in + at;
+        CAVMD_HIP_TRY(hipMemcpy(const_cast<void*>(arrays[k]), sections[k], (size_t)sizes[k], hipMemcpyHostToDevice));
+        at += (size_t)cavmd::snapshot_pad16(sizes[k]);
+    }
+    t->snapshot_loaded(sections); // (hipMemcpy has returned: the copies are complete, whichever stream launches next)
     return CAVMD_OK;
 }
 
@@ -386,6 +472,18 @@ struct SeriesTable : ItemTable<Item, Row>
         return CAVMD_OK;
     }
 
+    // the shape of the object's snapshot, and its arrays in the blob's order: the counters, then the whole ring
+    cavmd_snapshot_header series_shape(uint32_t kind, uint32_t word0, uint32_t word1) const
+    {
+        return cavmd::snapshot_header_make(kind, this->n, capacity, record_bytes, n_counters, word0, word1);
+    }
+    size_t snapshot_arrays(const void** arrays) const
+    {
+        arrays[0] = d_counters.ptr;
+        arrays[1] = d_series.ptr;
+        return 2;
+    }
+
     int device_ptr(const Record** records, const uint64_t** rows_written)
     {
         if (!records && !rows_written)
@@ -431,6 +529,17 @@ struct StateTable : ItemTable<Item, Row>
         DeviceGuard guard(this->device);
         CAVMD_HIP_TRY(hipMemsetAsync(d_state.ptr, 0, sizeof(State) * this->n, stream));
         return CAVMD_OK;
+    }
+
+    // the shape of the object's snapshot, and its one array
+    cavmd_snapshot_header state_shape(uint32_t kind, uint32_t word0, uint32_t word1) const
+    {
+        return cavmd::snapshot_header_make(kind, this->n, 0, sizeof(State), 0, word0, word1);
+    }
+    size_t snapshot_arrays(const void** arrays) const
+    {
+        arrays[0] = d_state.ptr;
+        return 1;
     }
 
     template <class PublicState>

@@ -72,6 +72,11 @@ int create_periodic(cavmd_workspace* ws, size_t n_items, const Item* h_items, si
 struct cavmd_recorder : PeriodicSeries<cavmd_recorder_item, RecorderRow, cavmd_record>
 {
     cavmd_recorder() : PeriodicSeries(cavmd_recorder_item_check) {}
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return series_shape(CAVMD_SNAPSHOT_RECORDER, 0, 0);
+    }
 };
 
 namespace
@@ -150,12 +155,32 @@ int cavmd_recorder_device_ptr(cavmd_recorder* r, const cavmd_record** records, c
     return r ? r->device_ptr(records, rows) : CAVMD_ERR_INVALID_VALUE;
 }
 
+int cavmd_snapshot_recorder_bytes(cavmd_recorder* r, size_t* bytes)
+{
+    return snapshot_bytes(r, bytes);
+}
+
+int cavmd_snapshot_recorder_save(cavmd_recorder* r, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(r, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_recorder_load(cavmd_recorder* r, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(r, (hipStream_t)stream_, h_in, bytes);
+}
+
 } // extern "C"
 
 // ---- the energy ledger of a batch: every term of the conserved energy per step (cavmd_ledger_kernel.hpp) ----------------------
 struct cavmd_ledger : PeriodicSeries<cavmd_ledger_item, LedgerItem, cavmd_ledger_row> // the recorder's shape
 {
     cavmd_ledger() : PeriodicSeries(cavmd_ledger_item_check) {}
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return series_shape(CAVMD_SNAPSHOT_LEDGER, 0, 0);
+    }
 };
 
 namespace
@@ -245,6 +270,21 @@ int cavmd_ledger_device_ptr(cavmd_ledger* l, const cavmd_ledger_row** series, co
     return l ? l->device_ptr(series, rows) : CAVMD_ERR_INVALID_VALUE;
 }
 
+int cavmd_snapshot_ledger_bytes(cavmd_ledger* l, size_t* bytes)
+{
+    return snapshot_bytes(l, bytes);
+}
+
+int cavmd_snapshot_ledger_save(cavmd_ledger* l, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(l, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_ledger_load(cavmd_ledger* l, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(l, (hipStream_t)stream_, h_in, bytes);
+}
+
 } // extern "C"
 
 // ---- trajectory frames of a batch: positions, velocities and images per due call (cavmd_trajectory_kernel.hpp) ----------------
@@ -284,6 +324,11 @@ struct cavmd_trajectory : SeriesTable<cavmd_trajectory_item, TrajectoryRow, unsi
     int capacity_status(size_t n_items) const
     {
         return capacity > CAVMD_TRAJECTORY_MAX_BYTES / layout.frame_bytes / n_items ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+    }
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return series_shape(CAVMD_SNAPSHOT_TRAJECTORY, layout.max_N, layout.format);
     }
     hipError_t alloc_own()
     {
@@ -432,6 +477,21 @@ int cavmd_trajectory_device_ptr(cavmd_trajectory* t, const void** series, const 
     if (st == CAVMD_OK && series)
         *series = p;
     return st;
+}
+
+int cavmd_snapshot_trajectory_bytes(cavmd_trajectory* t, size_t* bytes)
+{
+    return snapshot_bytes(t, bytes);
+}
+
+int cavmd_snapshot_trajectory_save(cavmd_trajectory* t, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(t, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_trajectory_load(cavmd_trajectory* t, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(t, (hipStream_t)stream_, h_in, bytes);
 }
 
 } // extern "C"

@@ -38,6 +38,11 @@ struct cavmd_verlet : StateTable<cavmd_verlet_item, VerletRow, VerletState> // l
         return launch((hipStream_t)stream, kernel, dim3((unsigned)n), dim3(256), 0, d_rows.ptr, d_order.ptr,
                       reinterpret_cast<const VerletInput*>(d_inputs), d_state.ptr);
     }
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return state_shape(CAVMD_SNAPSHOT_VERLET, 0, 0);
+    }
 };
 
 // ---- the step inputs of a batch drawn on the device, one launch per step (cavmd_draw_kernel.hpp) ------------------------------
@@ -62,6 +67,12 @@ struct cavmd_draw : StateTable<cavmd_draw_item, DrawRow, DrawState> // items cos
     uint64_t seed = 0;
 
     cavmd_draw() : StateTable(cavmd_draw_item_check, [](const cavmd_draw_item&) { return 0u; }, draw_row) {}
+
+    // (the seed is a word of the shape: states drawn under another seed do not continue this object's sequence)
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return state_shape(CAVMD_SNAPSHOT_DRAW, (uint32_t)seed, (uint32_t)(seed >> 32));
+    }
 };
 
 // ---- a Langevin bath on any set of particles of every item, drawn in step two (cavmd_bath_kernel.hpp) --------------------------
@@ -76,6 +87,11 @@ struct cavmd_bath : StateTable<cavmd_bath_item, BathRow, BathState> // tied to v
                      uploaded_as_it_is<cavmd_bath_item, BathRow>)
     {
     }
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return state_shape(CAVMD_SNAPSHOT_BATH, 0, 0);
+    }
 };
 
 // ---- the start of a batch: seeded momenta and the photon's placement, one launch (cavmd_thermalize_kernel.hpp) ----------------
@@ -85,6 +101,11 @@ struct cavmd_thermalize : StateTable<cavmd_thermalize_item, ThermalizeRow, Therm
         : StateTable(cavmd_thermalize_item_check, [](const cavmd_thermalize_item& it) { return it.N; },
                      uploaded_as_it_is<cavmd_thermalize_item, ThermalizeRow>)
     {
+    }
+
+    cavmd_snapshot_header snapshot_shape() const
+    {
+        return state_shape(CAVMD_SNAPSHOT_THERMALIZE, 0, 0);
     }
 };
 
@@ -278,6 +299,27 @@ int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_state** ou
     return v ? v->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
 }
 
+// (the one snapshot entry point that belongs to no object: host arithmetic, cavmd_snapshot.hpp)
+int cavmd_snapshot_check(const void* blob, size_t bytes, const cavmd_snapshot_header* expected)
+{
+    return snapshot_check(blob, bytes, expected);
+}
+
+int cavmd_snapshot_verlet_bytes(cavmd_verlet* v, size_t* bytes)
+{
+    return snapshot_bytes(v, bytes);
+}
+
+int cavmd_snapshot_verlet_save(cavmd_verlet* v, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(v, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_verlet_load(cavmd_verlet* v, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(v, (hipStream_t)stream_, h_in, bytes);
+}
+
 // ---- cavmd_draw ------------------------------------------------------------------------------------------------------------
 int cavmd_draw_item_check(const cavmd_draw_item* it)
 {
@@ -341,6 +383,21 @@ int cavmd_draw_reset(cavmd_draw* d, void* stream_)
 int cavmd_draw_state_device_ptr(cavmd_draw* d, const cavmd_draw_state** out)
 {
     return d ? d->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_snapshot_draw_bytes(cavmd_draw* d, size_t* bytes)
+{
+    return snapshot_bytes(d, bytes);
+}
+
+int cavmd_snapshot_draw_save(cavmd_draw* d, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(d, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_draw_load(cavmd_draw* d, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(d, (hipStream_t)stream_, h_in, bytes);
 }
 
 // ---- cavmd_bath ------------------------------------------------------------------------------------------------------------
@@ -410,6 +467,21 @@ int cavmd_bath_reset(cavmd_bath* b, void* stream_)
 int cavmd_bath_state_device_ptr(cavmd_bath* b, const cavmd_bath_state** out)
 {
     return b ? b->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_snapshot_bath_bytes(cavmd_bath* b, size_t* bytes)
+{
+    return snapshot_bytes(b, bytes);
+}
+
+int cavmd_snapshot_bath_save(cavmd_bath* b, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(b, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_bath_load(cavmd_bath* b, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(b, (hipStream_t)stream_, h_in, bytes);
 }
 
 // ---- cavmd_thermalize ------------------------------------------------------------------------------------------------------
@@ -489,6 +561,21 @@ int cavmd_thermalize_reset(cavmd_thermalize* t, void* stream_)
 int cavmd_thermalize_state_device_ptr(cavmd_thermalize* t, const cavmd_thermalize_state** out)
 {
     return t ? t->state_device_ptr(out) : CAVMD_ERR_INVALID_VALUE;
+}
+
+int cavmd_snapshot_thermalize_bytes(cavmd_thermalize* t, size_t* bytes)
+{
+    return snapshot_bytes(t, bytes);
+}
+
+int cavmd_snapshot_thermalize_save(cavmd_thermalize* t, void* stream_, void* h_out, size_t bytes)
+{
+    return snapshot_save(t, (hipStream_t)stream_, h_out, bytes);
+}
+
+int cavmd_snapshot_thermalize_load(cavmd_thermalize* t, void* stream_, const void* h_in, size_t bytes)
+{
+    return snapshot_load(t, (hipStream_t)stream_, h_in, bytes);
 }
 
 } // extern "C"

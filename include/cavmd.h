@@ -480,7 +480,8 @@ CAVMD_API int cavmd_bussi_batch_step(cavmd_bussi_batch* b, void* stream, const c
 CAVMD_API int cavmd_bussi_batch_last_sequence(cavmd_bussi_batch* b, uint64_t* out);
 /* out = n_items states after the last enqueued step: waits for the n_items stamps of THAT step only (every workgroup stamps
  * its item's host block after its velocity stores have been issued; a skipped item is stamped too and keeps its earlier
- * state), or for that step's stream to be idle; never a stream synchronisation.  Before any step: zeros.
+ * state), or for that step's stream to be idle; never a stream synchronisation.  Before any step: zeros (after a
+ * cavmd_snapshot_bussi_batch_load: the loaded states, copied from the device).
  * CAVMD_ERR_BAD_PARAMS, ONCE, if a step of any item was refused for zero kinetic energy since the last read; `out` is filled
  * all the same (per item: `refused`).  Once the batch has seen a capturing stream the stamps cannot be trusted (a replay
  * carries the sequence of its capture): the read then copies the device states behind a hipDeviceSynchronize, as
@@ -1544,6 +1545,110 @@ CAVMD_API int cavmd_profile_read(cavmd_workspace* ws, double ms[3], uint64_t* la
  * milliseconds (oldest first) into out[3 * cap] and stores the count in *n.  Call BEFORE cavmd_profile_read, which
  * clears them.  At most the last 4096 evaluations are kept. */
 CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap, size_t* n);
+
+/* ---- save and restore: what the objects of a batch run hold on the device, written out and put back, same bits -------------- */
+/* A run of the captured step can be stopped between two replays and taken up in another process: every state that launches
+ * write can be copied to HOST memory as one blob per object and copied back into an object of the same shape.  Nine objects
+ * hold such state: cavmd_verlet, cavmd_bath, cavmd_draw, cavmd_thermalize and cavmd_bussi_batch one state per item;
+ * cavmd_recorder, cavmd_ledger and cavmd_trajectory the counter words and the ring; cavmd_field_recorder those and the stored
+ * fields and references.  Each has three calls, cavmd_snapshot_<object>_bytes / _save / _load, which add no kernel and launch
+ * none: a synchronise and copies.
+ *
+ * A blob is a cavmd_snapshot_header followed by the object's device arrays VERBATIM, in this order, each section padded with
+ * zero bytes to a multiple of 16:
+ *   verlet, bath, draw, thermalize, bussi_batch   the n_items states (cavmd_*_state as cavmd_*_read gives them; for the
+ *                                                 thermostat batch cavmd_bussi_device_state)
+ *   recorder, ledger, trajectory                  the n_counters x n_items counter words (n_counters arrays of n_items, rows
+ *                                                 written first), then the WHOLE ring of n_items x capacity x record_bytes
+ *                                                 bytes, item-major by slot; slots never written are the zeros of creation
+ *   field_recorder                                those two, then the row of every reference (n_items x max_references words),
+ *                                                 the field of the last recorded call (n_items x n_k x 2 doubles) and the
+ *                                                 references (n_items x max_references x n_k x 2 doubles)
+ * Because the arrays are copied as they are, after a load every read, rows and read_fields answers what it answered when the
+ * blob was saved, by the rules it always had, and the next launch continues from there bit for bit.
+ *
+ * bytes  depends on the object's shape alone (the header's words); no synchronise, no device access.
+ * save   synchronises `stream` (CAVMD_ERR_INVALID_VALUE while it is being captured, as cavmd_*_read), then writes header and
+ *        sections to h_out.  `bytes` must be what cavmd_snapshot_<object>_bytes gives.  Nothing of the object changes.
+ * load   CAVMD_ERR_INVALID_VALUE while `stream` is being captured and for a blob cavmd_snapshot_check refuses against the
+ *        object's own shape, both before anything is touched; then waits for the object's launches in flight as
+ *        cavmd_*_set_items does (CAVMD_ERR_INVALID_VALUE while that stream is being captured) and for `stream`, copies host to
+ *        device and returns with the copy complete.  A refused load leaves the object as it was; a copy the runtime fails
+ *        half-way leaves the sections already written.  Device addresses do not change: a graph captured before a load
+ *        replays on the loaded state, and cavmd_*_device_ptr consumers stay valid.  For the thermostat batch the refusals
+ *        counted in the loaded states count as reported (the next cavmd_bussi_batch_read does not answer
+ *        CAVMD_ERR_BAD_PARAMS for them), cavmd_bussi_batch_read answers the loaded states also before the first step, and
+ *        the host's sequence keeps counting from where it is.
+ * A null object, a null buffer or a null `bytes` is CAVMD_ERR_INVALID_VALUE.
+ *
+ * NOT in a snapshot, and the caller's to recreate with the same arguments before a load: the item tables (every device
+ * pointer of an item is of the new process), seeds given per item (cavmd_bath_item, cavmd_thermalize_item), periods,
+ * intervals, kB, wavevectors and every other parameter of create.  The draw object's seed is in the header, so a blob of
+ * another seed is refused.  cavmd_batch, cavmd_molecular and cavmd_coulomb keep nothing between launches that a later launch
+ * reads, so they have no snapshot.  Result-history sequence numbers and cavmd_record.eval_sequence restart in a new process
+ * (they are diagnostic).  Host-side generators that made input rows are the caller's.  The arrays the items point to
+ * (positions, images, velocities, accelerations, input rows) are the caller's memory: save and restore them next to the blobs;
+ * the accelerations cannot be recomputed after a step with a bath, they contain its random force. */
+#define CAVMD_SNAPSHOT_MAGIC 0x3150414E53564143ull /* "CAVSNAP1" read as a little-endian word */
+#define CAVMD_SNAPSHOT_VERSION 1u
+#define CAVMD_SNAPSHOT_VERLET 1u
+#define CAVMD_SNAPSHOT_BATH 2u
+#define CAVMD_SNAPSHOT_DRAW 3u
+#define CAVMD_SNAPSHOT_THERMALIZE 4u
+#define CAVMD_SNAPSHOT_BUSSI_BATCH 5u
+#define CAVMD_SNAPSHOT_RECORDER 6u
+#define CAVMD_SNAPSHOT_LEDGER 7u
+#define CAVMD_SNAPSHOT_TRAJECTORY 8u
+#define CAVMD_SNAPSHOT_FIELD_RECORDER 9u
+
+typedef struct cavmd_snapshot_header     /* 64 B at the start of every blob; every field native-endian */
+{
+    uint64_t magic;           /* CAVMD_SNAPSHOT_MAGIC */
+    uint32_t version;         /* CAVMD_SNAPSHOT_VERSION */
+    uint32_t kind;            /* CAVMD_SNAPSHOT_*: the object the blob was saved from */
+    uint32_t n_items;
+    uint32_t n_counters;      /* counter words per item of a series object; 0 for a state object */
+    uint64_t capacity;        /* rows per item of a series object; 0 for a state object */
+    uint64_t record_bytes;    /* bytes of one record (for the trajectory: of one frame); for a state object of one state */
+    uint32_t word[2];         /* field_recorder: n_k, max_references; trajectory: max_N, format; draw: the seed's low and high
+                                 half; 0, 0 otherwise */
+    uint64_t bytes;           /* of the whole blob, this header included */
+    uint32_t reserved[2];     /* must be 0 */
+} cavmd_snapshot_header;
+
+/* Host arithmetic only, needs no device: CAVMD_OK if the `bytes` bytes at `blob` begin with a header that load would accept
+ * for an object whose cavmd_snapshot_<object>_bytes / _save header is *expected; CAVMD_ERR_INVALID_VALUE for a null pointer,
+ * bytes shorter than the header or different from the header's `bytes`, a wrong magic, version or kind, any shape word
+ * (n_items, n_counters, capacity, record_bytes, word[0], word[1], bytes) that differs from *expected, and reserved words that
+ * are not 0.  Reads the first 64 bytes of the blob only; the blob need not be aligned. */
+CAVMD_API int cavmd_snapshot_check(const void* blob, size_t bytes, const cavmd_snapshot_header* expected);
+CAVMD_API int cavmd_snapshot_verlet_bytes(cavmd_verlet* v, size_t* bytes);
+CAVMD_API int cavmd_snapshot_verlet_save(cavmd_verlet* v, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_verlet_load(cavmd_verlet* v, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_bath_bytes(cavmd_bath* b, size_t* bytes);
+CAVMD_API int cavmd_snapshot_bath_save(cavmd_bath* b, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_bath_load(cavmd_bath* b, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_draw_bytes(cavmd_draw* d, size_t* bytes);
+CAVMD_API int cavmd_snapshot_draw_save(cavmd_draw* d, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_draw_load(cavmd_draw* d, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_thermalize_bytes(cavmd_thermalize* t, size_t* bytes);
+CAVMD_API int cavmd_snapshot_thermalize_save(cavmd_thermalize* t, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_thermalize_load(cavmd_thermalize* t, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_bussi_batch_bytes(cavmd_bussi_batch* b, size_t* bytes);
+CAVMD_API int cavmd_snapshot_bussi_batch_save(cavmd_bussi_batch* b, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_bussi_batch_load(cavmd_bussi_batch* b, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_recorder_bytes(cavmd_recorder* r, size_t* bytes);
+CAVMD_API int cavmd_snapshot_recorder_save(cavmd_recorder* r, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_recorder_load(cavmd_recorder* r, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_ledger_bytes(cavmd_ledger* l, size_t* bytes);
+CAVMD_API int cavmd_snapshot_ledger_save(cavmd_ledger* l, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_ledger_load(cavmd_ledger* l, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_trajectory_bytes(cavmd_trajectory* t, size_t* bytes);
+CAVMD_API int cavmd_snapshot_trajectory_save(cavmd_trajectory* t, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_trajectory_load(cavmd_trajectory* t, void* stream, const void* h_in, size_t bytes);
+CAVMD_API int cavmd_snapshot_field_recorder_bytes(cavmd_field_recorder* r, size_t* bytes);
+CAVMD_API int cavmd_snapshot_field_recorder_save(cavmd_field_recorder* r, void* stream, void* h_out, size_t bytes);
+CAVMD_API int cavmd_snapshot_field_recorder_load(cavmd_field_recorder* r, void* stream, const void* h_in, size_t bytes);
 
 /* ---- tuning / introspection ------------------------------------------------------------------- */
 /* Launch knobs (for A/B measurements; the defaults are the measured best on MI355X).  name is one of
