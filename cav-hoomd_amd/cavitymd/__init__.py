@@ -22,13 +22,14 @@ from .thermalize_batch import BatchThermalizer
 from .ledger import BatchEnergyLedger
 from .trajectory import BatchTrajectoryRecorder
 from .checkpoint import BatchCheckpoint
+from .run_clock import run_until_finished
 from .molecular_batch import MolecularForceBatch
 from .coulomb_batch import CoulombForceBatch
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, bath_batch, checkpoint, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats, trajectory
+from . import _capi, bath_batch, checkpoint, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, run_clock, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats, trajectory
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "BatchTrajectoryRecorder", "BatchCheckpoint", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "bath_batch", "checkpoint", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats", "trajectory",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "BatchTrajectoryRecorder", "BatchCheckpoint", "run_until_finished", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "bath_batch", "checkpoint", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "run_clock", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats", "trajectory",
 ]
 __version__ = "0.1.0"

@@ -610,6 +610,10 @@ _PROTOTYPES = {
     "cavmd_snapshot_field_recorder_load": (_ci, [_vp, _vp, _vp, _sz]),
     "cavmd_set_tunable": (_ci, [_vp, _cstr, _ci]),
     "cavmd_get_tunable": (_ci, [_vp, _cstr, _P(_ci)]),
+    "cavmd_runclock_draw_set_end": (_ci, [_vp, _sz, _sz, _P(_dbl)]),
+    "cavmd_runclock_draw_finished": (_ci, [_vp, _vp, _P(_u64)]),
+    "cavmd_runclock_ledger_set_rule": (_ci, [_vp, _dbl, _dbl]),
+    "cavmd_runclock_field_set_rule": (_ci, [_vp, _vp, _u64, _dbl, _dbl]),
     "cavmd_device_info": (_ci, [_vp, _P(_ci), _P(_ci), _cstr, _sz]),
     "cavmd_error_string": (_cstr, [_ci]),
     "cavmd_version": (_ci, []),
@@ -1268,6 +1272,13 @@ class FieldRecorder(_SeriesHandle):
         check(self._lib.cavmd_field_recorder_record(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(take_reference_ptr)),
               "cavmd_field_recorder_record")
 
+    def set_time_rule(self, time0_ptr: int, stride_bytes: int, time_interval: float, reference_time_interval: float = 0.0) -> None:
+        """Rows (and, with reference_time_interval > 0, references) by each item's own clock: the double at device address
+        time0_ptr + item * stride_bytes.  time_interval 0 switches the rule off.  Set it before a capture."""
+        check(self._lib.cavmd_runclock_field_set_rule(self._h, ctypes.c_void_p(int(time0_ptr)), int(stride_bytes),
+                                                      float(time_interval), float(reference_time_interval)),
+              "cavmd_runclock_field_set_rule")
+
     def read_fields(self, stream: int, item: int):
         """(rho_now, rho_refs, ref_rows) of one item after synchronising `stream`: complex arrays of shape (n_k,) and
         (n_refs, n_k), and the row each reference was taken at."""
@@ -1376,6 +1387,12 @@ class Ledger(_SeriesHandle):
         """One kernel: every item's call counter moves; on every period-th call the item appends one row."""
         check(self._lib.cavmd_ledger_record(self._h, ctypes.c_void_p(stream)), "cavmd_ledger_record")
 
+    def set_time_rule(self, time_interval: float, max_time: float = 0.0) -> None:
+        """Rows by each item's own clock (``d_time``): a row where the clock moved by time_interval since the item's last
+        one, none past max_time (0: no last time).  time_interval 0 switches the rule off.  Set it before a capture."""
+        check(self._lib.cavmd_runclock_ledger_set_rule(self._h, float(time_interval), float(max_time)),
+              "cavmd_runclock_ledger_set_rule")
+
 
 class Draw(_StateHandle):
     """Owns one cavmd_draw: the integrator's and the thermostat's input rows of B independent small systems written by ONE
@@ -1393,6 +1410,18 @@ class Draw(_StateHandle):
     def fill(self, stream: int = 0) -> None:
         """One kernel: both input rows, the counters and the dt of every item."""
         check(self._lib.cavmd_draw_fill(self._h, ctypes.c_void_p(stream)), "cavmd_draw_fill")
+
+    def set_end(self, first: int, t_end) -> None:
+        """End times of items first .. first + len(t_end) - 1 (0: none); an item whose ``elapsed`` has reached its own rests."""
+        values = [float(t) for t in t_end]
+        check(self._lib.cavmd_runclock_draw_set_end(self._h, int(first), len(values), (ctypes.c_double * max(len(values), 1))(*values)),
+              "cavmd_runclock_draw_set_end")
+
+    def finished(self, stream: int = 0) -> int:
+        """How many items rest behind their end time, after synchronising `stream`."""
+        n = ctypes.c_uint64()
+        check(self._lib.cavmd_runclock_draw_finished(self._h, ctypes.c_void_p(stream), ctypes.byref(n)), "cavmd_runclock_draw_finished")
+        return int(n.value)
 
 
 def molecular_order(lib=None):

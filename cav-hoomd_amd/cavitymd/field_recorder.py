@@ -19,14 +19,28 @@ so ``record()`` captured into a graph next to ``CavityForceBatch.compute``, ``Ba
     series = fields.read()                # (B, steps) structured array, one copy, behind one synchronisation
     series["F"][:, :, 0]                  # F(k,t) of every system against its first reference
 
-``reference_interval`` counts recorded rows.  The reference's time-based ``reference_interval_ps`` under an adaptive timestep
-is the caller's policy: keep a uint32 tensor of B words on the device, set a word when that replica's clock passes its next
-reference time, and hand the tensor to ``record(take_reference=...)``; it is read when the kernel runs.  That clock exists
-on the device since ``StepDraw``: ``elapsed`` of its state (``cavmd_draw_state_device_ptr``) is the sum of every dt handed out.
+``period`` counts calls and ``reference_interval`` counts recorded rows.  Under an adaptive timestep the reference tracker
+goes by TIME instead (``--fkt-output-period-ps`` and ``--fkt-ref-interval``, its "PREFERRED for adaptive mode" rule,
+src/cavitymd/analysis.py:366-378), and so does this class once ``set_time_rule`` was called with the ``StepDraw`` whose
+``elapsed`` is every system's clock on the device::
+
+    fields = BatchFieldRecorder(positions, kmag=1.0, reference_interval=0)
+    fields.set_time_rule(draw, time_interval=period, reference_time_interval=ref_period)      # BEFORE the capture
+    ...
+    series = fields.read()
+    series["time"]                        # the clock of every row
+    fields.lag_times(series)              # (B, n, max_references): time of the row minus time of the reference's row
+
+A row is then written on a system's first ``record()`` and whenever its clock has moved by ``time_interval`` since its last
+row; a reference is taken (after the correlation, as always) with the first row, when ``take_reference`` asks, and whenever
+the clock has moved by ``reference_time_interval`` since the system's last reference of any cause.  A system at rest behind
+its end time (``StepDraw.set_end_time``) writes nothing more.  ``take_reference`` stays for any other policy of the caller's.
 
 There is no CPU fallback: CPU tensors raise.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -35,6 +49,16 @@ from . import _capi
 from ._device import device_tensor, one_device, stream_handle
 from .recorder import _SeriesRecorder
 from .observables import generate_fibonacci_sphere
+
+
+def _record_dtype() -> np.dtype:
+    """cavmd_field_record's dtype with ``time`` as one more field, at the offset of ``reserved``"""
+    base = _capi.field_record_dtype()
+    return np.dtype({"names": list(base.names) + ["time"], "formats": [base.fields[n][0] for n in base.names] + [np.dtype("<f8")],
+                     "offsets": [base.fields[n][1] for n in base.names] + [base.fields["reserved"][1]], "itemsize": base.itemsize})
+
+
+_RECORD_DTYPE = _record_dtype()
 
 
 class BatchFieldRecorder(_SeriesRecorder):
@@ -86,8 +110,55 @@ class BatchFieldRecorder(_SeriesRecorder):
     def read(self, first=0, count=None, stream=None) -> np.ndarray:
         """Structured array of shape (B, n), dtype mirroring ``cavmd_field_record``: rows first .. first + count - 1 (0-based
         count of recorded rows) of every system; ``first=None`` starts at the oldest row still held.  Waits for the device
-        (or, if given, for ``stream`` only); works the same before, between and after the replays of a graph."""
-        return self._read(first, count, stream)
+        (or, if given, for ``stream`` only); works the same before, between and after the replays of a graph.  ``time`` is
+        the record's ``reserved`` double under its name: the system's clock at the row under a time rule, 0 without one."""
+        return self._read(first, count, stream).view(_RECORD_DTYPE)
+
+    def set_time_rule(self, clock, time_interval, reference_time_interval=None) -> None:
+        """clock: the ``StepDraw`` of the same B systems (its ``elapsed`` is read on the device when the kernel runs), or a
+        contiguous (B,) float64 device tensor of clocks.  time_interval: a row whenever a system's clock has moved by this much
+        since its last row (the recorder must have ``period == 1``); None or 0 switches the rule off.
+        reference_time_interval: None or 0 keeps ``reference_interval`` (recorded rows); otherwise a reference whenever the
+        clock has moved by this much since the system's last reference.  Set it BEFORE ``record()`` is captured: the rule is
+        frozen into a captured launch.  Never inside a capture."""
+        on = bool(time_interval)
+        ptr = stride = 0
+        if on:
+            if isinstance(clock, torch.Tensor):
+                if clock.device.type != "cuda":
+                    raise RuntimeError("BatchFieldRecorder.set_time_rule needs the clocks in GPU memory; no CPU fallback exists "
+                                       "in this package")
+                if clock.dtype != torch.float64 or clock.shape != (self.n_systems,) or not clock.is_contiguous():
+                    raise ValueError(f"a clock tensor must be a contiguous ({self.n_systems},) float64 tensor")
+                ptr, stride = clock.data_ptr(), 8
+            else:
+                if getattr(clock, "n_systems", None) != self.n_systems:
+                    raise ValueError(f"BatchFieldRecorder.set_time_rule: the clock of the same {self.n_systems} systems")
+                ptr = clock._need().state_device_ptr() + _capi.DrawState.elapsed.offset
+                stride = ctypes.sizeof(_capi.DrawState)
+        self._need().set_time_rule(ptr, stride, float(time_interval) if on else 0.0,
+                                   float(reference_time_interval) if (on and reference_time_interval) else 0.0)
+        self._clock = clock if on else None   # kept alive for the kernel
+
+    def lag_times(self, series) -> np.ndarray:
+        """(B, n, max_references) float64: for every row of ``series`` (what ``read()`` gave) and every reference it was
+        correlated with, ``time`` of the row minus ``time`` of the row that took the reference (that row has
+        ``took_reference`` and ``n_references == r``); NaN where a row has no such reference.  Raises where the row that took a
+        reference a later row of ``series`` is correlated with is not in ``series`` (it has left the ring, or the slice starts
+        behind it)."""
+        B, n = series.shape
+        out = np.full((B, n, self.max_references), np.nan)
+        for b in range(B):
+            ref_time = {}
+            for j in range(n):
+                row = series[b, j]
+                for r in range(int(row["n_references"])):
+                    if r not in ref_time:
+                        raise ValueError(f"system {b}: the row that took reference {r} is not among the rows given")
+                    out[b, j, r] = row["time"] - ref_time[r]
+                if row["took_reference"]:
+                    ref_time[int(row["n_references"])] = float(row["time"])
+        return out
 
     def fields(self, item: int, stream=None):
         """(rho_now, rho_refs, ref_rows) of one system: the field of its last recorded call (complex, (n_k,)), its stored

@@ -215,6 +215,18 @@ class BatchEnergyLedger(_SeriesRecorder):
         after the replays of a graph, never inside a capture."""
         return self._read(first, count, stream).view(self._named_dtype)
 
+    def set_time_rule(self, time_interval, max_time=None) -> None:
+        """Rows by every system's own clock instead of by calls -- the reference's ``--energy-output-period-ps`` and
+        ``--max-energy-output-time`` (``EnergyTracker``, src/cavitymd/analysis.py:692-701) under an adaptive dt: a system
+        writes a row on its first ``record()`` and then whenever its clock has moved by ``time_interval`` since its last
+        row, and none once the clock is past ``max_time`` (None or 0: no last time).  The clock is the ``clock=`` the ledger
+        was built with, in its units; the ledger must have ``period == 1``.  ``time_interval`` None or 0 switches the rule
+        off.  Set it BEFORE ``record()`` is captured: the rule is frozen into a captured launch.  A system at rest behind its
+        end time (``StepDraw.set_end_time``) stops writing rows by itself.  Never inside a capture."""
+        if self._kept[-1] is None and time_interval:
+            raise ValueError("BatchEnergyLedger.set_time_rule needs the clock= the ledger is built with")
+        self._need().set_time_rule(0.0 if time_interval is None else float(time_interval), 0.0 if max_time is None else float(max_time))
+
     @property
     def ledger(self):
         return self._handle

@@ -36,6 +36,17 @@ _ROW_BYTES = 64
 _RECORD_BYTES = 128
 
 
+def _state_dtype() -> np.dtype:
+    """cavmd_draw_state's dtype with ``finished`` as one more field, at the offset of reserved[0]"""
+    base = _capi.draw_state_dtype()
+    names = list(base.names) + ["finished"]
+    return np.dtype({"names": names, "formats": [base.fields[n][0] for n in base.names] + [np.dtype("<u8")],
+                     "offsets": [base.fields[n][1] for n in base.names] + [base.fields["reserved"][1]], "itemsize": base.itemsize})
+
+
+_STATE_DTYPE = _state_dtype()
+
+
 def _inputs_of(owner, what: str):
     """The (B, 8) float64 device tensor a destination stands for: the ``inputs`` of a batch object, or the tensor itself."""
     t = getattr(owner, "inputs", owner)
@@ -121,12 +132,36 @@ class StepDraw(HandleOwner, Checkpointable):
         self._stream = handle
 
     def state(self, stream=None) -> np.ndarray:
-        """Per-system ``draws``, ``dt``, ``elapsed``, ``tolerance``, ``exhausted``.  Default: waits for the whole device (a
-        graph replays on the stream it is launched on), then reads; never inside a capture."""
+        """Per-system ``draws``, ``dt``, ``elapsed``, ``tolerance``, ``exhausted``, ``finished`` (1 while the system rests
+        behind its end time; the first of the three ``reserved`` words, under its name).  Default: waits for the whole device
+        (a graph replays on the stream it is launched on), then reads; never inside a capture."""
         draw = self._need()
         if stream is None:
             torch.cuda.synchronize(self._device)
-        return draw.read(stream_handle(stream, self._dev_index))
+        return draw.read(stream_handle(stream, self._dev_index)).view(_STATE_DTYPE)
+
+    def set_end_time(self, t_end) -> None:
+        """The end of the run by every system's own clock: one number, or one per system, in the units of ``elapsed``; None
+        or 0: no end.  From the ``fill()`` that finds ``elapsed >= t_end`` on, a system is at rest: its rows carry dt = 0 and
+        ``skip``, so the integrator, the bath and the thermostat leave it untouched, it draws no block and its clock stands
+        still -- the reference's ``ElapsedTimeTracker`` (src/cavitymd/analysis.py:1230-1259), per system and without a
+        read-back.  The last step is not clamped onto t_end.  A larger t_end given later lets a system go on, bit for bit as if
+        it had had that end time from the start.  Call it before ``fill()`` is captured: a graph captured before the FIRST
+        call keeps launching the kernel that knows no end times; later calls change values a captured launch reads.  Waits
+        for the stream of the last ``fill()``; never inside a capture."""
+        values = per_system(0.0 if t_end is None else t_end, self.n_systems, "t_end")
+        self._need().set_end(0, [0.0 if v is None else float(v) for v in values])
+
+    def finished(self, stream=None) -> np.ndarray:
+        """(B,) bool: which systems rest behind their end time.  Waits as ``state()`` does."""
+        return self.state(stream)["finished"] != 0
+
+    def n_finished(self, stream=None) -> int:
+        """How many systems rest behind their end time: one synchronisation and one small copy (``run_until_finished``)."""
+        draw = self._need()
+        if stream is None:
+            torch.cuda.synchronize(self._device)
+        return draw.finished(stream_handle(stream, self._dev_index))
 
     def reset(self, stream=None) -> None:
         """Zero every system's counters, ordered on ``stream`` (default: torch's current stream): the next ``fill`` draws the

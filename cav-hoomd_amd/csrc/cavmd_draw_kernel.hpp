@@ -66,7 +66,8 @@ struct DrawState
     uint64_t draws;
     double dt, elapsed, tolerance;
     uint64_t exhausted;
-    uint64_t pad[3];
+    uint64_t finished; // cavmd_draw_state.reserved[0]: 1 while the item is at rest behind its end time
+    uint64_t pad[2];
 };
 static_assert(sizeof(DrawState) == 64, "one draw state = 64 bytes");
 
@@ -140,90 +141,22 @@ __device__ __forceinline__ double draw_gamma_ge1(const DrawStream& s, double a, 
     return out;
 }
 
+// Both kernels have one body, cavmd_draw_fill_body.inc.  The first is the kernel of an object without end times, as it was
+// before there were any; the second is launched once cavmd_runclock_draw_set_end was called (t_end_all: n_items doubles).
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void draw_fill_kernel(const DrawRow* __restrict__ rows, unsigned n_items, unsigned seed_lo,
                                                           unsigned seed_hi, DrawState* __restrict__ state_all)
 {
-    const unsigned item = blockIdx.x * BLOCK + threadIdx.x;
-    if (item >= n_items) // the partly empty last workgroup
-        return;
-    const DrawRow r = rows[item];
-    DrawState st = state_all[item];
-    const bool adaptive = r.records != nullptr;
-    const uint64_t recorded = adaptive ? *r.rows : 0;
-    double S = 0.0;
-    if (recorded != 0)
-        S = r.records[(recorded - 1) % r.capacity].force_mass_sum;
+    constexpr bool END = false;
+    const double* const t_end_all = nullptr;
+#include "cavmd_draw_fill_body.inc"
+}
 
-    // ---- the time step ------------------------------------------------------------------------------------------------------
-    double dt = r.dt_initial, coeff = r.fixed_coeff, c = r.fixed_c, tolerance = 0.0;
-    if (adaptive)
-    {
-        tolerance = r.tol_target;
-        if (r.tol_time_constant != 0.0)
-            tolerance = r.tol_target - (r.tol_target - r.tol_initial) * exp(-st.elapsed / r.tol_time_constant);
-        if (recorded != 0)
-        {
-            dt = st.draws != 0 ? st.dt : r.dt_initial; // the last dt used
-            if (S > 0.0 && S <= 0x1.fffffffffffffp+1023) // the reference's `if force_mass_sum > 0`, and finite
-            {
-                dt = sqrt(tolerance / S);
-                dt = dt < r.dt_min ? r.dt_min : dt;
-                dt = dt > r.dt_max ? r.dt_max : dt;
-            }
-        }
-        coeff = (r.gamma != 0.0 && dt != 0.0) ? sqrt(((6.0 * r.gamma) * r.kT) / dt) : 0.0;
-        c = r.tau != 0.0 ? exp(-dt / r.tau) : 0.0;
-    }
-    const double skip = __longlong_as_double(dt == 0.0 ? 1ll : 0ll);
-
-    // ---- the variates -------------------------------------------------------------------------------------------------------
-    const DrawStream s = {(unsigned)st.draws, (unsigned)(st.draws >> 32), item, make_uint2(seed_lo, seed_hi)};
-    if (r.verlet_row)
-    {
-        const uint4 xy = s.block(kDrawPurposeLangevinXY);
-        const uint4 z = s.block(kDrawPurposeLangevinZ);
-        double* out = r.verlet_row;
-        out[0] = dt;
-        out[1] = r.gamma;
-        out[2] = coeff;
-        out[3] = 2.0 * draw_unit(xy.x, xy.y) - 1.0;
-        out[4] = 2.0 * draw_unit(xy.z, xy.w) - 1.0;
-        out[5] = 2.0 * draw_unit(z.x, z.y) - 1.0;
-        out[6] = skip;
-        out[7] = 0.0;
-    }
-    if (r.bussi_row)
-    {
-        double normal = 0.0, gamma_variate = 0.0;
-        if (r.dof != 0.0)
-            normal = s.normal(kDrawPurposeNormal);
-        if (r.dof > 1.0)
-        {
-            const double a = (r.dof - 1.0) / 2.0;
-            if (a >= 1.0)
-                gamma_variate = draw_gamma_ge1(s, a, &st.exhausted);
-            else
-            {
-                const uint4 w = s.block(kDrawPurposeBoost);
-                gamma_variate = draw_gamma_ge1(s, a + 1.0, &st.exhausted) * exp(log(draw_log_arg(w.x, w.y)) / a); // u^(1/a)
-            }
-        }
-        double* out = r.bussi_row;
-        out[0] = normal;
-        out[1] = gamma_variate;
-        out[2] = c;
-        out[3] = r.set_T;
-        out[4] = skip;
-        out[5] = 0.0;
-        out[6] = 0.0;
-        out[7] = 0.0;
-    }
-
-    st.draws += 1;
-    st.dt = dt;
-    st.elapsed = st.elapsed + dt;
-    st.tolerance = tolerance;
-    state_all[item] = st;
+template <int BLOCK, bool END>
+__global__ __launch_bounds__(BLOCK) void draw_fill_kernel(const DrawRow* __restrict__ rows, unsigned n_items, unsigned seed_lo,
+                                                          unsigned seed_hi, DrawState* __restrict__ state_all,
+                                                          const double* __restrict__ t_end_all)
+{
+#include "cavmd_draw_fill_body.inc"
 }
 } // namespace cavmd

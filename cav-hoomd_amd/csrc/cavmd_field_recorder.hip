@@ -27,6 +27,11 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
     DeviceArray<uint64_t> d_ref_rows; // n x max_refs: the row each reference was taken at
     DeviceArray<double> d_now;        // n x n_k x 2: the field of the last recorded call
     DeviceArray<double> d_refs;       // n x max_refs x n_k x 2
+    // the run clock's time rule (cavmd_runclock_field_set_rule); time_interval 0: off.  The values the kernel reads are in d_rule.
+    double time_interval = 0.0;
+    DeviceArray<double> d_rule;       // a FieldRule, then last_time (n) and last_reference_time (n): beside the counters, the
+                                      // time words zero from the first rule on
+    double* times() const { return d_rule.ptr + sizeof(FieldRule) / sizeof(double); }
 
     cavmd_field_recorder()
         : SeriesTable(kFldCounters, cavmd_field_recorder_item_check, [](const cavmd_field_item& it) { return it.N; },
@@ -58,7 +63,9 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
     // the series' two arrays, then what the object keeps beyond them (the wavevectors are create's, not state)
     cavmd_snapshot_header snapshot_shape() const
     {
-        return series_shape(CAVMD_SNAPSHOT_FIELD_RECORDER, (uint32_t)n_k, max_refs);
+        // a blob taken under the rule says so above the reference count and carries the two time arrays as a sixth section
+        return series_shape(CAVMD_SNAPSHOT_FIELD_RECORDER, (uint32_t)n_k,
+                            max_refs | (time_interval > 0.0 ? cavmd::kSnapshotFieldTimed : 0u));
     }
     size_t snapshot_arrays(const void** arrays) const
     {
@@ -66,7 +73,20 @@ struct cavmd_field_recorder : SeriesTable<cavmd_field_item, FieldRow, cavmd_fiel
         arrays[first] = d_ref_rows.ptr;
         arrays[first + 1] = d_now.ptr;
         arrays[first + 2] = d_refs.ptr;
-        return first + 3;
+        if (time_interval == 0.0)
+            return first + 3;
+        arrays[first + 3] = times();
+        return first + 4;
+    }
+
+    int reset(hipStream_t stream)
+    {
+        const int st = SeriesTable::reset(stream);
+        if (st != CAVMD_OK || !d_rule.ptr)
+            return st;
+        DeviceGuard guard(device);
+        CAVMD_HIP_TRY(hipMemsetAsync(times(), 0, sizeof(double) * 2 * n, stream));
+        return CAVMD_OK;
     }
 };
 
@@ -136,10 +156,45 @@ int cavmd_field_recorder_record(cavmd_field_recorder* r, void* stream_, const ui
 {
     if (!r || ((uintptr_t)d_take_reference & 3))
         return CAVMD_ERR_INVALID_VALUE;
+    if (r->time_interval > 0.0) // the variant and the rule's values are launch arguments: frozen in a captured launch
+        return r->launch((hipStream_t)stream_, field_recorder_batch_kernel<256, true>, dim3((unsigned)r->n), dim3(256), 0,
+                         r->d_rows.ptr, r->d_order.ptr, (unsigned)r->n, r->d_kvec.ptr, (unsigned)r->n_k, make_sincos_coef(),
+                         (uint64_t)r->capacity, r->max_refs, r->interval, d_take_reference, r->d_series.ptr, r->d_counters.ptr,
+                         r->d_ref_rows.ptr, r->d_now.ptr, r->d_refs.ptr, reinterpret_cast<FieldRule*>(r->d_rule.ptr));
     return r->launch((hipStream_t)stream_, field_recorder_batch_kernel<256>, dim3((unsigned)r->n), dim3(256), 0, r->d_rows.ptr,
                      r->d_order.ptr, (unsigned)r->n, r->d_kvec.ptr, (unsigned)r->n_k, make_sincos_coef(), (uint64_t)r->capacity,
                      r->period, r->max_refs, r->interval, d_take_reference, r->d_series.ptr, r->d_counters.ptr, r->d_ref_rows.ptr,
                      r->d_now.ptr, r->d_refs.ptr);
+}
+
+// the run clock of cavmd_field_recorder (include/cavmd.h, "the run clock")
+int cavmd_runclock_field_set_rule(cavmd_field_recorder* r, const double* d_time0, uint64_t stride_bytes, double time_interval,
+                                  double reference_time_interval)
+{
+    if (!r || !finite_nonnegative(time_interval) || !finite_nonnegative(reference_time_interval)
+        || (time_interval == 0.0 && reference_time_interval != 0.0))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (time_interval > 0.0
+        && (!d_time0 || ((uintptr_t)d_time0 & 7) || stride_bytes < 8 || (stride_bytes & 7) || r->period != 1))
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(r->device);
+    const int st = r->wait_idle(); // as set_items: refused while the last stream is being captured
+    if (st != CAVMD_OK)
+        return st;
+    if (time_interval > 0.0)
+    {
+        const FieldRule rule {reinterpret_cast<const char*>(d_time0), stride_bytes, time_interval + 0.0, reference_time_interval + 0.0};
+        if (!r->d_rule.ptr)
+        {
+            std::vector<double> block(sizeof(rule) / sizeof(double) + 2 * r->n, 0.0);
+            memcpy(block.data(), &rule, sizeof(rule));
+            CAVMD_HIP_TRY(r->d_rule.upload(block.data(), block.size())); // a copy that has returned: no stream launches ahead of it
+        }
+        else
+            CAVMD_HIP_TRY(hipMemcpy(r->d_rule.ptr, &rule, sizeof(rule), hipMemcpyHostToDevice));
+    }
+    r->time_interval = time_interval + 0.0;
+    return CAVMD_OK;
 }
 
 int cavmd_field_recorder_rows(cavmd_field_recorder* r, void* stream_, uint64_t* out)

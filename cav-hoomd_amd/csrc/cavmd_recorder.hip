@@ -175,11 +175,45 @@ int cavmd_snapshot_recorder_load(cavmd_recorder* r, void* stream_, const void* h
 // ---- the energy ledger of a batch: every term of the conserved energy per step (cavmd_ledger_kernel.hpp) ----------------------
 struct cavmd_ledger : PeriodicSeries<cavmd_ledger_item, LedgerItem, cavmd_ledger_row> // the recorder's shape
 {
+    using Base = PeriodicSeries<cavmd_ledger_item, LedgerItem, cavmd_ledger_row>;
+    // the run clock's time rule (cavmd_runclock_ledger_set_rule); time_interval 0: off
+    double time_interval = 0.0, max_time = 0.0;
+    DeviceArray<double> d_last_time; // n words beside the counters, zero from the first rule on; written under the rule alone
+
     cavmd_ledger() : PeriodicSeries(cavmd_ledger_item_check) {}
 
+    // a blob taken under the rule says so in word 0 and carries last_time behind the ring
     cavmd_snapshot_header snapshot_shape() const
     {
-        return series_shape(CAVMD_SNAPSHOT_LEDGER, 0, 0);
+        return series_shape(CAVMD_SNAPSHOT_LEDGER, time_interval > 0.0 ? 1 : 0, 0);
+    }
+    size_t snapshot_arrays(const void** arrays) const
+    {
+        const size_t count = Base::snapshot_arrays(arrays);
+        if (time_interval == 0.0)
+            return count;
+        arrays[count] = d_last_time.ptr;
+        return count + 1;
+    }
+
+    // (hides ItemTable's: under the rule an item needs its clock)
+    int set_items(size_t first, size_t count, const cavmd_ledger_item* h_items)
+    {
+        if (time_interval > 0.0 && within(first, count, h_items))
+            for (size_t i = 0; i < count; ++i)
+                if (!h_items[i].d_time)
+                    return CAVMD_ERR_INVALID_VALUE;
+        return Base::set_items(first, count, h_items);
+    }
+
+    int reset(hipStream_t stream)
+    {
+        const int st = Base::reset(stream);
+        if (st != CAVMD_OK || !d_last_time.ptr)
+            return st;
+        DeviceGuard guard(device);
+        CAVMD_HIP_TRY(hipMemsetAsync(d_last_time.ptr, 0, sizeof(double) * n, stream));
+        return CAVMD_OK;
     }
 };
 
@@ -246,7 +280,40 @@ int cavmd_ledger_set_items(cavmd_ledger* l, size_t first, size_t count, const ca
 
 int cavmd_ledger_record(cavmd_ledger* l, void* stream_)
 {
-    return l ? l->record(stream_, ledger_batch_kernel<256>) : CAVMD_ERR_INVALID_VALUE;
+    if (!l)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (l->time_interval > 0.0) // the variant and the rule's values are launch arguments: frozen in a captured launch
+        return l->launch((hipStream_t)stream_, ledger_batch_kernel<256, true>, dim3((unsigned)l->n), dim3(256), 0, l->d_rows.ptr,
+                         l->d_order.ptr, (unsigned)l->n, (uint64_t)l->capacity, l->kB, l->d_series.ptr, l->d_counters.ptr,
+                         l->time_interval, l->max_time, l->d_last_time.ptr);
+    return l->record(stream_, ledger_batch_kernel<256>);
+}
+
+// the run clock of cavmd_ledger (include/cavmd.h, "the run clock")
+int cavmd_runclock_ledger_set_rule(cavmd_ledger* l, double time_interval, double max_time)
+{
+    if (!l || !finite_nonnegative(time_interval) || !finite_nonnegative(max_time) || (time_interval == 0.0 && max_time != 0.0))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (time_interval > 0.0)
+    {
+        if (l->period != 1)
+            return CAVMD_ERR_INVALID_VALUE;
+        for (const cavmd_ledger_item& it : l->items)
+            if (!it.d_time)
+                return CAVMD_ERR_INVALID_VALUE;
+    }
+    DeviceGuard guard(l->device);
+    const int st = l->wait_idle(); // as set_items: refused while the last stream is being captured
+    if (st != CAVMD_OK)
+        return st;
+    if (time_interval > 0.0 && !l->d_last_time.ptr)
+    {
+        const std::vector<double> zero(l->n, 0.0);
+        CAVMD_HIP_TRY(l->d_last_time.upload(zero.data(), l->n)); // a copy that has returned: no stream launches ahead of it
+    }
+    l->time_interval = time_interval + 0.0;
+    l->max_time = max_time + 0.0;
+    return CAVMD_OK;
 }
 
 int cavmd_ledger_rows(cavmd_ledger* l, void* stream_, uint64_t* out)

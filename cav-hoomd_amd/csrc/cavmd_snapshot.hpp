@@ -8,9 +8,12 @@
 //   a state object (verlet, bath, draw, thermalize, bussi_batch)   the n_items states of record_bytes each
 //   a series object (recorder, ledger, trajectory)                 n_counters x n_items counter words of 8 bytes, then the whole
 //                                                                  ring of n_items x capacity x record_bytes bytes
+//   a ledger under the run clock's time rule (word[0] = 1)         those two, then last_time (n_items doubles)
 //   the field recorder                                             a series object's two, then d_ref_rows (n_items x
 //                                                                  max_references words), d_now (n_items x n_k x 2 doubles) and
 //                                                                  d_refs (n_items x max_references x n_k x 2 doubles)
+//   the field recorder under the run clock's time rule             those five, then last_time and last_reference_time
+//   (word[1] = max_references | kSnapshotFieldTimed)                (2 x n_items doubles)
 #pragma once
 
 #include <stddef.h>
@@ -21,7 +24,8 @@
 
 namespace cavmd
 {
-constexpr size_t kSnapshotMaxSections = 5;
+constexpr size_t kSnapshotMaxSections = 6;
+constexpr uint32_t kSnapshotFieldTimed = 0x10000u; // in word[1] of a field recorder's header, above max_references (<= 16)
 
 inline uint64_t snapshot_pad16(uint64_t x)
 {
@@ -48,12 +52,23 @@ inline size_t snapshot_sections(const cavmd_snapshot_header& h, uint64_t sizes[k
     case CAVMD_SNAPSHOT_FIELD_RECORDER:
         sizes[0] = sizeof(uint64_t) * h.n_counters * n;
         sizes[1] = n * h.capacity * h.record_bytes;
+        if (h.kind == CAVMD_SNAPSHOT_LEDGER && h.word[0] != 0) // word[0] = 1: taken under the run clock's time rule
+        {
+            sizes[2] = sizeof(double) * n; // last_time
+            return 3;
+        }
         if (h.kind != CAVMD_SNAPSHOT_FIELD_RECORDER)
             return 2;
-        sizes[2] = sizeof(uint64_t) * n * h.word[1];                    // word[0] = n_k, word[1] = max_references
+    {
+        const uint64_t max_refs = h.word[1] & (kSnapshotFieldTimed - 1); // word[0] = n_k, word[1] = max_references (| timed)
+        sizes[2] = sizeof(uint64_t) * n * max_refs;
         sizes[3] = sizeof(double) * 2 * n * h.word[0];
-        sizes[4] = sizeof(double) * 2 * n * h.word[1] * h.word[0];
-        return 5;
+        sizes[4] = sizeof(double) * 2 * n * max_refs * h.word[0];
+        if (!(h.word[1] & kSnapshotFieldTimed))
+            return 5;
+        sizes[5] = sizeof(double) * 2 * n; // taken under the run clock's time rule: last_time, last_reference_time
+        return 6;
+    }
     default:
         return 0;
     }

@@ -65,6 +65,10 @@ static DrawRow draw_row(const cavmd_draw_item& it)
 struct cavmd_draw : StateTable<cavmd_draw_item, DrawRow, DrawState> // items cost the same: launched in item order
 {
     uint64_t seed = 0;
+    // the run clock's end times (cavmd_runclock_draw_set_end): none until the first call, which allocates the device array once
+    // and for good -- a captured launch reads the values its replay finds there
+    std::vector<double> t_end;
+    DeviceArray<double> d_t_end;
 
     cavmd_draw() : StateTable(cavmd_draw_item_check, [](const cavmd_draw_item&) { return 0u; }, draw_row) {}
 
@@ -169,7 +173,8 @@ static_assert(sizeof(cavmd_draw_state) == sizeof(DrawState) && offsetof(cavmd_dr
                   && offsetof(cavmd_draw_state, dt) == offsetof(DrawState, dt)
                   && offsetof(cavmd_draw_state, elapsed) == offsetof(DrawState, elapsed)
                   && offsetof(cavmd_draw_state, tolerance) == offsetof(DrawState, tolerance)
-                  && offsetof(cavmd_draw_state, exhausted) == offsetof(DrawState, exhausted),
+                  && offsetof(cavmd_draw_state, exhausted) == offsetof(DrawState, exhausted)
+                  && offsetof(cavmd_draw_state, reserved) == offsetof(DrawState, finished),
               "the draw states are read out as they are");
 static_assert(sizeof(cavmd_record) == sizeof(DrawRecord)
                   && offsetof(cavmd_record, force_mass_sum) == offsetof(DrawRecord, force_mass_sum),
@@ -365,9 +370,13 @@ int cavmd_draw_fill(cavmd_draw* d, void* stream_)
 {
     if (!d)
         return CAVMD_ERR_INVALID_VALUE;
-    return d->launch((hipStream_t)stream_, draw_fill_kernel<kDrawBlock>, dim3((unsigned)((d->n + kDrawBlock - 1) / kDrawBlock)),
-                     dim3(kDrawBlock), 0, d->d_rows.ptr, (unsigned)d->n, (unsigned)d->seed, (unsigned)(d->seed >> 32),
-                     d->d_state.ptr);
+    const dim3 grid((unsigned)((d->n + kDrawBlock - 1) / kDrawBlock));
+    if (d->d_t_end.ptr) // the variant is chosen here: a launch captured before the first end time stays the old kernel
+        return d->launch((hipStream_t)stream_, draw_fill_kernel<kDrawBlock, true>, grid, dim3(kDrawBlock), 0, d->d_rows.ptr,
+                         (unsigned)d->n, (unsigned)d->seed, (unsigned)(d->seed >> 32), d->d_state.ptr,
+                         (const double*)d->d_t_end.ptr);
+    return d->launch((hipStream_t)stream_, draw_fill_kernel<kDrawBlock>, grid, dim3(kDrawBlock), 0, d->d_rows.ptr, (unsigned)d->n,
+                     (unsigned)d->seed, (unsigned)(d->seed >> 32), d->d_state.ptr);
 }
 
 int cavmd_draw_read(cavmd_draw* d, void* stream_, cavmd_draw_state* out)
@@ -398,6 +407,56 @@ int cavmd_snapshot_draw_save(cavmd_draw* d, void* stream_, void* h_out, size_t b
 int cavmd_snapshot_draw_load(cavmd_draw* d, void* stream_, const void* h_in, size_t bytes)
 {
     return snapshot_load(d, (hipStream_t)stream_, h_in, bytes);
+}
+
+// ---- the run clock of cavmd_draw: an end time per item, and how many items rest behind theirs ----------------------------------
+int cavmd_runclock_draw_set_end(cavmd_draw* d, size_t first, size_t count, const double* h_t_end)
+{
+    if (!d || !h_t_end || count == 0 || first >= d->n || count > d->n - first)
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+        if (!finite_nonnegative(h_t_end[i]))
+            return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(d->device);
+    const int st = d->wait_idle(); // as set_items: refused while the last stream is being captured
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<double> all(d->t_end);
+    all.resize(d->n, 0.0);
+    for (size_t i = 0; i < count; ++i)
+        all[first + i] = h_t_end[i] + 0.0; // -0 is +0: none
+    // The flags first: whether one of these items rests is decided again by the next launch, and until then it does not count
+    // as finished.  Should the copy of the end times fail after this one went through, end times and host stay as they were and
+    // the next launch sets the flags again by the old end times: nothing is left half-changed.
+    const std::vector<uint64_t> zero(count, 0);
+    CAVMD_HIP_TRY(hipMemcpy2D(&d->d_state.ptr[first].finished, sizeof(DrawState), zero.data(), sizeof(uint64_t), sizeof(uint64_t),
+                              count, hipMemcpyHostToDevice));
+    if (!d->d_t_end.ptr)
+        CAVMD_HIP_TRY(d->d_t_end.upload(all.data(), d->n));
+    else
+        CAVMD_HIP_TRY(hipMemcpy(d->d_t_end.ptr + first, all.data() + first, sizeof(double) * count, hipMemcpyHostToDevice));
+    d->t_end.swap(all); // only now: a failed copy leaves the host's view as it was
+    return CAVMD_OK;
+}
+
+int cavmd_runclock_draw_finished(cavmd_draw* d, void* stream_, uint64_t* n_finished)
+{
+    if (!d || !n_finished)
+        return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(d->device);
+    int st = d->wait_idle(); // the stream of the last fill, as every call of this section; then the caller's
+    if (st == CAVMD_OK)
+        st = sync_uncaptured((hipStream_t)stream_);
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<uint64_t> flags(d->n);
+    CAVMD_HIP_TRY(hipMemcpy2D(flags.data(), sizeof(uint64_t), &d->d_state.ptr->finished, sizeof(DrawState), sizeof(uint64_t), d->n,
+                              hipMemcpyDeviceToHost));
+    uint64_t count = 0;
+    for (uint64_t f : flags)
+        count += f != 0;
+    *n_finished = count;
+    return CAVMD_OK;
 }
 
 // ---- cavmd_bath ------------------------------------------------------------------------------------------------------------

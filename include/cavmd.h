@@ -35,6 +35,11 @@
  *   hoomd.write.GSD (positions, images and velocities every output period, the initial frame first), per replica
  *                               examples/05_advanced_run.py:1231-1246    cavmd_trajectory_create / cavmd_trajectory_record /
  *                                                                   cavmd_trajectory_read (a ring of frames in device memory)
+ *   ElapsedTimeTracker (--runtime) and EnergyTracker's --energy-output-period-ps / --max-energy-output-time, per replica
+ *                               src/cavitymd/analysis.py:1230-1259, 692-701   cavmd_runclock_draw_set_end /
+ *                                                                   cavmd_runclock_draw_finished / cavmd_runclock_ledger_set_rule /
+ *                                                                   cavmd_runclock_field_set_rule
+ *                                                                   (decided on the device, by each replica's own clock)
  *   CavityForceCompute::computeForces (the CPU semantics both follow)
  *                               src/CavityForceCompute.cc:134-208   (semantic contract, see below)
  *
@@ -1129,6 +1134,13 @@ CAVMD_API int cavmd_ledger_device_ptr(cavmd_ledger* l, const cavmd_ledger_row** 
  *      exp(log(u) / a), u the boost uniform as an argument of log.
  *      bussi_dof as BussiReservoirBatch.draw_inputs has it: the normal is drawn where dof != 0 (else 0), the gamma variate of
  *      shape (dof - 1) / 2 where dof > 1 (else 0).
+ *   4a. End time (only once cavmd_runclock_draw_set_end was called for the object; t_end = the item's, +0: none; `elapsed` as
+ *      the call finds it).  t_end > 0 and elapsed >= t_end: the item is AT REST -- both rows are the bytes
+ *      cavmd_verlet_input_make / cavmd_bussi_batch_input_make give for dt = 0 with every variate +0 (skip = 1, langevin_coeff =
+ *      0, c = tau != 0 ? 1 : 0), no block is consumed, draws, dt, elapsed, tolerance and exhausted are NOT written, and
+ *      `finished` (cavmd_draw_state.reserved[0]) becomes 1; items 5 and 6 do not apply.  Otherwise the call is items 5 and 6
+ *      and `finished` is written 0.  A NaN elapsed compares false: such an item never finishes.  The last step is not clamped:
+ *      an item stops at the first elapsed >= t_end, as the reference's ElapsedTimeTracker does.
  *   5. dt.  Fixed mode (d_records NULL): dt = dt_initial; langevin_coeff and c are the bytes cavmd_verlet_input_make and
  *      cavmd_bussi_batch_input_make give for it, taken on the HOST at create / set_items; `tolerance` is 0.  Adaptive mode:
  *        tolerance = tolerance_time_constant != 0
@@ -1173,7 +1185,8 @@ typedef struct cavmd_draw_state          /* 64 B; one per item, in device memory
     double elapsed;                      /* the left-to-right sum of every dt handed out */
     double tolerance;                    /* the last tolerance used (0 in fixed mode) */
     uint64_t exhausted;                  /* gamma draws none of whose 16 tries was accepted */
-    uint64_t reserved[3];
+    uint64_t reserved[3];                /* [0]: `finished`, 1 while the item rests behind its end time (the run clock's
+                                            section, below), else 0; [1], [2]: 0 */
 } cavmd_draw_state;
 typedef struct cavmd_draw cavmd_draw;    /* opaque; belongs to the workspace it was created from */
 
@@ -1532,6 +1545,79 @@ CAVMD_API int cavmd_trajectory_reset(cavmd_trajectory* t, void* stream);
  * the n_items row counters, for consumers that stay on the GPU (either may be NULL, not both). */
 CAVMD_API int cavmd_trajectory_device_ptr(cavmd_trajectory* t, const void** series, const uint64_t** rows);
 
+/* ---- the run clock: a batch run to an end time, energy and F(k,t) rows by each item's own clock ------------------------------- */
+/* Under an adaptive dt every item keeps its own clock on the device (cavmd_draw_state.elapsed), and the host cannot know on
+ * which replay an item reaches a given time without reading B clocks back.  The trajectory already obeys that clock (its rule
+ * 2); this section does the same for the end of the run (the reference's ElapsedTimeTracker, src/cavitymd/analysis.py:1230-
+ * 1259) and for the energy ledger's rows (EnergyTracker's --energy-output-period-ps and --max-energy-output-time,
+ * analysis.py:692-701) and for the field recorder's rows and references (--fkt-output-period-ps and --fkt-ref-interval, the
+ * reference's "PREFERRED for adaptive mode" rule, analysis.py:366-378).  A production run is then "capture once, replay until cavmd_runclock_draw_finished counts every item".
+ *
+ * End times (cavmd_draw).  Item 4a of the draw contract above.  An item at rest hands out skip = 1 rows, under which both
+ * half-steps, the bath step and the thermostat leave the item and its states untouched (cavmd_verlet_input.skip,
+ * cavmd_bussi_batch_input.skip); counters that count calls may move.  Raising an item's t_end lets it go on from where it
+ * stopped: `draws` did not move while it rested, so the continued run is bit for bit the run that had the larger t_end from
+ * the start.  `finished` is part of the 64-byte state: cavmd_draw_read, cavmd_draw_reset (which zeroes it) and the snapshot
+ * carry it.  End times are configuration, as items are: a rebuilt object is given them again before a snapshot is loaded.
+ *
+ * The ledger's time rule.  The trajectory's rule 2 with t = *item.d_time when the kernel runs, thread 0 alone reading and
+ * writing the item's words:
+ *     due = rows == 0 || t - last_time >= time_interval;   max_time > 0 && t > max_time: not due
+ * and a written row sets last_time = t.  The comparisons are IEEE: a NaN t is never due by them (as under the trajectory's
+ * rule, an item's first row is written whatever *d_time holds, and a NaN last_time then lets no further row be due).  A call that is not due moves `calls` alone.  last_time is one more word per item
+ * beside the four counters (whose layout is unchanged): cavmd_ledger_reset zeroes it, and while a rule is on it is a part of
+ * the snapshot blob -- the blob's header then carries word0 = 1, so that a blob taken under a rule and an object without one
+ * (or the reverse) meet as a header mismatch (CAVMD_ERR_INVALID_VALUE); without a rule blob and header are what they were.
+ * An item at rest stops writing rows by itself, its clock standing still.
+ *
+ * The field recorder's time rule.  cavmd_field_item holds no clock, so the rule takes a base DEVICE pointer and a byte stride:
+ * t = the double at d_time0 + item * stride_bytes when the kernel runs.  Rows are due as the ledger's, without max_time
+ * (due = rows == 0 || t - last_time >= time_interval; a written row sets last_time = t; a NaN t is never due by the
+ * comparison); a call whose row is not due moves `calls` alone and computes nothing, as a call inside a period does.  The
+ * record's `reserved` double holds t (it stays +0 without the rule), so that lag times can be formed from what is stored.
+ * With reference_time_interval > 0 the row-count condition of the reference rule (t_row - last_reference_row >=
+ * reference_interval) is replaced by t - last_reference_time >= reference_time_interval; last_reference_time follows EVERY
+ * reference taken, whatever its cause (the first row's, one asked for through d_take_reference, one by either interval);
+ * max_references, "the first row takes one", "correlate first, then maybe add" and d_take_reference stay as they are, and
+ * with reference_time_interval == 0 the row-count rule stays.  last_time and last_reference_time are two more arrays of
+ * n_items doubles beside the six counters: cavmd_field_recorder_reset zeroes them, and while a rule is on they are a sixth
+ * section of the snapshot blob, whose header then carries word[1] = max_references | 0x10000 -- a header mismatch against an
+ * object without the rule, and the reverse.  Unlike the ledger's, this rule's values (both intervals, d_time0, the stride) are
+ * NOT launch arguments: the kernel has no scalar registers to spare, so they live in device memory in front of the two time
+ * arrays and are read when the kernel runs -- a captured launch of the timed kernel sees the values of a later
+ * cavmd_runclock_field_set_rule.  WHICH kernel a launch is stays frozen at capture, as below.
+ *
+ * Captured launches.  Which kernel a call launches and the ledger's scalar rule values (time_interval, max_time) are launch arguments,
+ * frozen when a launch is captured: set the rules BEFORE the capture.  A graph captured before the first cavmd_runclock_* call
+ * of an object keeps the old behaviour.  The end times live in a device array whose address does not change after the first
+ * cavmd_runclock_draw_set_end, so a captured launch sees later changes of the VALUES: that is how t_end is extended between
+ * replays.
+ *
+ * Every call below synchronises the stream of the object's last launch first, as set_items does, and answers
+ * CAVMD_ERR_INVALID_VALUE while that stream is being captured, for a null handle or argument, and for a value that is negative
+ * or not finite. */
+/* Sets the end times of items first .. first + count - 1 from HOST memory (+0: none) and writes 0 to `finished` of those items:
+ * whether one of them rests is decided again by the next cavmd_draw_fill, and until then it does not count as finished.
+ * CAVMD_ERR_INVALID_VALUE also for a range outside the table.  The first call makes cavmd_draw_fill launch the kernel that
+ * reads end times.  The flags are written first: if the runtime then fails the copy of the end times, end times stay as they
+ * were and the next cavmd_draw_fill sets the flags again by them. */
+CAVMD_API int cavmd_runclock_draw_set_end(cavmd_draw* d, size_t first, size_t count, const double* h_t_end);
+/* Synchronises the stream of the last cavmd_draw_fill and `stream`, then *n_finished = the items whose `finished` is not 0 (one
+ * strided copy of n_items words).  CAVMD_ERR_INVALID_VALUE while either stream is being captured. */
+CAVMD_API int cavmd_runclock_draw_finished(cavmd_draw* d, void* stream, uint64_t* n_finished);
+/* Switches the ledger's time rule on (time_interval > 0) or off (time_interval == 0, and then max_time must be 0);
+ * max_time == 0: no last time.  CAVMD_ERR_INVALID_VALUE also unless the object was created with period == 1 and every item has
+ * a d_time; while the rule is on, cavmd_ledger_set_items refuses an item without d_time.  last_time is 0 until a row is written
+ * under the rule; switching the rule off and on again keeps it. */
+CAVMD_API int cavmd_runclock_ledger_set_rule(cavmd_ledger* l, double time_interval, double max_time);
+/* Switches the field recorder's time rule on (time_interval > 0) or off (time_interval == 0, and then reference_time_interval
+ * must be 0).  Item i's clock is the double at d_time0 + i * stride_bytes in DEVICE memory, read when the kernel runs (in
+ * practice &cavmd_draw_state[0].elapsed with stride 64).  CAVMD_ERR_INVALID_VALUE also for a rule on with a d_time0 that is NULL
+ * or not 8-byte aligned, a stride below 8 or not a multiple of 8, or an object created with period != 1.  Both time words are
+ * 0 until written under the rule; switching the rule off and on again keeps them. */
+CAVMD_API int cavmd_runclock_field_set_rule(cavmd_field_recorder* r, const double* d_time0, uint64_t stride_bytes,
+                                            double time_interval, double reference_time_interval);
+
 /* ---- measurement hooks (bench.py's roofline leg) ---------------------------------------------- */
 /* When enabled, every cavmd_compute_* brackets each of its kernels with hipEvents on `stream`. */
 CAVMD_API int cavmd_profile_enable(cavmd_workspace* ws, int on);
@@ -1561,9 +1647,13 @@ CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap
  *   recorder, ledger, trajectory                  the n_counters x n_items counter words (n_counters arrays of n_items, rows
  *                                                 written first), then the WHOLE ring of n_items x capacity x record_bytes
  *                                                 bytes, item-major by slot; slots never written are the zeros of creation
+ *   ledger under the run clock's time rule        those two, then last_time (n_items doubles); the header's word[0] is 1
+ *                                                 (0 without a rule, and the blob is then the two sections alone)
  *   field_recorder                                those two, then the row of every reference (n_items x max_references words),
  *                                                 the field of the last recorded call (n_items x n_k x 2 doubles) and the
  *                                                 references (n_items x max_references x n_k x 2 doubles)
+ *   field_recorder under the run clock's time rule those five, then last_time and last_reference_time (2 x n_items doubles);
+ *                                                 the header's word[1] is max_references | 0x10000
  * Because the arrays are copied as they are, after a load every read, rows and read_fields answers what it answered when the
  * blob was saved, by the rules it always had, and the next launch continues from there bit for bit.
  *
@@ -1583,7 +1673,8 @@ CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap
  *
  * NOT in a snapshot, and the caller's to recreate with the same arguments before a load: the item tables (every device
  * pointer of an item is of the new process), seeds given per item (cavmd_bath_item, cavmd_thermalize_item), periods,
- * intervals, kB, wavevectors and every other parameter of create.  The draw object's seed is in the header, so a blob of
+ * intervals, kB, wavevectors and every other parameter of create, and the run clock's end times and rules (cavmd_runclock_*).
+ * The draw object's seed is in the header, so a blob of
  * another seed is refused.  cavmd_batch, cavmd_molecular and cavmd_coulomb keep nothing between launches that a later launch
  * reads, so they have no snapshot.  Result-history sequence numbers and cavmd_record.eval_sequence restart in a new process
  * (they are diagnostic).  Host-side generators that made input rows are the caller's.  The arrays the items point to

@@ -2,7 +2,9 @@
 
 From every object file build/<flavour>/<unit>.o of both trees the gfx950 code object is taken out of its .hip_fatbin section
 (llvm-objcopy, clang-offload-bundler); per kernel, `code` compares the disassembly of the kernel's symbol (llvm-objdump -d,
-addresses dropped), `descriptor` the 64 bytes of its .kd symbol and the resource figures of its metadata note.  Needs no GPU.
+addresses dropped), `descriptor` the 64 bytes of its .kd symbol and the resource figures of its metadata note (`moved`: the
+figures and every byte but kernel_code_entry_byte_offset, bytes 16..23, agree -- where the code lies in a unit that gained a
+kernel; `new`: a kernel the parent has not).  Needs no GPU.
 
     python scripts/compare_device_code.py PARENT_CSRC THIS_CSRC > table.txt"""
 import glob
@@ -84,7 +86,7 @@ def demangled(names):
 
 def main():
     parent, this = sys.argv[1], sys.argv[2]
-    rows, counts = [], {}
+    rows, counts, new, moved = [], {}, 0, 0
     with tempfile.TemporaryDirectory() as tmp:
         for flavour in FLAVOURS:
             for obj in sorted(glob.glob(os.path.join(this, "build", flavour, "*.o"))):
@@ -103,10 +105,17 @@ def main():
                     code = "identical" if kern in dis0 and kern in dis1 and dis0[kern] == dis1[kern] and dis1[kern] else \
                         ("only parent" if kern not in dis1 else "only this" if kern not in dis0 else "DIFFERS")
                     desc = "identical" if kd0.get(kern) == kd1.get(kern) and fig0.get(kern) == fig1.get(kern) and kern in kd1 else "DIFFERS"
+                    if desc == "DIFFERS" and kern in kd0 and kern in kd1 and fig0.get(kern) == fig1.get(kern) \
+                            and kd0[kern][:16] + kd0[kern][24:] == kd1[kern][:16] + kd1[kern][24:]:
+                        desc = "moved"           # kernel_code_entry_byte_offset alone: a kernel was added to the unit
+                        moved += code == "identical"
+                    if code == "only this":
+                        desc = "new"
+                        new += 1
                     rows.append((f"{flavour}/{unit}", names[kern], code, desc) + tuple(str(x) for x in fig1.get(kern, fig0.get(kern))))
                     c = counts.setdefault(flavour.split("_")[0], [0, 0])
                     c[0] += 1
-                    c[1] += code == "identical" and desc == "identical"
+                    c[1] += code == "identical" and desc in ("identical", "moved")
     head = ("flavour/unit", "kernel", "code", "descriptor", "vgpr", "agpr", "sgpr", "lds_bytes", "scratch_bytes")
     widths = [max(len(r[i]) for r in rows + [head]) for i in range(len(head))]
     for r in [head] + rows:
@@ -114,10 +123,14 @@ def main():
     print()
     total = sum(c[0] for c in counts.values())
     same = sum(c[1] for c in counts.values())
-    print(f"product kernels: {counts['product'][0]}, identical in code and descriptor: {counts['product'][1]}")
+    print(f"product kernels: {counts['product'][0]}, of them with the parent's code, resource figures and descriptor "
+          f"(its code entry offset aside): {counts['product'][1]}")
+    print(f"descriptors byte-identical: {same - moved}; differing in kernel_code_entry_byte_offset alone (`moved`): {moved}; "
+          f"kernels the parent has not (`new`): {new}")
     print(f"all {total} rows ({counts['product'][0]} product, {counts['hooks'][0]} hooks, {counts['split'][0]} split variants): "
-          + ("identical" if same == total else f"{total - same} DIFFER"))
-    return 0 if same == total else 1
+          + (f"{new} new, " if new else "") + ("the rest identical" if new and same + new == total else
+                                                "identical" if same == total else f"{total - same - new} DIFFER"))
+    return 0 if same + new == total else 1
 
 
 if __name__ == "__main__":
