@@ -484,8 +484,8 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
     if (plan.path == Path::single_block)
     {
         ws->sequence += 1;
-        st = ls.launch(0, cavity_small_system_kernel<kSmallBlock>, 1u, kSmallBlock, in, n, Lx, Ly, Lz, dp, L_typeid,
-                       ws->sequence, d_result, host_block(ws), force2);
+        st = ls.launch(0, cavity_small_system_kernel<kSmallBlock>, 1u, kSmallBlock, in.pos2, in.charge, in.image, n, L_typeid,
+                       Lx, Ly, Lz, dp, ws->sequence, d_result, host_block(ws), force2);
         return st != CAVMD_OK ? st : evaluation_enqueued(ws, ls, stream);
     }
 
@@ -499,13 +499,15 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
             ws->sync_state_dirty = false;
         }
         ws->sequence += 1;
-        const AosInputT<2> inx {in.pos2, in.charge, in.image};
         const SyncState sync {ws->d_granules.ptr, ws->d_epoch.ptr,
                               ws->debug_spin_limit > 0 ? (unsigned)ws->debug_spin_limit : kSpinLimit, ws->debug_late_block,
                               (unsigned)ws->debug_late_ticks, ws->debug_silent_block, &ws->h_ctl.dev->sync_error};
+        // the kernel's G and the launch's grid are the same number, set here and nowhere else
         const auto launch = [&](auto kernel) {
-            return ls.launch_lds(0, plan.lds_bytes, kernel, plan.g1, kPersistBlock, inx, n, Lx, Ly, Lz, dp, L_typeid, sync,
-                                 ws->sequence, d_result, host_block(ws), force2, plan.lds_slots, plan.balanced);
+            const unsigned G = plan.g1;
+            return ls.launch_lds(0, plan.lds_bytes, kernel, G, kPersistBlock, in.pos2, in.charge, in.image, sync.epoch, n, G,
+                                 L_typeid, plan.lds_slots | (plan.balanced ? kBalancedBit : 0u), Lx, Ly, Lz, dp, rest_of(sync),
+                                 ws->sequence, d_result, host_block(ws), force2);
         };
 #ifdef CAVMD_TEST_HOOKS
         // fault injection (tests): one block starts late -> the grid starves itself and has to be repaired; or one block
@@ -527,9 +529,9 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
     // ---- launch 1: per-block partial sums + photon search
     st = with_constant(kUnrolls, plan.unroll, [&](auto u) {
         return with_constant(kLoadPolicies, plan.nt_load, [&](auto nt) {
-            using Input = AosInputT<decltype(nt)::value>;
-            return ls.launch(0, &dipole_partials_kernel<Input, kReduceBlock, decltype(u)::value>, plan.g1, kReduceBlock,
-                             Input {in.pos2, in.charge, in.image}, n, Lx, Ly, Lz, L_typeid, part);
+            const unsigned G = plan.g1; // the kernel's G and the launch's grid
+            return ls.launch(0, &dipole_partials_aos_kernel<decltype(nt)::value, kReduceBlock, decltype(u)::value>, G,
+                             kReduceBlock, in.pos2, in.charge, in.image, n, G, L_typeid, Lx, Ly, Lz, part);
         });
     });
     if (st != CAVMD_OK)
@@ -540,9 +542,10 @@ int cavmd_compute_hoomd(cavmd_workspace* ws, void* stream_, size_t N, const cavm
     {
         // ---- launch 2 of 2: every force-map block folds the partials itself, block 0 publishes the result block
         st = with_constant(kStorePolicies, plan.nt_store, [&](auto s) {
-            return ls.launch(2, &force_map_aos_fused_kernel<kMapBlock, kMapUnroll, decltype(s)::value>, plan.g2, kMapBlock, in, n,
-                             plan.g1, Lx, Ly, Lz, dp, L_typeid, part, ws->sequence, d_result, host_block(ws), force2,
-                             plan.map_reverse);
+            const unsigned G = plan.g2; // the kernel's G and the launch's grid
+            return ls.launch(2, &force_map_aos_fused_kernel<kMapBlock, kMapUnroll, decltype(s)::value>, G, kMapBlock, in.pos2,
+                             in.charge, in.image, part.d, part.i, n, G, (int)plan.map_reverse, plan.g1, part.stride, L_typeid, Lx,
+                             Ly, Lz, dp, ws->sequence, d_result, host_block(ws), force2);
         });
     }
     else

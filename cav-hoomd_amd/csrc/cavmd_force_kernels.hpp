@@ -284,24 +284,38 @@ __device__ __forceinline__ void row_accumulate(const typename Input::Raw& r, siz
 // next tile's row on its way before it starts the arithmetic, at the plain loop's bytes in flight (a whole-tile double buffer
 // holds two tiles in flight instead, which queued twice the bytes on the slowest paths and lost).  UNROLL == 1: a row is a tile,
 // rolling would BE that double buffer, so the plain loop stays.  row_hook(k, u, charge) runs once per row, before its
-// arithmetic (the single-launch kernel parks the charge in LDS; the reduction kernel does nothing).
-template <class Input, int BLOCK, int UNROLL, class RowHook>
+// arithmetic (the single-launch kernel parks the charge in LDS; the reduction kernel does nothing).  first_issued() runs once,
+// when the rows of the block's first tile have been issued and none has been consumed (not at all for a block without a full
+// tile): the place to wait for kernel arguments that the loads themselves did not need.  The UNROLL == 1 loop has its first
+// trip peeled for that; a test inside the loop would leave the wait in every trip, where the paths join.
+struct NoFirstIssuedHook
+{
+    __device__ __forceinline__ void operator()() const {}
+};
+template <class Input, int BLOCK, int UNROLL, class RowHook, class FirstIssued>
 __device__ __forceinline__ void accumulate_full_tiles(const Input& in, const TileSchedule& sch, double Lx, double Ly, double Lz,
-                                                      int L_typeid, Accum& acc, RowHook&& row_hook)
+                                                      int L_typeid, Accum& acc, RowHook&& row_hook, FirstIssued&& first_issued)
 {
     if constexpr (UNROLL == 1)
     {
-        for (unsigned k = 0; k < sch.nfull; ++k)
-        {
+        const auto one_tile = [&](unsigned k, auto first) {
             const size_t base = tile_row_base(sch, k, 0, BLOCK) + threadIdx.x;
             TileRegs<Input, 1> A;
             tile_load<Input, BLOCK, 1>(in, base, A);
             __builtin_amdgcn_sched_barrier(0);
-            if (k == 0)
+            if constexpr (decltype(first)::value)
+            {
                 CAVMD_PSTAMP(8);
+                first_issued();
+            }
             row_hook(k, 0, A.raw[0].c);
             tile_accumulate<Input, BLOCK, 1>(A, base, Lx, Ly, Lz, L_typeid, acc);
-        }
+        };
+        constexpr bool peel = !std::is_same_v<std::decay_t<FirstIssued>, NoFirstIssuedHook>; // nothing to run: the plain loop
+        if (peel && sch.nfull)
+            one_tile(0, std::true_type {});
+        for (unsigned k = peel ? 1 : 0; k < sch.nfull; ++k)
+            one_tile(k, std::false_type {});
     }
     else
     {
@@ -320,7 +334,8 @@ __device__ __forceinline__ void accumulate_full_tiles(const Input& in, const Til
             [&](int set, int u, unsigned k, size_t base) {
                 row_hook(k, u, R[set].raw[u].c);
                 row_accumulate<Input>(R[set].raw[u], base + threadIdx.x, Lx, Ly, Lz, L_typeid, acc);
-            });
+            },
+            first_issued);
     }
 }
 
@@ -351,16 +366,16 @@ __device__ __forceinline__ void accumulate_ragged_tile(const Input& in, size_t t
     }
 }
 
-template <class Input, int BLOCK, int UNROLL>
-__global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsigned N, double Lx, double Ly, double Lz,
-                                                                int L_typeid, Partials part)
+// The reduction of one block, G = the grid's size: the body of the two kernels below.  first_issued: see accumulate_full_tiles.
+template <class Input, int BLOCK, int UNROLL, class FirstIssued>
+__device__ __forceinline__ void dipole_partials_body(const Input& in, unsigned N, unsigned G, double Lx, double Ly, double Lz,
+                                                     int L_typeid, const Partials& part, FirstIssued&& first_issued)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
     Accum acc;
     const unsigned full_tiles = N / TILE;
-    const unsigned G = gridDim.x;
     accumulate_full_tiles<Input, BLOCK, UNROLL>(in, strided_tiles(N, G, blockIdx.x, TILE), Lx, Ly, Lz, L_typeid, acc,
-                                                [](unsigned, int, double) {});
+                                                [](unsigned, int, double) {}, first_issued);
     // ragged tail: one block takes it, bounds-checked (restates accumulate_ragged_tile: calling it moves instructions here)
     if (blockIdx.x == full_tiles % G)
     {
@@ -390,6 +405,32 @@ __global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsign
         part.i[0 * s + b] = acc.lmin;
         part.i[1 * s + b] = acc.lcnt;
     }
+}
+
+// any layout (the snapshot layout's reduction); the grid's size from the launch's hidden arguments
+template <class Input, int BLOCK, int UNROLL>
+__global__ __launch_bounds__(BLOCK) void dipole_partials_kernel(Input in, unsigned N, double Lx, double Ly, double Lz,
+                                                                int L_typeid, Partials part)
+{
+    dipole_partials_body<Input, BLOCK, UNROLL>(in, N, gridDim.x, Lx, Ly, Lz, L_typeid, part, NoFirstIssuedHook {});
+}
+
+// HOOMD's AoS layout.  The kernel arguments in the order a block needs them, so that the first fourteen dwords (the three
+// pointers, N, G, L_typeid and two of the box lengths) are handed over in registers at wave start (kernel-argument preload,
+// csrc/Makefile: fourteen = the sixteen user SGPRs less the pointer to the argument block); G = the grid's size, an argument
+// of its own: gridDim.x sits in the hidden arguments, behind the last explicit one, in a line of the argument block that
+// nothing else here needs.  The rest (Lz, the partials' place) is fetched by scalar loads issued at entry and waited for once,
+// when the first tile rows are on their way.
+template <int NT, int BLOCK, int UNROLL>
+__global__ __launch_bounds__(BLOCK) void dipole_partials_aos_kernel(const v2d* __restrict__ pos2,
+                                                                    const double* __restrict__ charge,
+                                                                    const int* __restrict__ image, unsigned N, unsigned G,
+                                                                    int L_typeid, double Lx, double Ly, double Lz,
+                                                                    Partials part)
+{
+    const AosInputT<NT> in {pos2, charge, image};
+    dipole_partials_body<AosInputT<NT>, BLOCK, UNROLL>(in, N, G, Lx, Ly, Lz, L_typeid, part,
+                                                       [&] { asm volatile("" : : "s"(Lz)); });
 }
 
 // ---- final reduction + scalars (shared by the stand-alone finalize kernel and the fused force map) ------------
@@ -707,11 +748,11 @@ __device__ __forceinline__ v2d force_chunk_typed(const MapScalars& m, double ng,
 // Body shared by the three-launch and the fused force map.  Its three chunk sites keep their own text of the rule above:
 // routed through force_chunk the compiler folds the photon test differently (profiles/single_launch_cleanup/README.md).
 // PRE: the caller has already loaded the charges of this block's first full tile into c_first (issued before its
-// prologue so that their latency is hidden behind it).
+// prologue so that their latency is hidden behind it).  G: the grid's size.
 template <int BLOCK, int UNROLL, int NT, bool PRE>
 __device__ __forceinline__ void force_map_body(const MapScalars m, const double* __restrict__ charge,
                                                const v2d* __restrict__ pos2, unsigned N, double g, int L_typeid,
-                                               v2d* __restrict__ force2, const double (&c_first)[UNROLL],
+                                               v2d* __restrict__ force2, const double (&c_first)[UNROLL], unsigned G,
                                                bool reverse = false)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
@@ -725,7 +766,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
     if (m.photon < 0)
     {
         // no photon: all forces are zero (src/CavityForceCompute.cc:145-156)
-        for (size_t k = (size_t)blockIdx.x * BLOCK + threadIdx.x; k < nchunks; k += (size_t)gridDim.x * BLOCK)
+        for (size_t k = (size_t)blockIdx.x * BLOCK + threadIdx.x; k < nchunks; k += (size_t)G * BLOCK)
             store_chunk<NT>(force2 + k, zero);
         return;
     }
@@ -734,10 +775,10 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
     {
         // Tiles blockIdx.x, blockIdx.x + grid, ...; `reverse` walks the same tiles from the last to the first, so that
         // the charge lines the reduction touched most recently (same XCD, see cavmd_capi.hip) are asked for first.
-        const unsigned count = blockIdx.x < full_tiles ? (full_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+        const unsigned count = blockIdx.x < full_tiles ? (full_tiles - blockIdx.x + G - 1) / G : 0;
         for (unsigned j = 0; j < count; ++j)
         {
-            const unsigned t = blockIdx.x + (reverse ? count - 1 - j : j) * gridDim.x;
+            const unsigned t = blockIdx.x + (reverse ? count - 1 - j : j) * G;
             const size_t base = (size_t)t * TILE + threadIdx.x;
             double c[UNROLL];
             if (PRE && j == 0)
@@ -764,7 +805,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
                 store_chunk<NT>(force2 + k, v);
             }
         }
-        if (blockIdx.x == full_tiles % gridDim.x)
+        if (blockIdx.x == full_tiles % G)
         {
             const size_t base = (size_t)full_tiles * TILE + threadIdx.x;
 #pragma unroll
@@ -787,7 +828,7 @@ __device__ __forceinline__ void force_map_body(const MapScalars m, const double*
 
     // Several L-typed particles (degenerate): the reference gives a molecular force only to particles
     // whose type is not L (src/CavityForceCompute.cc:190-191), so the type tag has to be read.
-    for (size_t k = (size_t)blockIdx.x * BLOCK + threadIdx.x; k < nchunks; k += (size_t)gridDim.x * BLOCK)
+    for (size_t k = (size_t)blockIdx.x * BLOCK + threadIdx.x; k < nchunks; k += (size_t)G * BLOCK)
     {
         const size_t p = k >> 1;
         const int tag = __double2loint(pos2[2 * p + 1].y);
@@ -813,21 +854,29 @@ __global__ __launch_bounds__(BLOCK) void force_map_aos_kernel(const double* __re
     m.photon = res->photon_idx;
     m.nL = res->n_photon_typed;
     const double none[UNROLL] = {};
-    force_map_body<BLOCK, UNROLL, NT, false>(m, charge, pos2, N, g, L_typeid, force2, none);
+    force_map_body<BLOCK, UNROLL, NT, false>(m, charge, pos2, N, g, L_typeid, force2, none, gridDim.x);
 }
 
 // two-launch path: every block folds the partials itself (same fixed order -> same bits in every block), block 0
 // publishes the result block; no separate finalize launch and no inter-workgroup hand-off inside the launch.
+// The first fourteen dwords of the argument block are what the prologue needs for the loads it issues first (the first tile's
+// charges, the speculative row) and all but the stride of what the partials' loads need, for the kernel-argument preload
+// (dipole_partials_aos_kernel above); G = the grid's size, reverse as an int.
 template <int BLOCK, int UNROLL, int NT>
-__global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(AosInput in, unsigned N, unsigned nparts, double Lx,
-                                                                    double Ly, double Lz, DeviceParams prm, int L_typeid,
-                                                                    Partials part, uint64_t sequence,
+__global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(const v2d* __restrict__ pos2,
+                                                                    const double* __restrict__ charge,
+                                                                    const int* __restrict__ image, double* part_d, int* part_i,
+                                                                    unsigned N, unsigned G, int reverse, unsigned nparts,
+                                                                    unsigned part_stride, int L_typeid, double Lx, double Ly,
+                                                                    double Lz, DeviceParams prm, uint64_t sequence,
                                                                     cavmd_result* __restrict__ res,
                                                                     HostResult* __restrict__ res_host,
-                                                                    v2d* __restrict__ force2, bool reverse)
+                                                                    v2d* __restrict__ force2)
 {
     __shared__ double s_m[5];
     __shared__ int s_mi[2];
+    const AosInput in {pos2, charge, image};
+    const Partials part {part_d, part_i, part_stride};
     // charges of the first tile: independent of the prologue, so issue them first
     double c_first[UNROLL] = {};
     {
@@ -835,8 +884,8 @@ __global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(AosInput in,
         const unsigned full_tiles = (unsigned)((2 * (size_t)N) / TILE);
         if (blockIdx.x < full_tiles)
         {
-            const unsigned count = (full_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
-            const unsigned t0 = blockIdx.x + (reverse ? count - 1 : 0) * gridDim.x;
+            const unsigned count = (full_tiles - blockIdx.x + G - 1) / G;
+            const unsigned t0 = blockIdx.x + (reverse ? count - 1 : 0) * G;
             const size_t base = (size_t)t0 * TILE + threadIdx.x;
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
@@ -855,7 +904,7 @@ __global__ __launch_bounds__(BLOCK) void force_map_aos_fused_kernel(AosInput in,
     }
     __syncthreads();
     const MapScalars m = map_scalars_from_lds(s_m, s_mi);
-    force_map_body<BLOCK, UNROLL, NT, true>(m, in.charge, in.pos2, N, prm.g, L_typeid, force2, c_first, reverse);
+    force_map_body<BLOCK, UNROLL, NT, true>(m, in.charge, in.pos2, N, prm.g, L_typeid, force2, c_first, G, reverse != 0);
 }
 
 constexpr int kSmallSystemLdsCharges = 4096; // charges the single-block kernel keeps in LDS (32 KB); beyond: re-read
@@ -865,13 +914,17 @@ constexpr int kSmallSystemLdsCharges = 4096; // charges the single-block kernel 
 // launches are pure latency (~4 us each); a single block that reduces, finalises and maps in one go halves it.  Used
 // below kSmallSystemMaxN particles, where one CU's bandwidth is not yet the limit.
 constexpr int kSmallBlock = 256; // the block size both the workspace and the batch launch this body with: the two paths share bits
+// (the arguments the loads need lead the argument block, for the kernel-argument preload: dipole_partials_aos_kernel above)
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void cavity_small_system_kernel(AosInput in, unsigned N, double Lx, double Ly, double Lz,
-                                                                    DeviceParams prm, int L_typeid, uint64_t sequence,
-                                                                    cavmd_result* __restrict__ res,
+__global__ __launch_bounds__(BLOCK) void cavity_small_system_kernel(const v2d* __restrict__ pos2,
+                                                                    const double* __restrict__ charge,
+                                                                    const int* __restrict__ image, unsigned N, int L_typeid,
+                                                                    double Lx, double Ly, double Lz, DeviceParams prm,
+                                                                    uint64_t sequence, cavmd_result* __restrict__ res,
                                                                     HostResult* __restrict__ res_host,
                                                                     v2d* __restrict__ force2)
 {
+    const AosInput in {pos2, charge, image};
 #include "cavmd_small_system_body.hpp" // the body, shared as text with cavity_batch_kernel
 }
 

@@ -80,6 +80,27 @@ struct SyncState
     unsigned* sync_error;         // the workspace's starvation flag, a fixed word in mapped host memory (kSyncFailed /
                                   // kSyncRepaired; the host consumes it): outside the per-evaluation result slots
 };
+// SyncState as the kernel receives it: the epoch pointer travels among the leading arguments (it is needed at entry), the rest
+// of the state behind them.
+struct SyncRest
+{
+    unsigned long long* granules;
+    unsigned spin_limit;
+    int late_block;
+    unsigned late_ticks;
+    int silent_block;
+    unsigned* sync_error;
+    __host__ __device__ SyncState with_epoch(unsigned* epoch) const
+    {
+        return SyncState {granules, epoch, spin_limit, late_block, late_ticks, silent_block, sync_error};
+    }
+};
+inline SyncRest rest_of(const SyncState& st)
+{
+    return SyncRest {st.granules, st.spin_limit, st.late_block, st.late_ticks, st.silent_block, st.sync_error};
+}
+// lds_slots and `balanced` share one of the leading dwords (block_range needs `balanced` before the first tile load)
+constexpr unsigned kBalancedBit = 1u << 31;
 // *SyncState::sync_error, and the low bits of HostResult::failed
 constexpr unsigned kSyncFailed = 1u;   // some block gave up and nobody could complete the evaluation: its forces hold NaN
 constexpr unsigned kSyncRepaired = 2u; // every block gave up; the last one completed the whole evaluation alone: results valid
@@ -266,9 +287,10 @@ __device__ __forceinline__ LaunchTag read_launch_tag(const SyncState& st, uint64
 
 // ---- phase 1: partial dipole of this block's tiles (every lane's share; the block tree follows); the charges of its first
 // lds_slots tiles are parked in LDS -------------------------------------------------------------------------------------------
-template <int BLOCK, int UNROLL>
+// first_issued: see accumulate_full_tiles
+template <int BLOCK, int UNROLL, class FirstIssued>
 __device__ __forceinline__ Accum block_partial(const AosInputT<2>& in, const BlockRange& rg, double Lx, double Ly, double Lz,
-                                               int L_typeid, double* s_charge, unsigned lds_slots)
+                                               int L_typeid, double* s_charge, unsigned lds_slots, FirstIssued&& first_issued)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
     const unsigned tid = threadIdx.x;
@@ -277,7 +299,8 @@ __device__ __forceinline__ Accum block_partial(const AosInputT<2>& in, const Blo
                                                        [&](unsigned slot, int u, double c) {
                                                            if (slot < lds_slots)
                                                                s_charge[slot * TILE + u * BLOCK + tid] = c;
-                                                       });
+                                                       },
+                                                       first_issued);
     if (rg.tail_count)
         accumulate_ragged_tile<AosInputT<2>, BLOCK, UNROLL>(in, rg.tail_base, rg.tail_count, Lx, Ly, Lz, L_typeid, acc,
                                                             [&](unsigned o, double c) {
@@ -412,9 +435,10 @@ __device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<2>& in,
                                                          uint64_t sequence, cavmd_result* __restrict__ res,
                                                          HostResult* __restrict__ res_host, v2d* __restrict__ force2,
                                                          const LaunchTag& lt, const Accum& acc, const PhotonRow& guess,
-                                                         const MapScalars& m, double* s_m, int* s_mi, unsigned* s_words)
+                                                         const MapScalars& m, double* s_m, int* s_mi, unsigned* s_words,
+                                                         unsigned G)
 {
-    const unsigned G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    const unsigned b = blockIdx.x, tid = threadIdx.x;
     const unsigned tag = lt.tag;
     unsigned long long* const block_slab = st.granules;
     __shared__ unsigned s_last;
@@ -581,18 +605,30 @@ __device__ __forceinline__ void map_own_tiles(const AosInputT<2>& in, const Bloc
 }
 
 // ---- the kernel: entry, phase 1, hand-off, scalars through LDS, then the bail path, the slow map or phase 2 -------------------
+// The argument block.  Its first twelve dwords -- the three input pointers, the epoch pointer, N, G, L_typeid and lds_slots
+// (with kBalancedBit) -- are everything a block needs up to and including the issue of its first tile rows, and they are plain
+// pointers and integers: gfx950 hands them to every wave in user SGPRs at wave start (kernel-argument preload, asked for in
+// csrc/Makefile; twelve because the dispatch pointer and the argument-block pointer take four of the sixteen user SGPRs), so
+// the first loads wait for no fetch of the argument block.  G is the grid's size: gridDim.x sits in the hidden arguments,
+// behind the last explicit one, in a line of its own.  A by-value struct in front (AosInputT, as before) disables the preload.
 template <int BLOCK, int UNROLL, int NT_STORE, bool FAULT = false>
-__global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> in, unsigned N, double Lx, double Ly, double Lz,
-                                                                  DeviceParams prm, int L_typeid, SyncState st,
-                                                                  uint64_t sequence, cavmd_result* __restrict__ res,
-                                                                  HostResult* __restrict__ res_host,
-                                                                  v2d* __restrict__ force2, unsigned lds_slots, int balanced)
+__global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(const v2d* __restrict__ pos2, const double* __restrict__ charge,
+                                                                  const int* __restrict__ image, unsigned* epoch, unsigned N,
+                                                                  unsigned G, int L_typeid, unsigned lds_slots_balanced,
+                                                                  double Lx, double Ly, double Lz, DeviceParams prm,
+                                                                  SyncRest rest, uint64_t sequence,
+                                                                  cavmd_result* __restrict__ res,
+                                                                  HostResult* __restrict__ res_host, v2d* __restrict__ force2)
 {
     constexpr unsigned TILE = BLOCK * UNROLL; // particles per tile; the same tile is 2 * TILE force chunks
     __shared__ double s_m[5];
     __shared__ int s_mi[3];
     double* s_charge = s_dyn_charge;
-    const unsigned G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    const unsigned b = blockIdx.x, tid = threadIdx.x;
+    const AosInputT<2> in {pos2, charge, image};
+    const SyncState st = rest.with_epoch(epoch);
+    const unsigned lds_slots = lds_slots_balanced & ~kBalancedBit;
+    const int balanced = (lds_slots_balanced & kBalancedBit) != 0;
 
     CAVMD_PSTAMP(0);
     if constexpr (FAULT) // tests only: this block starts late, as if its CU had been held by another grid
@@ -608,14 +644,16 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
     // that they are older than every tile load; nothing waits for them before scalars_from_total
     const LaunchTag lt = read_launch_tag(st, sequence);
     const PhotonRow guess = speculative_photon_row(in, N);
-    // The kernel arguments fetched last (L_typeid among them) are waited for HERE, where the scalar row's wait used to cover
-    // them; their lines are in the scalar cache by now.  Scalar loads return out of order, so the wait is a full lgkmcnt(0):
-    // left to the compiler it sits at L_typeid's first use, inside the tile loop, and there every row also waits for its
-    // own LDS store.
-    asm volatile("" : : "s"(L_typeid));
+    // Everything up to here and block_range came out of the preloaded registers.  The arguments behind them (box lengths first:
+    // the first row's arithmetic needs them) are fetched by scalar loads (the compiler issues them a few instructions ahead of the
+    // first rows, not at entry) and waited for ONCE, when the first tile rows are on their way: they return in the shadow of those
+    // rows' own round trip.  Scalar loads return out of order, so the
+    // wait is a full lgkmcnt(0); left to the compiler it sits at the first use, inside the tile loop, and there every row also
+    // waits for its own LDS store.
+    const auto arguments_landed = [&] { asm volatile("" : : "s"(Lx), "s"(Ly), "s"(Lz)); };
 
     const BlockRange rg = block_range<TILE>(N, G, b, balanced);
-    Accum acc = block_partial<BLOCK, UNROLL>(in, rg, Lx, Ly, Lz, L_typeid, s_charge, lds_slots);
+    Accum acc = block_partial<BLOCK, UNROLL>(in, rg, Lx, Ly, Lz, L_typeid, s_charge, lds_slots, arguments_landed);
     CAVMD_PSTAMP(1);
     acc = block_reduce<BLOCK>(acc);
     CAVMD_PSTAMP(2);
@@ -650,7 +688,7 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(AosInputT<2> i
     if (bad)
     {
         give_up_and_maybe_repair<BLOCK, UNROLL, NT_STORE>(in, N, Lx, Ly, Lz, prm, L_typeid, st, sequence, res, res_host, force2, lt,
-                                                          acc, guess, m, s_m, s_mi, s_words);
+                                                          acc, guess, m, s_m, s_mi, s_words, G);
         return;
     }
     if (m.photon < 0 || m.nL > 1)

@@ -56,9 +56,11 @@ CAVMD_HD size_t tile_row_base(const TileSchedule& s, unsigned k, unsigned u, uns
 
 // The rolling loop's order of events.  issue(set, u, base): start the loads of a row into register set `set`; landed(set, u):
 // wait for that row, and for nothing issued after it; consume(set, u, k, base): the row's arithmetic.  `set`, `u` are constants
-// once the calls are inlined and the u loops unrolled.
-template <int UNROLL, class Issue, class Landed, class Consume>
-CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue, Landed&& landed, Consume&& consume)
+// once the calls are inlined and the u loops unrolled.  first_issued(): once, when the rows of the block's first tile are on
+// their way and none has been waited for (the single-launch kernel waits there for the kernel arguments it did not need so far).
+template <int UNROLL, class Issue, class Landed, class Consume, class FirstIssued>
+CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue, Landed&& landed, Consume&& consume,
+                           FirstIssued&& first_issued)
 {
     if (s.nfull == 0)
         return;
@@ -85,6 +87,7 @@ CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue,
     for (int u = 0; u < UNROLL; ++u)
         issue(0, u, tile_row_base(s, 0, u, block));
     CAVMD_PSTAMP(8);
+    first_issued();
     unsigned k = 0;
     for (; k + 2 < s.nfull; k += 2)
     {
@@ -98,6 +101,11 @@ CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue,
     }
     else
         drain(0, k);
+}
+template <int UNROLL, class Issue, class Landed, class Consume>
+CAVMD_HD void rolling_rows(const TileSchedule& s, unsigned block, Issue&& issue, Landed&& landed, Consume&& consume)
+{
+    rolling_rows<UNROLL>(s, block, issue, landed, consume, [] {});
 }
 
 } // namespace cavmd

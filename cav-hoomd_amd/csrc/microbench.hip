@@ -210,11 +210,11 @@ int main(int argc, char** argv)
     V.push_back({NAME, B1, [&](int f) {                                                                                 \
                      const unsigned g1 = grid(N, BLOCK * UNROLL, BPC);                                                  \
                      if (NTL == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<2, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt2_of(f).pos2, in_nt2_of(f).charge, in_nt2_of(f).image, n, g1, 2, L, L, L, part); \
                      else if (NTL == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<1, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_nt1_of(f).pos2, in_nt1_of(f).charge, in_nt1_of(f).image, n, g1, 2, L, L, L, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<0, BLOCK, UNROLL>), dim3(g1), dim3(BLOCK), 0, st, in_of(f).pos2, in_of(f).charge, in_of(f).image, n, g1, 2, L, L, L, part); \
                  }, {}})
     K1("K1 simple nt2 bpc1", 256, 4, 2, 1);
     K1("K1 simple nt2 bpc2", 256, 4, 2, 2);
@@ -263,11 +263,11 @@ int main(int argc, char** argv)
     V.push_back({NAME, B, [&](int f) {                                                                                  \
                      const unsigned g1 = grid(N, KB * KU, KBPC);                                                        \
                      if (KNT == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<2, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f).pos2, in_nt2_of(f).charge, in_nt2_of(f).image, n, g1, 2, L, L, L, part); \
                      else if (KNT == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<1, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f).pos2, in_nt1_of(f).charge, in_nt1_of(f).image, n, g1, 2, L, L, L, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<0, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f).pos2, in_of(f).charge, in_of(f).image, n, g1, 2, L, L, L, part); \
                      hipLaunchKernelGGL((finalize_kernel<AosInput, 256>), dim3(1), dim3(256), 0, st, in_of(f), n, g1, L, L, L, P, part, 1ull, d_res, d_hres); \
                      hipLaunchKernelGGL((force_map_aos_kernel<MB, MU, MNT>), dim3(grid(2 * N, MB * MU, MBPC)), dim3(MB), 0, st, d_chg[f], (const v2d*)d_pos[f], n, 1e-3, 2, d_res, (v2d*)d_frc[f]); \
                  }, {}})
@@ -275,12 +275,12 @@ int main(int argc, char** argv)
     V.push_back({NAME, B, [&](int f) {                                                                                  \
                      const unsigned g1 = grid(N, KB * KU, KBPC);                                                        \
                      if (KNT == 2)                                                                                      \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<2>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<2, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt2_of(f).pos2, in_nt2_of(f).charge, in_nt2_of(f).image, n, g1, 2, L, L, L, part); \
                      else if (KNT == 1)                                                                                 \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f), n, L, L, L, 2, part); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<1, KB, KU>), dim3(g1), dim3(KB), 0, st, in_nt1_of(f).pos2, in_nt1_of(f).charge, in_nt1_of(f).image, n, g1, 2, L, L, L, part); \
                      else                                                                                               \
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInput, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f), n, L, L, L, 2, part); \
-                     hipLaunchKernelGGL((force_map_aos_fused_kernel<MB, MU, MNT>), dim3(grid(2 * N, MB * MU, MBPC)), dim3(MB), 0, st, in_of(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false); \
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<0, KB, KU>), dim3(g1), dim3(KB), 0, st, in_of(f).pos2, in_of(f).charge, in_of(f).image, n, g1, 2, L, L, L, part); \
+                     hipLaunchKernelGGL((force_map_aos_fused_kernel<MB, MU, MNT>), dim3(grid(2 * N, MB * MU, MBPC)), dim3(MB), 0, st, in_of(f).pos2, in_of(f).charge, in_of(f).image, part.d, part.i, n, grid(2 * N, MB * MU, MBPC), 0, g1, part.stride, 2, L, L, L, P, 1ull, d_res, d_hres, (v2d*)d_frc[f]); \
                  }, {}})
     // NT = charge-load policy of the reduction (1 below 5e6 particles, 2 above), stores non-temporal
 #define SWEEP(NT)                                                                                                   \

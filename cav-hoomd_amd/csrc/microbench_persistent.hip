@@ -144,14 +144,14 @@ int main(int argc, char** argv)
     V.push_back({"two launches (K1 nt1 bpc1 | fused map u4 bpc2)", [&](int f) {
                      const unsigned g1 = grid(N, 256 * unroll, 1);
                      if (unroll == 2)
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 2>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<1, 256, 2>), dim3(g1), dim3(256), 0, st, in1(f).pos2, in1(f).charge, in1(f).image, n, g1, 2, L, L, L, part);
                      else
-                         hipLaunchKernelGGL((dipole_partials_kernel<AosInputT<1>, 256, 1>), dim3(g1), dim3(256), 0, st, in1(f), n, L, L, L, 2, part);
+                         hipLaunchKernelGGL((dipole_partials_aos_kernel<1, 256, 1>), dim3(g1), dim3(256), 0, st, in1(f).pos2, in1(f).charge, in1(f).image, n, g1, 2, L, L, L, part);
                      const unsigned g2 = grid(2 * N, 1024, 2);
                      if (nts)
-                         hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, true>), dim3(g2), dim3(256), 0, st, in0(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false);
+                         hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, true>), dim3(g2), dim3(256), 0, st, in0(f).pos2, in0(f).charge, in0(f).image, part.d, part.i, n, g2, 0, g1, part.stride, 2, L, L, L, P, 1ull, d_res, d_hres, (v2d*)d_frc[f]);
                      else
-                         hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, false>), dim3(g2), dim3(256), 0, st, in0(f), n, g1, L, L, L, P, 2, part, 1ull, d_res, d_hres, (v2d*)d_frc[f], false);
+                         hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, false>), dim3(g2), dim3(256), 0, st, in0(f).pos2, in0(f).charge, in0(f).image, part.d, part.i, n, g2, 0, g1, part.stride, 2, L, L, L, P, 1ull, d_res, d_hres, (v2d*)d_frc[f]);
                  }, {}});
     auto persist = [&](int f, int bpc, int balanced = 0) {
         const unsigned g1 = grid(N, 256 * unroll, bpc);
@@ -161,7 +161,7 @@ int main(int argc, char** argv)
         const size_t cap = (156 * 1024 - 1024) / (tile * 8);
         const unsigned lds_slots = (unsigned)std::min(slots, cap);
         const size_t lds = (size_t)lds_slots * tile * 8;
-#define PL(UNR, NTS) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS>), dim3(g1), dim3(256), lds, st, in2(f), n, L, L, L, P, 2, sync, 1ull, d_res, d_hres, (v2d*)d_frc[f], lds_slots, balanced)
+#define PL(UNR, NTS) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS>), dim3(g1), dim3(256), lds, st, in2(f).pos2, in2(f).charge, in2(f).image, sync.epoch, n, g1, 2, lds_slots | (balanced ? kBalancedBit : 0u), L, L, L, P, rest_of(sync), 1ull, d_res, d_hres, (v2d*)d_frc[f])
         if (unroll == 2) { if (nts) PL(2, true); else PL(2, false); }
         else { if (nts) PL(1, true); else PL(1, false); }
     };
