@@ -12,15 +12,23 @@ Contents
     numpy_mirror   second, independent restatement in numpy (vectorised maths, sequential sums
                    via math.fsum-free python loops only for tiny N) + exactly rounded sums.
 
-Pinning status: PARITY UNPINNED by the reference's own tests (it has none for this path, and it
-cannot be built or imported here because HOOMD-blue is absent).  See the header of cavity_ref.c
-for what pins the oracle instead.
+    reference_driver/, reference_run.py
+                   a driver of our own around the reference's compiled CavityForceCompute, and its file format.
+                   ``build_reference()`` compiles the reference's .cc with it into ``oracle/_ref/`` where a checkout of
+                   the reference exists, and does nothing anywhere else.
+
+Pinning status: the reference has no test for this path, but its CPU class has been EXECUTED (on the stand-in headers of
+tests/stubs/hoomd_force_reference) and its output is committed as tests/golden/cavity_reference_cpp_golden.npz:
+cavity_ref.c and numpy_mirror's sequential mode reproduce it bit for bit (tests/test_reference_cpp_golden.py).  What still
+rests on memory of HOOMD-blue's own headers is vec3's operators, the association of ``dot`` and ``__scalar_as_int``; see
+the header of cavity_ref.c.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -46,7 +54,23 @@ def build(force: bool = False) -> str:
         or not os.path.exists(bso) or os.path.getmtime(bso) < os.path.getmtime(bsrc)
     if force or stale:
         subprocess.run(["make", "-C", _HERE, "-s", "all"], check=True)
+    build_reference()
     return so
+
+
+# the `src` directory of a checkout of the reference; present in the build container only
+REFERENCE_SRC = os.environ.get("CAVMD_REFERENCE_SRC", "/root/reference/src")
+REFERENCE_CPU = os.path.join(_HERE, "_ref", "cavity_reference_cpu")
+
+
+def build_reference() -> bool:
+    """Where a checkout of the reference exists, compile its own CavityForceCompute.cc with our driver into
+    oracle/_ref/cavity_reference_cpu{,_O0,_O3} (make decides what is stale).  Anywhere else: nothing happens, and nothing but
+    tests/golden/make_reference_cavity_cpp_golden.py and tests/test_reference_cpp_live.py ever looks for those programs."""
+    if not os.path.exists(os.path.join(REFERENCE_SRC, "CavityForceCompute.cc")):
+        return False
+    subprocess.run(["make", "-C", _HERE, "-s", "reference", f"REF_SRC={REFERENCE_SRC}", f"PYTHON={sys.executable}"], check=True)
+    return True
 
 
 def type_tag_as_double(typeid) -> np.ndarray:

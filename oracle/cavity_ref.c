@@ -6,10 +6,22 @@
  * unwrapped positions on every call, a memset of the force array.  Only tests/, bench.py's
  * cpu_baseline leg and __graft_entry__.smoke() may load it; the product (libcavmd.so) never does.
  *
- * Pinning status: the reference holds NO golden vector, known-answer test or fixture for this
- * path (its tests cover only the thermostat) and the reference itself can neither be compiled
- * nor imported in this environment (HOOMD-blue is absent), so by the reference's own material
- * PARITY IS UNPINNED.  What pins this file instead (tests/test_oracle_*.py):
+ * Pinning status: PINNED BY EXECUTION of the reference's own class.  The reference holds no golden
+ * vector, known-answer test or fixture for this path (its tests cover only the thermostat), but its
+ * src/CavityForceCompute.cc and .h compile unmodified on about 250 lines of stand-in headers
+ * (tests/stubs/hoomd_force_reference) next to oracle/reference_driver/cavity_reference_driver.cc
+ * (oracle/Makefile, target `reference`; oracle/_ref/ is never committed).  Its output on 37 cases is
+ * committed as tests/golden/cavity_reference_cpp_golden.npz, and this file reproduces every recorded
+ * force entry, energy, dipole, photon index and K BIT FOR BIT at -O2 and -O3, as built by the compiler
+ * of whichever machine runs tests/test_reference_cpp_golden.py; where the reference's checkout is
+ * present tests/test_reference_cpp_live.py repeats that on a few hundred random cases and up to
+ * N = 1 000 001.  The HIP kernels meet the same recorded numbers in
+ * tests/test_gpu_reference_cpp_golden.py without any call into this file.
+ * What still rests on memory of HOOMD-blue's headers, which are not available to compare with: that
+ * vec3's operators are component-wise with one rounding each, that dot(a, b) associates as
+ * (a.x*b.x + a.y*b.y) + a.z*b.z, and that __scalar_as_int reads the low four bytes -- the stand-in
+ * headers state exactly that, so the fixture pins the reference's class on top of THOSE definitions.
+ * The older, weaker pins stay (tests/test_oracle_*.py):
  *   - the unwrap convention and the unit constants are checked against outputs of the reference's
  *     own src/cavitymd/utils.py (the one module that loads standalone), committed as
  *     tests/golden/utils_*.json with the generating script;

@@ -61,7 +61,8 @@ def compute(pos4, charge, image, box_L, L_typeid: int, params: dict, summation: 
     elif summation == "fsum":
         d = np.array([math.fsum(tk[:, k].tolist()) for k in range(3)])
     elif summation == "pairwise":
-        d = tk.sum(axis=0)
+        # per contiguous column: a sum down the rows of an (N, 3) array would run in index order, not through numpy's tree
+        d = np.array([np.ascontiguousarray(tk[:, k]).sum() for k in range(3)])
     else:
         raise ValueError(summation)
     q = r[pidx]

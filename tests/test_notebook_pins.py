@@ -8,7 +8,8 @@ the reference itself that exist for these formulas.  What they pin:
   * the adaptive-timestep rule dt = sqrt(tol / sum |F_i|/m_i)   (src/cavitymd/simulation.py:66-92)   -- row f4
   * the F(k,t) reference interval in steps                      (src/cavitymd/analysis.py, time-based intervals)
 
-The force path itself (dipole, forces, energies) has no recorded number in the reference: it stays unpinned.
+The force path itself (dipole, forces, energies) has no recorded number in the reference; what pins it is the reference's
+CPU class executed on stand-in headers (tests/test_reference_cpp_golden.py).
 """
 import json
 import math
