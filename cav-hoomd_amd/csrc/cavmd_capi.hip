@@ -252,9 +252,11 @@ EvalPlan plan_evaluation(const cavmd_workspace& ws, size_t N, Layout layout)
     // every other force of the step), and not leaving 32 N dirty bytes behind shortens this kernel's drain and spares
     // the next reduction the evictions (measured on whole evaluations, profiles/r01/microbench_*.txt).
     p.nt_store = ws.map_nt_store < 0 ? (N >= kNtStoreMinN ? 1 : 0) : ws.map_nt_store;
-    // Load policy of the reduction.  pos and image are read once per evaluation: non-temporal.  charge is read again
-    // by the force map: keeping it temporal lets the map find it in the Infinity Cache while 8 N bytes fit there
-    // (measured per evaluation: -8 % at N = 6e6 and 1e7, -5 % at 2e7, tie at 5e7); non-temporal above.
+    // Load policy.  pos and image are new every step and read once per evaluation: non-temporal on every path.  Charges are
+    // temporal on every path while 8 N bytes fit the Infinity Cache: the force map reads them again (measured per evaluation:
+    // -8 % at N = 6e6 and 1e7, -5 % at 2e7, tie at 5e7; non-temporal above), and they are the same from step to step.  The
+    // single launch reads them temporal always, since it ends far below that size (NT_LOAD's default in
+    // cavmd_persistent_kernel.hpp; profiles/charge_temporal/README.md); nt_load governs the two-launch reduction only.
     p.nt_load = ws.reduce_nt_load < 0 ? (N <= kChargeTemporalMaxN ? 1 : 2) : ws.reduce_nt_load;
     // Reverse tile order in the force map: the charge lines the reduction touched last are then asked for first.  It only
     // matters where the per-XCD share of the charges (N bytes) is about the size of an XCD's 4 MiB L2: -3.3 % per

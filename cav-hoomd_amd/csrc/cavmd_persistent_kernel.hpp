@@ -288,21 +288,27 @@ __device__ __forceinline__ LaunchTag read_launch_tag(const SyncState& st, uint64
 // ---- phase 1: partial dipole of this block's tiles (every lane's share; the block tree follows); the charges of its first
 // lds_slots tiles are parked in LDS -------------------------------------------------------------------------------------------
 // first_issued: see accumulate_full_tiles
-template <int BLOCK, int UNROLL, class FirstIssued>
-__device__ __forceinline__ Accum block_partial(const AosInputT<2>& in, const BlockRange& rg, double Lx, double Ly, double Lz,
+template <int BLOCK, int UNROLL, int NT_LOAD, class FirstIssued>
+__device__ __forceinline__ Accum block_partial(const AosInputT<NT_LOAD>& in, const BlockRange& rg, double Lx, double Ly, double Lz,
                                                int L_typeid, double* s_charge, unsigned lds_slots, FirstIssued&& first_issued)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
     const unsigned tid = threadIdx.x;
     Accum acc;
-    accumulate_full_tiles<AosInputT<2>, BLOCK, UNROLL>(in, TileSchedule {rg.first, rg.step, rg.nfull}, Lx, Ly, Lz, L_typeid, acc,
-                                                       [&](unsigned slot, int u, double c) {
-                                                           if (slot < lds_slots)
-                                                               s_charge[slot * TILE + u * BLOCK + tid] = c;
-                                                       },
-                                                       first_issued);
+    const TileSchedule sch {rg.first, rg.step, rg.nfull};
+    const auto park_row = [&](unsigned slot, int u, double c) {
+        if (slot < lds_slots)
+            s_charge[slot * TILE + u * BLOCK + tid] = c;
+    };
+    // The one call of the rolling loop, spelled out for the A/B policy: tests/test_rolling_schedule_host.py finds the function the
+    // kernels share by this call's text, which therefore names its input type in full.
+    static_assert(NT_LOAD == 1 || NT_LOAD == 2, "pos and image are always non-temporal here");
+    if constexpr (NT_LOAD == 2)
+        accumulate_full_tiles<AosInputT<2>, BLOCK, UNROLL>(in, sch, Lx, Ly, Lz, L_typeid, acc, park_row, first_issued);
+    else
+        accumulate_full_tiles<AosInputT<1>, BLOCK, UNROLL>(in, sch, Lx, Ly, Lz, L_typeid, acc, park_row, first_issued);
     if (rg.tail_count)
-        accumulate_ragged_tile<AosInputT<2>, BLOCK, UNROLL>(in, rg.tail_base, rg.tail_count, Lx, Ly, Lz, L_typeid, acc,
+        accumulate_ragged_tile<AosInputT<NT_LOAD>, BLOCK, UNROLL>(in, rg.tail_base, rg.tail_count, Lx, Ly, Lz, L_typeid, acc,
                                                             [&](unsigned o, double c) {
                                                                 if (rg.nfull < lds_slots)
                                                                     s_charge[rg.nfull * TILE + o] = c;
@@ -388,8 +394,8 @@ __device__ __forceinline__ HandOff hand_off(const SyncState& st, unsigned G, uns
 
 // ---- the slow map, all from global memory: tiles t0, t0 + step, ...; NaN everywhere (poison), or the general rule -- no photon:
 // zeros (src/CavityForceCompute.cc:145-156); several L-typed particles: force_chunk_typed ---------------------------------------
-template <int BLOCK, int UNROLL, int NT_STORE>
-__device__ __forceinline__ void slow_map(const AosInputT<2>& in, unsigned N, double g, int L_typeid, v2d* __restrict__ force2,
+template <int BLOCK, int UNROLL, int NT_STORE, int NT_LOAD>
+__device__ __forceinline__ void slow_map(const AosInputT<NT_LOAD>& in, unsigned N, double g, int L_typeid, v2d* __restrict__ force2,
                                          unsigned t0, unsigned step, bool poison, const MapScalars& ms)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
@@ -429,8 +435,8 @@ __device__ __forceinline__ void slow_map(const AosInputT<2>& in, unsigned N, dou
 // evaluation alone: same records, same fold, same bits; a millisecond instead of microseconds, once, after which the
 // host keeps this workspace on two launches.  If some blocks did get the total while others gave up (a race of
 // microseconds after a wait of a third of a second), the count never completes and the evaluation stays failed.
-template <int BLOCK, int UNROLL, int NT_STORE>
-__device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<2>& in, unsigned N, double Lx, double Ly, double Lz,
+template <int BLOCK, int UNROLL, int NT_STORE, int NT_LOAD>
+__device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<NT_LOAD>& in, unsigned N, double Lx, double Ly, double Lz,
                                                          const DeviceParams& prm, int L_typeid, const SyncState& st,
                                                          uint64_t sequence, cavmd_result* __restrict__ res,
                                                          HostResult* __restrict__ res_host, v2d* __restrict__ force2,
@@ -488,7 +494,7 @@ __device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<2>& in,
                 record_from_lds(s_groups + tid * kGranulesPerRecord, o);
         }
         const Accum tot = fold_gathered(o);
-        const Scalars sc = scalars_from_total<AosInputT<2>>(tot, guess, in, N, Lx, Ly, Lz, prm, true);
+        const Scalars sc = scalars_from_total<AosInputT<NT_LOAD>>(tot, guess, in, N, Lx, Ly, Lz, prm, true);
         if (tid == 0)
         {
             park_scalars(s_m, s_mi, sc, ok);
@@ -517,8 +523,8 @@ __device__ __forceinline__ void give_up_and_maybe_repair(const AosInputT<2>& in,
 
 // ---- phase 2: forces of this block's own tiles, charges from LDS: the resident tiles, the tiles beyond the LDS budget and the
 // ragged tile; every chunk by force_chunk (one photon exactly: the caller has sent the other cases to slow_map) ----------------
-template <int BLOCK, int UNROLL, int NT_STORE>
-__device__ __forceinline__ void map_own_tiles(const AosInputT<2>& in, const BlockRange& rg, const MapScalars& m, double g,
+template <int BLOCK, int UNROLL, int NT_STORE, int NT_LOAD>
+__device__ __forceinline__ void map_own_tiles(const AosInputT<NT_LOAD>& in, const BlockRange& rg, const MapScalars& m, double g,
                                               v2d* __restrict__ force2, const double* s_charge, unsigned lds_slots)
 {
     constexpr unsigned TILE = BLOCK * UNROLL;
@@ -565,7 +571,10 @@ __device__ __forceinline__ void map_own_tiles(const AosInputT<2>& in, const Bloc
                 const size_t p0 = rg.first + (size_t)slot * rg.step;
 #pragma unroll
                 for (int u = 0; u < MU; ++u)
-                    c[d][u] = __builtin_nontemporal_load(in.charge + p0 + ((u * BLOCK + tid) >> 1));
+                {
+                    const double* q = in.charge + p0 + ((u * BLOCK + tid) >> 1);
+                    c[d][u] = (NT_LOAD == 2) ? __builtin_nontemporal_load(q) : *q; // the policy of AosInputT::load
+                }
             }
         };
         auto store_batch = [&](unsigned s0, const double (&c)[D][MU]) {
@@ -611,7 +620,11 @@ __device__ __forceinline__ void map_own_tiles(const AosInputT<2>& in, const Bloc
 // csrc/Makefile; twelve because the dispatch pointer and the argument-block pointer take four of the sixteen user SGPRs), so
 // the first loads wait for no fetch of the argument block.  G is the grid's size: gridDim.x sits in the hidden arguments,
 // behind the last explicit one, in a line of its own.  A by-value struct in front (AosInputT, as before) disables the preload.
-template <int BLOCK, int UNROLL, int NT_STORE, bool FAULT = false>
+// NT_LOAD is AosInputT's load policy.  The product instantiates the default only: pos and image non-temporal (new every step),
+// charge temporal -- the charges of a run do not change from step to step and 8 N bytes are far below the Infinity Cache
+// wherever this kernel runs, so they can be found there in the next evaluation, and in this one by the tiles beyond the LDS
+// budget that phase 2 reads again.  2 (charges non-temporal too) is kept for the A/B in csrc/microbench_persistent.hip.
+template <int BLOCK, int UNROLL, int NT_STORE, bool FAULT = false, int NT_LOAD = 1>
 __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(const v2d* __restrict__ pos2, const double* __restrict__ charge,
                                                                   const int* __restrict__ image, unsigned* epoch, unsigned N,
                                                                   unsigned G, int L_typeid, unsigned lds_slots_balanced,
@@ -625,7 +638,7 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(const v2d* __r
     __shared__ int s_mi[3];
     double* s_charge = s_dyn_charge;
     const unsigned b = blockIdx.x, tid = threadIdx.x;
-    const AosInputT<2> in {pos2, charge, image};
+    const AosInputT<NT_LOAD> in {pos2, charge, image};
     const SyncState st = rest.with_epoch(epoch);
     const unsigned lds_slots = lds_slots_balanced & ~kBalancedBit;
     const int balanced = (lds_slots_balanced & kBalancedBit) != 0;
@@ -666,7 +679,7 @@ __global__ __launch_bounds__(BLOCK) void cavity_persistent_kernel(const v2d* __r
         // LAST block: it holds the fewest tiles (the ragged tail, or one tile less than the first blocks), so the detour is
         // taken from its slack instead of from the kernel's critical path.
         const bool publisher = (b == G - 1);
-        const Scalars sc = scalars_from_total<AosInputT<2>>(h.total, guess, in, N, Lx, Ly, Lz, prm, publisher);
+        const Scalars sc = scalars_from_total<AosInputT<NT_LOAD>>(h.total, guess, in, N, Lx, Ly, Lz, prm, publisher);
         if (tid == 0)
         {
             park_scalars(s_m, s_mi, sc, h.ok);

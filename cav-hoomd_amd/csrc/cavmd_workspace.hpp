@@ -57,7 +57,9 @@ struct cavmd_workspace : WorkspaceTie // device and dependents: what the batch o
     int reduce_blocks_per_cu = 1; // <= 256 partials: the fused force map folds them with one load per thread
     int map_blocks_per_cu = 2;    // every fused block re-folds the partials, so few, long-lived blocks
     int map_nt_store = -1;        // -1 auto (non-temporal from kNtStoreMinN particles up), 0 plain, 1 non-temporal, 2 write-through
-    int reduce_nt_load = -1;      // -1 auto, 0 plain, 1 pos+image non-temporal, 2 all non-temporal
+    int reduce_nt_load = -1;      // -1 auto, 0 plain, 1 pos+image non-temporal, 2 all non-temporal.  The two-launch reduction
+                                  // only: the single launch always reads with policy 1 (a third dispatch dimension would
+                                  // triple its instantiations, and it never runs where the charges outgrow the cache)
     int fused_finalize = 1;       // 1: two launches (finalize folded into the force map), 0: three launches
     int map_reverse = -1;         // -1 auto, 1: the force map walks its tiles last-to-first, 0: first-to-last
     int small_system_max_n = kSmallSystemMaxN; // at or below this N: one single-block launch does everything; 0 disables

@@ -1,7 +1,8 @@
 // microbench_persistent.hip -- developer tool (not part of the product or of bench.py): the single-launch evaluation
 // (cavmd_persistent_kernel.hpp) against the two-launch path, interleaved round by round on HBM-cold frames, plus a
 // per-block time line of the single-launch kernel (wall_clock64 stamps, 10 ns resolution): entry, first tile row issued,
-// phase 1 done, and the points of the hand-off and the map.
+// phase 1 done, and the points of the hand-off and the map.  The single-launch kernel runs with the product's load policy
+// (NT_LOAD 1: charges temporal) and with NT_LOAD 2 (charges non-temporal as well), in the rounds and in a time line each.
 //
 //   ./microbench_persistent [N=1000001] [frames=7] [rounds=9] [launches_per_round=20]
 #include <hip/hip_runtime.h>
@@ -136,8 +137,9 @@ int main(int argc, char** argv)
     while (unroll > 1 && N / ((size_t)256 * unroll) < (size_t)CU * 5 / 4)
         unroll >>= 1;
     const bool nts = N >= 200000;
-#define ALLOW(UNR, NTS) CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, UNR, NTS>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
-    ALLOW(1, false); ALLOW(1, true); ALLOW(2, false); ALLOW(2, true);
+#define ALLOW(UNR, NTS, NTL) CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cavity_persistent_kernel<256, UNR, NTS, false, NTL>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
+    ALLOW(1, false, 1); ALLOW(1, true, 1); ALLOW(2, false, 1); ALLOW(2, true, 1);
+    ALLOW(1, false, 2); ALLOW(1, true, 2); ALLOW(2, false, 2); ALLOW(2, true, 2);
 
     std::vector<Variant> V;
     // the product's two-launch sequence
@@ -153,7 +155,8 @@ int main(int argc, char** argv)
                      else
                          hipLaunchKernelGGL((force_map_aos_fused_kernel<256, 4, false>), dim3(g2), dim3(256), 0, st, in0(f).pos2, in0(f).charge, in0(f).image, part.d, part.i, n, g2, 0, g1, part.stride, 2, L, L, L, P, 1ull, d_res, d_hres, (v2d*)d_frc[f]);
                  }, {}});
-    auto persist = [&](int f, int bpc, int balanced = 0) {
+    // ntl: the kernel's load policy (AosInputT): 1 = the product's (charges temporal), 2 = charges non-temporal as well
+    auto persist = [&](int f, int bpc, int balanced = 0, int ntl = 1) {
         const unsigned g1 = grid(N, 256 * unroll, bpc);
         const size_t tile = 256 * unroll;
         size_t slots = ((N + tile - 1) / tile + g1 - 1) / g1;
@@ -161,12 +164,26 @@ int main(int argc, char** argv)
         const size_t cap = (156 * 1024 - 1024) / (tile * 8);
         const unsigned lds_slots = (unsigned)std::min(slots, cap);
         const size_t lds = (size_t)lds_slots * tile * 8;
-#define PL(UNR, NTS) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS>), dim3(g1), dim3(256), lds, st, in2(f).pos2, in2(f).charge, in2(f).image, sync.epoch, n, g1, 2, lds_slots | (balanced ? kBalancedBit : 0u), L, L, L, P, rest_of(sync), 1ull, d_res, d_hres, (v2d*)d_frc[f])
-        if (unroll == 2) { if (nts) PL(2, true); else PL(2, false); }
-        else { if (nts) PL(1, true); else PL(1, false); }
+#define PL(UNR, NTS, NTL) hipLaunchKernelGGL((cavity_persistent_kernel<256, UNR, NTS, false, NTL>), dim3(g1), dim3(256), lds, st, in2(f).pos2, in2(f).charge, in2(f).image, sync.epoch, n, g1, 2, lds_slots | (balanced ? kBalancedBit : 0u), L, L, L, P, rest_of(sync), 1ull, d_res, d_hres, (v2d*)d_frc[f])
+#define PLS(UNR, NTS) do { if (ntl == 2) PL(UNR, NTS, 2); else PL(UNR, NTS, 1); } while (0)
+        if (unroll == 2) { if (nts) PLS(2, true); else PLS(2, false); }
+        else { if (nts) PLS(1, true); else PLS(1, false); }
     };
     V.push_back({"single launch, tiles dealt round-robin", [&](int f) { persist(f, 1, 0); }, {}});
+    V.push_back({"single launch, round-robin, charges non-temporal", [&](int f) { persist(f, 1, 0, 2); }, {}});
     V.push_back({"single launch, balanced contiguous shares", [&](int f) { persist(f, 1, 1); }, {}});
+
+    // Between two variants the caches are put into the state the NEXT variant leaves behind in steady use: a 512 MiB fill
+    // evicts what the previous variant kept in the Infinity Cache (temporal charge lines outlive non-temporal traffic, so the
+    // variant with non-temporal charges would otherwise find the other's lines), then one untimed pass over the ring.
+    char* d_flush = nullptr;
+    const size_t flush_bytes = (size_t)512 << 20;
+    CHECK(hipMalloc((void**)&d_flush, flush_bytes));
+    auto settle = [&](const std::function<void(int)>& launch) {
+        CHECK(hipMemsetAsync(d_flush, 0, flush_bytes, st));
+        for (int f = 0; f < frames; ++f) launch(f);
+        CHECK(hipDeviceSynchronize());
+    };
 
     {
         // every variant must give the bits of the first one (the product's two-launch path) in every force entry -- except the
@@ -200,6 +217,7 @@ int main(int argc, char** argv)
     {
         for (auto& v : V)
         {
+            settle(v.launch);
             CHECK(hipEventRecord(e0, st));
             for (int k = 0; k < per_round; ++k) { v.launch(frame); frame = (frame + 1) % frames; }
             CHECK(hipEventRecord(e1, st));
@@ -221,9 +239,10 @@ int main(int argc, char** argv)
     // CAVMD_TIMELINE_PARTITION=1: the balanced partition instead of the strided one
     const int timeline_partition = getenv("CAVMD_TIMELINE_PARTITION") && atoi(getenv("CAVMD_TIMELINE_PARTITION")) == 1;
     printf("time line of the variant with partition %d\n", timeline_partition);
-    for (int mode = 0; mode < 1; ++mode)
+    for (int ntl : {1, 2}) // the product's load policy, then charges non-temporal as well
     {
         const unsigned g1 = grid(N, 256 * unroll, 1);
+        settle([&](int f) { persist(f, 1, timeline_partition, ntl); });
         const char* names[kStampSlots] = {"start", "phase1 done", "block tree done", "total in wave 0", "scalars in LDS",
                                           "barrier passed", "stores issued", "group level done", "first tile row issued"};
         std::vector<std::vector<double>> med(kStampSlots), mx(kStampSlots), mnv(kStampSlots);
@@ -231,7 +250,7 @@ int main(int argc, char** argv)
         std::vector<int> xcc_frame(30, 0);
         for (int rep = 0; rep < 30; ++rep)
         {
-            for (int k = 0; k < 12; ++k) persist((rep + k) % frames, 1, timeline_partition); // steady state: the stamps are those of the last launch
+            for (int k = 0; k < 12; ++k) persist((rep + k) % frames, 1, timeline_partition, ntl); // steady state: the stamps are those of the last launch
             CHECK(hipDeviceSynchronize());
             std::vector<unsigned long long> h(4096 * kStampSlots);
             CHECK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_pstamps), sizeof(unsigned long long) * h.size()));
@@ -284,8 +303,8 @@ int main(int argc, char** argv)
         }
         printf("  mean phase-1-done per XCC_ID (us), one row per run (12 back-to-back launches each, stamps of the last):\n");
         for (int rep = 0; rep < 30; ++rep) { printf("   run %2d (frame %d):", rep, xcc_frame[rep]); for (int x = 0; x < 8; ++x) printf(" %6.2f", xcc_p1[rep][x]); printf("\n"); }
-        printf("time line, single launch, grid %u (us after the first block's start; median over 30 runs of the per-run min / median / max over blocks)\n",
-               g1);
+        printf("time line, single launch, %s, grid %u (us after the first block's start; median over 30 runs of the per-run min / median / max over blocks)\n",
+               ntl == 2 ? "charges non-temporal (NT_LOAD 2)" : "charges temporal (NT_LOAD 1, the product)", g1);
         for (int k : {0, 8, 1, 2, 7, 3, 4, 5, 6})
         {
             std::sort(med[k].begin(), med[k].end()); std::sort(mx[k].begin(), mx[k].end()); std::sort(mnv[k].begin(), mnv[k].end());
