@@ -10,7 +10,8 @@
 //              0x80000000 + b), b = 0, 1; `draws` is the item's counter in DEVICE memory, read when the kernel runs
 //   variates   u_x from w0,w1 and u_y from w2,w3 of block 0, u_z from w0,w1 of block 1, each 2 * (k * 2^-53) - 1
 //   bath       coeff_j = sqrt(((6 gamma_j) kT) / dt);  bd_c = u_c coeff_j - gamma_j v_c (v from BEFORE the kick);  F_c += bd_c;
-//              tally_j = (bd_x v_x + bd_y v_y) + bd_z v_z
+//              tally_j = (bd_x v'_x + bd_y v'_y) + bd_z v'_z, v' being the velocity the kernel stores (AFTER the kick): the
+//              work the bath does on the particle over the half-step, whose mean is 0 at the bath's temperature
 //   per item   coupled = their number;  T = the double-double sum of the tallies in an order fixed by N (lane-serial over the
 //              tiles, then block_tally of cavmd_reduce.hpp: a shuffle tree over the wave, the four waves in wave order), rounded
 //              once;  reservoir -= T dt;  draws += 1
@@ -171,35 +172,33 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_bath_kernel(const Verle
                 net2[2 * (size_t)j + 1] = Fzw;
             }
             double Fx = Fxy.x, Fy = Fxy.y, Fz = Fzw.x;
-            if ((int)j == langevin)
+            double bdx = 0.0, bdy = 0.0, bdz = 0.0;
+            const bool of_row = (int)j == langevin;
+            const bool of_group = !of_row && g[u] > 0.0; // NaN, 0, negative, beyond bath N: not coupled
+            if (of_row)
             {
                 // the row's bath of the one cavity particle, as verlet_step_two_kernel has it; it wins over the group's
-                const double vx = vxy[u].x, vy = vxy[u].y, vz = vzw[u].x;
-                const double bdx = ux * coeff - gamma * vx;
-                const double bdy = uy * coeff - gamma * vy;
-                const double bdz = uz * coeff - gamma * vz;
-                Fx = Fx + bdx;
-                Fy = Fy + bdy;
-                Fz = Fz + bdz;
-                const double tally = (bdx * vx + bdy * vy) + bdz * vz;
-                state_all[item].reservoir = state_all[item].reservoir - tally * dt;
+                bdx = ux * coeff - gamma * vxy[u].x;
+                bdy = uy * coeff - gamma * vxy[u].y;
+                bdz = uz * coeff - gamma * vzw[u].x;
             }
-            else if (g[u] > 0.0) // NaN, 0, negative, beyond bath N: not coupled
+            else if (of_group)
             {
                 const double gj = g[u];
                 // the counter layout restates DrawStream::block (see above)
                 const uint4 w0 = draw_philox(make_uint4((unsigned)draws, (unsigned)(draws >> 32), j, kBathPurpose), key);
                 const uint4 w1 = draw_philox(make_uint4((unsigned)draws, (unsigned)(draws >> 32), j, kBathPurpose + 1u), key);
                 const double cj = sqrt(((6.0 * gj) * kT) / dt);
-                const double vx = vxy[u].x, vy = vxy[u].y, vz = vzw[u].x; // from BEFORE the kick
-                const double bdx = (2.0 * draw_unit(w0.x, w0.y) - 1.0) * cj - gj * vx;
-                const double bdy = (2.0 * draw_unit(w0.z, w0.w) - 1.0) * cj - gj * vy;
-                const double bdz = (2.0 * draw_unit(w1.x, w1.y) - 1.0) * cj - gj * vz;
+                // the force from the velocity BEFORE the kick
+                bdx = (2.0 * draw_unit(w0.x, w0.y) - 1.0) * cj - gj * vxy[u].x;
+                bdy = (2.0 * draw_unit(w0.z, w0.w) - 1.0) * cj - gj * vxy[u].y;
+                bdz = (2.0 * draw_unit(w1.x, w1.y) - 1.0) * cj - gj * vzw[u].x;
+            }
+            if (of_row || of_group)
+            {
                 Fx = Fx + bdx;
                 Fy = Fy + bdy;
                 Fz = Fz + bdz;
-                dd_acc(t_hi, t_lo, (bdx * vx + bdy * vy) + bdz * vz);
-                coupled += 1;
             }
             const double ax = Fx * minv, ay = Fy * minv, az = Fz * minv;
             accel[3 * (size_t)j] = ax;
@@ -207,8 +206,20 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_bath_kernel(const Verle
             accel[3 * (size_t)j + 2] = az;
             vxy[u].x = vxy[u].x + (0.5 * ax) * dt;
             vxy[u].y = vxy[u].y + (0.5 * ay) * dt;
+            const double vz = vzw[u].x + (0.5 * az) * dt;
             vel2[2 * (size_t)j] = vxy[u];
-            reinterpret_cast<double*>(vel2)[4 * (size_t)j + 2] = vzw[u].x + (0.5 * az) * dt; // vel.w is never written
+            reinterpret_cast<double*>(vel2)[4 * (size_t)j + 2] = vz; // vel.w is never written
+            // the tallies, with the velocity just stored (AFTER the kick)
+            if (of_row)
+            {
+                const double tally = (bdx * vxy[u].x + bdy * vxy[u].y) + bdz * vz;
+                state_all[item].reservoir = state_all[item].reservoir - tally * dt;
+            }
+            else if (of_group)
+            {
+                dd_acc(t_hi, t_lo, (bdx * vxy[u].x + bdy * vxy[u].y) + bdz * vz);
+                coupled += 1;
+            }
         }
     }
     if (threadIdx.x == 0)

@@ -283,21 +283,18 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_kernel(const VerletRow*
                 net2[2 * (size_t)j + 1] = Fzw;
             }
             double Fx = Fxy.x, Fy = Fxy.y, Fz = Fzw.x;
+            double bdx = 0.0, bdy = 0.0, bdz = 0.0;
             if constexpr (!ACCEL_ONLY)
             {
                 if ((int)j == langevin)
                 {
-                    // the bath of the one cavity particle, with the velocity from BEFORE the kick; this lane owns the
-                    // item's reservoir word
-                    const double vx = vxy[u].x, vy = vxy[u].y, vz = vzw[u].x;
-                    const double bdx = ux * coeff - gamma * vx;
-                    const double bdy = uy * coeff - gamma * vy;
-                    const double bdz = uz * coeff - gamma * vz;
+                    // the bath of the one cavity particle: the force from the velocity BEFORE the kick
+                    bdx = ux * coeff - gamma * vxy[u].x;
+                    bdy = uy * coeff - gamma * vxy[u].y;
+                    bdz = uz * coeff - gamma * vzw[u].x;
                     Fx = Fx + bdx;
                     Fy = Fy + bdy;
                     Fz = Fz + bdz;
-                    const double tally = (bdx * vx + bdy * vy) + bdz * vz;
-                    state_all[item].reservoir = state_all[item].reservoir - tally * dt;
                 }
             }
             const double ax = Fx * minv, ay = Fy * minv, az = Fz * minv;
@@ -308,8 +305,15 @@ __global__ __launch_bounds__(BLOCK) void verlet_step_two_kernel(const VerletRow*
             {
                 vxy[u].x = vxy[u].x + (0.5 * ax) * dt;
                 vxy[u].y = vxy[u].y + (0.5 * ay) * dt;
+                const double vz = vzw[u].x + (0.5 * az) * dt;
                 vel2[2 * (size_t)j] = vxy[u];
-                reinterpret_cast<double*>(vel2)[4 * (size_t)j + 2] = vzw[u].x + (0.5 * az) * dt; // vel.w is never written
+                reinterpret_cast<double*>(vel2)[4 * (size_t)j + 2] = vz; // vel.w is never written
+                if ((int)j == langevin)
+                {
+                    // the tally, with the velocity just stored (AFTER the kick); this lane owns the item's reservoir word
+                    const double tally = (bdx * vxy[u].x + bdy * vxy[u].y) + bdz * vz;
+                    state_all[item].reservoir = state_all[item].reservoir - tally * dt;
+                }
             }
         }
     }

@@ -95,6 +95,11 @@ def main():
     print(f"drift of H + reservoirs over {steps} steps, relative to max |H|: worst system {np.abs(drift / scale).max():.3e}, "
           f"mean {np.abs(drift / scale).mean():.3e}")
     # the same quantity as a series: the ledger's universe_total of every step (its reservoirs are those the step's kernels saw)
+    # What a healthy value looks like: the excursion does not grow with the length of the run.  The Langevin tally is taken with
+    # the velocity from after the kick, so each reservoir holds exactly what its bath took, and what a row shows is the
+    # integrator's own error plus a zero-mean offset of the photon's bath (the row is taken between the bath force's two
+    # half-kicks) of the order of sqrt(gamma dt) kT, a few 1e-5 hartree here.  A reservoir tallied before the kick would add
+    # 3 gamma kT t / m = 9.5e-7 hartree per unit of time: 4.8e-3 hartree over 1000 steps (tests/thermostatted_twin.py).
     universe = energy["universe_total"]
     excursion = np.abs(universe - universe[:, :1]).max(axis=1) / np.abs(energy["system_total"]).max(axis=1)
     print(f"universe_total over the whole series, worst excursion from its first row relative to max |system_total|: worst system "

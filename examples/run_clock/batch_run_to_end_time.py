@@ -109,6 +109,10 @@ def main():
     print(f"F(k,t) rows per replica {int(fields.rows().min())} .. {int(fields.rows().max())}, references "
           f"{int(fkt['n_references'][:, -1].min())} .. {int(fkt['n_references'][:, -1].max())}; longest lag {np.nanmax(lags):.1f}; "
           f"F / F(0) of replica 0 against its first reference: {np.round(fkt['F'][0, :4, 0] / fkt['rho2'][0, 0], 3).tolist()} ...")
+    # A healthy value does not grow with the end time: the reservoirs hold exactly what the baths took (the Langevin tally is
+    # taken with the velocity from after the kick), so this is the integrator's own error plus a zero-mean offset of the
+    # photon's bath of the order of sqrt(gamma dt) kT.  A reservoir tallied before the kick would add 3 gamma kT t / m,
+    # 9.5e-7 hartree per unit of time (tests/thermostatted_twin.py).
     drift = np.abs(series["universe_total"][:, -1] - series["universe_total"][:, 0])
     print(f"|change of the conserved energy| over the run: at most {drift.max():.3e} hartree")
     again = draw.state()

@@ -711,10 +711,11 @@ CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cav
  *     2. F_c = ((f0_c + f1_c) + f2_c) + f3_c over the force arrays present
  *     3. d_net_force, if given, receives (F_x, F_y, F_z, the same left-to-right sum of .w)
  *     4. for j == langevin_index with langevin_gamma != 0, v being the velocity from BEFORE the kick:
- *        bd_c = uniform_c * langevin_coeff - langevin_gamma * v_c;  F_c = F_c + bd_c;
- *        tally = (bd_x * v_x + bd_y * v_y) + bd_z * v_z;  langevin_reservoir = langevin_reservoir - tally * dt
+ *        bd_c = uniform_c * langevin_coeff - langevin_gamma * v_c;  F_c = F_c + bd_c
  *     5. a_c = F_c * minv, stored to d_accel
- *     6. v_c = v_c + (0.5 * a_c) * dt
+ *     6. v'_c = v_c + (0.5 * a_c) * dt, stored to d_vel; then, for the particle of item 4, with v' the velocity just stored
+ *        (from AFTER the kick):
+ *        tally = (bd_x * v'_x + bd_y * v'_y) + bd_z * v'_z;  langevin_reservoir = langevin_reservoir - tally * dt
  *     7. steps += 1
  *   cavmd_verlet_accelerations is 1, 2, 3 and 5 only: no Langevin, no kick, nothing counted, no input row.
  * What item 4 amounts to.  `uniform` must be FRESH for every step and every item: three new variates, uniform in [-1, 1)
@@ -723,9 +724,13 @@ CAVMD_API int cavmd_field_recorder_device_ptr(cavmd_field_recorder* r, const cav
  * with x = langevin_gamma * dt / (2 m), 0 < x < 1, the stationary state has, per component:
  *     after step two   m <v^2> = kT, for any dt        (the kick is v' = (1 - x) v + n with <n^2> = x kT / m)
  *     after step one   m <v^2> (1 - x) = kT            (the half-step velocity, the one item 4 reads)
- *     langevin_reservoir grows by 3 gamma kT dt / (m (1 - x)) per step on average, because the tally is taken with the
- *     velocity from BEFORE the kick, with which the step's variates are uncorrelated.
- * (tests/langevin_twin.py derives the three; tests/test_gpu_langevin_batch.py holds the kernels to them.)
+ *     langevin_reservoir gains 0 per step on average, for every 0 < x < 1: bd acts through this kick and the next step's first
+ *     kick with one acceleration, v -> v' -> v'', v + v'' = 2 v', so bd . v' dt is exactly the kinetic energy it gives, and
+ *     -tally * dt what the bath took.  cavmd_ledger_row.universe_total is therefore conserved to the integrator's own error.
+ *     (Taken with the velocity from BEFORE the kick, as versions of this header before the ledger's column was rehearsed had
+ *     it, the tally misses the noise's heating and the reservoir grows by 3 gamma kT dt / (m (1 - x)) per step.)
+ * (tests/langevin_twin.py derives the three and the reservoir's spread; tests/test_gpu_langevin_batch.py holds the kernels to
+ * them; tests/thermostatted_twin.py and tests/test_gpu_conserved_energy.py hold the ledger's column to its band.)
  * pos.w (the type tag) and vel.w (the mass) are never written.  Langevin on more than one particle per system is the next
  * section's (cavmd_bath_*: the 3 N variates are drawn inside step two).  Out of scope: rotational degrees of freedom, triclinic
  * boxes. */
@@ -820,8 +825,9 @@ CAVMD_API int cavmd_verlet_state_device_ptr(cavmd_verlet* v, const cavmd_verlet_
  *   2. Variates, as the next section's item 2: u_x from w0,w1 and u_y from w2,w3 of block 0, u_z from w0,w1 of block 1, each
  *      2 * (k * 2^-53) - 1, in [-1, 1).
  *   3. coeff_j = sqrt(((6 * gamma_j) * kT) / dt), division and square root correctly rounded.
- *   4. bd_c = u_c * coeff_j - gamma_j * v_c with v from BEFORE the kick;  F_c = F_c + bd_c;
- *      tally_j = (bd_x * v_x + bd_y * v_y) + bd_z * v_z
+ *   4. bd_c = u_c * coeff_j - gamma_j * v_c with v from BEFORE the kick;  F_c = F_c + bd_c;  then the integrator's items 5
+ *      and 6, and with v' the velocity item 6 stores (from AFTER the kick):
+ *      tally_j = (bd_x * v'_x + bd_y * v'_y) + bd_z * v'_z
  *   5. Per item: coupled = the number of such particles; T = the sum of their tally_j, a compensated (double-double) sum in an
  *      order that depends on N only -- not on the batch, the item's place in it, the compute unit, or eager launch versus graph
  *      replay -- rounded once, within 2 ulp of the exact sum of those addends;  reservoir = reservoir - T * dt;  draws += 1.

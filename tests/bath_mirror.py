@@ -42,9 +42,11 @@ def coupled_particles(s, row, bath) -> np.ndarray:
     return np.nonzero(on)[0]
 
 
-def mirror_bath_step_two(s, row, bath, uniforms=None):
+def mirror_bath_step_two(s, row, bath, uniforms=None, tally_velocity="after"):
     """Step two with the bath.  Returns (tallies of the coupled particles, fsum of them), or None where the item is left
-    untouched.  uniforms: None (the contract's Philox variates) or a callable (j -> (len(j), 3)) for planted mistakes."""
+    untouched.  uniforms: None (the contract's Philox variates) or a callable (j -> (len(j), 3)) for planted mistakes.
+    tally_velocity: "after" is the contract; "before" is verlet_mirror.mirror_step_two's planted mistake, for the twins."""
+    assert tally_velocity in ("after", "before")
     if s["N"] == 0 or row.skip:
         return None
     dt, gamma, coeff = np.float64(row.dt), np.float64(row.langevin_gamma), np.float64(row.langevin_coeff)
@@ -54,13 +56,12 @@ def mirror_bath_step_two(s, row, bath, uniforms=None):
         s["net"] = F.copy()                                  # without any bath term
     F = F[:, :3].copy()
     j = s["langevin"]
-    if j >= 0 and gamma != 0.0:                              # the row's bath, as verlet_mirror.mirror_step_two has it
-        v = s["vel"][j, :3].copy()
-        bd = np.array(row.uniform[:], dtype=np.float64) * coeff - gamma * v
-        F[j] = F[j] + bd
-        tally = (bd[0] * v[0] + bd[1] * v[1]) + bd[2] * v[2]
-        s["reservoir"] = s["reservoir"] - tally * dt
-    tallies = np.zeros(0)
+    bathed = j >= 0 and gamma != 0.0
+    if bathed:                                               # the row's bath, as verlet_mirror.mirror_step_two has it
+        before_row = s["vel"][j, :3].copy()
+        bd_row = np.array(row.uniform[:], dtype=np.float64) * coeff - gamma * before_row
+        F[j] = F[j] + bd_row
+    on = np.zeros(0, dtype=np.int64)
     if bath["gamma"] is not None:
         on = coupled_particles(s, row, bath)
         if len(on):
@@ -68,16 +69,24 @@ def mirror_bath_step_two(s, row, bath, uniforms=None):
             u = variates(bath["seed"], bath["draws"], on) if uniforms is None else uniforms(on)
             with np.errstate(invalid="ignore", divide="ignore"):
                 c = np.sqrt(((6.0 * g) * np.float64(bath["kT"])) / dt)
-            v = s["vel"][on, :3].copy()                      # from BEFORE the kick
-            bd = u * c[:, None] - g[:, None] * v
+            before = s["vel"][on, :3].copy()                 # the force: from BEFORE the kick
+            bd = u * c[:, None] - g[:, None] * before
             F[on] = F[on] + bd
+    a = F * minv[:, None]
+    s["accel"] = a
+    s["vel"][:, :3] = s["vel"][:, :3] + (0.5 * a) * dt
+    if bathed:                                               # the tallies: from AFTER the kick, the velocity just stored
+        v = s["vel"][j, :3] if tally_velocity == "after" else before_row
+        tally = (bd_row[0] * v[0] + bd_row[1] * v[1]) + bd_row[2] * v[2]
+        s["reservoir"] = s["reservoir"] - tally * dt
+    tallies = np.zeros(0)
+    if bath["gamma"] is not None:
+        if len(on):
+            v = s["vel"][on, :3] if tally_velocity == "after" else before
             tallies = (bd[:, 0] * v[:, 0] + bd[:, 1] * v[:, 1]) + bd[:, 2] * v[:, 2]
         T = np.float64(math.fsum(tallies.tolist()))
         bath["coupled"] = len(on)
         bath["reservoir"] = bath["reservoir"] - T * dt
         bath["draws"] += 1
-    a = F * minv[:, None]
-    s["accel"] = a
-    s["vel"][:, :3] = s["vel"][:, :3] + (0.5 * a) * dt
     s["steps"] += 1
     return tallies, (math.fsum(tallies.tolist()) if bath["gamma"] is not None else 0.0)

@@ -12,18 +12,18 @@ from types import SimpleNamespace
 import numpy as np
 
 import bath_mirror
-from langevin_twin import BOX, BURN_IN, COUNTED, DT, GAMMA, KT, MASS, closed_forms, ratios  # noqa: F401
+from langevin_twin import BOX, BURN_IN, COUNTED, DT, EXPECTED, GAMMA, KT, MASS, closed_forms, member_sd, ratios  # noqa: F401
 from verlet_mirror import mirror_step_one
 
 SIZES = (1, 2, 513)
 PARTICLES = sum(SIZES)
-MISTAKES = ("frozen_step_counter",)
-# The acceptance band of the three ratios (measured / closed form) in tests/test_gpu_bath_batch.py: 6 standard deviations across
-# the 24 seeds of `run` at these very sizes, steps and parameters, as printed by tests/test_bath_abi.py (which fails if these
-# literals are not that run's figures).  Not from a GPU run.  That run: seeds 0..23, standard deviations 0.00165, 0.00136,
-# 0.00134 around means 0.99958, 0.99961, 0.99972, worst single seed 0.0033 from 1.
-BAND = (0.0099, 0.0082, 0.0081)
-
+MISTAKES = ("frozen_step_counter", "tally_with_pre_kick_velocity")
+# The acceptance band of the three figures around langevin_twin.EXPECTED = (1, 1, 0) in tests/test_gpu_bath_batch.py: 6 standard
+# deviations across the 24 seeds of `run` at these very sizes, steps and parameters, as printed by tests/test_bath_abi.py (which
+# fails if these literals are not that run's figures).  Not from a GPU run.  That run: seeds 0..23, standard deviations 0.00165,
+# 0.00136, 0.000069 around means 0.99958, 0.99961, -0.00001, worst single seed 0.0033 from the expected.
+BAND = (0.0099, 0.0082, 0.000411)
+BAND_DIGITS = (0.5e-4, 0.5e-4, 0.5e-6)      # how closely the literals are held to the run
 
 def systems():
     """the twin's three systems at rest, as dicts of tests/verlet_mirror.py"""
@@ -43,12 +43,14 @@ def baths(seed):
 
 
 def run(seed, mistake=None, burn_in=BURN_IN, counted=COUNTED) -> np.ndarray:
-    """the 516 free particles from rest through burn_in + counted steps -> the three ratios over the counted steps"""
+    """the 516 free particles from rest through burn_in + counted steps -> the three figures of langevin_twin.ratios over the
+    counted steps"""
     assert mistake is None or mistake in MISTAKES
     ss, bs = systems(), baths(seed)
     row = SimpleNamespace(dt=DT, langevin_gamma=0.0, langevin_coeff=0.0, uniform=(0.0, 0.0, 0.0), skip=0)
     sums = np.zeros(2)
     start = 0.0
+    tally_velocity = "before" if mistake == "tally_with_pre_kick_velocity" else "after"
     for step in range(burn_in + counted):
         if step == burn_in:
             sums[:] = 0.0
@@ -59,7 +61,7 @@ def run(seed, mistake=None, burn_in=BURN_IN, counted=COUNTED) -> np.ndarray:
             sums[1] += float((half * half).sum())
             if mistake == "frozen_step_counter":                             # the planted mistake: every step draws block 0
                 b["draws"] = 0
-            bath_mirror.mirror_bath_step_two(s, row, b)
+            bath_mirror.mirror_bath_step_two(s, row, b, tally_velocity=tally_velocity)
             full = s["vel"][:, :3]
             sums[0] += float((full * full).sum())
     assert all(s["steps"] == burn_in + counted and s["out_of_box"] == 0 for s in ss)

@@ -518,8 +518,9 @@ def test_a_capturing_stream_is_refused_as_the_recorders_is():
 def test_forty_full_steps_with_both_baths_row_by_row():
     """B = 2 systems of 27 diatomics and the photon, 40 eager steps of the full step of examples/batch_coulomb_md_in_one_graph.py
     (cavity force, bonds and Lennard-Jones, Ewald Coulomb, the Langevin bath on the photon, the Bussi thermostat on the
-    molecules): after every step the ledger's row is the host's view of the state the kernel saw.  No drift bound is asserted:
-    none has been measured; the example prints the drift."""
+    molecules): after every step the ledger's row is the host's view of the state the kernel saw.  This test holds the row's
+    terms; that their sum, universe_total, is CONSERVED under these baths is asserted by tests/test_gpu_conserved_energy.py,
+    against a band measured on the host twin of this step (tests/thermostatted_twin.py), so no excursion is printed here."""
     B, STEPS, kT, dt = 2, 40, 3.167e-4, 5.0
     rng = np.random.default_rng(0)
     sysdefs, velocities, bonds, bond_typeid = [], [], [], []
@@ -597,9 +598,6 @@ def test_forty_full_steps_with_both_baths_row_by_row():
         for name in ("molecular", "coulomb", "kinetic_group", "kinetic_cavity", "langevin", "universe_total"):
             assert len(set(series[k][name])) == STEPS, name
         assert len(set(series[k]["bussi"])) == STEPS and series[k]["bussi"][0] == 0.0
-        excursion = np.abs(series[k]["universe_total"] - series[k]["universe_total"][0]).max()
-        print(f"system {k}: worst excursion of universe_total over {STEPS} steps {excursion:.3e} (max |system_total| "
-              f"{np.abs(series[k]['system_total']).max():.3e}); not asserted")
     print(f"worst potential term: {worst:.2f} ulp from math.fsum")
     for obj in (ledger, clock, recorder, integrator, coulomb, molecular, cavity):
         obj.close()

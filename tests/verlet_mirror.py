@@ -44,7 +44,10 @@ def mirror_step_one(s, row, classify=None) -> None:
         s["pos"][:, c] = x
 
 
-def mirror_step_two(s, row) -> None:
+def mirror_step_two(s, row, tally_velocity="after") -> None:
+    """tally_velocity: "after" is the contract; "before" (the velocity the force is formed with) is kept as a planted mistake
+    for the twins, under which langevin_reservoir heats by 3 gamma kT dt / m per step and the ledger's total drifts."""
+    assert tally_velocity in ("after", "before")
     if s["N"] == 0 or row.skip:
         return
     dt, gamma, coeff = np.float64(row.dt), np.float64(row.langevin_gamma), np.float64(row.langevin_coeff)
@@ -54,13 +57,16 @@ def mirror_step_two(s, row) -> None:
         s["net"] = F.copy()
     F = F[:, :3].copy()
     j = s["langevin"]
-    if j >= 0 and gamma != 0.0:
-        v = s["vel"][j, :3].copy()                           # from BEFORE the kick
-        bd = np.array(row.uniform[:], dtype=np.float64) * coeff - gamma * v
+    bathed = j >= 0 and gamma != 0.0
+    if bathed:
+        before = s["vel"][j, :3].copy()                      # the force: from BEFORE the kick
+        bd = np.array(row.uniform[:], dtype=np.float64) * coeff - gamma * before
         F[j] = F[j] + bd
-        tally = (bd[0] * v[0] + bd[1] * v[1]) + bd[2] * v[2]
-        s["reservoir"] = s["reservoir"] - tally * dt
     a = F * minv[:, None]
     s["accel"] = a
     s["vel"][:, :3] = s["vel"][:, :3] + (0.5 * a) * dt
+    if bathed:
+        v = s["vel"][j, :3] if tally_velocity == "after" else before   # the tally: from AFTER the kick, the velocity just stored
+        tally = (bd[0] * v[0] + bd[1] * v[1]) + bd[2] * v[2]
+        s["reservoir"] = s["reservoir"] - tally * dt
     s["steps"] += 1
