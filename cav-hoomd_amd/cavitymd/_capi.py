@@ -263,6 +263,9 @@ TRAJECTORY_FORCED, TRAJECTORY_HAS_VELOCITIES = 1, 2     # cavmd_trajectory_heade
 COULOMB_MAX_ITEM_N = 2048
 COULOMB_MAX_K = 4096
 COULOMB_MAX_EXCLUSIONS = 4
+EWALD_RECIPROCAL_DIRECT = 0
+EWALD_RECIPROCAL_FACTORED = 1
+EWALD_RECIPROCAL = {"direct": EWALD_RECIPROCAL_DIRECT, "factored": EWALD_RECIPROCAL_FACTORED}
 MOLECULAR_MAX_ITEM_N = 2048
 MOLECULAR_MAX_BONDS = 4
 FIELD_MAX_WAVEVECTORS = 256
@@ -614,6 +617,9 @@ _PROTOTYPES = {
     "cavmd_runclock_draw_finished": (_ci, [_vp, _vp, _P(_u64)]),
     "cavmd_runclock_ledger_set_rule": (_ci, [_vp, _dbl, _dbl]),
     "cavmd_runclock_field_set_rule": (_ci, [_vp, _vp, _u64, _dbl, _dbl]),
+    "cavmd_ewald_order": (_ci, [_P(_ci)] * 5),
+    "cavmd_ewald_set_reciprocal": (_ci, [_vp, _ci]),
+    "cavmd_ewald_get_reciprocal": (_ci, [_vp, _P(_ci)]),
     "cavmd_device_info": (_ci, [_vp, _P(_ci), _P(_ci), _cstr, _sz]),
     "cavmd_error_string": (_cstr, [_ci]),
     "cavmd_version": (_ci, []),
@@ -1506,6 +1512,15 @@ def coulomb_k_count(item: CoulombItem) -> int:
     return int(K.value)
 
 
+def ewald_order(lib=None):
+    """(TILE, SEG, MAX_M, ROWS, SEGROWS) of the factored reciprocal method: the particles whose phase tables launch 1 holds in
+    LDS at a time, the k-vectors of a segment, the largest |m| per axis, the particles a workgroup of launch 2 owns and the
+    segments a workgroup of launch 1 owns, as the library was compiled."""
+    v = [ctypes.c_int() for _ in range(5)]
+    check((lib or load()).cavmd_ewald_order(*[ctypes.byref(x) for x in v]), "cavmd_ewald_order")
+    return tuple(int(x.value) for x in v)
+
+
 class Coulomb(_ItemTableHandle):
     """Owns one cavmd_coulomb: the Ewald Coulomb forces of B independent small systems in TWO kernel launches (structure
     factors, ceil(K / KROWS) workgroups per system; forces, ceil(N / ROWS)).  Workgroups start by N descending."""
@@ -1518,6 +1533,17 @@ class Coulomb(_ItemTableHandle):
     def compute(self, stream: int = 0) -> None:
         """Two kernels: every structure factor, then every entry of every item's force array."""
         check(self._lib.cavmd_coulomb_compute(self._h, ctypes.c_void_p(stream)), "cavmd_coulomb_compute")
+
+    def set_reciprocal(self, method: int) -> None:
+        """Which two kernels ``compute`` enqueues from now on: EWALD_RECIPROCAL_DIRECT or EWALD_RECIPROCAL_FACTORED.  Raises
+        CavmdError (CAVMD_ERR_CAPACITY, nothing changed) when an item's largest |m| exceeds the factored method's limit."""
+        check(self._lib.cavmd_ewald_set_reciprocal(self._h, int(method)), "cavmd_ewald_set_reciprocal")
+
+    @property
+    def reciprocal(self) -> int:
+        method = ctypes.c_int()
+        check(self._lib.cavmd_ewald_get_reciprocal(self._h, ctypes.byref(method)), "cavmd_ewald_get_reciprocal")
+        return int(method.value)
 
     def structure_device_ptr(self):
         """(device address of the structure-factor table, per-item offsets in entries of two doubles): item i owns K_i + 1

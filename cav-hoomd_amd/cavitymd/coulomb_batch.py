@@ -4,7 +4,8 @@ The reference's driver adds the pair of forces returned by ``make_pppm_coulomb_f
 (examples/05_advanced_run.py:598-608): HOOMD-blue's PPPM, a mesh approximation of the Ewald sum.  For systems of at most 2048
 particles the sum itself is cheaper than a mesh, so this class is the Ewald sum (``cavmd_coulomb_compute``; the expressions are
 spelled out in include/cavmd.h): real space over all pairs out of LDS, reciprocal space as a direct sum over the kept
-k-vectors.  It is the twin of ``MolecularForceBatch``, and its force arrays are further forces of the integrator's items::
+k-vectors -- with one sincos per (particle, k), or with ``reciprocal="factored"`` from per-axis phase factors.  It is the
+twin of ``MolecularForceBatch``, and its force arrays are further forces of the integrator's items::
 
     coulomb = CoulombForceBatch(sysdefs, exclusions=bonds, r_cut=12.0, accuracy=1e-6)
     integrator = VerletBatch(cavity, velocities, extra_forces=[[m, c] for m, c in zip(molecular.forces, coulomb.forces)])
@@ -27,10 +28,14 @@ class CoulombForceBatch(ForceBatchBase):
     """sysdefs: the systems (positions, charges -- ``getCharges()`` -- and boxes are taken from them; all on one GPU);
     exclusions: per system an (n, 2) integer array of pairs whose Coulomb interaction is removed (the bonds), or None;
     r_cut: the real-space cut-off, at most half the shortest box length; then either ``accuracy`` (kappa and k_cut follow from
-    ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``.  ``compute`` is TWO kernels; column 3 of a force array is the
-    particle's share of the Coulomb energy."""
+    ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``.  ``reciprocal``: "direct" (one sincos per particle and
+    k-vector) or "factored" (per-axis phase factors, ``cavmd_ewald_set_reciprocal``; same expressions, results within the
+    rounding bound, not the same bits).  ``compute`` is TWO kernels; column 3 of a force array is the particle's share of the
+    Coulomb energy."""
 
-    def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None):
+    def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None, reciprocal="direct"):
+        if reciprocal not in _capi.EWALD_RECIPROCAL:
+            raise ValueError(f"reciprocal: one of {sorted(_capi.EWALD_RECIPROCAL)}, not {reciprocal!r}")
         pds = self._systems(sysdefs)
         self._need_gpu(pds, lambda pd: (pd.getPositions(), pd.getCharges()), "position and charge")
         if (accuracy is None) == (kappa is None or k_cut is None) or (accuracy is not None and (kappa is not None or k_cut is not None)):
@@ -67,8 +72,40 @@ class CoulombForceBatch(ForceBatchBase):
                     raise ValueError(f"system {k}: k_cut = {self.k_cut:.4g} keeps more than {_capi.COULOMB_MAX_K} k-vectors in its box; "
                                      "ask for a coarser accuracy or a larger r_cut") from e
                 raise
+        self._boxes = [tuple(float(l) for l in pd.getGlobalBox().getL()) for pd in pds]
         self._open(self._device, lambda ws: _capi.Coulomb(ws, items))
+        try:
+            self.set_reciprocal(reciprocal)
+        except Exception:
+            self.close()
+            raise
 
     @property
     def coulomb(self) -> _capi.Coulomb:
         return self._handle
+
+    @property
+    def reciprocal(self) -> str:
+        """"direct" or "factored": how ``compute`` obtains cos(k.x) and sin(k.x)."""
+        method = self._need().reciprocal
+        return next(name for name, value in _capi.EWALD_RECIPROCAL.items() if value == method)
+
+    def set_reciprocal(self, name: str) -> None:
+        """Selects the reciprocal-space method of later ``compute`` calls (a launch already captured keeps its own).  Not during
+        a stream capture.  A system whose k-vectors reach beyond the factored method's per-axis limit raises ValueError and
+        leaves the method as it was."""
+        if name not in _capi.EWALD_RECIPROCAL:
+            raise ValueError(f"reciprocal: one of {sorted(_capi.EWALD_RECIPROCAL)}, not {name!r}")
+        try:
+            self._need().set_reciprocal(_capi.EWALD_RECIPROCAL[name])
+        except _capi.CavmdError as e:
+            if e.status != _capi.CAVMD_ERR_CAPACITY:
+                raise
+            max_m = _capi.ewald_order()[2]
+            for k, box in enumerate(self._boxes):
+                for axis, length in zip("xyz", box):
+                    M = int(self.k_cut * length / (2.0 * np.pi)) if self._sizes[k] else 0
+                    if M > max_m:
+                        raise ValueError(f"system {k}: the k-vectors reach M = {M} along {axis}, beyond the factored method's "
+                                         f"{max_m}; use reciprocal='direct'") from e
+            raise

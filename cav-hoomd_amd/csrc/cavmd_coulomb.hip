@@ -4,6 +4,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 
 #include "cavmd.h"
 #include "cavmd_coulomb_batch_kernel.hpp"
+#include "cavmd_ewald_factored_kernel.hpp"
 #include "cavmd_item_table.hpp"
 
 using namespace cavmd;
@@ -28,12 +30,28 @@ static_assert(kCoulombKSplit == 1 || kCoulombKSplit == 4 || kCoulombKSplit == 16
 static_assert(sizeof(cavmd_coulomb_item) == 96, "coulomb item layout");
 static_assert(CAVMD_COULOMB_MAX_EXCLUSIONS == kCoulombMaxExclusions, "the header's limit is the kernel's");
 static_assert(coulomb_lds_bytes(CAVMD_COULOMB_MAX_ITEM_N) <= 64 * 1024, "the largest system fits the LDS a kernel gets without opt-in");
+// the factored reciprocal method (cavmd_ewald_factored_kernel.hpp): its splits are its own, whatever the direct kernels' are
+constexpr unsigned kEwaldRows = kCoulombBlock / kEwaldJSplit;
+constexpr unsigned kEwaldSegRows = kCoulombBlock / kEwaldKSplit;
+static_assert(CAVMD_EWALD_MAX_M >= 16 && CAVMD_EWALD_MAX_M < 32768, "the driver's geometry needs 11; a segment keeps mx and my in 16 bits");
+static_assert(ewald_structure_lds_bytes(CAVMD_EWALD_MAX_M) <= 64 * 1024 && ewald_structure_lds_bytes(CAVMD_EWALD_MAX_M + 1) > 64 * 1024,
+              "CAVMD_EWALD_MAX_M is the largest limit whose tile of tables fits the LDS a kernel gets without opt-in");
+static_assert(ewald_force_lds_bytes(CAVMD_COULOMB_MAX_ITEM_N, CAVMD_EWALD_MAX_M, kEwaldRows) <= 64 * 1024, "launch 2 as well");
 constexpr double kCoulombPi = 3.141592653589793;
 constexpr double kCoulombSqrtPi = 1.7724538509055159;
 
+// what the factored method needs of an item's k-vectors: every row (mx, my) of consecutive mz cut into segments of at most
+// kEwaldSegment vectors from its first mz on ({mx | my << 16, first mz, count, first k}), and the largest |m| per axis
+struct EwaldLattice
+{
+    std::vector<uint4> segments;
+    unsigned m[3] = {0, 0, 0};
+};
+
 // The kept k-vectors of an item (whose box and cut-offs have been checked), in the contract's order; stops at `limit` + 1.
 // Every loop visits kept vectors and one more per row, so the work is bounded by the limit whatever k_cut is.
-void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<CoulombK>* out, size_t* count)
+void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<CoulombK>* out, size_t* count,
+                       EwaldLattice* lattice = nullptr)
 {
     const double two_pi = 2.0 * kCoulombPi;
     const double kc2 = it.k_cut * it.k_cut;
@@ -97,6 +115,21 @@ void coulomb_k_vectors(const cavmd_coulomb_item& it, size_t limit, std::vector<C
                     *count = K;
                     return;
                 }
+                if (lattice)
+                {
+                    // (the kept mz of a row are consecutive: k2 grows with |mz|)
+                    std::vector<uint4>& segs = lattice->segments;
+                    const unsigned key = ((unsigned)mx & 0xFFFFu) | (((unsigned)my & 0xFFFFu) << 16);
+                    const unsigned k = (unsigned)(K - 1);
+                    if (!segs.empty() && segs.back().x == key && segs.back().z < (unsigned)kEwaldSegment &&
+                        segs.back().w + segs.back().z == k && (long)(int)segs.back().y + (long)segs.back().z == mz)
+                        segs.back().z += 1;
+                    else
+                        segs.push_back(make_uint4(key, (unsigned)(int)mz, 1u, k));
+                    lattice->m[0] = std::max(lattice->m[0], (unsigned)mx);
+                    lattice->m[1] = std::max(lattice->m[1], (unsigned)std::labs(my));
+                    lattice->m[2] = std::max(lattice->m[2], (unsigned)std::labs(mz));
+                }
                 if (out)
                     out->push_back(CoulombK {kx, ky, kz, ((4.0 * kCoulombPi) / V) * exp(-k2 / four_kappa2) / k2});
             }
@@ -110,6 +143,7 @@ struct CoulombDerived
 {
     std::vector<uint32_t> slots;
     std::vector<CoulombK> ktab;
+    EwaldLattice lattice;
 };
 
 // The status of one item.  `out`, if given, receives the item's derived tables, `out_K` the number of its k-vectors.
@@ -143,10 +177,13 @@ int coulomb_item_status(const cavmd_coulomb_item* it, CoulombDerived* out, size_
         return st;
     size_t K = 0;
     if (out)
+    {
         out->ktab.clear();
+        out->lattice = EwaldLattice();
+    }
     if (it->N != 0)
     {
-        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, out ? &out->ktab : nullptr, &K);
+        coulomb_k_vectors(*it, CAVMD_COULOMB_MAX_K, out ? &out->ktab : nullptr, &K, out ? &out->lattice : nullptr);
         if (K > CAVMD_COULOMB_MAX_K)
             return CAVMD_ERR_CAPACITY;
     }
@@ -185,20 +222,36 @@ struct CoulombTables
     DeviceArray<uint4> k_blocks, blocks, partners;
     DeviceArray<CoulombK> ktab;
     DeviceArray<v2d> structure;
+    DeviceArray<uint4> ewald;      // the factored method's tables, one array (cavmd_ewald_factored_kernel.hpp)
     std::vector<uint32_t> offsets; // per item: its first entry of ktab / structure
     CoulombHeader header;
     unsigned lds_n = 2;
+    unsigned lds_m = 1; // the largest |m| of the table on any axis, at least 1
+    unsigned n_ewald_k_blocks = 0, n_ewald_blocks = 0; // workgroups of the factored launches (header.pad[1] holds both)
 };
+
+// CAVMD_OK, or CAVMD_ERR_CAPACITY for an item the factored method has no LDS for
+int ewald_capacity_status(const EwaldLattice& l)
+{
+    return std::max(l.m[0], std::max(l.m[1], l.m[2])) > (unsigned)CAVMD_EWALD_MAX_M ? CAVMD_ERR_CAPACITY : CAVMD_OK;
+}
 } // namespace
 
 // workgroups by N descending
 struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, CoulombDerived, CoulombTables>
 {
+    int reciprocal = CAVMD_EWALD_RECIPROCAL_DIRECT; // which two kernels compute enqueues
+
     cavmd_coulomb() : LinkedTable([](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row) {}
 
+    // (while the factored method is selected, an item beyond its per-axis limit is refused like any other bad row; `out` is
+    // never NULL here: LinkedTable::check_into is the only caller)
     int item_status(const cavmd_coulomb_item* it, CoulombDerived* out) const override
     {
-        return coulomb_item_status(it, out, nullptr);
+        const int st = coulomb_item_status(it, out, nullptr);
+        if (st != CAVMD_OK || reciprocal != CAVMD_EWALD_RECIPROCAL_FACTORED)
+            return st;
+        return ewald_capacity_status(out->lattice);
     }
 
     void strip(cavmd_coulomb_item* it) const override
@@ -230,7 +283,46 @@ struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, Coulomb
             emit_blocks(&k_table, item, (unsigned)d[item].ktab.size(), kCoulombKRows, t->offsets[item], 0u);
             emit_blocks(&table, item, all[item].N, kCoulombRows, partner_base[item], t->offsets[item]);
         }
+        // the factored method's tables: {where each begins}, launch-1 workgroups, launch-2 workgroups, items, segments
+        size_t n_segments = 0, n_seg_blocks = 0, n_row_blocks = 0;
+        for (size_t i = 0; i < B; ++i)
+        {
+            if (all[i].N == 0)
+                continue;
+            n_segments += d[i].lattice.segments.size();
+            n_seg_blocks += (d[i].lattice.segments.size() + kEwaldSegRows - 1) / kEwaldSegRows;
+            n_row_blocks += (all[i].N + kEwaldRows - 1) / kEwaldRows;
+        }
+        const size_t at_seg_blocks = 1, at_row_blocks = at_seg_blocks + n_seg_blocks, at_items = at_row_blocks + n_row_blocks;
+        const size_t at_segments = at_items + B;
+        std::vector<uint4> ewald(at_segments + n_segments, make_uint4(0, 0, 0, 0));
+        ewald[0] = make_uint4((unsigned)at_seg_blocks, (unsigned)at_row_blocks, (unsigned)at_items, 0u);
+        unsigned lds_m = 1;
+        size_t seg_at = at_segments;
+        for (size_t i = 0; i < B; ++i)
+        {
+            if (all[i].N == 0)
+                continue;
+            const EwaldLattice& l = d[i].lattice;
+            ewald[at_items + i] = make_uint4((unsigned)seg_at, (unsigned)l.segments.size(), l.m[0] | (l.m[1] << 16), l.m[2]);
+            std::copy(l.segments.begin(), l.segments.end(), ewald.begin() + seg_at);
+            seg_at += l.segments.size();
+            lds_m = std::max(lds_m, std::max(l.m[0], std::max(l.m[1], l.m[2])));
+        }
+        size_t seg_block = at_seg_blocks, row_block = at_row_blocks;
+        for (unsigned item : launch)
+        {
+            if (all[item].N == 0)
+                continue;
+            const uint4 info = ewald[at_items + item];
+            for (unsigned first = 0; first < info.y; first += kEwaldSegRows)
+                ewald[seg_block++] = make_uint4(item, info.x + first, std::min(info.y - first, kEwaldSegRows), t->offsets[item]);
+            for (unsigned first = 0; first < all[item].N; first += kEwaldRows)
+                ewald[row_block++] = make_uint4(item, first, partner_base[item], t->offsets[item]);
+        }
         hipError_t e = t->k_blocks.upload(k_table.data(), k_table.size());
+        if (e == hipSuccess)
+            e = t->ewald.upload(ewald.data(), ewald.size());
         if (e == hipSuccess)
             e = t->blocks.upload(table.data(), table.size());
         if (e == hipSuccess)
@@ -247,7 +339,12 @@ struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, Coulomb
         t->header.structure = t->structure.ptr;
         t->header.n_k_blocks = (unsigned)k_table.size();
         t->header.n_blocks = (unsigned)table.size();
+        t->header.pad[0] = (uint64_t)(uintptr_t)t->ewald.ptr;
+        t->header.pad[1] = (uint64_t)n_seg_blocks | ((uint64_t)n_row_blocks << 32);
+        t->n_ewald_k_blocks = (unsigned)n_seg_blocks;
+        t->n_ewald_blocks = (unsigned)n_row_blocks;
         t->lds_n = lds_particles(largest);
+        t->lds_m = lds_m;
         return e;
     }
 };
@@ -316,6 +413,17 @@ int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)
         return CAVMD_ERR_INVALID_VALUE;
     hipStream_t stream = (hipStream_t)stream_;
     const CoulombTables& t = c->tables;
+    if (c->reciprocal == CAVMD_EWALD_RECIPROCAL_FACTORED)
+    {
+        const int st = c->launch(stream, ewald_structure_factored_kernel<kCoulombBlock, kEwaldKSplit, kEwaldSegment, kEwaldTile>,
+                                 dim3(std::max(t.n_ewald_k_blocks, 1u)), dim3(kCoulombBlock), ewald_structure_lds_bytes(t.lds_m),
+                                 c->d_rows.ptr, c->d_header.ptr, t.lds_m);
+        if (st != CAVMD_OK)
+            return st;
+        return c->launch(stream, ewald_force_factored_kernel<kCoulombBlock, kEwaldJSplit, kEwaldSegment>,
+                         dim3(std::max(t.n_ewald_blocks, 1u)), dim3(kCoulombBlock),
+                         ewald_force_lds_bytes(t.lds_n, t.lds_m, kEwaldRows), c->d_rows.ptr, c->d_header.ptr, t.lds_n, t.lds_m);
+    }
     const size_t lds = coulomb_lds_bytes(t.lds_n);
     // two launches, each noted once it is in flight: a refused second one leaves the first to be waited for
     const int st = c->launch(stream, coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>, dim3(std::max(t.header.n_k_blocks, 1u)),
@@ -334,6 +442,44 @@ int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, con
         *out = reinterpret_cast<const double*>(c->tables.structure.ptr);
     if (h_offsets)
         *h_offsets = c->tables.offsets.data();
+    return CAVMD_OK;
+}
+
+// ---- the reciprocal-space method of a Coulomb batch (include/cavmd.h) ----------------------------------------------------------
+int cavmd_ewald_order(int* tile, int* segment, int* max_m, int* rows, int* segment_rows)
+{
+    if (tile)
+        *tile = kEwaldTile;
+    if (segment)
+        *segment = kEwaldSegment;
+    if (max_m)
+        *max_m = CAVMD_EWALD_MAX_M;
+    if (rows)
+        *rows = (int)kEwaldRows;
+    if (segment_rows)
+        *segment_rows = (int)kEwaldSegRows;
+    return CAVMD_OK;
+}
+
+int cavmd_ewald_set_reciprocal(cavmd_coulomb* c, int method)
+{
+    if (!c || (method != CAVMD_EWALD_RECIPROCAL_DIRECT && method != CAVMD_EWALD_RECIPROCAL_FACTORED))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (c->enqueued && stream_capturing(c->last_stream))
+        return CAVMD_ERR_INVALID_VALUE;
+    if (method == CAVMD_EWALD_RECIPROCAL_FACTORED)
+        for (size_t i = 0; i < c->n; ++i)
+            if (c->items[i].N != 0 && ewald_capacity_status(c->derived[i].lattice) != CAVMD_OK)
+                return CAVMD_ERR_CAPACITY;
+    c->reciprocal = method;
+    return CAVMD_OK;
+}
+
+int cavmd_ewald_get_reciprocal(const cavmd_coulomb* c, int* method)
+{
+    if (!c || !method)
+        return CAVMD_ERR_INVALID_VALUE;
+    *method = c->reciprocal;
     return CAVMD_OK;
 }
 

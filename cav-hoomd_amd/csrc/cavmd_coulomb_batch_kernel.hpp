@@ -13,7 +13,8 @@
 //   2. coulomb_force_kernel: ceil(n / ROWS) workgroups per system, the same LDS image; S = BLOCK / ROWS adjacent lanes share
 //      particle i and split first the j-walk (real-space term inside the cut-off, exclusion term for the listed partners, and
 //      the total charge Q on the way) and then the k-walk (S(k) of launch 1 and the library's table of k and a_k out of global
-//      memory), fold left to right with shuffles, and lane 0 adds the self and background terms and stores.
+//      memory), fold left to right with shuffles, and lane 0 adds the self and background terms and stores.  Its body is
+//      cavmd_coulomb_force_body.inc, which the factored method's launch 2 (cavmd_ewald_factored_kernel.hpp) includes too.
 //
 // LDS is four arrays of doubles (x, y, z, q), not 32-byte records: the S (or T) lanes of a group read S consecutive doubles
 // with one ds_read_b64 -- S distinct banks, every other lane of the wave a broadcast -- where records would put j and j + 8 on
@@ -21,6 +22,7 @@
 // partner tables are built and checked by the library), and every slot and every force entry is written by its owner.
 #pragma once
 
+#include "cavmd_ewald_phase.hpp"
 #include "cavmd_reduce.hpp"
 
 #pragma clang fp contract(off)
@@ -170,132 +172,9 @@ __global__ __launch_bounds__(BLOCK) void coulomb_force_kernel(const CoulombRow* 
                                                               const CoulombHeader* __restrict__ hdr, unsigned lds_n)
 {
     static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_coulomb[];
-    if (blockIdx.x >= hdr->n_blocks)
-        return; // a launch captured for a larger table
-    const uint4 blk = hdr->blocks[blockIdx.x];
-    const unsigned item = __builtin_amdgcn_readfirstlane(blk.x);
-    const unsigned first = __builtin_amdgcn_readfirstlane(blk.y);
-    const unsigned partner_base = __builtin_amdgcn_readfirstlane(blk.z);
-    const unsigned k_base = __builtin_amdgcn_readfirstlane(blk.w);
-    const CoulombRow* __restrict__ row = rows + item;
-    const unsigned n = row->n, n_k = row->n_k;
-    v2d* __restrict__ force2 = row->force2;
-    const unsigned r = threadIdx.x / S, s = threadIdx.x % S;
-    const unsigned i = first + r;
-    const bool owner = (i < n);
-    if (n > lds_n)
-    {
-        if (owner && s == 0)
-        {
-            const double nan = __builtin_nan("");
-            const v2d bad = {nan, nan};
-            force2[2 * (size_t)i] = bad;
-            force2[2 * (size_t)i + 1] = bad;
-        }
-        return;
-    }
-    double* __restrict__ sx = reinterpret_cast<double*>(s_coulomb);
-    double* __restrict__ sy = sx + lds_n;
-    double* __restrict__ sz = sy + lds_n;
-    double* __restrict__ sq = sz + lds_n;
-    coulomb_stage<BLOCK>(row, n, sx, sy, sz, sq);
-
-    const double Lx = row->Lx, Ly = row->Ly, Lz = row->Lz;
-    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5;
-    const double kappa = row->kappa, rcutsq = row->rcutsq;
-    const double two_self_c = 2.0 * row->self_c; // 2 kappa / sqrt(pi)
-    const unsigned ii = owner ? i : 0u;          // lanes past the end walk nothing and write nothing, but take part in the shuffles
-    const double xi = sx[ii], yi = sy[ii], zi = sz[ii], qi = sq[ii];
-    uint4 slots = {kCoulombNoPartner, kCoulombNoPartner, kCoulombNoPartner, kCoulombNoPartner};
-    if (owner)
-        slots = hdr->partners[(size_t)partner_base + i];
-
-    // real space: partial s of particle i, and of the total charge
-    double px = 0.0, py = 0.0, pz = 0.0, pw = 0.0, pq = 0.0;
-    const unsigned j_end = owner ? n : 0u;
-    for (unsigned j = s; j < j_end; j += S)
-    {
-        const double qj = sq[j];
-        pq = pq + qj;
-        if (j == i)
-            continue;
-        const bool excluded = (j == slots.x) | (j == slots.y) | (j == slots.z) | (j == slots.w);
-        const double dx = min_image(xi - sx[j], Lx, hx);
-        const double dy = min_image(yi - sy[j], Ly, hy);
-        const double dz = min_image(zi - sz[j], Lz, hz);
-        const double rsq = (dx * dx + dy * dy) + dz * dz;
-        if (!excluded && !(rsq < rcutsq))
-            continue;
-        const double rr = sqrt(rsq);
-        const double kr = kappa * rr;
-        const double g = two_self_c * exp(-(kr * kr));
-        const double qq = qi * qj;
-        double e, fdivr;
-        if (excluded)
-        {
-            const double u = erf(kr) / rr;
-            e = -(qq * u);
-            fdivr = -(qq * (u - g)) / rsq;
-        }
-        else
-        {
-            const double u = erfc(kr) / rr;
-            e = qq * u;
-            fdivr = (qq * (u + g)) / rsq;
-        }
-        px = px + dx * fdivr;
-        py = py + dy * fdivr;
-        pz = pz + dz * fdivr;
-        pw = pw + 0.5 * e;
-    }
-
-    // reciprocal space: partial s over k = s, s + S, ...; the factors q_i and 2 q_i are applied once, to the partial
-    double rx = 0.0, ry = 0.0, rz = 0.0, rw = 0.0;
-    const unsigned k_end = owner ? n_k : 0u;
-    const CoulombK* __restrict__ ktab = hdr->ktab + (size_t)k_base;
-    const v2d* __restrict__ structure = hdr->structure + (size_t)k_base;
-    for (unsigned k = s; k < k_end; k += S)
-    {
-        const CoulombK kv = ktab[k];
-        const v2d AB = structure[k];
-        const double theta = (kv.kx * xi + kv.ky * yi) + kv.kz * zi;
-        double sn, cs;
-        sincos(theta, &sn, &cs);
-        const double f = kv.a * (AB.x * sn - AB.y * cs);
-        rx = rx + kv.kx * f;
-        ry = ry + kv.ky * f;
-        rz = rz + kv.kz * f;
-        rw = rw + kv.a * (AB.x * cs + AB.y * sn);
-    }
-    const double qi2 = 2.0 * qi;
-    px = px + qi2 * rx;
-    py = py + qi2 * ry;
-    pz = pz + qi2 * rz;
-    pw = pw + qi * rw;
-
-    // P = ((p0 + p1) + p2) + ...: every lane of the group folds the same S values in the same order
-    double Px = __shfl(px, 0, S), Py = __shfl(py, 0, S), Pz = __shfl(pz, 0, S), Pw = __shfl(pw, 0, S), Q = __shfl(pq, 0, S);
-#pragma unroll 1
-    for (int u = 1; u < S; ++u)
-    {
-        Px = Px + __shfl(px, u, S);
-        Py = Py + __shfl(py, u, S);
-        Pz = Pz + __shfl(pz, u, S);
-        Pw = Pw + __shfl(pw, u, S);
-        Q = Q + __shfl(pq, u, S);
-    }
-    if (!owner || s != 0)
-        return;
-    // self and background
-    Pw = (Pw - row->self_c * (qi * qi)) - row->bg_c * (qi * Q);
-    const v2d Fxy = {Px, Py}, Fzw = {Pz, Pw};
-    force2[2 * (size_t)i] = Fxy;
-    force2[2 * (size_t)i + 1] = Fzw;
-    if (i == 0)
-    {
-        const v2d Q0 = {Q, 0.0};
-        hdr->structure[(size_t)k_base + n_k] = Q0;
-    }
+    constexpr bool FACTORED = false;
+    [[maybe_unused]] constexpr int SEG = 1;        // (of the factored method: nothing here reads them)
+    [[maybe_unused]] constexpr unsigned lds_m = 0;
+#include "cavmd_coulomb_force_body.inc"
 }
 } // namespace cavmd

@@ -1438,6 +1438,52 @@ CAVMD_API int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream);
  * above and then {Q, 0}.  Both are valid until the next cavmd_coulomb_set_items or cavmd_coulomb_destroy. */
 CAVMD_API int cavmd_coulomb_structure_device_ptr(cavmd_coulomb* c, const double** out, const uint32_t** h_offsets);
 
+/* ---- the reciprocal-space method of a Coulomb batch: the direct sum, or per-axis phase factors (opt-in) ------------------------ */
+/* The k-vectors lie on a lattice, so exp(i k.x) = E_x(mx) E_y(my) E_z(mz) with E_c(m) = exp(i m phi_c): the FACTORED method takes
+ * cos theta and sin theta of the section above from three sincos per particle and about one complex multiplication per
+ * (particle, k), where the DIRECT method calls sincos(k.x) once per (particle, k) in either launch.  Everything else IS the
+ * section above: the same kept set and order of k-vectors, the same a_k table, the same S(k) slots (launch 1 fills {A, B}, launch 2
+ * stores {Q, 0}), the same real-space, exclusion, self and background terms (the same device code), two launches, no FMA, no
+ * atomics, no workgroup that waits for another.  Only (cos theta, sin theta) = P(m) is obtained differently, per particle x:
+ *   base angles:     phi_c = k1_c * x_c with k1_c = (2 pi * 1) / L_c, the library's own k-component for m = 1
+ *   per-axis tables: E_c(0) = (1, 0);  E_c(1) = (cos phi_c, sin phi_c), ONE device sincos per particle and axis;
+ *                    E_c(m) = E_c(m - 1) * E_c(1) for m = 2 .. M_c (M_c: the item's largest |m_c|);  E_c(-m) = conj E_c(m)
+ *   segments:        the kept vectors of one (mx, my) are consecutive in mz and in k; from its first mz on, such a row is cut
+ *                    into segments of at most SEG = CAVMD_EWALD_SEGMENT vectors.  For a segment that starts at zs:
+ *                    P(mx, my, zs) = (E_x(mx) * E_y(my)) * E_z(zs);   P(mx, my, mz + 1) = P(mx, my, mz) * E_z(1)
+ *   a * b            = (a.re b.re - a.im b.im, a.re b.im + a.im b.re), each operation rounded (no FMA contraction)
+ * so the multiplications behind P(m) number max(mx - 1, 0) + max(|my| - 1, 0) + max(|zs| - 1, 0) + 2 + (mz - zs), at most
+ * Mx + My + Mz + SEG - 2.  Fold orders, fixed by compile-time constants of the library alone (cavmd_ewald_order):
+ *   launch 1: ceil(segments / SEGROWS) workgroups per system; a workgroup walks the system in tiles of CAVMD_EWALD_TILE particles
+ *             whose tables it builds in LDS (TILE * (3 (M + 1) * 16 + 8) bytes, M the largest M_c of the batch), 256 / SEGROWS
+ *             lanes share a segment, lane t adds q_j P for j = t, t + 256 / SEGROWS, ... and the group folds left to right;
+ *   launch 2: ceil(N / ROWS) workgroups per system; the lanes of particle i take the real-space walk as in the section above,
+ *             then the segments g = s, s + 256 / ROWS, ..., each in k order, and fold left to right.
+ * The same input gives the same bits on every launch and every graph replay.  The results are NOT bit-comparable with the
+ * direct method's: both are held to a derived rounding bound (tests/coulomb_mirror.py, tests/coulomb_factored_mirror.py). */
+#define CAVMD_EWALD_RECIPROCAL_DIRECT 0   /* one sincos per (particle, k): what a new batch uses */
+#define CAVMD_EWALD_RECIPROCAL_FACTORED 1 /* per-axis phase factors */
+#define CAVMD_EWALD_TILE 64               /* particles whose tables launch 1 holds in LDS at a time */
+#define CAVMD_EWALD_SEGMENT 8             /* SEG */
+#define CAVMD_EWALD_MAX_M 20              /* largest |m_c| of an item under the factored method: 64 * (3 * 21 * 16 + 8) = 65024 bytes
+                                           * of LDS in launch 1, the most a kernel gets without opt-in (M = 21 would need 68096) */
+/* The tile length, SEG and CAVMD_EWALD_MAX_M, ROWS of the factored launch 2 and SEGROWS of the factored launch 1, as the library
+ * was compiled (they do not depend on CAVMD_COULOMB_J_SPLIT / CAVMD_COULOMB_K_SPLIT); any may be NULL.  Needs no device. */
+CAVMD_API int cavmd_ewald_order(int* tile, int* segment, int* max_m, int* rows, int* segment_rows);
+/* Selects which two kernels cavmd_coulomb_compute enqueues from now on: a host-side switch that allocates nothing, copies
+ * nothing and waits for nothing (the factored method's tables are built with the others, by create and set_items).
+ * CAVMD_ERR_INVALID_VALUE for a null handle, an unknown method, and while the stream of the batch's last launch is being
+ * captured.  A launch that WAS captured keeps the kernels it was captured with: a graph captured under one method goes on
+ * computing with that method after the switch.  CAVMD_ERR_CAPACITY, and nothing is changed, for CAVMD_EWALD_RECIPROCAL_FACTORED
+ * when an item's largest |m| on some axis exceeds CAVMD_EWALD_MAX_M (a long thin box can reach 4096 inside CAVMD_COULOMB_MAX_K).
+ * While the factored method is selected cavmd_coulomb_set_items refuses such an item with CAVMD_ERR_CAPACITY, whole, as it
+ * refuses any bad row.  A captured factored launch keeps its LDS sizes (those of the largest N and the largest M it was
+ * captured with); on replay a system with a larger N or M gets NaN structure factors and NaN forces, never an out-of-bounds
+ * access. */
+CAVMD_API int cavmd_ewald_set_reciprocal(cavmd_coulomb* c, int method);
+/* The method of the batch.  CAVMD_ERR_INVALID_VALUE for a null handle or a null output. */
+CAVMD_API int cavmd_ewald_get_reciprocal(const cavmd_coulomb* c, int* method);
+
 /* ---- trajectory frames of a batch: positions, velocities and images recorded on the device in ONE launch --------------------- */
 /* What the driver's hoomd.write.GSD (examples/05_advanced_run.py:1231-1246) saves every --gsd-output-period-ps, with the initial
  * frame written first -- the positions, images and velocities of every replica -- as ONE launch for all systems that either
