@@ -266,6 +266,8 @@ COULOMB_MAX_EXCLUSIONS = 4
 EWALD_RECIPROCAL_DIRECT = 0
 EWALD_RECIPROCAL_FACTORED = 1
 EWALD_RECIPROCAL = {"direct": EWALD_RECIPROCAL_DIRECT, "factored": EWALD_RECIPROCAL_FACTORED}
+COULOMB_PART_SHORT, COULOMB_PART_LONG = 1, 2   # CAVMD_COULOMB_PART_*
+COULOMB_PARTS = {"short": COULOMB_PART_SHORT, "long": COULOMB_PART_LONG, "both": COULOMB_PART_SHORT | COULOMB_PART_LONG}
 MOLECULAR_MAX_ITEM_N = 2048
 MOLECULAR_MAX_BONDS = 4
 FIELD_MAX_WAVEVECTORS = 256
@@ -516,6 +518,7 @@ _PROTOTYPES = {
     "cavmd_verlet_accelerations": (_ci, [_vp, _vp]),
     "cavmd_verlet_step_one": (_ci, [_vp, _vp, _vp]),
     "cavmd_verlet_step_two": (_ci, [_vp, _vp, _vp]),
+    "cavmd_mts_verlet_kick": (_ci, [_vp, _vp, _vp, _vp, _dbl]),
     "cavmd_verlet_read": (_ci, [_vp, _vp, _vp]),
     "cavmd_verlet_reset": (_ci, [_vp, _vp]),
     "cavmd_verlet_state_device_ptr": (_ci, [_vp, _P(_vp)]),
@@ -620,6 +623,8 @@ _PROTOTYPES = {
     "cavmd_ewald_order": (_ci, [_P(_ci)] * 5),
     "cavmd_ewald_set_reciprocal": (_ci, [_vp, _ci]),
     "cavmd_ewald_get_reciprocal": (_ci, [_vp, _P(_ci)]),
+    "cavmd_mts_coulomb_set_long_forces": (_ci, [_vp, _sz, _P(_vp)]),
+    "cavmd_mts_coulomb_compute_parts": (_ci, [_vp, _vp, ctypes.c_uint]),
     "cavmd_device_info": (_ci, [_vp, _P(_ci), _P(_ci), _cstr, _sz]),
     "cavmd_error_string": (_cstr, [_ci]),
     "cavmd_version": (_ci, []),
@@ -1332,6 +1337,12 @@ class Verlet(_StateHandle):
         check(self._lib.cavmd_verlet_step_two(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr)),
               "cavmd_verlet_step_two")
 
+    def kick(self, stream: int, inputs_ptr: int, forces_ptr: int, weight: float) -> None:
+        """One kernel: v += (f / m) (weight dt) of every item, f through the DEVICE table of n_items device pointers at
+        ``forces_ptr``, read with the input rows when the kernel runs.  Nothing but the velocities is written."""
+        check(self._lib.cavmd_mts_verlet_kick(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(inputs_ptr), ctypes.c_void_p(forces_ptr),
+                                          float(weight)), "cavmd_mts_verlet_kick")
+
 
 BATH_KEY_STRIDE = 0x9E3779B97F4A7C15
 
@@ -1533,6 +1544,16 @@ class Coulomb(_ItemTableHandle):
     def compute(self, stream: int = 0) -> None:
         """Two kernels: every structure factor, then every entry of every item's force array."""
         check(self._lib.cavmd_coulomb_compute(self._h, ctypes.c_void_p(stream)), "cavmd_coulomb_compute")
+
+    def set_long_forces(self, long_ptrs) -> None:
+        """Gives every item its LONG array (device addresses, 0 for an item with N == 0), or drops the split (all 0)."""
+        ptrs = [int(p) for p in long_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        check(self._lib.cavmd_mts_coulomb_set_long_forces(self._h, len(ptrs), arr), "cavmd_mts_coulomb_set_long_forces")
+
+    def compute_parts(self, stream: int = 0, parts: int = COULOMB_PART_SHORT | COULOMB_PART_LONG) -> None:
+        """SHORT: one kernel into the items' force arrays; LONG: two kernels into their long arrays; both: three."""
+        check(self._lib.cavmd_mts_coulomb_compute_parts(self._h, ctypes.c_void_p(stream), int(parts)), "cavmd_mts_coulomb_compute_parts")
 
     def set_reciprocal(self, method: int) -> None:
         """Which two kernels ``compute`` enqueues from now on: EWALD_RECIPROCAL_DIRECT or EWALD_RECIPROCAL_FACTORED.  Raises

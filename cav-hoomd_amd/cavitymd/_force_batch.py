@@ -63,7 +63,11 @@ class ForceBatchBase(HandleOwner):
         """(B,) device tensor: the energy of every system, the sum of its ``.w`` column, ordered on torch's current stream
         (the kernels keep no totals across workgroups)."""
         self._need()
-        w = self._pool[:sum(self._sizes), 3]
+        return self._pool_energy(self._pool)
+
+    def _pool_energy(self, pool) -> torch.Tensor:
+        """the per-system sums of the ``.w`` column of one allocation laid out like ``_pool``"""
+        w = pool[:sum(self._sizes), 3]
         if len(set(self._sizes)) == 1 and self._sizes[0] > 0:
             return w.reshape(self.n_systems, self._sizes[0]).sum(dim=1)
         return torch.segment_reduce(w.contiguous(), "sum", lengths=self._lengths)

@@ -12,6 +12,15 @@ twin of ``MolecularForceBatch``, and its force arrays are further forces of the 
     with torch.cuda.graph(graph):
         integrator.step_one(); cavity.compute(); molecular.compute(); coulomb.compute(); integrator.step_two()
 
+The reference treats electrostatics as two forces (``short, long = make_pppm_coulomb_forces(...)``) and logs an energy column
+for each.  ``split=True`` gives the batch a second set of arrays and evaluates the sum in those two groups
+(``cavmd_mts_coulomb_compute_parts``): ``forces`` are then the SHORT part (the erfc terms inside the cut-off), ``forces_long`` the
+LONG part (the exclusion partners' erf terms, the reciprocal sum, the self and background terms), and ``compute(parts=...)``
+evaluates "both", "short" or "long".  ``short`` and ``long`` are small objects with ``.forces`` for ``VerletBatch`` force
+slots, ``VerletBatch.kick`` and ``BatchEnergyLedger(terms=[("ewald_short", c.short), ("ewald_long", c.long)])``.  Evaluating
+the long part every n-th step and kicking with it is the impulse multiple-time-step scheme
+(examples/mts/batch_mts_coulomb_in_one_graph.py); it is defined for a dt that stays the same through an outer step.
+
 Parity with HOOMD-blue's PPPM is not pinned: what separates the two is PPPM's discretisation error.  No CPU fallback: CPU
 tensors raise.
 """
@@ -21,7 +30,23 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import stream_handle
 from ._force_batch import ForceBatchBase
+
+
+class CoulombPart:
+    """One part of a split batch: ``forces``, per system an (N_k, 4) float64 device tensor (``.w``: the particle's share of
+    the part's energy).  Keeps the batch alive."""
+
+    def __init__(self, batch, name: str, forces):
+        self.batch, self.name, self._forces = batch, name, forces
+
+    @property
+    def forces(self):
+        return list(self._forces)
+
+    def __len__(self) -> int:
+        return len(self._forces)
 
 
 class CoulombForceBatch(ForceBatchBase):
@@ -31,9 +56,10 @@ class CoulombForceBatch(ForceBatchBase):
     ``cavmd_coulomb_parameters``) or both ``kappa`` and ``k_cut``.  ``reciprocal``: "direct" (one sincos per particle and
     k-vector) or "factored" (per-axis phase factors, ``cavmd_ewald_set_reciprocal``; same expressions, results within the
     rounding bound, not the same bits).  ``compute`` is TWO kernels; column 3 of a force array is the particle's share of the
-    Coulomb energy."""
+    Coulomb energy.  ``split``: the object owns a second set of arrays, ``forces_long``, and ``compute`` evaluates the SHORT
+    part into ``forces`` (one kernel) and the LONG part into ``forces_long`` (two), together or one at a time."""
 
-    def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None, reciprocal="direct"):
+    def __init__(self, sysdefs, exclusions, r_cut, accuracy=None, kappa=None, k_cut=None, reciprocal="direct", split=False):
         if reciprocal not in _capi.EWALD_RECIPROCAL:
             raise ValueError(f"reciprocal: one of {sorted(_capi.EWALD_RECIPROCAL)}, not {reciprocal!r}")
         pds = self._systems(sysdefs)
@@ -74,8 +100,17 @@ class CoulombForceBatch(ForceBatchBase):
                 raise
         self._boxes = [tuple(float(l) for l in pd.getGlobalBox().getL()) for pd in pds]
         self._open(self._device, lambda ws: _capi.Coulomb(ws, items))
+        self.split = bool(split)
         try:
             self.set_reciprocal(reciprocal)
+            if self.split:
+                self._pool_long = torch.zeros_like(self._pool)
+                starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+                self._force_long = [self._pool_long[int(starts[k]):int(starts[k + 1])] for k in range(B)]
+                torch.cuda.current_stream(self._device).synchronize()
+                self._need().set_long_forces([f.data_ptr() if n else 0 for f, n in zip(self._force_long, sizes)])
+                self.short = CoulombPart(self, "short", self._force)
+                self.long = CoulombPart(self, "long", self._force_long)
         except Exception:
             self.close()
             raise
@@ -83,6 +118,31 @@ class CoulombForceBatch(ForceBatchBase):
     @property
     def coulomb(self) -> _capi.Coulomb:
         return self._handle
+
+    def compute(self, timestep: int = 0, stream=None, parts=None) -> None:
+        """Not split: today's TWO kernels, the whole sum into ``forces`` (``parts`` raises).  Split: ``parts`` is "both" (the
+        default; three kernels), "short" (one kernel, writes ``forces``) or "long" (two kernels, writes ``forces_long``).  May
+        be captured; ``timestep`` is not used."""
+        if not self.split:
+            if parts is not None:
+                raise ValueError("parts: the batch was not created with split=True")
+            return super().compute(timestep, stream)
+        parts = "both" if parts is None else parts
+        if parts not in _capi.COULOMB_PARTS:
+            raise ValueError(f"parts: one of {sorted(_capi.COULOMB_PARTS)}, not {parts!r}")
+        self._need().compute_parts(stream_handle(stream, self._dev_index), _capi.COULOMB_PARTS[parts])
+
+    @property
+    def forces_long(self):
+        """Split batches only: per-system (N_k, 4) float64 device tensors of the LONG part."""
+        if not self.split:
+            raise AttributeError("forces_long: the batch was not created with split=True")
+        return list(self._force_long)
+
+    def potential_energy(self) -> torch.Tensor:
+        """(B,) device tensor: the Coulomb energy of every system; for a split batch the sum of both parts' ``.w``."""
+        e = super().potential_energy()
+        return e + self._pool_energy(self._pool_long) if self.split else e
 
     @property
     def reciprocal(self) -> str:

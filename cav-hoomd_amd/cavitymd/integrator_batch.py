@@ -83,6 +83,7 @@ class VerletBatch(HandleOwner, Checkpointable):
         self._step_inputs = StepInputs(B, dev, skip_column=6)
         self.inputs = self._step_inputs.tensor
         self._stream = 0
+        self._kick_tables = {}   # pointers of a kick's force arrays -> (their device table, the arrays): kick_table
         torch.cuda.current_stream(dev).synchronize()   # accel, inputs and the states are zero before any stream steps
 
     # -- the step's inputs -------------------------------------------------------------------------------------------------
@@ -131,6 +132,49 @@ class VerletBatch(HandleOwner, Checkpointable):
     def step_two(self, stream=None) -> None:
         """ONE kernel: F = sum of the force arrays (+ the bath on the Langevin particle), a = F / m, v += (a / 2) dt."""
         self._launch(_capi.Verlet.step_two, stream, self.inputs.data_ptr())
+
+    def kick_table(self, forces) -> torch.Tensor:
+        """The device table of B force pointers ``kick`` hands to its kernel, built once per list of arrays and kept alive
+        here with the arrays.  forces: a list of B (N_k, 4) device tensors (None: that system is left alone), or an object
+        with ``.forces``.  A new table is an upload from the host: not during a stream capture (``kick`` the same arrays once
+        before capturing, or call this)."""
+        self._need()
+        flist = list(getattr(forces, "forces", forces))
+        if len(flist) != self.n_systems:
+            raise ValueError(f"forces: one array per system ({self.n_systems})")
+        ptrs = []
+        for k, f in enumerate(flist):
+            n = self._velocities[k].shape[0]
+            if f is None or n == 0:
+                ptrs.append(0)
+                continue
+            if device_tensor(f, "VerletBatch", "force").shape != (n, 4) or f.dtype != torch.float64 or not f.is_contiguous() \
+                    or f.device != self._device:
+                raise ValueError(f"system {k}: the kick's force array is a contiguous ({n}, 4) float64 tensor on the "
+                                 "integrator's device")
+            ptrs.append(f.data_ptr())
+        tables = self._kick_tables
+        key = tuple(ptrs)
+        if key not in tables:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("VerletBatch.kick: the pointer table of these force arrays is not on the device yet; call "
+                                   "kick_table(forces) before the capture")
+            table = torch.zeros(max(len(ptrs), 1), dtype=torch.int64, device=self._device)
+            table[:len(ptrs)] = torch.from_numpy(np.array(ptrs, dtype=np.uint64).view(np.int64).copy()).to(self._device)
+            torch.cuda.current_stream(self._device).synchronize()
+            tables[key] = (table, flist)
+        return tables[key][0]
+
+    def kick(self, forces, weight, inputs=None, stream=None) -> None:
+        """ONE kernel: v += (f / m) (weight dt) with a force that is none of the integrator's own arrays, and nothing else
+        written -- the outer half-kicks of the impulse multiple-time-step scheme, ``kick(coulomb.long, n / 2)`` before and
+        after n plain steps.  forces: as for ``kick_table``; inputs: a (B, 8) device tensor of input rows, default
+        ``inputs``.  Pointers and rows are read when the kernel runs.  May be captured once the table exists."""
+        table = self.kick_table(forces)
+        rows = self.inputs if inputs is None else inputs
+        if rows.shape != (self.n_systems, 8) or rows.dtype != torch.float64 or rows.device != self._device or not rows.is_contiguous():
+            raise ValueError(f"inputs: a contiguous ({self.n_systems}, 8) float64 tensor on the integrator's device")
+        self._launch(_capi.Verlet.kick, stream, rows.data_ptr(), table.data_ptr(), float(weight))
 
     def state(self, stream=None) -> np.ndarray:
         """Per-system counters (``steps``, ``out_of_box``, ``langevin_reservoir``).  Default: waits for the whole device (a

@@ -24,8 +24,9 @@ captured into a graph appends a NEW row on every replay::
 
 Each potential term is a fixed-order compensated sum within 2 ulp of the exact one; ``kinetic_group`` and ``kinetic_cavity``
 have the bits of ``BatchRecorder``'s ``kinetic_energy`` and ``cavity_kinetic``; every total is the expression listed in
-include/cavmd.h, one rounding per operation.  One ``.w`` per force array: the reference's ``harmonic`` / ``lj`` and
-``ewald_short`` / ``ewald_long`` columns are not split; create two force batches for that.
+include/cavmd.h, one rounding per operation.  One ``.w`` per force array: the reference's ``harmonic`` / ``lj`` columns are
+not split (create two force batches for that); ``ewald_short`` / ``ewald_long`` are the two arrays of a split
+``CoulombForceBatch``, ``terms=[("ewald_short", coulomb.short), ("ewald_long", coulomb.long)]``.
 
 There is no CPU fallback: CPU tensors raise.
 """

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -241,8 +242,19 @@ int ewald_capacity_status(const EwaldLattice& l)
 struct cavmd_coulomb final : LinkedTable<cavmd_coulomb_item, CoulombRow, CoulombDerived, CoulombTables>
 {
     int reciprocal = CAVMD_EWALD_RECIPROCAL_DIRECT; // which two kernels compute enqueues
+    std::vector<uint64_t> long_forces;              // per item its LONG array (cavmd_mts_coulomb_set_long_forces); empty: not split
 
     cavmd_coulomb() : LinkedTable([](const cavmd_coulomb_item& it) { return it.N; }, coulomb_row) {}
+
+    // the long pointers of items [first, first + count) into the rows' spare word (a row built from an item carries 0 there);
+    // the caller holds the DeviceGuard and has waited for the launches in flight
+    hipError_t write_long(size_t first, size_t count, const uint64_t* values)
+    {
+        if (count == 0)
+            return hipSuccess;
+        char* at = reinterpret_cast<char*>(d_rows.ptr + first) + offsetof(CoulombRow, pad);
+        return hipMemcpy2D(at, sizeof(CoulombRow), values, sizeof(uint64_t), sizeof(uint64_t), count, hipMemcpyHostToDevice);
+    }
 
     // (while the factored method is selected, an item beyond its per-axis limit is refused like any other bad row; `out` is
     // never NULL here: LinkedTable::check_into is the only caller)
@@ -404,7 +416,91 @@ int cavmd_coulomb_destroy(cavmd_coulomb* c)
 
 int cavmd_coulomb_set_items(cavmd_coulomb* c, size_t first, size_t count, const cavmd_coulomb_item* h_items)
 {
-    return c ? c->set_items(first, count, h_items) : CAVMD_ERR_INVALID_VALUE;
+    if (!c)
+        return CAVMD_ERR_INVALID_VALUE;
+    if (c->long_forces.empty())
+        return c->set_items(first, count, h_items);
+    // a split batch: every item keeps its long array, so a new item must be able to live with the one it inherits
+    if (!c->within(first, count, h_items))
+        return CAVMD_ERR_INVALID_VALUE;
+    for (size_t i = 0; i < count; ++i)
+    {
+        const uint64_t kept = c->long_forces[first + i];
+        if ((h_items[i].N != 0 && kept == 0) || (kept != 0 && kept == (uint64_t)(uintptr_t)h_items[i].d_force))
+            return CAVMD_ERR_INVALID_VALUE;
+    }
+    const int st = c->set_items(first, count, h_items);
+    if (st != CAVMD_OK)
+        return st;
+    DeviceGuard guard(c->device);
+    return hip_status(c->write_long(first, count, c->long_forces.data() + first)); // (set_items has waited; nothing is in flight)
+}
+
+int cavmd_mts_coulomb_set_long_forces(cavmd_coulomb* c, size_t n_items, cavmd_double4* const* h_long_force)
+{
+    if (!c || !h_long_force || n_items != c->n)
+        return CAVMD_ERR_INVALID_VALUE;
+    size_t set = 0;
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        const uintptr_t p = (uintptr_t)h_long_force[i];
+        if ((p & 15) || (p != 0 && p == (uintptr_t)c->items[i].d_force))
+            return CAVMD_ERR_INVALID_VALUE;
+        set += (p != 0);
+    }
+    if (set != 0) // all NULL drops the split; otherwise NULL only for N == 0
+        for (size_t i = 0; i < n_items; ++i)
+            if (!h_long_force[i] && c->items[i].N != 0)
+                return CAVMD_ERR_INVALID_VALUE;
+    DeviceGuard guard(c->device);
+    const int st = c->wait_idle(); // refuses while the stream of the last launch is being captured
+    if (st != CAVMD_OK)
+        return st;
+    std::vector<uint64_t> values(n_items);
+    for (size_t i = 0; i < n_items; ++i)
+        values[i] = (uint64_t)(uintptr_t)h_long_force[i];
+    CAVMD_HIP_TRY(c->write_long(0, n_items, values.data()));
+    if (set == 0)
+        values.clear();
+    c->long_forces.swap(values);
+    return CAVMD_OK;
+}
+
+int cavmd_mts_coulomb_compute_parts(cavmd_coulomb* c, void* stream_, unsigned parts)
+{
+    if (!c || c->long_forces.empty() || parts == 0 || (parts & ~(CAVMD_COULOMB_PART_SHORT | CAVMD_COULOMB_PART_LONG)) != 0)
+        return CAVMD_ERR_INVALID_VALUE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const CoulombTables& t = c->tables;
+    const size_t lds = coulomb_lds_bytes(t.lds_n);
+    const dim3 block(kCoulombBlock), rows_grid(std::max(t.header.n_blocks, 1u));
+    if (parts & CAVMD_COULOMB_PART_SHORT)
+    {
+        const int st = c->launch(stream, coulomb_short_kernel<kCoulombBlock, kCoulombJSplit>, rows_grid, block, lds, c->d_rows.ptr,
+                                 c->d_header.ptr, t.lds_n);
+        if (st != CAVMD_OK)
+            return st;
+    }
+    if (!(parts & CAVMD_COULOMB_PART_LONG))
+        return CAVMD_OK;
+    // the structure factors by the batch's method, as cavmd_coulomb_compute launches them, then the long kernel of that method
+    if (c->reciprocal == CAVMD_EWALD_RECIPROCAL_FACTORED)
+    {
+        const int st = c->launch(stream, ewald_structure_factored_kernel<kCoulombBlock, kEwaldKSplit, kEwaldSegment, kEwaldTile>,
+                                 dim3(std::max(t.n_ewald_k_blocks, 1u)), block, ewald_structure_lds_bytes(t.lds_m), c->d_rows.ptr,
+                                 c->d_header.ptr, t.lds_m);
+        if (st != CAVMD_OK)
+            return st;
+        return c->launch(stream, ewald_long_factored_kernel<kCoulombBlock, kEwaldJSplit, kEwaldSegment>,
+                         dim3(std::max(t.n_ewald_blocks, 1u)), block, ewald_force_lds_bytes(t.lds_n, t.lds_m, kEwaldRows),
+                         c->d_rows.ptr, c->d_header.ptr, t.lds_n, t.lds_m);
+    }
+    const int st = c->launch(stream, coulomb_structure_kernel<kCoulombBlock, kCoulombKSplit>, dim3(std::max(t.header.n_k_blocks, 1u)),
+                             block, lds, c->d_rows.ptr, c->d_header.ptr, t.lds_n);
+    if (st != CAVMD_OK)
+        return st;
+    return c->launch(stream, coulomb_long_kernel<kCoulombBlock, kCoulombJSplit>, rows_grid, block, lds, c->d_rows.ptr, c->d_header.ptr,
+                     t.lds_n);
 }
 
 int cavmd_coulomb_compute(cavmd_coulomb* c, void* stream_)

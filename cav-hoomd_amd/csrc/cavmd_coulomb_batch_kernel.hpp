@@ -32,6 +32,9 @@ namespace cavmd
 constexpr int kCoulombBlock = 256;
 constexpr int kCoulombMaxExclusions = 4;
 constexpr unsigned kCoulombNoPartner = 0xFFFFFFFFu;
+// which terms a kernel built on cavmd_coulomb_force_body.inc carries (PART there): the whole sum, or one of the two parts of
+// include/cavmd.h (the values of CAVMD_COULOMB_PART_SHORT / CAVMD_COULOMB_PART_LONG)
+constexpr unsigned kCoulombPartAll = 0, kCoulombPartShort = 1, kCoulombPartLong = 2;
 
 // One system as the kernels read it.
 struct CoulombRow
@@ -46,7 +49,7 @@ struct CoulombRow
     double bg_c;    // pi / (2 V kappa^2)
     unsigned n;
     unsigned n_k; // K, the kept k-vectors
-    uint64_t pad;
+    uint64_t pad; // the item's LONG array (cavmd_mts_coulomb_set_long_forces), 0 without one: read by the LONG kernels alone
 };
 static_assert(sizeof(CoulombRow) == 96, "one coulomb row = 96 bytes");
 
@@ -173,7 +176,35 @@ __global__ __launch_bounds__(BLOCK) void coulomb_force_kernel(const CoulombRow* 
 {
     static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
     constexpr bool FACTORED = false;
+    constexpr unsigned PART = kCoulombPartAll;
     [[maybe_unused]] constexpr int SEG = 1;        // (of the factored method: nothing here reads them)
+    [[maybe_unused]] constexpr unsigned lds_m = 0;
+#include "cavmd_coulomb_force_body.inc"
+}
+
+// The two parts of the sum (include/cavmd.h, "the two parts of the Ewald sum"), the same body: SHORT into the item's force
+// array -- no structure factor is read, so it needs no launch before it -- and LONG, after coulomb_structure_kernel, into the
+// item's long array.  Workgroups, LDS image, j partition and fold are coulomb_force_kernel's.
+template <int BLOCK, int S>
+__global__ __launch_bounds__(BLOCK) void coulomb_short_kernel(const CoulombRow* __restrict__ rows,
+                                                              const CoulombHeader* __restrict__ hdr, unsigned lds_n)
+{
+    static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
+    constexpr bool FACTORED = false;
+    constexpr unsigned PART = kCoulombPartShort;
+    [[maybe_unused]] constexpr int SEG = 1;
+    [[maybe_unused]] constexpr unsigned lds_m = 0;
+#include "cavmd_coulomb_force_body.inc"
+}
+
+template <int BLOCK, int S>
+__global__ __launch_bounds__(BLOCK) void coulomb_long_kernel(const CoulombRow* __restrict__ rows,
+                                                             const CoulombHeader* __restrict__ hdr, unsigned lds_n)
+{
+    static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
+    constexpr bool FACTORED = false;
+    constexpr unsigned PART = kCoulombPartLong;
+    [[maybe_unused]] constexpr int SEG = 1;
     [[maybe_unused]] constexpr unsigned lds_m = 0;
 #include "cavmd_coulomb_force_body.inc"
 }

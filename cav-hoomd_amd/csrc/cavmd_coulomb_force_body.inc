@@ -2,13 +2,19 @@
 // (cavmd_coulomb_batch_kernel.hpp) and ewald_force_factored_kernel (cavmd_ewald_factored_kernel.hpp), included into each.  It is
 // the text of a kernel and not a function the two call: as functions, inlined, the shared parts changed the code of the kernel
 // that was there before the factored method, whose device code stays what it was.  In scope: BLOCK, S, FACTORED (a constant
-// expression), rows, hdr, lds_n, and for FACTORED: SEG, lds_m and what cavmd_ewald_factored_kernel.hpp declares (the direct
+// expression), PART, rows, hdr, lds_n, and for FACTORED: SEG, lds_m and what cavmd_ewald_factored_kernel.hpp declares (the direct
 // kernel declares SEG and lds_m as constants that nothing reads).
 //
 // The real-space walk, the fold, the self and background terms and the stores are the same text for both.  FACTORED: the
 // workgroup table and the item's segments come from the tables behind hdr->pad[0], the guard also refuses a system whose M
 // the launch has no LDS for, and the walk over k takes cos theta and sin theta from the particle's per-axis tables, which are
 // written over the LDS image once every lane is done with it.
+//
+// PART (a constant expression, cavmd_coulomb_batch_kernel.hpp) selects the terms.  kCoulombPartAll: everything, into
+// row->force2 -- the two kernels of cavmd_coulomb_compute, whose device code the `if constexpr` branches below leave what it
+// was.  kCoulombPartShort (never FACTORED): the real-space terms of the pairs that are no exclusion partners and lie inside
+// the cut-off, into row->force2; no Q, no walk over k, no self or background term.  kCoulombPartLong: the erf terms of the
+// exclusion partners, Q, the walk over k, the self and background terms and the {Q, 0} slot, into the array row->pad names.
     extern __shared__ __attribute__((aligned(16))) unsigned char s_coulomb[];
     uint4 blk;
     [[maybe_unused]] unsigned seg_first = 0, seg_count = 0, Mx = 0, My = 0, Mz = 0;
@@ -39,6 +45,12 @@
     const CoulombRow* __restrict__ row = rows + item;
     const unsigned n = row->n, n_k = row->n_k;
     v2d* __restrict__ force2 = row->force2;
+    if constexpr (PART == kCoulombPartLong)
+    {
+        force2 = reinterpret_cast<v2d*>(row->pad);
+        if (!force2)
+            return; // a launch captured before the long arrays were dropped
+    }
     const unsigned r = threadIdx.x / S, s = threadIdx.x % S;
     const unsigned i = first + r;
     const bool owner = (i < n);
@@ -78,10 +90,17 @@
     for (unsigned j = s; j < j_end; j += S)
     {
         const double qj = sq[j];
-        pq = pq + qj;
+        if constexpr (PART != kCoulombPartShort)
+            pq = pq + qj;
         if (j == i)
             continue;
         const bool excluded = (j == slots.x) | (j == slots.y) | (j == slots.z) | (j == slots.w);
+        if constexpr (PART == kCoulombPartShort)
+            if (excluded)
+                continue;
+        if constexpr (PART == kCoulombPartLong)
+            if (!excluded)
+                continue;
         const double dx = min_image(xi - sx[j], Lx, hx);
         const double dy = min_image(yi - sy[j], Ly, hy);
         const double dz = min_image(zi - sz[j], Lz, hz);
@@ -114,7 +133,9 @@
     // reciprocal space: partial s over k = s, s + S, ... (FACTORED: over the segments g = s, s + S, ..., each in k order); the
     // factors q_i and 2 q_i are applied once, to the partial
     double rx = 0.0, ry = 0.0, rz = 0.0, rw = 0.0;
-    const unsigned k_end = owner ? n_k : 0u;
+    unsigned k_end = owner ? n_k : 0u;
+    if constexpr (PART == kCoulombPartShort)
+        k_end = 0u; // no walk over k
     const CoulombK* __restrict__ ktab = hdr->ktab + (size_t)k_base;
     const v2d* __restrict__ structure = hdr->structure + (size_t)k_base;
     if constexpr (FACTORED)
@@ -212,11 +233,14 @@
             rw = rw + kv.a * (AB.x * cs + AB.y * sn);
         }
     }
-    const double qi2 = 2.0 * qi;
-    px = px + qi2 * rx;
-    py = py + qi2 * ry;
-    pz = pz + qi2 * rz;
-    pw = pw + qi * rw;
+    if constexpr (PART != kCoulombPartShort)
+    {
+        const double qi2 = 2.0 * qi;
+        px = px + qi2 * rx;
+        py = py + qi2 * ry;
+        pz = pz + qi2 * rz;
+        pw = pw + qi * rw;
+    }
 
     // P = ((p0 + p1) + p2) + ...: every lane of the group folds the same S values in the same order
     double Px = __shfl(px, 0, S), Py = __shfl(py, 0, S), Pz = __shfl(pz, 0, S), Pw = __shfl(pw, 0, S), Q = __shfl(pq, 0, S);
@@ -232,12 +256,14 @@
     if (!owner || s != 0)
         return;
     // self and background
-    Pw = (Pw - row->self_c * (qi * qi)) - row->bg_c * (qi * Q);
+    if constexpr (PART != kCoulombPartShort)
+        Pw = (Pw - row->self_c * (qi * qi)) - row->bg_c * (qi * Q);
     const v2d Fxy = {Px, Py}, Fzw = {Pz, Pw};
     force2[2 * (size_t)i] = Fxy;
     force2[2 * (size_t)i + 1] = Fzw;
-    if (i == 0)
-    {
-        const v2d Q0 = {Q, 0.0};
-        hdr->structure[(size_t)k_base + n_k] = Q0;
-    }
+    if constexpr (PART != kCoulombPartShort)
+        if (i == 0)
+        {
+            const v2d Q0 = {Q, 0.0};
+            hdr->structure[(size_t)k_base + n_k] = Q0;
+        }

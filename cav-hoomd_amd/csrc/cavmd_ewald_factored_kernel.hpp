@@ -180,6 +180,19 @@ __global__ __launch_bounds__(BLOCK) void ewald_force_factored_kernel(const Coulo
 {
     static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
     constexpr bool FACTORED = true;
+    constexpr unsigned PART = kCoulombPartAll;
+#include "cavmd_coulomb_force_body.inc"
+}
+
+// the LONG part under the factored method (coulomb_long_kernel is the direct one), after ewald_structure_factored_kernel
+template <int BLOCK, int S, int SEG>
+__global__ __launch_bounds__(BLOCK) void ewald_long_factored_kernel(const CoulombRow* __restrict__ rows,
+                                                                    const CoulombHeader* __restrict__ hdr, unsigned lds_n,
+                                                                    unsigned lds_m)
+{
+    static_assert(S >= 1 && S <= kWave && (S & (S - 1)) == 0 && BLOCK % S == 0, "S lanes of one wave share a particle");
+    constexpr bool FACTORED = true;
+    constexpr unsigned PART = kCoulombPartLong;
 #include "cavmd_coulomb_force_body.inc"
 }
 } // namespace cavmd

@@ -13,6 +13,7 @@
 
 #include "cavmd.h"
 #include "cavmd_verlet_batch_kernel.hpp"
+#include "cavmd_mts_verlet_kick_kernel.hpp"
 #include "cavmd_draw_kernel.hpp"
 #include "cavmd_bath_kernel.hpp"
 #include "cavmd_thermalize_kernel.hpp"
@@ -287,6 +288,15 @@ int cavmd_verlet_step_two(cavmd_verlet* v, void* stream_, const cavmd_verlet_inp
     if (!v || !d_inputs || ((uintptr_t)d_inputs & 7))
         return CAVMD_ERR_INVALID_VALUE;
     return v->launch_step(stream_, verlet_step_two_kernel<256, false>, d_inputs);
+}
+
+int cavmd_mts_verlet_kick(cavmd_verlet* v, void* stream_, const cavmd_verlet_input* d_inputs, const cavmd_double4* const* d_forces,
+                      double weight)
+{
+    if (!v || !d_inputs || ((uintptr_t)d_inputs & 7) || !d_forces || ((uintptr_t)d_forces & 7) || !isfinite(weight))
+        return CAVMD_ERR_INVALID_VALUE;
+    return v->launch((hipStream_t)stream_, verlet_kick_kernel<256>, dim3((unsigned)v->n), dim3(256), 0, v->d_rows.ptr, v->d_order.ptr,
+                     reinterpret_cast<const VerletInput*>(d_inputs), reinterpret_cast<const v2d* const*>(d_forces), weight);
 }
 
 int cavmd_verlet_read(cavmd_verlet* v, void* stream_, cavmd_verlet_state* out)

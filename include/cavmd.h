@@ -794,6 +794,20 @@ CAVMD_API int cavmd_verlet_set_items(cavmd_verlet* v, size_t first, size_t count
 CAVMD_API int cavmd_verlet_accelerations(cavmd_verlet* v, void* stream);
 CAVMD_API int cavmd_verlet_step_one(cavmd_verlet* v, void* stream, const cavmd_verlet_input* d_inputs);
 CAVMD_API int cavmd_verlet_step_two(cavmd_verlet* v, void* stream, const cavmd_verlet_input* d_inputs);
+/* A kick with a force that is none of the items' d_force arrays: what the impulse multiple-time-step scheme (Verlet-I /
+ * r-RESPA) needs around n plain steps -- the LONG part of a split Coulomb batch, weight n / 2 before and after them.  Enqueues
+ * exactly ONE kernel of n_items 256-thread workgroups, tiles as in step two; may be captured.  d_forces: a DEVICE array of
+ * n_items DEVICE pointers (N entries each, 16-byte aligned), owned by the caller; the pointers, the input rows and the items'
+ * rows are all read when the kernel RUNS.  For an item with skip == 0, N > 0 and a non-NULL force pointer, per particle and
+ * component, every operation one rounding, no FMA:
+ *     h = weight * dt;   minv = 1.0 / m;   v_c = v_c + (f_c * minv) * h
+ * and NOTHING else is written: vel.w, d_accel, d_net_force, the state and its `steps` keep their bytes.  A skipped item, an
+ * item with N == 0 and an item whose pointer is NULL are left untouched.  CAVMD_ERR_INVALID_VALUE for a null handle, a null
+ * or not 8-byte aligned d_inputs or d_forces, and a weight that is not finite.  The scheme is defined for a dt that is the
+ * same through an outer step (the fixed mode of cavmd_draw); under the adaptive rule it is unsupported, and an end time of the
+ * run clock that falls inside an outer step leaves that item with an unmatched opening kick: nothing is built for either. */
+CAVMD_API int cavmd_mts_verlet_kick(cavmd_verlet* v, void* stream, const cavmd_verlet_input* d_inputs,
+                                const cavmd_double4* const* d_forces, double weight);
 /* Synchronises `stream`, then out = the n_items states.  CAVMD_ERR_INVALID_VALUE while `stream` is being captured. */
 CAVMD_API int cavmd_verlet_read(cavmd_verlet* v, void* stream, cavmd_verlet_state* out);
 /* Zero the states of all items (ordered on `stream`). */
@@ -1483,6 +1497,44 @@ CAVMD_API int cavmd_ewald_order(int* tile, int* segment, int* max_m, int* rows, 
 CAVMD_API int cavmd_ewald_set_reciprocal(cavmd_coulomb* c, int method);
 /* The method of the batch.  CAVMD_ERR_INVALID_VALUE for a null handle or a null output. */
 CAVMD_API int cavmd_ewald_get_reciprocal(const cavmd_coulomb* c, int* method);
+
+/* ---- the two parts of the Ewald sum: a short and a long force array, each evaluated on its own (opt-in) ------------------------ */
+/* The reference treats electrostatics as two forces: `short, long = make_pppm_coulomb_forces(...)` (examples/05_advanced_run.py:601),
+ * HOOMD's pair.Ewald over the bond-excluding list and HOOMD's PPPM force, and its energy file has a column for each
+ * (ewald_short_energy, ewald_long_energy).  A batch that has been given LONG arrays evaluates the sum of the Ewald section in
+ * the same two groups.  Every expression is that section's; only the grouping of the terms is new:
+ *   SHORT  into the item's d_force: for every j != i that is NOT an exclusion partner and has rsq < r_cut^2 (strict) the
+ *          real-space term.  Partial s walks j = s, s + S, ... and the partials fold left to right (S and ROWS of
+ *          cavmd_coulomb_order, whichever reciprocal method is selected).  .w is that sum: no self and no background term.
+ *   LONG   into the item's long array: the erf term of the at most four exclusion partners (no cut-off) in the same j
+ *          partition, Q accumulated over all j on the way; then the walk over k by the batch's reciprocal method (direct, or
+ *          factored in segment order) into r;  p = p + (2 q_i) r (.w: p + q_i r), and the same fold.  Lane 0 adds the self and
+ *          background terms to .w, and the owner of particle 0 stores {Q, 0} behind the structure factors, as the combined
+ *          evaluation does.
+ * SHORT + LONG is the Ewald sum.  It is NOT bit-comparable with cavmd_coulomb_compute, whose partials hold both groups before
+ * the fold; each part is held to its own derived bound (tests/coulomb_parts_mirror.py) and the sum to the sum of the two.  With
+ * k_cut = 0 and no exclusions the x, y, z of SHORT compare equal to cavmd_coulomb_compute's.  No atomics, no FMA contraction,
+ * no workgroup that waits for another: the same input gives the same bits on every launch and every graph replay. */
+#define CAVMD_COULOMB_PART_SHORT 1u
+#define CAVMD_COULOMB_PART_LONG  2u
+/* Gives every item its LONG array: a HOST array of n_items DEVICE pointers (N entries each, 16-byte aligned; NULL only for an
+ * item with N == 0), or all NULL to drop the split again.  Synchronises the stream of the last launch first.
+ * CAVMD_ERR_INVALID_VALUE, and nothing is changed, for a null argument, n_items that is not the batch's, a misaligned pointer, a
+ * pointer equal to the item's d_force, a NULL among non-NULL pointers for an item with N > 0, and while that stream is being
+ * captured.  The pointer lives in a word of the item's device row that cavmd_coulomb_compute's kernels never read, so launches
+ * captured before the call follow it (a captured LONG launch that finds NULL writes nothing).  cavmd_coulomb_set_items keeps
+ * every item's long pointer; on a split batch it refuses a new item whose d_force is that pointer, and one with N > 0 where the
+ * pointer is NULL. */
+CAVMD_API int cavmd_mts_coulomb_set_long_forces(cavmd_coulomb* c, size_t n_items, cavmd_double4* const* h_long_force);
+/* Enqueues the kernels of `parts` on `stream`: CAVMD_COULOMB_PART_SHORT is ONE kernel and writes the items' d_force;
+ * CAVMD_COULOMB_PART_LONG is TWO (the structure factors of the selected reciprocal method, then the long kernel) and writes the
+ * long arrays; both together are three.  No allocation, no copy, no host wait; may be captured.  EVERY entry of an array a part
+ * owns is written by every evaluation of that part, and nothing of the other part's array.  CAVMD_ERR_INVALID_VALUE for a null
+ * handle, any other value of `parts`, and for a batch without long arrays.  What cavmd_coulomb_set_items says about launches
+ * captured before it holds for these: NaN in all four components of the rows a workgroup owns for a system beyond the captured
+ * LDS, in the array of the part, never an out-of-bounds access.  cavmd_coulomb_compute is not changed by a split: it writes
+ * the combined sum into d_force and never touches a long array. */
+CAVMD_API int cavmd_mts_coulomb_compute_parts(cavmd_coulomb* c, void* stream, unsigned parts);
 
 /* ---- trajectory frames of a batch: positions, velocities and images recorded on the device in ONE launch --------------------- */
 /* What the driver's hoomd.write.GSD (examples/05_advanced_run.py:1231-1246) saves every --gsd-output-period-ps, with the initial
