@@ -12,6 +12,7 @@ from .forces import CavityForce
 from .compute import CavityForceComputeHIP
 from .history import EnergyHistory
 from .batch import BatchEnergyHistory, CavityForceBatch
+from .shared_cavity import SharedCavityForceBatch
 from .thermostat_batch import BussiReservoirBatch
 from .recorder import BatchRecorder
 from .field_recorder import BatchFieldRecorder
@@ -26,10 +27,10 @@ from .run_clock import run_until_finished
 from .molecular_batch import MolecularForceBatch
 from .coulomb_batch import CoulombForceBatch
 from .state import BoxDim, ParticleData, SystemDefinition
-from . import _capi, bath_batch, checkpoint, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, run_clock, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats, trajectory
+from . import _capi, bath_batch, checkpoint, coulomb_batch, field_recorder, integrator_batch, ledger, molecular_batch, observables, recorder, replicas, run_clock, shared_cavity, step_draw, synthetic, thermalize_batch, thermostat_batch, thermostats, trajectory
 
 __all__ = [
-    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "BatchTrajectoryRecorder", "BatchCheckpoint", "run_until_finished", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
-    "SystemDefinition", "bath_batch", "checkpoint", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "run_clock", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats", "trajectory",
+    "CavityForce", "CavityForceComputeHIP", "CavityForceBatch", "SharedCavityForceBatch", "BatchEnergyHistory", "BussiReservoirBatch", "BatchRecorder", "BatchFieldRecorder", "VerletBatch", "StepDraw", "LangevinBathBatch", "BatchThermalizer", "BatchEnergyLedger", "BatchTrajectoryRecorder", "BatchCheckpoint", "run_until_finished", "MolecularForceBatch", "CoulombForceBatch", "EnergyHistory", "PhysicalConstants", "unwrap_positions", "BoxDim", "ParticleData",
+    "SystemDefinition", "bath_batch", "checkpoint", "coulomb_batch", "field_recorder", "integrator_batch", "ledger", "molecular_batch", "observables", "recorder", "replicas", "run_clock", "shared_cavity", "step_draw", "synthetic", "thermalize_batch", "thermostat_batch", "thermostats", "trajectory",
 ]
 __version__ = "0.1.0"

@@ -77,6 +77,14 @@ class BatchItem(ctypes.Structure):
                 ("params", Params), ("N", ctypes.c_uint32), ("L_typeid", ctypes.c_int32), ("reserved", ctypes.c_uint64 * 4)]
 
 
+class SharedCavityItem(ctypes.Structure):
+    """cavmd_shared_cavity_item (128 bytes): cavmd_batch_item with the cavity's id in its first reserved word."""
+    _fields_ = [("d_pos", ctypes.c_void_p), ("d_charge", ctypes.c_void_p), ("d_image", ctypes.c_void_p),
+                ("d_force", ctypes.c_void_p), ("Lx", ctypes.c_double), ("Ly", ctypes.c_double), ("Lz", ctypes.c_double),
+                ("params", Params), ("N", ctypes.c_uint32), ("L_typeid", ctypes.c_int32), ("cavity", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 3)]
+
+
 class BussiBatchItem(ctypes.Structure):
     """cavmd_bussi_batch_item (64 bytes): one system of a thermostat batch; d_vel / d_members are DEVICE pointers."""
     _fields_ = [("d_vel", ctypes.c_void_p), ("d_members", ctypes.c_void_p), ("n_members", ctypes.c_uint32),
@@ -294,6 +302,15 @@ def batch_item(N, pos_ptr, charge_ptr, image_ptr, force_ptr, box_L, L_typeid, pa
     return it
 
 
+def shared_cavity_item(N, pos_ptr, charge_ptr, image_ptr, force_ptr, box_L, L_typeid, params, cavity) -> "SharedCavityItem":
+    it = SharedCavityItem()
+    it.d_pos, it.d_charge, it.d_image, it.d_force = pos_ptr or None, charge_ptr or None, image_ptr or None, force_ptr or None
+    it.Lx, it.Ly, it.Lz = float(box_L[0]), float(box_L[1]), float(box_L[2])
+    it.params = params
+    it.N, it.L_typeid, it.cavity = int(N), int(L_typeid), int(cavity)
+    return it
+
+
 def bussi_batch_item(vel_ptr, members_ptr, n_members, dof_translational) -> "BussiBatchItem":
     it = BussiBatchItem()
     it.d_vel, it.d_members = vel_ptr or None, members_ptr or None
@@ -469,6 +486,18 @@ _PROTOTYPES = {
     "cavmd_batch_results_at": (_ci, [_vp, _u64, _P(Result)]),
     "cavmd_batch_energies_at": (_ci, [_vp, _u64, _vp]),
     "cavmd_batch_results_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_shared_cavity_item_check": (_ci, [_P(SharedCavityItem)]),
+    "cavmd_shared_cavity_table_check": (_ci, [_sz, _P(SharedCavityItem), _P(_u32)]),
+    "cavmd_shared_cavity_create": (_ci, [_vp, _sz, _P(SharedCavityItem), _P(_vp)]),
+    "cavmd_shared_cavity_destroy": (_ci, [_vp]),
+    "cavmd_shared_cavity_set_items": (_ci, [_vp, _sz, _sz, _P(SharedCavityItem)]),
+    "cavmd_shared_cavity_compute": (_ci, [_vp, _vp]),
+    "cavmd_shared_cavity_last_sequence": (_ci, [_vp, _P(_u64)]),
+    "cavmd_shared_cavity_results_read": (_ci, [_vp, _vp, _P(Result)]),
+    "cavmd_shared_cavity_results_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_shared_cavity_cell_dipoles_device_ptr": (_ci, [_vp, _P(_vp)]),
+    "cavmd_shared_cavity_count": (_ci, [_vp, _P(_u32)]),
+    "cavmd_shared_cavity_carrier": (_ci, [_vp, _u32, _P(_u32)]),
     "cavmd_set_wavevectors": (_ci, [_vp, _sz, _vp]),
     "cavmd_density_field": (_ci, [_vp, _vp, _sz, _vp, _sz]),
     "cavmd_density_field_read": (_ci, [_vp, _vp]),
@@ -957,8 +986,8 @@ class Workspace:
 
 
 class _ItemTableHandle:
-    """What the twelve batch objects share (Batch, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Thermalize, Ledger, Draw,
-    Molecular, Coulomb and Trajectory): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
+    """What the thirteen batch objects share (Batch, SharedCavity, BussiBatch, Recorder, FieldRecorder, Verlet, Bath, Thermalize,
+    Ledger, Draw, Molecular, Coulomb and Trajectory): a handle created from a workspace (kept alive here) over a table of items, released outside stream captures
     only.  A subclass names its item structure, its ``cavmd_*`` prefix and the size the library sorts its launch order by.
     Nothing here relies on ``__init__`` having run."""
     _ITEM = None    # the ctypes structure of one item
@@ -1191,6 +1220,63 @@ class Batch(_ItemTableHandle):
         p = ctypes.c_void_p()
         check(self._lib.cavmd_batch_results_device_ptr(self._h, ctypes.byref(p)), "cavmd_batch_results_device_ptr")
         return int(p.value)
+
+
+SHARED_CAVITY_MAX_MEMBERS = 1024
+shared_cavity_item_check = _item_check("cavmd_shared_cavity", "shared_cavity")
+
+
+def shared_cavity_table_check(items):
+    """(status, n_cavities) cavmd_shared_cavity_create would give this table (host arithmetic only: needs no device);
+    n_cavities is None for a table that is refused."""
+    items = list(items)
+    n = ctypes.c_uint32()
+    st = int(load().cavmd_shared_cavity_table_check(len(items), (SharedCavityItem * max(len(items), 1))(*items), ctypes.byref(n)))
+    return st, (int(n.value) if st == CAVMD_OK else None)
+
+
+class SharedCavity(_ItemTableHandle):
+    """Owns one cavmd_shared_cavity: the items of a batch grouped into cavities, each cavity's photon coupled to the summed
+    dipole of its members; TWO kernel launches per evaluation, one workgroup per item in each.  Launched by N descending."""
+    _ITEM, _PREFIX = SharedCavityItem, "cavmd_shared_cavity"
+    _size = staticmethod(lambda it: int(it.N))
+
+    def __init__(self, workspace: Workspace, items):
+        self._create(workspace, items)
+
+    def compute(self, stream: int = 0) -> None:
+        check(self._lib.cavmd_shared_cavity_compute(self._h, ctypes.c_void_p(stream)), "cavmd_shared_cavity_compute")
+
+    def last_sequence(self) -> int:
+        out = ctypes.c_uint64()
+        self._call("last_sequence", ctypes.byref(out))
+        return int(out.value)
+
+    def results(self, stream: int = 0):
+        """The n_items result blocks of the last evaluation (a ctypes array of Result), after a wait for ``stream``."""
+        out = (Result * self.n_items)()
+        self._call("results_read", ctypes.c_void_p(stream), out)
+        return out
+
+    def results_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        self._call("results_device_ptr", ctypes.byref(p))
+        return int(p.value)
+
+    def cell_dipoles_device_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        self._call("cell_dipoles_device_ptr", ctypes.byref(p))
+        return int(p.value)
+
+    def count(self) -> int:
+        n = ctypes.c_uint32()
+        self._call("count", ctypes.byref(n))
+        return int(n.value)
+
+    def carrier(self, cavity: int) -> int:
+        item = ctypes.c_uint32()
+        self._call("carrier", int(cavity), ctypes.byref(item))
+        return int(item.value)
 
 
 def bussi_batch_input_make(deltaT, set_T, tau, normal_variate, gamma_variate) -> BussiBatchInput:

@@ -1,5 +1,5 @@
-// Host-only: what the twelve "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip,
-// cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder, the ledger, which has its shape, and the trajectory),
+// Host-only: what the thirteen "batch of small systems" objects share.  They live in seven units: cavmd_batch.hip (the batch
+// and the shared cavity), cavmd_bussi_batch.hip, cavmd_recorder.hip (the recorder, the ledger, which has its shape, and the trajectory),
 // cavmd_field_recorder.hip, cavmd_verlet.hip (the integrator, the draw object that writes its input rows, the bath that
 // supplies its second half-step and the thermalize object that starts a run), cavmd_molecular.hip and cavmd_coulomb.hip.
 // ItemTable is how a table of items lives on the host and on the device; create_table makes an object and ties it to its
@@ -7,7 +7,7 @@
 // SeriesTable, a ring of records per item (the two recorders, the ledger and the trajectory); StateTable, one state per
 // item (the integrator, the draw object, the bath, the thermalize object and the thermostat batch); LinkedTable, tables derived
 // from the items that the kernels find through a header at a fixed device address and that set_items replaces together (the
-// two force batches).  What a SeriesTable or a StateTable holds on the device can be saved to a host blob and loaded back
+// two force batches and the shared cavity).  What a SeriesTable or a StateTable holds on the device can be saved to a host blob and loaded back
 // (snapshot_bytes / snapshot_save / snapshot_load below, on the arithmetic of cavmd_snapshot.hpp).
 // Those units see cavmd_workspace as an incomplete type: what they need of one is its WorkspaceTie.
 #pragma once

@@ -326,6 +326,106 @@ CAVMD_API int cavmd_batch_energies_at(cavmd_batch* b, uint64_t sequence, double*
 /* Device address of the n_items result blocks (indexed by item), for consumers that stay on the GPU. */
 CAVMD_API int cavmd_batch_results_device_ptr(cavmd_batch* b, const cavmd_result** out);
 
+/* ---- several systems of a batch coupled to ONE shared cavity mode, in TWO launches ---------------------------------------- */
+/* Collective coupling: one photon coordinate feels the summed dipole of many molecular cells.  The cells are the items of a
+ * batch, each with its own box, and the cavity term is the only force that crosses their boundaries.  The reference has no such
+ * mode; its formulas (src/CavityForceCompute.cc:166-207) carry over with `dipole` replaced by the sum over the cavity's cells,
+ * and a cavity of one cell is the evaluation of cavmd_batch_compute for that item, bit for bit (forces and every field of
+ * cavmd_result but sequence and n_partials).
+ *
+ * A cavity is a set of 1 to CAVMD_SHARED_CAVITY_MAX_MEMBERS items of the object.  Exactly one of them, the carrier, names a
+ * photon type (L_typeid >= 0).  The photon is the carrier's first particle of that type, found on the device as
+ * cavmd_batch_compute finds it.  Every other member passes L_typeid = -1.
+ * With r unwrapped by each member's own box, d_c = sum_i q_i r_i of member c, and D = sum_c d_c:
+ *   - The photon is excluded as in the reference.  Further L-typed particles of the carrier are treated as for a single system
+ *     (added back to the dipole, zero force).
+ *   - E_h = 1/2 K q.q, E_c = g (D_xy . q_xy), E_d = 1/2 (g^2/K) D_xy.D_xy.
+ *   - Dq = q_xy + (g/K) D_xy.
+ *   - Every non-L particle of every member gets ((-g) q_i) Dq in x and y, with z = 0 and w = 0.
+ *   - The photon gets -K q - g D_xy.
+ *   - The operator association is the one of a single system (the library evaluates both with the same function).
+ *   - If the carrier has no particle of the named type, every force of every member of that cavity is zero and its energies
+ *     are zero.  Other cavities are unaffected.
+ *   - Members with N == 0 are legal and contribute nothing.
+ *
+ * Summation order (results are reproducible).  Launch 1 leaves, per member, the un-normalised double-double block total
+ * produced by the per-lane order of cavmd_batch_compute: particles base + j*256 + tid, four in flight, then the fixed tree over
+ * the 256 threads.  Launch 2 folds the totals of a cavity in ascending item index:
+ *   1. Thread t merges members t, t+256, t+512, t+768, in that order, into an identity accumulator.
+ *   2. The fixed tree over the 256 threads.
+ *   3. The renormalisation hi = fl(hi + lo).
+ * The L-typed sums, the photon's index, the count of L-typed particles and the photon row come from the carrier's record alone.
+ * Every member's workgroup performs the same fold, so all of them hold identical bits of Dq.  Inside a launch no workgroup
+ * waits for another one (no flags, no atomics): the kernel boundary on the stream orders launch 1 before launch 2, hence no
+ * starvation and no CAVMD_ERR_SYNC_TIMEOUT on this path.
+ *
+ * One cavmd_result per item on the device; the recorder, the ledger and the thermalize object take them as they take the
+ * batch's (d_result, n_particles == N, photon_idx local to the item):
+ *   field                      carrier                                      other member
+ *   dipole, dipole_lo          the cavity's D                               its own cell's d_c
+ *   total_dipole               D, the L-typed sum joined before rounding    its own cell's d_c
+ *   q, Dq                      the cavity's                                 copies of the cavity's
+ *   energy, photon_force       the cavity's                                 zero
+ *   photon_idx                 local index                                  -1
+ *   n_photon_typed             as counted                                   0
+ *   n_particles                its N                                        its N
+ *   n_partials                 the number of members                        1
+ * Summing energy over a cavity's members therefore gives the cavity's.  No member is conserved on its own. */
+#define CAVMD_SHARED_CAVITY_MAX_MEMBERS 1024
+typedef struct cavmd_shared_cavity_item
+{
+    const cavmd_double4* d_pos; /* as cavmd_batch_item: all DEVICE pointers, same alignments (16/8/4/16) */
+    const double* d_charge;
+    const cavmd_int3* d_image;
+    cavmd_double4* d_force;     /* all N entries are written by every evaluation */
+    double Lx, Ly, Lz;
+    cavmd_params params;        /* 32 B; bitwise equal in every member of a cavity */
+    uint32_t N;                 /* 0 is legal */
+    int32_t L_typeid;           /* >= 0: the carrier of its cavity; -1: another member */
+    uint32_t cavity;            /* 0 .. n_cavities - 1 */
+    uint32_t reserved0;         /* must be 0 */
+    uint64_t reserved[3];       /* must be 0 */
+} cavmd_shared_cavity_item;     /* 128 B = 32 + 24 + 32 + 8 + 8 + 24 */
+typedef struct cavmd_shared_cavity cavmd_shared_cavity; /* opaque; belongs to the workspace it was created from */
+
+/* The per-row rules of cavmd_batch_item_check (same statuses); host arithmetic only. */
+CAVMD_API int cavmd_shared_cavity_item_check(const cavmd_shared_cavity_item* item);
+/* Every row, then the rules that cross rows; host arithmetic only, needs no device.  Cavity ids are dense in
+ * 0 .. n_cavities - 1 and every cavity has exactly one carrier, else CAVMD_ERR_INVALID_VALUE; `params` are bitwise equal within
+ * a cavity, else CAVMD_ERR_BAD_PARAMS; at most CAVMD_SHARED_CAVITY_MAX_MEMBERS members per cavity, else CAVMD_ERR_CAPACITY.
+ * n_items 1 .. CAVMD_BATCH_MAX_ITEMS.  *n_cavities (may be NULL) is written for a table that passes. */
+CAVMD_API int cavmd_shared_cavity_table_check(size_t n_items, const cavmd_shared_cavity_item* h_items, uint32_t* n_cavities);
+/* Validates the table as cavmd_shared_cavity_table_check does, copies it and the member lists derived from it to the device of
+ * `ws` and allocates, per item, one cavmd_result, one 128-byte record and four doubles of cell dipole. */
+CAVMD_API int cavmd_shared_cavity_create(cavmd_workspace* ws, size_t n_items, const cavmd_shared_cavity_item* h_items,
+                                         cavmd_shared_cavity** out);
+/* Synchronises the stream of the last evaluation (unless that stream is being captured), then frees. */
+CAVMD_API int cavmd_shared_cavity_destroy(cavmd_shared_cavity* c);
+/* Rewrites rows first .. first + count - 1 from HOST memory after synchronising the stream of the last evaluation.  The whole
+ * table is validated after substitution and nothing is changed if it is refused; membership may change (the member lists are
+ * replaced together with the rows, behind a header at a fixed device address, so a graph captured before follows the new
+ * table).  CAVMD_ERR_INVALID_VALUE while that stream is being captured, and for a range outside the table. */
+CAVMD_API int cavmd_shared_cavity_set_items(cavmd_shared_cavity* c, size_t first, size_t count,
+                                            const cavmd_shared_cavity_item* h_items);
+/* Enqueues exactly TWO kernels of n_items workgroups each on `stream`: no allocation, no copy, no host wait; may be captured
+ * into a hipGraph.  Workgroups start in order of N descending (ties in item order); results stay indexed by item.  The object
+ * counts its own evaluations (the first one is 1): every item's cavmd_result.sequence carries that number (a replay carries the
+ * number of its capture). */
+CAVMD_API int cavmd_shared_cavity_compute(cavmd_shared_cavity* c, void* stream);
+/* Sequence number of the last evaluation enqueued (0 before any).  No wait. */
+CAVMD_API int cavmd_shared_cavity_last_sequence(cavmd_shared_cavity* c, uint64_t* out);
+/* Synchronises `stream`, then copies the n_items device blocks to `out`.  CAVMD_ERR_INVALID_VALUE while `stream` is being
+ * captured, CAVMD_ERR_NOT_COMPUTED before any evaluation. */
+CAVMD_API int cavmd_shared_cavity_results_read(cavmd_shared_cavity* c, void* stream, cavmd_result* out);
+/* Device address of the n_items result blocks (indexed by item), for consumers that stay on the GPU. */
+CAVMD_API int cavmd_shared_cavity_results_device_ptr(cavmd_shared_cavity* c, const cavmd_result** out);
+/* Device address of the cell dipoles: n_items x 4 doubles (d_c in x, y, z, then 0), each rounded once from its double-double
+ * sum; written by launch 1 of every evaluation, also where the cavity has no photon. */
+CAVMD_API int cavmd_shared_cavity_cell_dipoles_device_ptr(cavmd_shared_cavity* c, const double** out);
+/* The number of cavities of the table, and the item index of a cavity's carrier. */
+CAVMD_API int cavmd_shared_cavity_count(cavmd_shared_cavity* c, uint32_t* n_cavities);
+CAVMD_API int cavmd_shared_cavity_carrier(cavmd_shared_cavity* c, uint32_t cavity, uint32_t* item);
+
 /* ---- observables next to the force path ------------------------------------------- */
 /* Wavevectors for the density field: n_k rows of (kx, ky, kz) in HOST memory; copied into the workspace once.
  * The reference builds them as kmag * generate_fibonacci_sphere(50) (src/cavitymd/analysis.py:296-306). */
@@ -1779,8 +1879,8 @@ CAVMD_API int cavmd_profile_samples(cavmd_workspace* ws, double* out, size_t cap
  * pointer of an item is of the new process), seeds given per item (cavmd_bath_item, cavmd_thermalize_item), periods,
  * intervals, kB, wavevectors and every other parameter of create, and the run clock's end times and rules (cavmd_runclock_*).
  * The draw object's seed is in the header, so a blob of
- * another seed is refused.  cavmd_batch, cavmd_molecular and cavmd_coulomb keep nothing between launches that a later launch
- * reads, so they have no snapshot.  Result-history sequence numbers and cavmd_record.eval_sequence restart in a new process
+ * another seed is refused.  cavmd_batch, cavmd_shared_cavity, cavmd_molecular and cavmd_coulomb keep nothing between launches
+ * that a later evaluation reads, so they have no snapshot. Result-history sequence numbers and cavmd_record.eval_sequence restart in a new process
  * (they are diagnostic).  Host-side generators that made input rows are the caller's.  The arrays the items point to
  * (positions, images, velocities, accelerations, input rows) are the caller's memory: save and restore them next to the blobs;
  * the accelerations cannot be recomputed after a step with a bath, they contain its random force. */
